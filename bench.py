@@ -20,10 +20,16 @@ iteration one more carries the advantage sums of all 16 minibatches.
   --rendezvous-only   ranks meet over gloo, exchange a communicator id and exit (CPU test of the spawn + id exchange)
   --minibatches 1     north_star's "single all-reduce per update epoch" (one optimiser step per epoch, ppo.jl:5)
   --strict-profiles   exit 2 (instead of reporting traffic = null) when the committed PMC summaries were taken with other kernel sources
+  --dump-outputs DIR  after the timed steps, the state the last timed iteration left (parameters, Adam state, a fixed seeded sample of the rollout
+                      buffers, episode statistics) as DIR/<name>.npy: the same arguments give the same inputs, so two builds compare output for output
+  --full              everything below besides the headline (off by default)
 
-The default N = 1 run repeats the commanded timed region (exactly K iterations between barrier + synchronize pairs) FIVE times on one handle: `value` / `ms_per_step` are the
-median region, `ms_per_step_runs` lists all five; `clock` carries the shader clock the box sustains under vector load (crl_clock_probe) before and after. Side records on the same line:
-`strict_f32` (24-bit operands), `with_stats_readback`, `configs` = BASELINE configs[1] (c2), [2] (c3), one shard of [3] (shard_8192) — each with its own strict_f32 twin — and [4] (a2c, dqn).
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times exactly K iterations between barrier + synchronize pairs, and prints the line:
+`value` = env-steps/s of that region, `ms_per_step` = its time ÷ K. With --full the N = 1 run repeats the timed region FIVE times on one handle: `value` /
+`ms_per_step` are the median region, `ms_per_step_runs` lists all five; `clock` carries the shader clock the box sustains under vector load (crl_clock_probe)
+before and after. Side records of --full on the same line: `roofline_gae` (the standalone scan, cold / warm / past the Infinity Cache), `strict_f32` (24-bit
+operands), `with_stats_readback`, `configs` = BASELINE configs[1] (c2), [2] (c3), one shard of [3] (shard_8192) — each with its own strict_f32 twin — and
+[4] (a2c, dqn), and `cpu_baseline`.
 
 The `roofline` record of the headline prices the dominant kernel (update_x2_kernel, ≈80 % of the iteration) against what PMC shows
 it bound by: vector-instruction ISSUE. achieved = vector-ALU instructions per launch (SQ_INSTS_VALU of the committed PMC pass,
@@ -61,7 +67,7 @@ PROFILE_TAG = "r06"                   # profiles/<tag>_* hold the rocprofv3 summ
 DTYPE = ("f32 (64x64 products as fp16x2 split operands — hi + lo in f16, >= 22 significant bits — 3 f16 MFMAs per product, f32 accumulate; measured against a "
          "Float64 product on the headline's own operands this is as close as a plain f32 FMA chain: profiles/r06_product_error.json)")
 DTYPE_C3 = "f32 (256x256 products as fp16x2 split operands: hi + lo in f16, 3 f16 MFMAs per product, f32 accumulate)"
-TIMED_REGIONS = 5                     # the default N = 1 run repeats the commanded timed region this many times on one handle: value = median
+TIMED_REGIONS = 5                     # the --full N = 1 run repeats the commanded timed region this many times on one handle: value = median
 
 
 def log(*a):
@@ -416,8 +422,31 @@ def gae_beyond_cache(crl, sizes=(262144, 524288), reps=8):
                     f"{reps} launches; frac = algorithmic bytes ÷ time ÷ 8 TB/s; over_copy = copy time ÷ scan time"}
 
 
+DUMP_SAMPLE = 1 << 19                 # --dump-outputs: rollout entries kept per buffer (of num_envs x num_steps), the same seeded indices every run
+
+
+def dump_outputs(h, L, ep, out_dir):
+    """--dump-outputs: what crl_ppo_iterate leaves its caller after the last timed iteration, as <out_dir>/<name>.npy (float32, or float64
+    where the library keeps float64): the whole parameter vector and Adam state; the rollout buffers of that iteration (action, logprob,
+    value, reward, terminal, advantage, return) at DUMP_SAMPLE fixed, seeded positions of the flattened (num_envs, num_steps) array, their
+    positions in sample_index; and the episode statistics of the run (episodes, return sum, length sum, return max). About 19 MB at the headline size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = h.nt * h.k
+    idx = np.sort(np.random.default_rng(20260).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    arrays = {"params": h.read(L.F_PARAMS), "adam_m": h.read(L.F_ADAM_M), "adam_v": h.read(L.F_ADAM_V)}
+    for name, f in (("action", L.F_ACTION), ("logprob", L.F_LOGPROB), ("value", L.F_VALUE), ("reward", L.F_REWARD),
+                    ("terminal", L.F_TERMINAL), ("advantage", L.F_ADVANTAGE), ("return", L.F_RETURN)):
+        arrays[name] = h.read(f).ravel(order="F")[idx]
+    arrays["sample_index"] = idx.astype(np.float64)
+    arrays["episode_stats"] = np.array([ep["episodes"], ep["return_sum"], ep["length_sum"], ep["return_max"]], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+    log(f"bench.py: --dump-outputs: {len(arrays)} arrays ({sum(a.size for a in arrays.values())} values) in {out_dir}")
+
+
 def run_workload(args, wl, world, rank, local_rank, dist, torch, crl, crl_dist, total_envs=None, steps=None, warmup=None, with_gae=True,
-                 extra_opts=None, readback=False, regions=1):
+                 extra_opts=None, readback=False, regions=1, dump_dir=None):
     """One timed run: W warm-up iterations, then exactly K iterations between barriers. Returns (record or None on ranks > 0)."""
     L = crl._lib
     spec = WORKLOADS[wl]
@@ -497,6 +526,8 @@ def run_workload(args, wl, world, rank, local_rank, dist, torch, crl, crl_dist, 
     n_timed = steps * len(dts)
     prof = h.prof_read()
     ep = h.episode_stats()
+    if dump_dir and rank == 0:
+        dump_outputs(h, L, ep, dump_dir)   # before the read-back iteration below: the state the last TIMED iteration left
     stats = h.iterate(1)  # one extra, untimed, to read the loss records back
     reruns = h.exact_reruns
     options = h.options()
@@ -711,7 +742,14 @@ def main():
     ap.add_argument("--total-envs", type=int, default=0, help="override the workload's env count (0 = the workload's own)")
     ap.add_argument("--minibatches", type=int, default=4, help="num_minibatches (ppo.jl:5); 1 = one optimiser step and one gradient all-reduce per epoch")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of --steps iterations each (value = the median region); 0 = 5 for the default N = 1 headline run, 1 otherwise")
+    ap.add_argument("--regions", type=int, default=0, help="timed regions of --steps iterations each (value = the median region); 0 = 5 for the N = 1 headline run "
+                                                            "under --full, 1 otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: shader-clock probes, five timed regions, the standalone GAE rooflines, strict_f32, "
+                         "with_stats_readback, configs (C2, C3, shard_8192, A2C, DQN) and cpu_baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed iteration left the caller (parameters, optimiser state, a fixed "
+                         "seeded sample of the rollout buffers, episode statistics) as DIR/<name>.npy")
     ap.add_argument("--no-extras", action="store_true", help="skip the strict_f32 / with_stats_readback sub-runs of the headline line (A/B scripts)")
     ap.add_argument("--kernel-breakdown", action="store_true",
                     help="time every kernel class with recorded HIP events (kernel_ms_per_step gets all entries; the events cost "
@@ -779,9 +817,11 @@ def main():
 
     import cleanrl_jl_amd as crl
     torch.cuda.set_device(local_rank)
-    plain_n1 = world == 1 and args.workload == "cartpole" and not args.total_envs and not args.no_extras and not args.kernel_breakdown
-    clocks = [clock_record(crl, local_rank, "before the timed regions")] if (rank == 0 and world == 1) else []
-    out = run_workload(args, args.workload, world, rank, local_rank, dist, torch, crl, crl_dist, regions=args.regions or (TIMED_REGIONS if plain_n1 else 1))
+    # a plain run times the headline and nothing else; the side records below are --full's
+    plain_n1 = args.full and world == 1 and args.workload == "cartpole" and not args.total_envs and not args.no_extras and not args.kernel_breakdown
+    clocks = [clock_record(crl, local_rank, "before the timed regions")] if (args.full and rank == 0 and world == 1) else []
+    out = run_workload(args, args.workload, world, rank, local_rank, dist, torch, crl, crl_dist, with_gae=args.full, dump_dir=args.dump_outputs,
+                       regions=args.regions or (TIMED_REGIONS if plain_n1 else 1))
     if rank == 0:
         if clocks:
             clocks.append(clock_record(crl, local_rank, "after the timed regions"))
@@ -844,7 +884,7 @@ def main():
                             "computes between all-reduces); c3's roofline is the f16 matrix pipe's issued TFLOP/s over the optimiser step's launches, the "
                             "others the update kernel's vector-instruction issue rate like the headline")
             out["configs"] = cfgs
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cartpole":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cartpole":
             out["cpu_baseline"] = cpu_baseline()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
