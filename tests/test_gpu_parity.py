@@ -289,6 +289,59 @@ def test_full_iteration_matches_oracle(crl, n_iters, fuse_optim, gemm):
     agent.close(); st.close()
 
 
+@pytest.mark.parametrize("route", ["fused,gemm=2", "fused,gemm=1", "wide"])
+@pytest.mark.parametrize("nt", [4, 1, 3, 5, 7])
+def test_reference_default_config_whole_iterations_match_oracle(crl, nt, route, monkeypatch):
+    """The reference's own default call, PPOConfig() (ppo.jl:1-19: 4 envs x 32 steps, 4 minibatches, 4 epochs, 500,000 steps for the
+    annealing schedule), and the same with 1, 3, 5 and 7 envs — minibatches of 8 x num_envs samples, below any tile of the kernels —
+    for three whole iterations of crl_ppo_iterate against orc_iterate (serial Fisher–Yates): actions and permutation bit-equal,
+    advantages at 1e-5, all 16 loss records at IT_LOSS, parameters at IT_PARAM. On the fused CartPole kernels (gemm 2 and the bf16x3
+    flavour 1) and on the layer-wise path (CRL_FORCE_WIDE=1)."""
+    if route == "wide":
+        monkeypatch.setenv("CRL_FORCE_WIDE", "1")
+    cfg = crl.PPOConfig(num_envs=nt)
+    assert (cfg.num_steps, cfg.num_minibatches, cfg.update_epochs) == (32, 4, 4)
+    agent = crl.Agent(cfg, shuffle_mode=0, options={"gemm": int(route[-1])} if route != "wide" else None)
+    params = agent.get_params()
+    cfgo, st = _oracle_state(nt, cfg.num_steps, params)
+    _three_iterations(crl, agent, st, cfg.total_timesteps // (nt * cfg.num_steps))
+
+
+def test_reference_default_config_on_a_2x256_network_matches_oracle(crl, monkeypatch):
+    """PPOConfig() with obs 8 / act 4 / 2x256 on the synthetic env: M = 32, exactly one register-stationary tile, but M % 128 != 0 routes
+    every minibatch to the layer-wise kernels. Same three iterations and bars as above."""
+    from test_gpu_wide import spread_params
+    monkeypatch.setenv("CRL_FORCE_WIDE", "1")
+    cfg = crl.PPOConfig()
+    D, A, Hd = 8, 4, 256
+    cfgo = O.make_config(num_envs=cfg.num_envs, num_steps=cfg.num_steps, obs_dim=D, n_act=A, hidden=Hd, env_kind=1)
+    params = spread_params(cfgo, 7)
+    off = O.param_offsets(cfgo)
+    params[off[4]:off[5]] /= 10
+    agent = crl.Agent(cfg, params=params, shuffle_mode=0, obs_dim=D, n_act=A, hidden=Hd, env_kind=crl._lib.ENV_SYNTHETIC)
+    st = O.State(cfgo); st.params[:] = params; st.env_init()
+    _three_iterations(crl, agent, st, cfg.total_timesteps // (cfg.num_envs * cfg.num_steps))
+
+
+def _three_iterations(crl, agent, st, num_updates):
+    h = agent.handle; F = crl._lib
+    h.env_reset()
+    for it in range(3):
+        gs = h.iterate(1)
+        os_ = st.iterate(num_updates, gen_perm=True)
+        assert np.array_equal(h.read(F.F_PERM), st.perm)
+        acts = h.read(F.F_ACTION)
+        assert np.array_equal(acts, st.action), f"iteration {it}: {np.sum(acts != st.action)} actions differ"
+        assert rel_err(h.read(F.F_ADVANTAGE), st.adv) < RTOL
+        assert len(gs) == len(os_) == 16
+        for a, b in zip(gs, os_):
+            for key in ("loss", "pg_loss", "v_loss", "entropy_loss"):
+                assert loss_close(key, a[key], b[key], IT_LOSS), (it, key, a[key], b[key])
+        pg, po = h.read(F.F_PARAMS), st.params
+        assert np.max(np.abs(pg - po)) < IT_PARAM, (it, np.max(np.abs(pg - po)))
+    agent.close(); st.close()
+
+
 def test_fused_and_two_launch_optimiser_steps_agree_at_c2_size(crl):
     """reduce_optim_kernel (one launch, grid-wide meeting point) against reduce_kernel + clipnorm_adam_kernel on 4096 envs x 128 steps,
     two whole iterations = 32 optimiser steps: the gradients are the same bits, the per-array norms differ at most in the order their

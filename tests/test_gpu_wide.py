@@ -136,11 +136,14 @@ def test_wide_update_gradient_matches_oracle(crl, D, A, Hd, nt, k, ret_scale, cl
     agent.close(); st.close()
 
 
-@pytest.mark.parametrize("opts", [
+FLAVOURS_2X256 = [
     {"wide_fuse": 0}, {"wide_fuse": 1}, {"wide_fuse": 2}, {"wide_fuse": 3},
     {"wide_fuse": 3, "wide_fuse_pc": 0}, {"wide_fuse": 2, "wide_fuse_pc": 0}, {"wide_fuse": 3, "wide_wgrad_full": 0},
     {"wide_fuse": 3, "shuffle_overlap": 0}, {"wide_fuse": 3, "wide_fwd_wbufs": 3, "wide_rs": 0}, {"wide_fuse": 3, "wide_fwd_wbufs": 0, "wide_rs": 0},
-    {"wide_fuse": 3, "wide_d2_split": 0}, {"wide_fuse": 3, "wide_rs": 0}, {"wide_fuse": 3, "wide_rs": 1}, {"wide_fuse": 3, "wide_rs": 8}, {"wide_fuse": 3, "wide_rs": 9}, {"wide_fuse": 3, "wide_rs": 11}, {"wide_fuse": 3, "wide_rs": 27}], ids=lambda o: ",".join(f"{a}={b}" for a, b in o.items()))
+    {"wide_fuse": 3, "wide_d2_split": 0}, {"wide_fuse": 3, "wide_rs": 0}, {"wide_fuse": 3, "wide_rs": 1}, {"wide_fuse": 3, "wide_rs": 8}, {"wide_fuse": 3, "wide_rs": 9}, {"wide_fuse": 3, "wide_rs": 11}, {"wide_fuse": 3, "wide_rs": 27}]
+
+
+@pytest.mark.parametrize("opts", FLAVOURS_2X256, ids=lambda o: ",".join(f"{a}={b}" for a, b in o.items()))
 @pytest.mark.parametrize("D,A,nt", [(8, 4, 24), (16, 8, 16), (3, 2, 12)])
 def test_every_2x256_kernel_flavour_matches_the_oracle(crl, opts, D, A, nt):
     """The 2x256 shape has four selectable pipelines (option wide_fuse: 0 layer-wise GEMMs, 1 tile-resident forward, 2 + tile-
@@ -149,8 +152,21 @@ def test_every_2x256_kernel_flavour_matches_the_oracle(crl, opts, D, A, nt):
     forward and backward of wide_fuse = 3 are the register-stationary wide_rs_fwd_kernel / wide_rs_bwd_kernel — option wide_rs bits 0 and 3,
     obs_dim a multiple of 4 — and wide_rs = 0 keeps round 5's kernels and their flavours alive).  Every one of them must give the oracle's loss scalars and gradient on the same
     buffers — the default is only the fastest of equals.  Shapes: C3's, the largest the fused kernels take (obs 16, 8
-    actions) and an odd small one (obs 3, 2 actions)."""
-    k, Hd = 128, 256
+    actions) and an odd small one (obs 3, 2 actions). num_steps 128: minibatches of a whole number of 128-sample tiles, which the fused and
+    register-stationary kernels take."""
+    _flavour_case(crl, opts, D, A, nt, 128)
+
+
+@pytest.mark.parametrize("opts", FLAVOURS_2X256, ids=lambda o: ",".join(f"{a}={b}" for a, b in o.items()))
+@pytest.mark.parametrize("D,A,nt", [(8, 4, 24), (16, 8, 16), (3, 2, 12)])
+def test_every_2x256_kernel_flavour_matches_the_oracle_on_a_576_sample_minibatch(crl, opts, D, A, nt):
+    """The same flavours and shapes with num_steps = 2304 / num_envs: M = 576, a multiple of 32 samples but not of 128, so every flavour
+    hands the minibatch back from the fused and register-stationary kernels to the layer-wise ones."""
+    _flavour_case(crl, opts, D, A, nt, 2304 // nt)
+
+
+def _flavour_case(crl, opts, D, A, nt, k):
+    Hd = 256
     rng = np.random.default_rng(nt + D)
     cfg = ocfg(nt, k, D, A, Hd)
     params = O.orthogonal_params(cfg, 5) + (0.05 * rng.standard_normal(O.lib().orc_param_count(cfg))).astype(np.float32)
@@ -162,7 +178,7 @@ def test_every_2x256_kernel_flavour_matches_the_oracle(crl, opts, D, A, nt):
     inject(crl, agent, st, rng, D, A, 3.0)
     h.adv_stats()
     M = nt * k // 4
-    assert M % 128 == 0
+    assert M == 576 if k != 128 else M % 128 == 0
     off = O.param_offsets(cfg)
     for mb in (0, 3):
         gs = h.update_minibatch(mb, 2.5e-4, apply_update=False)
@@ -334,12 +350,13 @@ def test_2x256_rollout_flavours_match_the_oracle(crl, rs, env, D, A, nt, k):
     agent.close(); st.close()
 
 
-@pytest.mark.parametrize("persist", [2, 1, 0, {"wide_rs_actor_pct": 60}, {"wide_rs": 11}, {"wide_rs": 0}], ids=str)
+@pytest.mark.parametrize("persist", [2, 1, 0, {"wide_rs_actor_pct": 60}, {"wide_rs": 11}, {"wide_rs": 0}, {"wide_gemm": 1}, {"wide_tanh_rational": 1}], ids=str)
 def test_c3_shaped_iteration_at_1024_envs_matches_oracle(crl, persist):
     """(wide_rollout_persist = 2: the rollout as one launch — since round 6 the register-stationary wide_rs_rollout_kernel, with wide_rs = 0 round 5's
     producer / consumer wide_rollout_pc_kernel; 1: one launch, wide_rollout_persist_kernel; 0: three launches per step. The dict cases: the
     register-stationary backward with the CUs split 60 : 40 between the actor's and the critic's blocks — 128 tiles per network here, the smallest
-    launch that takes the uneven split —, with the dW3 sweeps still launched, and round 5's kernels throughout.)
+    launch that takes the uneven split —, with the dW3 sweeps still launched, round 5's kernels throughout, the bf16x3 flavour (wide_gemm = 1:
+    bench.py's C3 `strict_f32` record) and tanh_fast in every layer (wide_tanh_rational = 1: no fused kernel at all).)
     BASELINE configs[2]'s shape (obs 8 / act 4 / 2x256, synthetic env) at num_envs = 1024 — 32 tiles per launch, so the multi-tile
     paths of the layer-wise kernels run (chunked weight gradients, several blocks per GEMM) — for one whole iteration against the
     oracle at the north_star bar: actions and permutation bit-equal, advantages / losses within 1e-5 relative, parameters within 1e-5
