@@ -1102,12 +1102,23 @@ int32_t crl_ppo_get_option(crl_ppo* h, const char* key, int64_t* value) {
   CRL_GUARD(h);
   if (!value) { set_error("crl_ppo_get_option: null argument"); return 1; }
   if (key && std::strcmp(key, "gemm_fallback_seen") == 0) {
-    // read-only: 1 once a launch has run a role as bf16x3 because a hidden-layer weight left the fp16x2 window (|w| >= 255)
+    // read-only: 1 once a launch has run a role as bf16x3 because a hidden-layer weight left the fp16x2 window (|w| >= 255, or all |w| < 2^-11)
     double re = 0.0;
     if (h->wide) { *value = 0; return 0; }   // the layer-wise path scales its fp16x2 weight pieces per step: it has no fallback to take
     CRL_HIP_CHECK(hipMemcpyAsync(&re, h->vfix + 5, sizeof(re), hipMemcpyDeviceToHost, h->stream));
     CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
     *value = re != 0.0 ? 1 : 0;
+    return 0;
+  }
+  const bool dw_a = key && std::strcmp(key, "dw_scale_log2_actor") == 0, dw_c = key && std::strcmp(key, "dw_scale_log2_critic") == 0;
+  if (dw_a || dw_c) {
+    // read-only: the exponent of the weight-gradient scale G the next fp16x2 launch of that role will use (mlp_x2.hpp; a power of two).
+    // gemm = 1 launches neither read nor move it: the value waits for the next fp16x2 launch. The layer-wise path has no carried G.
+    if (h->wide) { set_error(std::string("crl_ppo_get_option: ") + key + " has no meaning on the layer-wise path (it carries no weight-gradient scale)"); return 1; }
+    float g = 0.0f;
+    CRL_HIP_CHECK(hipMemcpyAsync(&g, h->dscale + (dw_c ? 1 : 0), sizeof(g), hipMemcpyDeviceToHost, h->stream));
+    CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+    *value = std::ilogb(g);
     return 0;
   }
   const int id = opt_find(key);

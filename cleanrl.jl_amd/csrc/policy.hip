@@ -182,7 +182,7 @@ __device__ __forceinline__ void gae_tail_compat(const RolloutArgs& a, int e) {
 
 // CX2: the critic runs as fp16x2 with the exp2-based activation (mlp_x2.hpp) — its output is a value compared at 1e-5, while
 // the actor keeps bf16x3 + the reference's rational tanh_fast because its output decides action indices that are bit-compared.
-// A critic whose hidden-layer weights leave the fp16 window (|w| >= 255) is restaged and run as bf16x3 by the same launch.
+// A critic whose hidden-layer weights leave the fp16 window (|w| >= 255, or all |w| < 2^-11) is restaged and run as bf16x3 by the same launch.
 template <int A, bool CX2>
 __global__ void __launch_bounds__(512, 2) rollout_cartpole_kernel(RolloutArgs a) {
   constexpr int D = 4;
@@ -430,7 +430,7 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
   float* hd = reinterpret_cast<float*>(pcs + 2 * 2 * 3 * 64);              // [A][64] wave 0's partial head sums
   int* flag = reinterpret_cast<int*>(hd + A * 64);
   stage_net_x3<D, A, false>(imgA0, a.params, threadIdx.x, blockDim.x);
-  bool cx2 = true;   // block-uniform: false = the critic's weights left the fp16 window (|w| >= 255) and it runs as bf16x3
+  bool cx2 = true;   // block-uniform: false = the critic's weights left the fp16 window (|w| >= 255, or all |w| < 2^-11) and it runs as bf16x3
   if (!stage_net_x2<D, 1, false>(imgC0, a.params + NetParams<D, A>::SIZE, threadIdx.x, blockDim.x, flag)) {
     if (threadIdx.x == 0 && blockIdx.x == 0) a.range_err[0] = 1.0;   // informational: the fallback ran
     cx2 = false;

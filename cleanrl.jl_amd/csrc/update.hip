@@ -110,7 +110,7 @@ constexpr int SCR_FLOATS_X3 = SCR_FLOATS + ACC_SLOTS * 64;
 // X2 (with X3): the forward and backward-data products run as fp16x2 (mlp_x2.hpp: three MFMAs per product instead of six, h1
 // carried as 2^14·h1), the weight-gradient product stays on bf16x3.
 // Returns false — before any work, uniformly for the block — only in the fp16x2 flavour when a hidden-layer weight of this role does
-// not fit the fp16 window (|w| >= 255, mlp_x2.hpp): the caller then runs the bf16x3 flavour of the same role on the same LDS.
+// not fit the fp16 window (|w| >= 255, or all |w| < 2^-11: mlp_x2.hpp): the caller then runs the bf16x3 flavour of the same role on the same LDS.
 //
 // Record prefetch (fp16x2 main pass, `pfslots` != nullptr). A tile starts with two DEPENDENT global round trips — perm[pos], then the
 // random 64-byte record — which a wave with one partner on its SIMD cannot hide (≈2 µs of an ≈8 µs tile parked on vmcnt). So the
@@ -791,7 +791,7 @@ __global__ void __launch_bounds__(512, 2) update_x2_kernel(UpdateArgs a) {
   if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= 4) {
     for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(16);
   }
-  // a role whose hidden-layer weights left the fp16 window (|w| >= 255) runs as bf16x3 for this launch: same operands, no range limit
+  // a role whose hidden-layer weights left the fp16 window (|w| >= 255, or all |w| < 2^-11) runs as bf16x3 for this launch: same operands, no range limit
   float* pfslots = smem + X2_KERNEL_LDS_FLOATS;   // 8 x 1 KB record-prefetch slots behind the larger (bf16x3) layout
 #ifdef CRL_COUNT_PROBE
   if ((int)blockIdx.x < a.nblk[0]) update_role<D, A, 0, false, true, 8, 0, true>(a, blockIdx.x, smem, smem + NetImageX2<D, A>::SIZE, pfslots);

@@ -63,7 +63,7 @@ struct NetImageT16 {
   static constexpr int SIZE = ((B3 + NOUT + 3) / 4) * 4;
 };
 
-// false (for every thread) when a hidden-layer weight does not fit the fp16 window
+// false (for every thread) when a hidden-layer weight does not fit the fp16 window, or all of them sit below X2_W_SMALL (stage_net_x2)
 template <int NOUT>
 __device__ __forceinline__ bool stage_net_t16(float* img, const float* __restrict__ p, int tid, int nthreads, int* lds_flag) {
   using I = NetImageT16<NOUT>;
@@ -72,13 +72,14 @@ __device__ __forceinline__ bool stage_net_t16(float* img, const float* __restric
   _Float16* wb = reinterpret_cast<_Float16*>(img + I::WB2H);
   if (tid == 0) *lds_flag = 0;
   __syncthreads();
-  bool bad = false;
+  bool bad = false, big = false;
   for (int idx = tid; idx < 4096; idx += nthreads) {
     const int slot = idx & 7, lane = (idx >> 3) & 63, s = (idx >> 9) & 1, t = idx >> 10;
     const int m = 16 * t + (lane & 15), k = kmap16(s, slot, lane >> 4);
     {
       const float w0 = p[P::W2 + m + H * k];
       bad |= !(__builtin_fabsf(w0) < X2_W_LIMIT);
+      big |= __builtin_fabsf(w0) >= X2_W_SMALL;
       const float w = w0 * X2_W_SCALE;
       const _Float16 h = (_Float16)w;
       wf[idx] = h; wf[4096 + idx] = (_Float16)(w - (float)h);
@@ -104,9 +105,10 @@ __device__ __forceinline__ bool stage_net_t16(float* img, const float* __restric
     img[I::W3L + idx] = p[P::W3 + a + NOUT * row16(t, i, g)];
   }
   for (int idx = tid; idx < NOUT; idx += nthreads) img[I::B3 + idx] = p[P::B3 + idx];
-  if (bad) *lds_flag = 1;
+  if (bad) atomicOr(lds_flag, 1);
+  if (big) atomicOr(lds_flag, 2);
   __syncthreads();
-  return *lds_flag == 0;
+  return *lds_flag == 2;
 }
 
 __device__ __forceinline__ P2 load_wfrag16(const float* piece0, int t, int s, int lane) {
@@ -217,7 +219,7 @@ __device__ __forceinline__ void update16_role(const UpdateArgs& a, const int rb,
 
   int tile = rb * RW16 + wave;
   if (!in_range) {
-    // a hidden-layer weight outside the fp16 window: this launch contributes nothing and raises the miss flag — update_repair_kernel then
+    // a hidden-layer weight outside the fp16 window (mlp_x2.hpp): this launch contributes nothing and raises the miss flag — update_repair_kernel then
     // recomputes the whole minibatch as bf16x3 (no range limit), exactly as for a tile the carried weight-gradient scale does not fit
     if (tid == 0 && rb == 0) a.range_err[0] = 1.0;   // gemm_fallback_seen
     missed = true;

@@ -238,7 +238,7 @@ int32_t crl_comm_destroy(crl_ppo* h);
  * environment variables). Integer-valued, by name; unknown names and out-of-range values are errors. The defaults are what
  * bench.py measures. crl_ppo_option_count / crl_ppo_option_name enumerate them.
  *   gemm                    2 = 64x64 products as fp16x2 split operands (default); 1 = bf16x3 everywhere — the fallback flavour, which
- *                           a launch also takes by itself, per role, when a hidden-layer weight leaves the fp16 window (|w| >= 255)
+ *                           a launch also takes by itself, per role, when a hidden-layer weight leaves the fp16 window (|w| >= 255, or all of a network's |w| < 2^-11)
  *   rollout_split (4)       small-shard rollout kernel, waves per 32-env tile: 4 = by size (default) — six (the actor's hidden rows over four waves on 16x16x32 products,
  *                           the critic's over two: rollout_split6_kernel) for shards up to rollout_split_max_tiles; 3 = six, 1 = three, 2 = two, 0 = one
  *   rollout_split_max_tiles largest shard, in 32-env tiles, the split kernels take (512)
@@ -297,7 +297,11 @@ int32_t crl_comm_destroy(crl_ppo* h);
  *                           rank-order sum -> ClipNorm + Adam). Taken only where the launch's whole grid can be resident (checked at crl_ppo_create) and never
  *                           with an RCCL communicator, a host-side exchange or the inline value-loss fix-up
  * Read-only through crl_ppo_get_option: gemm_fallback_seen (1 once any launch of the fused 4/2/64 path took the bf16x3 fallback; the
- * layer-wise path needs none: it scales its fp16x2 weight pieces by the largest |w| of the layer at every optimiser step).
+ * layer-wise path needs none: it scales its fp16x2 weight pieces by the largest |w| of the layer at every optimiser step);
+ * dw_scale_log2_actor / dw_scale_log2_critic (log2 of the power-of-two weight-gradient scale G that the next fp16x2 update launch of
+ * that role uses: predicted from the previous launch's largest |δ2|, kept while it fits, clamped to [-100, 100]; see mlp_x2.hpp. Under
+ * gemm = 1 no launch reads or moves it: the value is the one the next fp16x2 launch starts from. An error on a layer-wise handle, which
+ * carries no such scale).
  * The environment variable CRL_OPTIONS="key=value,key=value" applies options at crl_ppo_create (shell-driven experiments). */
 int32_t crl_ppo_set_option(crl_ppo* h, const char* key, int64_t value);
 int32_t crl_ppo_get_option(crl_ppo* h, const char* key, int64_t* value);

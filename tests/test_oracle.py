@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import oraclelib as O
+from oraclelib import torch_loss as _torch_loss
 
 
 def test_philox_known_answer():
@@ -88,56 +89,6 @@ def test_gae_batch_layout_and_returns():
 
 
 # ---- SURVEY §8-KA loss vector -----------------------------------------------------------------------------
-def _torch_loss(params64, cfg, off, states, actions, old_lp, old_v, adv, ret, adv_stats=None):
-    """Independent float64 autograd restatement of ppo.jl:203-243 (formulas of SURVEY §8-LOSS)."""
-    h, d, A = cfg.hidden, cfg.obs_dim, cfg.n_act
-
-    def tanh_fast(x):
-        x2 = x * x
-        n = 1.0 + x2 * (0.1346604 + x2 * (0.0035974074 + x2 * (2.2332108e-5 + x2 * 1.587199e-8)))
-        dd = 1.0 + x2 * (0.4679937 + x2 * (0.026262015 + x2 * (0.0003453992 + x2 * 8.7767893e-7)))
-        return torch.where(x2 < 66.0, x * (n / dd), torch.sign(x))
-
-    def net(base, n_out, x):
-        W1 = params64[off[base]:off[base + 1]].reshape(d, h).T
-        b1 = params64[off[base + 1]:off[base + 2]]
-        W2 = params64[off[base + 2]:off[base + 3]].reshape(h, h).T
-        b2 = params64[off[base + 3]:off[base + 4]]
-        W3 = params64[off[base + 4]:off[base + 5]].reshape(h, n_out).T
-        b3 = params64[off[base + 5]:off[base + 6]]
-        h1 = tanh_fast(W1 @ x + b1[:, None])
-        h2 = tanh_fast(W2 @ h1 + b2[:, None])
-        return W3 @ h2 + b3[:, None]
-
-    x = torch.tensor(states, dtype=torch.float64)
-    z = net(0, A, x)
-    v = net(6, 1, x)[0]
-    lp = torch.log_softmax(z, dim=0)
-    p = torch.softmax(z, dim=0)
-    M = x.shape[1]
-    nlp = lp[torch.tensor(actions, dtype=torch.long), torch.arange(M)]
-    E = -(p * lp)
-    a = torch.tensor(adv, dtype=torch.float64)
-    if adv_stats is None:
-        Ahat = (a - a.mean()) / (a.std(unbiased=True) + 1e-8)
-    else:
-        Ahat = (a - adv_stats[0]) / (adv_stats[1] + 1e-8)
-    ratio = torch.exp(nlp - torch.tensor(old_lp, dtype=torch.float64))
-    eps = float(np.float32(cfg.clip_coef))
-    lo, hi = float(np.float32(1) - np.float32(cfg.clip_coef)), float(np.float32(1) + np.float32(cfg.clip_coef))
-    pg = torch.maximum(-Ahat * ratio, -Ahat * torch.clamp(ratio, lo, hi)).mean()
-    R = torch.tensor(ret, dtype=torch.float64); ov = torch.tensor(old_v, dtype=torch.float64)
-    if cfg.clip_value_loss:
-        u = (v - R ** 2).mean()
-        vc = ov + torch.clamp(v - ov, -eps, eps)
-        vl = 0.5 * torch.maximum(u.expand_as(vc), (vc - R) ** 2).mean()
-    else:
-        vl = 0.5 * ((v - R) ** 2).mean()
-    ent = E.mean()
-    loss = pg - float(np.float32(cfg.ent_coeff)) * ent + float(np.float32(cfg.v_coef)) * vl
-    return loss, pg, vl, ent
-
-
 def test_loss_formulas_known_answer():
     """§8-KA loss vector evaluated directly on the formulas (logits given, no network)."""
     z = torch.tensor([[0, 1, -1, .5], [0, 0, 1, -.5]], dtype=torch.float64)
