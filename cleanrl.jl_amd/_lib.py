@@ -64,6 +64,7 @@ EXPORTS = [
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
+    "crl_env_step",
 ]
 
 DQN_PARAM_COUNT = 10934
@@ -109,7 +110,7 @@ class CrlA2CEpisode(C.Structure):
 F_OBS, F_ACTION, F_LOGPROB, F_REWARD, F_TERMINAL, F_VALUE, F_ADVANTAGE, F_RETURN, F_PERM, F_PARAMS, F_GRADS, F_ADAM_M, \
     F_ADAM_V, F_ENV_STATE, F_CUR_OBS, F_NEXT_DONE, F_ENV_T, F_BETAP, F_ADV_SUMS = range(19)
 GAE_COMPAT, GAE_FIXED = 0, 1
-ENV_CARTPOLE, ENV_SYNTHETIC, ENV_EXTERNAL = 0, 1, 2
+ENV_CARTPOLE, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_MOUNTAINCAR, ENV_ACROBOT = 0, 1, 2, 3, 4
 SHUFFLE_FISHER_YATES, SHUFFLE_BIJECTION, SHUFFLE_BLOCKED_FY = 0, 1, 2
 K_ROLLOUT, K_GAE, K_SHUFFLE, K_ADV_STATS, K_UPDATE, K_REDUCE, K_OPTIM, K_ALLREDUCE, K_PACK, K_PERMUTE = range(10)
 KERNEL_NAMES = ["rollout", "gae", "shuffle", "adv_stats", "update", "reduce", "optim", "allreduce", "pack", "permute"]
@@ -143,6 +144,7 @@ def load():
     L.crl_rollout_store.argtypes = [vp, C.c_int32, fp, ip, fp, fp, u8p, fp]
     L.crl_env_reset.argtypes = [vp]
     L.crl_rollout_run.argtypes = [vp]
+    L.crl_env_step.argtypes = [vp, ip, C.c_uint64, fp, fp, u8p]
     L.crl_episode_stats_read.argtypes = [vp, C.POINTER(CrlEpisodeStats)]
     L.crl_compute_gae.argtypes = [vp]
     L.crl_shuffle.argtypes = [vp, C.c_uint64]
@@ -347,6 +349,16 @@ class Handle:
 
     def rollout_run(self):
         check(load().crl_rollout_run(self._h))
+
+    def env_step(self, action, gstep=0):
+        """crl_env_step: the on-device envs take the caller's 0-based actions (ppo.jl:130-165 without the policy); gstep keys the reset stream like
+        step `gstep` of the training loop. Returns (next_obs (obs_dim, nt), reward, done)."""
+        action = np.ascontiguousarray(action, np.int32)
+        if action.shape != (self.nt,):
+            raise ValueError(f"env_step: {self.nt} actions expected, got shape {action.shape}")
+        obs = np.zeros((self.d, self.nt), np.float32, order="F"); reward = np.zeros(self.nt, np.float32); done = np.zeros(self.nt, np.uint8)
+        check(load().crl_env_step(self._h, _ptr(action, C.c_int32), int(gstep), _ptr(obs, C.c_float), _ptr(reward, C.c_float), _ptr(done, C.c_uint8)))
+        return obs, reward, done
 
     def episode_stats(self):
         st = CrlEpisodeStats()

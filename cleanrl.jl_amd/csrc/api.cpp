@@ -249,7 +249,14 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   if (cfg->env_kind == CRL_ENV_CARTPOLE && (cfg->obs_dim != 4 || cfg->n_act != 2)) {
     set_error("env_kind = CRL_ENV_CARTPOLE needs obs_dim=4, n_act=2 (use CRL_ENV_SYNTHETIC or CRL_ENV_EXTERNAL)"); return 1;
   }
-  if (cfg->env_kind != CRL_ENV_CARTPOLE && cfg->env_kind != CRL_ENV_SYNTHETIC && cfg->env_kind != CRL_ENV_EXTERNAL) {
+  if (cfg->env_kind == CRL_ENV_ACROBOT && (cfg->obs_dim != 6 || cfg->n_act != 3)) {
+    set_error("env_kind = CRL_ENV_ACROBOT needs obs_dim=6, n_act=3"); return 1;
+  }
+  if (cfg->env_kind == CRL_ENV_MOUNTAINCAR && (cfg->obs_dim != 2 || cfg->n_act != 3)) {
+    set_error("env_kind = CRL_ENV_MOUNTAINCAR needs obs_dim=2, n_act=3"); return 1;
+  }
+  if (cfg->env_kind != CRL_ENV_CARTPOLE && cfg->env_kind != CRL_ENV_SYNTHETIC && cfg->env_kind != CRL_ENV_EXTERNAL &&
+      cfg->env_kind != CRL_ENV_MOUNTAINCAR && cfg->env_kind != CRL_ENV_ACROBOT) {
     set_error("unknown env_kind"); return 1;
   }
   if (cfg->env_kind == CRL_ENV_SYNTHETIC && !wide) {
@@ -560,6 +567,41 @@ int32_t crl_rollout_run(crl_ppo* h) {
   return launch_rollout(h);
 }
 
+int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done) {
+  CRL_GUARD_SETTLED(h);
+  const int kind = h->cfg.env_kind;
+  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
+    set_error("crl_env_step needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
+  }
+  if (!action) { set_error("crl_env_step: null action"); return 1; }
+  if (ensure_env(h)) return 1;
+  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D;
+  const size_t o_act = 0, o_rew = o_act + nt * 4, o_bad = o_rew + nt * 4, o_done = o_bad + 16, total = o_done + nt;
+  if (ensure_stage(h, total)) return 1;
+  char* s = static_cast<char*>(h->stage);
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, action, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemsetAsync(s + o_bad, 0, 16, h->stream));
+  if (launch_env_step(h, (const int32_t*)(s + o_act), gstep, (float*)(s + o_rew), (uint8_t*)(s + o_done), (uint32_t*)(s + o_bad))) return 1;
+  uint32_t bad = 0;
+  CRL_HIP_CHECK(hipMemcpyAsync(&bad, s + o_bad, 4, hipMemcpyDeviceToHost, h->stream));
+  if (next_obs) CRL_HIP_CHECK(hipMemcpyAsync(next_obs, h->cur_obs, nt * d * 4, hipMemcpyDeviceToHost, h->stream));
+  if (reward) CRL_HIP_CHECK(hipMemcpyAsync(reward, s + o_rew, nt * 4, hipMemcpyDeviceToHost, h->stream));
+  if (done) CRL_HIP_CHECK(hipMemcpyAsync(done, s + o_done, nt, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  if (bad) { set_error("crl_env_step: an action is outside 0 … n_act - 1 (those envs were not stepped)"); return 1; }
+  return 0;
+}
+
+// CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT: the accumulator holds an order-preserving key of the true maximum (wide.hip: stat_max_key), 0 = no episode
+static double return_max_of(const crl_ppo* h, double raw) {
+  if (h->cfg.env_kind != CRL_ENV_MOUNTAINCAR && h->cfg.env_kind != CRL_ENV_ACROBOT) return raw;
+  uint64_t k; std::memcpy(&k, &raw, 8);
+  if (k == 0) return 0.0;
+  k = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double x; std::memcpy(&x, &k, 8);
+  return x;
+}
+
 int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out) {
   CRL_GUARD(h);
   if (!out) { set_error("null argument"); return 1; }
@@ -567,7 +609,7 @@ int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out) {
   double v[4];
   CRL_HIP_CHECK(hipMemcpyAsync(v, h->ep_stats, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  out->episodes = v[0]; out->return_sum = v[1]; out->length_sum = v[2]; out->return_max = v[3];
+  out->episodes = v[0]; out->return_sum = v[1]; out->length_sum = v[2]; out->return_max = return_max_of(h, v[3]);
   return 0;
 }
 
@@ -974,7 +1016,7 @@ static int deliver_status(crl_ppo* h, int64_t k, crl_ppo_iteration_report* rep, 
     double ep[4];
     std::memcpy(ep, p + ST_OFF_EP, 32);
     rep->iteration = k;
-    rep->episodes.episodes = ep[0]; rep->episodes.return_sum = ep[1]; rep->episodes.length_sum = ep[2]; rep->episodes.return_max = ep[3];
+    rep->episodes.episodes = ep[0]; rep->episodes.return_sum = ep[1]; rep->episodes.length_sum = ep[2]; rep->episodes.return_max = return_max_of(h, ep[3]);
     rep->n_episodes = h->ep_ring_cap > 0 ? (int64_t)ring_cnt : (int64_t)ep[0];
     uint32_t n = h->ep_ring_cap > 0 ? (ring_cnt < (uint32_t)h->ep_ring_cap ? ring_cnt : (uint32_t)h->ep_ring_cap) : 0u;
     if (n > (uint32_t)(max_ring > 0 ? max_ring : 0)) n = (uint32_t)(max_ring > 0 ? max_ring : 0);

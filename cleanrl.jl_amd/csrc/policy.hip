@@ -125,6 +125,48 @@ __global__ void env_reset_kernel(DevCfg c, float* __restrict__ env_state, int32_
   env_t[e] = 0; next_done[e] = 0; ep_return[e] = 0.0f; ep_length[e] = 0;
 }
 
+// the same for the stateful envs of the layer-wise path (CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT): env_state holds obs_dim floats per env, the
+// env's state words first
+__global__ void env_reset_kind_kernel(DevCfg c, float* __restrict__ env_state, int32_t* __restrict__ env_t,
+                                      float* __restrict__ cur_obs, uint8_t* __restrict__ next_done,
+                                      float* __restrict__ ep_return, int32_t* __restrict__ ep_length, double* ep_stats) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e == 0) { ep_stats[0] = ep_stats[1] = ep_stats[2] = ep_stats[3] = 0.0; }
+  if (e >= c.nt) return;
+  float s[4], o[ENV_OBS_MAX];
+  env_reset(c.env_kind, s, c.seed, c.env_id_offset + (uint32_t)e, 0, 2);
+  env_observe(c.env_kind, s, o);
+  const int ns = env_state_dim(c.env_kind);
+#pragma unroll
+  for (int i = 0; i < ENV_OBS_MAX; ++i)
+    if (i < c.D) { env_state[(size_t)c.D * e + i] = i < ns ? s[i] : 0.0f; cur_obs[(size_t)c.D * e + i] = o[i]; }
+  env_t[e] = 0; next_done[e] = 0; ep_return[e] = 0.0f; ep_length[e] = 0;
+}
+
+// crl_env_step: env(action), reward, is_terminated, state, reset!(env) of the terminated (ppo.jl:130-132,143-144,164) for caller-chosen actions.
+// One thread per env; an action outside 0 … n_act - 1 raises *bad and leaves the env alone.
+__global__ void __launch_bounds__(256) env_step_kernel(DevCfg c, const int32_t* __restrict__ action, uint64_t gstep, float* __restrict__ env_state,
+                                                       int32_t* __restrict__ env_t, float* __restrict__ cur_obs, uint8_t* __restrict__ next_done,
+                                                       float* __restrict__ reward, uint8_t* __restrict__ done_out, uint32_t* bad) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= c.nt) return;
+  const int act = action[e];
+  if (act < 0 || act >= c.A) { atomicOr(bad, 1u); return; }
+  const int ns = env_state_dim(c.env_kind);
+  float* es = env_state + (size_t)c.D * e;
+  float* co = cur_obs + (size_t)c.D * e;
+  float s[4], so[ENV_OBS_MAX];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s[i] = i < ns ? es[i] : 0.0f;
+  int t_env = env_t[e];
+  bool done; float rew;
+  env_transition(c.env_kind, c.stale_obs, s, t_env, act, c.seed, c.env_id_offset + (uint32_t)e, gstep, so, rew, done);
+#pragma unroll
+  for (int i = 0; i < ENV_OBS_MAX; ++i) if (i < c.D) { co[i] = so[i]; es[i] = i < ns ? s[i] : 0.0f; }
+  env_t[e] = t_env; next_done[e] = done ? 1 : 0;
+  reward[e] = rew; done_out[e] = done ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // The rollout loop — ppo.jl:123-166 — one launch for all num_steps.
 // ------------------------------------------------------------------------------------------------------
@@ -1031,9 +1073,22 @@ int launch_next_value(crl_ppo* h) {
 
 int launch_env_reset(crl_ppo* h) {
   if (h->cfg.env_kind == CRL_ENV_SYNTHETIC) return wide_env_reset(h);
+  if (h->cfg.env_kind == CRL_ENV_MOUNTAINCAR || h->cfg.env_kind == CRL_ENV_ACROBOT) {
+    hipLaunchKernelGGL(env_reset_kind_kernel, dim3((h->dc.nt + 255) / 256), dim3(256), 0, h->stream, h->dc, h->env_state, h->env_t,
+                       h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->ep_stats);
+    CRL_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   if (h->cfg.env_kind != CRL_ENV_CARTPOLE) { set_error("crl_env_reset: envs are stepped by the caller (CRL_ENV_EXTERNAL)"); return 1; }
   hipLaunchKernelGGL(env_reset_kernel, dim3((h->dc.nt + 255) / 256), dim3(256), 0, h->stream, h->dc, h->env_state, h->env_t,
                      h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->ep_stats);
+  CRL_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_env_step(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* reward_d, uint8_t* done_d, uint32_t* bad_d) {
+  hipLaunchKernelGGL(env_step_kernel, dim3((h->dc.nt + 255) / 256), dim3(256), 0, h->stream, h->dc, action_d, gstep, h->env_state, h->env_t,
+                     h->cur_obs, h->next_done, reward_d, done_d, bad_d);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -242,6 +242,7 @@ int launch_policy_act(crl_ppo* h, const float* obs_d, const double* u_d, int n, 
                       float* value_d);
 int launch_logprob_actions(crl_ppo* h, const float* obs_d, const int32_t* act_d, int n, float* logprob_d, float* ent_d);
 int launch_env_reset(crl_ppo* h);
+int launch_env_step(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* reward_d, uint8_t* done_d, uint32_t* bad_d);
 int launch_rollout(crl_ppo* h, bool fuse_gae = false);
 bool rollout_can_fuse_gae(const crl_ppo* h);
 int launch_next_value(crl_ppo* h);

@@ -1738,6 +1738,17 @@ struct WStepArgs {
   uint64_t iteration; int step;
 };
 
+// A lane's running return_max. CartPole / synthetic keep max(0, ·) (their accumulator is ordered as an unsigned bit pattern, which holds for values >= 0);
+// kinds whose returns can be negative (env_signed_returns) keep the true maximum of the lane's finished episodes: st_n says whether there was one yet.
+__device__ __forceinline__ double step_stat_max(int kind, double st_n, double st_max, double ep_ret) {
+  if (!env_signed_returns(kind)) return fmax(st_max, fmax(0.0, ep_ret));
+  return st_n > 1.0 ? fmax(st_max, ep_ret) : ep_ret;
+}
+// order-preserving map of a double onto u64 (never 0 for a number: 0 = "no episode yet", which is what the accumulator is cleared to)
+__device__ __host__ __forceinline__ unsigned long long stat_max_key(double x) {
+  unsigned long long b; __builtin_memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 // one env, one step; the episode statistics of a finished episode are added to the caller's running sums. zreg: the env's logits when the caller holds them
 // in registers (else they come from a.Z); xout: receives the env's next observation (16 floats, zero beyond obs_dim) besides cur_obs; a.V may be null (the
 // caller fills the value buffer later: wide_rs_rollout_kernel)
@@ -1764,22 +1775,19 @@ __device__ __forceinline__ void wide_step_env(const WStepArgs& a, int e, int ste
   for (int i = 0; i < D; ++i) ob[i] = co[i];                        // ppo.jl:133-140 Buffer.add!
   a.action[b] = act; a.logprob[b] = lpa; a.terminal[b] = a.next_done[e]; if (a.V) a.value[b] = a.V[e];
   bool done; float rew;
-  if (c.env_kind == CRL_ENV_CARTPOLE) {
-    float s[4] = {es[0], es[1], es[2], es[3]};
+  if (env_stateful(c.env_kind)) {
+    const int ns = env_state_dim(c.env_kind);
+    float s[4], so[ENV_OBS_MAX];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = i < ns ? es[i] : 0.0f;
     int t_env = a.env_t[e];
-    done = cartpole_step(s, t_env, act);                             // ppo.jl:130
-    rew = done ? 0.0f : 1.0f;                                        // ppo.jl:132
-    float so[4] = {s[0], s[1], s[2], s[3]};                          // ppo.jl:143: the observation is taken before the reset (Q7)
-    if (done) {
-      cartpole_reset(s, c.seed, gid, gstep, 1);                      // ppo.jl:164
-      t_env = 0;
-      if (!c.stale_obs) for (int i = 0; i < 4; ++i) so[i] = s[i];
-    }
-    for (int i = 0; i < 4; ++i) { co[i] = so[i]; es[i] = s[i]; }
+    env_transition(c.env_kind, c.stale_obs, s, t_env, act, c.seed, gid, gstep, so, rew, done);   // ppo.jl:130-132,143,164
+#pragma unroll
+    for (int i = 0; i < ENV_OBS_MAX; ++i) if (i < D) { co[i] = so[i]; es[i] = i < ns ? s[i] : 0.0f; }
     a.env_t[e] = t_env;
     if (xout) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) xout[i] = i < 4 ? so[i] : 0.0f;
+      for (int i = 0; i < 16; ++i) xout[i] = (i < ENV_OBS_MAX && i < D) ? so[i] : 0.0f;
     }
   } else {
     if (xout) {
@@ -1805,7 +1813,7 @@ __device__ __forceinline__ void wide_step_env(const WStepArgs& a, int e, int ste
   a.next_done[e] = done ? 1 : 0;                                     // ppo.jl:144
   float ep_ret = a.ep_return[e] + rew;                               // ppo.jl:145
   if (done) {                                                        // ppo.jl:147-165
-    st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, fmax(0.0, (double)ep_ret));
+    st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = step_stat_max(c.env_kind, st_n, st_max, (double)ep_ret);
     if (a.ring_cap > 0) {
       const uint32_t slot = atomicAdd(a.ring_count, 1u);
       if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
@@ -1815,7 +1823,10 @@ __device__ __forceinline__ void wide_step_env(const WStepArgs& a, int e, int ste
   a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
 }
 // a wave's episode statistics into the handle's four accumulators
-__device__ __forceinline__ void wide_step_stats(double* ep_stats, double st_n, double st_ret, double st_len, double st_max) {
+// (signed: the env kind's returns can be negative — lanes without a finished episode stand aside, and the accumulator holds stat_max_key of the maximum,
+// which the host maps back: api.cpp return_max_of)
+__device__ __forceinline__ void wide_step_stats(double* ep_stats, double st_n, double st_ret, double st_len, double st_max, bool is_signed = false) {
+  if (is_signed && !(st_n > 0.0)) st_max = -__builtin_inf();
   st_n = wave_sum(st_n);
   if (st_n > 0.0) {
     st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
@@ -1823,7 +1834,7 @@ __device__ __forceinline__ void wide_step_stats(double* ep_stats, double st_n, d
     for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
     if ((threadIdx.x & 63) == 0) {
       atomicAdd(&ep_stats[0], st_n); atomicAdd(&ep_stats[1], st_ret); atomicAdd(&ep_stats[2], st_len);
-      atomicMax(reinterpret_cast<unsigned long long*>(&ep_stats[3]), (unsigned long long)__double_as_longlong(st_max));
+      atomicMax(reinterpret_cast<unsigned long long*>(&ep_stats[3]), is_signed ? stat_max_key(st_max) : (unsigned long long)__double_as_longlong(st_max));
     }
   }
 }
@@ -1832,7 +1843,7 @@ __global__ void __launch_bounds__(256) wide_step_kernel(WStepArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
   if (e < a.c.nt) wide_step_env(a, e, a.step, st_n, st_ret, st_len, st_max);
-  wide_step_stats(a.ep_stats, st_n, st_ret, st_len, st_max);
+  wide_step_stats(a.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(a.c.env_kind));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1888,7 +1899,7 @@ __global__ void __launch_bounds__(512, 4) wide_rollout_persist_kernel(WRollArgs 
     if (tid < 32 && e < nt) wide_step_env(r.s, e, step, st_n, st_ret, st_len, st_max);
     __syncthreads();
   }
-  if (tid < 64) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max);
+  if (tid < 64) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2144,7 +2155,7 @@ __global__ void __launch_bounds__(512) wide_rollout_pc_kernel(RollPCArgs r) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
-    if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max);
+    if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
   }
 }
 

@@ -854,18 +854,11 @@ __device__ __forceinline__ void rs_step_env(const WStepArgs& a, int e, int step,
   a.action[b] = act; a.logprob[b] = lpa; a.terminal[b] = (uint8_t)nd;
   bool done; float rew;
   f32x4 es = s1; int t_env = __float_as_int(s0[3]);
-  if (c.env_kind == CRL_ENV_CARTPOLE) {
-    float s[4] = {s1[0], s1[1], s1[2], s1[3]};
-    done = cartpole_step(s, t_env, act);                             // ppo.jl:130
-    rew = done ? 0.0f : 1.0f;                                        // ppo.jl:132
-    float so[4] = {s[0], s[1], s[2], s[3]};                          // ppo.jl:143: the observation is taken before the reset (Q7)
-    if (done) {
-      cartpole_reset(s, c.seed, gid, gstep, 1);                      // ppo.jl:164
-      t_env = 0;
-      if (!c.stale_obs) for (int i = 0; i < 4; ++i) so[i] = s[i];
-    }
+  if (env_stateful(c.env_kind)) {
+    float s[4] = {s1[0], s1[1], s1[2], s1[3]}, so[ENV_OBS_MAX];
+    env_transition(c.env_kind, c.stale_obs, s, t_env, act, c.seed, gid, gstep, so, rew, done);   // ppo.jl:130-132,143,164
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { x[0][i] = so[i]; es[i] = s[i]; }
+    for (int i = 0; i < 4; ++i) { x[0][i] = so[i]; x[1][i] = so[4 + i]; es[i] = s[i]; }
   } else {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -880,7 +873,7 @@ __device__ __forceinline__ void rs_step_env(const WStepArgs& a, int e, int step,
   a.reward[b] = rew;
   float ep_ret = s0[1] + rew;                                        // ppo.jl:145
   if (done) {                                                        // ppo.jl:147-165
-    st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, fmax(0.0, (double)ep_ret));
+    st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = step_stat_max(c.env_kind, st_n, st_max, (double)ep_ret);
     if (a.ring_cap > 0) {
       const uint32_t slot = atomicAdd(a.ring_count, 1u);
       if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
@@ -1047,16 +1040,16 @@ __global__ void __launch_bounds__(512) wide_rs_rollout_kernel(RsRollArgs r) {
     __builtin_amdgcn_s_barrier();                                       // B4: the next observations are in LDS
     if (st_) RS_STAMP(9);
   }
-  if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max);
+  if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
   if (tid < RR_MB) {                                                    // the envs' state back to global memory for the next launch
     const int e = m0 + tid;
     const float* q = stl + tid * 8;
     r.s.next_done[e] = (uint8_t)__float_as_int(q[0]); r.s.ep_return[e] = q[1]; r.s.ep_length[e] = __float_as_int(q[2]); r.s.env_t[e] = __float_as_int(q[3]);
-    const bool cart = r.s.c.env_kind == CRL_ENV_CARTPOLE;
+    const bool cart = env_stateful(r.s.c.env_kind);
     for (int i = 0; i < Dst; ++i) {
       const float o = obsl[tid * 16 + (i < 16 ? i : 0)];
       r.s.cur_obs[(size_t)Dst * e + i] = o;
-      r.s.env_state[(size_t)Dst * e + i] = cart ? (i < 4 ? q[4 + i] : 0.0f) : o;   // the synthetic env's state is its observation
+      r.s.env_state[(size_t)Dst * e + i] = cart ? (i < 4 ? q[4 + i] : 0.0f) : o;   // a stateful env's (at most four) state words; the synthetic env's state is its observation
     }
   }
 }

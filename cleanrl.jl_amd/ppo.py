@@ -45,6 +45,29 @@ def _crl_config(config: PPOConfig, *, obs_dim=4, n_act=2, hidden=64, gae_mode=L.
                        int(stale_obs), env_id_offset, shuffle_mode, seed)
 
 
+# The on-device envs by name: env_kind, obs_dim, n_act — what ppo.jl:85-86 reads off `single_obs_space` / `single_act_space` of the env of ppo.jl:82
+ENVS = {
+    "cartpole": (L.ENV_CARTPOLE, 4, 2),        # CartPoleEnv(T=Float32, max_steps=500)
+    "mountaincar": (L.ENV_MOUNTAINCAR, 2, 3),  # MountainCarEnv(T=Float32, max_steps=200)
+    "acrobot": (L.ENV_ACROBOT, 6, 3),          # AcrobotEnv(T=Float32, max_steps=200)
+}
+
+
+def env_shape(env, **shape):
+    """ppo.jl:82,85-86: the shape keywords of an Agent for the named env (`env=None`: the keywords as given — an explicit env_kind keeps working).
+    obs_dim / n_act / env_kind given next to `env` must agree with it."""
+    if env is None:
+        return shape
+    key = str(env).lower().replace("env", "").replace("_", "").replace("-", "")
+    if key not in ENVS:
+        raise ValueError(f"unknown env {env!r}: one of {sorted(ENVS)} (or pass env_kind / obs_dim / n_act yourself)")
+    kind, obs_dim, n_act = ENVS[key]
+    for name, want in (("env_kind", kind), ("obs_dim", obs_dim), ("n_act", n_act)):
+        if shape.get(name, want) != want:
+            raise ValueError(f"env={env!r} has {name}={want}, got {name}={shape[name]}")
+    return shape | dict(env_kind=kind, obs_dim=obs_dim, n_act=n_act)
+
+
 class Policy:
     """What `actor` / `critic` (Flux Chains in the reference, networks.jl:36-49) are here: a view of one network of an
     Agent whose weights live in HBM."""
@@ -188,8 +211,9 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0):
 
 
 def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096, run_name="ppo-2-test",
-        logger_kw=None, **shape):
-    """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. Like the Julia shell
+        logger_kw=None, env=None, **shape):
+    """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. `env="cartpole" | "mountaincar" |
+    "acrobot"` is the one-line change of ppo.jl:82: obs_dim / n_act follow from it (ppo.jl:85-86). Like the Julia shell
     (julia/CleanRLHip.jl) it logs ONE "Episode Statistics" record per finished episode in the reference's order (ppo.jl:147-165), up
     to `episode_records` per rollout (the device ring's capacity; 0 = one aggregate record per update), and the 16 "Training
     Statistics" records of every update (ppo.jl:246-248). `logger_kw` goes to Logger.make_logger (logger.jl:7); `shape` keywords
@@ -197,6 +221,7 @@ def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=
     (ppo.jl:85-87)."""
     from . import logger as _logger
     config = config or PPOConfig()
+    shape = env_shape(env, **shape)      # ppo.jl:82,85-86 (an unknown env is a ValueError before anything is created)
     _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
     agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, **shape)
     try:

@@ -36,6 +36,8 @@ extern "C" {
 #define CRL_ENV_CARTPOLE 0 /* CartPoleEnv(T=Float32, max_steps=500) ppo.jl:82 */
 #define CRL_ENV_SYNTHETIC 1 /* stateless generator for shapes the reference has no env for: obs ~ U(-1,1)^d, reward ~ U(-1,1), done ~ B(1/200) */
 #define CRL_ENV_EXTERNAL 2 /* envs stepped by the caller: crl_policy_act + crl_rollout_store */
+#define CRL_ENV_MOUNTAINCAR 3 /* MountainCarEnv(T=Float32, max_steps=200): obs_dim=2, n_act=3; on-device, layer-wise path (parity unpinned: csrc/env.hpp) */
+#define CRL_ENV_ACROBOT 4     /* AcrobotEnv(T=Float32, max_steps=200): obs_dim=6, n_act=3, RK4 "book" dynamics; on-device, layer-wise path (parity unpinned) */
 /* shuffle mode */
 #define CRL_SHUFFLE_FISHER_YATES 0 /* exact serial Fisher–Yates on device (ppo.jl:194 semantics) */
 #define CRL_SHUFFLE_BIJECTION 1     /* perm[p] = keyed bijection of [0,B): O(1) per element, pseudo-random (throughput path) */
@@ -156,6 +158,14 @@ int32_t crl_rollout_store(crl_ppo* h, int32_t step, const float* obs, const int3
 int32_t crl_env_reset(crl_ppo* h);
 /* The whole `for step in 1:num_steps` loop — ppo.jl:123-166 — in one launch (on-device env + policy + sampling). */
 int32_t crl_rollout_run(crl_ppo* h);
+/* env(actions) + reward / is_terminated / state + reset!(env) of the terminated — ppo.jl:130-165 without the policy: steps the handle's on-device envs
+ * with the caller's actions; gstep keys the reset stream like step `gstep` of the training loop. Outputs may be NULL. Leaves the rollout buffer alone.
+ * action[num_envs] 0-based (out of range is an error); next_obs (obs_dim, num_envs) is what CRL_F_CUR_OBS holds afterwards (stale_obs decides whether a
+ * terminated env shows its last or its fresh state); CRL_F_ENV_STATE / CRL_F_ENV_T / CRL_F_NEXT_DONE advance, the episode counters and statistics do
+ * not. CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR and CRL_ENV_ACROBOT on both paths; an error for CRL_ENV_SYNTHETIC (stateless) and CRL_ENV_EXTERNAL. */
+int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done);
+/* return_max is the largest return among the rollout's finished episodes, 0 when none finished. (CRL_ENV_CARTPOLE / CRL_ENV_SYNTHETIC keep their
+ * historical max(0, ·): CartPole's returns are >= 0 anyway.) */
 int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out);
 /* Per-episode records of the last rollout (the fields of ppo.jl:157's "Episode Statistics"): off by default; once enabled
  * every episode end appends {return, length, global env id, step of the rollout} to a device ring of `capacity` records

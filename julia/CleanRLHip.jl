@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!,
        comm_destroy!, set_option!, get_option
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -195,9 +195,32 @@ _default_make_logger() = isdefined(parentmodule(@__MODULE__), :Logger) ? getfiel
 # the library's restatement of it (init_params!, seeded by init_seed) when it does not. There is no path that leaves the handle's zeros in place:
 # under data parallelism every rank must end up with the SAME parameters, so pass `params` or a seeded init there (init_params! with one
 # init_seed is identical on all ranks; the reference builder draws from each process's own RNG).
+# ppo.jl:82 — the env is one keyword: ppo(config; env = :acrobot). obs_dim / n_act follow from it like ppo.jl:85-86 reads them off the env's spaces;
+# env_kind numbers are include/cleanrl_hip.h's CRL_ENV_*. `env = nothing` keeps the explicit shape keywords (env_kind = ... keeps working).
+const ENVS = Dict(:cartpole => (env_kind=0, obs_dim=4, n_act=2), :mountaincar => (env_kind=3, obs_dim=2, n_act=3), :acrobot => (env_kind=4, obs_dim=6, n_act=3))
+function env_shape(env::Union{Nothing,Symbol,AbstractString}; shape...)
+  env === nothing && return (; shape...)
+  key = Symbol(lowercase(String(env)))
+  haskey(ENVS, key) || throw(ArgumentError("unknown env $(repr(env)): one of $(sort(collect(keys(ENVS))))"))
+  want = ENVS[key]
+  for (k, v) in pairs(want)
+    haskey(shape, k) && shape[k] != v && throw(ArgumentError("env = $(repr(env)) has $k = $v, got $k = $(shape[k])"))
+  end
+  return merge((; shape...), want)
+end
+# env(actions) + reward / is_terminated / state + reset!(env) of the terminated (ppo.jl:130-165 without the policy) on the agent's on-device envs:
+# 0-based actions, `gstep` keys the reset stream like step gstep of the training loop. Returns (next_obs (obs_dim, num_envs), reward, done).
+function env_step!(a::Agent, action::Vector{Int32}, gstep::Integer=0)
+  nt = length(action)
+  obs = Matrix{Float32}(undef, a.obs_dim, nt); reward = Vector{Float32}(undef, nt); done = Vector{UInt8}(undef, nt)
+  GC.@preserve action obs reward done check(ccall((:crl_env_step, libcrl), Int32, (Ptr{Cvoid}, Ptr{Int32}, UInt64, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}),
+                                                  a.h, action, UInt64(gstep), obs, reward, done))
+  return obs, reward, done .!= 0
+end
 function ppo(config::PPOConfig=PPOConfig(); device::Integer=0, params::Union{Nothing,Vector{Float32}}=nothing, init=_default_init(), init_seed::Integer=0,
              episode_records::Integer=4096, comm::Union{Nothing,Tuple{Vector{UInt8},Int,Int}}=nothing, run_name::AbstractString="ppo-2-test",
-             make_logger=_default_make_logger(), shape...)
+             make_logger=_default_make_logger(), env::Union{Nothing,Symbol,AbstractString}=nothing, shape...)
+  shape = env_shape(env; shape...)                                         # ppo.jl:82,85-86
   make_logger === nothing || make_logger(run_name; to_terminal=false)      # ppo.jl:77
   world, rank = comm === nothing ? (1, 0) : (comm[2], comm[3])
   agent = Agent(config; device, env_id_offset=rank * config.num_envs, shape...)

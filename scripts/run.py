@@ -3,6 +3,7 @@
 command line option (ConfigParser.argparse_struct), records go to the "CleanRL" logger sinks (Logger.make_logger).
 
     python scripts/run.py ppo --num_envs 4096 --num_steps 128 --total_timesteps 10485760
+    python scripts/run.py ppo --env acrobot --hidden 256 --num_envs 256 --num_steps 128      (--env cartpole | mountaincar | acrobot: ppo.jl:82)
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
 """
@@ -20,7 +21,15 @@ def main():
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
     if algo == "ppo":
-        crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False))
+        kw = {}
+        for flag, cast in (("--env", str), ("--hidden", int)):      # not PPOConfig fields: the env of ppo.jl:82 and the width of networks.jl:36
+            if flag in argv:
+                i = argv.index(flag)
+                if i + 1 >= len(argv):
+                    raise SystemExit(f"{flag} needs a value")
+                kw[flag[2:]] = cast(argv[i + 1])
+                argv = argv[:i] + argv[i + 2:]
+        crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False).close()
     else:
