@@ -52,13 +52,29 @@ static inline WideNetPack pack_layout(int H, int D8, int O8) {
   return p;
 }
 
+// One network (0 = actor, 1 = critic) as the launchers see it. Everything in it is a constant of the handle — params, pack, wsc and the
+// workspace are allocated once (crl_ppo_create, wide_create) and never move — so wide_create fills it once and no launcher does
+// pointer arithmetic of its own.
+struct WideNet {
+  int NO, O8;                    // head outputs (n_act | 1) and the multiple of 8 the head GEMMs pad them to (A8 | 8)
+  int pbase, kbase;              // float offset of the network in h->params / of its packed copies in WideWs::pack (the pack kernels take offsets)
+  WideNetPack pk;
+  const float *W1, *b1, *W2, *b2, *W3, *b3;   // flat Flux parameters inside h->params
+  float *w1, *w3, *w2t, *w3t, *x3f, *x3b, *x2f, *x2b, *wmax, *w1s, *w1f;   // the packed copies: pack + kbase + pk.<name>
+  float *wsc, *w1sc;             // {scale, 1/scale} of the W2 pieces (wide_w2scale_kernel) / of the W1 fragments (wide_fused.hpp)
+  float* out; int ldo;           // head output: z (ld A8) | v (ld 1)
+  float* dout; int ldd;          // head cotangent, K padded to 8: z (ld A8) | dv8 (ld 8)
+  float *h1 = nullptr, *h2 = nullptr;   // [H × Mw] tanh activations
+  float *d2, *d2s;               // fused backward: this network's δ2 (dA | dB) and the per-sample inverse scales of its split planes
+  float *pW1 = nullptr, *pB1 = nullptr, *pW2 = nullptr, *pB2 = nullptr, *pW3 = nullptr;   // gradient partials
+};
+
 struct WideWs {
   int H, D, D8, A, A8, Mw;       // Mw = samples the activation buffers hold
-  WideNetPack pk[2]; int pk_base[2];
+  WideNet net[2];
   float* pack = nullptr;         // padded / transposed weight copies, rebuilt after every parameter change
   bool pack_dirty = true;
   float* wsc = nullptr;          // [2 networks][scale, 1/scale]: the power of two the fp16x2 pieces of W2 are staged with (wide_w2scale_kernel)
-  float *h1[2] = {nullptr, nullptr}, *h2[2] = {nullptr, nullptr};  // [H × Mw] tanh activations, actor / critic
   float* z = nullptr;            // [A8 × Mw] logits, overwritten by their cotangent
   float* v = nullptr;            // [Mw] critic outputs
   float* dv8 = nullptr;          // [8 × Mw] critic-output cotangent in row 0 (rows 1-7 zero: K of the head GEMM is padded to 8)
@@ -66,13 +82,9 @@ struct WideWs {
   float* d2s = nullptr;                // [2][Mw] per-sample inverse scales of the split δ2 planes (option wide_d2_split)
   // gradient partials
   int S2 = 1, chunk2 = 32, Ss = 1, chunks = 256, nlb = 1;
-  float *pW2[2] = {nullptr, nullptr}, *pB2[2] = {nullptr, nullptr};
-  float *pW1[2] = {nullptr, nullptr}, *pB1[2] = {nullptr, nullptr};
-  float* pW3[2] = {nullptr, nullptr};
   double* lpart = nullptr;       // [nlb][WLS]
   float* wrec = nullptr;         // [B][8]: action (bits), logprob, value, advantage | return, 0, 0, 0 — what the loss kernel reads of a sample, one 32-byte piece
   double* vpart = nullptr;       // [1024]
-  double* u_dev = nullptr;       // [0] u (reserved), [1] = double(count) under DP
   int cus = 256;                 // compute units of the device (grid of the persistent fused backward)
   int w3_blocks = 0;             // 1: the last backward (wide_rs_bwd_kernel) left the dW3 partials itself (one per block, like dW1): no sweeps over h2
   int fb_blocks_net[2] = {0, 0}; // … per network (the register-stationary backward may split the CUs unevenly)
@@ -97,12 +109,27 @@ bool wide_shape_ok(const crl_ppo_config* cfg, std::string* why) {
 void wide_destroy(crl_ppo* h) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
   if (!w) return;
-  void* ptrs[] = {w->pack, w->h1[0], w->h1[1], w->h2[0], w->h2[1], w->z, w->v, w->dv8, w->dA, w->dB, w->pW2[0], w->pW2[1],
-                  w->pB2[0], w->pB2[1], w->pW1[0], w->pW1[1], w->pB1[0], w->pB1[1], w->pW3[0], w->pW3[1], w->lpart, w->wrec, w->vpart,
-                  w->u_dev, w->wsc, w->d2s};
+  void* ptrs[] = {w->pack, w->z, w->v, w->dv8, w->dA, w->dB, w->lpart, w->wrec, w->vpart, w->wsc, w->d2s};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (const WideNet& n : w->net)
+    for (void* p : {(void*)n.h1, (void*)n.h2, (void*)n.pW2, (void*)n.pB2, (void*)n.pW1, (void*)n.pB1, (void*)n.pW3}) if (p) (void)hipFree(p);
   delete w;
   h->wide_ws = nullptr;
+}
+
+// the per-network view over the allocations of crl_ppo_create (params) and wide_create (everything else)
+static void wide_fill_net(const crl_ppo* h, WideWs* w, int net) {
+  WideNet& n = w->net[net];
+  const int H = w->H;
+  float* P = h->params + n.pbase;
+  n.W1 = P; n.b1 = n.W1 + H * w->D; n.W2 = n.b1 + H; n.b2 = n.W2 + H * H; n.W3 = n.b2 + H; n.b3 = n.W3 + n.NO * H;
+  float* k = w->pack + n.kbase;
+  n.w1 = k + n.pk.w1; n.w3 = k + n.pk.w3; n.w2t = k + n.pk.w2t; n.w3t = k + n.pk.w3t; n.x3f = k + n.pk.x3f; n.x3b = k + n.pk.x3b;
+  n.x2f = k + n.pk.x2f; n.x2b = k + n.pk.x2b; n.wmax = k + n.pk.wmax; n.w1s = k + n.pk.w1s; n.w1f = k + n.pk.w1f;
+  n.wsc = w->wsc + 2 * net; n.w1sc = w->wsc + 4 + 2 * net;
+  n.out = net ? w->v : w->z; n.ldo = net ? 1 : w->A8;
+  n.dout = net ? w->dv8 : w->z; n.ldd = n.O8;
+  n.d2 = net ? w->dB : w->dA; n.d2s = w->d2s + (size_t)net * w->Mw;
 }
 
 int wide_create(crl_ppo* h) {
@@ -117,14 +144,17 @@ int wide_create(crl_ppo* h) {
   // gfx950 has 160 KB of LDS per workgroup; the #error guard of update.hip also admits gfx942 (64 KB), where the tile-resident kernels
   // cannot launch: there the layer-wise kernels (wide_fuse = 0, wide_rollout_persist = 1) run instead of a launch failure
   { int lds = 0; if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess && lds > 0) w->lds_max = lds; }
-  w->pk[0] = pack_layout(w->H, w->D8, w->A8);
-  w->pk[1] = pack_layout(w->H, w->D8, 8);
-  w->pk_base[0] = 0; w->pk_base[1] = w->pk[0].size;
+  for (int n = 0; n < 2; ++n) {
+    WideNet& q = w->net[n];
+    q.NO = n ? 1 : w->A; q.O8 = n ? 8 : w->A8;
+    q.pk = pack_layout(w->H, w->D8, q.O8);
+    q.pbase = n ? (int)h->Pa : 0; q.kbase = n ? w->net[0].pk.size : 0;
+  }
   const size_t H = (size_t)w->H, Mw = (size_t)w->Mw;
   int rc = 0;
-  rc |= walloc(&w->pack, (size_t)w->pk[0].size + w->pk[1].size);
+  rc |= walloc(&w->pack, (size_t)w->net[0].pk.size + w->net[1].pk.size);
   rc |= walloc(&w->wsc, 8);   // [net][scale, 1/scale] of the W2 pieces, then the same of the W1 fragments (wide_fused.hpp)
-  for (int n = 0; n < 2; ++n) { rc |= walloc(&w->h1[n], H * Mw); rc |= walloc(&w->h2[n], H * Mw); }
+  for (WideNet& q : w->net) { rc |= walloc(&q.h1, H * Mw); rc |= walloc(&q.h2, H * Mw); }
   rc |= walloc(&w->z, (size_t)w->A8 * Mw); rc |= walloc(&w->v, Mw); rc |= walloc(&w->dv8, 8 * Mw);
   rc |= walloc(&w->dA, H * Mw); rc |= walloc(&w->dB, H * Mw); rc |= walloc(&w->d2s, 2 * Mw);
   // weight-gradient splits: ≈2048-sample chunks for the MFMA kernel, 512-sample chunks for the VALU kernels
@@ -136,17 +166,16 @@ int wide_create(crl_ppo* h) {
   int ss = (M + 511) / 512; if (ss > 1024) ss = 1024; if (ss < 1) ss = 1;
   w->Ss = ss; w->chunks = (M + ss - 1) / ss;
   w->nlb = (M + 255) / 256;
-  for (int n = 0; n < 2; ++n) {
-    const size_t NO = n ? 1 : (size_t)w->A;
-    rc |= walloc(&w->pW2[n], (size_t)w->S2 * H * H); rc |= walloc(&w->pB2[n], (size_t)w->S2 * H);
-    rc |= walloc(&w->pW1[n], (size_t)w->Ss * H * w->D); rc |= walloc(&w->pB1[n], (size_t)w->Ss * H);
-    rc |= walloc(&w->pW3[n], (size_t)w->Ss * H * NO);
+  for (WideNet& q : w->net) {
+    rc |= walloc(&q.pW2, (size_t)w->S2 * H * H); rc |= walloc(&q.pB2, (size_t)w->S2 * H);
+    rc |= walloc(&q.pW1, (size_t)w->Ss * H * w->D); rc |= walloc(&q.pB1, (size_t)w->Ss * H);
+    rc |= walloc(&q.pW3, (size_t)w->Ss * H * q.NO);
   }
   rc |= walloc(reinterpret_cast<float**>(&w->lpart), (size_t)w->nlb * WLS * 2);
   rc |= walloc(&w->wrec, (size_t)h->dc.B * 8);
   rc |= walloc(reinterpret_cast<float**>(&w->vpart), 1024 * 2);
-  rc |= walloc(reinterpret_cast<float**>(&w->u_dev), 4 * 2);
   if (rc) { wide_destroy(h); return 1; }
+  wide_fill_net(h, w, 0); wide_fill_net(h, w, 1);
   return 0;
 }
 
@@ -295,47 +324,41 @@ __global__ void wide_prep_b_kernel(PrepArgs a);
 static int ensure_pack(crl_ppo* h) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
   if (!w->pack_dirty) return 0;
+  const int nb_w1s = (w->H * w->D8 + w->H + 255) / 256;
   if (w->H == 256 && wide_x2(h) && w->D <= 16) {
     PrepArgs a;
     a.params = h->params; a.pack = w->pack; a.wsc = w->wsc; a.H = w->H; a.D = w->D; a.D8 = w->D8;
-    int nbp = 0;
+    a.nb_pack = 0; a.nb_w1s = nb_w1s;
     for (int n = 0; n < 2; ++n) {
-      a.n[n].pbase = n ? (int)h->Pa : 0; a.n[n].kbase = w->pk_base[n]; a.n[n].pk = w->pk[n]; a.n[n].NO = n ? 1 : w->A; a.n[n].O8 = n ? 8 : w->A8;
-      const int nb = (w->pk[n].x3f + 255) / 256;
-      if (nb > nbp) nbp = nb;
+      const WideNet& q = w->net[n];
+      a.n[n].pbase = q.pbase; a.n[n].kbase = q.kbase; a.n[n].pk = q.pk; a.n[n].NO = q.NO; a.n[n].O8 = q.O8;
+      const int nb = (q.pk.x3f + 255) / 256;
+      if (nb > a.nb_pack) a.nb_pack = nb;
     }
-    a.nb_pack = nbp; a.nb_w1s = (w->H * w->D8 + w->H + 255) / 256;
     hipLaunchKernelGGL(wide_prep_a_kernel, dim3(a.nb_pack + a.nb_w1s + 3, 2), dim3(256), 0, h->stream, a);
     hipLaunchKernelGGL(wide_prep_b_kernel, dim3(64 + 2, 2), dim3(256), 0, h->stream, a);
     CRL_HIP_CHECK(hipGetLastError());
     w->pack_dirty = false;
     return 0;
   }
-  for (int n = 0; n < 2; ++n) {
-    const int NO = n ? 1 : w->A, O8 = n ? 8 : w->A8;
-    hipLaunchKernelGGL(wide_pack_kernel, dim3((w->pk[n].x3f + 255) / 256), dim3(256), 0, h->stream, h->params, w->pack, w->H, w->D,
-                       w->D8, NO, O8, n ? (int)h->Pa : 0, w->pk_base[n], w->pk[n]);
+  const dim3 frag_grid(2 * 8 * 2 * 8 * 64 / 256);   // one thread per (dir, slab, kstep, ntile, lane) of the W2 fragment images
+  for (const WideNet& q : w->net) {
+    const int w2off = (int)(q.W2 - h->params);
+    hipLaunchKernelGGL(wide_pack_kernel, dim3((q.pk.x3f + 255) / 256), dim3(256), 0, h->stream, h->params, w->pack, w->H, w->D,
+                       w->D8, q.NO, q.O8, q.pbase, q.kbase, q.pk);
     if (w->H == 256) {
       if (!wide_x2(h))   // the bf16x3 fragments are read by the wide_gemm = 1 flavour only
-        hipLaunchKernelGGL(wide_pack_x3_kernel, dim3(2 * 8 * 2 * 8 * 64 / 256), dim3(256), 0, h->stream, h->params, w->pack,
-                           (n ? (int)h->Pa : 0) + w->H * w->D + w->H, w->pk_base[n], w->pk[n]);
-      hipLaunchKernelGGL(wide_w2scale_kernel, dim3(1), dim3(1024), 0, h->stream, h->params + (n ? (int)h->Pa : 0) + w->H * w->D + w->H,
-                         w->H * w->H, w->wsc + 2 * n);
-      hipLaunchKernelGGL(wide_pack_x2_kernel, dim3(2 * 8 * 2 * 8 * 64 / 256), dim3(256), 0, h->stream, h->params, w->pack,
-                         (n ? (int)h->Pa : 0) + w->H * w->D + w->H, w->pk_base[n], w->pk[n], w->wsc + 2 * n);
+        hipLaunchKernelGGL(wide_pack_x3_kernel, frag_grid, dim3(256), 0, h->stream, h->params, w->pack, w2off, q.kbase, q.pk);
+      hipLaunchKernelGGL(wide_w2scale_kernel, dim3(1), dim3(1024), 0, h->stream, q.W2, w->H * w->H, q.wsc);
+      hipLaunchKernelGGL(wide_pack_x2_kernel, frag_grid, dim3(256), 0, h->stream, h->params, w->pack, w2off, q.kbase, q.pk, q.wsc);
     }
     if (w->H == 256 && w->D <= 16) {
-      const float* W1 = h->params + (n ? (int)h->Pa : 0);
-      hipLaunchKernelGGL(wide_w1scale_kernel, dim3(1), dim3(256), 0, h->stream, W1, w->H * w->D, w->wsc + 4 + 2 * n);
-      hipLaunchKernelGGL(wide_pack_w1f_kernel, dim3(2), dim3(256), 0, h->stream, W1, W1 + w->H * w->D, w->D, w->wsc + 4 + 2 * n,
-                         w->pack + w->pk_base[n] + w->pk[n].w1f);
+      hipLaunchKernelGGL(wide_w1scale_kernel, dim3(1), dim3(256), 0, h->stream, q.W1, w->H * w->D, q.w1sc);
+      hipLaunchKernelGGL(wide_pack_w1f_kernel, dim3(2), dim3(256), 0, h->stream, q.W1, q.b1, w->D, q.w1sc, q.w1f);
     }
     if (w->H == 256)
-      hipLaunchKernelGGL(wide_pack_w1s_kernel, dim3((w->H * w->D8 + w->H + 255) / 256), dim3(256), 0, h->stream, h->params + (n ? (int)h->Pa : 0),
-                         h->params + (n ? (int)h->Pa : 0) + w->H * w->D, w->H, w->D, w->D8, w->pack + w->pk_base[n] + w->pk[n].w1s);
-    hipLaunchKernelGGL(wide_wmax_kernel, dim3(1), dim3(64), 0, h->stream,
-                       h->params + (n ? (int)h->Pa : 0) + w->H * w->D + w->H + w->H * w->H + w->H, NO, w->H,
-                       w->pack + w->pk_base[n] + w->pk[n].wmax);
+      hipLaunchKernelGGL(wide_pack_w1s_kernel, dim3(nb_w1s), dim3(256), 0, h->stream, q.W1, q.b1, w->H, w->D, w->D8, q.w1s);
+    hipLaunchKernelGGL(wide_wmax_kernel, dim3(1), dim3(64), 0, h->stream, q.W3, q.NO, w->H, q.wmax);
   }
   CRL_HIP_CHECK(hipGetLastError());
   w->pack_dirty = false;
@@ -1034,43 +1057,39 @@ static int dense_launch(hipStream_t st, int NP, const DenseArgs& a) {
   return 0;
 }
 
-// flat Flux parameter offsets inside one network
-struct NetOff { int W1, b1, W2, b2, W3, b3, size; };
-static NetOff net_off(int H, int D, int NO) {
-  NetOff o; o.W1 = 0; o.b1 = H * D; o.W2 = o.b1 + H; o.b2 = o.W2 + H * H; o.W3 = o.b2 + H; o.b3 = o.W3 + NO * H; o.size = o.b3 + NO;
-  return o;
+// Argument builders of the layer-wise forward: a function of the network view and the few things that differ per site.
+// layer 1: h1 = tanh(W1·x + b1) over M samples at X (ld ldx, gathered through idx)
+static DenseArgs dense_l1_args(const WideWs* w, const WideNet& n, const float* X, int ldx, const int32_t* idx, int M, int fast) {
+  DenseArgs a;
+  a.W = n.w1; a.Kp = w->D8; a.X = X; a.ldx = ldx; a.Kt = w->D; a.idx = idx; a.bias = n.b1; a.S = nullptr; a.lds = 0;
+  a.Y = n.h1; a.ldy = w->H; a.Nt = w->H; a.M = M; a.fast_act = fast;
+  return a;
+}
+// 2×256 layer 2 on a split-product kernel, h2 = tanh(W2·h1 + b2), with the head Z = W3·h2 + b3 out of its epilogue (tile_tanh_head)
+static DenseX3Args dense_x3_fwd_args(const crl_ppo* h, const WideNet& n, int M, float* Z, int ldz, int fast) {
+  DenseX3Args x;
+  x.Wx3 = wide_x2(h) ? n.x2f : n.x3f; x.X = n.h1; x.K = 256; x.bias = n.b2; x.S = nullptr; x.Y = n.h2; x.M = M;
+  x.W3t = n.w3t; x.b3 = n.b3; x.Z = Z; x.A = n.NO; x.ldz = ldz;
+  x.dZ = nullptr; x.ldd = 0; x.Ad = 0; x.bz = nullptr; x.bld = 0; x.bA = 0; x.wmax = nullptr; x.fast_act = fast; x.wsc = n.wsc;
+  return x;
 }
 
 // forward of one network over M samples: h1, h2 kept in the workspace, head output to out (ld ldo)
 // fast_act: the exp2-based activation (wide_tanh) — the update pass and the critic; the actor of the rollout / get_action keeps
 // tanh_fast because its logits decide action indices that are compared bit for bit
 static int wide_forward(crl_ppo* h, int net, const float* X, int ldx, const int32_t* idx, int M, float* out, int ldo, bool fast_act = false) {
-  fast_act = fast_act && !opt(h, OPT_WIDE_TANH_RATIONAL);
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
-  const int H = w->H, NO = net ? 1 : w->A;
-  const NetOff o = net_off(H, w->D, NO);
-  const float* P = h->params + (net ? h->Pa : 0);
-  const float* pk = w->pack + w->pk_base[net];
-  DenseArgs a;
-  a.idx = idx; a.S = nullptr; a.lds = 0; a.M = M; a.fast_act = fast_act ? 1 : 0;
-  a.W = pk + w->pk[net].w1; a.Kp = w->D8; a.X = X; a.ldx = ldx; a.Kt = w->D; a.bias = P + o.b1; a.Y = w->h1[net]; a.ldy = H; a.Nt = H;
+  const WideNet& n = w->net[net];
+  const int H = w->H, fast = fast_act && !opt(h, OPT_WIDE_TANH_RATIONAL) ? 1 : 0;
+  DenseArgs a = dense_l1_args(w, n, X, ldx, idx, M, fast);
   if (dense_launch<EPI_TANH>(h->stream, H, a)) return 1;
-  a.idx = nullptr;
   if (H == 256 && wide_x3(h)) {
-    DenseX3Args x;
-    x.Wx3 = pk + w->pk[net].x3f; x.X = w->h1[net]; x.K = H; x.bias = P + o.b2; x.S = nullptr; x.Y = w->h2[net]; x.M = M;
-    const bool fuse = true;   // the head comes out of the layer-2 epilogue (tile_tanh_head)
-    x.W3t = pk + w->pk[net].w3t; x.b3 = P + o.b3; x.Z = fuse ? out : nullptr; x.A = NO; x.ldz = ldo;
-    x.dZ = nullptr; x.ldd = 0; x.Ad = 0; x.bz = nullptr; x.bld = 0; x.bA = 0; x.wmax = nullptr; x.fast_act = fast_act ? 1 : 0;
-    if (wide_x2(h)) { x.Wx3 = pk + w->pk[net].x2f; x.wsc = w->wsc + 2 * net; if (dense_x2_launch<EPI_TANH>(h->stream, x)) return 1; }
-    else if (dense_x3_launch<EPI_TANH>(h->stream, x)) return 1;
-    if (fuse) return 0;   // the head came out of the layer-2 epilogue
-  } else {
-    a.W = P + o.W2; a.Kp = H; a.X = w->h1[net]; a.ldx = H; a.Kt = H; a.bias = P + o.b2; a.Y = w->h2[net];
-    if (dense_launch<EPI_TANH>(h->stream, H, a)) return 1;
+    const DenseX3Args x = dense_x3_fwd_args(h, n, M, out, ldo, fast);
+    return wide_x2(h) ? dense_x2_launch<EPI_TANH>(h->stream, x) : dense_x3_launch<EPI_TANH>(h->stream, x);
   }
-  a.ldx = H; a.Kt = H;
-  a.W = pk + w->pk[net].w3; a.Kp = H; a.X = w->h2[net]; a.bias = P + o.b3; a.Y = out; a.ldy = ldo; a.Nt = NO;
+  a.idx = nullptr; a.W = n.W2; a.Kp = H; a.X = n.h1; a.ldx = H; a.Kt = H; a.bias = n.b2; a.Y = n.h2;
+  if (dense_launch<EPI_TANH>(h->stream, H, a)) return 1;
+  a.W = n.w3; a.X = n.h2; a.bias = n.b3; a.Y = out; a.ldy = ldo; a.Nt = n.NO;
   return dense_launch<EPI_BIAS>(h->stream, 32, a);
 }
 
@@ -1079,30 +1098,16 @@ static int wide_forward(crl_ppo* h, int net, const float* X, int ldx, const int3
 // are instantiated for); anything else runs the two networks one after the other.
 static int wide_forward_pair(crl_ppo* h, const float* X, int ldx, int M, float* outA, int ldoA, float* outC, int ldoC) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
-  const bool fast_ok = !opt(h, OPT_WIDE_TANH_RATIONAL);
   if (!(w->H == 256 && wide_x2(h) && M > 0 && M <= 32768)) {
     if (wide_forward(h, 0, X, ldx, nullptr, M, outA, ldoA)) return 1;          // ppo.jl:127
     return wide_forward(h, 1, X, ldx, nullptr, M, outC, ldoC, true);           // ppo.jl:128
   }
-  const int H = 256;
-  DenseArgs a[2]; DenseX3Args x[2];
-  for (int net = 0; net < 2; ++net) {
-    const int NO = net ? 1 : w->A;
-    const NetOff o = net_off(H, w->D, NO);
-    const float* P = h->params + (net ? h->Pa : 0);
-    const float* pk = w->pack + w->pk_base[net];
-    const int fast = (net == 1 && fast_ok) ? 1 : 0;      // the actor keeps tanh_fast: its logits decide bit-compared action indices
-    a[net].idx = nullptr; a[net].S = nullptr; a[net].lds = 0; a[net].M = M; a[net].fast_act = fast;
-    a[net].W = pk + w->pk[net].w1; a[net].Kp = w->D8; a[net].X = X; a[net].ldx = ldx; a[net].Kt = w->D; a[net].bias = P + o.b1;
-    a[net].Y = w->h1[net]; a[net].ldy = H; a[net].Nt = H;
-    x[net].Wx3 = pk + w->pk[net].x2f; x[net].X = w->h1[net]; x[net].K = H; x[net].bias = P + o.b2; x[net].S = nullptr; x[net].Y = w->h2[net]; x[net].M = M;
-    x[net].W3t = pk + w->pk[net].w3t; x[net].b3 = P + o.b3; x[net].Z = net ? outC : outA; x[net].A = NO; x[net].ldz = net ? ldoC : ldoA;
-    x[net].dZ = nullptr; x[net].ldd = 0; x[net].Ad = 0; x[net].bz = nullptr; x[net].bld = 0; x[net].bA = 0; x[net].wmax = nullptr; x[net].fast_act = fast;
-    x[net].wsc = w->wsc + 2 * net;
-  }
-  hipLaunchKernelGGL((wide_dense_pair_kernel<4, 2, 1, 1, EPI_TANH>), dim3((M + 31) / 32, 2), dim3(256), sizeof(float) * (32 * 256 + 32 * WXS), h->stream, a[0], a[1]);
-  const size_t s0 = dense_x2_smem(x[0], 32), s1 = dense_x2_smem(x[1], 32);
-  hipLaunchKernelGGL((wide_dense_x2_pair_kernel<EPI_TANH, 1>), dim3((M + 31) / 32, 2), dim3(512), s0 > s1 ? s0 : s1, h->stream, x[0], x[1]);
+  const int fastC = opt(h, OPT_WIDE_TANH_RATIONAL) ? 0 : 1;   // the actor keeps tanh_fast: its logits decide bit-compared action indices
+  const DenseArgs a0 = dense_l1_args(w, w->net[0], X, ldx, nullptr, M, 0), a1 = dense_l1_args(w, w->net[1], X, ldx, nullptr, M, fastC);
+  const DenseX3Args x0 = dense_x3_fwd_args(h, w->net[0], M, outA, ldoA, 0), x1 = dense_x3_fwd_args(h, w->net[1], M, outC, ldoC, fastC);
+  hipLaunchKernelGGL((wide_dense_pair_kernel<4, 2, 1, 1, EPI_TANH>), dim3((M + 31) / 32, 2), dim3(256), sizeof(float) * (32 * 256 + 32 * WXS), h->stream, a0, a1);
+  const size_t s0 = dense_x2_smem(x0, 32), s1 = dense_x2_smem(x1, 32);
+  hipLaunchKernelGGL((wide_dense_x2_pair_kernel<EPI_TANH, 1>), dim3((M + 31) / 32, 2), dim3(512), s0 > s1 ? s0 : s1, h->stream, x0, x1);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -2507,7 +2512,122 @@ int wide_env_reset(crl_ppo* h) {
   return 0;
 }
 
-static bool wide_fused_ok(const crl_ppo* h);
+// ------------------------------------------------------------------------------------------------------
+// Routes. Which kernels a (shape, options, batch size) reaches is decided in the two functions below and nowhere else: every
+// predicate is written once, and the launchers only read the result.
+// ------------------------------------------------------------------------------------------------------
+// The tile-resident kernels of wide_fused.hpp apply: 2x256, fp16x2, obs_dim <= 16, exp2-based activation (what
+// wide_forward(…, fast_act = true) computes layer by layer). Option wide_fuse = 0 keeps the layer-wise launches.
+static bool wide_fused_ok(const crl_ppo* h) {
+  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
+  return w->H == 256 && wide_x2(h) && w->D8 <= 16 && w->A <= AMAX && opt(h, OPT_WIDE_FUSE) != 0 && !opt(h, OPT_WIDE_TANH_RATIONAL) &&
+         w->lds_max >= FB_OFF_W3 + FB_AMAX * 1024;    // the largest request of the fused forward / backward / weight-gradient kernels
+}
+
+// RS_ACTOR: register-stationary actor for all steps (wide_rs_rollout_kernel), then the critic as ONE batched forward — on wide_rs_fwd_kernel
+// if critic_rs (wide_rs bit 2), else on wide_fused_fwd_pc_kernel; PC: one launch for all steps, producer / consumer form (wide_rollout_pc_kernel);
+// PERSIST: one launch for all steps (wide_rollout_persist_kernel); STEPWISE: wide_forward_pair + wide_step_kernel per step
+struct WideRolloutRoute { enum Kind { RS_ACTOR, PC, PERSIST, STEPWISE } kind; bool critic_rs; };
+static WideRolloutRoute wide_rollout_route(const crl_ppo* h) {
+  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
+  const int persist = (int)opt(h, OPT_WIDE_ROLLOUT_PERSIST), rs = (int)opt(h, OPT_WIDE_RS), nt = h->dc.nt;
+  const bool x2_256 = w->H == 256 && wide_x2(h) && w->D <= 16;
+  WideRolloutRoute r;
+  r.critic_rs = false;
+  if ((rs & 2) && x2_256 && w->A <= 8 && persist >= 2 && nt % RR_MB == 0 && w->lds_max >= RR_LDS && wide_fused_ok(h) && h->dc.B % FX_MB == 0) {
+    r.kind = WideRolloutRoute::RS_ACTOR;
+    r.critic_rs = (rs & 4) && w->D % 4 == 0 && w->lds_max >= R2_LDS;   // measured slower: 1.21 vs 0.87 ms at C3
+  } else if (x2_256 && w->A <= PC_AMAX && persist >= 2 && nt % RP_MB == 0 && w->lds_max >= RP_LDS) r.kind = WideRolloutRoute::PC;
+  else if (x2_256 && persist) r.kind = WideRolloutRoute::PERSIST;
+  else r.kind = WideRolloutRoute::STEPWISE;
+  return r;
+}
+
+// One minibatch of M samples. With bwd == BWD_LAYERS wide_backward runs per network, and split / wgrad / side_stream say nothing.
+struct WideUpdateRoute {
+  // wide_forward per network | wide_fused_fwd_kernel (symmetric: wide_fuse_pc = 0 or n_act > PC_AMAX) | wide_fused_fwd_pc_kernel (producer /
+  // consumer, persistent) | wide_rs_fwd_kernel (register-stationary, wide_rs bit 0: no weight stream at all)
+  enum Fwd { FWD_LAYERS, FWD_FUSED, FWD_FUSED_PC, FWD_RS } fwd;
+  int wbufs;        // FWD_FUSED_PC: three weight buffers (the slab after next in flight) where the W3ᵀ table leaves room for them, option
+                    // wide_fwd_wbufs = 2 keeps two, 0 = weight fragments straight into the consumers' registers
+  bool h1_free;     // h1 is never stored: the fused backward does not read it and the weight gradient regenerates it (option wide_fuse = 3, the default)
+  // wide_backward per network | wide_fused_bwd_kernel | wide_rs_bwd_kernel (wide_rs bit 3) | the same with dW3 inside the kernel instead of
+  // the two sweeps over h2 (wide_rs bit 4)
+  enum Bwd { BWD_LAYERS, BWD_FUSED, BWD_RS, BWD_RS_DW3 } bwd;
+  bool split;       // δ2 as the backward's own fp16x2 pieces when its only reader is the 256x256 weight-gradient kernel (whole 32-sample slabs: M % 128 == 0 here)
+  // dW2 / db2: wide_wgrad_x2_kernel<4> per network on the stored h1 | wide_wgrad_x2_kernel<4, true> per network, h1 regenerated, 256 x 128 tiles
+  // (wide_wgrad_full = 0) | wide_wgrad_gen_kernel, both networks in one launch, 256 x 256 tile per block | wide_wgrad_split_kernel, the same from the split planes
+  enum Wgrad { WGRAD_H1, WGRAD_GEN_128, WGRAD_GEN_256, WGRAD_SPLIT } wgrad;
+  bool side_stream; // the dW3 sweeps run on the second stream beside the backward kernel: fork behind the loss kernel, join behind the weight gradient
+};
+static WideUpdateRoute wide_update_route(const crl_ppo* h, int M) {
+  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
+  const int fuse = (int)opt(h, OPT_WIDE_FUSE), rs = (int)opt(h, OPT_WIDE_RS), wbufs = (int)opt(h, OPT_WIDE_FWD_WBUFS);
+  const bool fused_shape = wide_fused_ok(h) && M % FX_MB == 0;
+  const bool pc = opt(h, OPT_WIDE_FUSE_PC) && w->A <= PC_AMAX;
+  const bool rs_shape = M % RS_MB == 0 && w->D % 4 == 0;      // what the register-stationary update kernels ask of a minibatch
+  WideUpdateRoute r;
+  r.h1_free = fuse >= 3 && pc && w->A <= FB_AMAX && w->D <= 16;
+  r.wbufs = wbufs == 0 ? 0 : (w->A <= pc_amax(3) && wbufs >= 3 && w->lds_max >= pc_lds(3)) ? 3 : 2;
+  r.fwd = !fused_shape ? WideUpdateRoute::FWD_LAYERS
+        : !pc ? WideUpdateRoute::FWD_FUSED
+        : ((rs & 1) && r.h1_free && rs_shape && w->lds_max >= R2_LDS) ? WideUpdateRoute::FWD_RS : WideUpdateRoute::FWD_FUSED_PC;
+  r.split = r.h1_free && opt(h, OPT_WIDE_WGRAD_FULL) && opt(h, OPT_WIDE_D2_SPLIT) && w->chunk2 % 32 == 0 && w->lds_max >= WS_LDS;
+  const bool rsb = r.split && (rs & 8) && rs_shape && w->A <= 8 && w->lds_max >= RB_LDS;
+  r.bwd = !(fused_shape && w->A <= FB_AMAX && fuse >= 2) ? WideUpdateRoute::BWD_LAYERS
+        : !rsb ? WideUpdateRoute::BWD_FUSED
+        : (rs & 16) ? WideUpdateRoute::BWD_RS_DW3 : WideUpdateRoute::BWD_RS;
+  r.wgrad = !r.h1_free ? WideUpdateRoute::WGRAD_H1
+          : !opt(h, OPT_WIDE_WGRAD_FULL) ? WideUpdateRoute::WGRAD_GEN_128
+          : r.split ? WideUpdateRoute::WGRAD_SPLIT : WideUpdateRoute::WGRAD_GEN_256;
+  // (nothing goes to the side stream when the backward kernel formed dW3 itself: no fork / join — 13 µs per step)
+  r.side_stream = r.bwd != WideUpdateRoute::BWD_LAYERS && opt(h, OPT_SHUFFLE_OVERLAP) != 0 && r.bwd != WideUpdateRoute::BWD_RS_DW3;
+  return r;
+}
+
+// The (DP, NA) template ladder of the tile-resident kernels: DP = obs_dim padded to 8 or 16, NA = head rows held in registers, 4 or 8.
+// f(dp, na) receives the pair as std::integral_constants.
+template <class F>
+static void wide_dp_na(const WideWs* w, F&& f) {
+  using I4 = std::integral_constant<int, 4>; using I8 = std::integral_constant<int, 8>; using I16 = std::integral_constant<int, 16>;
+  if (w->D8 == 8 && w->A <= 4) f(I8{}, I4{});
+  else if (w->D8 == 8) f(I8{}, I8{});
+  else if (w->A <= 4) f(I16{}, I4{});
+  else f(I16{}, I8{});
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Argument builders: one per kernel argument struct that is filled at more than one site
+// ------------------------------------------------------------------------------------------------------
+// the producer / consumer and register-stationary forward of one network over M samples of h->obs (gathered through perm)
+static FusedFwdPCArgs fused_fwd_pc_args(const crl_ppo* h, const WideNet& n, const int32_t* perm, int M, float* H1, float* H2, float* Z) {
+  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
+  FusedFwdPCArgs q;
+  q.obs = h->obs; q.perm = perm; q.D = w->D; q.W1f = n.w1f; q.w1sc = n.w1sc; q.Wx2 = n.x2f; q.b2 = n.b2; q.wsc = n.wsc;
+  q.W3t = n.w3t; q.b3 = n.b3; q.A = n.NO; q.ldz = n.ldo; q.H1 = H1; q.H2 = H2; q.Z = Z; q.M = M;
+  return q;
+}
+// one network of the one-launch rollouts; rat: 1 = tanh_fast (rational), 0 = the exp2 form
+static RollPCNet roll_pc_net(const WideNet& n, int rat) {
+  RollPCNet r;
+  r.W1f = n.w1f; r.w1sc = n.w1sc; r.Wx2 = n.x2f; r.b2 = n.b2; r.wsc = n.wsc; r.W3t = n.w3t; r.b3 = n.b3; r.Z = n.out; r.A = n.NO; r.ldz = n.ldo; r.rat = rat;
+  return r;
+}
+// dW3[a, k] = Σ δ3[a]·h2[k]; D2out non-null: the same sweep over h2 also leaves δ2 there (wide_skinny_kernel<.., D2>)
+static SkinnyArgs dw3_args(const WideWs* w, const WideNet& n, int M, float* D2out) {
+  SkinnyArgs s;
+  s.Big = n.h2; s.H = w->H; s.Small = n.dout; s.lds = n.ldd; s.idx = nullptr; s.M = M; s.chunk = w->chunks;
+  s.pW = n.pW3; s.os_row = n.NO; s.os_s = 1; s.St = n.NO; s.wsize = w->H * n.NO; s.pB = nullptr; s.D2out = D2out; s.W3t = n.w3t;
+  return s;
+}
+// dW2 = δ2·Xᵀ, db2 = Σ δ2 with δ2 at dY; X = the stored h1, or null for the flavour that regenerates it (the caller adds the GEN fields)
+static WgradArgs wgrad_args(const WideWs* w, const WideNet& n, const float* dY, const float* X, int M) {
+  WgradArgs g;
+  g.dY = dY; g.X = X; g.H = w->H; g.M = M; g.chunk = w->chunk2; g.pW = n.pW2; g.pB = n.pB2;
+  g.dZ = nullptr; g.ldd = n.ldd; g.Ad = n.NO; g.W3t = n.w3t; g.bz = n.dout; g.bld = n.ldd; g.bA = n.NO; g.wmax = n.wmax;
+  return g;
+}
+
 int wide_rollout(crl_ppo* h) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
   if (ensure_pack(h)) return 1;
@@ -2520,132 +2640,84 @@ int wide_rollout(crl_ppo* h) {
   a.ring = h->ep_ring; a.ring_count = h->ep_ring_count; a.ring_cap = h->ep_ring_cap;
   if (h->ep_ring_cap > 0) CRL_HIP_CHECK(hipMemsetAsync(h->ep_ring_count, 0, sizeof(uint32_t), h->stream));
   ProfScope ps(h, CRL_K_ROLLOUT);
-  if ((opt(h, OPT_WIDE_RS) & 2) && w->H == 256 && wide_x2(h) && w->D <= 16 && w->A <= 8 && opt(h, OPT_WIDE_ROLLOUT_PERSIST) >= 2 && h->dc.nt % RR_MB == 0 &&
-      w->lds_max >= RR_LDS && wide_fused_ok(h) && h->dc.B % FX_MB == 0) {
-    // register-stationary actor for all steps (wide_rs_rollout_kernel), then the critic over the stored observations as ONE batched forward
-    RsRollArgs r;
-    {
-      const NetOff o = net_off(256, w->D, w->A);
-      const float* pk = w->pack + w->pk_base[0];
-      RollPCNet& n = r.n;
-      n.W1f = pk + w->pk[0].w1f; n.w1sc = w->wsc + 4; n.Wx2 = pk + w->pk[0].x2f; n.b2 = h->params + o.b2; n.wsc = w->wsc;
-      n.W3t = pk + w->pk[0].w3t; n.b3 = h->params + o.b3; n.Z = w->z; n.A = w->A; n.ldz = w->A8; n.rat = 1;
+  const WideRolloutRoute rt = wide_rollout_route(h);
+  const int ratC = opt(h, OPT_WIDE_TANH_RATIONAL) ? 1 : 0;   // the critic's activation; the actor keeps tanh_fast: its logits decide bit-compared action indices
+  const int nt = h->dc.nt;
+  switch (rt.kind) {
+    case WideRolloutRoute::RS_ACTOR: {
+      RsRollArgs r;
+      r.n = roll_pc_net(w->net[0], 1); r.s = a; r.s.V = nullptr; r.D = w->D;
+      wide_dp_na(w, [&](auto dp, auto na) {
+        hipLaunchKernelGGL((wide_rs_rollout_kernel<decltype(dp)::value, decltype(na)::value>), dim3(nt / RR_MB), dim3(512), RR_LDS, h->stream, r);
+      });
+      CRL_HIP_CHECK(hipGetLastError());
+      // values of all num_steps x num_envs stored observations (ppo.jl:128 evaluates the critic on the same observation the buffer keeps)
+      const FusedFwdPCArgs q = fused_fwd_pc_args(h, w->net[1], nullptr, h->dc.B, nullptr, nullptr, h->value);
+      if (!rt.critic_rs) {
+        int nbc = w->cus; const int ntiles = h->dc.B / FX_MB; if (nbc > ntiles) nbc = ntiles;
+        if (w->D8 == 8) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<8, false, 2>), dim3(nbc, 1), dim3(512), pc_lds(2), h->stream, q, q);
+        else hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<16, false, 2>), dim3(nbc, 1), dim3(512), pc_lds(2), h->stream, q, q);
+      } else {
+        // register-stationary forward, every block on the critic: the grid's y = 0 half (the actor flavour) gets an empty argument and leaves at once
+        FusedFwdPCArgs q0 = q; q0.M = 0;
+        int nbc = w->cus; const int nt32 = h->dc.B / RS_MB; if (nbc > nt32) nbc = nt32;
+        if (w->D8 == 8) hipLaunchKernelGGL((wide_rs_fwd_kernel<8, 4, false>), dim3(nbc, 2), dim3(512), R2_LDS, h->stream, q0, q);
+        else hipLaunchKernelGGL((wide_rs_fwd_kernel<16, 4, false>), dim3(nbc, 2), dim3(512), R2_LDS, h->stream, q0, q);
+      }
+      break;
     }
-    r.s = a; r.s.V = nullptr; r.D = w->D;
-    const int nb = h->dc.nt / RR_MB;
-#define CRL_RSROLL(dp, na) hipLaunchKernelGGL((wide_rs_rollout_kernel<dp, na>), dim3(nb), dim3(512), RR_LDS, h->stream, r)
-    if (w->D8 == 8 && w->A <= 4) CRL_RSROLL(8, 4);
-    else if (w->D8 == 8) CRL_RSROLL(8, 8);
-    else if (w->A <= 4) CRL_RSROLL(16, 4);
-    else CRL_RSROLL(16, 8);
-#undef CRL_RSROLL
-    CRL_HIP_CHECK(hipGetLastError());
-    // values of all num_steps x num_envs stored observations (ppo.jl:128 evaluates the critic on the same observation the buffer keeps)
-    FusedFwdPCArgs q;
-    {
-      const NetOff o = net_off(256, w->D, 1);
-      const float* P = h->params + h->Pa;
-      const float* pk = w->pack + w->pk_base[1];
-      q.obs = h->obs; q.perm = nullptr; q.D = w->D; q.W1f = pk + w->pk[1].w1f; q.w1sc = w->wsc + 4 + 2; q.Wx2 = pk + w->pk[1].x2f; q.b2 = P + o.b2;
-      q.wsc = w->wsc + 2; q.W3t = pk + w->pk[1].w3t; q.b3 = P + o.b3; q.A = 1; q.ldz = 1; q.H1 = nullptr; q.H2 = nullptr; q.Z = h->value; q.M = h->dc.B;
+    case WideRolloutRoute::PC: {
+      RollPCArgs r;
+      r.n[0] = roll_pc_net(w->net[0], 1); r.n[1] = roll_pc_net(w->net[1], ratC); r.s = a; r.D = w->D;
+      if (w->D8 == 8) hipLaunchKernelGGL(wide_rollout_pc_kernel<8>, dim3(nt / RP_MB), dim3(512), RP_LDS, h->stream, r);
+      else hipLaunchKernelGGL(wide_rollout_pc_kernel<16>, dim3(nt / RP_MB), dim3(512), RP_LDS, h->stream, r);
+      break;
     }
-    if (!(opt(h, OPT_WIDE_RS) & 4) || w->D % 4 != 0 || w->lds_max < R2_LDS) {  // (bit 2: the same pass on the register-stationary forward instead — measured slower: 1.21 vs 0.87 ms at C3)
-      int nbc = w->cus; const int ntiles = h->dc.B / FX_MB; if (nbc > ntiles) nbc = ntiles;
-      if (w->D8 == 8) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<8, false, 2>), dim3(nbc, 1), dim3(512), pc_lds(2), h->stream, q, q);
-      else hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<16, false, 2>), dim3(nbc, 1), dim3(512), pc_lds(2), h->stream, q, q);
-    } else {
-      // register-stationary forward, every block on the critic: the grid's y = 0 half (the actor flavour) gets an empty argument and leaves at once
-      FusedFwdPCArgs q0 = q; q0.M = 0;
-      int nbc = w->cus; const int nt32 = h->dc.B / RS_MB; if (nbc > nt32) nbc = nt32;
-      if (w->D8 == 8) hipLaunchKernelGGL((wide_rs_fwd_kernel<8, 4, false>), dim3(nbc, 2), dim3(512), R2_LDS, h->stream, q0, q);
-      else hipLaunchKernelGGL((wide_rs_fwd_kernel<16, 4, false>), dim3(nbc, 2), dim3(512), R2_LDS, h->stream, q0, q);
+    case WideRolloutRoute::PERSIST: {
+      WRollArgs r;
+      for (int net = 0; net < 2; ++net) {
+        const WideNet& n = w->net[net];
+        r.fast[net] = net ? 1 - ratC : 0;
+        r.x[net] = dense_x3_fwd_args(h, n, nt, n.out, n.ldo, r.fast[net]);
+        r.W1[net] = n.W1; r.b1[net] = n.b1; r.h1[net] = n.h1;
+      }
+      r.s = a; r.D = w->D;
+      const size_t s0 = dense_x2_smem(r.x[0], 32), s1 = dense_x2_smem(r.x[1], 32);
+      r.obs_off = ((s0 > s1 ? s0 : s1) + 15) & ~(size_t)15;
+      hipLaunchKernelGGL(wide_rollout_persist_kernel, dim3((nt + 31) / 32), dim3(512), r.obs_off + (size_t)32 * w->D * 4, h->stream, r);
+      break;
     }
-    CRL_HIP_CHECK(hipGetLastError());
-    return 0;
+    case WideRolloutRoute::STEPWISE:
+      for (int step = 0; step < h->dc.k; ++step) {
+        if (wide_forward_pair(h, h->cur_obs, w->D, nt, w->z, w->A8, w->v, 1)) return 1;   // ppo.jl:127-128
+        a.step = step;
+        hipLaunchKernelGGL(wide_step_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, a);
+        CRL_HIP_CHECK(hipGetLastError());
+      }
+      break;
   }
-  if (w->H == 256 && wide_x2(h) && w->D <= 16 && w->A <= PC_AMAX && opt(h, OPT_WIDE_ROLLOUT_PERSIST) >= 2 && h->dc.nt % RP_MB == 0 && w->lds_max >= RP_LDS) {
-    // one launch for all steps, producer / consumer form (wide_rollout_pc_kernel)
-    RollPCArgs r;
-    const bool fast_ok = !opt(h, OPT_WIDE_TANH_RATIONAL);
-    for (int net = 0; net < 2; ++net) {
-      const int NO = net ? 1 : w->A;
-      const NetOff o = net_off(256, w->D, NO);
-      const float* P = h->params + (net ? h->Pa : 0);
-      const float* pk = w->pack + w->pk_base[net];
-      RollPCNet& n = r.n[net];
-      n.W1f = pk + w->pk[net].w1f; n.w1sc = w->wsc + 4 + 2 * net; n.Wx2 = pk + w->pk[net].x2f; n.b2 = P + o.b2; n.wsc = w->wsc + 2 * net;
-      n.W3t = pk + w->pk[net].w3t; n.b3 = P + o.b3; n.Z = net ? w->v : w->z; n.A = NO; n.ldz = net ? 1 : w->A8;
-      n.rat = (net == 1 && fast_ok) ? 0 : 1;            // the actor keeps tanh_fast: its logits decide bit-compared action indices
-    }
-    r.s = a; r.D = w->D;
-    const int nb = h->dc.nt / RP_MB;
-    if (w->D8 == 8) hipLaunchKernelGGL(wide_rollout_pc_kernel<8>, dim3(nb), dim3(512), RP_LDS, h->stream, r);
-    else hipLaunchKernelGGL(wide_rollout_pc_kernel<16>, dim3(nb), dim3(512), RP_LDS, h->stream, r);
-    CRL_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (w->H == 256 && wide_x2(h) && w->D <= 16 && opt(h, OPT_WIDE_ROLLOUT_PERSIST)) {   // one launch for all steps (wide_rollout_persist_kernel)
-    WRollArgs r;
-    const bool fast_ok = !opt(h, OPT_WIDE_TANH_RATIONAL);
-    for (int net = 0; net < 2; ++net) {
-      const int NO = net ? 1 : w->A;
-      const NetOff o = net_off(256, w->D, NO);
-      const float* P = h->params + (net ? h->Pa : 0);
-      const float* pk = w->pack + w->pk_base[net];
-      DenseX3Args& x = r.x[net];
-      x.Wx3 = pk + w->pk[net].x2f; x.X = w->h1[net]; x.K = 256; x.bias = P + o.b2; x.S = nullptr; x.Y = w->h2[net]; x.M = h->dc.nt;
-      x.W3t = pk + w->pk[net].w3t; x.b3 = P + o.b3; x.Z = net ? w->v : w->z; x.A = NO; x.ldz = net ? 1 : w->A8;
-      x.dZ = nullptr; x.ldd = 0; x.Ad = 0; x.bz = nullptr; x.bld = 0; x.bA = 0; x.wmax = nullptr;
-      x.fast_act = (net == 1 && fast_ok) ? 1 : 0;      // the actor keeps tanh_fast: its logits decide bit-compared action indices
-      x.wsc = w->wsc + 2 * net;
-      r.W1[net] = P + o.W1; r.b1[net] = P + o.b1; r.h1[net] = w->h1[net]; r.fast[net] = x.fast_act;
-    }
-    r.s = a; r.D = w->D;
-    const size_t s0 = dense_x2_smem(r.x[0], 32), s1 = dense_x2_smem(r.x[1], 32);
-    r.obs_off = ((s0 > s1 ? s0 : s1) + 15) & ~(size_t)15;
-    hipLaunchKernelGGL(wide_rollout_persist_kernel, dim3((h->dc.nt + 31) / 32), dim3(512), r.obs_off + (size_t)32 * w->D * 4, h->stream, r);
-    CRL_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  for (int step = 0; step < h->dc.k; ++step) {
-    if (wide_forward_pair(h, h->cur_obs, w->D, h->dc.nt, w->z, w->A8, w->v, 1)) return 1;   // ppo.jl:127-128
-    a.step = step;
-    hipLaunchKernelGGL(wide_step_kernel, dim3((h->dc.nt + 255) / 256), dim3(256), 0, h->stream, a);
-    CRL_HIP_CHECK(hipGetLastError());
-  }
+  CRL_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// backward of one network: head cotangent (K padded to 8, ld ldd) → all six parameter-gradient partials
-static int wide_backward(crl_ppo* h, int net, const float* dOut, int ldd, const int32_t* idx) {
+// backward of one network, layer by layer: head cotangent (n.dout, K padded to 8) → all six parameter-gradient partials
+static int wide_backward(crl_ppo* h, int net, const int32_t* idx) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
-  const int H = w->H, NO = net ? 1 : w->A, M = h->dc.M;
-  const NetOff o = net_off(H, w->D, NO);
-  (void)o;
-  const float* pk = w->pack + w->pk_base[net];
+  const WideNet& n = w->net[net];
+  const int H = w->H, M = h->dc.M;
   // δ2 = (W3ᵀ·δ3) ⊙ (1 − h2²) comes out of the dW3 sweep over h2 (wide_skinny_kernel<.., D2>) when the head has ≤ 8 outputs,
   // else it is its own K ≤ 16 MFMA launch. (Measured and dropped: forming δ2 on the fly inside its two consumers — update 76.4 vs
   // 70.2 ms per iteration at C3, the extra VALU work sits on those kernels' critical path.)
-  constexpr bool fuse2 = false;
-  const bool d2_sweep = NO <= 8;
+  const bool d2_sweep = n.NO <= 8;
   DenseArgs d;
   d.idx = nullptr; d.bias = nullptr; d.M = M;
-  if (!fuse2 && !d2_sweep) {
-    d.W = pk + w->pk[net].w3t; d.Kp = ldd; d.X = dOut; d.ldx = ldd; d.Kt = ldd; d.S = w->h2[net]; d.lds = H; d.Y = w->dA; d.ldy = H; d.Nt = H;
+  if (!d2_sweep) {
+    d.W = n.w3t; d.Kp = n.ldd; d.X = n.dout; d.ldx = n.ldd; d.Kt = n.ldd; d.S = n.h2; d.lds = H; d.Y = w->dA; d.ldy = H; d.Nt = H;
     if (dense_launch<EPI_DTANH>(h->stream, H, d)) return 1;
   }
-  // dW3[a, k] = Σ δ3[a]·h2[k]
-  SkinnyArgs s;
-  s.Big = w->h2[net]; s.H = H; s.Small = dOut; s.lds = ldd; s.idx = nullptr; s.M = M; s.chunk = w->chunks;
-  s.pW = w->pW3[net]; s.os_row = NO; s.os_s = 1; s.St = NO; s.wsize = H * NO; s.pB = nullptr;
-  s.D2out = d2_sweep ? w->dA : nullptr; s.W3t = pk + w->pk[net].w3t;
-  if (skinny_launch(h->stream, w->Ss, s)) return 1;
-  s.D2out = nullptr;
+  if (skinny_launch(h->stream, w->Ss, dw3_args(w, n, M, d2_sweep ? w->dA : nullptr))) return 1;
   // dW2 = δ2·h1ᵀ, db2 = Σ δ2
-  WgradArgs g;
-  g.dY = fuse2 ? w->h2[net] : w->dA; g.X = w->h1[net]; g.H = H; g.M = M; g.chunk = w->chunk2; g.pW = w->pW2[net]; g.pB = w->pB2[net];
-  g.dZ = fuse2 ? dOut : nullptr; g.ldd = ldd; g.Ad = NO; g.W3t = pk + w->pk[net].w3t;
-  g.bz = dOut; g.bld = ldd; g.bA = NO; g.wmax = pk + w->pk[net].wmax;
+  const WgradArgs g = wgrad_args(w, n, w->dA, n.h1, M);
   const bool x2 = H == 256 && wide_x2(h);
   if (x2) hipLaunchKernelGGL(wide_wgrad_x2_kernel<4>, dim3(w->S2, 2), dim3(512), 2 * (256 + 128) * X3ROW * 2, h->stream, g);
   else if (H == 256 && wide_x3(h))   // 256×128 output tiles (dY read twice, X once: 1.5 GB per launch at C3; 128×128 tiles read 2 GB)
@@ -2656,214 +2728,156 @@ static int wide_backward(crl_ppo* h, int net, const float* dOut, int ldd, const 
   // δ1 = (W2ᵀ·δ2) ⊙ (1 − h1²)
   if (H == 256 && wide_x3(h)) {
     DenseX3Args x;
-    x.Wx3 = pk + w->pk[net].x3b; x.X = fuse2 ? w->h2[net] : w->dA; x.K = H; x.bias = nullptr; x.S = w->h1[net]; x.Y = w->dB; x.M = M;
-    x.W3t = pk + w->pk[net].w3t; x.b3 = nullptr; x.Z = nullptr; x.A = 0; x.ldz = 0;
-    x.dZ = fuse2 ? dOut : nullptr; x.ldd = ldd; x.Ad = NO;
-    x.bz = dOut; x.bld = ldd; x.bA = NO; x.wmax = pk + w->pk[net].wmax;
-    if (x2) { x.Wx3 = pk + w->pk[net].x2b; x.wsc = w->wsc + 2 * net; if (dense_x2_launch<EPI_DTANH>(h->stream, x)) return 1; }
-    else if (dense_x3_launch<EPI_DTANH>(h->stream, x)) return 1;
+    x.Wx3 = x2 ? n.x2b : n.x3b; x.X = w->dA; x.K = H; x.bias = nullptr; x.S = n.h1; x.Y = w->dB; x.M = M;
+    x.W3t = n.w3t; x.b3 = nullptr; x.Z = nullptr; x.A = 0; x.ldz = 0;
+    x.dZ = nullptr; x.ldd = n.ldd; x.Ad = n.NO;
+    x.bz = n.dout; x.bld = n.ldd; x.bA = n.NO; x.wmax = n.wmax; x.wsc = n.wsc;
+    if (x2 ? dense_x2_launch<EPI_DTANH>(h->stream, x) : dense_x3_launch<EPI_DTANH>(h->stream, x)) return 1;
   } else {
-    d.W = pk + w->pk[net].w2t; d.Kp = H; d.X = w->dA; d.ldx = H; d.Kt = H; d.S = w->h1[net]; d.lds = H; d.Y = w->dB; d.ldy = H; d.Nt = H;
+    d.W = n.w2t; d.Kp = H; d.X = w->dA; d.ldx = H; d.Kt = H; d.S = n.h1; d.lds = H; d.Y = w->dB; d.ldy = H; d.Nt = H;
     if (dense_launch<EPI_DTANH>(h->stream, H, d)) return 1;
   }
   // dW1 = δ1·xᵀ, db1 = Σ δ1
-  s.Big = w->dB; s.Small = h->obs; s.lds = w->D; s.idx = idx; s.pW = w->pW1[net]; s.os_row = 1; s.os_s = H; s.St = w->D;
-  s.wsize = H * w->D; s.pB = w->pB1[net];
+  SkinnyArgs s;
+  s.Big = w->dB; s.H = H; s.Small = h->obs; s.lds = w->D; s.idx = idx; s.M = M; s.chunk = w->chunks;
+  s.pW = n.pW1; s.os_row = 1; s.os_s = H; s.St = w->D; s.wsize = H * w->D; s.pB = n.pB1; s.D2out = nullptr; s.W3t = n.w3t;
   return skinny_launch(h->stream, w->Ss, s);
 }
 
-// The update pass's forward of BOTH networks as one launch of the tile-resident kernel (wide_fused.hpp): 2x256, fp16x2, obs_dim <= 16,
-// exp2-based activation (what wide_forward(…, fast_act = true) computes layer by layer). Option wide_fuse = 0 keeps the layer-wise launches.
-static bool wide_fused_ok(const crl_ppo* h) {
-  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
-  return w->H == 256 && wide_x2(h) && w->D8 <= 16 && w->A <= AMAX && opt(h, OPT_WIDE_FUSE) != 0 && !opt(h, OPT_WIDE_TANH_RATIONAL) &&
-         w->lds_max >= FB_OFF_W3 + FB_AMAX * 1024;    // the largest request of the fused forward / backward / weight-gradient kernels
-}
-// h1 is never stored: the fused backward does not read it and the weight gradient regenerates it (option wide_fuse = 3, the default)
-static bool wide_h1_free(const crl_ppo* h) {
-  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
-  return opt(h, OPT_WIDE_FUSE) >= 3 && opt(h, OPT_WIDE_FUSE_PC) && w->A <= PC_AMAX && w->A <= FB_AMAX && w->D <= 16;
-}
-static int wide_forward_fused(crl_ppo* h, const int32_t* perm, int M) {
+// The update pass's forward of BOTH networks as one launch of a tile-resident kernel (wide_fused.hpp, wide_rs.hpp): rt.fwd != FWD_LAYERS
+static int wide_forward_fused(crl_ppo* h, const WideUpdateRoute& rt, const int32_t* perm, int M) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
-  FusedFwdArgs a[2];
-  for (int net = 0; net < 2; ++net) {
-    const int NO = net ? 1 : w->A;
-    const NetOff o = net_off(256, w->D, NO);
-    const float* P = h->params + (net ? h->Pa : 0);
-    const float* pk = w->pack + w->pk_base[net];
-    a[net].obs = h->obs; a[net].perm = perm; a[net].D = w->D;
-    a[net].W1s = pk + w->pk[net].w1s; a[net].Wx2 = pk + w->pk[net].x2f; a[net].b2 = P + o.b2; a[net].wsc = w->wsc + 2 * net;
-    a[net].W3t = pk + w->pk[net].w3t; a[net].b3 = P + o.b3; a[net].A = NO; a[net].ldz = net ? 1 : w->A8;
-    a[net].H1 = w->h1[net]; a[net].H2 = w->h2[net]; a[net].Z = net ? w->v : w->z; a[net].M = M;
-  }
-  if (opt(h, OPT_WIDE_FUSE_PC) && w->A <= PC_AMAX) {
-    // producer / consumer form, persistent: one block per CU, half of them per network
-    FusedFwdPCArgs q[2];
-    for (int net = 0; net < 2; ++net) {
-      const float* pk = w->pack + w->pk_base[net];
-      q[net].obs = a[net].obs; q[net].perm = perm; q[net].D = w->D; q[net].W1f = pk + w->pk[net].w1f; q[net].w1sc = w->wsc + 4 + 2 * net;
-      q[net].Wx2 = a[net].Wx2; q[net].b2 = a[net].b2; q[net].wsc = a[net].wsc; q[net].W3t = a[net].W3t; q[net].b3 = a[net].b3; q[net].A = a[net].A;
-      q[net].ldz = a[net].ldz; q[net].H1 = a[net].H1; q[net].H2 = a[net].H2; q[net].Z = a[net].Z; q[net].M = M;
-    }
-    if ((opt(h, OPT_WIDE_RS) & 1) && wide_h1_free(h) && M % RS_MB == 0 && w->D % 4 == 0 && w->lds_max >= R2_LDS) {
-      // register-stationary form (wide_rs.hpp): no weight stream at all
-      int nbr = w->cus / 2; const int nt32 = M / RS_MB; if (nbr > nt32) nbr = nt32; if (nbr < 1) nbr = 1;
-      if (w->D8 == 8 && w->A <= 4) hipLaunchKernelGGL((wide_rs_fwd_kernel<8, 4, true>), dim3(nbr, 2), dim3(512), R2_LDS, h->stream, q[0], q[1]);
-      else if (w->D8 == 8) hipLaunchKernelGGL((wide_rs_fwd_kernel<8, 8, true>), dim3(nbr, 2), dim3(512), R2_LDS, h->stream, q[0], q[1]);
-      else if (w->A <= 4) hipLaunchKernelGGL((wide_rs_fwd_kernel<16, 4, true>), dim3(nbr, 2), dim3(512), R2_LDS, h->stream, q[0], q[1]);
-      else hipLaunchKernelGGL((wide_rs_fwd_kernel<16, 8, true>), dim3(nbr, 2), dim3(512), R2_LDS, h->stream, q[0], q[1]);
-      CRL_HIP_CHECK(hipGetLastError());
-      return 0;
-    }
-    int nb = w->cus / 2; const int ntiles = M / FX_MB; if (nb > ntiles) nb = ntiles; if (nb < 1) nb = 1;
-    // three weight buffers (the slab after next in flight) where the W3ᵀ table leaves room for them, option wide_fwd_wbufs = 2 keeps two
-    const bool three = w->A <= pc_amax(3) && opt(h, OPT_WIDE_FWD_WBUFS) >= 3 && w->lds_max >= pc_lds(3);
-    const bool regs = opt(h, OPT_WIDE_FWD_WBUFS) == 0;      // weight fragments straight into the consumers' registers
+  if (rt.fwd != WideUpdateRoute::FWD_FUSED) {   // persistent: one block per CU, half of them per network
+    const WideNet &n0 = w->net[0], &n1 = w->net[1];
+    const FusedFwdPCArgs q0 = fused_fwd_pc_args(h, n0, perm, M, n0.h1, n0.h2, n0.out), q1 = fused_fwd_pc_args(h, n1, perm, M, n1.h1, n1.h2, n1.out);
+    const int tile = rt.fwd == WideUpdateRoute::FWD_RS ? RS_MB : FX_MB;
+    int nb = w->cus / 2; if (nb > M / tile) nb = M / tile; if (nb < 1) nb = 1;
 #define CRL_FWD_PC(dp, wh1)                                                                                                                      \
     do {                                                                                                                                           \
-      if (regs) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 0>), dim3(nb, 2), dim3(512), pc_lds(0), h->stream, q[0], q[1]);              \
-      else if (three) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 3>), dim3(nb, 2), dim3(512), pc_lds(3), h->stream, q[0], q[1]);        \
-      else hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 2>), dim3(nb, 2), dim3(512), pc_lds(2), h->stream, q[0], q[1]);                   \
+      if (rt.wbufs == 0) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 0>), dim3(nb, 2), dim3(512), pc_lds(0), h->stream, q0, q1);         \
+      else if (rt.wbufs == 3) hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 3>), dim3(nb, 2), dim3(512), pc_lds(3), h->stream, q0, q1);    \
+      else hipLaunchKernelGGL((wide_fused_fwd_pc_kernel<dp, wh1, 2>), dim3(nb, 2), dim3(512), pc_lds(2), h->stream, q0, q1);                       \
     } while (0)
-    if (wide_h1_free(h)) { if (w->D8 == 8) CRL_FWD_PC(8, false); else CRL_FWD_PC(16, false); }
+    if (rt.fwd == WideUpdateRoute::FWD_RS)
+      wide_dp_na(w, [&](auto dp, auto na) {
+        hipLaunchKernelGGL((wide_rs_fwd_kernel<decltype(dp)::value, decltype(na)::value, true>), dim3(nb, 2), dim3(512), R2_LDS, h->stream, q0, q1);
+      });
+    else if (rt.h1_free) { if (w->D8 == 8) CRL_FWD_PC(8, false); else CRL_FWD_PC(16, false); }
     else if (w->D8 == 8) CRL_FWD_PC(8, true);
     else CRL_FWD_PC(16, true);
 #undef CRL_FWD_PC
-    CRL_HIP_CHECK(hipGetLastError());
-    return 0;
+  } else {
+    FusedFwdArgs a[2];
+    for (int net = 0; net < 2; ++net) {
+      const WideNet& n = w->net[net];
+      a[net].obs = h->obs; a[net].perm = perm; a[net].D = w->D;
+      a[net].W1s = n.w1s; a[net].Wx2 = n.x2f; a[net].b2 = n.b2; a[net].wsc = n.wsc;
+      a[net].W3t = n.w3t; a[net].b3 = n.b3; a[net].A = n.NO; a[net].ldz = n.ldo;
+      a[net].H1 = n.h1; a[net].H2 = n.h2; a[net].Z = n.out; a[net].M = M;
+    }
+    const dim3 grid((M + FX_MB - 1) / FX_MB, 2);
+    if (w->D8 == 8) hipLaunchKernelGGL((wide_fused_fwd_kernel<8, true>), grid, dim3(512), FX_LDS, h->stream, a[0], a[1]);
+    else hipLaunchKernelGGL((wide_fused_fwd_kernel<16, true>), grid, dim3(512), FX_LDS, h->stream, a[0], a[1]);
   }
-  const dim3 grid((M + FX_MB - 1) / FX_MB, 2);
-  if (w->D8 == 8) hipLaunchKernelGGL((wide_fused_fwd_kernel<8, true>), grid, dim3(512), FX_LDS, h->stream, a[0], a[1]);
-  else hipLaunchKernelGGL((wide_fused_fwd_kernel<16, true>), grid, dim3(512), FX_LDS, h->stream, a[0], a[1]);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// Backward of BOTH networks: one launch of the tile-resident kernel (δ2 → dA / dB, dW1 / db1 partials), then per network the dW3 sweep over
-// h2 and the 256x256 weight-gradient kernel on the stored δ2 and h1.
-// the register-stationary backward with dW3 inside (wide_rs bits 3 + 4) will run for this minibatch: nothing is launched on the side stream
-static bool wide_rs_bwd_forms_dw3(const crl_ppo* h, int M) {
-  const WideWs* w = static_cast<const WideWs*>(h->wide_ws);
-  const bool split = wide_h1_free(h) && opt(h, OPT_WIDE_WGRAD_FULL) && opt(h, OPT_WIDE_D2_SPLIT) && w->chunk2 % 32 == 0 && w->lds_max >= WS_LDS;
-  return split && (opt(h, OPT_WIDE_RS) & 8) && (opt(h, OPT_WIDE_RS) & 16) && M % RS_MB == 0 && w->A <= 8 && w->D % 4 == 0 && w->lds_max >= RB_LDS;
-}
-static int wide_backward_fused(crl_ppo* h, const int32_t* perm, int M) {
+// Backward of BOTH networks (rt.bwd != BWD_LAYERS): one launch of a tile-resident kernel (δ2 → dA / dB, dW1 / db1 partials), then the dW3
+// sweeps over h2 unless that kernel formed dW3 itself, then the 256-wide weight gradient of rt.wgrad.
+static int wide_backward_fused(crl_ppo* h, const WideUpdateRoute& rt, const int32_t* perm, int M) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
-  const int ntiles = M / FX_MB;
-  // δ2 as the backward's own fp16x2 pieces when its only reader is the 256x256 weight-gradient kernel (whole 32-sample slabs: M % 128 == 0 here)
-  const bool split = wide_h1_free(h) && opt(h, OPT_WIDE_WGRAD_FULL) && opt(h, OPT_WIDE_D2_SPLIT) && w->chunk2 % 32 == 0 && w->lds_max >= WS_LDS;
-  int nb = w->cus / 2; if (nb > ntiles) nb = ntiles; if (nb > w->Ss) nb = w->Ss; if (nb < 1) nb = 1;
+  const bool dw3 = rt.bwd == WideUpdateRoute::BWD_RS_DW3, rsb = dw3 || rt.bwd == WideUpdateRoute::BWD_RS;
+  // The dW3 sweeps over h2 depend on the loss kernel only, like the backward kernel: they run on the second stream beside it. The fork
+  // sits behind the loss kernel (the last launch of the caller), the join at the end of this function.
+  if (rt.side_stream) CRL_HIP_CHECK(hipEventRecord(h->ev_fork, h->stream));
   FusedBwdArgs a[2];
   for (int net = 0; net < 2; ++net) {
-    const int NO = net ? 1 : w->A;
-    const float* pk = w->pack + w->pk_base[net];
-    a[net].H2 = w->h2[net]; a[net].dZ = net ? w->dv8 : w->z; a[net].ldd = net ? 8 : w->A8; a[net].A = NO;
-    a[net].W3t = pk + w->pk[net].w3t; a[net].wmax = pk + w->pk[net].wmax; a[net].Wx2b = pk + w->pk[net].x2b; a[net].wsc = w->wsc + 2 * net;
-    a[net].obs = h->obs; a[net].perm = perm; a[net].D = w->D; a[net].W1s = pk + w->pk[net].w1s;
-    a[net].D2 = net ? w->dB : w->dA; a[net].pW1 = w->pW1[net]; a[net].pB1 = w->pB1[net]; a[net].M = M;
-    a[net].D2h = split ? reinterpret_cast<_Float16*>(net ? w->dB : w->dA) : nullptr; a[net].d2s = split ? w->d2s + (size_t)net * w->Mw : nullptr;
+    const WideNet& n = w->net[net];
+    a[net].H2 = n.h2; a[net].dZ = n.dout; a[net].ldd = n.ldd; a[net].A = n.NO;
+    a[net].W3t = n.w3t; a[net].wmax = n.wmax; a[net].Wx2b = n.x2b; a[net].wsc = n.wsc;
+    a[net].obs = h->obs; a[net].perm = perm; a[net].D = w->D; a[net].W1s = n.w1s;
+    a[net].D2 = n.d2; a[net].pW1 = n.pW1; a[net].pB1 = n.pB1; a[net].M = M;
+    a[net].D2h = rt.split ? reinterpret_cast<_Float16*>(n.d2) : nullptr; a[net].d2s = rt.split ? n.d2s : nullptr;
+    if (rsb) { a[net].W1f = n.w1f; a[net].w1sc = n.w1sc; a[net].pW3 = n.pW3; }
   }
-  const size_t lds = (size_t)FB_OFF_W3 + (size_t)w->A * 1024;
-  const bool rsb = split && (opt(h, OPT_WIDE_RS) & 8) && M % RS_MB == 0 && w->A <= 8 && w->D % 4 == 0 && w->lds_max >= RB_LDS;
+  // persistent: one block per CU, half of them per network, each leaving one dW1 / db1 partial (at most Ss of them fit)
+  const int tile = rsb ? RS_MB : FX_MB;
+  int nb = w->cus / 2; if (nb > M / tile) nb = M / tile; if (nb > w->Ss) nb = w->Ss; if (nb < 1) nb = 1;
+  w->fb_blocks_net[0] = w->fb_blocks_net[1] = nb;
   if (rsb) {     // register-stationary form (wide_rs.hpp)
-    for (int net = 0; net < 2; ++net) { const float* pk = w->pack + w->pk_base[net]; a[net].W1f = pk + w->pk[net].w1f; a[net].w1sc = w->wsc + 4 + 2 * net; a[net].pW3 = w->pW3[net]; }
-    int nbr = w->cus / 2; const int nt32 = M / RS_MB; if (nbr > nt32) nbr = nt32; if (nbr > w->Ss) nbr = w->Ss; if (nbr < 1) nbr = 1;
-    nb = nbr;
-    w->fb_blocks_net[0] = w->fb_blocks_net[1] = nbr;
     const int pct = (int)opt(h, OPT_WIDE_RS_ACTOR_PCT);
-    if (pct != 50 && 2 * nbr == w->cus && w->cus <= 2 * w->Ss) {        // uneven split of the CUs: the grid's x extent is the larger share
+    if (pct != 50 && 2 * nb == w->cus && w->cus <= 2 * w->Ss) {        // uneven split of the CUs: the grid's x extent is the larger share
       int na = w->cus * pct / 100; if (na < 1) na = 1; if (na > w->cus - 1) na = w->cus - 1;
       if (na <= w->Ss && w->cus - na <= w->Ss) { a[0].nblk = na; a[1].nblk = w->cus - na; w->fb_blocks_net[0] = na; w->fb_blocks_net[1] = w->cus - na; nb = na > w->cus - na ? na : w->cus - na; }
     }
-    const bool dw3 = (opt(h, OPT_WIDE_RS) & 16) != 0;                 // dW3 inside the backward kernel instead of the two sweeps over h2
-#define CRL_RSB(dp, na)                                                                                                              \
-    do {                                                                                                                             \
-      if (dw3) hipLaunchKernelGGL((wide_rs_bwd_kernel<dp, na, true>), dim3(nb, 2), dim3(512), RB_LDS, h->stream, a[0], a[1]);        \
-      else hipLaunchKernelGGL((wide_rs_bwd_kernel<dp, na, false>), dim3(nb, 2), dim3(512), RB_LDS, h->stream, a[0], a[1]);           \
-    } while (0)
-    if (w->D8 == 8 && w->A <= 4) CRL_RSB(8, 4);
-    else if (w->D8 == 8) CRL_RSB(8, 8);
-    else if (w->A <= 4) CRL_RSB(16, 4);
-    else CRL_RSB(16, 8);
-#undef CRL_RSB
+    wide_dp_na(w, [&](auto dp, auto na) {
+      constexpr int DP = decltype(dp)::value, NA = decltype(na)::value;
+      if (dw3) hipLaunchKernelGGL((wide_rs_bwd_kernel<DP, NA, true>), dim3(nb, 2), dim3(512), RB_LDS, h->stream, a[0], a[1]);
+      else hipLaunchKernelGGL((wide_rs_bwd_kernel<DP, NA, false>), dim3(nb, 2), dim3(512), RB_LDS, h->stream, a[0], a[1]);
+    });
   } else {
-#define CRL_BWD(dp, na)                                                                                                                  \
-  do {                                                                                                                                   \
-    if (split) hipLaunchKernelGGL((wide_fused_bwd_kernel<dp, na, true>), dim3(nb, 2), dim3(512), lds, h->stream, a[0], a[1]);            \
-    else hipLaunchKernelGGL((wide_fused_bwd_kernel<dp, na, false>), dim3(nb, 2), dim3(512), lds, h->stream, a[0], a[1]);                 \
-  } while (0)
-  if (w->D8 == 8 && w->A <= 4) CRL_BWD(8, 4);
-  else if (w->D8 == 8) CRL_BWD(8, 8);
-  else if (w->A <= 4) CRL_BWD(16, 4);
-  else CRL_BWD(16, 8);
-#undef CRL_BWD
+    const size_t lds = (size_t)FB_OFF_W3 + (size_t)w->A * 1024;
+    wide_dp_na(w, [&](auto dp, auto na) {
+      constexpr int DP = decltype(dp)::value, NA = decltype(na)::value;
+      if (rt.split) hipLaunchKernelGGL((wide_fused_bwd_kernel<DP, NA, true>), dim3(nb, 2), dim3(512), lds, h->stream, a[0], a[1]);
+      else hipLaunchKernelGGL((wide_fused_bwd_kernel<DP, NA, false>), dim3(nb, 2), dim3(512), lds, h->stream, a[0], a[1]);
+    });
   }
   CRL_HIP_CHECK(hipGetLastError());
   w->fb_blocks = nb;
-  if (!rsb) w->fb_blocks_net[0] = w->fb_blocks_net[1] = nb;
-  const bool rsb_dw3 = rsb && (opt(h, OPT_WIDE_RS) & 16) != 0;
-  w->w3_blocks = rsb_dw3 ? 1 : 0;
-  // The dW3 sweeps over h2 depend on the loss kernel only, like the fused backward: they run on the second stream beside it and join at
-  // the end of this function.
-  const bool side = opt(h, OPT_SHUFFLE_OVERLAP) != 0 && !rsb_dw3;      // (nothing goes to the side stream when the backward kernel formed dW3 itself: no fork / join — 13 µs per step)
-  hipStream_t sk = side ? h->stream2 : h->stream;
-  if (side) CRL_HIP_CHECK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));   // ev_fork was recorded behind the loss kernel (wide_grad_passes)
-  for (int net = 0; net < 2; ++net) {
-    const int NO = net ? 1 : w->A;
-    const float* pk = w->pack + w->pk_base[net];
-    const float* dOut = net ? w->dv8 : w->z; const int ldd = net ? 8 : w->A8;
-    SkinnyArgs s;   // dW3[a, k] = Σ δ3[a]·h2[k]
-    s.Big = w->h2[net]; s.H = 256; s.Small = dOut; s.lds = ldd; s.idx = nullptr; s.M = M; s.chunk = w->chunks;
-    s.pW = w->pW3[net]; s.os_row = NO; s.os_s = 1; s.St = NO; s.wsize = 256 * NO; s.pB = nullptr; s.D2out = nullptr; s.W3t = pk + w->pk[net].w3t;
-    if (!rsb_dw3 && skinny_launch(sk, w->Ss, s)) return 1;
-    if (!wide_h1_free(h)) {
-      WgradArgs g;    // dW2 = δ2·h1ᵀ, db2 = Σ δ2 from the stored h1
-      g.dY = net ? w->dB : w->dA; g.X = w->h1[net]; g.H = 256; g.M = M; g.chunk = w->chunk2; g.pW = w->pW2[net]; g.pB = w->pB2[net];
-      g.dZ = nullptr; g.ldd = ldd; g.Ad = NO; g.W3t = pk + w->pk[net].w3t; g.bz = dOut; g.bld = ldd; g.bA = NO; g.wmax = pk + w->pk[net].wmax;
-      hipLaunchKernelGGL(wide_wgrad_x2_kernel<4>, dim3(w->S2, 2), dim3(512), 2 * (256 + 128) * X3ROW * 2, h->stream, g);
+  w->w3_blocks = dw3 ? 1 : 0;
+  hipStream_t sk = rt.side_stream ? h->stream2 : h->stream;
+  if (rt.side_stream) CRL_HIP_CHECK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
+  const size_t wgrad_x2_lds = 2 * (256 + 128) * X3ROW * 2;
+  for (const WideNet& n : w->net) {
+    if (!dw3 && skinny_launch(sk, w->Ss, dw3_args(w, n, M, nullptr))) return 1;
+    if (rt.wgrad == WideUpdateRoute::WGRAD_H1) {
+      const WgradArgs g = wgrad_args(w, n, n.d2, n.h1, M);
+      hipLaunchKernelGGL(wide_wgrad_x2_kernel<4>, dim3(w->S2, 2), dim3(512), wgrad_x2_lds, h->stream, g);
       CRL_HIP_CHECK(hipGetLastError());
     }
   }
-  if (wide_h1_free(h) && !opt(h, OPT_WIDE_WGRAD_FULL)) {
-    // h1 regenerated inside wide_wgrad_x2_kernel's own structure (256 x 128 tiles, two blocks per CU: the stream of δ2 hides under the other block)
-    for (int net = 0; net < 2; ++net) {
-      const float* pk = w->pack + w->pk_base[net];
-      WgradArgs g;
-      g.dY = net ? w->dB : w->dA; g.X = nullptr; g.H = 256; g.M = M; g.chunk = w->chunk2; g.pW = w->pW2[net]; g.pB = w->pB2[net];
-      g.dZ = nullptr; g.ldd = net ? 8 : w->A8; g.Ad = net ? 1 : w->A; g.W3t = pk + w->pk[net].w3t;
-      g.bz = net ? w->dv8 : w->z; g.bld = net ? 8 : w->A8; g.bA = net ? 1 : w->A; g.wmax = pk + w->pk[net].wmax;
-      g.obs = h->obs; g.perm = perm; g.D = w->D; g.W1f = pk + w->pk[net].w1f; g.w1sc = w->wsc + 4 + 2 * net;
-      hipLaunchKernelGGL((wide_wgrad_x2_kernel<4, true>), dim3(w->S2, 2), dim3(512), 2 * (256 + 128) * X3ROW * 2, h->stream, g);
-      CRL_HIP_CHECK(hipGetLastError());
+  switch (rt.wgrad) {
+    case WideUpdateRoute::WGRAD_H1: break;   // launched above, each behind its network's dW3 sweep
+    case WideUpdateRoute::WGRAD_GEN_128:
+      // h1 regenerated inside wide_wgrad_x2_kernel's own structure (256 x 128 tiles, two blocks per CU: the stream of δ2 hides under the other block)
+      for (const WideNet& n : w->net) {
+        WgradArgs g = wgrad_args(w, n, n.d2, nullptr, M);
+        g.obs = h->obs; g.perm = perm; g.D = w->D; g.W1f = n.w1f; g.w1sc = n.w1sc;
+        hipLaunchKernelGGL((wide_wgrad_x2_kernel<4, true>), dim3(w->S2, 2), dim3(512), wgrad_x2_lds, h->stream, g);
+      }
+      break;
+    case WideUpdateRoute::WGRAD_SPLIT: {
+      WgradSplitArgs g[2];
+      for (int net = 0; net < 2; ++net) {
+        const WideNet& n = w->net[net];
+        g[net].Yh = reinterpret_cast<const _Float16*>(n.d2); g[net].ys = n.d2s;
+        g[net].obs = h->obs; g[net].perm = perm; g[net].D = w->D; g[net].W1f = n.w1f; g[net].w1sc = n.w1sc;
+        g[net].pW = n.pW2; g[net].pB = n.pB2; g[net].M = M; g[net].chunk = w->chunk2;
+      }
+      if (w->D8 == 8) hipLaunchKernelGGL((wide_wgrad_split_kernel<8>), dim3(w->S2, 2), dim3(512), WS_LDS, h->stream, g[0], g[1]);
+      else hipLaunchKernelGGL((wide_wgrad_split_kernel<16>), dim3(w->S2, 2), dim3(512), WS_LDS, h->stream, g[0], g[1]);
+      break;
     }
-  } else if (split) {             // both networks in one launch, 256 x 256 tile per block, from the split planes (wide_wgrad_split_kernel)
-    WgradSplitArgs g[2];
-    for (int net = 0; net < 2; ++net) {
-      const float* pk = w->pack + w->pk_base[net];
-      g[net].Yh = reinterpret_cast<const _Float16*>(net ? w->dB : w->dA); g[net].ys = w->d2s + (size_t)net * w->Mw;
-      g[net].obs = h->obs; g[net].perm = perm; g[net].D = w->D; g[net].W1f = pk + w->pk[net].w1f; g[net].w1sc = w->wsc + 4 + 2 * net;
-      g[net].pW = w->pW2[net]; g[net].pB = w->pB2[net]; g[net].M = M; g[net].chunk = w->chunk2;
+    case WideUpdateRoute::WGRAD_GEN_256: {
+      WgradGenArgs g[2];
+      for (int net = 0; net < 2; ++net) {
+        const WideNet& n = w->net[net];
+        g[net].dY = n.d2; g[net].obs = h->obs; g[net].perm = perm; g[net].D = w->D; g[net].W1f = n.w1f; g[net].w1sc = n.w1sc;
+        g[net].bz = n.dout; g[net].bld = n.ldd; g[net].bA = n.NO; g[net].wmax = n.wmax;
+        g[net].pW = n.pW2; g[net].pB = n.pB2; g[net].M = M; g[net].chunk = w->chunk2;
+      }
+      if (w->D8 == 8) hipLaunchKernelGGL((wide_wgrad_gen_kernel<8>), dim3(w->S2, 2), dim3(512), WG_LDS, h->stream, g[0], g[1]);
+      else hipLaunchKernelGGL((wide_wgrad_gen_kernel<16>), dim3(w->S2, 2), dim3(512), WG_LDS, h->stream, g[0], g[1]);
+      break;
     }
-    if (w->D8 == 8) hipLaunchKernelGGL((wide_wgrad_split_kernel<8>), dim3(w->S2, 2), dim3(512), WS_LDS, h->stream, g[0], g[1]);
-    else hipLaunchKernelGGL((wide_wgrad_split_kernel<16>), dim3(w->S2, 2), dim3(512), WS_LDS, h->stream, g[0], g[1]);
-    CRL_HIP_CHECK(hipGetLastError());
-  } else if (wide_h1_free(h)) {   // both networks in one launch, 256 x 256 tile per block (wide_wgrad_gen_kernel)
-    WgradGenArgs g[2];
-    for (int net = 0; net < 2; ++net) {
-      const float* pk = w->pack + w->pk_base[net];
-      g[net].dY = net ? w->dB : w->dA; g[net].obs = h->obs; g[net].perm = perm; g[net].D = w->D; g[net].W1f = pk + w->pk[net].w1f; g[net].w1sc = w->wsc + 4 + 2 * net;
-      g[net].bz = net ? w->dv8 : w->z; g[net].bld = net ? 8 : w->A8; g[net].bA = net ? 1 : w->A; g[net].wmax = pk + w->pk[net].wmax;
-      g[net].pW = w->pW2[net]; g[net].pB = w->pB2[net]; g[net].M = M; g[net].chunk = w->chunk2;
-    }
-    if (w->D8 == 8) hipLaunchKernelGGL((wide_wgrad_gen_kernel<8>), dim3(w->S2, 2), dim3(512), WG_LDS, h->stream, g[0], g[1]);
-    else hipLaunchKernelGGL((wide_wgrad_gen_kernel<16>), dim3(w->S2, 2), dim3(512), WG_LDS, h->stream, g[0], g[1]);
-    CRL_HIP_CHECK(hipGetLastError());
   }
+  CRL_HIP_CHECK(hipGetLastError());
   // The dW3 partials are first read by the reduction that follows this function: the join sits behind the weight-gradient launches, so the
   // sweeps' blocks may fill the tails of BOTH big kernels (each of those owns every CU's registers while its blocks run; joined before the
   // weight gradient, the two sweeps took 2 x 480 µs on their stream against the backward's 764: the main stream waited for them)
-  if (side) { CRL_HIP_CHECK(hipEventRecord(h->ev_join, h->stream2)); CRL_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_join, 0)); }
+  if (rt.side_stream) { CRL_HIP_CHECK(hipEventRecord(h->ev_join, h->stream2)); CRL_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_join, 0)); }
   return 0;
 }
 
@@ -2871,8 +2885,9 @@ static int wide_backward_fused(crl_ppo* h, const int32_t* perm, int M) {
 static int wide_grad_passes(crl_ppo* h, int mb, const int32_t* perm, double Mglobal, bool dp) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
   const int M = h->dc.M;
-  if (wide_fused_ok(h) && M % FX_MB == 0) {
-    if (wide_forward_fused(h, perm, M)) return 1;
+  const WideUpdateRoute rt = wide_update_route(h, M);
+  if (rt.fwd != WideUpdateRoute::FWD_LAYERS) {
+    if (wide_forward_fused(h, rt, perm, M)) return 1;
   } else {
     if (wide_forward(h, 1, h->obs, w->D, perm, M, w->v, 1, true)) return 1;
     if (wide_forward(h, 0, h->obs, w->D, perm, M, w->z, w->A8, true)) return 1;
@@ -2910,13 +2925,9 @@ static int wide_grad_passes(crl_ppo* h, int mb, const int32_t* perm, double Mglo
     CRL_HIP_CHECK(hipGetLastError());
   }
   w->fb_blocks = 0; w->w3_blocks = 0;
-  if (wide_fused_ok(h) && M % FX_MB == 0 && w->A <= FB_AMAX && opt(h, OPT_WIDE_FUSE) >= 2) {
-    if (opt(h, OPT_SHUFFLE_OVERLAP) && !wide_rs_bwd_forms_dw3(h, M)) CRL_HIP_CHECK(hipEventRecord(h->ev_fork, h->stream));   // behind the loss kernel: the side stream starts here
-    return wide_backward_fused(h, perm, M);
-  }
-  if (wide_backward(h, 0, w->z, w->A8, perm)) return 1;
-  if (wide_backward(h, 1, w->dv8, 8, perm)) return 1;
-  return 0;
+  if (rt.bwd != WideUpdateRoute::BWD_LAYERS) return wide_backward_fused(h, rt, perm, M);   // (forks the side stream here, behind the loss kernel)
+  if (wide_backward(h, 0, perm)) return 1;
+  return wide_backward(h, 1, perm);
 }
 
 // One optimiser step's gradient (ppo.jl:197-244): forward → u → loss → backward → fixed-order reduce → [all-reduce] →
@@ -2944,11 +2955,11 @@ int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot) {
     for (int i = 0; i < 12; ++i) r.off[i + 1] = r.off[i] + sizes[i];
     for (int n = 0; n < 2; ++n) {
       const int b = 6 * n;
-      r.part[b + 0] = w->pW1[n]; r.nparts[b + 0] = w->fb_blocks ? w->fb_blocks_net[n] : w->Ss;
-      r.part[b + 1] = w->pB1[n]; r.nparts[b + 1] = w->fb_blocks ? w->fb_blocks_net[n] : w->Ss;
-      r.part[b + 2] = w->pW2[n]; r.nparts[b + 2] = w->S2;
-      r.part[b + 3] = w->pB2[n]; r.nparts[b + 3] = w->S2;
-      r.part[b + 4] = w->pW3[n]; r.nparts[b + 4] = w->w3_blocks ? w->fb_blocks_net[n] : w->Ss;
+      r.part[b + 0] = w->net[n].pW1; r.nparts[b + 0] = w->fb_blocks ? w->fb_blocks_net[n] : w->Ss;
+      r.part[b + 1] = w->net[n].pB1; r.nparts[b + 1] = w->fb_blocks ? w->fb_blocks_net[n] : w->Ss;
+      r.part[b + 2] = w->net[n].pW2; r.nparts[b + 2] = w->S2;
+      r.part[b + 3] = w->net[n].pB2; r.nparts[b + 3] = w->S2;
+      r.part[b + 4] = w->net[n].pW3; r.nparts[b + 4] = w->w3_blocks ? w->fb_blocks_net[n] : w->Ss;
       r.part[b + 5] = nullptr; r.nparts[b + 5] = 0;
     }
     r.lpart = w->lpart; r.nlb = w->nlb; r.out = h->comm_buf; r.P = P; r.A = A;

@@ -1,7 +1,8 @@
 """Parity of every route of the layer-wise ("wide") path against the CPU oracle, not only the default one. The shapes the library takes
-(obs 1..64, act 2..16, hidden 64 / 128 / 256) are split between kernels by a handful of predicates in wide.hip; each case below is
-sized to reach one of them. Same bars as test_gpu_wide.py / test_gpu_parity.py: actions, permutations, env fields bit-equal; float32
-results within RTOL = 1e-5 (rel_err / rel_err_s), losses by loss_close, gradients by _grad_close; whole iterations as test_wide_full_iteration_matches_oracle.
+(obs 1..64, act 2..16, hidden 64 / 128 / 256) are split between kernels by a handful of predicates in wide.hip — those of the rollout
+and of the update pass each written once, in wide_rollout_route and wide_update_route; each case below is sized to reach one of them.
+Same bars as test_gpu_wide.py / test_gpu_parity.py: actions, permutations, env fields bit-equal; float32 results within RTOL = 1e-5
+(rel_err / rel_err_s), losses by loss_close, gradients by _grad_close; whole iterations as test_wide_full_iteration_matches_oracle.
 
 | case                                   | kernels it reaches                                                  | predicate (wide.hip)                                        |
 |----------------------------------------|---------------------------------------------------------------------|-------------------------------------------------------------|
@@ -10,20 +11,20 @@ results within RTOL = 1e-5 (rel_err / rel_err_s), losses by loss_close, gradient
 |                                        | wide_dense_x3_kernel<EPI_DTANH, 1, 8>                               |                                                             |
 | wide_gemm = 0, hidden 256               | wide_dense_kernel<4, 2, 1, 1> for both 256x256 layers, wide_wgrad_  | !wide_x3: dense_launch(256), H >= 128 wgrad                 |
 |                                        | kernel<2>                                                           |                                                             |
-| wide_tanh_rational = 1                  | no fused kernel; tanh_fast in every layer (rollout kernels too)     | wide_fused_ok false; fast_act = 0 (wide_forward, rollout)   |
-| 2x256, 9..16 actions (12/16, 33/9,     | update: wide_fused_fwd_kernel<dp, true> (h1 stored), layer-wise     | wide_fused_ok (A <= AMAX = 16) but A > PC_AMAX = FB_AMAX = 8;|
-|  64/16)                                 | wide_backward with its own K = 16 δ2 launch and wide_wgrad_x2_kernel| d2_sweep = NO <= 8 false; rollout: A > PC_AMAX with D <= 16 |
-|                                        | over the stored h1; rollout: wide_rollout_persist_kernel (D <= 16)  | and wide_rollout_persist >= 1                               |
+| wide_tanh_rational = 1                  | no fused kernel; tanh_fast in every layer (rollout kernels too)     | wide_fused_ok false (both routes); fast_act = 0 (wide_forward)|
+| 2x256, 9..16 actions (12/16, 33/9,     | update: wide_fused_fwd_kernel<dp, true> (h1 stored), layer-wise     | wide_update_route: wide_fused_ok (A <= AMAX = 16) but A >    |
+|  64/16)                                 | wide_backward with its own K = 16 δ2 launch and wide_wgrad_x2_kernel| PC_AMAX = FB_AMAX = 8 (FWD_FUSED, BWD_LAYERS); d2_sweep = NO |
+|                                        | over the stored h1; rollout: wide_rollout_persist_kernel (D <= 16)  | <= 8 false; wide_rollout_route: A > PC_AMAX, D <= 16: PERSIST|
 | obs 17..64 at hidden 256 / 128          | generic layer 1 with K up to 64 behind the x2 layer 2; the non-prep | ensure_pack: D <= 16 false; wide_forward_pair per-net       |
 |                                        | branch of ensure_pack (wide_pack_kernel, wide_pack_x2_kernel)       | fallback only past M 32768 (else the pair kernels)          |
 | (5, 6, 256)                            | D % 4 != 0 with 4 < A <= 8: the fused producer / consumer kernels,  | wide_rs needs D % 4 == 0                                    |
 |                                        | not the register-stationary ones                                    |                                                             |
-| M % 128 != 0 (96, odd, < 32)           | the layer-wise update kernels behind a fused-shape network          | wide_fused_ok && M % FX_MB == 0 (wide_grad_passes)          |
+| M % 128 != 0 (96, odd, < 32)           | the layer-wise update kernels behind a fused-shape network          | wide_update_route: wide_fused_ok && M % FX_MB == 0          |
 | ragged M in (32768, 131072], wide_fuse 0| wide_dense_kernel<4, 2, 1, 2>, wide_dense_x2_kernel<EPI, 2>,        | dense_launch / dense_x2_launch / dense_x3_launch: M > 32768 |
 |                                        | wide_dense_x3_kernel<EPI, 2, 8>                                     |                                                             |
 | ragged M > 131072, wide_fuse 0          | wide_dense_x2_kernel<EPI, 4>                                        | dense_x2_launch: M > 131072                                 |
 | rollout at 33,000 envs, obs 33          | per-network wide_forward with the M > 32768 tiles                   | wide_forward_pair: M <= 32768 false                         |
-| wide_rollout_persist 2 / 1 / 0          | wide_rs_rollout_kernel / wide_rollout_pc_kernel (nt % 64 == 0),     | opt wide_rollout_persist, nt % RP_MB, A <= PC_AMAX          |
+| wide_rollout_persist 2 / 1 / 0          | wide_rs_rollout_kernel / wide_rollout_pc_kernel (nt % 64 == 0),     | wide_rollout_route: wide_rollout_persist, nt % RP_MB, A <= 8 |
 |                                        | wide_rollout_persist_kernel, wide_forward_pair + wide_step_kernel   |                                                             |
 """
 import numpy as np
