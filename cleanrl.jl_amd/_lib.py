@@ -50,6 +50,20 @@ class CrlIterationReport(C.Structure):
     _fields_ = [("iteration", C.c_int64), ("episodes", CrlEpisodeStats), ("n_episodes", C.c_int64), ("n_ring", C.c_int32), ("pad", C.c_int32)]
 
 
+class CrlEvalConfig(C.Structure):
+    """crl_eval_config: what crl_ppo_evaluate runs (mode: EVAL_GREEDY / EVAL_SAMPLE)."""
+    _fields_ = [("num_envs", C.c_int32), ("episodes_per_env", C.c_int32), ("mode", C.c_int32), ("trace_steps", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CrlEvalReport(C.Structure):
+    """crl_eval_report: Float64 summary of the per-episode arrays (population standard deviation; env_steps = sum of the lengths)."""
+    _fields_ = [("episodes", C.c_int64), ("env_steps", C.c_int64), ("return_mean", C.c_double), ("return_std", C.c_double),
+                ("return_min", C.c_double), ("return_max", C.c_double), ("length_mean", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/cleanrl_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "crl_version", "crl_last_error", "crl_device_count", "crl_ppo_create", "crl_ppo_destroy", "crl_ppo_param_count",
@@ -64,7 +78,7 @@ EXPORTS = [
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
-    "crl_env_step",
+    "crl_env_step", "crl_ppo_evaluate",
 ]
 
 DQN_PARAM_COUNT = 10934
@@ -111,6 +125,7 @@ F_OBS, F_ACTION, F_LOGPROB, F_REWARD, F_TERMINAL, F_VALUE, F_ADVANTAGE, F_RETURN
     F_ADAM_V, F_ENV_STATE, F_CUR_OBS, F_NEXT_DONE, F_ENV_T, F_BETAP, F_ADV_SUMS = range(19)
 GAE_COMPAT, GAE_FIXED = 0, 1
 ENV_CARTPOLE, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_MOUNTAINCAR, ENV_ACROBOT = 0, 1, 2, 3, 4
+EVAL_GREEDY, EVAL_SAMPLE = 0, 1
 SHUFFLE_FISHER_YATES, SHUFFLE_BIJECTION, SHUFFLE_BLOCKED_FY = 0, 1, 2
 K_ROLLOUT, K_GAE, K_SHUFFLE, K_ADV_STATS, K_UPDATE, K_REDUCE, K_OPTIM, K_ALLREDUCE, K_PACK, K_PERMUTE = range(10)
 KERNEL_NAMES = ["rollout", "gae", "shuffle", "adv_stats", "update", "reduce", "optim", "allreduce", "pack", "permute"]
@@ -145,6 +160,7 @@ def load():
     L.crl_env_reset.argtypes = [vp]
     L.crl_rollout_run.argtypes = [vp]
     L.crl_env_step.argtypes = [vp, ip, C.c_uint64, fp, fp, u8p]
+    L.crl_ppo_evaluate.argtypes = [vp, C.POINTER(CrlEvalConfig), C.POINTER(CrlEvalReport), fp, ip, ip]
     L.crl_episode_stats_read.argtypes = [vp, C.POINTER(CrlEpisodeStats)]
     L.crl_compute_gae.argtypes = [vp]
     L.crl_shuffle.argtypes = [vp, C.c_uint64]
@@ -359,6 +375,25 @@ class Handle:
         obs = np.zeros((self.d, self.nt), np.float32, order="F"); reward = np.zeros(self.nt, np.float32); done = np.zeros(self.nt, np.uint8)
         check(load().crl_env_step(self._h, _ptr(action, C.c_int32), int(gstep), _ptr(obs, C.c_float), _ptr(reward, C.c_float), _ptr(done, C.c_uint8)))
         return obs, reward, done
+
+    def evaluate(self, num_envs, episodes_per_env=1, mode=EVAL_GREEDY, seed=0, trace_steps=0, want_arrays=True):
+        """crl_ppo_evaluate: the current actor, frozen, on `num_envs` fresh private envs until each has finished `episodes_per_env` episodes (one
+        launch). Returns {"report": {...}, "returns": (episodes_per_env, num_envs) float32, "lengths": … int32[, "trace": (trace_steps, num_envs) int32,
+        -1 once an env had finished its quota]}; want_arrays=False passes NULL for the arrays and returns the report only."""
+        cfg = CrlEvalConfig(int(num_envs), int(episodes_per_env), int(mode), int(trace_steps), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        rep = CrlEvalReport()
+        shape = (max(cfg.episodes_per_env, 0), max(cfg.num_envs, 0))
+        ret = np.zeros(shape, np.float32) if want_arrays else None
+        length = np.zeros(shape, np.int32) if want_arrays else None
+        trace = np.zeros((cfg.trace_steps, max(cfg.num_envs, 0)), np.int32) if cfg.trace_steps > 0 else None
+        check(load().crl_ppo_evaluate(self._h, C.byref(cfg), C.byref(rep), None if ret is None else _ptr(ret, C.c_float),
+                                      None if length is None else _ptr(length, C.c_int32), None if trace is None else _ptr(trace, C.c_int32)))
+        out = {"report": rep.as_dict()}
+        if want_arrays:
+            out["returns"] = ret; out["lengths"] = length
+        if trace is not None:
+            out["trace"] = trace
+        return out
 
     def episode_stats(self):
         st = CrlEpisodeStats()

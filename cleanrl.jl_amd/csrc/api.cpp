@@ -364,7 +364,7 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
   void* ptrs[] = {h->obs, h->action, h->logprob, h->reward, h->terminal, h->value, h->adv, h->ret, h->env_state, h->env_t,
                   h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->next_value, h->ep_stats, h->ep_ring, h->ep_ring_count, h->params,
                   h->adam_m, h->adam_v, h->betap, h->optim_part, h->ticket, h->perm_base, h->recs, h->adv_part, h->perm_tmp, h->bfy_ws, h->bfy_adv_part, h->bfy_bucket_mb, h->bfy_mbid, h->bfy_dig1, h->gpart, h->lpart,
-                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage};
+                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int s = 0; s < 2; ++s) {
     if (h->status_dev[s]) (void)hipFree(h->status_dev[s]);
@@ -589,6 +589,65 @@ int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* n
   if (done) CRL_HIP_CHECK(hipMemcpyAsync(done, s + o_done, nt, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
   if (bad) { set_error("crl_env_step: an action is outside 0 … n_act - 1 (those envs were not stepped)"); return 1; }
+  return 0;
+}
+
+// Held-out evaluation (csrc/eval.hip): argument checks, scratch, ONE launch, the per-episode arrays back to the host, the report in Float64.
+int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report* report, float* returns, int32_t* lengths, int32_t* trace_action) {
+  CRL_GUARD_SETTLED(h);
+  if (!cfg || !report) { set_error("crl_ppo_evaluate: null cfg or report"); return 1; }
+  const int kind = h->cfg.env_kind;
+  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
+    set_error("crl_ppo_evaluate needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
+  }
+  if (cfg->num_envs < 1) { set_error("crl_ppo_evaluate: num_envs must be >= 1, got " + std::to_string(cfg->num_envs)); return 1; }
+  if (cfg->episodes_per_env < 1) { set_error("crl_ppo_evaluate: episodes_per_env must be >= 1, got " + std::to_string(cfg->episodes_per_env)); return 1; }
+  if (cfg->mode != CRL_EVAL_GREEDY && cfg->mode != CRL_EVAL_SAMPLE) { set_error("crl_ppo_evaluate: unknown mode " + std::to_string(cfg->mode)); return 1; }
+  if (cfg->trace_steps < 0) { set_error("crl_ppo_evaluate: trace_steps must be >= 0, got " + std::to_string(cfg->trace_steps)); return 1; }
+  if ((cfg->trace_steps > 0) != (trace_action != nullptr)) { set_error("crl_ppo_evaluate: trace_action must be given exactly when trace_steps > 0"); return 1; }
+  const int64_t n = cfg->num_envs, E = cfg->episodes_per_env, T = cfg->trace_steps;
+  if (n > (1 << 20) || E > 4096 || n * E > (1 << 24) || T * n > (1 << 26)) {
+    set_error("crl_ppo_evaluate: size past the cap (num_envs <= 1048576, episodes_per_env <= 4096, num_envs * episodes_per_env <= 16777216, "
+              "trace_steps * num_envs <= 67108864)");
+    return 1;
+  }
+  CRL_NEED_PARAMS(h, "crl_ppo_evaluate");
+  const size_t ne = (size_t)(n * E), o_ret = 0, o_len = o_ret + ne * 4, o_tr = o_len + ne * 4, total = o_tr + (size_t)(T * n) * 4;
+  if (h->eval_ws_bytes < total) {
+    CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (h->eval_ws) CRL_HIP_CHECK(hipFree(h->eval_ws));
+    h->eval_ws = nullptr; h->eval_ws_bytes = 0;
+    CRL_HIP_CHECK(hipMalloc(&h->eval_ws, total));
+    h->eval_ws_bytes = total;
+  }
+  char* ws = static_cast<char*>(h->eval_ws);
+  // every (episode, env) slot is written by the launch (the loop bound covers the longest quota); a slot that was not shows as length 0 below.
+  // Trace rows behind an env's last step — and behind the step a whole tile finished at — stay at -1.
+  CRL_HIP_CHECK(hipMemsetAsync(ws + o_ret, 0, 2 * ne * 4, h->stream));
+  if (T > 0) CRL_HIP_CHECK(hipMemsetAsync(ws + o_tr, 0xFF, (size_t)(T * n) * 4, h->stream));
+  if (launch_eval(h, cfg, (float*)(ws + o_ret), (int32_t*)(ws + o_len), T > 0 ? (int32_t*)(ws + o_tr) : nullptr)) return 1;
+  std::vector<float> ret(ne); std::vector<int32_t> len(ne);
+  CRL_HIP_CHECK(hipMemcpyAsync(ret.data(), ws + o_ret, ne * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(len.data(), ws + o_len, ne * 4, hipMemcpyDeviceToHost, h->stream));
+  if (T > 0) CRL_HIP_CHECK(hipMemcpyAsync(trace_action, ws + o_tr, (size_t)(T * n) * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  const int cap = eval_episode_cap(kind);
+  double rsum = 0.0, lsum = 0.0, rmin = (double)ret[0], rmax = (double)ret[0];
+  int64_t steps = 0;
+  for (size_t i = 0; i < ne; ++i) {
+    if (len[i] < 1 || len[i] > cap) { set_error("crl_ppo_evaluate: an episode did not end inside the step bound (length " + std::to_string(len[i]) + ")"); return 1; }
+    const double r = (double)ret[i];
+    rsum += r; lsum += (double)len[i]; steps += len[i];
+    rmin = r < rmin ? r : rmin; rmax = r > rmax ? r : rmax;
+  }
+  const double mean = rsum / (double)ne;
+  double var = 0.0;
+  for (size_t i = 0; i < ne; ++i) { const double d = (double)ret[i] - mean; var += d * d; }
+  report->episodes = (int64_t)ne; report->env_steps = steps;
+  report->return_mean = mean; report->return_std = std::sqrt(var / (double)ne); report->return_min = rmin; report->return_max = rmax;
+  report->length_mean = lsum / (double)ne;
+  if (returns) std::memcpy(returns, ret.data(), ne * 4);
+  if (lengths) std::memcpy(lengths, len.data(), ne * 4);
   return 0;
 }
 

@@ -170,6 +170,7 @@ struct crl_ppo {
   // staging for host-pointer calls
   void* stage = nullptr; size_t stage_bytes = 0;
   void* pinned = nullptr; size_t pinned_bytes = 0;
+  void* eval_ws = nullptr; size_t eval_ws_bytes = 0;   // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
   // Pipelined read-back (crl_ppo_iterate_async): what a logging host reads after every update — the loss records, the episode statistics, the per-episode ring,
   // the speculation flag and the error words — is gathered by ONE launch into a device slot at the end of an iteration, copied to pinned host memory on the
   // stream and fenced by an event; the host picks it up one iteration later, behind the next iteration's launches, so the GPU never waits for the host.
@@ -258,6 +259,9 @@ int launch_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot, bool inline_fix
 int launch_update_exact_dp(crl_ppo* h, int mb, crl_ppo_stats* stats_slot);
 int launch_optim(crl_ppo* h, double eta);
 int comm_allreduce(crl_ppo* h, void* buf, size_t count, bool is_double);
+// eval.hip — crl_ppo_evaluate's one launch
+int launch_eval(crl_ppo* h, const crl_eval_config* c, float* returns_d, int32_t* lengths_d, int32_t* trace_d);
+int eval_episode_cap(int kind);   // the longest episode of an env kind, in steps
 // wide.hip — layer-wise path for other network shapes
 bool wide_shape_ok(const crl_ppo_config* cfg, std::string* why);
 int wide_create(crl_ppo* h);

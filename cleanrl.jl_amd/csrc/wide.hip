@@ -21,6 +21,7 @@
 #include "env.hpp"
 #include "mlp_x2.hpp"
 #include "mlp_x3.hpp"
+#include "policy_rt.hpp"
 #include "ppo_ctx.hpp"
 #include "stats.hpp"
 
@@ -28,7 +29,6 @@ namespace crl {
 
 constexpr int WXS = 36;    // LDS stride (floats) of one staged sample row: 32 k + 4 pad → conflict-free ds_read_b128
 constexpr int WLS = 24;    // doubles per loss-kernel block partial: pg, Σ-entropy, Σ(v−R²), Σ value term, db3a[16], db3c
-constexpr int AMAX = 16;
 constexpr int AFUSE = 8;   // most head outputs the fused δ2 paths keep in registers (more ⇒ the separate launch)
 
 enum { EPI_TANH = 0, EPI_BIAS = 1, EPI_DTANH = 2, EPI_STORE = 3 };
@@ -1661,37 +1661,7 @@ static int skinny_launch(hipStream_t st, int blocks, const SkinnyArgs& a) {
 // Per-sample pieces shared by the act / logprob / loss kernels (runtime n_act ≤ 16, same operation order as
 // softmax_logsoftmax<A> and sample_weights<A> in common.hpp)
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void softmax_rt(const float (&z)[AMAX], int A, float (&p)[AMAX], float (&lp)[AMAX]) {
-  float m = z[0];
-#pragma unroll
-  for (int a = 1; a < AMAX; ++a) if (a < A) m = fmaxf(m, z[a]);
-  float s = 0.0f;
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) if (a < A) { p[a] = expf(z[a] - m); s += p[a]; }
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) if (a < A) p[a] = p[a] / s;
-  float ls = 0.0f;
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) if (a < A) { lp[a] = z[a] - m; ls += expf(lp[a]); }
-  const float l = logf(ls);
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) if (a < A) lp[a] = lp[a] - l;
-}
-__device__ __forceinline__ int sample_rt(const float (&p)[AMAX], int A, double u) {
-  float sw = 0.0f;
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) if (a < A) sw += p[a];
-  const double t = u * (double)sw;
-  int i = 0;
-  float cw = p[0];
-#pragma unroll
-  for (int a = 1; a < AMAX; ++a) {
-    const bool go = (a < A) && ((double)cw < t) && (i == a - 1);
-    i = go ? a : i;
-    cw = go ? cw + p[a] : cw;
-  }
-  return i;
-}
+// softmax_rt / sample_rt: policy_rt.hpp (shared with eval.hip)
 __device__ __forceinline__ float pick_rt(const float (&v)[AMAX], int A, int i) {
   float r = v[0];
 #pragma unroll

@@ -152,12 +152,50 @@ def _linear_eta(config, update, num_updates):
     return frac * float(np.float32(config.lr))
 
 
-def train(agent: Agent, num_updates=None, log_every=1, episode_records=0):
+EVAL_SEED = 0xE7A1    # default key of the evaluation envs: its own, so that a held-out score does not replay the training envs' initial states
+
+
+def _check_eval_args(num_envs, episodes_per_env, seed, trace_steps):
+    for name, v, lo in (("num_envs", num_envs, 1), ("episodes_per_env", episodes_per_env, 1), ("trace_steps", trace_steps, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"evaluate: {name} must be an integer, got {type(v).__name__}")
+        if v < lo:
+            raise ValueError(f"evaluate: {name} must be >= {lo}, got {v}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"evaluate: seed must be an integer in [0, 2^64), got {seed!r}")
+    if num_envs > 1 << 20 or episodes_per_env > 4096 or num_envs * episodes_per_env > 1 << 24 or trace_steps * num_envs > 1 << 26:
+        raise ValueError("evaluate: size past the cap (num_envs <= 1048576, episodes_per_env <= 4096, num_envs * episodes_per_env <= 16777216, "
+                         "trace_steps * num_envs <= 67108864)")
+
+
+def evaluate(agent, *, num_envs=256, episodes_per_env=1, greedy=True, seed=EVAL_SEED, trace_steps=0):
+    """How good is the current policy? crl_ppo_evaluate: the agent's actor, frozen, plays `episodes_per_env` whole episodes on each of `num_envs`
+    fresh envs of its kind, in one launch on the GPU (no reference counterpart: ppo.jl only logs the returns of its sampled training rollouts).
+    greedy=True takes the largest logit (lowest index on a tie), False samples like get_action (ppo.jl:21-32). Training state is not touched.
+    Returns {"report": {episodes, env_steps, return_mean, return_std, return_min, return_max, length_mean}, "returns", "lengths"} — the arrays
+    are (episodes_per_env, num_envs) — plus "trace" (trace_steps, num_envs), the actions of the first trace_steps steps, when trace_steps > 0.
+    Arguments are validated here, before the library is touched."""
+    _check_eval_args(num_envs, episodes_per_env, seed, trace_steps)
+    if not isinstance(greedy, (bool, np.bool_)):
+        raise TypeError(f"evaluate: greedy must be a bool, got {type(greedy).__name__}")
+    if not isinstance(agent, Agent):
+        raise TypeError("evaluate: agent must be a cleanrl_jl_amd Agent (PPO); A2C / DQN handles have no evaluation entry")
+    return agent.handle.evaluate(num_envs, episodes_per_env, L.EVAL_GREEDY if greedy else L.EVAL_SAMPLE, seed, trace_steps)
+
+
+def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_every=0, eval_envs=256, eval_episodes=1):
     """`train!`-style driver = the `for update in 1:num_updates` loop of ppo.jl:117-253, fully on device.
     Emits the reference's two records: "Episode Statistics" and "Training Statistics". By default the episode record is one
     aggregate per rollout (with 65536 envs the reference's one-record-per-episode is ~10^5 log lines per update);
     `episode_records=N` turns on the device ring (crl_episode_ring_enable) and logs up to N episodes per rollout one by one,
-    in the reference's order (step, then env; global_step as in ppo.jl:124,148)."""
+    in the reference's order (step, then env; global_step as in ppo.jl:124,148).
+    `eval_every=N > 0` adds an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_length_mean, global_step) after every N-th
+    update: a greedy crl_ppo_evaluate of the parameters that update left, on eval_envs fresh envs x eval_episodes episodes. 0 (default) keeps the
+    record stream what it was."""
+    if eval_every:
+        if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
+            raise ValueError(f"train: eval_every must be an integer >= 0, got {eval_every!r}")
+        _check_eval_args(eval_envs, eval_episodes, EVAL_SEED, 0)
     cfg = agent.config
     batch_size = cfg.num_steps * cfg.num_envs
     if num_updates is None:
@@ -200,10 +238,23 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0):
 
     # Pipelined read-back (crl_ppo_iterate_async): update k's records are picked up after update k + 1 has been enqueued, so the GPU never idles while the host
     # logs; the record stream is the same, one update late, and crl_ppo_drain hands over the last one.
-    for _ in range(num_updates):
+    def emit_eval(update):
+        # the evaluation reads the parameters update `update` (1-based) left: it runs behind that update on the stream, before the next one is enqueued
+        ev = h.evaluate(eval_envs, eval_episodes, L.EVAL_GREEDY, EVAL_SEED, 0, want_arrays=False)["report"]
+        log.info("Evaluation Statistics", extra={"crl": dict(
+            eval_return_mean=ev["return_mean"], eval_return_std=ev["return_std"], eval_length_mean=ev["length_mean"],
+            global_step=update * batch_size)})
+
+    for update in range(1, num_updates + 1):
         rep = h.iterate_async(want_stats=bool(log_every))
         if rep is not None:
             emit(rep)
+        if eval_every and update % eval_every == 0:
+            # keep the record order of the stream: update's own records first (they are one call late otherwise), then its evaluation
+            rep = h.drain(want_stats=bool(log_every))
+            if rep is not None:
+                emit(rep)
+            emit_eval(update)
     rep = h.drain(want_stats=bool(log_every))
     if rep is not None:
         emit(rep)
@@ -211,21 +262,21 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0):
 
 
 def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096, run_name="ppo-2-test",
-        logger_kw=None, env=None, **shape):
+        logger_kw=None, env=None, eval_every=0, eval_envs=256, eval_episodes=1, **shape):
     """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. `env="cartpole" | "mountaincar" |
     "acrobot"` is the one-line change of ppo.jl:82: obs_dim / n_act follow from it (ppo.jl:85-86). Like the Julia shell
     (julia/CleanRLHip.jl) it logs ONE "Episode Statistics" record per finished episode in the reference's order (ppo.jl:147-165), up
     to `episode_records` per rollout (the device ring's capacity; 0 = one aggregate record per update), and the 16 "Training
     Statistics" records of every update (ppo.jl:246-248). `logger_kw` goes to Logger.make_logger (logger.jl:7); `shape` keywords
     (obs_dim, n_act, hidden, env_kind, gae_mode, stale_obs, shuffle_mode) to the Agent — the reference derives them from the env
-    (ppo.jl:85-87)."""
+    (ppo.jl:85-87). `eval_every=N > 0`: an "Evaluation Statistics" record after every N-th update (see train / evaluate)."""
     from . import logger as _logger
     config = config or PPOConfig()
     shape = env_shape(env, **shape)      # ppo.jl:82,85-86 (an unknown env is a ValueError before anything is created)
     _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
     agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, **shape)
     try:
-        train(agent, episode_records=episode_records)
+        train(agent, episode_records=episode_records, eval_every=eval_every, eval_envs=eval_envs, eval_episodes=eval_episodes)
         return agent.get_params()
     finally:
         agent.close()

@@ -164,6 +164,30 @@ int32_t crl_rollout_run(crl_ppo* h);
  * terminated env shows its last or its fresh state); CRL_F_ENV_STATE / CRL_F_ENV_T / CRL_F_NEXT_DONE advance, the episode counters and statistics do
  * not. CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR and CRL_ENV_ACROBOT on both paths; an error for CRL_ENV_SYNTHETIC (stateless) and CRL_ENV_EXTERNAL. */
 int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done);
+/* Held-out evaluation of the current policy — no reference counterpart (ppo.jl only ever sees the returns of its training rollouts): the handle's
+ * actor, with frozen parameters, runs on a fresh, private set of cfg->num_envs on-device envs of the handle's env_kind until EVERY env has finished
+ * cfg->episodes_per_env episodes (the first N episodes of each env, not the first N to finish: short episodes are not over-represented), in ONE launch
+ * (csrc/eval.hip). The trajectory is the one a twin handle of the same shape with num_envs = cfg->num_envs, seed = cfg->seed, env_id_offset = 0 and
+ * stale_obs = 0 sees under crl_env_reset followed by crl_env_step(actions, gstep = g), g = 0, 1, 2, …, where the action of env e at step g comes from
+ * the actor's logits at the twin's CRL_F_CUR_OBS: CRL_EVAL_GREEDY = the lowest index of the largest logit; CRL_EVAL_SAMPLE = get_action's sampler
+ * (ppo.jl:21-32) on the uniform of Philox stream 0 of (cfg->seed, e, g) — the draw a training rollout takes at step g of iteration 0. An episode's
+ * return is the Float32 running sum of its rewards in step order (ppo.jl:145), its length its step count; an env that has finished its quota stops.
+ * returns / lengths: (episodes_per_env, num_envs), env fastest; either may be NULL. trace_action: (trace_steps, num_envs), the action taken at each of
+ * the first trace_steps steps, -1 once the env had finished its quota; NULL exactly when trace_steps = 0 (it exists so that tests can follow the
+ * device's trajectory). The report is computed on the host in Float64 from the per-episode arrays, sums in array order: return_std is the population
+ * standard deviation, env_steps = Σ lengths. Reads CRL_F_PARAMS and nothing else of the handle — rollout buffer, env state, CRL_F_CUR_OBS, episode
+ * statistics and ring, iteration counter, optimiser state, options, a pending crl_ppo_iterate_async report and the communicator stay as they are (under
+ * data parallelism every rank evaluates locally) — but, like every entry point that reads state, it first closes an open guard window, refuses a handle
+ * whose parameters were never set, and synchronises before it returns. Every episode ends by itself (CartPole after at most 501 steps — RLEnvs ends it
+ * at t > max_steps = 500 —, the other two after 200), so the launch is bounded by episodes_per_env times that. Errors: NULL cfg / report, num_envs or
+ * episodes_per_env < 1, unknown mode, trace_steps < 0 or without a trace_action, CRL_ENV_SYNTHETIC / CRL_ENV_EXTERNAL, and sizes past the caps:
+ * num_envs <= 1048576, episodes_per_env <= 4096, num_envs * episodes_per_env <= 16777216, trace_steps * num_envs <= 67108864. Device scratch is
+ * allocated on first use, kept on the handle and freed by crl_ppo_destroy. */
+#define CRL_EVAL_GREEDY 0
+#define CRL_EVAL_SAMPLE 1
+typedef struct crl_eval_config { int32_t num_envs, episodes_per_env, mode, trace_steps; uint64_t seed; } crl_eval_config;
+typedef struct crl_eval_report { int64_t episodes, env_steps; double return_mean, return_std, return_min, return_max, length_mean; } crl_eval_report;
+int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report* report, float* returns, int32_t* lengths, int32_t* trace_action);
 /* return_max is the largest return among the rollout's finished episodes, 0 when none finished. (CRL_ENV_CARTPOLE / CRL_ENV_SYNTHETIC keep their
  * historical max(0, ·): CartPole's returns are >= 0 anyway.) */
 int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out);

@@ -8,7 +8,7 @@
 module CleanRLHip
 
 export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!,
-       comm_destroy!, set_option!, get_option
+       comm_destroy!, set_option!, get_option, evaluate
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
 
@@ -53,6 +53,12 @@ struct CrlEpisodeRecord    # crl_episode_record: one per finished episode (ppo.j
 end
 struct CrlIterationReport  # crl_ppo_iteration_report: whose records crl_ppo_iterate_async / crl_ppo_drain handed back
   iteration::Int64; episodes::CrlEpisodeStats; n_episodes::Int64; n_ring::Int32; pad::Int32
+end
+struct CrlEvalConfig       # crl_eval_config: what crl_ppo_evaluate runs (mode 0 = greedy, 1 = sampled)
+  num_envs::Int32; episodes_per_env::Int32; mode::Int32; trace_steps::Int32; seed::UInt64
+end
+struct CrlEvalReport       # crl_eval_report: Float64 summary of the per-episode arrays (population standard deviation)
+  episodes::Int64; env_steps::Int64; return_mean::Float64; return_std::Float64; return_min::Float64; return_max::Float64; length_mean::Float64
 end
 
 check(rc::Int32) = rc == 0 || error(unsafe_string(ccall((:crl_last_error, libcrl), Cstring, ())))
@@ -217,10 +223,34 @@ function env_step!(a::Agent, action::Vector{Int32}, gstep::Integer=0)
                                                   a.h, action, UInt64(gstep), obs, reward, done))
   return obs, reward, done .!= 0
 end
+# How good is the current policy? crl_ppo_evaluate: the agent's actor, frozen, plays episodes_per_env whole episodes on each of num_envs fresh on-device
+# envs of its kind, in one launch; training state is not touched (no reference counterpart: ppo.jl only logs the returns of its sampled rollouts).
+# greedy = largest logit (lowest index on a tie), else get_action's sampler (ppo.jl:21-32). returns / lengths are (num_envs, episodes_per_env) —
+# the C arrays are env-fastest —, trace (num_envs, trace_steps) holds the 0-based actions of the first trace_steps steps, -1 once an env was done.
+const EVAL_SEED = UInt64(0xE7A1)
+function evaluate(a::Agent; num_envs::Integer=256, episodes_per_env::Integer=1, greedy::Bool=true, seed::Integer=EVAL_SEED, trace_steps::Integer=0)
+  num_envs >= 1 || throw(ArgumentError("evaluate: num_envs must be >= 1, got $num_envs"))
+  episodes_per_env >= 1 || throw(ArgumentError("evaluate: episodes_per_env must be >= 1, got $episodes_per_env"))
+  trace_steps >= 0 || throw(ArgumentError("evaluate: trace_steps must be >= 0, got $trace_steps"))
+  cfg = Ref(CrlEvalConfig(num_envs, episodes_per_env, greedy ? 0 : 1, trace_steps, UInt64(seed)))
+  report = Ref{CrlEvalReport}()
+  returns = Matrix{Float32}(undef, num_envs, episodes_per_env); lengths = Matrix{Int32}(undef, num_envs, episodes_per_env)
+  trace = Matrix{Int32}(undef, num_envs, trace_steps)
+  GC.@preserve returns lengths trace check(ccall((:crl_ppo_evaluate, libcrl), Int32,
+                                                 (Ptr{Cvoid}, Ref{CrlEvalConfig}, Ref{CrlEvalReport}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}),
+                                                 a.h, cfg, report, returns, lengths, trace_steps > 0 ? pointer(trace) : Ptr{Int32}(C_NULL)))
+  return (; report = report[], returns, lengths, trace)
+end
 function ppo(config::PPOConfig=PPOConfig(); device::Integer=0, params::Union{Nothing,Vector{Float32}}=nothing, init=_default_init(), init_seed::Integer=0,
              episode_records::Integer=4096, comm::Union{Nothing,Tuple{Vector{UInt8},Int,Int}}=nothing, run_name::AbstractString="ppo-2-test",
-             make_logger=_default_make_logger(), env::Union{Nothing,Symbol,AbstractString}=nothing, shape...)
+             make_logger=_default_make_logger(), env::Union{Nothing,Symbol,AbstractString}=nothing,
+             eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1, shape...)
   shape = env_shape(env; shape...)                                         # ppo.jl:82,85-86
+  eval_every >= 0 || throw(ArgumentError("ppo: eval_every must be >= 0, got $eval_every"))
+  if eval_every > 0                                                        # checked here, not at the first evaluation in the middle of training
+    eval_envs >= 1 || throw(ArgumentError("ppo: eval_envs must be >= 1, got $eval_envs"))
+    eval_episodes >= 1 || throw(ArgumentError("ppo: eval_episodes must be >= 1, got $eval_episodes"))
+  end
   make_logger === nothing || make_logger(run_name; to_terminal=false)      # ppo.jl:77
   world, rank = comm === nothing ? (1, 0) : (comm[2], comm[3])
   agent = Agent(config; device, env_id_offset=rank * config.num_envs, shape...)
@@ -273,10 +303,20 @@ function ppo(config::PPOConfig=PPOConfig(); device::Integer=0, params::Union{Not
     GC.@preserve stats recs check(ccall((:crl_ppo_iterate_async, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlIterationReport}, Ptr{CrlStats}, Ptr{CrlEpisodeRecord}, Int32),
                                         agent.h, rep, stats, recs, episode_records))
     rep[].iteration >= 0 && emit(rep[])
+    evaluating = eval_every > 0 && update % eval_every == 0
+    if evaluating || update == num_updates
+      # the update's own records, which would otherwise arrive one call late: after the last update, and in front of an evaluation, whose record
+      # follows them (the next crl_ppo_iterate_async then has nothing to hand over)
+      GC.@preserve stats recs check(ccall((:crl_ppo_drain, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlIterationReport}, Ptr{CrlStats}, Ptr{CrlEpisodeRecord}, Int32),
+                                          agent.h, rep, stats, recs, episode_records))
+      rep[].iteration >= 0 && emit(rep[])
+    end
+    if evaluating
+      # "Evaluation Statistics": a greedy held-out score of the parameters this update left (the call runs behind the update on the stream)
+      ev = evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report
+      @info "Evaluation Statistics" eval_return_mean = ev.return_mean eval_return_std = ev.return_std eval_length_mean = ev.length_mean global_step = update * batch_size
+    end
   end
-  GC.@preserve stats recs check(ccall((:crl_ppo_drain, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlIterationReport}, Ptr{CrlStats}, Ptr{CrlEpisodeRecord}, Int32),
-                                      agent.h, rep, stats, recs, episode_records))
-  rep[].iteration >= 0 && emit(rep[])
   agent
 end
 
