@@ -64,6 +64,18 @@ class CrlEvalReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CrlDiag(C.Structure):
+    """crl_ppo_diag: raw Float64 sums of crl_ppo_diagnose over the resident rollout buffer (shards add them field by field; min / max for ratio_*)
+    and the fields derived from them (entropy = policy entropy per sample = n_act x the reference's entropy_loss)."""
+    _fields_ = ([("n", C.c_int64), ("n_clipped", C.c_int64)] + [(n, C.c_double) for n in (
+        "sum_logratio", "sum_kl", "sum_entropy", "ratio_min", "ratio_max",
+        "sum_ret", "sum_ret2", "sum_res_old", "sum_res_old2", "sum_res_new", "sum_res_new2",
+        "old_approx_kl", "approx_kl", "clipfrac", "entropy", "explained_variance", "explained_variance_new")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/cleanrl_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "crl_version", "crl_last_error", "crl_device_count", "crl_ppo_create", "crl_ppo_destroy", "crl_ppo_param_count",
@@ -78,7 +90,7 @@ EXPORTS = [
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
-    "crl_env_step", "crl_ppo_evaluate",
+    "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
 ]
 
 DQN_PARAM_COUNT = 10934
@@ -161,6 +173,7 @@ def load():
     L.crl_rollout_run.argtypes = [vp]
     L.crl_env_step.argtypes = [vp, ip, C.c_uint64, fp, fp, u8p]
     L.crl_ppo_evaluate.argtypes = [vp, C.POINTER(CrlEvalConfig), C.POINTER(CrlEvalReport), fp, ip, ip]
+    L.crl_ppo_diagnose.argtypes = [vp, C.POINTER(CrlDiag), fp, fp]
     L.crl_episode_stats_read.argtypes = [vp, C.POINTER(CrlEpisodeStats)]
     L.crl_compute_gae.argtypes = [vp]
     L.crl_shuffle.argtypes = [vp, C.c_uint64]
@@ -393,6 +406,18 @@ class Handle:
             out["returns"] = ret; out["lengths"] = length
         if trace is not None:
             out["trace"] = trace
+        return out
+
+    def diagnose(self, per_sample=False):
+        """crl_ppo_diagnose: approx-KL, clip fraction, entropy and explained variance of the resident rollout buffer under the current parameters (one
+        read-only launch). Returns the struct's fields as a dict; per_sample=True adds "new_logprob" and "new_value", (num_envs, num_steps) float32."""
+        d = CrlDiag()
+        lp = np.zeros((self.nt, self.k), np.float32, order="F") if per_sample else None
+        v = np.zeros((self.nt, self.k), np.float32, order="F") if per_sample else None
+        check(load().crl_ppo_diagnose(self._h, C.byref(d), None if lp is None else _ptr(lp, C.c_float), None if v is None else _ptr(v, C.c_float)))
+        out = d.as_dict()
+        if per_sample:
+            out["new_logprob"] = lp; out["new_value"] = v
         return out
 
     def episode_stats(self):

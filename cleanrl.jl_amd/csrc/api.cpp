@@ -364,13 +364,14 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
   void* ptrs[] = {h->obs, h->action, h->logprob, h->reward, h->terminal, h->value, h->adv, h->ret, h->env_state, h->env_t,
                   h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->next_value, h->ep_stats, h->ep_ring, h->ep_ring_count, h->params,
                   h->adam_m, h->adam_v, h->betap, h->optim_part, h->ticket, h->perm_base, h->recs, h->adv_part, h->perm_tmp, h->bfy_ws, h->bfy_adv_part, h->bfy_bucket_mb, h->bfy_mbid, h->bfy_dig1, h->gpart, h->lpart,
-                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws};
+                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int s = 0; s < 2; ++s) {
     if (h->status_dev[s]) (void)hipFree(h->status_dev[s]);
     if (h->status_host[s]) (void)hipHostFree(h->status_host[s]);
     if (h->status_ev[s]) (void)hipEventDestroy(h->status_ev[s]);
   }
+  for (int s = 0; s < 2; ++s) if (h->diag_ev[s]) (void)hipEventDestroy(h->diag_ev[s]);
   for (int k = 0; k < CRL_K_COUNT; ++k)
     for (auto& pr : h->prof_slots[k].pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
@@ -649,6 +650,14 @@ int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report
   if (returns) std::memcpy(returns, ret.data(), ne * 4);
   if (lengths) std::memcpy(lengths, len.data(), ne * 4);
   return 0;
+}
+
+// Update diagnostics (csrc/diag.hip): ONE read-only launch over the resident buffer with the current parameters; the block records are added on the host.
+int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value) {
+  CRL_GUARD_SETTLED(h);
+  if (!out) { set_error("crl_ppo_diagnose: null out"); return 1; }
+  CRL_NEED_PARAMS(h, "crl_ppo_diagnose");
+  return launch_diag(h, out, new_logprob, new_value);
 }
 
 // CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT: the accumulator holds an order-preserving key of the true maximum (wide.hip: stat_max_key), 0 = no episode
@@ -1211,6 +1220,7 @@ int32_t crl_ppo_get_option(crl_ppo* h, const char* key, int64_t* value) {
     *value = re != 0.0 ? 1 : 0;
     return 0;
   }
+  if (key && std::strcmp(key, "diag_last_ns") == 0) { *value = h->diag_last_ns; return 0; }   // read-only: HIP-event time of the last crl_ppo_diagnose launch
   const bool dw_a = key && std::strcmp(key, "dw_scale_log2_actor") == 0, dw_c = key && std::strcmp(key, "dw_scale_log2_critic") == 0;
   if (dw_a || dw_c) {
     // read-only: the exponent of the weight-gradient scale G the next fp16x2 launch of that role will use (mlp_x2.hpp; a power of two).

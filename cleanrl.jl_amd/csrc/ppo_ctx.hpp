@@ -171,6 +171,8 @@ struct crl_ppo {
   void* stage = nullptr; size_t stage_bytes = 0;
   void* pinned = nullptr; size_t pinned_bytes = 0;
   void* eval_ws = nullptr; size_t eval_ws_bytes = 0;   // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
+  void* diag_ws = nullptr; size_t diag_ws_bytes = 0;   // crl_ppo_diagnose: per-block records | new_logprob | new_value (allocated on first use)
+  hipEvent_t diag_ev[2] = {nullptr, nullptr}; int64_t diag_last_ns = 0; int diag_cus = 0;   // events around its launch (read-only option diag_last_ns), CU count
   // Pipelined read-back (crl_ppo_iterate_async): what a logging host reads after every update — the loss records, the episode statistics, the per-episode ring,
   // the speculation flag and the error words — is gathered by ONE launch into a device slot at the end of an iteration, copied to pinned host memory on the
   // stream and fenced by an event; the host picks it up one iteration later, behind the next iteration's launches, so the GPU never waits for the host.
@@ -262,6 +264,8 @@ int comm_allreduce(crl_ppo* h, void* buf, size_t count, bool is_double);
 // eval.hip — crl_ppo_evaluate's one launch
 int launch_eval(crl_ppo* h, const crl_eval_config* c, float* returns_d, int32_t* lengths_d, int32_t* trace_d);
 int eval_episode_cap(int kind);   // the longest episode of an env kind, in steps
+// diag.hip — crl_ppo_diagnose's one launch and the report
+int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value);
 // wide.hip — layer-wise path for other network shapes
 bool wide_shape_ok(const crl_ppo_config* cfg, std::string* why);
 int wide_create(crl_ppo* h);

@@ -183,7 +183,20 @@ def evaluate(agent, *, num_envs=256, episodes_per_env=1, greedy=True, seed=EVAL_
     return agent.handle.evaluate(num_envs, episodes_per_env, L.EVAL_GREEDY if greedy else L.EVAL_SAMPLE, seed, trace_steps)
 
 
-def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_every=0, eval_envs=256, eval_episodes=1):
+def diagnose(agent, per_sample=False):
+    """Is the update healthy? crl_ppo_diagnose: one read-only launch over the rollout buffer the agent currently holds, with its current parameters
+    (after an update: the last rollout against the post-update policy; no reference counterpart). Returns the fields of crl_ppo_diag as a dict —
+    approx_kl, old_approx_kl, clipfrac, entropy (per sample: n_act x the reference's entropy_loss), explained_variance (stored values) and
+    explained_variance_new (current critic), ratio_min / ratio_max, n, n_clipped and the raw Float64 sums; per_sample=True adds "new_logprob" and
+    "new_value" as (num_envs, num_steps) arrays. Training state is not touched."""
+    if not isinstance(per_sample, (bool, np.bool_)):
+        raise TypeError(f"diagnose: per_sample must be a bool, got {type(per_sample).__name__}")
+    if not isinstance(agent, Agent):
+        raise TypeError("diagnose: agent must be a cleanrl_jl_amd Agent (PPO); A2C / DQN handles have no diagnostics entry")
+    return agent.handle.diagnose(bool(per_sample))
+
+
+def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_every=0, eval_envs=256, eval_episodes=1, diag_every=0):
     """`train!`-style driver = the `for update in 1:num_updates` loop of ppo.jl:117-253, fully on device.
     Emits the reference's two records: "Episode Statistics" and "Training Statistics". By default the episode record is one
     aggregate per rollout (with 65536 envs the reference's one-record-per-episode is ~10^5 log lines per update);
@@ -191,7 +204,12 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
     in the reference's order (step, then env; global_step as in ppo.jl:124,148).
     `eval_every=N > 0` adds an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_length_mean, global_step) after every N-th
     update: a greedy crl_ppo_evaluate of the parameters that update left, on eval_envs fresh envs x eval_episodes episodes. 0 (default) keeps the
-    record stream what it was."""
+    record stream what it was. `diag_every=N > 0` adds a "Policy Diagnostics" record (approx_kl, old_approx_kl, clipfrac, entropy, explained_variance,
+    global_step) after every N-th update: crl_ppo_diagnose of that update's rollout against the parameters it left; placed like the evaluation record
+    (in front of it when both fall on one update). 0 (default) keeps the record stream what it was."""
+    if diag_every:
+        if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
+            raise ValueError(f"train: diag_every must be an integer >= 0, got {diag_every!r}")
     if eval_every:
         if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
             raise ValueError(f"train: eval_every must be an integer >= 0, got {eval_every!r}")
@@ -245,16 +263,28 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
             eval_return_mean=ev["return_mean"], eval_return_std=ev["return_std"], eval_length_mean=ev["length_mean"],
             global_step=update * batch_size)})
 
+    def emit_diag(update):
+        # the buffer still holds update `update`'s rollout and the parameters are the ones it left: the next update has not been enqueued
+        d = h.diagnose()
+        log.info("Policy Diagnostics", extra={"crl": dict(
+            approx_kl=d["approx_kl"], old_approx_kl=d["old_approx_kl"], clipfrac=d["clipfrac"], entropy=d["entropy"],
+            explained_variance=d["explained_variance"], global_step=update * batch_size)})
+
     for update in range(1, num_updates + 1):
         rep = h.iterate_async(want_stats=bool(log_every))
         if rep is not None:
             emit(rep)
-        if eval_every and update % eval_every == 0:
-            # keep the record order of the stream: update's own records first (they are one call late otherwise), then its evaluation
+        evaluating = bool(eval_every) and update % eval_every == 0
+        diagnosing = bool(diag_every) and update % diag_every == 0
+        if evaluating or diagnosing:
+            # keep the record order of the stream: update's own records first (they are one call late otherwise), then its diagnostics and evaluation
             rep = h.drain(want_stats=bool(log_every))
             if rep is not None:
                 emit(rep)
-            emit_eval(update)
+            if diagnosing:
+                emit_diag(update)
+            if evaluating:
+                emit_eval(update)
     rep = h.drain(want_stats=bool(log_every))
     if rep is not None:
         emit(rep)
@@ -262,21 +292,24 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
 
 
 def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096, run_name="ppo-2-test",
-        logger_kw=None, env=None, eval_every=0, eval_envs=256, eval_episodes=1, **shape):
+        logger_kw=None, env=None, eval_every=0, eval_envs=256, eval_episodes=1, diag_every=0, **shape):
     """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. `env="cartpole" | "mountaincar" |
     "acrobot"` is the one-line change of ppo.jl:82: obs_dim / n_act follow from it (ppo.jl:85-86). Like the Julia shell
     (julia/CleanRLHip.jl) it logs ONE "Episode Statistics" record per finished episode in the reference's order (ppo.jl:147-165), up
     to `episode_records` per rollout (the device ring's capacity; 0 = one aggregate record per update), and the 16 "Training
     Statistics" records of every update (ppo.jl:246-248). `logger_kw` goes to Logger.make_logger (logger.jl:7); `shape` keywords
     (obs_dim, n_act, hidden, env_kind, gae_mode, stale_obs, shuffle_mode) to the Agent — the reference derives them from the env
-    (ppo.jl:85-87). `eval_every=N > 0`: an "Evaluation Statistics" record after every N-th update (see train / evaluate)."""
+    (ppo.jl:85-87). `eval_every=N > 0`: an "Evaluation Statistics" record after every N-th update (see train / evaluate);
+    `diag_every=N > 0`: a "Policy Diagnostics" record after every N-th update (see train / diagnose). Both are validated before a device is touched."""
+    if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
+        raise ValueError(f"ppo: diag_every must be an integer >= 0, got {diag_every!r}")
     from . import logger as _logger
     config = config or PPOConfig()
     shape = env_shape(env, **shape)      # ppo.jl:82,85-86 (an unknown env is a ValueError before anything is created)
     _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
     agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, **shape)
     try:
-        train(agent, episode_records=episode_records, eval_every=eval_every, eval_envs=eval_envs, eval_episodes=eval_episodes)
+        train(agent, episode_records=episode_records, eval_every=eval_every, eval_envs=eval_envs, eval_episodes=eval_episodes, diag_every=diag_every)
         return agent.get_params()
     finally:
         agent.close()

@@ -188,6 +188,39 @@ int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* n
 typedef struct crl_eval_config { int32_t num_envs, episodes_per_env, mode, trace_steps; uint64_t seed; } crl_eval_config;
 typedef struct crl_eval_report { int64_t episodes, env_steps; double return_mean, return_std, return_min, return_max, length_mean; } crl_eval_report;
 int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report* report, float* returns, int32_t* lengths, int32_t* trace_action);
+/* Diagnostics of the update — no reference counterpart (ppo.jl:247 logs its four losses and nothing else): approximate KL between the behaviour policy
+ * and the current one, clip fraction, policy entropy and the critic's explained variance, from ONE read-only, forward-only launch (csrc/diag.hip) over
+ * whatever the resident rollout buffer currently holds — CRL_F_OBS, CRL_F_ACTION, CRL_F_LOGPROB, CRL_F_VALUE, CRL_F_RETURN — with the handle's CURRENT
+ * CRL_F_PARAMS: after crl_ppo_iterate that is the last rollout against the post-update parameters; after crl_rollout_run + crl_compute_gae, the rollout
+ * against the parameters that drew it (approx_kl ≈ 0, clipfrac = 0). Per sample b (flat index e + num_envs * t): lp_new = logsoftmax(actor(obs_b))[action_b]
+ * (ppo.jl:34-45), H_b = Σ_a -p_a * log p_a from the Float32 elements of the reference's entropy matrix added in index order, v_new = critic(obs_b),
+ * logratio = lp_new - logprob_b as a Float32 difference (ppo.jl:224); from there on Float64: r = logratio, ratio = exp(r), kl_b = (ratio - 1) - r,
+ * clipped_b = |ratio - 1| > (double)clip_coef. The forward is the same for every handle: W2 as bf16x3 (24-bit operands) with Float32 accumulation, NNlib's
+ * rational tanh_fast; no option (gemm, wide_gemm, wide_*) changes a bit of the result. The raw sums are part of the struct so that data-parallel ranks (or
+ * the host) can add their shards' reports field by field (n, n_clipped and the sum_* fields; min / max of the ratio_* fields) and apply the formulas below;
+ * the call itself is local to the shard, like crl_ppo_evaluate. With mean(s) = s / n:
+ *   old_approx_kl = -sum_logratio / n          approx_kl = sum_kl / n          clipfrac = n_clipped / n
+ *   entropy = sum_entropy / n — the policy entropy PER SAMPLE: n_act times the reference's entropy_loss (crl_ppo_stats), which is the mean over all
+ *             n_act * n elements of the (n_act, B) matrix
+ *   explained_variance = 1 - Var(ret - value) / Var(ret), Var(x) = sum_x2 / n - (sum_x / n)^2 (population variances, sum_res_old* = Σ(ret - value),
+ *             Σ(ret - value)^2 in Float64); NaN when Var(ret) is not positive (constant returns)
+ *   explained_variance_new = the same with v_new in place of value (sum_res_new*)
+ * Every block of the launch adds its samples in Float64 and the host adds the blocks' records in block order: two calls on the same state return the
+ * same bits. new_logprob / new_value: (num_envs, num_steps) host arrays receiving lp_new / v_new, either may be NULL (they exist so that tests can
+ * locate a wrong tile; NULL = the launch stores nothing per sample). Works for every env_kind — CRL_ENV_EXTERNAL and CRL_ENV_SYNTHETIC included, no env
+ * is stepped — and both paths: obs 4 / act 2 / hidden 64 and every layer-wise shape (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256). Reads the buffer
+ * and CRL_F_PARAMS and changes nothing: env state, permutations, records, optimiser state, options, a pending crl_ppo_iterate_async report and the
+ * iteration counter stay as they are; like every entry point that reads state it first closes an open guard window, refuses a handle whose parameters
+ * were never set, and synchronises before it returns. Errors: NULL h or out. Device scratch (one record per block, the two per-sample arrays when asked
+ * for) is allocated on first use, kept on the handle and freed by crl_ppo_destroy. crl_ppo_get_option("diag_last_ns") (read-only) is the HIP-event time
+ * of the last call's launch. */
+typedef struct crl_ppo_diag {
+  int64_t n, n_clipped;
+  double sum_logratio, sum_kl, sum_entropy, ratio_min, ratio_max;
+  double sum_ret, sum_ret2, sum_res_old, sum_res_old2, sum_res_new, sum_res_new2;
+  double old_approx_kl, approx_kl, clipfrac, entropy, explained_variance, explained_variance_new;
+} crl_ppo_diag;
+int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value);
 /* return_max is the largest return among the rollout's finished episodes, 0 when none finished. (CRL_ENV_CARTPOLE / CRL_ENV_SYNTHETIC keep their
  * historical max(0, ·): CartPole's returns are >= 0 anyway.) */
 int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out);

@@ -8,7 +8,7 @@
 module CleanRLHip
 
 export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!,
-       comm_destroy!, set_option!, get_option, evaluate
+       comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
 
@@ -59,6 +59,12 @@ struct CrlEvalConfig       # crl_eval_config: what crl_ppo_evaluate runs (mode 0
 end
 struct CrlEvalReport       # crl_eval_report: Float64 summary of the per-episode arrays (population standard deviation)
   episodes::Int64; env_steps::Int64; return_mean::Float64; return_std::Float64; return_min::Float64; return_max::Float64; length_mean::Float64
+end
+struct CrlDiag             # crl_ppo_diag: raw Float64 sums of crl_ppo_diagnose and the fields derived from them (entropy: per sample = n_act x entropy_loss)
+  n::Int64; n_clipped::Int64
+  sum_logratio::Float64; sum_kl::Float64; sum_entropy::Float64; ratio_min::Float64; ratio_max::Float64
+  sum_ret::Float64; sum_ret2::Float64; sum_res_old::Float64; sum_res_old2::Float64; sum_res_new::Float64; sum_res_new2::Float64
+  old_approx_kl::Float64; approx_kl::Float64; clipfrac::Float64; entropy::Float64; explained_variance::Float64; explained_variance_new::Float64
 end
 
 check(rc::Int32) = rc == 0 || error(unsafe_string(ccall((:crl_last_error, libcrl), Cstring, ())))
@@ -240,6 +246,17 @@ function evaluate(a::Agent; num_envs::Integer=256, episodes_per_env::Integer=1, 
                                                  (Ptr{Cvoid}, Ref{CrlEvalConfig}, Ref{CrlEvalReport}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}),
                                                  a.h, cfg, report, returns, lengths, trace_steps > 0 ? pointer(trace) : Ptr{Int32}(C_NULL)))
   return (; report = report[], returns, lengths, trace)
+end
+# Is the update healthy? crl_ppo_diagnose: one read-only launch over the rollout buffer the agent currently holds, with its current parameters (after an
+# update: the last rollout against the post-update policy; no reference counterpart). Returns the CrlDiag struct: approx_kl, old_approx_kl, clipfrac,
+# entropy, explained_variance, explained_variance_new, the ratio's range and the raw sums. per_sample = true also returns new_logprob / new_value (num_envs, num_steps).
+function diagnose(a::Agent; per_sample::Bool=false)
+  out = Ref{CrlDiag}()
+  nt, k = Int(a.config.num_envs), Int(a.config.num_steps)
+  lp = Matrix{Float32}(undef, per_sample ? nt : 0, per_sample ? k : 0); v = similar(lp)
+  GC.@preserve lp v check(ccall((:crl_ppo_diagnose, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlDiag}, Ptr{Float32}, Ptr{Float32}),
+                                a.h, out, per_sample ? pointer(lp) : Ptr{Float32}(C_NULL), per_sample ? pointer(v) : Ptr{Float32}(C_NULL)))
+  return per_sample ? (; report = out[], new_logprob = lp, new_value = v) : out[]
 end
 function ppo(config::PPOConfig=PPOConfig(); device::Integer=0, params::Union{Nothing,Vector{Float32}}=nothing, init=_default_init(), init_seed::Integer=0,
              episode_records::Integer=4096, comm::Union{Nothing,Tuple{Vector{UInt8},Int,Int}}=nothing, run_name::AbstractString="ppo-2-test",

@@ -5,6 +5,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ppo --num_envs 4096 --num_steps 128 --total_timesteps 10485760
     python scripts/run.py ppo --env acrobot --hidden 256 --num_envs 256 --num_steps 128      (--env cartpole | mountaincar | acrobot: ppo.jl:82)
     python scripts/run.py ppo --env acrobot --eval_every 10 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": a greedy held-out score every 10 updates)
+    python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
 """
@@ -23,8 +24,8 @@ def main():
     algo, argv = sys.argv[1], sys.argv[2:]
     if algo == "ppo":
         kw = {}
-        # not PPOConfig fields: the env of ppo.jl:82, the width of networks.jl:36 and the evaluation cadence (crl_ppo_evaluate)
-        for flag, cast in (("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)):
+        # not PPOConfig fields: the env of ppo.jl:82, the width of networks.jl:36 and the evaluation / diagnostics cadence (crl_ppo_evaluate, crl_ppo_diagnose)
+        for flag, cast in (("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int), ("--diag_every", int)):
             if flag in argv:
                 i = argv.index(flag)
                 if i + 1 >= len(argv):
