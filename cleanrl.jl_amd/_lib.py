@@ -91,6 +91,7 @@ EXPORTS = [
     "crl_dqn_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
+    "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
 ]
 
 DQN_PARAM_COUNT = 10934
@@ -226,6 +227,12 @@ def load():
     L.crl_clock_probe.argtypes = [C.c_int32, C.c_double, dp, dp, dp]
     L.crl_ppo_iterate_async.argtypes = [vp, C.POINTER(CrlIterationReport), C.POINTER(CrlStats), C.POINTER(CrlEpisodeRecord), C.c_int32]
     L.crl_ppo_drain.argtypes = [vp, C.POINTER(CrlIterationReport), C.POINTER(CrlStats), C.POINTER(CrlEpisodeRecord), C.c_int32]
+    # device-pointer path: addresses travel as plain integers (devptr() below), never as host arrays
+    L.crl_ppo_stream.argtypes = [vp, C.POINTER(vp)]
+    L.crl_rollout_act_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    L.crl_rollout_record_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    L.crl_env_step_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.crl_ppo_update.argtypes = [vp, C.POINTER(CrlStats)]
     L.crl_product_probe.argtypes = [C.c_int32, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp]
     for name in EXPORTS:
         if name not in ("crl_version", "crl_last_error"):
@@ -247,6 +254,85 @@ def device_count():
 
 def _ptr(a, ct):
     return a.ctypes.data_as(C.POINTER(ct))
+
+
+def devptr(x, what="pointer", optional=False):
+    """The device address behind a pointer argument of the device-pointer calls: an int address or any object with data_ptr() (a torch tensor) —
+    nothing else (a numpy array is HOST memory). 0 / None is a ValueError unless `optional`; raised before the library is touched."""
+    if x is None or (isinstance(x, int) and not isinstance(x, bool) and x == 0):
+        if optional:
+            return None
+        raise ValueError(f"{what}: a device pointer is required, got {x!r}")
+    if isinstance(x, bool) or not (isinstance(x, int) or hasattr(x, "data_ptr")):
+        raise TypeError(f"{what}: an int device address or an object with data_ptr() is expected, got {type(x).__name__}")
+    a = x if isinstance(x, int) else int(x.data_ptr())
+    if a <= 0 or a >= 1 << 64:
+        raise ValueError(f"{what}: {a:#x} is not a device address")
+    return a
+
+
+_hip = None
+
+
+def hip_runtime():
+    """libamdhip64 through ctypes (hipMalloc / hipFree / hipMemcpy / hipMemset / hipSetDevice): by name, else through libcleanrl_hip.so, which links it."""
+    global _hip
+    if _hip is None:
+        load()
+        try:
+            R = C.CDLL("libamdhip64.so")
+        except OSError:
+            R = C.CDLL(LIB_PATH)
+        R.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        R.hipFree.argtypes = [C.c_void_p]
+        R.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        R.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        R.hipSetDevice.argtypes = [C.c_int]
+        R.hipGetErrorString.argtypes = [C.c_int]; R.hipGetErrorString.restype = C.c_char_p
+        _hip = R
+    return _hip
+
+
+class DeviceBuffer:
+    """`nbytes` of device memory from hipMalloc, zeroed; data_ptr() makes it a pointer argument of the device-pointer calls. read() / write() are
+    synchronous hipMemcpy (tests and set-up only — nothing on the stepping path uses them)."""
+
+    def __init__(self, nbytes, device=0):
+        self._R = hip_runtime()
+        self.nbytes, self.device = int(nbytes), device
+        self._p = C.c_void_p()
+        self._ok(self._R.hipSetDevice(device))
+        self._ok(self._R.hipMalloc(C.byref(self._p), max(self.nbytes, 1)))
+        self._ok(self._R.hipMemset(self._p, 0, max(self.nbytes, 1)))
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise CrlError("HIP runtime: " + self._R.hipGetErrorString(rc).decode("utf-8", "replace"))
+
+    def data_ptr(self):
+        return self._p.value or 0
+
+    def write(self, arr):
+        a = np.ascontiguousarray(arr) if not arr.flags.f_contiguous else arr
+        if a.nbytes != self.nbytes:
+            raise ValueError(f"DeviceBuffer.write: {self.nbytes} bytes expected, got {a.nbytes}")
+        self._ok(self._R.hipMemcpy(self._p, a.ctypes.data_as(C.c_void_p), a.nbytes, 1))
+
+    def read(self, dtype, shape=None, order="F"):
+        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize if shape is None else shape, dtype, order=order)
+        self._ok(self._R.hipMemcpy(out.ctypes.data_as(C.c_void_p), self._p, out.nbytes, 2))
+        return out
+
+    def close(self):
+        if self._p.value:
+            self._R.hipFree(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def product_probe(flavour, A, B, chunks=1, scale_a=1.0, scale_b=1.0, col_scale=None, device=0):
@@ -310,6 +396,7 @@ class Handle:
         check(load().crl_ppo_param_count(self._h, C.byref(n)))
         self.P = n.value
         self.nt, self.k, self.d, self.A = cfg.num_envs, cfg.num_steps, cfg.obs_dim, cfg.n_act
+        self.device = device
         self.B = self.nt * self.k
 
     def close(self):
@@ -388,6 +475,39 @@ class Handle:
         obs = np.zeros((self.d, self.nt), np.float32, order="F"); reward = np.zeros(self.nt, np.float32); done = np.zeros(self.nt, np.uint8)
         check(load().crl_env_step(self._h, _ptr(action, C.c_int32), int(gstep), _ptr(obs, C.c_float), _ptr(reward, C.c_float), _ptr(done, C.c_uint8)))
         return obs, reward, done
+
+    # ---- device-resident external envs: every pointer is an int device address or an object with data_ptr(); no call below synchronises the host
+    @property
+    def stream(self):
+        """crl_ppo_stream: the handle's hipStream_t as an int (e.g. for torch.cuda.ExternalStream)."""
+        s = C.c_void_p()
+        check(load().crl_ppo_stream(self._h, C.byref(s)))
+        return s.value or 0
+
+    def act_device(self, step, obs, done, action, peer_stream=None):
+        """crl_rollout_act_device: ppo.jl:127-128 + the policy's share of Buffer.add! for slot `step`, one launch; the sampled 0-based actions land in `action`."""
+        o, d, a = devptr(obs, "act_device: obs"), devptr(done, "act_device: done"), devptr(action, "act_device: action")
+        ps = devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_rollout_act_device(self._h, int(step), o, d, a, ps))
+
+    def record_device(self, step, reward, next_obs, next_done, peer_stream=None):
+        """crl_rollout_record_device: ppo.jl:132,137,143-165 — reward into slot `step`, next_obs / next_done, episode bookkeeping."""
+        r, o, d = devptr(reward, "record_device: reward"), devptr(next_obs, "record_device: next_obs"), devptr(next_done, "record_device: next_done")
+        ps = devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_rollout_record_device(self._h, int(step), r, o, d, ps))
+
+    def env_step_device(self, action, gstep, next_obs, reward, done, peer_stream=None):
+        """crl_env_step_device: crl_env_step on device pointers (next_obs may be None: CRL_F_CUR_OBS holds it); a bad action surfaces at the next sync()."""
+        a, r, d = devptr(action, "env_step_device: action"), devptr(reward, "env_step_device: reward"), devptr(done, "env_step_device: done")
+        o, ps = devptr(next_obs, "env_step_device: next_obs", optional=True), devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_env_step_device(self._h, a, int(gstep), o, r, d, ps))
+
+    def update(self, want_stats=True):
+        """crl_ppo_update: ppo.jl:168-253 on the resident buffer (the update half of iterate)."""
+        n = self.cfg.update_epochs * self.cfg.num_minibatches
+        arr = (CrlStats * n)()
+        check(load().crl_ppo_update(self._h, arr if want_stats else None))
+        return [a.as_dict() for a in arr] if want_stats else None
 
     def evaluate(self, num_envs, episodes_per_env=1, mode=EVAL_GREEDY, seed=0, trace_steps=0, want_arrays=True):
         """crl_ppo_evaluate: the current actor, frozen, on `num_envs` fresh private envs until each has finished `episodes_per_env` episodes (one

@@ -303,7 +303,7 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   rc |= dalloc(&h->terminal, B); rc |= dalloc(&h->value, B); rc |= dalloc(&h->adv, B); rc |= dalloc(&h->ret, B);
   rc |= dalloc(&h->env_state, nt * d); rc |= dalloc(&h->env_t, nt); rc |= dalloc(&h->cur_obs, nt * d);
   rc |= dalloc(&h->next_done, nt); rc |= dalloc(&h->ep_return, nt); rc |= dalloc(&h->ep_length, nt);
-  rc |= dalloc(&h->next_value, nt); rc |= dalloc(&h->ep_stats, 4);
+  rc |= dalloc(&h->next_value, nt); rc |= dalloc(&h->ep_stats, 4); rc |= dalloc(&h->ext_bad, 1);
   rc |= dalloc(&h->params, h->P); rc |= dalloc(&h->adam_m, h->P); rc |= dalloc(&h->adam_v, h->P);
   const size_t E = (size_t)cfg->update_epochs;
   rc |= dalloc(&h->betap, 24); rc |= dalloc(&h->perm_base, E * B); rc |= dalloc(&h->optim_part, (size_t)h->P / 4096 + 16 + 12 * ((size_t)h->P / 64 + 1)); rc |= dalloc(&h->ticket, 2);
@@ -364,7 +364,7 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
   void* ptrs[] = {h->obs, h->action, h->logprob, h->reward, h->terminal, h->value, h->adv, h->ret, h->env_state, h->env_t,
                   h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->next_value, h->ep_stats, h->ep_ring, h->ep_ring_count, h->params,
                   h->adam_m, h->adam_v, h->betap, h->optim_part, h->ticket, h->perm_base, h->recs, h->adv_part, h->perm_tmp, h->bfy_ws, h->bfy_adv_part, h->bfy_bucket_mb, h->bfy_mbid, h->bfy_dig1, h->gpart, h->lpart,
-                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws};
+                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws, h->ext_bad};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int s = 0; s < 2; ++s) {
     if (h->status_dev[s]) (void)hipFree(h->status_dev[s]);
@@ -372,6 +372,7 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
     if (h->status_ev[s]) (void)hipEventDestroy(h->status_ev[s]);
   }
   for (int s = 0; s < 2; ++s) if (h->diag_ev[s]) (void)hipEventDestroy(h->diag_ev[s]);
+  for (int s = 0; s < 2; ++s) if (h->peer_ev[s]) (void)hipEventDestroy(h->peer_ev[s]);
   for (int k = 0; k < CRL_K_COUNT; ++k)
     for (auto& pr : h->prof_slots[k].pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
@@ -392,7 +393,18 @@ int32_t crl_sync(crl_ppo* h) {
   CRL_GUARD(h);
   if (settle(h)) return 1;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return check_bfy(h);
+  if (check_bfy(h)) return 1;
+  // crl_env_step_device never reads its out-of-range-action word back: the first synchronising call after it reports (and lowers) it
+  if (!h->ext_bad_armed) return 0;
+  h->ext_bad_armed = false;
+  uint32_t bad = 0;
+  CRL_HIP_CHECK(hipMemcpyAsync(&bad, h->ext_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if (bad) {
+    CRL_HIP_CHECK(hipMemsetAsync(h->ext_bad, 0, sizeof(bad), h->stream));
+    set_error("crl_env_step_device: an action was outside 0 … n_act - 1 (those envs were not stepped)"); return 1;
+  }
+  return 0;
 }
 
 
@@ -660,9 +672,9 @@ int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, floa
   return launch_diag(h, out, new_logprob, new_value);
 }
 
-// CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT: the accumulator holds an order-preserving key of the true maximum (wide.hip: stat_max_key), 0 = no episode
+// CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT / CRL_ENV_EXTERNAL (extenv.hip: returns of any sign): the accumulator holds an order-preserving key of the true maximum (wide.hip: stat_max_key), 0 = no episode
 static double return_max_of(const crl_ppo* h, double raw) {
-  if (h->cfg.env_kind != CRL_ENV_MOUNTAINCAR && h->cfg.env_kind != CRL_ENV_ACROBOT) return raw;
+  if (h->cfg.env_kind != CRL_ENV_MOUNTAINCAR && h->cfg.env_kind != CRL_ENV_ACROBOT && h->cfg.env_kind != CRL_ENV_EXTERNAL) return raw;
   uint64_t k; std::memcpy(&k, &raw, 8);
   if (k == 0) return 0.0;
   k = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
@@ -936,14 +948,15 @@ static int stage_status(crl_ppo* h, int64_t k) {
 }
 
 // one pass of the ppo.jl:117-253 loop body
-static int iterate_once(crl_ppo* h, bool exact) {
+// (with_rollout = false: crl_ppo_update — the update half on whatever the resident buffer holds)
+static int iterate_once(crl_ppo* h, bool exact, bool with_rollout = true) {
   const int E = h->cfg.update_epochs, nmb = h->dc.nmb;
   const double eta = anneal_eta(h);
   const uint64_t ep0 = (uint64_t)h->iteration * (uint64_t)E;
   h->recs_dirty = true;
   if (h->wide) {
     // layer-wise path: per-epoch shuffle → statistics (→ all-reduce) → optimiser steps, gathering through the permutation
-    if (launch_rollout(h)) return 1;
+    if (with_rollout && launch_rollout(h)) return 1;
     if (compute_gae(h)) return 1;
     if (h->cfg.shuffle_mode == CRL_SHUFFLE_FISHER_YATES && launch_iota(h)) return 1;  // ppo.jl:191
     for (int ep = 0; ep < E; ++ep) {
@@ -970,8 +983,8 @@ static int iterate_once(crl_ppo* h, bool exact) {
     if (rc) return 1;
     CRL_HIP_CHECK(hipEventRecord(h->ev_join, h->stream2));
   }
-  const bool fuse = rollout_can_fuse_gae(h);
-  if (launch_rollout(h, fuse)) return 1;
+  const bool fuse = with_rollout && rollout_can_fuse_gae(h);
+  if (with_rollout && launch_rollout(h, fuse)) return 1;
   if (!fuse && compute_gae(h)) return 1;
   if (launch_pack_records(h)) return 1;
   if (overlap) CRL_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
@@ -1010,7 +1023,7 @@ static int settle(crl_ppo* h) {
   CRL_HIP_CHECK(hipMemsetAsync(h->vfix + 4, 0, sizeof(double), h->stream));
   h->iteration = h->snap_iteration;
   for (int i = 0; i < n; ++i) {
-    if (iterate_once(h, /*exact=*/true)) return 1;
+    if (iterate_once(h, /*exact=*/true, /*with_rollout=*/!h->window_update_only)) return 1;
     h->iteration += 1;
     // pipelined read-back: the slots of the repeated iterations now hold what the exact pass produced (and a lowered flag)
     if (h->pipelined && h->status_dev[0] && stage_status(h, h->iteration - 1)) return 1;
@@ -1134,6 +1147,105 @@ int32_t crl_ppo_drain(crl_ppo* h, crl_ppo_iteration_report* last, crl_ppo_stats*
   last->episodes.episodes = last->episodes.return_sum = last->episodes.length_sum = last->episodes.return_max = 0.0;
   if (!h->status_dev[0] || h->staged_last <= h->delivered_last) return 0;
   return deliver_status(h, h->staged_last, last, last_stats, last_ring, max_ring);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Device-resident external envs (csrc/extenv.hip): every pointer is device memory, nothing is staged, the calls only enqueue. peer_stream: the caller's
+// stream when it is not the handle's — the handle's stream waits for what the caller has enqueued so far, the caller's stream for this call's work; one
+// event record + hipStreamWaitEvent each way, the two events kept on the handle. No host wait.
+// ---------------------------------------------------------------------------------------------------------------
+static int peer_enter(crl_ppo* h, void* peer_stream) {
+  hipStream_t ps = static_cast<hipStream_t>(peer_stream);
+  if (!ps || ps == h->stream) return 0;
+  if (!h->peer_ev[0]) {
+    CRL_HIP_CHECK(hipEventCreateWithFlags(&h->peer_ev[0], hipEventDisableTiming));
+    CRL_HIP_CHECK(hipEventCreateWithFlags(&h->peer_ev[1], hipEventDisableTiming));
+  }
+  CRL_HIP_CHECK(hipEventRecord(h->peer_ev[0], ps));
+  CRL_HIP_CHECK(hipStreamWaitEvent(h->stream, h->peer_ev[0], 0));
+  return 0;
+}
+static int peer_leave(crl_ppo* h, void* peer_stream) {
+  hipStream_t ps = static_cast<hipStream_t>(peer_stream);
+  if (!ps || ps == h->stream) return 0;
+  CRL_HIP_CHECK(hipEventRecord(h->peer_ev[1], h->stream));
+  CRL_HIP_CHECK(hipStreamWaitEvent(ps, h->peer_ev[1], 0));
+  return 0;
+}
+
+int32_t crl_ppo_stream(crl_ppo* h, void** stream) {
+  if (!h || !stream) { set_error("crl_ppo_stream: null argument"); return 1; }
+  *stream = static_cast<void*>(h->stream);
+  return 0;
+}
+
+int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, int32_t* action_d, void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  CRL_NEED_PARAMS(h, "crl_rollout_act_device");
+  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_act_device: step out of range"); return 1; }
+  if (!obs_d || !done_d || !action_d) { set_error("crl_rollout_act_device: null argument"); return 1; }
+  if (peer_enter(h, peer_stream)) return 1;
+  if (step == 0) {   // a new rollout: its episode statistics and ring start empty, as in launch_rollout
+    CRL_HIP_CHECK(hipMemsetAsync(h->ep_stats, 0, 4 * sizeof(double), h->stream));
+    if (h->ep_ring_cap > 0) CRL_HIP_CHECK(hipMemsetAsync(h->ep_ring_count, 0, sizeof(uint32_t), h->stream));
+  }
+  if (launch_ext_act(h, step, obs_d, done_d, action_d)) return 1;
+  h->recs_dirty = true;
+  return peer_leave(h, peer_stream);
+}
+
+int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d, void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_record_device: step out of range"); return 1; }
+  if (!reward_d || !next_obs_d || !next_done_d) { set_error("crl_rollout_record_device: null argument"); return 1; }
+  if (peer_enter(h, peer_stream)) return 1;
+  if (launch_ext_record(h, step, reward_d, next_obs_d, next_done_d)) return 1;
+  return peer_leave(h, peer_stream);
+}
+
+int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d, void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  const int kind = h->cfg.env_kind;
+  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
+    set_error("crl_env_step_device needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
+  }
+  if (!action_d || !reward_d || !done_d) { set_error("crl_env_step_device: null action, reward or done"); return 1; }
+  if (ensure_env(h)) return 1;
+  if (peer_enter(h, peer_stream)) return 1;
+  if (launch_env_step(h, action_d, gstep, reward_d, done_d, h->ext_bad)) return 1;
+  h->ext_bad_armed = true;
+  if (next_obs_d) CRL_HIP_CHECK(hipMemcpyAsync(next_obs_d, h->cur_obs, (size_t)h->dc.nt * h->dc.D * 4, hipMemcpyDeviceToDevice, h->stream));
+  return peer_leave(h, peer_stream);
+}
+
+int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats) {
+  CRL_GUARD_SETTLED(h);
+  CRL_NEED_PARAMS(h, "crl_ppo_update");
+  if (has_comm(h) || h->external_comm) {
+    set_error("crl_ppo_update: single-rank only — a communicator is attached (multi-rank external envs are not supported)"); return 1;
+  }
+  const int E = h->cfg.update_epochs, nmb = h->dc.nmb;
+  // a guard window of its own: snapshot, the update phase, settle. A failed speculation restores the snapshot and repeats the update phase exactly —
+  // no rollout launch anywhere in the replay (window_update_only) — for one host synchronisation per call.
+  const bool guard = guard_on(h);
+  if (guard) {
+    if (guard_copy(h, /*save=*/true)) return 1;
+    h->snap_iteration = h->iteration;
+  }
+  if (iterate_once(h, /*exact=*/false, /*with_rollout=*/false)) return 1;
+  h->iteration += 1;
+  if (guard) {
+    h->window_count = 1; h->window_update_only = true;
+    const int rc = settle(h);
+    h->window_update_only = false;
+    if (rc) return 1;
+  }
+  if (stats) {
+    CRL_HIP_CHECK(hipMemcpyAsync(stats, h->stats_dev, sizeof(crl_ppo_stats) * (size_t)E * nmb, hipMemcpyDeviceToHost, h->stream));
+    CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (check_bfy(h)) return 1;
+  }
+  return 0;
 }
 
 int32_t crl_ppo_exact_reruns(const crl_ppo* h, int64_t* n) {

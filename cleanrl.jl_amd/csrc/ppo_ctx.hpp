@@ -173,6 +173,11 @@ struct crl_ppo {
   void* eval_ws = nullptr; size_t eval_ws_bytes = 0;   // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
   void* diag_ws = nullptr; size_t diag_ws_bytes = 0;   // crl_ppo_diagnose: per-block records | new_logprob | new_value (allocated on first use)
   hipEvent_t diag_ev[2] = {nullptr, nullptr}; int64_t diag_last_ns = 0; int diag_cus = 0;   // events around its launch (read-only option diag_last_ns), CU count
+  // device-resident external envs (extenv.hip): the peer_stream fences (recorded on the caller's stream before a launch, on the handle's after it), the
+  // step kernel's blocks per CU (asked once), the sticky out-of-range-action word of crl_env_step_device (reported by crl_sync)
+  hipEvent_t peer_ev[2] = {nullptr, nullptr}; int ext_per_cu = 0; uint32_t* ext_bad = nullptr;
+  bool ext_bad_armed = false;   // crl_env_step_device ran since the word was last read
+  bool window_update_only = false;   // the open guard window is crl_ppo_update's: its replay has no rollout launch
   // Pipelined read-back (crl_ppo_iterate_async): what a logging host reads after every update — the loss records, the episode statistics, the per-episode ring,
   // the speculation flag and the error words — is gathered by ONE launch into a device slot at the end of an iteration, copied to pinned host memory on the
   // stream and fenced by an event; the host picks it up one iteration later, behind the next iteration's launches, so the GPU never waits for the host.
@@ -266,6 +271,9 @@ int launch_eval(crl_ppo* h, const crl_eval_config* c, float* returns_d, int32_t*
 int eval_episode_cap(int kind);   // the longest episode of an env kind, in steps
 // diag.hip — crl_ppo_diagnose's one launch and the report
 int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value);
+// extenv.hip — the per-step launches of crl_rollout_act_device / crl_rollout_record_device
+int launch_ext_act(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, int32_t* action_d);
+int launch_ext_record(crl_ppo* h, int step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d);
 // wide.hip — layer-wise path for other network shapes
 bool wide_shape_ok(const crl_ppo_config* cfg, std::string* why);
 int wide_create(crl_ppo* h);

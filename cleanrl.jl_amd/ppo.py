@@ -291,6 +291,135 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
     return agent
 
 
+# ---------------------------------------------------------------------------------------------------------------- device-resident external envs
+# The device-env protocol. `ppo(config, env=obj)` / `train_external(agent, obj)` drive any object with
+#   num_envs, obs_dim, n_act          ints (ppo.jl:85-86 reads them off the env's spaces)
+#   reset() -> (obs, done)            ppo.jl:112-115: obs (obs_dim, num_envs) Float32, done [num_envs] UInt8
+#   step(action) -> (reward, next_obs, next_done)
+#                                     ppo.jl:130-144: `action` is the pointer-like the agent wrote its 0-based Int32 actions [num_envs] to; reward
+#                                     [num_envs] Float32; terminated envs are already reset, next_obs is what the policy sees next
+#   stream (optional)                 the hipStream_t (int) the env enqueues its work on; passed as peer_stream, so neither side waits on the host
+#   action (optional)                 pointer-like [num_envs] Int32 the env wants the actions written into (a torch env hands over its own tensor and
+#                                     gets it back in step); without it the loop allocates a DeviceBuffer
+# where every pointer-like is an int device address or an object with data_ptr() (a torch tensor, a DeviceBuffer) into buffers the ENV owns, on the
+# agent's device. Nothing in the loop touches host memory; the one host wait per update is crl_ppo_update's (4 / 2 / 64 path only).
+_PROTOCOL = ("num_envs", "obs_dim", "n_act", "reset", "step")
+
+
+def check_device_env(env):
+    """TypeError naming the first protocol attribute `env` lacks (nothing on the device is touched)."""
+    for name in _PROTOCOL:
+        if not hasattr(env, name):
+            raise TypeError(f"env={type(env).__name__} is neither an env name nor a device env: it has no `{name}` "
+                            f"(the device-env protocol needs {', '.join(_PROTOCOL)} and optionally stream, action)")
+    for name in ("reset", "step"):
+        if not callable(getattr(env, name)):
+            raise TypeError(f"device env: `{name}` must be callable")
+    return env
+
+
+class LibraryEnv:
+    """One of the library's on-device envs ("cartpole", "mountaincar", "acrobot") behind the device-env protocol: a second handle's built-in env stepped
+    with crl_env_reset + crl_env_step_device into device buffers this object owns (hipMalloc through ctypes; torch is not needed). The reference
+    implementation of the protocol — and the env of its tests. stale_obs / env_id_offset as for an Agent: with the Agent's defaults the env is the one a
+    built-in-env Agent of the same seed trains on."""
+
+    def __init__(self, name, num_envs, seed=0x5EED, device=0, stale_obs=True, env_id_offset=0):
+        shape = env_shape(name)
+        self.name, self.num_envs, self.obs_dim, self.n_act = name, int(num_envs), shape["obs_dim"], shape["n_act"]
+        cfg = _crl_config(PPOConfig(num_envs=self.num_envs, num_steps=1, num_minibatches=1, total_timesteps=self.num_envs), seed=seed,
+                          stale_obs=stale_obs, env_id_offset=env_id_offset, hidden=64, **shape)
+        self.handle = L.Handle(cfg, device)          # only its env is used: its parameters stay unset
+        self.stream = self.handle.stream
+        n, d = self.num_envs, self.obs_dim
+        self.obs, self.reward, self.done = L.DeviceBuffer(4 * n * d, device), L.DeviceBuffer(4 * n, device), L.DeviceBuffer(n, device)
+        self.gstep = 0
+
+    def reset(self):
+        """ppo.jl:112-115. (Set-up, not the stepping path: the initial observation is read from CRL_F_CUR_OBS through the host once.)"""
+        h = self.handle
+        h.env_reset()
+        self.obs.write(h.read(L.F_CUR_OBS)); self.done.write(h.read(L.F_NEXT_DONE))
+        self.gstep = 0
+        return self.obs, self.done
+
+    def step(self, action):
+        self.handle.env_step_device(action, self.gstep, self.obs, self.reward, self.done)   # on the env handle's own stream
+        self.gstep += 1
+        return self.reward, self.obs, self.done
+
+    def close(self):
+        self.handle.close()
+        for b in (self.obs, self.reward, self.done):
+            b.close()
+
+
+def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_records=0, eval_every=0, diag_every=0):
+    """The `for update in 1:num_updates` loop of ppo.jl:117-253 with the env OUTSIDE the library but on the same GPU (the device-env protocol above):
+    reset once; per step crl_rollout_act_device -> env.step -> crl_rollout_record_device; per update crl_ppo_update. Emits the records of `train`:
+    "Episode Statistics" (one aggregate per rollout, or one per episode with episode_records=N), "Training Statistics", and "Policy Diagnostics" every
+    diag_every-th update. eval_every is refused: crl_ppo_evaluate has no external env to run."""
+    if eval_every:
+        raise ValueError("train_external: eval_every is not available — crl_ppo_evaluate runs the library's own envs and has none for an external env")
+    if diag_every:
+        if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
+            raise ValueError(f"train_external: diag_every must be an integer >= 0, got {diag_every!r}")
+    check_device_env(env)
+    cfg = agent.config
+    if (env.num_envs, env.obs_dim, env.n_act) != (cfg.num_envs, agent.crl_cfg.obs_dim, agent.crl_cfg.n_act):
+        raise ValueError(f"train_external: the env has (num_envs, obs_dim, n_act) = {(env.num_envs, env.obs_dim, env.n_act)}, the agent "
+                         f"{(cfg.num_envs, agent.crl_cfg.obs_dim, agent.crl_cfg.n_act)}")
+    batch_size = cfg.num_steps * cfg.num_envs
+    if num_updates is None:
+        num_updates = max(1, cfg.total_timesteps // batch_size)  # ppo.jl:91
+    h = agent.handle
+    if episode_records:
+        h.episode_ring_enable(int(episode_records))
+    peer = getattr(env, "stream", None) or None
+    action = getattr(env, "action", None)
+    if action is None:
+        action = L.DeviceBuffer(4 * cfg.num_envs, agent.handle.device)
+    start_time = time.time()
+    last_log_step = 0
+    obs, done = env.reset()                                                        # ppo.jl:112-115
+    for update in range(1, num_updates + 1):
+        base = (update - 1) * batch_size
+        for step in range(cfg.num_steps):                                          # ppo.jl:123-166
+            h.act_device(step, obs, done, action, peer_stream=peer)
+            reward, obs, done = env.step(action)
+            h.record_device(step, reward, obs, done, peer_stream=peer)
+        # the episode records of this rollout are read before the next rollout's first step clears them; the reads are this loop's host waits
+        ep = h.episode_stats()
+        records = h.episode_records()[0] if episode_records else []
+        stats = h.update(want_stats=bool(log_every))                               # ppo.jl:168-253
+        global_step = base + batch_size
+        if episode_records:
+            for step, _env, ret, length in records:
+                gs = base + (step + 1) * cfg.num_envs
+                inc = 0 if last_log_step == 0 else gs - last_log_step
+                log.info("Episode Statistics", extra={"crl": dict(
+                    episode_return=ret, episode_length=length, global_step=gs,
+                    steps_per_sec=int(gs / max(time.time() - start_time, 1e-9)), log_step_increment=inc)})
+                last_log_step = gs
+        elif ep["episodes"] > 0:
+            inc = 0 if last_log_step == 0 else global_step - last_log_step
+            log.info("Episode Statistics", extra={"crl": dict(
+                episode_return=ep["return_sum"] / ep["episodes"], episode_length=ep["length_sum"] / ep["episodes"],
+                global_step=global_step, steps_per_sec=int(global_step / max(time.time() - start_time, 1e-9)), log_step_increment=inc)})
+            last_log_step = global_step
+        for s in stats or []:
+            inc = 0 if last_log_step == 0 else global_step - last_log_step
+            log.info("Training Statistics", extra={"crl": dict(
+                loss=s["loss"], pg_loss=s["pg_loss"], v_loss=s["v_loss"], entropy_loss=s["entropy_loss"], log_step_increment=inc)})
+            last_log_step = global_step
+        if diag_every and update % diag_every == 0:
+            d = h.diagnose()
+            log.info("Policy Diagnostics", extra={"crl": dict(
+                approx_kl=d["approx_kl"], old_approx_kl=d["old_approx_kl"], clipfrac=d["clipfrac"], entropy=d["entropy"],
+                explained_variance=d["explained_variance"], global_step=update * batch_size)})
+    return agent
+
+
 def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096, run_name="ppo-2-test",
         logger_kw=None, env=None, eval_every=0, eval_envs=256, eval_episodes=1, diag_every=0, **shape):
     """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. `env="cartpole" | "mountaincar" |
@@ -300,11 +429,32 @@ def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=
     Statistics" records of every update (ppo.jl:246-248). `logger_kw` goes to Logger.make_logger (logger.jl:7); `shape` keywords
     (obs_dim, n_act, hidden, env_kind, gae_mode, stale_obs, shuffle_mode) to the Agent — the reference derives them from the env
     (ppo.jl:85-87). `eval_every=N > 0`: an "Evaluation Statistics" record after every N-th update (see train / evaluate);
-    `diag_every=N > 0`: a "Policy Diagnostics" record after every N-th update (see train / diagnose). Both are validated before a device is touched."""
+    `diag_every=N > 0`: a "Policy Diagnostics" record after every N-th update (see train / diagnose). Both are validated before a device is touched.
+    `env=<object>` (not a string): a device-resident external env following the device-env protocol above — the agent is built with
+    env_kind=ENV_EXTERNAL and the object's obs_dim / n_act, and the loop is train_external; an object that lacks a protocol attribute is a TypeError."""
     if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
         raise ValueError(f"ppo: diag_every must be an integer >= 0, got {diag_every!r}")
+    external = env is not None and not isinstance(env, str)
+    if external:     # a device env (see the protocol above): its shape comes from the object, the loop is train_external
+        check_device_env(env)
+        if eval_every:
+            raise ValueError("ppo: eval_every is not available with a device env (crl_ppo_evaluate has no external env)")
+        for name in ("env_kind", "obs_dim", "n_act"):
+            if name in shape:
+                raise ValueError(f"ppo: {name} follows from the device env, do not pass it")
     from . import logger as _logger
     config = config or PPOConfig()
+    if external:
+        if env.num_envs != config.num_envs:
+            raise ValueError(f"ppo: the env has num_envs={env.num_envs}, the config {config.num_envs}")
+        _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
+        agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params,
+                      **(shape | dict(env_kind=L.ENV_EXTERNAL, obs_dim=int(env.obs_dim), n_act=int(env.n_act))))
+        try:
+            train_external(agent, env, episode_records=episode_records, diag_every=diag_every)
+            return agent.get_params()
+        finally:
+            agent.close()
     shape = env_shape(env, **shape)      # ppo.jl:82,85-86 (an unknown env is a ValueError before anything is created)
     _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
     agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, **shape)

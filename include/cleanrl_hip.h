@@ -269,6 +269,45 @@ typedef struct crl_ppo_iteration_report {
 } crl_ppo_iteration_report;
 int32_t crl_ppo_iterate_async(crl_ppo* h, crl_ppo_iteration_report* prev, crl_ppo_stats* prev_stats, crl_episode_record* prev_ring, int32_t max_ring);
 int32_t crl_ppo_drain(crl_ppo* h, crl_ppo_iteration_report* last, crl_ppo_stats* last_stats, crl_episode_record* last_ring, int32_t max_ring);
+
+/* ---- Device-resident external envs (csrc/extenv.hip): CRL_ENV_EXTERNAL for a simulator that lives on the handle's GPU (a torch-ROCm tensor env,
+ * AMDGPU.jl arrays, the caller's own HIP kernels). Every `_d` pointer below is DEVICE memory on the handle's device; nothing is staged, the calls only
+ * enqueue work on the handle's stream and never make the host wait (the one exception is stated at crl_ppo_update). The host-pointer pair
+ * crl_policy_act + crl_rollout_store keeps working unchanged next to them.
+ * The peer_stream rule, the same for every call that takes one. NULL (or the handle's own stream): the caller orders its work itself — it runs on the
+ * stream of crl_ppo_stream, or it has synchronised. Any other hipStream_t: before its launch the call makes the handle's stream wait for everything
+ * enqueued on peer_stream so far, and after its launch it makes peer_stream wait for that launch — an event record plus hipStreamWaitEvent each way, the
+ * two events created once and kept on the handle. */
+/* The handle's hipStream_t (non-blocking): run the env on it, or order another stream against it. */
+int32_t crl_ppo_stream(crl_ppo* h, void** stream);
+/* ppo.jl:127-128 plus the state / action / logprob / terminal / value fields of Buffer.add! (:133-140) in ONE launch: for env e, actor logits and critic
+ * value of obs_d (obs_dim, num_envs), get_action's sampler (ppo.jl:21-32) on the uniform of Philox stream 0 of (seed, env_id_offset + e,
+ * iteration * num_steps + step) — the draw every on-device rollout kernel takes for that env and step —, the 0-based action to action_d[e], and obs,
+ * action, logprob, value and terminal = done_d[e] (next_done of ppo.jl:115,144) into slot `step` of the resident buffer. The forward is the one of
+ * the diagnostics launch for every handle: W2 as bf16x3 with Float32 accumulation, NNlib's rational tanh_fast; no option changes a bit of it. step = 0
+ * starts a rollout: the episode statistics and the ring count are cleared on the stream first. Shapes: obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256.
+ * Errors: NULL pointers, step outside 0 … num_steps - 1, parameters never set. */
+int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, int32_t* action_d, void* peer_stream);
+/* ppo.jl:132,137,143-165 in one small launch: reward_d[num_envs] into slot `step`; CRL_F_CUR_OBS / CRL_F_NEXT_DONE <- next_obs_d (obs_dim, num_envs) /
+ * next_done_d[num_envs] (what the fixed-mode bootstrap of crl_compute_gae reads); per env episode_length += 1 and episode_return += reward as a Float32
+ * running sum in step order; where next_done is set the episode is added to the statistics of crl_episode_stats_read, appended as
+ * {return, length, env_id_offset + e, step} to the ring of crl_episode_ring_enable, and the two accumulators restart at zero. The statistics are Float64
+ * sums of the Float32 returns, added per wave and then atomically (exact, hence order-free, as long as the returns' binary exponents span less than
+ * 29 - log2(episodes) bits); return_max is the true signed maximum, 0 when no episode ended. Errors: NULL pointers, step out of range. */
+int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d, void* peer_stream);
+/* crl_env_step without the staging — one handle's built-in env as another handle's external env, entirely on device (ppo.jl:130-165 without the policy).
+ * action_d / reward_d / done_d [num_envs] and next_obs_d (obs_dim, num_envs; may be NULL: CRL_F_CUR_OBS holds it) are device memory. An action outside
+ * 0 … n_act - 1 leaves its env unstepped and raises a sticky device word instead of being read back here: the next crl_sync on this handle returns the
+ * error and lowers the word. CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR and CRL_ENV_ACROBOT. */
+int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d, void* peer_stream);
+/* ppo.jl:168-253 on whatever the resident buffer holds — the loop body of crl_ppo_iterate without its rollout launch: bootstrap + GAE, all epoch
+ * permutations, advantage statistics, update_epochs * num_minibatches optimiser steps with the annealed eta of the current iteration, then the
+ * iteration counter advances. Every env_kind. On the 4 / 2 / 64 path the call is a value-loss speculation guard window of its own (see
+ * crl_ppo_exact_reruns): snapshot, update phase, one read of the flag — the ONE host synchronisation of the device-pointer path, once per num_steps step
+ * launches — and, when the speculation failed, the snapshot restored and the update phase repeated exactly; no rollout is replayed. The layer-wise path
+ * does not synchronise. stats (may be NULL; non-NULL synchronises) receives the update_epochs * num_minibatches records of this update. Single rank
+ * only: with an RCCL, peer or external communicator attached the call returns an error (multi-rank external envs are not supported). */
+int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats);
 /* how many iterations had their update phase re-run with the exact value-loss pass under data parallelism: the fused
  * kernels speculate on u = mean(v - R^2) <= 0 (ppo.jl:232-237); with an RCCL communicator a failed speculation restores the
  * parameters / Adam state of the iteration's start and repeats its optimiser steps exactly (two more small all-reduces each) */

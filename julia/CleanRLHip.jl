@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -335,6 +335,70 @@ function ppo(config::PPOConfig=PPOConfig(); device::Integer=0, params::Union{Not
     end
   end
   agent
+end
+
+# ------------------------------------------------------------------------------------------------------
+# Device-resident external envs (include/cleanrl_hip.h, "Device-resident external envs"): the env lives on the agent's GPU — AMDGPU.jl arrays, the caller's
+# own kernels — and hands over DEVICE pointers (`pointer(roc_array)`); nothing is staged and no call below makes the host wait, except update! on the
+# 4 / 2 / 64 path (once per update). peer_stream: the env's hipStream_t when it is not the agent's (`C_NULL`: the caller orders its work itself).
+# ------------------------------------------------------------------------------------------------------
+# the agent's hipStream_t: run the env on it (AMDGPU.jl: HIPStream(stream(agent))), or pass the env's own stream as peer_stream
+function stream(a::Agent)
+  s = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:crl_ppo_stream, libcrl), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), a.h, s))
+  return s[]
+end
+# ppo.jl:127-128 + the policy's share of Buffer.add! (:133-140) for slot `step` (0-based), one launch; the 0-based actions land in action_d
+act_device!(a::Agent, step::Integer, obs_d::Ptr{Float32}, done_d::Ptr{UInt8}, action_d::Ptr{Int32}; peer_stream::Ptr{Cvoid}=C_NULL) =
+  check(ccall((:crl_rollout_act_device, libcrl), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Cvoid}),
+              a.h, step, obs_d, done_d, action_d, peer_stream))
+# ppo.jl:132,137,143-165: reward into slot `step`, next_obs / next_done, the episode bookkeeping
+record_device!(a::Agent, step::Integer, reward_d::Ptr{Float32}, next_obs_d::Ptr{Float32}, next_done_d::Ptr{UInt8}; peer_stream::Ptr{Cvoid}=C_NULL) =
+  check(ccall((:crl_rollout_record_device, libcrl), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Cvoid}),
+              a.h, step, reward_d, next_obs_d, next_done_d, peer_stream))
+# ppo.jl:168-253 on the resident buffer; returns the update_epochs * num_minibatches loss records
+function update!(a::Agent)
+  stats = Vector{CrlStats}(undef, a.config.update_epochs * a.config.num_minibatches)
+  GC.@preserve stats check(ccall((:crl_ppo_update, libcrl), Int32, (Ptr{Cvoid}, Ptr{CrlStats}), a.h, stats))
+  return stats
+end
+# The ppo.jl:117-253 loop with the env outside the library. `env` is anything with env.num_envs, env.obs_dim, env.n_act, env.action (a Ptr{Int32} the actions
+# are written to), reset!(env) -> (obs_d, done_d) and step!(env) -> (reward_d, next_obs_d, next_done_d), all device pointers into arrays the env keeps alive;
+# env.stream (a hipStream_t, optional) is passed as peer_stream. `reset!` / `step!` are the caller's functions, given as keywords.
+function ppo_external(config::PPOConfig, env; reset!, step!, device::Integer=0, params::Union{Nothing,Vector{Float32}}=nothing, init_seed::Integer=0,
+                      run_name::AbstractString="ppo-external", make_logger=_default_make_logger(), shape...)
+  make_logger === nothing || make_logger(run_name; to_terminal=false)
+  agent = Agent(config; device, obs_dim=env.obs_dim, n_act=env.n_act, env_kind=2, shape...)
+  params === nothing ? init_params!(agent, init_seed) : set_params!(agent, params)
+  peer = hasproperty(env, :stream) ? Ptr{Cvoid}(env.stream) : Ptr{Cvoid}(C_NULL)
+  batch_size = config.num_steps * config.num_envs
+  num_updates = config.total_timesteps ÷ batch_size
+  last_log_step = 0; start_time = time()
+  obs_d, done_d = reset!(env)                                              # ppo.jl:112-115
+  for update in 1:num_updates
+    for step in 0:config.num_steps - 1                                     # ppo.jl:123-166
+      act_device!(agent, step, obs_d, done_d, env.action; peer_stream=peer)
+      reward_d, obs_d, done_d = step!(env)
+      record_device!(agent, step, reward_d, obs_d, done_d; peer_stream=peer)
+    end
+    ep = Ref{CrlEpisodeStats}()
+    check(ccall((:crl_episode_stats_read, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlEpisodeStats}), agent.h, ep))
+    stats = update!(agent)                                                 # ppo.jl:168-253
+    global_step = update * batch_size
+    if ep[].episodes > 0
+      steps_per_sec = trunc(global_step / (time() - start_time))
+      episode_return = ep[].return_sum / ep[].episodes; episode_length = ep[].length_sum / ep[].episodes
+      log_step_inc = last_log_step == 0 ? 0 : global_step - last_log_step
+      @info "Episode Statistics" episode_return episode_length global_step steps_per_sec log_step_increment = log_step_inc
+      last_log_step = global_step
+    end
+    for s in stats
+      log_step_inc = last_log_step == 0 ? 0 : global_step - last_log_step
+      @info "Training Statistics" loss = s.loss pg_loss = s.pg_loss v_loss = s.v_loss entropy_loss = s.entropy_loss log_step_increment = log_step_inc
+      last_log_step = global_step
+    end
+  end
+  return agent
 end
 
 # ------------------------------------------------------------------------------------------------------
