@@ -8,7 +8,9 @@
 #include <utility>
 #include <vector>
 
+#include "env.hpp"
 #include "ppo_ctx.hpp"
+#include "stats.hpp"
 
 namespace crl {
 thread_local std::string g_err;
@@ -109,14 +111,22 @@ int reset_dw_scale(crl_ppo* h) {
   return 0;
 }
 
-int ensure_stage(crl_ppo* h, size_t bytes) {
-  if (h->stage_bytes >= bytes) return 0;
-  if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
-  h->stage = nullptr; h->stage_bytes = 0;
-  size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-  CRL_HIP_CHECK(hipMalloc(&h->stage, want));
-  h->stage_bytes = want;
+int ensure_scratch(crl_ppo* h, void** buf, size_t* have, size_t want) {
+  if (*have >= want) return 0;
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // work enqueued earlier may still read the old buffer
+  if (*buf) CRL_HIP_CHECK(hipFree(*buf));
+  *buf = nullptr; *have = 0;
+  CRL_HIP_CHECK(hipMalloc(buf, want));
+  *have = want;
   return 0;
+}
+int ensure_stage(crl_ppo* h, size_t bytes) { return ensure_scratch(h, &h->stage, &h->stage_bytes, bytes < (1u << 20) ? (1u << 20) : bytes); }
+
+// the entry points that step an on-device env themselves
+static int need_stateful_env(const crl_ppo* h, const char* who) {
+  if (env_stateful(h->cfg.env_kind)) return 0;
+  set_error(std::string(who) + " needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)");
+  return 1;
 }
 
 template <typename T>
@@ -246,15 +256,15 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
     std::string why;
     if (!wide_shape_ok(cfg, &why)) { set_error("unsupported network shape: " + why); return 1; }
   }
-  if (cfg->env_kind == CRL_ENV_CARTPOLE && (cfg->obs_dim != 4 || cfg->n_act != 2)) {
-    set_error("env_kind = CRL_ENV_CARTPOLE needs obs_dim=4, n_act=2 (use CRL_ENV_SYNTHETIC or CRL_ENV_EXTERNAL)"); return 1;
-  }
-  if (cfg->env_kind == CRL_ENV_ACROBOT && (cfg->obs_dim != 6 || cfg->n_act != 3)) {
-    set_error("env_kind = CRL_ENV_ACROBOT needs obs_dim=6, n_act=3"); return 1;
-  }
-  if (cfg->env_kind == CRL_ENV_MOUNTAINCAR && (cfg->obs_dim != 2 || cfg->n_act != 3)) {
-    set_error("env_kind = CRL_ENV_MOUNTAINCAR needs obs_dim=2, n_act=3"); return 1;
-  }
+  static const struct { int kind; const char* name; int obs_dim, n_act; const char* hint; } kEnvShapes[] = {
+      {CRL_ENV_CARTPOLE, "CRL_ENV_CARTPOLE", 4, 2, " (use CRL_ENV_SYNTHETIC or CRL_ENV_EXTERNAL)"},
+      {CRL_ENV_ACROBOT, "CRL_ENV_ACROBOT", 6, 3, ""},
+      {CRL_ENV_MOUNTAINCAR, "CRL_ENV_MOUNTAINCAR", 2, 3, ""},
+  };
+  for (const auto& s : kEnvShapes)
+    if (cfg->env_kind == s.kind && (cfg->obs_dim != s.obs_dim || cfg->n_act != s.n_act)) {
+      set_error(std::string("env_kind = ") + s.name + " needs obs_dim=" + std::to_string(s.obs_dim) + ", n_act=" + std::to_string(s.n_act) + s.hint); return 1;
+    }
   if (cfg->env_kind != CRL_ENV_CARTPOLE && cfg->env_kind != CRL_ENV_SYNTHETIC && cfg->env_kind != CRL_ENV_EXTERNAL &&
       cfg->env_kind != CRL_ENV_MOUNTAINCAR && cfg->env_kind != CRL_ENV_ACROBOT) {
     set_error("unknown env_kind"); return 1;
@@ -326,9 +336,9 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   // update grid: two 256-thread blocks per CU, alternating roles; never more waves than tiles
   hipDeviceProp_t prop;
   CRL_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-  const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   int ntiles = (c.M + 31) / 32;
-  int ub = cus;  // blocks per role
+  int ub = h->cus;  // blocks per role
   if (ub * 4 > ntiles) ub = (ntiles + 3) / 4;
   if (ub < 1) ub = 1;
   h->update_blocks = ub;
@@ -582,10 +592,7 @@ int32_t crl_rollout_run(crl_ppo* h) {
 
 int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done) {
   CRL_GUARD_SETTLED(h);
-  const int kind = h->cfg.env_kind;
-  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
-    set_error("crl_env_step needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
-  }
+  if (need_stateful_env(h, "crl_env_step")) return 1;
   if (!action) { set_error("crl_env_step: null action"); return 1; }
   if (ensure_env(h)) return 1;
   const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D;
@@ -609,10 +616,7 @@ int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* n
 int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report* report, float* returns, int32_t* lengths, int32_t* trace_action) {
   CRL_GUARD_SETTLED(h);
   if (!cfg || !report) { set_error("crl_ppo_evaluate: null cfg or report"); return 1; }
-  const int kind = h->cfg.env_kind;
-  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
-    set_error("crl_ppo_evaluate needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
-  }
+  if (need_stateful_env(h, "crl_ppo_evaluate")) return 1;
   if (cfg->num_envs < 1) { set_error("crl_ppo_evaluate: num_envs must be >= 1, got " + std::to_string(cfg->num_envs)); return 1; }
   if (cfg->episodes_per_env < 1) { set_error("crl_ppo_evaluate: episodes_per_env must be >= 1, got " + std::to_string(cfg->episodes_per_env)); return 1; }
   if (cfg->mode != CRL_EVAL_GREEDY && cfg->mode != CRL_EVAL_SAMPLE) { set_error("crl_ppo_evaluate: unknown mode " + std::to_string(cfg->mode)); return 1; }
@@ -626,13 +630,7 @@ int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report
   }
   CRL_NEED_PARAMS(h, "crl_ppo_evaluate");
   const size_t ne = (size_t)(n * E), o_ret = 0, o_len = o_ret + ne * 4, o_tr = o_len + ne * 4, total = o_tr + (size_t)(T * n) * 4;
-  if (h->eval_ws_bytes < total) {
-    CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (h->eval_ws) CRL_HIP_CHECK(hipFree(h->eval_ws));
-    h->eval_ws = nullptr; h->eval_ws_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->eval_ws, total));
-    h->eval_ws_bytes = total;
-  }
+  if (ensure_scratch(h, &h->eval_ws, &h->eval_ws_bytes, total)) return 1;
   char* ws = static_cast<char*>(h->eval_ws);
   // every (episode, env) slot is written by the launch (the loop bound covers the longest quota); a slot that was not shows as length 0 below.
   // Trace rows behind an env's last step — and behind the step a whole tile finished at — stay at -1.
@@ -644,7 +642,7 @@ int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report
   CRL_HIP_CHECK(hipMemcpyAsync(len.data(), ws + o_len, ne * 4, hipMemcpyDeviceToHost, h->stream));
   if (T > 0) CRL_HIP_CHECK(hipMemcpyAsync(trace_action, ws + o_tr, (size_t)(T * n) * 4, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
-  const int cap = eval_episode_cap(kind);
+  const int cap = eval_episode_cap(h->cfg.env_kind);
   double rsum = 0.0, lsum = 0.0, rmin = (double)ret[0], rmax = (double)ret[0];
   int64_t steps = 0;
   for (size_t i = 0; i < ne; ++i) {
@@ -672,14 +670,11 @@ int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, floa
   return launch_diag(h, out, new_logprob, new_value);
 }
 
-// CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT / CRL_ENV_EXTERNAL (extenv.hip: returns of any sign): the accumulator holds an order-preserving key of the true maximum (wide.hip: stat_max_key), 0 = no episode
+// CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT / CRL_ENV_EXTERNAL (extenv.hip: returns of any sign): the accumulator holds an order-preserving key of the true maximum (stats.hpp: stat_max_key), 0 = no episode
 static double return_max_of(const crl_ppo* h, double raw) {
-  if (h->cfg.env_kind != CRL_ENV_MOUNTAINCAR && h->cfg.env_kind != CRL_ENV_ACROBOT && h->cfg.env_kind != CRL_ENV_EXTERNAL) return raw;
-  uint64_t k; std::memcpy(&k, &raw, 8);
-  if (k == 0) return 0.0;
-  k = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  double x; std::memcpy(&x, &k, 8);
-  return x;
+  if (!env_signed_returns(h->cfg.env_kind) && h->cfg.env_kind != CRL_ENV_EXTERNAL) return raw;
+  unsigned long long k; std::memcpy(&k, &raw, 8);
+  return stat_max_unkey(k);
 }
 
 int32_t crl_episode_stats_read(crl_ppo* h, crl_episode_stats* out) {
@@ -1205,10 +1200,7 @@ int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_
 
 int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
-  const int kind = h->cfg.env_kind;
-  if (kind != CRL_ENV_CARTPOLE && kind != CRL_ENV_MOUNTAINCAR && kind != CRL_ENV_ACROBOT) {
-    set_error("crl_env_step_device needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)"); return 1;
-  }
+  if (need_stateful_env(h, "crl_env_step_device")) return 1;
   if (!action_d || !reward_d || !done_d) { set_error("crl_env_step_device: null action, reward or done"); return 1; }
   if (ensure_env(h)) return 1;
   if (peer_enter(h, peer_stream)) return 1;

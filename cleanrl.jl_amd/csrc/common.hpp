@@ -76,6 +76,16 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
+  return v;
+}
 
 // Orders one wave's LDS traffic between phases of wave-private scratch use (no s_barrier needed: the LDS
 // pipeline executes a wave's DS instructions in issue order; this only pins the compiler's order).

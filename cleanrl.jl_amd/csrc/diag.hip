@@ -4,29 +4,23 @@
 // of. No reference counterpart (ppo.jl logs its four losses only). One kernel family for the fused 4 / 2 / 64 shape and every layer-wise shape
 // (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256); no option and no route of the handle is read.
 //
-// diag_kernel<H>: the eval_rollout_kernel block (H / 32 waves, wave w keeps rows 32w … 32w + 31 of W2 as bf16x3 A fragments in registers, the last three
-// k-steps in LDS at 256) made persistent over 32-sample tiles of the flat batch. ROLES ARE BLOCKS: even blocks hold the actor, odd blocks the critic, and
-// block 2j / 2j + 1 both walk tiles j, j + nrb, j + 2 nrb, … — every tile gets its actor forward and its critic forward, W2 of one network stays where it is
-// for the life of the block, and neither role needs anything of the other: the actor's sums are Σr, Σkl, Σclipped, ΣH, min / max ratio, the critic's
-// Σret, Σret², Σ(ret − value), Σ(ret − value)², Σ(ret − v_new), Σ(ret − v_new)². (The price is that a tile's observations are fetched twice.)
-//   LDS       the head partials live where the h1 pieces were (one more barrier per tile buys 16 KB at 256, which is what lets obs 64 / act 16 / hidden 256 fit)
-//   per tile  the 32 x obs_dim observations, contiguous in the buffer, to LDS (rows padded by four floats: obs_dim up to 64 does not fit a thread's
-//             registers next to W2, so layer 1 streams x and W1 from LDS in chunks of four) | barrier | layer 1 on the vector pipe: tanh_fast, bf16x3 split,
-//             B-fragment order | barrier | layer 2 on the matrix pipe (f32 accumulation), tanh_fast | barrier | the wave's head partials | barrier | lanes 0-31 of
-//             wave 0: one sample each — log-softmax at the stored action, entropy, or the value — then Float64 from the Float32 log-ratio on.
+// diag_kernel<H>: the register-stationary bf16x3 forward block and the role-pair frame of fwd_rs_x3.hpp (even blocks hold the actor, odd blocks the critic, both
+// persistent over 32-sample tiles of the flat batch; the price is that a tile's observations are fetched twice). W2 of one network stays where it is for the
+// life of the block, and neither role needs anything of the other: the actor's sums are Σr, Σkl, Σclipped, ΣH, min / max ratio, the critic's
+// Σret, Σret², Σ(ret − value), Σ(ret − value)², Σ(ret − v_new), Σ(ret − v_new)².
+//   per tile  what the last phase needs of the buffer and the 32 x obs_dim observations, contiguous in the buffer, to LDS | barrier | layer 1 | barrier |
+//             layer 2 | barrier | the wave's head partials | barrier | lanes 0-31 of wave 0: one sample each — log-softmax at the stored action, entropy, or
+//             the value — then Float64 from the Float32 log-ratio on.
 //   exit      wave 0 adds its lanes' sums (butterfly, fixed order) and writes ONE record of six doubles; the host adds the records in block order, so two
 //             calls on the same state give the same bits. Nothing B-sized is written unless the caller asked for the per-sample outputs.
 #include <vector>
 
-#include "common.hpp"
-#include "mlp_x3.hpp"
-#include "policy_rt.hpp"
-#include "ppo_ctx.hpp"
+#include "fwd_rs_x3.hpp"
 
 namespace crl {
 
 constexpr int DIAG_REC = 8;        // doubles per block record (six used)
-constexpr int DIAG_OBS_MAX = 64;
+constexpr int DIAG_OWN = 6 * 32 * 2;   // the kernel's own LDS floats: the running sums [6][32 lanes] (Float64)
 
 struct DiagArgs {
   const float* params; int64_t Pa;   // actor | critic, each W1(H,D) b1(H) W2(H,H) b2(H) W3(n_out,H) b3(n_out), (out,in) column-major
@@ -38,83 +32,22 @@ struct DiagArgs {
   float* new_logprob; float* new_value;   // [B] each, may be null
 };
 
-__host__ __device__ constexpr int diag_ks_lds(int H) { return H == 256 ? 3 : 0; }
-// LDS (floats): h1 pieces | W2 fragments of the k-steps that are not in registers | the running sums [6][32 lanes] (Float64) | b1 | b2 (C-fragment order) | b3 |
-// W3 (C-fragment order) [n_out][H] | observations [32][D | 1] | W1 [D][H] as the parameters hold it (when it fits)
-__host__ __device__ constexpr int diag_lds_fixed(int H) { return 3 * H * 16 + diag_ks_lds(H) * 3 * (H / 32) * 64 * 4 + 6 * 32 * 2 + H + H + AMAX; }
-__host__ __device__ constexpr int diag_xs(int D) { return D | 1; }   // odd row stride: the 32 samples of a column sit in 32 banks
-static inline size_t diag_lds_bytes(int H, int D, int A, bool w1_lds) {
-  return sizeof(float) * (size_t)(diag_lds_fixed(H) + ((A * H + 3) & ~3) + ((32 * diag_xs(D) + 3) & ~3) + (w1_lds ? H * D : 0));
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { const double u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
-  return v;
-}
-
-// eight consecutive hidden rows of one sample: column k of W1 (out, in column-major: rows r … r + 7 are two 16-byte reads, from LDS or from the
-// parameters as they lie in HBM) times x[k], k in order
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // the critic's W1 starts where the actor's parameters end: 4-byte aligned only
-template <typename V>
-__device__ __forceinline__ void diag_layer1(const float* wcol, int ldw, const float* x, int D, float (&hv)[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hv[j] = 0.0f;
-#pragma unroll 2
-  for (int k = 0; k < D; ++k) {
-    const V w0 = reinterpret_cast<const V*>(wcol + (size_t)ldw * k)[0], w1 = reinterpret_cast<const V*>(wcol + (size_t)ldw * k)[1];
-    const float xv = x[k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { hv[j] = __builtin_fmaf(w0[j], xv, hv[j]); hv[4 + j] = __builtin_fmaf(w1[j], xv, hv[4 + j]); }
-  }
-}
-
 template <int H>
 __global__ void __launch_bounds__(2 * H) diag_kernel(DiagArgs a) {
-  constexpr int NW = H / 32, KS = H / 16, NT = 2 * H, KL = diag_ks_lds(H), KR = KS - KL;
+  constexpr int NT = RsGeom<H>::NT, KR = RsGeom<H>::KR;
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int D = a.D, XS = diag_xs(D), B = a.B;
+  const int D = a.D, XS = rs_xs(D), B = a.B;
   const int role = blockIdx.x & 1, rb = blockIdx.x >> 1, nrb = gridDim.x >> 1;   // 0 = actor, 1 = critic
   const int A = role ? 1 : a.A;
-  bf16x8* h1p = reinterpret_cast<bf16x8*>(sm);                  // [piece][ks][lane]: B fragments of h1, k = 16 ks + 8 (lane >> 5) + j
-  bf16x8* wl = h1p + 3 * KS * 64;                               // [KL][piece][wave][lane]: A fragments of the last KL k-steps of W2
-  double* acc64 = reinterpret_cast<double*>(sm + 3 * H * 16 + KL * 3 * NW * 64 * 4);   // [6][32]: lane's sums, in LDS so that they cost W2 no registers
-  float* b1l = sm + 3 * H * 16 + KL * 3 * NW * 64 * 4 + 6 * 32 * 2;
-  float* b2c = b1l + H;                                         // [wave][hf][16]: b2[32 wave + rowmap(r, hf)]
-  float* b3l = b2c + H;
-  float* zp = sm;                                               // [wave][AMAX][32 samples]: head partials, in the first third of the h1 region once layer 2 has read it
-  float* w3c = b3l + AMAX;                                      // [A][wave][hf][16]
-  float* xt = w3c + ((a.A * H + 3) & ~3);                       // [32 samples][XS]
-  float* w1l = xt + ((32 * XS + 3) & ~3);                       // [D][H], column k at 16-byte aligned H k
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hf = lane >> 5, i = lane & 31;
-  const float* W1 = a.params + (role ? a.Pa : 0); const float* b1 = W1 + H * D; const float* W2 = b1 + H; const float* b2 = W2 + H * H;
-  const float* W3 = b2 + H; const float* b3 = W3 + A * H;
+  const RsRoleLds l = rs_role_lds<H>(sm, DIAG_OWN, D, a.A);
+  double* acc64 = reinterpret_cast<double*>(l.own);             // [6][32]: lane's sums, in LDS so that they cost W2 no registers
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const RsNet net = rs_net<H>(a.params + (role ? a.Pa : 0), D, A);
 
-  if (a.w1_lds) for (int idx = tid; idx < H * D; idx += NT) w1l[idx] = W1[idx];
-  for (int idx = tid; idx < H; idx += NT) {
-    b1l[idx] = b1[idx];
-    b2c[idx] = b2[32 * (idx >> 5) + rowmap(idx & 15, (idx >> 4) & 1)];
-  }
-  for (int idx = tid; idx < A * H; idx += NT) {
-    const int aa = idx / H, q = idx % H;
-    w3c[idx] = W3[aa + A * (32 * (q >> 5) + rowmap(q & 15, (q >> 4) & 1))];
-  }
-  if (tid < AMAX) b3l[tid] = tid < A ? b3[tid] : 0.0f;
-  P3 wr[KR];                                                     // this wave's 32 rows of W2: A fragments, row = 32 w + i
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = W2[(32 * w + i) + H * (16 * ks + 8 * hf + j)];
-    if (ks < KR) wr[ks] = split3(v);
-    else { const P3 p = split3(v); bf16x8* q = wl + ((ks - KR) * 3 * NW + w) * 64 + lane; q[0] = p.hi; q[NW * 64] = p.mid; q[2 * NW * 64] = p.lo; }
-    if (ks & 1) __builtin_amdgcn_sched_barrier(0);               // raw rows of two k-steps in flight: the split pieces fill the file
-  }
+  if (a.w1_lds) for (int idx = tid; idx < H * D; idx += NT) l.w1l[idx] = net.W1[idx];
+  rs_stage_head<H>(net, A, l.b1l, l.b2c, l.w3c, l.b3l, tid);
+  P3 wr[KR];
+  rs_stage_w2<H>(net.W2, wr, l.wl, w, lane);
   __syncthreads();
 
   // lane's sums (lanes 0-31 of wave 0, nobody else touches them). actor: Σr, Σkl, Σclipped, ΣH, min ratio, max ratio; critic: Σret, Σret², Σ(ret − value),
@@ -136,72 +69,18 @@ __global__ void __launch_bounds__(2 * H) diag_kernel(DiagArgs a) {
     }
     for (int idx = tid; idx < 32 * D; idx += NT) {               // obs (D, B): the tile's 32 D floats are contiguous
       const int m = idx / D, k = idx - m * D;
-      xt[m * XS + k] = m < nb ? a.obs[(size_t)b0 * D + idx] : 0.0f;
+      l.xt[m * XS + k] = m < nb ? a.obs[(size_t)b0 * D + idx] : 0.0f;
     }
     __syncthreads();
-    {                                                            // layer 1: sample m, hidden rows 8 oct … 8 oct + 7
-      const int m = tid & 31, g8 = tid >> 5;
-#pragma unroll 1
-      for (int half = 0; half < 2; ++half) {
-        const int oct = g8 + half * (H / 16);
-        float hv[8];
-        if (a.w1_lds) diag_layer1<f32x4>(w1l + 8 * oct, H, xt + m * XS, D, hv);
-        else diag_layer1<f32x4u>(W1 + 8 * oct, H, xt + m * XS, D, hv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) hv[j] = tanh_fast(hv[j] + b1l[8 * oct + j]);
-        const P3 p = split3(hv);
-        const int slot = (oct >> 1) * 64 + (oct & 1) * 32 + m;
-        h1p[slot] = p.hi; h1p[KS * 64 + slot] = p.mid; h1p[2 * KS * 64 + slot] = p.lo;
-      }
-    }
+    rs_layer1_stream<H>(l, net.W1, a.w1_lds, D, tid);
     __syncthreads();
-    {                                                            // layer 2 + the wave's head partials
-      f32x16 acc = load16(b2c + (2 * w + hf) * 16);
-      const bf16x8* hb = h1p + lane;
-      asm volatile("" : "+v"(hb));                               // one base per tile, constant offsets behind it
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        P3 b;
-        b.hi = hb[ks * 64]; b.mid = hb[(KS + ks) * 64]; b.lo = hb[(2 * KS + ks) * 64];
-        if (ks < KR) acc = mfma_x3(wr[ks], b, acc);
-        else {
-          const bf16x8* q = wl + ((ks - KR) * 3 * NW + w) * 64 + lane;
-          P3 aw; aw.hi = q[0]; aw.mid = q[NW * 64]; aw.lo = q[2 * NW * 64];
-          acc = mfma_x3(aw, b, acc);
-        }
-        if (ks & 1) __builtin_amdgcn_sched_barrier(0);           // at most two k-steps of B fragments in flight
-      }
-      __syncthreads();                                           // every wave has read its h1 fragments: the region now takes the head partials
-      float h2[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) h2[r] = tanh_fast(acc[r]);
-      for (int aa = 0; aa < A; ++aa) {
-        const f32x4* wv = reinterpret_cast<const f32x4*>(w3c + aa * H + (2 * w + hf) * 16);
-        float p = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = wv[q];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) p = __builtin_fmaf(v[c], h2[4 * q + c], p);
-        }
-        p = add32(p);
-        if (hf == 0) zp[(w * AMAX + aa) * 32 + i] = p;
-      }
-    }
+    const f32x16 acc = rs_layer2<H>(wr, l.wl, l.h1p, l.b2c, w, lane);
+    __syncthreads();                                             // every wave has read its h1 fragments: the region now takes the head partials
+    rs_head_partials<H>(acc, l.w3c, A, l.zp, w, lane);
     __syncthreads();
     if (mine) {                                                  // one lane per sample; the next tile's first barrier stands between these reads of zp and layer 1's writes of h1
       float z[AMAX];
-      const float* zl = zp + lane;
-      asm volatile("" : "+v"(zl));
-#pragma unroll
-      for (int aa = 0; aa < AMAX; ++aa) {
-        float v = 0.0f;
-        if (aa < A) {
-          v = b3l[aa];
-          for (int ww = 0; ww < NW; ++ww) v += zl[(ww * AMAX + aa) * 32];
-        }
-        z[aa] = v;
-      }
+      rs_logits<H>(l.zp, l.b3l, A, lane, z);
       if (role == 0) {
         // softmax_rt's operations in its order (policy_rt.hpp), an action at a time: p = exp(z - m) / Σ, lp = (z - m) - log Σ
         float mx = z[0];
@@ -269,38 +148,15 @@ static void diag_finish(crl_ppo_diag* d) {
 // back to the host, the records added in block order.
 int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value) {
   const int H = h->cfg.hidden, D = h->dc.D, A = h->dc.A, B = h->dc.B;
-  if (D < 1 || D > DIAG_OBS_MAX || A < 1 || A > AMAX || (H != 64 && H != 128 && H != 256)) {
-    set_error("crl_ppo_diagnose: no diagnostics kernel for this shape (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256)");
-    return 1;
-  }
-  const bool w1_lds = diag_lds_bytes(H, D, A, true) <= 160 * 1024;
-  const size_t lds = diag_lds_bytes(H, D, A, w1_lds);
-  if (lds > 160 * 1024) { set_error("crl_ppo_diagnose: this shape needs more LDS than a CU has"); return 1; }
-  if (h->diag_cus == 0) {
-    hipDeviceProp_t prop;
-    CRL_HIP_CHECK(hipGetDeviceProperties(&prop, h->device));
-    h->diag_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  // persistent grid: what the device holds at once (registers and LDS decide), at most four blocks per CU, half of them per role, never more than tiles
+  bool w1_lds; size_t lds;
+  if (rs_role_shape(h, DIAG_OWN, "crl_ppo_diagnose: no diagnostics kernel for this shape (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256)",
+                    "crl_ppo_diagnose: this shape needs more LDS than a CU has", &w1_lds, &lds)) return 1;
   int per_cu = 0;
-  if (H == 64) CRL_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, diag_kernel<64>, 2 * H, lds));
-  else if (H == 128) CRL_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, diag_kernel<128>, 2 * H, lds));
-  else CRL_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, diag_kernel<256>, 2 * H, lds));
-  per_cu = per_cu > 4 ? 4 : per_cu < 1 ? 1 : per_cu;
-  const int ntiles = (B + 31) / 32;
-  int nrb = per_cu * h->diag_cus / 2;
-  nrb = nrb > ntiles ? ntiles : nrb;
-  nrb = nrb < 1 ? 1 : nrb;
-  const int nblk = 2 * nrb;
+  if (rs_dispatch_h(H, [&](auto hc) { return rs_role_per_cu(diag_kernel<decltype(hc)::value>, H, lds, &per_cu); })) return 1;
+  const int nblk = 2 * rs_role_pairs(h, per_cu, B);
   const bool per_sample = new_logprob || new_value;
   const size_t o_lp = ((size_t)nblk * DIAG_REC * 8 + 255) & ~(size_t)255, o_v = o_lp + (per_sample ? (size_t)B * 4 : 0), total = o_v + (per_sample ? (size_t)B * 4 : 0);
-  if (h->diag_ws_bytes < total) {
-    CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (h->diag_ws) CRL_HIP_CHECK(hipFree(h->diag_ws));
-    h->diag_ws = nullptr; h->diag_ws_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->diag_ws, total));
-    h->diag_ws_bytes = total;
-  }
+  if (ensure_scratch(h, &h->diag_ws, &h->diag_ws_bytes, total)) return 1;
   if (!h->diag_ev[0]) { CRL_HIP_CHECK(hipEventCreate(&h->diag_ev[0])); CRL_HIP_CHECK(hipEventCreate(&h->diag_ev[1])); }
   char* ws = static_cast<char*>(h->diag_ws);
   DiagArgs a;
@@ -312,9 +168,7 @@ int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_va
   a.new_value = new_value ? reinterpret_cast<float*>(ws + o_v) : nullptr;
   const dim3 grid(nblk), block(2 * H);
   CRL_HIP_CHECK(hipEventRecord(h->diag_ev[0], h->stream));
-  if (H == 64) hipLaunchKernelGGL(diag_kernel<64>, grid, block, lds, h->stream, a);
-  else if (H == 128) hipLaunchKernelGGL(diag_kernel<128>, grid, block, lds, h->stream, a);
-  else hipLaunchKernelGGL(diag_kernel<256>, grid, block, lds, h->stream, a);
+  rs_dispatch_h(H, [&](auto hc) { hipLaunchKernelGGL(diag_kernel<decltype(hc)::value>, grid, block, lds, h->stream, a); return 0; });
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipEventRecord(h->diag_ev[1], h->stream));
   std::vector<double> part((size_t)nblk * DIAG_REC);

@@ -90,6 +90,7 @@ struct crl_ppo {
   crl_ppo_config cfg;
   crl::DevCfg dc;
   int device = 0;
+  int cus = 0;                     // compute units of the device (crl_ppo_create)
   hipStream_t stream = nullptr;
   // second stream: crl_ppo_iterate draws the epoch permutations (which depend on nothing the rollout produces) next to the
   // rollout kernel, whose 128 dependent steps leave most issue slots and all of the memory system idle
@@ -172,7 +173,7 @@ struct crl_ppo {
   void* pinned = nullptr; size_t pinned_bytes = 0;
   void* eval_ws = nullptr; size_t eval_ws_bytes = 0;   // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
   void* diag_ws = nullptr; size_t diag_ws_bytes = 0;   // crl_ppo_diagnose: per-block records | new_logprob | new_value (allocated on first use)
-  hipEvent_t diag_ev[2] = {nullptr, nullptr}; int64_t diag_last_ns = 0; int diag_cus = 0;   // events around its launch (read-only option diag_last_ns), CU count
+  hipEvent_t diag_ev[2] = {nullptr, nullptr}; int64_t diag_last_ns = 0;   // events around its launch (read-only option diag_last_ns)
   // device-resident external envs (extenv.hip): the peer_stream fences (recorded on the caller's stream before a launch, on the handle's after it), the
   // step kernel's blocks per CU (asked once), the sticky out-of-range-action word of crl_env_step_device (reported by crl_sync)
   hipEvent_t peer_ev[2] = {nullptr, nullptr}; int ext_per_cu = 0; uint32_t* ext_bad = nullptr;
@@ -212,6 +213,7 @@ inline uint64_t shuffle_seed(const crl_ppo* h) {
 }
 void select_slot(crl_ppo* h, int slot);
 int ensure_records(crl_ppo* h);
+int ensure_scratch(crl_ppo* h, void** buf, size_t* have, size_t want);   // a device scratch buffer of the handle, grown on first use (the stream is drained before the old one is freed)
 int ensure_stage(crl_ppo* h, size_t bytes);
 int reset_dw_scale(crl_ppo* h);
 // option "gemm": 2 (default) = fp16x2 products in the update kernel and the rollout's critic, bf16x3 for the rollout's actor

@@ -1,4 +1,4 @@
-// stats.hpp — the "Training Statistics" record (ppo.jl:243-247) from the four loss sums of one optimiser step.
+// stats.hpp — the "Training Statistics" record (ppo.jl:243-247) from the four loss sums of one optimiser step, and the key return_max travels as.
 #pragma once
 #include "ppo_ctx.hpp"
 
@@ -28,6 +28,20 @@ __device__ __forceinline__ void compute_stats4(float s0, float s1, float s2, flo
 __device__ __forceinline__ void compute_stats(const float* msg, int P, const DevCfg& c, double Mglobal, const double* adv_ms,
                                               int mb, double* vfix, crl_ppo_stats* out, int mode) {
   compute_stats4(msg[P], msg[P + 1], msg[P + 2], msg[P + 3], c, Mglobal, adv_ms, mb, vfix, out, mode);
+}
+
+// return_max of the env kinds whose episode returns can be negative (env_signed_returns, and CRL_ENV_EXTERNAL): ep_stats[3] holds an order-preserving map of
+// the double onto u64 (never 0 for a number: 0 = "no episode yet", which is what the accumulator is cleared to), so one unsigned atomicMax keeps the maximum;
+// the host maps what it reads back
+__device__ __host__ __forceinline__ unsigned long long stat_max_key(double x) {
+  unsigned long long b; __builtin_memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __host__ __forceinline__ double stat_max_unkey(unsigned long long k) {
+  if (k == 0) return 0.0;
+  k = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double x; __builtin_memcpy(&x, &k, 8);
+  return x;
 }
 
 struct StatsArgs {

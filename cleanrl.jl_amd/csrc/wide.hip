@@ -1719,11 +1719,6 @@ __device__ __forceinline__ double step_stat_max(int kind, double st_n, double st
   if (!env_signed_returns(kind)) return fmax(st_max, fmax(0.0, ep_ret));
   return st_n > 1.0 ? fmax(st_max, ep_ret) : ep_ret;
 }
-// order-preserving map of a double onto u64 (never 0 for a number: 0 = "no episode yet", which is what the accumulator is cleared to)
-__device__ __host__ __forceinline__ unsigned long long stat_max_key(double x) {
-  unsigned long long b; __builtin_memcpy(&b, &x, 8);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 // one env, one step; the episode statistics of a finished episode are added to the caller's running sums. zreg: the env's logits when the caller holds them
 // in registers (else they come from a.Z); xout: receives the env's next observation (16 floats, zero beyond obs_dim) besides cur_obs; a.V may be null (the
 // caller fills the value buffer later: wide_rs_rollout_kernel)

@@ -168,8 +168,11 @@ def test_act_device_errors(crl):   # noqa: F811
 
 
 # --------------------------------------------------------------------------------------------------------------- 2. diagnose agrees
-@pytest.mark.parametrize("D,A,H,nt", [(4, 2, 64, 37), (8, 4, 256, 64)], ids=["fused-37", "8-4-256-64"])
+@pytest.mark.parametrize("D,A,H,nt", [(4, 2, 64, 37), (8, 4, 256, 64), (64, 16, 256, 33)], ids=["fused-37", "8-4-256-64", "64-16-256-33"])
 def test_diagnose_agrees_with_an_external_rollout(crl, D, A, H, nt):   # noqa: F811
+    """The values are compared bit for bit as well: crl_ppo_diagnose and crl_rollout_act_device run the critic through the same forward block
+    (csrc/fwd_rs_x3.hpp) on the same observations and parameters, so a difference means the two kernels no longer share it. 64 / 16 / 256 streams W1 from the
+    parameters instead of LDS. The logprobs keep their bar: the two kernels write the log-softmax differently."""
     F = crl._lib
     agent = _agent(crl, D, A, H, nt, params=_params(crl, D, A, H))
     h = agent.handle
@@ -183,6 +186,7 @@ def test_diagnose_agrees_with_an_external_rollout(crl, D, A, H, nt):   # noqa: F
         d = h.diagnose(per_sample=True)
     lp, v = h.read(F.F_LOGPROB), h.read(F.F_VALUE)
     assert _within_bar(d["new_logprob"], lp).all() and _within_bar(d["new_value"], v).all()
+    assert np.array_equal(d["new_value"].view(np.uint32), v.view(np.uint32)), "new_value and CRL_F_VALUE differ in bits"
     assert d["clipfrac"] == 0.0
     # |logratio| of a sample is at most the logprob bar r = 1e-5 max|logprob| + 1e-6; kl_b = (e^x - 1) - x = x^2 / 2 + O(x^3) <= x^2 for |x| <= 1, so the mean
     # over the samples, approx_kl, is below r^2
