@@ -5,7 +5,7 @@
 // any host read-back in between: dqn_collect_kernel (ε-greedy action — q_net forward only on greedy steps —, env step,
 // ring-buffer add, episode bookkeeping, up to the next training step), then the minibatch draw without replacement, both
 // forwards, TD target, Flux.mse, the pullbacks, Adam and the hard target copy as multi-CU kernels.
-// Float64 arithmetic with Float32 weights like the reference (see a2c.hip); relu has no transcendental, every sum runs
+// Float64 arithmetic with Float32 weights like the reference (see a2c.hip; both step the CartPoleEnv{Float64} of env64.hpp); relu has no transcendental, every sum runs
 // in the oracle's order with contraction off ⇒ the run is BIT-IDENTICAL to oracle/dqn_oracle.c.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "env64.hpp"
 #include "ppo_ctx.hpp"
 
 struct crl_dqn;
@@ -42,48 +43,6 @@ struct DQNDev {
   int32_t* idx;                               // [k] minibatch indices into the ring
 };
 
-// CartPoleEnv{Float64}: shared with a2c.hip's restatement (oracle: a2c_cartpole_step)
-__device__ __forceinline__ double dq_sin64(double x) {
-  const double c[10] = {-1.0 / 6, 1.0 / 120, -1.0 / 5040, 1.0 / 362880, -1.0 / 39916800, 1.0 / 6227020800.0,
-                        -1.0 / 1307674368000.0, 1.0 / 355687428096000.0, -1.0 / 121645100408832000.0,
-                        1.0 / 51090942171709440000.0};
-  const double x2 = x * x;
-  double p = c[9];
-#pragma unroll
-  for (int i = 8; i >= 0; --i) p = __builtin_fma(p, x2, c[i]);
-  return __builtin_fma(x * x2, p, x);
-}
-__device__ __forceinline__ double dq_cos64(double x) {
-  const double c[10] = {-0.5, 1.0 / 24, -1.0 / 720, 1.0 / 40320, -1.0 / 3628800, 1.0 / 479001600.0,
-                        -1.0 / 87178291200.0, 1.0 / 20922789888000.0, -1.0 / 6402373705728000.0,
-                        1.0 / 2432902008176640000.0};
-  const double x2 = x * x;
-  double p = c[9];
-#pragma unroll
-  for (int i = 8; i >= 0; --i) p = __builtin_fma(p, x2, c[i]);
-  return __builtin_fma(x2, p, 1.0);
-}
-__device__ __forceinline__ bool dq_cartpole_step(double* s, int& t, int action, int max_steps) {
-#pragma clang fp contract(off)
-  const double gravity = 9.8, masspole = 0.1, totalmass = 1.1, halflength = 0.5, pml = 0.05;
-  const double forcemag = 10.0, dt = 0.02, ththr = 12.0 * 2.0 * 3.141592653589793 / 360.0, xthr = 2.4;
-  t += 1;
-  const double force = action == 1 ? forcemag : -forcemag;
-  const double xdot = s[1], theta = s[2], thetadot = s[3];
-  const double costheta = dq_cos64(theta), sintheta = dq_sin64(theta);
-  const double tmp = (force + pml * thetadot * thetadot * sintheta) / totalmass;
-  const double thetaacc = (gravity * sintheta - costheta * tmp) / (halflength * (4.0 / 3.0 - masspole * costheta * costheta / totalmass));
-  const double xacc = tmp - pml * thetaacc * costheta / totalmass;
-  s[0] += dt * xdot;
-  s[1] += dt * xacc;
-  s[2] += dt * thetadot;
-  s[3] += dt * thetaacc;
-  return (fabs(s[0]) > xthr) || (fabs(s[2]) > ththr) || (t > max_steps);
-}
-__device__ __forceinline__ void dq_env_reset(double* s, uint64_t seed, uint64_t gstep, uint32_t stream) {
-#pragma clang fp contract(off)
-  for (int i = 0; i < 4; ++i) s[i] = 0.1 * u53(philox_env(seed, (uint32_t)i, gstep, stream)) - 0.05;
-}
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
 #pragma clang fp contract(off)
   const double slope = (end_e - start_e) / duration;
@@ -161,7 +120,7 @@ __global__ void __launch_bounds__(128) dqn_collect_kernel(DQNDev a) {
     if (tid == 0) {
       const uint64_t gstep = (uint64_t)c.global_step;
       const int action = need_q ? (qs[1] > qs[0] ? 1 : 0) : action_s;               // dqn.jl:65 argmax: first maximum
-      const bool done = dq_cartpole_step(c.env, c.env_t, action, a.cfg.max_steps);  // dqn.jl:68
+      const bool done = cartpole_step64(c.env, c.env_t, action, a.cfg.max_steps);  // dqn.jl:68
       const double rew = done ? 0.0 : 1.0;
       const size_t p = (size_t)c.ptr;                                                // dqn.jl:71-78 Buffer.add!
       for (int i = 0; i < QD; ++i) { a.rb_state[QD * p + i] = obs[i]; a.rb_next[QD * p + i] = c.env[i]; }
@@ -176,7 +135,7 @@ __global__ void __launch_bounds__(128) dqn_collect_kernel(DQNDev a) {
         }
         c.n_eps += 1;
         c.episode_length = 0; c.episode_return = 0.0;
-        dq_env_reset(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
+        env_reset64(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
       }
       c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step % a.cfg.train_freq == 0) ? 1 : 0;   // dqn.jl:93
     }
@@ -379,7 +338,7 @@ __global__ void dqn_init_kernel(DQNDev a) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   DQNCtl c;
   memset(&c, 0, sizeof(c));
-  dq_env_reset(c.env, a.cfg.seed, 0, 2);                                             // dqn.jl:56 reset!(env)
+  env_reset64(c.env, a.cfg.seed, 0, 2);                                             // dqn.jl:56 reset!(env)
   *a.ctl = c;
 }
 

@@ -172,7 +172,7 @@ __device__ __forceinline__ void acrobot_reset(float (&s)[4], uint64_t seed, uint
 constexpr int ENV_OBS_MAX = 8;
 __device__ __host__ __forceinline__ bool env_stateful(int kind) { return kind == CRL_ENV_CARTPOLE || kind == CRL_ENV_MOUNTAINCAR || kind == CRL_ENV_ACROBOT; }
 __device__ __host__ __forceinline__ int env_state_dim(int kind) { return kind == CRL_ENV_MOUNTAINCAR ? 2 : 4; }
-// episode returns of these kinds can be negative: return_max travels as an order-preserving key (wide_step_stats)
+// episode returns of these kinds can be negative: return_max travels as an order-preserving key (stats.hpp: episode_stats_flush)
 __device__ __host__ __forceinline__ bool env_signed_returns(int kind) { return kind == CRL_ENV_MOUNTAINCAR || kind == CRL_ENV_ACROBOT; }
 
 __device__ __forceinline__ void env_observe(int kind, const float (&s)[4], float (&o)[ENV_OBS_MAX]) {

@@ -99,7 +99,7 @@ struct ExtRecArgs {
 __global__ void __launch_bounds__(256) ext_record_kernel(ExtRecArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   const bool live = e < a.N;
-  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = -__builtin_inf();
+  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
   if (live) {
     const float rew = a.reward_in[e];
     a.reward[e] = rew;                                            // ppo.jl:132,137
@@ -110,21 +110,12 @@ __global__ void __launch_bounds__(256) ext_record_kernel(ExtRecArgs a) {
     float ep_ret = a.ep_return[e] + rew;                          // ppo.jl:145
     if (nd) {                                                     // ppo.jl:147-165
       st_n = 1.0; st_ret = (double)ep_ret; st_len = (double)ep_len; st_max = (double)ep_ret;
-      if (a.ring_cap > 0) {
-        const uint32_t slot = atomicAdd(a.ring_count, 1u);
-        if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)(a.gid0 + (uint32_t)e), a.step};
-      }
+      episode_ring_push(a.ring, a.ring_count, a.ring_cap, ep_ret, ep_len, a.gid0 + (uint32_t)e, a.step);
       ep_ret = 0.0f; ep_len = 0;
     }
     a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
   }
-  // one atomic set per wave (lanes past num_envs bring the neutral elements)
-  st_n = wave_sum(st_n); st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-  st_max = wave_max(st_max);
-  if ((threadIdx.x & 63) == 0 && st_n > 0.0) {
-    atomicAdd(&a.ep_stats[0], st_n); atomicAdd(&a.ep_stats[1], st_ret); atomicAdd(&a.ep_stats[2], st_len);
-    atomicMax(reinterpret_cast<unsigned long long*>(&a.ep_stats[3]), stat_max_key(st_max));
-  }
+  episode_stats_flush(a.ep_stats, st_n, st_ret, st_len, st_max, true);   // lanes past num_envs bring the neutral elements
 }
 
 // The launch of crl_rollout_act_device on the handle's stream.

@@ -222,4 +222,32 @@ __device__ __forceinline__ void mlp_forward_x3(const float* img, const float (&x
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Pieces of a forward pass whose hidden rows are spread over waves (policy.hip: rollout_split3_kernel, rollout_split6_kernel).
+// ------------------------------------------------------------------------------------------------------
+// layer 1's pre-activations of hidden rows 32·mo … 32·mo + 31, C-fragment order; I: NetImageX3 or NetImageX2 (the f32 layer-1 image is the same)
+template <class I, int D>
+__device__ __forceinline__ f32x16 layer1_rows32(const float* img, const float (&cx)[D], int mo, int lane) {
+  const int hf = lane >> 5;
+  f32x16 acc = load16(img + I::B1C + hf * 32 + 16 * mo);
+#pragma unroll
+  for (int ks = 0; ks < D / 2; ++ks) {
+    const float bv = hf ? cx[2 * ks + 1] : cx[2 * ks];
+    acc = mfma32(img[I::WF1 + (mo * (D / 2) + ks) * 64 + lane], bv, acc);
+  }
+  return acc;
+}
+// 16 terms of a head's dot product in mlp_forward_x3's chain order: accv += w16[r] · act(h[r]) over the 16 C-fragment registers of one 32-row block
+template <class Act>
+__device__ __forceinline__ float head_partial16(const float* w16, const f32x16& h, float accv, Act act) {
+  const f32x4* w = reinterpret_cast<const f32x4*>(w16);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 wv = w[q];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) accv = __builtin_fmaf(wv[i], act(h[q * 4 + i]), accv);
+  }
+  return accv;
+}
+
 }  // namespace crl

@@ -13,6 +13,7 @@
 #include "mlp_x3.hpp"
 #include "mlp_x2.hpp"
 #include "ppo_ctx.hpp"
+#include "rollout_env.hpp"
 
 namespace crl {
 
@@ -170,57 +171,41 @@ __global__ void __launch_bounds__(256) env_step_kernel(DevCfg c, const int32_t* 
 // ------------------------------------------------------------------------------------------------------
 // The rollout loop — ppo.jl:123-166 — one launch for all num_steps.
 // ------------------------------------------------------------------------------------------------------
-struct RolloutArgs {
-  DevCfg c;
-  const float* params;
-  float* obs; int32_t* action; float* logprob; float* reward; uint8_t* terminal; float* value;
-  float* env_state; int32_t* env_t; float* cur_obs; uint8_t* next_done; float* ep_return; int32_t* ep_length;
-  double* ep_stats;
-  crl_episode_record* ring; uint32_t* ring_count; int ring_cap;   // per-episode records (ring_cap = 0: off)
-  uint64_t iteration;
-  int stagger;  // s_sleep units (64 clocks) by which waves 4-7 of an 8-wave block start late
-  // GAE fused into the tail of the rollout (crl_ppo_iterate, compat mode): the wave that stepped 32 envs for num_steps steps
-  // scans their value / reward / terminal columns — which it has just written and which still sit in L2 — backwards and
-  // writes advantages and returns (ppo.jl:48-73,173-181): no separate launch, no HBM read of the scan's inputs.
-  float* adv; float* ret; int fuse_gae; float gamma, gl;
-  double* range_err = nullptr;   // fp16x2 weight-window error word (CX2 kernels)
+// RolloutArgs, the env owner's pieces (load / step / store / finish) and the fused GAE tail: rollout_env.hpp. Each kernel's dynamic LDS is carved by ONE
+// layout (offsets in floats, like the weight images): the kernel takes its pointers from it and launch_rollout its byte count.
+template <int A>
+struct RolloutLds1 {   // rollout_cartpole_kernel
+  static constexpr int IMG_A = 0;
+  static constexpr int IMG_C = IMG_A + NetImageX3<4, A, false>::SIZE;       // sized for the critic's bf16x3 fallback image
+  static constexpr int FLAG = IMG_C + NetImageX3<4, 1, false>::SIZE;
+  static constexpr int SIZE = FLAG + 4;
+  static_assert(NetImageX3<4, 1, false>::SIZE >= NetImageX2<4, 1, false>::SIZE, "the bf16x3 critic image (three pieces) is the larger one");
+  static_assert(IMG_C % 4 == 0, "16-byte aligned images");
 };
-
-// gae(values, rewards, terminals, γ, λ) for ONE env (this lane), compat mode (ppo.jl:66: the loop starts at k-1, the last slot
-// is defined as 0 — Q1): the reference's serial Float64 recurrence, step by step ⇒ bit-identical to orc_gae.
-__device__ __forceinline__ void gae_tail_compat(const RolloutArgs& a, int e) {
-#pragma clang fp contract(off)
-  const int nt = a.c.nt, k = a.c.k;
-  size_t idx = (size_t)e + (size_t)nt * (k - 1);
-  float vnext = a.value[idx];
-  uint32_t tnext = a.terminal[idx];
-  a.adv[idx] = 0.0f; a.ret[idx] = 0.0f + vnext;
-  double A = 0.0;
-  // eight steps' inputs are loaded together (the loads cannot be hoisted above the stores by the compiler: it must assume
-  // adv / ret alias the inputs), then the serial recurrence runs on registers: one L2 round trip per eight steps
-  constexpr int CH = 8;
-  for (int t0 = k - 2; t0 >= 0; t0 -= CH) {
-    float v[CH], r[CH]; uint32_t tm[CH];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const bool ok = t0 - i >= 0;
-      const size_t ix = ok ? (size_t)e + (size_t)nt * (t0 - i) : (size_t)e;
-      v[i] = a.value[ix]; r[i] = a.reward[ix]; tm[i] = a.terminal[ix];
-    }
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      if (t0 - i < 0) break;
-      const size_t ix = (size_t)e + (size_t)nt * (t0 - i);
-      const double nonterm = 1.0 - (double)(tnext ? 1 : 0);
-      const double delta = (double)r[i] + ((double)a.gamma * nonterm) * (double)vnext - (double)v[i];
-      const double cc = (double)a.gl * nonterm;
-      A = delta + (cc * A);
-      const float a32 = (float)A;
-      a.adv[ix] = a32; a.ret[ix] = a32 + v[i];
-      vnext = v[i]; tnext = tm[i];
-    }
-  }
-}
+template <int A>
+struct RolloutLds2 {   // rollout_split_kernel
+  static constexpr int IMG_A = 0;
+  static constexpr int IMG_C = IMG_A + NetImageX3<4, A, false>::SIZE;
+  static constexpr int XCH = IMG_C + NetImageX3<4, 1, false>::SIZE;         // float4 [2][TILE] observations
+  static constexpr int SIZE = XCH + 2 * TILE * 4;
+  static_assert(IMG_C % 4 == 0 && XCH % 4 == 0, "16-byte aligned images and float4 region");
+};
+template <int A>
+struct RolloutLds3 {   // rollout_split3_kernel
+  static constexpr int IMG_A = 0;
+  static constexpr int IMG_C = IMG_A + NetImageX3<4, A, false>::SIZE;       // sized for the critic's bf16x3 fallback image
+  static constexpr int XCH = IMG_C + NetImageX3<4, 1, false>::SIZE;         // float4 [2][TILE] observations
+  static constexpr int PCS = XCH + 2 * TILE * 4;                            // bf16x8 [2 waves][2 k-steps][3 pieces][64 lanes]
+  static constexpr int HD = PCS + 2 * 2 * 3 * 64 * 4;                       // [A][64] wave 0's partial head sums
+  static constexpr int FLAG = HD + A * 64;
+  static constexpr int SIZE = FLAG + 4;
+  static_assert(NetImageX3<4, 1, false>::SIZE >= NetImageX2<4, 1, false>::SIZE, "the bf16x3 critic image (three pieces) is the larger one");
+  static_assert(IMG_C % 4 == 0 && XCH % 4 == 0 && PCS % 4 == 0, "16-byte aligned images, float4 and bf16x8 regions");
+};
+static_assert(RolloutLds1<2>::SIZE == NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 4, "the sum launch_rollout used to state");
+static_assert(RolloutLds2<2>::SIZE == NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4, "the sum launch_rollout used to state");
+static_assert(RolloutLds3<2>::SIZE == NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4 + 2 * 2 * 3 * 64 * 4 + 2 * 64 + 4,
+              "the sum launch_rollout used to state");
 
 // CX2: the critic runs as fp16x2 with the exp2-based activation (mlp_x2.hpp) — its output is a value compared at 1e-5, while
 // the actor keeps bf16x3 + the reference's rational tanh_fast because its output decides action indices that are bit-compared.
@@ -228,15 +213,14 @@ __device__ __forceinline__ void gae_tail_compat(const RolloutArgs& a, int e) {
 template <int A, bool CX2>
 __global__ void __launch_bounds__(512, 2) rollout_cartpole_kernel(RolloutArgs a) {
   constexpr int D = 4;
-  constexpr int IASIZE = NetImageX3<D, A, false>::SIZE;
+  using L = RolloutLds1<A>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* imgA0 = smem;
-  float* imgC0 = smem + IASIZE;
+  float* imgA0 = smem + L::IMG_A;
+  float* imgC0 = smem + L::IMG_C;
   bool cx2 = CX2;   // block-uniform
   stage_net_x3<D, A, false>(imgA0, a.params, threadIdx.x, blockDim.x);
   if (CX2) {
-    static_assert(NetImageX3<D, 1, false>::SIZE >= NetImageX2<D, 1, false>::SIZE, "the bf16x3 critic image (three pieces) is the larger one");
-    int* flag = reinterpret_cast<int*>(imgC0 + NetImageX3<D, 1, false>::SIZE);
+    int* flag = reinterpret_cast<int*>(smem + L::FLAG);
     if (!stage_net_x2<D, 1, false>(imgC0, a.params + NetParams<D, A>::SIZE, threadIdx.x, blockDim.x, flag)) {
       if (threadIdx.x == 0 && blockIdx.x == 0) a.range_err[0] = 1.0;   // informational: the fallback ran
       cx2 = false;
@@ -253,18 +237,8 @@ __global__ void __launch_bounds__(512, 2) rollout_cartpole_kernel(RolloutArgs a)
   const int ee = ok ? e : 0;
   const uint32_t gid = c.env_id_offset + (uint32_t)ee;
 
-  float s[4], co[4];
-  {
-    const float4 sv = reinterpret_cast<const float4*>(a.env_state)[ee];
-    const float4 cv = reinterpret_cast<const float4*>(a.cur_obs)[ee];
-    s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
-    co[0] = cv.x; co[1] = cv.y; co[2] = cv.z; co[3] = cv.w;
-  }
-  int t_env = a.env_t[ee];
-  uint8_t nd = a.next_done[ee];
-  float ep_ret = a.ep_return[ee];
-  int ep_len = a.ep_length[ee];
-  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
+  EnvOwner env;
+  env_owner_load(env, a, ee);
 
   // Waves w and w+4 of an 8-wave block share a SIMD and run the same program: started together they march through
   // the MFMA-heavy and VALU-only phases of a step in lockstep and leave the matrix pipe idle; a one-time delay of
@@ -276,69 +250,29 @@ __global__ void __launch_bounds__(512, 2) rollout_cartpole_kernel(RolloutArgs a)
   for (int step = 0; step < c.k; ++step) {
     const uint64_t gstep = a.iteration * (uint64_t)c.k + (uint64_t)step;
     const size_t b = (size_t)ee + (size_t)c.nt * step;
-    ep_len += 1;                                                     // ppo.jl:125
     f32x16 h1[2], h2[2];
-    float z[A], v[1], p[A], lp[A];
+    float z[A], v[1];
     // opaque per-step offset: the weight fragments are re-read from LDS every step instead of being hoisted out of
     // the 128-step loop into ~250 registers (which would halve the waves per SIMD)
     int lds_off = 0;
     asm volatile("" : "+v"(lds_off));
     const float* imgA = imgA0 + lds_off;
     const float* imgC = imgC0 + lds_off;
-    mlp_forward_x3<D, A, false>(imgA, co, h1, h2, z, lane);          // ppo.jl:127 get_action
-    softmax_logsoftmax<A>(z, p, lp);
-    const double u = u53(philox_env(c.seed, gid, gstep, 0));
-    const int act = sample_weights<A>(p, u);
-    float lpa = lp[0];
-#pragma unroll
-    for (int i = 1; i < A; ++i) lpa = (act == i) ? lp[i] : lpa;
-    if (CX2 && cx2) mlp_forward_x2<D, 1, false>(imgC, co, h1, h2, v, lane);  // ppo.jl:128
-    else mlp_forward_x3<D, 1, false>(imgC, co, h1, h2, v, lane);
-    const bool done = cartpole_step(s, t_env, act);                  // ppo.jl:130
-    const float rew = done ? 0.0f : 1.0f;                            // ppo.jl:132 (RLEnvs: reward 0 on the terminal step)
-    if (writer) {                                                    // ppo.jl:133-140 Buffer.add!
-      // obs/action/logprob are next read by the update pass, a full GAE + shuffle later: stream them past the caches
-      // (nontemporal) so the 75 MB the GAE scan needs (value, reward, terminal) stay resident in L2 / Infinity Cache
-      store_nt4(reinterpret_cast<f32x4*>(a.obs) + b, co[0], co[1], co[2], co[3]);
-      __builtin_nontemporal_store(act, a.action + b); __builtin_nontemporal_store(lpa, a.logprob + b);
-      a.reward[b] = rew; a.terminal[b] = nd; a.value[b] = v[0];
-    }
-    co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3];         // ppo.jl:143 next_obs (before reset!, Q7)
-    nd = done ? 1 : 0;                                               // ppo.jl:144
-    ep_ret += rew;                                                   // ppo.jl:145
-    if (done) {                                                      // ppo.jl:147-165
-      if (writer) {
-        st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, (double)ep_ret);
-        if (a.ring_cap > 0) {
-          const uint32_t slot = atomicAdd(a.ring_count, 1u);
-          if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-        }
-      }
-      ep_ret = 0.0f; ep_len = 0;
-      cartpole_reset(s, c.seed, gid, gstep, 1);                      // ppo.jl:164 reset!(env)
-      t_env = 0;
-      if (!c.stale_obs) { co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3]; }
-    }
+    const float cx[4] = {env.co[0], env.co[1], env.co[2], env.co[3]};   // the forwards pick x[2ks + hf] per lane half: from a plain array, so that env stays in registers
+    mlp_forward_x3<D, A, false>(imgA, cx, h1, h2, z, lane);          // ppo.jl:127 get_action
+    float lpa;
+    const int act = env_owner_sample<A>(z, u53(philox_env(c.seed, gid, gstep, 0)), lpa);
+    if (CX2 && cx2) mlp_forward_x2<D, 1, false>(imgC, cx, h1, h2, v, lane);  // ppo.jl:128
+    else mlp_forward_x3<D, 1, false>(imgC, cx, h1, h2, v, lane);
+    if (writer) a.value[b] = v[0];                                   // Buffer.add!'s value; the other fields: env_owner_advance (which moves on env.co)
+    env_owner_advance(env, a, act, lpa, gid, gstep, step, b, writer);
   }
-  if (writer) {
-    reinterpret_cast<float4*>(a.env_state)[e] = make_float4(s[0], s[1], s[2], s[3]);
-    reinterpret_cast<float4*>(a.cur_obs)[e] = make_float4(co[0], co[1], co[2], co[3]);
-    a.env_t[e] = t_env; a.next_done[e] = nd; a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-  }
+  if (writer) env_owner_store(env, a, e);
   if (a.fuse_gae) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's own stores are what the scan reads back
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    if (writer) gae_tail_compat(a, e);
   }
-  // episode statistics of this rollout ("Episode Statistics" record, aggregated): one atomic set per wave
-  st_n = wave_sum(st_n); st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
-  if (lane == 0 && st_n > 0.0) {
-    atomicAdd(&a.ep_stats[0], st_n); atomicAdd(&a.ep_stats[1], st_ret); atomicAdd(&a.ep_stats[2], st_len);
-    // return_max: episode returns are non-negative integers ≤ 501 here, so the f64 bit pattern orders like u64
-    atomicMax(reinterpret_cast<unsigned long long*>(&a.ep_stats[3]), (unsigned long long)__double_as_longlong(st_max));
-  }
+  env_owner_finish(env, a, e, writer);
 }
 
 // Small shards (≤ 512 tiles = 16384 envs, e.g. 8192 envs per GPU under 8-way data parallelism) leave most SIMDs idle and the
@@ -348,11 +282,11 @@ __global__ void __launch_bounds__(512, 2) rollout_cartpole_kernel(RolloutArgs a)
 template <int A>
 __global__ void __launch_bounds__(128) rollout_split_kernel(RolloutArgs a) {
   constexpr int D = 4;
-  constexpr int IASIZE = NetImageX3<D, A, false>::SIZE, ICSIZE = NetImageX3<D, 1, false>::SIZE;
+  using L = RolloutLds2<A>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* imgA0 = smem;
-  float* imgC0 = smem + IASIZE;
-  float4* xch = reinterpret_cast<float4*>(smem + IASIZE + ICSIZE);  // [2][TILE] observations
+  float* imgA0 = smem + L::IMG_A;
+  float* imgC0 = smem + L::IMG_C;
+  float4* xch = reinterpret_cast<float4*>(smem + L::XCH);           // [2][TILE] observations
   stage_net_x3<D, A, false>(imgA0, a.params, threadIdx.x, blockDim.x);
   stage_net_x3<D, 1, false>(imgC0, a.params + NetParams<D, A>::SIZE, threadIdx.x, blockDim.x);
   const DevCfg& c = a.c;
@@ -363,18 +297,10 @@ __global__ void __launch_bounds__(128) rollout_split_kernel(RolloutArgs a) {
   const int ee = ok ? e : 0;
   const uint32_t gid = c.env_id_offset + (uint32_t)ee;
 
-  float s[4] = {0, 0, 0, 0}, co[4] = {0, 0, 0, 0};
-  int t_env = 0, ep_len = 0;
-  uint8_t nd = 0;
-  float ep_ret = 0.0f;
-  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
+  EnvOwner env;
   if (wave == 0) {
-    const float4 sv = reinterpret_cast<const float4*>(a.env_state)[ee];
-    const float4 cv = reinterpret_cast<const float4*>(a.cur_obs)[ee];
-    s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
-    co[0] = cv.x; co[1] = cv.y; co[2] = cv.z; co[3] = cv.w;
-    t_env = a.env_t[ee]; nd = a.next_done[ee]; ep_ret = a.ep_return[ee]; ep_len = a.ep_length[ee];
-    if (hf == 0) xch[j] = cv;
+    env_owner_load(env, a, ee);
+    if (hf == 0) xch[j] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
   }
   __syncthreads();
 
@@ -385,41 +311,13 @@ __global__ void __launch_bounds__(128) rollout_split_kernel(RolloutArgs a) {
     asm volatile("" : "+v"(lds_off));  // keep the weight reads in LDS (see rollout_cartpole_kernel)
     f32x16 h1[2], h2[2];
     if (wave == 0) {
-      ep_len += 1;                                                   // ppo.jl:125
-      float z[A], p[A], lp[A];
+      float z[A];
       // the step's uniform does not depend on the network: drawn first, its ≈80 integer instructions can sit in the shadow of
       // the forward pass's MFMA chains instead of behind the softmax on the step's critical path
       const double u = u53(philox_env(c.seed, gid, gstep, 0));
-      mlp_forward_x3<D, A, false>(imgA0 + lds_off, co, h1, h2, z, lane);  // ppo.jl:127 get_action
-      softmax_logsoftmax<A>(z, p, lp);
-      const int act = sample_weights<A>(p, u);
-      float lpa = lp[0];
-#pragma unroll
-      for (int i = 1; i < A; ++i) lpa = (act == i) ? lp[i] : lpa;
-      const bool done = cartpole_step(s, t_env, act);                // ppo.jl:130
-      const float rew = done ? 0.0f : 1.0f;                          // ppo.jl:132
-      if (writer) {                                                  // ppo.jl:133-140 Buffer.add! (value: wave 1)
-        store_nt4(reinterpret_cast<f32x4*>(a.obs) + b, co[0], co[1], co[2], co[3]);
-        __builtin_nontemporal_store(act, a.action + b); __builtin_nontemporal_store(lpa, a.logprob + b);
-        a.reward[b] = rew; a.terminal[b] = nd;
-      }
-      co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3];       // ppo.jl:143
-      nd = done ? 1 : 0;                                             // ppo.jl:144
-      ep_ret += rew;                                                 // ppo.jl:145
-      if (done) {                                                    // ppo.jl:147-165
-        if (writer) {
-          st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, (double)ep_ret);
-          if (a.ring_cap > 0) {
-            const uint32_t slot = atomicAdd(a.ring_count, 1u);
-            if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-          }
-        }
-        ep_ret = 0.0f; ep_len = 0;
-        cartpole_reset(s, c.seed, gid, gstep, 1);                    // ppo.jl:164
-        t_env = 0;
-        if (!c.stale_obs) { co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3]; }
-      }
-      if (hf == 0) xch[((step + 1) & 1) * TILE + j] = make_float4(co[0], co[1], co[2], co[3]);
+      mlp_forward_x3<D, A, false>(imgA0 + lds_off, env.co, h1, h2, z, lane);  // ppo.jl:127 get_action
+      env_owner_step<A>(env, a, z, u, gid, gstep, step, b, writer);   // Buffer.add!'s value: wave 1
+      if (hf == 0) xch[((step + 1) & 1) * TILE + j] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
     } else {
       const float4 cv = xch[(step & 1) * TILE + j];
       const float cx[4] = {cv.x, cv.y, cv.z, cv.w};
@@ -429,21 +327,9 @@ __global__ void __launch_bounds__(128) rollout_split_kernel(RolloutArgs a) {
     }
     __syncthreads();
   }
-  if (wave == 0) {
-    if (writer) {
-      reinterpret_cast<float4*>(a.env_state)[e] = make_float4(s[0], s[1], s[2], s[3]);
-      reinterpret_cast<float4*>(a.cur_obs)[e] = make_float4(co[0], co[1], co[2], co[3]);
-      a.env_t[e] = t_env; a.next_done[e] = nd; a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-      // value[] was written by wave 1 of this block; the step loop's closing __syncthreads() made it visible here
-      if (a.fuse_gae) gae_tail_compat(a, e);
-    }
-    st_n = wave_sum(st_n); st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
-    if (lane == 0 && st_n > 0.0) {
-      atomicAdd(&a.ep_stats[0], st_n); atomicAdd(&a.ep_stats[1], st_ret); atomicAdd(&a.ep_stats[2], st_len);
-      atomicMax(reinterpret_cast<unsigned long long*>(&a.ep_stats[3]), (unsigned long long)__double_as_longlong(st_max));
-    }
+  if (wave == 0) {   // value[] was written by wave 1 of this block; the step loop's closing __syncthreads() made it visible to the GAE tail
+    if (writer) env_owner_store(env, a, e);
+    env_owner_finish(env, a, e, writer);
   }
 }
 
@@ -462,15 +348,14 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
   constexpr int D = 4;
   using IA = NetImageX3<D, A, false>;
   using IC = NetImageX2<D, 1, false>;
-  constexpr int ICMAX = NetImageX3<D, 1, false>::SIZE;   // room for the bf16x3 fallback image of the critic
-  static_assert(ICMAX >= IC::SIZE, "the bf16x3 critic image (three pieces) is the larger one");
+  using L = RolloutLds3<A>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* imgA0 = smem;
-  float* imgC0 = imgA0 + IA::SIZE;
-  float4* xch = reinterpret_cast<float4*>(imgC0 + ICMAX);                  // [2][TILE] observations
-  bf16x8* pcs = reinterpret_cast<bf16x8*>(reinterpret_cast<float*>(xch) + 2 * TILE * 4);   // [2 waves][2 k-steps][3 pieces][64 lanes]
-  float* hd = reinterpret_cast<float*>(pcs + 2 * 2 * 3 * 64);              // [A][64] wave 0's partial head sums
-  int* flag = reinterpret_cast<int*>(hd + A * 64);
+  float* imgA0 = smem + L::IMG_A;
+  float* imgC0 = smem + L::IMG_C;
+  float4* xch = reinterpret_cast<float4*>(smem + L::XCH);                  // [2][TILE] observations
+  bf16x8* pcs = reinterpret_cast<bf16x8*>(smem + L::PCS);                  // [2 waves][2 k-steps][3 pieces][64 lanes]
+  float* hd = smem + L::HD;                                                // [A][64] wave 0's partial head sums
+  int* flag = reinterpret_cast<int*>(smem + L::FLAG);
   stage_net_x3<D, A, false>(imgA0, a.params, threadIdx.x, blockDim.x);
   bool cx2 = true;   // block-uniform: false = the critic's weights left the fp16 window (|w| >= 255, or all |w| < 2^-11) and it runs as bf16x3
   if (!stage_net_x2<D, 1, false>(imgC0, a.params + NetParams<D, A>::SIZE, threadIdx.x, blockDim.x, flag)) {
@@ -486,18 +371,10 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
   const int ee = ok ? e : 0;
   const uint32_t gid = c.env_id_offset + (uint32_t)ee;
 
-  float s[4] = {0, 0, 0, 0}, co[4] = {0, 0, 0, 0};
-  int t_env = 0, ep_len = 0;
-  uint8_t nd = 0;
-  float ep_ret = 0.0f;
-  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
+  EnvOwner env;
   if (wave == 1) {   // the wave that ends the head's chain has the logits first: it samples and owns the env
-    const float4 sv = reinterpret_cast<const float4*>(a.env_state)[ee];
-    const float4 cv = reinterpret_cast<const float4*>(a.cur_obs)[ee];
-    s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
-    co[0] = cv.x; co[1] = cv.y; co[2] = cv.z; co[3] = cv.w;
-    t_env = a.env_t[ee]; nd = a.next_done[ee]; ep_ret = a.ep_return[ee]; ep_len = a.ep_length[ee];
-    if (hf == 0) xch[j] = cv;
+    env_owner_load(env, a, ee);
+    if (hf == 0) xch[j] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
   }
   __syncthreads();
 
@@ -510,17 +387,11 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
       const int mo = wave;
       const float* img = imgA0 + lds_off;
       float cx[4];
-      if (wave == 1) { cx[0] = co[0]; cx[1] = co[1]; cx[2] = co[2]; cx[3] = co[3]; }
+      if (wave == 1) { cx[0] = env.co[0]; cx[1] = env.co[1]; cx[2] = env.co[2]; cx[3] = env.co[3]; }
       else { const float4 cv = xch[(step & 1) * TILE + j]; cx[0] = cv.x; cx[1] = cv.y; cx[2] = cv.z; cx[3] = cv.w; }
       double u = 0.0;
-      if (wave == 1) { ep_len += 1; u = u53(philox_env(c.seed, gid, gstep, 0)); }           // ppo.jl:125; drawn early (see split kernel)
-      // layer 1, this wave's 32 rows
-      f32x16 acc = load16(img + IA::B1C + hf * 32 + 16 * mo);
-#pragma unroll
-      for (int ks = 0; ks < D / 2; ++ks) {
-        const float bv = hf ? cx[2 * ks + 1] : cx[2 * ks];
-        acc = mfma32(img[IA::WF1 + (mo * (D / 2) + ks) * 64 + lane], bv, acc);
-      }
+      if (wave == 1) u = u53(philox_env(c.seed, gid, gstep, 0));                             // drawn early (see split kernel)
+      f32x16 acc = layer1_rows32<IA>(img, cx, mo, lane);                                     // layer 1, this wave's 32 rows
       f32x16 h;
 #pragma unroll
       for (int r = 0; r < 16; ++r) h[r] = tanh_fast(acc[r]);
@@ -551,64 +422,18 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) h[r] = tanh_fast(acc[r]);
       // head: one chain per lane half over idx = 0 … 31 (mlp_forward_x3): wave 0 owns idx 0-15, wave 1 continues with 16-31
+      const auto same = [](float x) { return x; };
       if (mo == 0) {
 #pragma unroll
-        for (int o = 0; o < A; ++o) {
-          const f32x4* w = reinterpret_cast<const f32x4*>(img + IA::W3 + o * 64 + hf * 32);
-          float accv = 0.0f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 wv = w[q];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) accv = __builtin_fmaf(wv[i], h[q * 4 + i], accv);
-          }
-          hd[o * 64 + lane] = accv;
-        }
+        for (int o = 0; o < A; ++o) hd[o * 64 + lane] = head_partial16(img + IA::W3 + o * 64 + hf * 32, h, 0.0f, same);
       }
       __syncthreads();                                                                       // (2) wave 0's partial sums are there
       if (mo == 1) {
-        float z[A], p[A], lp[A];
+        float z[A];
 #pragma unroll
-        for (int o = 0; o < A; ++o) {
-          const f32x4* w = reinterpret_cast<const f32x4*>(img + IA::W3 + o * 64 + hf * 32);
-          float accv = hd[o * 64 + lane];
-#pragma unroll
-          for (int q = 4; q < 8; ++q) {
-            const f32x4 wv = w[q];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) accv = __builtin_fmaf(wv[i], h[(q - 4) * 4 + i], accv);
-          }
-          z[o] = add32(accv) + img[IA::B3 + o];
-        }
-        softmax_logsoftmax<A>(z, p, lp);                                                     // ppo.jl:127 get_action
-        const int act = sample_weights<A>(p, u);
-        float lpa = lp[0];
-#pragma unroll
-        for (int i = 1; i < A; ++i) lpa = (act == i) ? lp[i] : lpa;
-        const bool done = cartpole_step(s, t_env, act);                                      // ppo.jl:130
-        const float rew = done ? 0.0f : 1.0f;                                                // ppo.jl:132
-        if (writer) {                                                                        // ppo.jl:133-140 Buffer.add! (value: wave 2)
-          store_nt4(reinterpret_cast<f32x4*>(a.obs) + b, co[0], co[1], co[2], co[3]);
-          __builtin_nontemporal_store(act, a.action + b); __builtin_nontemporal_store(lpa, a.logprob + b);
-          a.reward[b] = rew; a.terminal[b] = nd;
-        }
-        co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3];                             // ppo.jl:143
-        nd = done ? 1 : 0;                                                                   // ppo.jl:144
-        ep_ret += rew;                                                                       // ppo.jl:145
-        if (done) {                                                                          // ppo.jl:147-165
-          if (writer) {
-            st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, (double)ep_ret);
-            if (a.ring_cap > 0) {
-              const uint32_t slot = atomicAdd(a.ring_count, 1u);
-              if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-            }
-          }
-          ep_ret = 0.0f; ep_len = 0;
-          cartpole_reset(s, c.seed, gid, gstep, 1);                                          // ppo.jl:164
-          t_env = 0;
-          if (!c.stale_obs) { co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3]; }
-        }
-        if (hf == 0) xch[((step + 1) & 1) * TILE + j] = make_float4(co[0], co[1], co[2], co[3]);
+        for (int o = 0; o < A; ++o) z[o] = add32(head_partial16(img + IA::W3 + o * 64 + hf * 32 + 16, h, hd[o * 64 + lane], same)) + img[IA::B3 + o];
+        env_owner_step<A>(env, a, z, u, gid, gstep, step, b, writer);                          // ppo.jl:127 get_action … Buffer.add! (value: wave 2)
+        if (hf == 0) xch[((step + 1) & 1) * TILE + j] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
       }
     } else if (!cx2) {
       // critic as bf16x3 (the fallback flavour): same three barriers per step
@@ -625,13 +450,7 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
       const float* img = imgC0 + lds_off;
       const float4 cv = xch[(step & 1) * TILE + j];
       const float cx[4] = {cv.x, cv.y, cv.z, cv.w};
-      f32x16 a0 = load16(img + IC::B1C + hf * 32), a1 = load16(img + IC::B1C + hf * 32 + 16);
-#pragma unroll
-      for (int ks = 0; ks < D / 2; ++ks) {
-        const float bv = hf ? cx[2 * ks + 1] : cx[2 * ks];
-        a0 = mfma32(img[IC::WF1 + (0 * (D / 2) + ks) * 64 + lane], bv, a0);
-        a1 = mfma32(img[IC::WF1 + (1 * (D / 2) + ks) * 64 + lane], bv, a1);
-      }
+      f32x16 a0 = layer1_rows32<IC>(img, cx, 0, lane), a1 = layer1_rows32<IC>(img, cx, 1, lane);
       f32x16 h1s[2];
 #pragma unroll
       for (int r = 0; r < 16; ++r) { h1s[0][r] = tanh_exp2_arg(a0[r], X2_ACT_SCALE); h1s[1][r] = tanh_exp2_arg(a1[r], X2_ACT_SCALE); }
@@ -656,21 +475,9 @@ __global__ void __launch_bounds__(192) rollout_split3_kernel(RolloutArgs a) {
     }
     __syncthreads();                                                                         // (3) next observations are published
   }
-  if (wave == 1) {
-    if (writer) {
-      reinterpret_cast<float4*>(a.env_state)[e] = make_float4(s[0], s[1], s[2], s[3]);
-      reinterpret_cast<float4*>(a.cur_obs)[e] = make_float4(co[0], co[1], co[2], co[3]);
-      a.env_t[e] = t_env; a.next_done[e] = nd; a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-      // value[] was written by wave 2 of this block; the step loop's closing __syncthreads() made it visible here
-      if (a.fuse_gae) gae_tail_compat(a, e);
-    }
-    st_n = wave_sum(st_n); st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
-    if (lane == 0 && st_n > 0.0) {
-      atomicAdd(&a.ep_stats[0], st_n); atomicAdd(&a.ep_stats[1], st_ret); atomicAdd(&a.ep_stats[2], st_len);
-      atomicMax(reinterpret_cast<unsigned long long*>(&a.ep_stats[3]), (unsigned long long)__double_as_longlong(st_max));
-    }
+  if (wave == 1) {   // value[] was written by wave 2 of this block; the step loop's closing __syncthreads() made it visible to the GAE tail
+    if (writer) env_owner_store(env, a, e);
+    env_owner_finish(env, a, e, writer);
   }
 }
 
@@ -728,28 +535,100 @@ __device__ __forceinline__ void stage_net_a16(float* img, const float* __restric
   for (int idx = tid; idx < A; idx += nthreads) img[I::B3 + idx] = p[P::B3 + idx];
 }
 
+template <int A>
+struct RolloutLds6 {   // rollout_split6_kernel
+  static constexpr int IMG_A = 0;
+  static constexpr int IMG_C = IMG_A + NetImageA16<A>::SIZE;                // sized for the critic's bf16x3 fallback image
+  static constexpr int XCH = IMG_C + NetImageX3<4, 1, false>::SIZE;         // float4 [2][TILE] observations
+  static constexpr int PCS_A = XCH + 2 * TILE * 4;                          // uint2 [s 2][ct 2][piece 3][lane 64][half 2]: the actor's h1 pieces in B-fragment order
+  static constexpr int PCS_C = PCS_A + 2 * 2 * 3 * 64 * 2 * 2;              // f16x8 [mo 2][q 2][piece 2][lane 64]: the critic's h1 pieces (three bf16 pieces in the fallback flavour: sized for those)
+  static constexpr int HD_A = PCS_C + 2 * 2 * 3 * 64 * 4;                   // [wave 4][A][TILE] partial logits
+  static constexpr int HD_C = HD_A + 4 * A * TILE;                          // [mo 2][TILE] partial values
+  static constexpr int UBUF = HD_C + 2 * TILE;                              // double [2][TILE]: the next step's uniforms
+  static constexpr int RBUF = UBUF + 2 * 2 * TILE;                          // float4 [2][TILE]: the next step's reset states
+  static constexpr int FLAG = RBUF + 4 * 2 * TILE;
+  static constexpr int SIZE = FLAG + 4;
+  static_assert(NetImageX3<4, 1, false>::SIZE >= NetImageX2<4, 1, false>::SIZE, "the bf16x3 critic image (three pieces) is the larger one");
+  static_assert(IMG_C % 4 == 0 && XCH % 4 == 0 && PCS_A % 4 == 0 && PCS_C % 4 == 0 && RBUF % 4 == 0, "16-byte aligned images, float4, uint2 / bf16x8 and f16x8 regions");
+  static_assert(UBUF % 2 == 0, "8-byte aligned doubles");
+};
+static_assert(RolloutLds6<2>::SIZE == NetImageA16<2>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4 + 2 * 2 * 3 * 64 * 2 * 2 + 2 * 2 * 3 * 64 * 4 + 4 * 2 * TILE + 2 * TILE +
+                                          2 * 2 * TILE + 4 * 2 * TILE + 4, "the sum launch_rollout used to state");
+
+// The critic's two flavours in the six-wave kernel: what differs between the fp16x2 critic and its bf16x3 fallback inside ONE body (split6_critic_step)
+struct Split6CriticX2 {
+  using I = NetImageX2<4, 1, false>; using V = f16x8; using P = P2;
+  static constexpr int NP = 2;       // pieces per operand
+  static __device__ __forceinline__ float act1(float x) { return tanh_exp2_arg(x, X2_ACT_SCALE); }
+  static __device__ __forceinline__ float act2(float x) { return tanh_exp2(x, TWO_LOG2E * X2_FWD_UNSCALE, 1.0f); }
+  static __device__ __forceinline__ void put(V* dst, const float (&xb)[8]) { const P2 p = split2(xb); dst[0] = p.hi; dst[64] = p.lo; }
+  static __device__ __forceinline__ f32x16 kstep(const float* img, int mo, int ks, int lane, const V* src, f32x16 acc) {
+    P2 bq; bq.hi = src[0]; bq.lo = src[64];
+    return mfma_x2(load_wfrag2(img + I::WF2H, mo, ks, lane), bq, acc);
+  }
+};
+struct Split6CriticX3 {
+  using I = NetImageX3<4, 1, false>; using V = bf16x8; using P = P3;
+  static constexpr int NP = 3;
+  static __device__ __forceinline__ float act1(float x) { return tanh_fast(x); }
+  static __device__ __forceinline__ float act2(float x) { return tanh_fast(x); }
+  static __device__ __forceinline__ void put(V* dst, const float (&xb)[8]) { const P3 p = split3(xb); dst[0] = p.hi; dst[64] = p.mid; dst[128] = p.lo; }
+  static __device__ __forceinline__ f32x16 kstep(const float* img, int mo, int ks, int lane, const V* src, f32x16 acc) {
+    P3 bq; bq.hi = src[0]; bq.mid = src[64]; bq.lo = src[128];
+    acc = mfma_x3(load_wfrag(img + I::WF2P, mo, ks, lane), bq, acc);
+    __builtin_amdgcn_sched_barrier(0);
+    return acc;
+  }
+};
+// One step of the critic (ppo.jl:128) on two waves: wave 4 + mo owns hidden rows 32·mo … of both layers (the split3 kernel's actor structure), up to and
+// including barrier (2), after which hdC holds the two partial values. Every k-step's B pieces come back from LDS, this wave's own too: 8 / 12 registers
+// live instead of 32 / 48, which keeps the kernel inside 128 registers (mlp_forward_x3 whole on one wave needs 221 VGPRs, which alone made the kernel too
+// fat for the shuffle's blocks to share its CUs: the iteration's first leg then ended with the shuffle, not the rollout).
+template <class F>
+__device__ __forceinline__ void split6_critic_step(const float* img, const float* xcur, void* pcsC, float* hdC, int mo, int lane) {
+  using I = typename F::I;
+  const int j = lane & 31, hf = lane >> 5;
+  const float4 cv = reinterpret_cast<const float4*>(xcur)[j];
+  const float cx[4] = {cv.x, cv.y, cv.z, cv.w};
+  f32x16 acc = layer1_rows32<I>(img, cx, mo, lane);
+  typename F::V* pcs = reinterpret_cast<typename F::V*>(pcsC);       // [mo 2][q 2][piece NP][lane 64]
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    float xb[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xb[i] = F::act1(acc[8 * q + i]);
+    F::put(pcs + ((mo * 2 + q) * F::NP) * 64 + lane, xb);
+  }
+  __syncthreads();                                                                          // (1)
+  acc = load16(img + I::B2C + hf * 32 + 16 * mo);
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) acc = F::kstep(img, mo, ks, lane, pcs + (((ks >> 1) * 2 + (ks & 1)) * F::NP) * 64 + lane, acc);
+  const float accv = add32(head_partial16(img + I::W3 + hf * 32 + 16 * mo, acc, 0.0f, [](float x) { return F::act2(x); }));
+  if (hf == 0) hdC[mo * TILE + j] = accv;
+  __syncthreads();                                                                          // (2)
+}
+
 // 128 VGPRs at most: six waves on four SIMDs put two of them on two SIMDs, and 2 x 128 leaves the other half of those register files to the shuffle's leaf blocks
 // (1024 threads = four 56-register waves per SIMD), which otherwise wait for the whole rollout to end and the iteration's first leg gains nothing
 template <int A>
 __global__ void __attribute__((amdgpu_flat_work_group_size(384, 384), amdgpu_waves_per_eu(4, 4))) rollout_split6_kernel(RolloutArgs a) {
   constexpr int D = 4;
   using IA = NetImageA16<A>;
-  using IC = NetImageX2<D, 1, false>;
-  constexpr int ICMAX = NetImageX3<D, 1, false>::SIZE;   // room for the bf16x3 fallback image of the critic
+  using L = RolloutLds6<A>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* imgA0 = smem;
-  float* imgC0 = imgA0 + IA::SIZE;
-  float* xch = imgC0 + ICMAX;                                              // [2][TILE][4] observations
-  uint2* pcsA = reinterpret_cast<uint2*>(xch + 2 * TILE * 4);              // [s 2][ct 2][piece 3][lane 64][half 2] x 8 B: the actor's h1 pieces in B-fragment order
-  f16x8* pcsC = reinterpret_cast<f16x8*>(pcsA + 2 * 2 * 3 * 64 * 2);       // [mo 2][q 2][piece 2][lane 64]: the critic's h1 pieces (three bf16 pieces in the fallback flavour: sized for those)
-  float* hdA = reinterpret_cast<float*>(pcsC + 2 * 2 * 3 * 64);            // [wave 4][A][TILE] partial logits
-  float* hdC = hdA + 4 * A * TILE;                                         // [mo 2][TILE] partial values
+  float* imgA0 = smem + L::IMG_A;
+  float* imgC0 = smem + L::IMG_C;
+  float* xch = smem + L::XCH;                                              // [2][TILE][4] observations
+  uint2* pcsA = reinterpret_cast<uint2*>(smem + L::PCS_A);
+  float* pcsC = smem + L::PCS_C;
+  float* hdA = smem + L::HD_A;
+  float* hdC = smem + L::HD_C;
   // The two Philox calls of a step — the action draw and the reset state of an env that ends — depend on (seed, env, step) only: waves 1 and 2, idle
   // between barriers (2) and (3) while wave 0 samples and steps the envs, compute them for the NEXT step and leave them here (100 instructions each
   // off the critical wave's path: 2.65 -> 2.3 µs per step)
-  double* ubuf = reinterpret_cast<double*>(hdC + 2 * TILE);                // [2][TILE]
-  float4* rbuf = reinterpret_cast<float4*>(ubuf + 2 * TILE);               // [2][TILE]
-  int* flag = reinterpret_cast<int*>(rbuf + 2 * TILE);
+  double* ubuf = reinterpret_cast<double*>(smem + L::UBUF);
+  float4* rbuf = reinterpret_cast<float4*>(smem + L::RBUF);
+  int* flag = reinterpret_cast<int*>(smem + L::FLAG);
   stage_net_a16<A>(imgA0, a.params, threadIdx.x, blockDim.x);
   bool cx2 = true;   // block-uniform: false = the critic's weights left the fp16 window and wave 4 runs it as bf16x3
   if (!stage_net_x2<D, 1, false>(imgC0, a.params + NetParams<D, A>::SIZE, threadIdx.x, blockDim.x, flag)) {
@@ -766,18 +645,10 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(384, 384), amdgpu_wav
   const bool writer = ok && envlane;
   const int ee = ok ? e : 0;
   const uint32_t gid = c.env_id_offset + (uint32_t)ee;
-  float s[4] = {0, 0, 0, 0}, co[4] = {0, 0, 0, 0};
-  int t_env = 0, ep_len = 0;
-  uint8_t nd = 0;
-  float ep_ret = 0.0f;
-  double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
+  EnvOwner env;
   if (envlane) {
-    const float4 sv = reinterpret_cast<const float4*>(a.env_state)[ee];
-    const float4 cv = reinterpret_cast<const float4*>(a.cur_obs)[ee];
-    s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
-    co[0] = cv.x; co[1] = cv.y; co[2] = cv.z; co[3] = cv.w;
-    t_env = a.env_t[ee]; nd = a.next_done[ee]; ep_ret = a.ep_return[ee]; ep_len = a.ep_length[ee];
-    reinterpret_cast<float4*>(xch)[lane] = cv;
+    env_owner_load(env, a, ee);
+    reinterpret_cast<float4*>(xch)[lane] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
   }
   {
     const uint64_t g0 = a.iteration * (uint64_t)c.k;
@@ -810,7 +681,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(384, 384), amdgpu_wav
     asm volatile("" : "+v"(lds_off));  // keep the weight reads in LDS (see rollout_cartpole_kernel)
     const float* xcur = xch + (step & 1) * (TILE * 4) + lds_off;
     if (wave < 4) {
-      if (envlane) ep_len += 1;                                                               // ppo.jl:125
       // layer 1: this wave's 16 rows, two 16-sample tiles
       f32x4 h1[2];
 #pragma unroll
@@ -873,39 +743,13 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(384, 384), amdgpu_wav
       }
       __syncthreads();                                                                        // (2) every wave's partial logits (and the critic's partial values) are there
       if (envlane) {
-        float z[A], p[A], lp[A];
+        float z[A];
 #pragma unroll
-        for (int o = 0; o < A; ++o)
-          z[o] = ((hdA[(0 * A + o) * TILE + lane] + hdA[(1 * A + o) * TILE + lane]) + (hdA[(2 * A + o) * TILE + lane] + hdA[(3 * A + o) * TILE + lane])) + imgA0[IA::B3 + o];
-        softmax_logsoftmax<A>(z, p, lp);                                                      // ppo.jl:127 get_action
-        const int act = sample_weights<A>(p, ubuf[(step & 1) * TILE + lane]);                 // the draw of (env, step): Philox stream 0, computed a step ahead by wave 1
-        float lpa = lp[0];
-#pragma unroll
-        for (int i = 1; i < A; ++i) lpa = (act == i) ? lp[i] : lpa;
-        const bool done = cartpole_step(s, t_env, act);                                       // ppo.jl:130
-        const float rew = done ? 0.0f : 1.0f;                                                 // ppo.jl:132
-        if (writer) {                                                                         // ppo.jl:133-140 Buffer.add! (value: wave 4)
-          store_nt4(reinterpret_cast<f32x4*>(a.obs) + b, co[0], co[1], co[2], co[3]);
-          __builtin_nontemporal_store(act, a.action + b); __builtin_nontemporal_store(lpa, a.logprob + b);
-          a.reward[b] = rew; a.terminal[b] = nd;
-        }
-        co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3];                              // ppo.jl:143
-        nd = done ? 1 : 0;                                                                    // ppo.jl:144
-        ep_ret += rew;                                                                        // ppo.jl:145
-        if (done) {                                                                           // ppo.jl:147-165
-          if (writer) {
-            st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = fmax(st_max, (double)ep_ret);
-            if (a.ring_cap > 0) {
-              const uint32_t slot = atomicAdd(a.ring_count, 1u);
-              if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-            }
-          }
-          ep_ret = 0.0f; ep_len = 0;
-          { const float4 rv = rbuf[(step & 1) * TILE + lane]; s[0] = rv.x; s[1] = rv.y; s[2] = rv.z; s[3] = rv.w; }   // ppo.jl:164 reset!: cartpole_reset(seed, env, step), computed a step ahead by wave 2
-          t_env = 0;
-          if (!c.stale_obs) { co[0] = s[0]; co[1] = s[1]; co[2] = s[2]; co[3] = s[3]; }
-        }
-        reinterpret_cast<float4*>(xch + ((step + 1) & 1) * (TILE * 4))[lane] = make_float4(co[0], co[1], co[2], co[3]);
+        for (int i = 0; i < A; ++i)
+          z[i] = ((hdA[(0 * A + i) * TILE + lane] + hdA[(1 * A + i) * TILE + lane]) + (hdA[(2 * A + i) * TILE + lane] + hdA[(3 * A + i) * TILE + lane])) + imgA0[IA::B3 + i];
+        // the draw of (env, step) — Philox stream 0 — and the reset state were computed a step ahead by waves 1 and 2; value: wave 4
+        env_owner_step<A>(env, a, z, ubuf[(step & 1) * TILE + lane], gid, gstep, step, b, writer, rbuf + (step & 1) * TILE + lane);
+        reinterpret_cast<float4*>(xch + ((step + 1) & 1) * (TILE * 4))[lane] = make_float4(env.co[0], env.co[1], env.co[2], env.co[3]);
       } else if (wave == 1 && lane < 32) {
         ubuf[((step + 1) & 1) * TILE + lane] = u53(philox_env(c.seed, gid, gstep + 1, 0));
       } else if (wave == 2 && lane < 32) {
@@ -913,111 +757,19 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(384, 384), amdgpu_wav
         cartpole_reset(r, c.seed, gid, gstep + 1, 1);
         rbuf[((step + 1) & 1) * TILE + lane] = make_float4(r[0], r[1], r[2], r[3]);
       }
-    } else if (!cx2) {
-      // critic as bf16x3 (the fallback flavour: a hidden-layer weight left the fp16 window), in the same two-wave form — wave 4 + mo owns hidden rows 32·mo …
-      // (mlp_forward_x3 whole on one wave needs 221 VGPRs, which alone made this kernel too fat for the shuffle's blocks to share its CUs: the iteration's
-      // first leg then ended with the shuffle, not the rollout)
-      const int mo = wave - 4, j = lane & 31, hf = lane >> 5;
-      using IC3 = NetImageX3<D, 1, false>;
-      const float* img = imgC0 + lds_off;
-      const float4 cv = reinterpret_cast<const float4*>(xcur)[j];
-      const float cx[4] = {cv.x, cv.y, cv.z, cv.w};
-      f32x16 acc = load16(img + IC3::B1C + hf * 32 + 16 * mo);
-#pragma unroll
-      for (int ks = 0; ks < D / 2; ++ks) {
-        const float bv = hf ? cx[2 * ks + 1] : cx[2 * ks];
-        acc = mfma32(img[IC3::WF1 + (mo * (D / 2) + ks) * 64 + lane], bv, acc);
-      }
-      bf16x8* pcs3 = reinterpret_cast<bf16x8*>(pcsC);                  // [mo 2][q 2][piece 3][lane 64]
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        float xb[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xb[i] = tanh_fast(acc[8 * q + i]);
-        const P3 mine = split3(xb);
-        bf16x8* dst = pcs3 + ((mo * 2 + q) * 3) * 64 + lane;
-        dst[0] = mine.hi; dst[64] = mine.mid; dst[128] = mine.lo;
-      }
-      __syncthreads();                                                                        // (1)
-      acc = load16(img + IC3::B2C + hf * 32 + 16 * mo);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {     // every k-step's B pieces come back from LDS (this wave's own too): 12 registers live instead of 48
-        const bf16x8* src = pcs3 + (((ks >> 1) * 2 + (ks & 1)) * 3) * 64 + lane;
-        P3 bq; bq.hi = src[0]; bq.mid = src[64]; bq.lo = src[128];
-        acc = mfma_x3(load_wfrag(img + IC3::WF2P, mo, ks, lane), bq, acc);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const f32x4* w = reinterpret_cast<const f32x4*>(img + IC3::W3 + hf * 32 + 16 * mo);
-      float accv = 0.0f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 wv = w[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) accv = __builtin_fmaf(wv[i], tanh_fast(acc[q * 4 + i]), accv);
-      }
-      accv = add32(accv);
-      if (hf == 0) hdC[mo * TILE + j] = accv;
-      __syncthreads();                                                                        // (2)
-      if (mo == 0 && hf == 0 && ok) a.value[(size_t)(blockIdx.x * TILE + j) + (size_t)c.nt * step] = (hdC[j] + hdC[TILE + j]) + img[IC3::B3];
     } else {
-      // critic (ppo.jl:128) as fp16x2 on two waves: wave 4 + mo owns hidden rows 32·mo … of both layers (the split3 kernel's actor structure)
-      const int mo = wave - 4, j = lane & 31, hf = lane >> 5;
+      // critic on waves 4 and 5: fp16x2, or bf16x3 where a hidden-layer weight left the fp16 window
+      const int mo = wave - 4;
       const float* img = imgC0 + lds_off;
-      const float4 cv = reinterpret_cast<const float4*>(xcur)[j];
-      const float cx[4] = {cv.x, cv.y, cv.z, cv.w};
-      f32x16 acc = load16(img + IC::B1C + hf * 32 + 16 * mo);
-#pragma unroll
-      for (int ks = 0; ks < D / 2; ++ks) {
-        const float bv = hf ? cx[2 * ks + 1] : cx[2 * ks];
-        acc = mfma32(img[IC::WF1 + (mo * (D / 2) + ks) * 64 + lane], bv, acc);
-      }
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        float xb[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xb[i] = tanh_exp2_arg(acc[8 * q + i], X2_ACT_SCALE);
-        const P2 mine = split2(xb);
-        f16x8* dst = pcsC + ((mo * 2 + q) * 2) * 64 + lane;
-        dst[0] = mine.hi; dst[64] = mine.lo;
-      }
-      __syncthreads();                                                                        // (1)
-      acc = load16(img + IC::B2C + hf * 32 + 16 * mo);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {     // every k-step's B pieces come back from LDS, this wave's own too: the kernel stays inside 128 registers (see the attribute above)
-        const f16x8* src = pcsC + (((ks >> 1) * 2 + (ks & 1)) * 2) * 64 + lane;
-        P2 bq; bq.hi = src[0]; bq.lo = src[64];
-        acc = mfma_x2(load_wfrag2(img + IC::WF2H, mo, ks, lane), bq, acc);
-      }
-      const f32x4* w = reinterpret_cast<const f32x4*>(img + IC::W3 + hf * 32 + 16 * mo);
-      float accv = 0.0f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 wv = w[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) accv = __builtin_fmaf(wv[i], tanh_exp2(acc[q * 4 + i], TWO_LOG2E * X2_FWD_UNSCALE, 1.0f), accv);
-      }
-      accv = add32(accv);
-      if (hf == 0) hdC[mo * TILE + j] = accv;
-      __syncthreads();                                                                        // (2)
-      if (mo == 0 && hf == 0 && ok) a.value[(size_t)(blockIdx.x * TILE + j) + (size_t)c.nt * step] = (hdC[j] + hdC[TILE + j]) + img[IC::B3];
+      if (cx2) split6_critic_step<Split6CriticX2>(img, xcur, pcsC, hdC, mo, lane);
+      else split6_critic_step<Split6CriticX3>(img, xcur, pcsC, hdC, mo, lane);
+      if (mo == 0 && lane < 32 && ok) a.value[(size_t)e + (size_t)c.nt * step] = (hdC[lane] + hdC[TILE + lane]) + img[cx2 ? Split6CriticX2::I::B3 : Split6CriticX3::I::B3];
     }
     __syncthreads();                                                                          // (3) next observations are published, the exchange buffers are free
   }
-  if (wave == 0) {
-    if (writer) {
-      reinterpret_cast<float4*>(a.env_state)[e] = make_float4(s[0], s[1], s[2], s[3]);
-      reinterpret_cast<float4*>(a.cur_obs)[e] = make_float4(co[0], co[1], co[2], co[3]);
-      a.env_t[e] = t_env; a.next_done[e] = nd; a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-      // value[] was written by wave 4 of this block; the step loop's closing __syncthreads() made it visible here
-      if (a.fuse_gae) gae_tail_compat(a, e);
-    }
-    st_n = wave_sum(st_n); st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
-    if (lane == 0 && st_n > 0.0) {
-      atomicAdd(&a.ep_stats[0], st_n); atomicAdd(&a.ep_stats[1], st_ret); atomicAdd(&a.ep_stats[2], st_len);
-      atomicMax(reinterpret_cast<unsigned long long*>(&a.ep_stats[3]), (unsigned long long)__double_as_longlong(st_max));
-    }
+  if (wave == 0) {   // value[] was written by wave 4 of this block; the step loop's closing __syncthreads() made it visible to the GAE tail
+    if (writer) env_owner_store(env, a, e);
+    env_owner_finish(env, a, e, writer);
   }
 }
 
@@ -1121,17 +873,14 @@ int launch_rollout(crl_ppo* h, bool fuse_gae) {
   const bool six = split == 3 || split == 4;
   if (gemm_x2(h) && six && small) {
     // six waves per tile: the actor's hidden rows over four waves (16x16x32 products), the critic's over two
-    const size_t smem = sizeof(float) * (NetImageA16<2>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4 + 2 * 2 * 3 * 64 * 2 * 2 + 2 * 2 * 3 * 64 * 4 + 4 * 2 * TILE + 2 * TILE + 2 * 2 * TILE + 4 * 2 * TILE + 4);
-    hipLaunchKernelGGL((rollout_split6_kernel<2>), dim3(tiles), dim3(384), smem, h->stream, a);
+    hipLaunchKernelGGL((rollout_split6_kernel<2>), dim3(tiles), dim3(384), sizeof(float) * RolloutLds6<2>::SIZE, h->stream, a);
   } else if (gemm_x2(h) && (split == 1 || split == 4) && small) {
     // three waves per tile: the actor's hidden rows split over two waves, the critic (fp16x2) on the third
-    const size_t smem = sizeof(float) * (NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4 + 2 * 2 * 3 * 64 * 4 + 2 * 64 + 4);
-    hipLaunchKernelGGL((rollout_split3_kernel<2>), dim3(tiles), dim3(192), smem, h->stream, a);
+    hipLaunchKernelGGL((rollout_split3_kernel<2>), dim3(tiles), dim3(192), sizeof(float) * RolloutLds3<2>::SIZE, h->stream, a);
   } else if (split != 0 && small) {   // two waves per tile (actor + env | critic), all bf16x3: rollout_split = 2, or gemm = 1
-    const size_t smem = sizeof(float) * (NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 2 * TILE * 4);
-    hipLaunchKernelGGL((rollout_split_kernel<2>), dim3(tiles), dim3(128), smem, h->stream, a);
+    hipLaunchKernelGGL((rollout_split_kernel<2>), dim3(tiles), dim3(128), sizeof(float) * RolloutLds2<2>::SIZE, h->stream, a);
   } else {
-    const size_t smem = sizeof(float) * (NetImageX3<4, 2, false>::SIZE + NetImageX3<4, 1, false>::SIZE + 4);   // 53 KB: critic image sized for its bf16x3 fallback
+    const size_t smem = sizeof(float) * RolloutLds1<2>::SIZE;   // 53 KB: critic image sized for its bf16x3 fallback
     if (gemm_x2(h)) hipLaunchKernelGGL((rollout_cartpole_kernel<2, true>), dim3(blocks), dim3(64 * wpb), smem, h->stream, a);
     else hipLaunchKernelGGL((rollout_cartpole_kernel<2, false>), dim3(blocks), dim3(64 * wpb), smem, h->stream, a);
   }

@@ -1,5 +1,7 @@
-// stats.hpp — the "Training Statistics" record (ppo.jl:243-247) from the four loss sums of one optimiser step, and the key return_max travels as.
+// stats.hpp — the "Training Statistics" record (ppo.jl:243-247) from the four loss sums of one optimiser step, the key return_max travels as, and
+// the two pieces every rollout kernel ends an episode with: the per-episode record and the per-wave flush of the "Episode Statistics" sums.
 #pragma once
+#include "common.hpp"
 #include "ppo_ctx.hpp"
 
 namespace crl {
@@ -42,6 +44,30 @@ __device__ __host__ __forceinline__ double stat_max_unkey(unsigned long long k) 
   k = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   double x; __builtin_memcpy(&x, &k, 8);
   return x;
+}
+
+// ppo.jl:147-165 per-episode records (opt-in, ring_cap = 0: off): every episode end takes a slot; past the capacity it is counted, not stored
+__device__ __forceinline__ void episode_ring_push(crl_episode_record* ring, uint32_t* ring_count, int ring_cap, float ep_ret, int ep_len, uint32_t gid, int step) {
+  if (ring_cap > 0) {
+    const uint32_t slot = atomicAdd(ring_count, 1u);
+    if (slot < (uint32_t)ring_cap) ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
+  }
+}
+
+// A wave's episode statistics into the handle's four accumulators: one atomic set per wave that finished an episode. Called by whole waves; lanes without
+// an env bring zeros. return_max: returns of the non-negative kinds (CartPole, synthetic) are ordered by their f64 bit pattern read as u64; is_signed (the
+// env kind's returns can be negative: env_signed_returns, CRL_ENV_EXTERNAL) — lanes without a finished episode stand aside and the accumulator holds
+// stat_max_key of the maximum, which the host maps back (api.cpp return_max_of).
+__device__ __forceinline__ void episode_stats_flush(double* ep_stats, double st_n, double st_ret, double st_len, double st_max, bool is_signed = false) {
+  if (is_signed && !(st_n > 0.0)) st_max = -__builtin_inf();
+  st_n = wave_sum(st_n);
+  if (st_n > 0.0) {
+    st_ret = wave_sum(st_ret); st_len = wave_sum(st_len); st_max = wave_max(st_max);
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(&ep_stats[0], st_n); atomicAdd(&ep_stats[1], st_ret); atomicAdd(&ep_stats[2], st_len);
+      atomicMax(reinterpret_cast<unsigned long long*>(&ep_stats[3]), is_signed ? stat_max_key(st_max) : (unsigned long long)__double_as_longlong(st_max));
+    }
+  }
 }
 
 struct StatsArgs {

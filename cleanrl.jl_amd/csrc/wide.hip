@@ -1784,36 +1784,17 @@ __device__ __forceinline__ void wide_step_env(const WStepArgs& a, int e, int ste
   float ep_ret = a.ep_return[e] + rew;                               // ppo.jl:145
   if (done) {                                                        // ppo.jl:147-165
     st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = step_stat_max(c.env_kind, st_n, st_max, (double)ep_ret);
-    if (a.ring_cap > 0) {
-      const uint32_t slot = atomicAdd(a.ring_count, 1u);
-      if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-    }
+    episode_ring_push(a.ring, a.ring_count, a.ring_cap, ep_ret, ep_len, gid, step);
     ep_ret = 0.0f; ep_len = 0;
   }
   a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-}
-// a wave's episode statistics into the handle's four accumulators
-// (signed: the env kind's returns can be negative — lanes without a finished episode stand aside, and the accumulator holds stat_max_key of the maximum,
-// which the host maps back: api.cpp return_max_of)
-__device__ __forceinline__ void wide_step_stats(double* ep_stats, double st_n, double st_ret, double st_len, double st_max, bool is_signed = false) {
-  if (is_signed && !(st_n > 0.0)) st_max = -__builtin_inf();
-  st_n = wave_sum(st_n);
-  if (st_n > 0.0) {
-    st_ret = wave_sum(st_ret); st_len = wave_sum(st_len);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) st_max = fmax(st_max, __shfl_xor(st_max, o, 64));
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&ep_stats[0], st_n); atomicAdd(&ep_stats[1], st_ret); atomicAdd(&ep_stats[2], st_len);
-      atomicMax(reinterpret_cast<unsigned long long*>(&ep_stats[3]), is_signed ? stat_max_key(st_max) : (unsigned long long)__double_as_longlong(st_max));
-    }
-  }
 }
 
 __global__ void __launch_bounds__(256) wide_step_kernel(WStepArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
   if (e < a.c.nt) wide_step_env(a, e, a.step, st_n, st_ret, st_len, st_max);
-  wide_step_stats(a.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(a.c.env_kind));
+  episode_stats_flush(a.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(a.c.env_kind));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1869,7 +1850,7 @@ __global__ void __launch_bounds__(512, 4) wide_rollout_persist_kernel(WRollArgs 
     if (tid < 32 && e < nt) wide_step_env(r.s, e, step, st_n, st_ret, st_len, st_max);
     __syncthreads();
   }
-  if (tid < 64) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
+  if (tid < 64) episode_stats_flush(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2125,7 +2106,7 @@ __global__ void __launch_bounds__(512) wide_rollout_pc_kernel(RollPCArgs r) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
-    if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
+    if (wave == 0) episode_stats_flush(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
   }
 }
 

@@ -874,10 +874,7 @@ __device__ __forceinline__ void rs_step_env(const WStepArgs& a, int e, int step,
   float ep_ret = s0[1] + rew;                                        // ppo.jl:145
   if (done) {                                                        // ppo.jl:147-165
     st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = step_stat_max(c.env_kind, st_n, st_max, (double)ep_ret);
-    if (a.ring_cap > 0) {
-      const uint32_t slot = atomicAdd(a.ring_count, 1u);
-      if (slot < (uint32_t)a.ring_cap) a.ring[slot] = crl_episode_record{ep_ret, ep_len, (int32_t)gid, step};
-    }
+    episode_ring_push(a.ring, a.ring_count, a.ring_cap, ep_ret, ep_len, gid, step);
     ep_ret = 0.0f; ep_len = 0;
   }
   f32x4 n0; n0[0] = __int_as_float(done ? 1 : 0); n0[1] = ep_ret; n0[2] = __int_as_float(ep_len); n0[3] = __int_as_float(t_env);   // ppo.jl:144
@@ -1040,7 +1037,7 @@ __global__ void __launch_bounds__(512) wide_rs_rollout_kernel(RsRollArgs r) {
     __builtin_amdgcn_s_barrier();                                       // B4: the next observations are in LDS
     if (st_) RS_STAMP(9);
   }
-  if (wave == 0) wide_step_stats(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
+  if (wave == 0) episode_stats_flush(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
   if (tid < RR_MB) {                                                    // the envs' state back to global memory for the next launch
     const int e = m0 + tid;
     const float* q = stl + tid * 8;

@@ -160,6 +160,37 @@ def test_rollout_matches_oracle(crl, nt, stale, split):
     agent.close(); st.close()
 
 
+def test_rollout_kernels_of_one_two_and_three_waves_agree_bit_for_bit(crl):
+    """The one-wave kernel (gemm = 1, rollout_split = 0), the two-wave kernel (gemm = 1, rollout_split = 2) and the three-wave kernel
+    (rollout_split = 1) run the same actor arithmetic in the same order — the three-wave kernel's head is one chain over the 64 rows,
+    handed from wave 0 to wave 1 — and the same env owner: everything but the value is bit-equal across the three. The first two also
+    run the whole bf16x3 critic on one wave: their values are bit-equal too. One full tile, one ragged tile, 4 live envs in a third."""
+    L = crl._lib
+    nt, k = 70, 128
+    first = make_agent(crl, nt=nt, k=k, options={"gemm": 1, "rollout_split": 0})
+    params = first.get_params()
+    agents = [first, make_agent(crl, nt=nt, k=k, params=params, options={"gemm": 1, "rollout_split": 2}),
+              make_agent(crl, nt=nt, k=k, params=params, options={"rollout_split": 1})]
+    fields = {"action": L.F_ACTION, "logprob": L.F_LOGPROB, "obs": L.F_OBS, "reward": L.F_REWARD, "terminal": L.F_TERMINAL,
+              "next_done": L.F_NEXT_DONE, "env_state": L.F_ENV_STATE}
+    got = []
+    for agent in agents:
+        h = agent.handle
+        h.env_reset(); h.rollout_run()
+        out = {name: h.read(f) for name, f in fields.items()}
+        out["value"] = h.read(L.F_VALUE)
+        es = h.episode_stats()
+        out["sums"] = (es["episodes"], es["return_sum"], es["length_sum"])
+        got.append(out)
+        agent.close()
+    assert got[0]["sums"][0] > 100
+    for other in got[1:]:
+        for name in fields:
+            assert got[0][name].tobytes() == other[name].tobytes(), f"{name}: {np.sum(got[0][name] != other[name])} elements differ"
+        assert got[0]["sums"] == other["sums"]
+    assert got[0]["value"].tobytes() == got[1]["value"].tobytes(), f"value: {np.sum(got[0]['value'] != got[1]['value'])} elements differ"
+
+
 def _inject_batch(crl, agent, st, rng, ret_scale=10.0):
     """Same synthetic rollout buffer into the GPU handle and the oracle state."""
     nt, k = st.cfg.num_envs, st.cfg.num_steps
@@ -847,15 +878,17 @@ def _episodes_from_buffers(reward, terminal, next_done, env_id_offset=0):
     return out
 
 
-@pytest.mark.parametrize("kind", ["fused-split", "fused-split6", "fused-single", "wide"])
+@pytest.mark.parametrize("kind", ["fused-split", "fused-split2", "fused-split6", "fused-single", "wide"])
 def test_episode_record_ring(crl, kind, monkeypatch):
     """ppo.jl:147-165 per-episode records (opt-in ring): every episode end of a rollout with its return, length, env and
-    step — equal to what the stored rewards / terminals imply; overflow is counted, not stored."""
+    step — equal to what the stored rewards / terminals imply; overflow is counted, not stored. The aggregated statistics of the same
+    rollout (one flush per wave: three sums and a maximum) must say what the records say: CartPole returns are small integers in
+    float32, so the sum and the maximum are exact."""
     L = crl._lib
     nt, k = 70, 128
     if kind == "wide":
         monkeypatch.setenv("CRL_FORCE_WIDE", "1")      # read once, by crl_ppo_create
-    agent = make_agent(crl, nt=nt, k=k, env_id_offset=1000, options={"rollout_split": {"fused-split": 1, "fused-split6": 3}.get(kind, 0)})
+    agent = make_agent(crl, nt=nt, k=k, env_id_offset=1000, options={"rollout_split": {"fused-split": 1, "fused-split2": 2, "fused-split6": 3}.get(kind, 0)})
     h = agent.handle
     with pytest.raises(crl.CrlError, match="not enabled"):
         h._ring_cap = 4; h.episode_records()
@@ -866,10 +899,13 @@ def test_episode_record_ring(crl, kind, monkeypatch):
     assert total == len(want) > 100 and recs == want
     es = h.episode_stats()
     assert es["episodes"] == total and es["length_sum"] == sum(r[3] for r in recs)
+    assert es["return_sum"] == sum(r[2] for r in recs) and es["return_max"] == max(r[2] for r in recs)
     h.episode_ring_enable(16)                      # a ring smaller than the episode count keeps counting
     h.env_reset(); h.rollout_run()
     recs2, total2 = h.episode_records()
     assert total2 == total and len(recs2) == 16 and set(recs2) <= set(want)
+    es2 = h.episode_stats()                        # the statistics do not depend on what the ring kept
+    assert es2["return_sum"] == sum(r[2] for r in want) and es2["return_max"] == max(r[2] for r in want)
     h.episode_ring_enable(0)
     agent.close()
 
