@@ -19,13 +19,13 @@
 
 #include "common.hpp"
 #include "env64.hpp"
+#include "optim.hpp"
 #include "ppo_ctx.hpp"
 
 struct crl_a2c;
 
 namespace crl {
-int launch_clipnorm_adam_range(hipStream_t st, float* params, const float* grads, float* m, float* v, double* betap,
-                               const int* off13, int a0, int a1, double eta);
+int launch_clipnorm_adam_range(hipStream_t st, const OptimCore& c, const float* grads, int a0, int a1);   // optim.hip
 
 constexpr int AH = 64, AD = 4, AA = 2;       // hidden / obs / actions of the reference's CartPole networks
 constexpr int A2C_MAX_EPS = 4096;
@@ -338,7 +338,7 @@ struct crl_a2c {
   // training workspace, [·, cap]
   double *h1[2] = {nullptr, nullptr}, *h2[2] = {nullptr, nullptr}, *d1 = nullptr, *d2 = nullptr;
   double *vout = nullptr, *z = nullptr, *G = nullptr, *adv = nullptr, *dvc = nullptr, *dza = nullptr, *lp_adv = nullptr;
-  int off[13];
+  crl::ParamTable tab;   // the PPO layout at 4 / 2 / 64
 };
 
 namespace crl {
@@ -379,8 +379,9 @@ static int a2c_update(crl_a2c* h, int n) {
                        h->d2, h->d1, h->grads);
     CRL_HIP_CHECK(hipGetLastError());
   }
-  if (launch_clipnorm_adam_range(st, h->params, h->grads, h->m, h->v, h->betap, h->off, 6, 12, h->cfg.lr)) return 1;
-  if (launch_clipnorm_adam_range(st, h->params, h->grads, h->m, h->v, h->betap, h->off, 0, 6, h->cfg.lr)) return 1;
+  const OptimCore oc{h->tab, h->params, h->m, h->v, h->betap, h->cfg.lr, CLIPNORM_THRESH};
+  if (launch_clipnorm_adam_range(st, oc, h->grads, 6, 12)) return 1;
+  if (launch_clipnorm_adam_range(st, oc, h->grads, 0, 6)) return 1;
   hipLaunchKernelGGL(a2c_finish_kernel, dim3(1), dim3(1), 0, st, a);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
@@ -406,10 +407,8 @@ int32_t crl_a2c_create(const crl_a2c_config* cfg, int32_t device, crl_a2c** out)
   crl_a2c* h = new (std::nothrow) crl_a2c();
   if (!h) { set_error("out of host memory"); return 1; }
   h->cfg = *cfg; h->device = device; h->cap = 2 * cfg->min_replay_size;       // a2c.jl:46
-  const int sizes[12] = {AH * AD, AH, AH * AH, AH, AA * AH, AA, AH * AD, AH, AH * AH, AH, AH, 1};
-  h->off[0] = 0;
-  for (int i = 0; i < 12; ++i) h->off[i + 1] = h->off[i] + sizes[i];
-  h->P = h->off[12];
+  h->tab = param_table(AD, AA, AH);
+  h->P = h->tab.off[12];
   hipError_t se = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   if (se != hipSuccess) { set_error(std::string("hipStreamCreate: ") + hipGetErrorString(se)); delete h; return 1; }
   const size_t cap = (size_t)h->cap, P = (size_t)h->P;

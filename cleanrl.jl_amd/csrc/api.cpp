@@ -295,10 +295,9 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   c.D = cfg->obs_dim; c.A = cfg->n_act; c.gamma = cfg->gamma; c.lambda = cfg->gae_lambda; c.clip = cfg->clip_coef;
   c.ent_coeff = cfg->ent_coeff; c.v_coef = cfg->v_coef; c.clip_vloss = cfg->clip_value_loss; c.gae_mode = cfg->gae_mode;
   c.env_kind = cfg->env_kind; c.stale_obs = cfg->stale_obs; c.env_id_offset = (uint32_t)cfg->env_id_offset; c.seed = cfg->seed;
-  const int hN = cfg->hidden, d = cfg->obs_dim, A = cfg->n_act;
-  h->Pa = (int64_t)hN * d + hN + hN * hN + hN + A * hN + A;
-  h->Pc = (int64_t)hN * d + hN + hN * hN + hN + hN + 1;
-  h->P = h->Pa + h->Pc;
+  const int d = cfg->obs_dim;
+  h->ptab = param_table(d, cfg->n_act, cfg->hidden);
+  h->Pa = h->ptab.off[6]; h->P = h->ptab.off[12]; h->Pc = h->P - h->Pa;
   h->num_updates = cfg->total_timesteps / B64;
   if (h->num_updates < 1) h->num_updates = 1;
   int rc = 0;

@@ -4,7 +4,7 @@
 // `for global_step` body (dqn.jl:57-119) runs here as a fixed sequence of launches per train_freq steps, enqueued without
 // any host read-back in between: dqn_collect_kernel (ε-greedy action — q_net forward only on greedy steps —, env step,
 // ring-buffer add, episode bookkeeping, up to the next training step), then the minibatch draw without replacement, both
-// forwards, TD target, Flux.mse, the pullbacks, Adam and the hard target copy as multi-CU kernels.
+// forwards, TD target, Flux.mse, the pullbacks, Adam (the entry step PPO's optimiser kernels share: optim.hpp) and the hard target copy as multi-CU kernels.
 // Float64 arithmetic with Float32 weights like the reference (see a2c.hip; both step the CartPoleEnv{Float64} of env64.hpp); relu has no transcendental, every sum runs
 // in the oracle's order with contraction off ⇒ the run is BIT-IDENTICAL to oracle/dqn_oracle.c.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "env64.hpp"
+#include "optim.hpp"
 #include "ppo_ctx.hpp"
 
 struct crl_dqn;
@@ -301,7 +302,8 @@ __global__ void __launch_bounds__(64) dqn_wgrad_kernel(DQNDev a) {
   }
   a.grads[p] = (float)g;
 }
-// Flux Adam(lr) (dqn.jl:41,109) + hard target copy (dqn.jl:111-113) + loss record (dqn.jl:115-117); one block
+// Flux Adam(lr) (dqn.jl:41,109: optim.hpp's entry step without the clip, one β-power pair per array) + hard target copy (dqn.jl:111-113) + loss record
+// (dqn.jl:115-117); one block
 __global__ void __launch_bounds__(1024) dqn_adam_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
@@ -310,19 +312,13 @@ __global__ void __launch_bounds__(1024) dqn_adam_kernel(DQNDev a) {
   const bool copy = gstep % a.cfg.target_net_freq == 0;
   for (int p = tid; p < QP; p += nth) {
     const int arr = p < Qob1 ? 0 : p < QoW2 ? 1 : p < Qob2 ? 2 : p < QoW3 ? 3 : p < Qob3 ? 4 : 5;
-    const double b1 = 0.9, b2 = 0.999, epsn = 1e-8;
-    const double bp0 = a.betap[2 * arr], bp1 = a.betap[2 * arr + 1];
-    const double gg = (double)a.grads[p];
-    const float mi = (float)(b1 * (double)a.m[p] + (1 - b1) * gg);
-    const float vi = (float)(b2 * (double)a.v[p] + (1 - b2) * gg * gg);
-    a.m[p] = mi; a.v[p] = vi;
-    const double delta = (double)mi / (1 - bp0) / (sqrt((double)vi / (1 - bp1)) + epsn) * a.cfg.lr;
-    const float w = a.q[p] - (float)delta;
-    a.q[p] = w;
+    float mi, vi, w;
+    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
+    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
     if (copy) a.t[p] = w;
   }
   __syncthreads();
-  if (tid < 12) a.betap[tid] = a.betap[tid] * ((tid & 1) ? 0.999 : 0.9);
+  if (tid < 6) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
   if (tid == 0) {
     DQNCtl* c = a.ctl;
     c->n_updates += 1;

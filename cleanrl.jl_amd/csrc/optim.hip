@@ -1,6 +1,8 @@
-// optim.hip — advantage statistics (ppo.jl:221) and Optimiser(ClipNorm(0.5), Adam(η)) (ppo.jl:93,250).
+// optim.hip — advantage statistics (ppo.jl:221) and the two-launch routes of Optimiser(ClipNorm(0.5), Adam(η)) (ppo.jl:93,250): one block per array,
+// or slices of 4,096. The per-element arithmetic, the array table and the shared arguments are optim.hpp's.
 #include "bijection.hpp"
 #include "common.hpp"
+#include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "stats.hpp"
 
@@ -127,13 +129,11 @@ int launch_adv_stats_finish(crl_ppo* h, int slot0, int nslots) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Flux 0.13.4 Optimiser(ClipNorm(thresh), Adam(η, (0.9, 0.999), 1e-8)) applied to each of the 12 parameter arrays
-// independently (Q9): one block per array, Float64 scalar math, Float32 state — oracle: orc_clipnorm_adam.
+// Optimiser(ClipNorm(thresh), Adam(η)) applied to each of the 12 parameter arrays independently (Q9): one block per array. The arithmetic per
+// element is optim.hpp's (oracle: orc_clipnorm_adam); this file owns the order in which Σg² is added.
 // ------------------------------------------------------------------------------------------------------
 struct OptimArgs {
-  int off[13]; int arr0;
-  float* params; const float* grads; float* m; float* v; double* betap;
-  double eta, thresh;
+  OptimCore c; const float* grads; int arr0;
   // data-parallel step: the "Training Statistics" record of the all-reduced message rides in this launch as one extra block
   // (it depends on nothing the optimiser writes) instead of being a launch of its own between the all-reduce and the optimiser
   int stats_block = -1; int P = 0; StatsArgs st{};
@@ -145,8 +145,9 @@ __global__ void __launch_bounds__(1024) clipnorm_adam_kernel(OptimArgs a) {
     if (threadIdx.x == 0) compute_stats(a.grads, a.P, a.st.c, a.st.Mglobal, a.st.adv_ms, a.st.mb, a.st.vfix, a.st.out, 0);
     return;
   }
+  const OptimCore& c = a.c;
   const int arr = blockIdx.x + a.arr0;
-  const int lo = a.off[arr], hi = a.off[arr + 1];
+  const int lo = c.tab.off[arr], hi = c.tab.off[arr + 1];
   __shared__ double sm[16];
   double ss = 0.0;
   for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) { const double g = a.grads[i]; ss += g * g; }
@@ -155,41 +156,33 @@ __global__ void __launch_bounds__(1024) clipnorm_adam_kernel(OptimArgs a) {
   __syncthreads();
   ss = 0.0;
   for (int w = 0; w < (int)(blockDim.x >> 6); ++w) ss += sm[w];
-  const float nrm = (float)sqrt(ss);
-  const bool clip = (double)nrm > a.thresh;
-  const double sc = clip ? a.thresh / (double)nrm : 1.0;
-  const double b1 = 0.9, b2 = 0.999, epsn = 1e-8;
-  const double bp0 = a.betap[2 * arr], bp1 = a.betap[2 * arr + 1];
+  double sc;
+  const bool clip = clipnorm_scale(ss, c.thresh, sc);
+  const double bp0 = c.betap[2 * arr], bp1 = c.betap[2 * arr + 1];
   for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    double g = (double)a.grads[i];
-    if (clip) g = (double)(float)(g * sc);
-    const float mi = (float)(b1 * (double)a.m[i] + (1 - b1) * g);
-    const float vi = (float)(b2 * (double)a.v[i] + (1 - b2) * g * g);
-    a.m[i] = mi; a.v[i] = vi;
-    const double delta = (double)mi / (1 - bp0) / (sqrt((double)vi / (1 - bp1)) + epsn) * a.eta;
-    a.params[i] = a.params[i] - (float)delta;
+    float mi, vi, pi;
+    adam_entry((double)a.grads[i], c.m[i], c.v[i], c.params[i], bp0, bp1, c.eta, clip, sc, mi, vi, pi);
+    c.m[i] = mi; c.v[i] = vi; c.params[i] = pi;
   }
   __syncthreads();
-  if (threadIdx.x == 0) { a.betap[2 * arr] = bp0 * b1; a.betap[2 * arr + 1] = bp1 * b2; }
+  if (threadIdx.x == 0) betap_advance(c.betap, arr, bp0, bp1);
 }
 
 // The same optimiser for large parameter arrays (2×256: W2 has 65,536 entries), where one block per array makes the step a
 // 100 µs serial walk: slices of 4,096 entries per block. Two launches: per-slice Σg² partials (Float64; the array's first slice also sets the step's β
 // powers aside) → every slice sums its array's partials in slice order (one norm, identical in all slices), clips and applies Adam to its entries with
-// the powers set aside, and the array's first slice advances the running powers (a launch of its own until round 5). Same arithmetic per element as
-// clipnorm_adam_kernel; only the order of the Σg² sum differs (by slices).
+// the powers set aside, and the array's first slice advances the running powers. Only the order of the Σg² sum differs from clipnorm_adam_kernel (by slices).
 constexpr int OPT_SLICE = 4096;
 struct OptimSliceArgs {
-  int off[13]; int first_blk[13];   // first_blk[a] = index of array a's first slice; first_blk[12] = number of slices
-  float* params; const float* grads; float* m; float* v; double* betap; double* part;
-  double eta, thresh;
+  OptimCore c; int first_blk[13];   // first_blk[a] = index of array a's first slice; first_blk[12] = number of slices
+  const float* grads; double* part;
 };
 __device__ __forceinline__ void optim_locate(const OptimSliceArgs& a, int blk, int& arr, int& lo, int& hi) {
   arr = 0;
   while (arr < 11 && blk >= a.first_blk[arr + 1]) ++arr;
   const int sl = blk - a.first_blk[arr];
-  lo = a.off[arr] + sl * OPT_SLICE;
-  hi = lo + OPT_SLICE < a.off[arr + 1] ? lo + OPT_SLICE : a.off[arr + 1];
+  lo = a.c.tab.off[arr] + sl * OPT_SLICE;
+  hi = lo + OPT_SLICE < a.c.tab.off[arr + 1] ? lo + OPT_SLICE : a.c.tab.off[arr + 1];
 }
 __global__ void __launch_bounds__(1024) clipnorm_partial_kernel(OptimSliceArgs a) {
 #pragma clang fp contract(off)
@@ -206,56 +199,41 @@ __global__ void __launch_bounds__(1024) clipnorm_partial_kernel(OptimSliceArgs a
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sm[w];
     a.part[blockIdx.x] = t;
     // the β powers this step uses, set aside by the array's first block: adam_slice_kernel reads the copy and its first block of the array advances the
-    // original — no block can read a power another one has already advanced (betap_advance_kernel was a launch of its own for that reason)
-    if ((int)blockIdx.x == a.first_blk[arr]) { a.part[a.first_blk[12] + 2 * arr] = a.betap[2 * arr]; a.part[a.first_blk[12] + 2 * arr + 1] = a.betap[2 * arr + 1]; }
+    // original — no block can read a power another one has already advanced
+    if ((int)blockIdx.x == a.first_blk[arr]) { a.part[a.first_blk[12] + 2 * arr] = a.c.betap[2 * arr]; a.part[a.first_blk[12] + 2 * arr + 1] = a.c.betap[2 * arr + 1]; }
   }
 }
 __global__ void __launch_bounds__(1024) adam_slice_kernel(OptimSliceArgs a) {
 #pragma clang fp contract(off)
+  const OptimCore& c = a.c;
   int arr, lo, hi;
   optim_locate(a, blockIdx.x, arr, lo, hi);
   double ss = 0.0;
   for (int b = a.first_blk[arr]; b < a.first_blk[arr + 1]; ++b) ss += a.part[b];
-  const float nrm = (float)sqrt(ss);
-  const bool clip = (double)nrm > a.thresh;
-  const double sc = clip ? a.thresh / (double)nrm : 1.0;
-  const double b1 = 0.9, b2 = 0.999, epsn = 1e-8;
+  double sc;
+  const bool clip = clipnorm_scale(ss, c.thresh, sc);
   const double bp0 = a.part[a.first_blk[12] + 2 * arr], bp1 = a.part[a.first_blk[12] + 2 * arr + 1];
-  if ((int)blockIdx.x == a.first_blk[arr] && threadIdx.x == 0) { a.betap[2 * arr] = bp0 * b1; a.betap[2 * arr + 1] = bp1 * b2; }
+  if ((int)blockIdx.x == a.first_blk[arr] && threadIdx.x == 0) betap_advance(c.betap, arr, bp0, bp1);
   for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    double g = (double)a.grads[i];
-    if (clip) g = (double)(float)(g * sc);
-    const float mi = (float)(b1 * (double)a.m[i] + (1 - b1) * g);
-    const float vi = (float)(b2 * (double)a.v[i] + (1 - b2) * g * g);
-    a.m[i] = mi; a.v[i] = vi;
-    const double delta = (double)mi / (1 - bp0) / (sqrt((double)vi / (1 - bp1)) + epsn) * a.eta;
-    a.params[i] = a.params[i] - (float)delta;
+    float mi, vi, pi;
+    adam_entry((double)a.grads[i], c.m[i], c.v[i], c.params[i], bp0, bp1, c.eta, clip, sc, mi, vi, pi);
+    c.m[i] = mi; c.v[i] = vi; c.params[i] = pi;
   }
-}
-__global__ void betap_advance_kernel(double* betap) {
-  const int arr = threadIdx.x;
-  if (arr < 12) { betap[2 * arr] *= 0.9; betap[2 * arr + 1] *= 0.999; }
 }
 
 int launch_optim(crl_ppo* h, double eta) {
-  OptimArgs a;
-  const int hN = h->cfg.hidden, d = h->cfg.obs_dim, A = h->cfg.n_act;
-  const int sizes[12] = {hN * d, hN, hN * hN, hN, A * hN, A, hN * d, hN, hN * hN, hN, hN, 1};
-  a.off[0] = 0;
-  for (int i = 0; i < 12; ++i) a.off[i + 1] = a.off[i] + sizes[i];
-  a.params = h->params; a.grads = h->comm_buf; a.m = h->adam_m; a.v = h->adam_v; a.betap = h->betap;
-  a.eta = eta; a.thresh = 0.5; a.arr0 = 0;
   ProfScope ps(h, CRL_K_OPTIM);
   if (h->P > 32768 && h->optim_part) {
     OptimSliceArgs b;
-    int nb = 0;
-    for (int i = 0; i < 12; ++i) { b.off[i] = a.off[i]; b.first_blk[i] = nb; nb += (sizes[i] + OPT_SLICE - 1) / OPT_SLICE; }
-    b.off[12] = a.off[12]; b.first_blk[12] = nb;
-    b.params = h->params; b.grads = h->comm_buf; b.m = h->adam_m; b.v = h->adam_v; b.betap = h->betap; b.part = h->optim_part;
-    b.eta = eta; b.thresh = 0.5;
+    b.c = optim_core(h, eta); b.grads = h->comm_buf; b.part = h->optim_part;
+    b.first_blk[0] = 0;
+    for (int i = 0; i < 12; ++i) b.first_blk[i + 1] = b.first_blk[i] + (b.c.tab.off[i + 1] - b.c.tab.off[i] + OPT_SLICE - 1) / OPT_SLICE;
+    const int nb = b.first_blk[12];
     hipLaunchKernelGGL(clipnorm_partial_kernel, dim3(nb), dim3(1024), 0, h->stream, b);
     hipLaunchKernelGGL(adam_slice_kernel, dim3(nb), dim3(1024), 0, h->stream, b);
   } else {
+    OptimArgs a;
+    a.c = optim_core(h, eta); a.grads = h->comm_buf; a.arr0 = 0;
     int blocks = 12;
     if (h->stats_pending) {
       a.stats_block = 12; a.P = (int)h->P; blocks = 13;
@@ -270,14 +248,10 @@ int launch_optim(crl_ppo* h, double eta) {
   return 0;
 }
 
-
-// Optimiser(ClipNorm(0.5), Adam(η)) over parameter arrays [a0, a1) of a flat 12-array layout (A2C updates the critic's and
-// the actor's arrays in separate calls, a2c.jl:88,98)
-int launch_clipnorm_adam_range(hipStream_t st, float* params, const float* grads, float* m, float* v, double* betap,
-                               const int* off13, int a0, int a1, double eta) {
+// The same step over parameter arrays [a0, a1) of the layout (A2C updates the critic's and the actor's arrays in separate calls, a2c.jl:88,98)
+int launch_clipnorm_adam_range(hipStream_t st, const OptimCore& c, const float* grads, int a0, int a1) {
   OptimArgs a;
-  for (int i = 0; i < 13; ++i) a.off[i] = off13[i];
-  a.params = params; a.grads = grads; a.m = m; a.v = v; a.betap = betap; a.eta = eta; a.thresh = 0.5; a.arr0 = a0;
+  a.c = c; a.grads = grads; a.arr0 = a0;
   hipLaunchKernelGGL(clipnorm_adam_kernel, dim3(a1 - a0), dim3(1024), 0, st, a);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;

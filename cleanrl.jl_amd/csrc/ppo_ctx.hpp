@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/cleanrl_hip.h"
+#include "optim.hpp"
 
 namespace crl {
 
@@ -97,6 +98,7 @@ struct crl_ppo {
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int64_t P = 0, Pa = 0, Pc = 0;  // total / actor / critic parameter counts
+  crl::ParamTable ptab{};          // where each of the 12 parameter arrays starts (crl_ppo_create)
   int64_t iteration = 0;
   int64_t exact_reruns = 0;        // iterations whose update phase was re-run exactly under data parallelism (Q4)
   bool env_ready = false;          // crl_env_reset has run (crl_ppo_iterate / crl_rollout_run do it on first use)
@@ -221,6 +223,8 @@ int reset_dw_scale(crl_ppo* h);
 // leaves the fp16x2 window
 inline bool gemm_x2(const crl_ppo* h) { return h->opt[OPT_GEMM] == 2; }
 inline int64_t opt(const crl_ppo* h, int id) { return h->opt[id]; }
+// the handle's ClipNorm(0.5) + Adam(eta) step (optim.hpp), for whichever kernel runs it
+inline OptimCore optim_core(const crl_ppo* h, double eta) { return OptimCore{h->ptab, h->params, h->adam_m, h->adam_v, h->betap, eta, CLIPNORM_THRESH}; }
 
 // HIP-event timing of one kernel class. attach=true: the events are handed to hipExtLaunchKernelGGL, which stamps the
 // kernel's own begin/end (what rocprofv3 reports); otherwise they are recorded on the stream around the launch(es).

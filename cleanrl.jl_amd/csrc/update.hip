@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "mlp_x2.hpp"
 #include "mlp_x3.hpp"
+#include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "stats.hpp"
 #include "update_args.hpp"
@@ -820,108 +821,18 @@ __global__ void __launch_bounds__(256, 2) update_vfix_kernel(UpdateArgs a) {
 // folded in order): 256-B coalesced rows and every partial of an output in flight at once — at 256 update blocks a
 // thread issues its 8 loads back to back instead of walking 32 of them in 8 dependent rounds — still a fixed summation order.
 constexpr int RG = 16;
-template <int MODE>
-__global__ void __launch_bounds__(64 * RG) reduce_kernel(const float* __restrict__ gpart, const double* __restrict__ lpart,
-                                                         int nblkA, int nblkC, int pmax, int gstride, int Pa, int Pc,
-                                                         float* __restrict__ msg, StatsArgs st) {
-  const double* vfix = st.vfix;
-  if (MODE == 1 && vfix[3] == 0.0) return;
-  __shared__ float sm[RG][64];
-  __shared__ double smd[RG][4];
-  const int P = Pa + Pc;
+// What reduce_kernel and reduce_optim_kernel start with, in two calls on one LDS image. reduce_partial_sums: thread (o, g) adds the partials b ≡ g (mod RG) of output
+// i = 64·blockIdx.x + o in block order, four loads in flight per round; in the block that carries the loss sums thread (o < 4, g) does the same for sum o (0 pg, 1 ent:
+// actor; 2 u, 3 q: critic); ends with the block's barrier. reduce_fold: group 0 folds the RG groups in order — `grad` where g == 0 and live (0 elsewhere), `lsum` where
+// g == 0 and o < 4 in the loss block. with_actor = false (the exact critic-only pass) leaves the actor's two loss sums out; its outputs the caller masks through `live`.
+// Two calls, so that reduce_optim_kernel can issue its state loads between them and have the fold run under their latency.
+struct ReduceLds { float sm[RG][64]; double smd[RG][4]; };
+// this thread's column o is a loss sum of the pass
+__device__ __forceinline__ bool loss_column(bool loss_block, bool with_actor) { const int o = threadIdx.x & 63; return loss_block && o < 4 && (with_actor || (o >> 1) != 0); }
+__device__ __forceinline__ void reduce_partial_sums(ReduceLds& lds, const float* __restrict__ gpart, const double* __restrict__ lpart, int nblkA, int nblkC, int pmax,
+                                                    int gstride, int Pa, int i, bool live, bool loss_block, bool with_actor) {
   const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + o;
   float s = 0.0f;
-  bool live = i < P;
-  int role = 0;
-  if (live) {
-    role = i >= Pa;
-    if (MODE == 1 && role == 0) live = false;
-  }
-  if (live) {
-    const float* gp = gpart + (size_t)role * pmax * gstride + (role ? i - Pa : i);
-    const int blocks_per_role = role ? nblkC : nblkA;
-    int b = g;
-    for (; b + 3 * RG < blocks_per_role; b += 4 * RG) {
-      const float v0 = gp[(size_t)b * gstride], v1 = gp[(size_t)(b + RG) * gstride], v2 = gp[(size_t)(b + 2 * RG) * gstride],
-                  v3 = gp[(size_t)(b + 3 * RG) * gstride];
-      s += v0; s += v1; s += v2; s += v3;
-    }
-    for (; b < blocks_per_role; b += RG) s += gp[(size_t)b * gstride];
-  }
-  sm[g][o] = s;
-  // the four loss sums ride on the last block: thread (which = o < 4, group g)
-  double ds = 0.0;
-  const bool last = blockIdx.x == gridDim.x - 1;
-  if (last && o < 4) {
-    const int which = o, lrole = which >> 1;  // 0 pg, 1 ent (actor) ; 2 u, 3 q (critic)
-    if (!(MODE == 1 && lrole == 0)) {
-      const double* l = lpart + (size_t)lrole * pmax * 2 + (which & 1);
-      const int nb = lrole ? nblkC : nblkA;
-      for (int b = g; b < nb; b += RG) ds += l[b * 2];
-    }
-    smd[g][o] = ds;
-  }
-  __syncthreads();
-  if (g == 0 && live) {
-    float t = sm[0][o];
-#pragma unroll
-    for (int q = 1; q < RG; ++q) t += sm[q][o];
-    msg[i] = t;
-  }
-  if (last && g == 0 && o < 4 && !(MODE == 1 && (o >> 1) == 0)) {
-    double t = smd[0][o];
-#pragma unroll
-    for (int q = 1; q < RG; ++q) t += smd[q][o];
-    msg[P + o] = (float)t;
-  }
-  if (MODE == 0 && last && st.dscale && threadIdx.x < 2) {
-    // fp16x2 weight gradient: this launch's largest |δ2| becomes the next launch's scale (mlp_x2.hpp), per role
-    unsigned* mx = reinterpret_cast<unsigned*>(st.dscale + 2);
-    st.dscale[threadIdx.x] = dw_next_scale(mx[threadIdx.x], st.dscale[threadIdx.x]);
-    mx[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) mx[2] = 0u;   // the 16-sample kernel's miss flag: update_repair_kernel has run by now
-  }
-  if (last && st.fused) {
-    __syncthreads();  // the four sums written above are visible to thread 0 of this block
-    if (threadIdx.x == 0) compute_stats(msg, P, st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, MODE);
-  }
-}
-
-// reduce_kernel<0> + Optimiser(ClipNorm(0.5), Adam(η)) in ONE launch (single GPU, speculative step: nothing sits between the
-// gradient and the optimiser). Same blocks, same fixed summation order as reduce_kernel; then every block leaves Σg² of its 64
-// outputs per parameter array, the grid meets at a ticket (144 blocks of 1024 threads: all resident — nothing else runs on the
-// device between an update kernel and the next one), every block sums the partials of the arrays it touches in block order
-// (all blocks that touch an array compute the same norm bit for bit) and applies ClipNorm + Adam to its 64 entries with the
-// arithmetic of clipnorm_adam_kernel (optim.hip; oracle: orc_clipnorm_adam). The β powers are read before the ticket and
-// advanced after it by the block that holds an array's first entry. Saves a launch, a launch gap and the one-block-per-array
-// walk of the 4,096-entry arrays per optimiser step.
-struct FusedOptimArgs {
-  int off[13];
-  float* params; float* m; float* v; double* betap; double* part /* [12][gridDim.x] */; unsigned* ticket /* [0] arrivals, [1] sticky time-out flag */; unsigned target;
-  unsigned long long timeout;   // ticks of the 100 MHz wall clock a block waits at the meeting point before it gives up (2 s)
-  double eta, thresh;
-};
-// PEER = true (round 5): the DATA-PARALLEL optimiser step as one launch over the peer mailboxes of peer.hip — reduce → push this block's 64 sums into
-// every rank's mailbox → flag → wait for the W flags of this chunk → add the W slots in rank order → Σg² → ticket → ClipNorm + Adam. Replaces
-// reduce_kernel + peer_allreduce_kernel + clipnorm_adam_kernel (three launches, ≈ 40 µs beside an 85 µs update launch at 8192 envs per rank). A chunk
-// is a block's 64 floats, so chunks never wait on each other across ranks; the grid-wide ticket stays local to the GPU. The four loss sums ride in the
-// last block's chunk (indices P … P + 3), the statistics record is written from the all-reduced sums by that block. Every rank adds the same slots in
-// the same order and clips by the same norms: replicas stay bit-identical.
-template <bool PEER>
-__global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __restrict__ gpart, const double* __restrict__ lpart,
-                                                               int nblkA, int nblkC, int pmax, int gstride, int Pa, int Pc,
-                                                               float* __restrict__ msg, StatsArgs st, FusedOptimArgs oa, PeerArgs pa) {
-#pragma clang fp contract(off)
-  __shared__ float sm[RG][64];
-  __shared__ double smd[RG][4];
-  __shared__ double nrm2[12];
-  __shared__ float gsum[4];
-  const int P = Pa + Pc;
-  const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + o;
-  float s = 0.0f;
-  const bool live = i < P;
   if (live) {
     const int role = i >= Pa;
     const float* gp = gpart + (size_t)role * pmax * gstride + (role ? i - Pa : i);
@@ -934,44 +845,122 @@ __global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __re
     }
     for (; b < blocks_per_role; b += RG) s += gp[(size_t)b * gstride];
   }
-  sm[g][o] = s;
-  double ds = 0.0;
-  // the block whose chunk holds the loss sums (indices P … P + 3; the launcher sizes the grid so that one block holds all four)
-  const bool last = blockIdx.x == (unsigned)(P / 64);
-  if (last && o < 4) {
-    const int which = o, lrole = which >> 1;
-    const double* l = lpart + (size_t)lrole * pmax * 2 + (which & 1);
-    const int nb = lrole ? nblkC : nblkA;
-    for (int b = g; b < nb; b += RG) ds += l[b * 2];
-    smd[g][o] = ds;
+  lds.sm[g][o] = s;
+  if (loss_block && o < 4) {
+    double ds = 0.0;
+    if (loss_column(loss_block, with_actor)) {
+      const int lrole = o >> 1;
+      const double* l = lpart + (size_t)lrole * pmax * 2 + (o & 1);
+      const int nb = lrole ? nblkC : nblkA;
+      for (int b = g; b < nb; b += RG) ds += l[b * 2];
+    }
+    lds.smd[g][o] = ds;
   }
   __syncthreads();
+}
+__device__ __forceinline__ void reduce_fold(const ReduceLds& lds, bool live, bool loss_block, bool with_actor, float& grad, double& lsum) {
+  const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
+  grad = 0.0f; lsum = 0.0;
+  if (g == 0 && live) {
+    float t = lds.sm[0][o];
+#pragma unroll
+    for (int q = 1; q < RG; ++q) t += lds.sm[q][o];
+    grad = t;
+  }
+  if (g == 0 && loss_column(loss_block, with_actor)) {
+    double t = lds.smd[0][o];
+#pragma unroll
+    for (int q = 1; q < RG; ++q) t += lds.smd[q][o];
+    lsum = t;
+  }
+}
+// fp16x2 weight gradient: the launch's largest |δ2| becomes the next launch's scale (mlp_x2.hpp), per role — threads 0 and 1 of the one block that calls it
+__device__ __forceinline__ void dw_scale_rollover(float* dscale) {
+  if (!dscale || threadIdx.x >= 2) return;
+  unsigned* mx = reinterpret_cast<unsigned*>(dscale + 2);
+  dscale[threadIdx.x] = dw_next_scale(mx[threadIdx.x], dscale[threadIdx.x]);
+  mx[threadIdx.x] = 0u;
+  if (threadIdx.x == 0) mx[2] = 0u;   // the 16-sample kernel's miss flag: update_repair_kernel has run by now
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(64 * RG) reduce_kernel(const float* __restrict__ gpart, const double* __restrict__ lpart,
+                                                         int nblkA, int nblkC, int pmax, int gstride, int Pa, int Pc,
+                                                         float* __restrict__ msg, StatsArgs st) {
+  const double* vfix = st.vfix;
+  if (MODE == 1 && vfix[3] == 0.0) return;
+  const int P = Pa + Pc;
+  const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + o;
+  const bool live = i < P && !(MODE == 1 && i < Pa);   // the exact pass recomputes the critic only
+  const bool last = blockIdx.x == gridDim.x - 1;       // the four loss sums ride on the last block
+  __shared__ ReduceLds lds;
+  float grad; double lsum;
+  reduce_partial_sums(lds, gpart, lpart, nblkA, nblkC, pmax, gstride, Pa, i, live, last, MODE != 1);
+  reduce_fold(lds, live, last, MODE != 1, grad, lsum);
+  if (g == 0 && live) msg[i] = grad;
+  if (last && g == 0 && o < 4 && !(MODE == 1 && (o >> 1) == 0)) msg[P + o] = (float)lsum;
+  if (MODE == 0 && last) dw_scale_rollover(st.dscale);
+  if (last && st.fused) {
+    __syncthreads();  // the four sums written above are visible to thread 0 of this block
+    if (threadIdx.x == 0) compute_stats(msg, P, st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, MODE);
+  }
+}
+
+// reduce_kernel<0> + Optimiser(ClipNorm(0.5), Adam(η)) in ONE launch (single GPU, speculative step: nothing sits between the
+// gradient and the optimiser). Same blocks, same fixed summation order as reduce_kernel; then every block leaves Σg² of its 64
+// outputs per parameter array, the grid meets at a ticket (144 blocks of 1024 threads: all resident — nothing else runs on the
+// device between an update kernel and the next one), every block sums the partials of the arrays it touches in block order
+// (all blocks that touch an array compute the same norm bit for bit) and applies ClipNorm + Adam to its 64 entries with
+// optim.hpp's arithmetic, like clipnorm_adam_kernel (oracle: orc_clipnorm_adam). The β powers are read before the ticket and
+// advanced after it by the block that holds an array's first entry. Saves a launch, a launch gap and the one-block-per-array
+// walk of the 4,096-entry arrays per optimiser step.
+struct FusedOptimArgs {
+  OptimCore c;
+  double* part /* [12][gridDim.x] */; unsigned* ticket /* [0] arrivals, [1] sticky time-out flag */; unsigned target;
+  unsigned long long timeout;   // ticks of the 100 MHz wall clock a block waits at the meeting point before it gives up (2 s)
+};
+// PEER = true (round 5): the DATA-PARALLEL optimiser step as one launch over the peer mailboxes of peer.hip — reduce → push this block's 64 sums into
+// every rank's mailbox → flag → wait for the W flags of this chunk → add the W slots in rank order → Σg² → ticket → ClipNorm + Adam. Replaces
+// reduce_kernel + peer_allreduce_kernel + clipnorm_adam_kernel (three launches, ≈ 40 µs beside an 85 µs update launch at 8192 envs per rank). A chunk
+// is a block's 64 floats, so chunks never wait on each other across ranks; the grid-wide ticket stays local to the GPU. The four loss sums ride in the
+// last block's chunk (indices P … P + 3), the statistics record is written from the all-reduced sums by that block. Every rank adds the same slots in
+// the same order and clips by the same norms: replicas stay bit-identical.
+template <bool PEER>
+__global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __restrict__ gpart, const double* __restrict__ lpart,
+                                                               int nblkA, int nblkC, int pmax, int gstride, int Pa, int Pc,
+                                                               float* __restrict__ msg, StatsArgs st, FusedOptimArgs oa, PeerArgs pa) {
+#pragma clang fp contract(off)
+  __shared__ double nrm2[12];
+  __shared__ float gsum[4];
+  const ParamTable& tab = oa.c.tab;
+  const int P = Pa + Pc;
+  const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + o;
+  const bool live = i < P;
+  // the block whose chunk holds the loss sums (indices P … P + 3; the launcher sizes the grid so that one block holds all four)
+  const bool last = blockIdx.x == (unsigned)(P / 64);
+  __shared__ ReduceLds lds;
+  reduce_partial_sums(lds, gpart, lpart, nblkA, nblkC, pmax, gstride, Pa, i, live, last, true);
+  // this entry's optimiser state: fetched before the meeting point, under its latency (the fold over the groups runs under these loads as well)
+  float m_old = 0.0f, v_old = 0.0f, p_old = 0.0f;
+  if (g == 0 && live) { m_old = oa.c.m[i]; v_old = oa.c.v[i]; p_old = oa.c.params[i]; }
+  float grad; double lsum4;
+  reduce_fold(lds, live, last, true, grad, lsum4);
   // the arrays this block's 64 outputs belong to: [a_lo, a_hi]
   const int i_lo = blockIdx.x * 64, i_hi = (i_lo + 63 < P - 1) ? i_lo + 63 : P - 1;
   int a_lo = 0, a_hi = 0;
-  while (a_lo < 11 && i_lo >= oa.off[a_lo + 1]) ++a_lo;
-  while (a_hi < 11 && i_hi >= oa.off[a_hi + 1]) ++a_hi;
+  while (a_lo < 11 && i_lo >= tab.off[a_lo + 1]) ++a_lo;
+  while (a_hi < 11 && i_hi >= tab.off[a_hi + 1]) ++a_hi;
   int arr = a_lo;
-  float grad = 0.0f;
   double bp0 = 0.0, bp1 = 0.0;
-  float m_old = 0.0f, v_old = 0.0f, p_old = 0.0f;   // this entry's optimiser state: fetched before the meeting point, under its latency
-  if (last && g == 0 && o < 4) {
-    double t = smd[0][o];
-#pragma unroll
-    for (int q = 1; q < RG; ++q) t += smd[q][o];
-    gsum[o] = (float)t;
-  }
+  if (last && g == 0 && o < 4) gsum[o] = (float)lsum4;
   if (last) __syncthreads();
   unsigned timed_out = 0;
   if (g == 0) {
     if (live) {
-      m_old = oa.m[i]; v_old = oa.v[i]; p_old = oa.params[i];
-      float t = sm[0][o];
-#pragma unroll
-      for (int q = 1; q < RG; ++q) t += sm[q][o];
-      grad = t;
-      while (arr < 11 && i >= oa.off[arr + 1]) ++arr;
-      bp0 = oa.betap[2 * arr]; bp1 = oa.betap[2 * arr + 1];
+      while (arr < 11 && i >= tab.off[arr + 1]) ++arr;
+      bp0 = oa.c.betap[2 * arr]; bp1 = oa.c.betap[2 * arr + 1];
     }
     const bool lsum = last && i >= P && i < P + 4;          // this lane carries one of the four loss sums
     float val = live ? grad : (lsum ? gsum[i - P] : 0.0f);
@@ -1017,13 +1006,8 @@ __global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __re
       if (o == 0) __hip_atomic_store(oa.part + (size_t)a * gridDim.x + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if (last && st.dscale && threadIdx.x < 2) {
-    unsigned* mx = reinterpret_cast<unsigned*>(st.dscale + 2);
-    st.dscale[threadIdx.x] = dw_next_scale(mx[threadIdx.x], st.dscale[threadIdx.x]);
-    mx[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) mx[2] = 0u;   // the 16-sample kernel's miss flag: update_repair_kernel has run by now
-  }
   if (last) {
+    dw_scale_rollover(st.dscale);
     __syncthreads();
     if (threadIdx.x == 0) compute_stats4(gsum[0], gsum[1], gsum[2], gsum[3], st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, 0);
   }
@@ -1064,7 +1048,7 @@ __global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __re
   __builtin_amdgcn_wave_barrier();
   asm volatile("" ::: "memory");
   for (int a = a_lo; a <= a_hi; ++a) {
-    const int b0 = oa.off[a] / 64, b1 = (oa.off[a + 1] - 1) / 64;
+    const int b0 = tab.off[a] / 64, b1 = (tab.off[a + 1] - 1) / 64;
     double t = 0.0;
     for (int b = b0 + o; b <= b1; b += 64) t += __hip_atomic_load(oa.part + (size_t)a * gridDim.x + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     t = wave_sum(t);
@@ -1072,18 +1056,12 @@ __global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __re
   }
   wave_lds_fence();
   if (!live) return;
-  const float nrm = (float)sqrt(nrm2[arr]);
-  const bool clip = (double)nrm > oa.thresh;
-  const double sc = clip ? oa.thresh / (double)nrm : 1.0;
-  const double b1c = 0.9, b2c = 0.999, epsn = 1e-8;
-  double gd = (double)grad;
-  if (clip) gd = (double)(float)(gd * sc);
-  const float mi = (float)(b1c * (double)m_old + (1 - b1c) * gd);
-  const float vi = (float)(b2c * (double)v_old + (1 - b2c) * gd * gd);
-  oa.m[i] = mi; oa.v[i] = vi;
-  const double delta = (double)mi / (1 - bp0) / (sqrt((double)vi / (1 - bp1)) + epsn) * oa.eta;
-  oa.params[i] = p_old - (float)delta;
-  if (i == oa.off[arr]) { oa.betap[2 * arr] = bp0 * b1c; oa.betap[2 * arr + 1] = bp1 * b2c; }
+  double sc;
+  const bool clip = clipnorm_scale(nrm2[arr], oa.c.thresh, sc);
+  float mi, vi, pi;
+  adam_entry((double)grad, m_old, v_old, p_old, bp0, bp1, oa.c.eta, clip, sc, mi, vi, pi);
+  oa.c.m[i] = mi; oa.c.v[i] = vi; oa.c.params[i] = pi;
+  if (i == tab.off[arr]) betap_advance(oa.c.betap, arr, bp0, bp1);
 }
 
 // Can the whole grid of reduce_optim_kernel be resident at once on this device? Its meeting point needs every block running: (P+4+63)/64
@@ -1245,17 +1223,13 @@ int launch_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot, bool inline_fix
         set_error("internal: the fused optimiser step needs a speculative step that is local or exchanged through the peer mailboxes"); return 1;
       }
       FusedOptimArgs oa;
-      const int hN = h->cfg.hidden, d = h->cfg.obs_dim, A = h->cfg.n_act;
-      const int sizes[12] = {hN * d, hN, hN * hN, hN, A * hN, A, hN * d, hN, hN * hN, hN, hN, 1};
-      oa.off[0] = 0;
-      for (int q = 0; q < 12; ++q) oa.off[q + 1] = oa.off[q] + sizes[q];
       const unsigned nb = (unsigned)((P + 4 + 63) / 64);     // the four loss sums ride behind the gradient, in the chunk of index P
       CRL_HIP_CHECK(hipGetLastError());   // an error left behind by an earlier call is reported as such, not mistaken for this launch's
       PeerArgs pa{};
       if (dp && peer_next_args(h, &pa, (int)nb, (size_t)P + 4)) return 1;
       h->ticket_target += nb;
-      oa.params = h->params; oa.m = h->adam_m; oa.v = h->adam_v; oa.betap = h->betap; oa.part = h->optim_part; oa.ticket = h->ticket;
-      oa.target = h->ticket_target; oa.eta = eta; oa.thresh = 0.5; oa.timeout = 200000000ull;
+      oa.c = optim_core(h, eta); oa.part = h->optim_part; oa.ticket = h->ticket;
+      oa.target = h->ticket_target; oa.timeout = 200000000ull;
       if (dp) {
         // a peer that never arrives ends the wait after peer_timeout_ms; the grid's own meeting point must outlast that
         const unsigned long long pt = (unsigned long long)pa.timeout_ticks + 200000000ull;

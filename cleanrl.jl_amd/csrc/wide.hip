@@ -21,6 +21,7 @@
 #include "env.hpp"
 #include "mlp_x2.hpp"
 #include "mlp_x3.hpp"
+#include "optim.hpp"
 #include "policy_rt.hpp"
 #include "ppo_ctx.hpp"
 #include "stats.hpp"
@@ -2317,7 +2318,7 @@ __global__ void __launch_bounds__(256) wide_loss_kernel(WLossArgs a) {
 // Fixed-order sum of all partials → flat Flux-ordered gradient + the four loss sums (the all-reduce message)
 // ------------------------------------------------------------------------------------------------------
 struct WRedArgs {
-  const float* part[12]; int nparts[12]; int off[13];
+  const float* part[12]; int nparts[12]; ParamTable tab;
   int boff[13];                      // first block of every array (256 elements per block; arrays without partials get none)
   const double* lpart; int nlb; float* out; int P; int A;
   int with_stats; StatsArgs st;      // one GPU: the block that folds the loss sums also writes the "Training Statistics" record (no launch of its own)
@@ -2360,8 +2361,8 @@ __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
       if (live) {
         const float f = (float)sm[q][0];
         if (q < 4) { a.out[a.P + q] = f; lsum4[q] = f; }
-        else if (q == 4 + AMAX) a.out[a.off[11]] = f;
-        else a.out[a.off[5] + (q - 4)] = f;
+        else if (q == 4 + AMAX) a.out[a.tab.off[11]] = f;
+        else a.out[a.tab.off[5] + (q - 4)] = f;
       }
     }
     __syncthreads();
@@ -2376,7 +2377,7 @@ __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
   int arr = 0;
 #pragma unroll
   for (int k = 1; k < 12; ++k) arr = ((int)blockIdx.x >= a.boff[k]) ? k : arr;
-  const int size = a.off[arr + 1] - a.off[arr], idx = ((int)blockIdx.x - a.boff[arr]) * 256 + 4 * e4, np = a.nparts[arr];
+  const int size = a.tab.off[arr + 1] - a.tab.off[arr], idx = ((int)blockIdx.x - a.boff[arr]) * 256 + 4 * e4, np = a.nparts[arr];
   const float* p = a.part[arr];
   const bool live = p != nullptr && idx < size;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -2406,7 +2407,7 @@ __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
   __syncthreads();
   {
     const int e = threadIdx.x, i = ((int)blockIdx.x - a.boff[arr]) * 256 + e;
-    if (p != nullptr && i < size) a.out[a.off[arr] + i] = (float)(((fold[0][e] + fold[1][e]) + fold[2][e]) + fold[3][e]);
+    if (p != nullptr && i < size) a.out[a.tab.off[arr] + i] = (float)(((fold[0][e] + fold[1][e]) + fold[2][e]) + fold[3][e]);
   }
 }
 
@@ -2895,10 +2896,7 @@ int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot) {
   }
   {
     WRedArgs r;
-    const int H = w->H, D = w->D, A = w->A;
-    const int sizes[12] = {H * D, H, H * H, H, A * H, A, H * D, H, H * H, H, H, 1};
-    r.off[0] = 0;
-    for (int i = 0; i < 12; ++i) r.off[i + 1] = r.off[i] + sizes[i];
+    r.tab = h->ptab;
     for (int n = 0; n < 2; ++n) {
       const int b = 6 * n;
       r.part[b + 0] = w->net[n].pW1; r.nparts[b + 0] = w->fb_blocks ? w->fb_blocks_net[n] : w->Ss;
@@ -2908,11 +2906,11 @@ int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot) {
       r.part[b + 4] = w->net[n].pW3; r.nparts[b + 4] = w->w3_blocks ? w->fb_blocks_net[n] : w->Ss;
       r.part[b + 5] = nullptr; r.nparts[b + 5] = 0;
     }
-    r.lpart = w->lpart; r.nlb = w->nlb; r.out = h->comm_buf; r.P = P; r.A = A;
+    r.lpart = w->lpart; r.nlb = w->nlb; r.out = h->comm_buf; r.P = P; r.A = w->A;
     r.with_stats = dp ? 0 : 1;
     r.st.c = h->dc; r.st.Mglobal = Mglobal; r.st.adv_ms = h->adv_ms; r.st.mb = mb; r.st.vfix = h->vfix; r.st.out = stats_slot; r.st.fused = 0; r.st.dscale = nullptr;
     r.boff[0] = 0;
-    for (int i = 0; i < 12; ++i) r.boff[i + 1] = r.boff[i] + (r.part[i] ? (sizes[i] + 255) / 256 : 0);
+    for (int i = 0; i < 12; ++i) r.boff[i + 1] = r.boff[i] + (r.part[i] ? (r.tab.off[i + 1] - r.tab.off[i] + 255) / 256 : 0);
     ProfScope pr(h, CRL_K_REDUCE);
     hipLaunchKernelGGL(wide_reduce_kernel, dim3(r.boff[12] + 1), dim3(256), 0, h->stream, r);
     CRL_HIP_CHECK(hipGetLastError());
