@@ -6,7 +6,7 @@
 // the reference's own layout — and every dense layer is one tiled v_mfma_f32_32x32x2_f32 GEMM:
 //   forward          Y = act(W·X + b)            wide_dense_kernel<EPI_TANH | EPI_BIAS>
 //   backward (data)  dX = (Wᵀ·dY) ⊙ (1 − X²)     wide_dense_kernel<EPI_DTANH> on a transposed weight copy
-//   backward (weight) dW = dY·Xᵀ, db = Σ dY      wide_wgrad_kernel: the reduction runs over samples, both operands are
+//   backward (weight) dW = dY·Xᵀ, db = Σ dY      wide_wgrad_kernel (wide_wgrad.hpp): the reduction runs over samples, both operands are
 //                                                 read feature-fastest (no transpose anywhere), split over sample
 //                                                 chunks into per-block partials, summed in fixed order afterwards
 //   K ≤ 16 / N ≤ 16 weight gradients (dW1, dW3)  wide_skinny_kernel on the VALU (no MFMA shape fits)
@@ -30,7 +30,6 @@ namespace crl {
 
 constexpr int WXS = 36;    // LDS stride (floats) of one staged sample row: 32 k + 4 pad → conflict-free ds_read_b128
 constexpr int WLS = 24;    // doubles per loss-kernel block partial: pg, Σ-entropy, Σ(v−R²), Σ value term, db3a[16], db3c
-constexpr int AFUSE = 8;   // most head outputs the fused δ2 paths keep in registers (more ⇒ the separate launch)
 
 enum { EPI_TANH = 0, EPI_BIAS = 1, EPI_DTANH = 2, EPI_STORE = 3 };
 
@@ -623,9 +622,6 @@ struct DenseX3Args {
   float* Y; int M;
   // optional fused head (EPI_TANH, 8-wave variant): Z[a, m] = Σ_n W3[a, n]·Y[n, m] + b3[a] while the tile is at hand
   const float* W3t; const float* b3; float* Z; int A; int ldz;   // W3t: [256 × ·] column-major (ld 256); Z null = no head
-  // optional virtual input (EPI_DTANH): X holds h2 and the operand is formed on the fly as δ2 = (W3ᵀ·δ3) ⊙ (1 − h2²) from
-  // the head cotangent dZ[·, m] (ld ldd, zero-padded) — the [256 × M] δ2 array is never written or read
-  const float* dZ; int ldd; int Ad;      // dZ null = X is the operand itself; Ad = live rows of dZ
   // fp16x2 backward-data (wide_dense_x2_kernel<EPI_DTANH>): the head cotangent and wmax, from which each sample's scale comes
   const float* bz; int bld; int bA; const float* wmax;
   int fast_act = 0;   // as DenseArgs::fast_act
@@ -698,36 +694,7 @@ __global__ void __launch_bounds__(64 * NW) wide_dense_x3_kernel(DenseX3Args a) {
   }
   u32x4v wr[WR]; f32x4 xr[XR];
   const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  // virtual input: this thread's samples are fixed for the whole K walk, so their head cotangents sit in registers
-  const bool virt = (EPI == EPI_DTANH) && a.dZ != nullptr;   // compile-time dead in the forward instantiations
-  float dzr[XR][AFUSE];
-  if (virt) {
-#pragma unroll
-    for (int u = 0; u < XR; ++u) {
-      const int i = tid + NT * u, mm = i >> 3, m = m0 + mm;
-#pragma unroll
-      for (int q2 = 0; q2 < AFUSE; ++q2) dzr[u][q2] = (xok[u] && q2 < a.Ad) ? a.dZ[(size_t)a.ldd * m + q2] : 0.0f;
-    }
-  }
-  auto load_x = [&](int sl, int u) -> f32x4 {
-    if (!xok[u]) return zero4;
-    f32x4 v = xsrc[u][sl * 8];
-    if (virt) {
-      const int k = 32 * sl + 4 * ((tid + NT * u) & 7);
-      f32x4 sacc = zero4;
-#pragma unroll
-      for (int q2 = 0; q2 < AFUSE; ++q2) {
-        if (q2 < a.Ad) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(a.W3t + (size_t)256 * q2 + k);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sacc[e] = __builtin_fmaf(w[e], dzr[u][q2], sacc[e]);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = sacc[e] * (1.0f - v[e] * v[e]);
-    }
-    return v;
-  };
+  auto load_x = [&](int sl, int u) -> f32x4 { return xok[u] ? xsrc[u][sl * 8] : zero4; };
 #pragma unroll
   for (int u = 0; u < WR; ++u) wr[u] = wsrc[NT * u];
 #pragma unroll
@@ -892,6 +859,7 @@ __device__ __forceinline__ void tile_out_x2(float* scr, const f32x16& acc, int l
 
 }  // namespace crl
 #include "wide_fused.hpp"
+#include "wide_wgrad.hpp"
 namespace crl {
 
 template <int EPI, int TM>
@@ -1071,7 +1039,7 @@ static DenseX3Args dense_x3_fwd_args(const crl_ppo* h, const WideNet& n, int M, 
   DenseX3Args x;
   x.Wx3 = wide_x2(h) ? n.x2f : n.x3f; x.X = n.h1; x.K = 256; x.bias = n.b2; x.S = nullptr; x.Y = n.h2; x.M = M;
   x.W3t = n.w3t; x.b3 = n.b3; x.Z = Z; x.A = n.NO; x.ldz = ldz;
-  x.dZ = nullptr; x.ldd = 0; x.Ad = 0; x.bz = nullptr; x.bld = 0; x.bA = 0; x.wmax = nullptr; x.fast_act = fast; x.wsc = n.wsc;
+  x.bz = nullptr; x.bld = 0; x.bA = 0; x.wmax = nullptr; x.fast_act = fast; x.wsc = n.wsc;
   return x;
 }
 
@@ -1111,436 +1079,6 @@ static int wide_forward_pair(crl_ppo* h, const float* X, int ldx, int M, float* 
   hipLaunchKernelGGL((wide_dense_x2_pair_kernel<EPI_TANH, 1>), dim3((M + 31) / 32, 2), dim3(512), s0 > s1 ? s0 : s1, h->stream, x0, x1);
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Weight gradient of a hidden layer: dW[n, k] = Σ_m dY[n, m]·X[k, m], db[n] = Σ_m dY[n, m] over one sample chunk.
-// Block = one (64·TW)² output tile × one chunk; both operands are (feature, sample) arrays, so a 32-sample slab of
-// either is BT contiguous floats per sample and the MFMA operands are read feature-fastest from LDS.
-// ------------------------------------------------------------------------------------------------------
-struct WgradArgs {
-  const float* dY; const float* X; int H; int M; int chunk; float* pW; float* pB;
-  // x3 kernel only: dZ != null ⇒ dY holds h2 and the operand is δ2 = (W3ᵀ·δ3) ⊙ (1 − h2²), formed while staging
-  const float* dZ; int ldd; int Ad; const float* W3t;
-  // x2 kernel: the head cotangent (bz, ld bld, bA live rows) and wmax bound |δ2| per sample — the block's scale comes from them
-  const float* bz; int bld; int bA; const float* wmax;
-  // GEN flavour (wide_wgrad_x2_kernel<4, true>): X is not read — h1 is regenerated from the observations (wide_fused.hpp, wide_wgrad_gen_kernel)
-  const float* obs = nullptr; const int32_t* perm = nullptr; int D = 0; const float* W1f = nullptr; const float* w1sc = nullptr;
-};
-
-template <int TW>
-__global__ void __launch_bounds__(256) wide_wgrad_kernel(WgradArgs a) {
-  constexpr int BT = 64 * TW;
-  __shared__ __attribute__((aligned(16))) float Yl[32 * BT];
-  __shared__ __attribute__((aligned(16))) float Xl[32 * BT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hf = lane >> 5;
-  const int nb = a.H / BT, tnb = blockIdx.y % nb, tkb = blockIdx.y / nb;
-  const int n0 = tnb * BT, kk0 = tkb * BT;
-  const int wn = wave & 1, wk = wave >> 1;
-  f32x16 acc[TW][TW];
-#pragma unroll
-  for (int x = 0; x < TW; ++x)
-#pragma unroll
-    for (int y = 0; y < TW; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.0f;
-  f32x4 bacc = {0.0f, 0.0f, 0.0f, 0.0f};
-  const int c0 = blockIdx.x * a.chunk;
-  const int c1 = (c0 + a.chunk) < a.M ? (c0 + a.chunk) : a.M;
-  // thread t stages float4 slots t, t+256, … of the [32][BT] slab: slot → (sample p / BT, rows p % BT); BT·8 slots / 256
-  // threads = BT/32 per thread, each a fixed (sample offset, row) pair — pointers are set up once
-  constexpr int NU = BT / 32;
-  int soff[NU], mmu[NU];   // element offset of the slot inside a slab (rows relative to the block's first row)
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int p = 4 * (tid + 256 * u), mm = p / BT, n = p - mm * BT;
-    mmu[u] = mm;
-    soff[u] = a.H * mm + n;
-  }
-  const float* ybase = a.dY + (size_t)a.H * c0 + n0;
-  const float* xbase = a.X + (size_t)a.H * c0 + kk0;
-  const bool do_bias = (tkb == 0) && a.pB;
-  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  f32x4 yr[NU], xr[NU];
-  auto fetch = [&](int m) {
-    const int mv = c1 - m;   // samples left in the chunk
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const bool ok = mmu[u] < mv;
-      const size_t off = (size_t)a.H * (m - c0);   // wave-uniform
-      yr[u] = ok ? *reinterpret_cast<const f32x4*>(ybase + off + soff[u]) : zero4;
-      xr[u] = ok ? *reinterpret_cast<const f32x4*>(xbase + off + soff[u]) : zero4;
-    }
-  };
-  if (c0 < c1) fetch(c0);
-  for (int m = c0; m < c1; m += 32) {
-    if (m != c0) __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      *reinterpret_cast<f32x4*>(Yl + 4 * (tid + 256 * u)) = yr[u];
-      *reinterpret_cast<f32x4*>(Xl + 4 * (tid + 256 * u)) = xr[u];
-      if (do_bias) bacc += yr[u];
-    }
-    __syncthreads();
-    if (m + 32 < c1) fetch(m + 32);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int mm = 2 * s + hf;
-      float av[TW], bv[TW];
-#pragma unroll
-      for (int x = 0; x < TW; ++x) av[x] = Yl[mm * BT + (wn * TW + x) * 32 + j];
-#pragma unroll
-      for (int y = 0; y < TW; ++y) bv[y] = Xl[mm * BT + (wk * TW + y) * 32 + j];
-#pragma unroll
-      for (int x = 0; x < TW; ++x)
-#pragma unroll
-        for (int y = 0; y < TW; ++y) acc[x][y] = mfma32(av[x], bv[y], acc[x][y]);
-    }
-  }
-  __syncthreads();
-  float* pw = a.pW + (size_t)blockIdx.x * a.H * a.H;
-#pragma unroll
-  for (int x = 0; x < TW; ++x)
-#pragma unroll
-    for (int y = 0; y < TW; ++y) {
-      const int k = kk0 + (wk * TW + y) * 32 + j;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = n0 + (wn * TW + x) * 32 + 8 * g + 4 * hf;
-        f32x4 o; o[0] = acc[x][y][4 * g]; o[1] = acc[x][y][4 * g + 1]; o[2] = acc[x][y][4 * g + 2]; o[3] = acc[x][y][4 * g + 3];
-        *reinterpret_cast<f32x4*>(pw + (size_t)a.H * k + n) = o;
-      }
-    }
-  if (tkb == 0 && a.pB) {
-    // thread t always staged rows (4t mod BT)..+3: fold the 1024/BT threads that share a row quad, in thread order
-    *reinterpret_cast<f32x4*>(Yl + 4 * tid) = bacc;
-    __syncthreads();
-    if (tid < BT) {
-      const int quad = tid >> 2, e = tid & 3;
-      float s = 0.0f;
-      for (int q = 0; q < 1024 / BT; ++q) s += Yl[4 * (quad + (BT / 4) * q) + e];
-      a.pB[(size_t)blockIdx.x * a.H + n0 + tid] = s;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The same weight gradient on the bf16 matrix pipe (bf16x3) for 256-wide layers. The reduction runs over SAMPLES, so an
-// MFMA operand needs 8 consecutive samples of one row — the strided direction of the (feature, sample) arrays. The
-// staging loads are therefore shaped as 4×4 blocks per thread (4 consecutive rows × 4 consecutive samples: four 16-B
-// loads), which a thread can transpose in its own registers: each row's 4 samples are split into bf16 hi/mid/lo and
-// written with one ds_write_b64 per piece into row-major [row][sample] LDS images (row stride 80 B: conflict-free
-// b128 fragment reads). No f32 copy of the slab ever exists in LDS.
-// ------------------------------------------------------------------------------------------------------
-template <int WNB>   // output tile = (64·WNB rows of dY) × (128 rows of X); 2·WNB waves, each 2×2 MFMA tiles
-__global__ void __launch_bounds__(128 * WNB) wide_wgrad_x3_kernel(WgradArgs a) {
-  constexpr int BN = 64 * WNB, BK = 128;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smw[];
-  __bf16* Yp = reinterpret_cast<__bf16*>(smw);                 // [3][BN][X3ROW]
-  __bf16* Xp = Yp + 3 * BN * X3ROW;                            // [3][BK][X3ROW]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hf = lane >> 5;
-  const int nbn = a.H / BN;
-  const int tnb = blockIdx.y % nbn, tkb = blockIdx.y / nbn;
-  const int n0 = tnb * BN, kk0 = tkb * BK;
-  const int wn = wave % WNB, wk = wave / WNB;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.0f;
-  const int c0 = blockIdx.x * a.chunk;
-  const int c1 = (c0 + a.chunk) < a.M ? (c0 + a.chunk) : a.M;
-  // staging role of this thread: rows 32·wave + 4·ql .. +3, samples 4·sg .. +3 of the slab's 32 (X: the first 4 waves).
-  // sg on the low lane bits: the 16 lanes one ds_write_b64 group covers are then 8 sample groups (16 consecutive dwords)
-  // of two row quads (80 dwords apart = 16 banks) — conflict-free; with the row quad on the low bits the same store
-  // was 4-way conflicted (SQ_LDS_BANK_CONFLICT 21 % of the kernel's CU cycles)
-  const int sg = lane & 7, ql = lane >> 3;
-  const int rrow = 32 * wave + 4 * ql;
-  const bool stage_x = wave < BK / 32;
-  const float* ybase = a.dY + (size_t)a.H * c0 + n0 + rrow;
-  const float* xbase = a.X + (size_t)a.H * c0 + kk0 + rrow;
-  const bool do_bias = (tkb == 0) && a.pB;
-  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  f32x4 yr[4], xr[4], bacc = zero4;
-  // virtual dY: the head's rows for this thread's four hidden units stay in registers for the whole chunk
-  const bool virt = a.dZ != nullptr;
-  f32x4 w3r[AFUSE];
-  if (virt) {
-#pragma unroll
-    for (int q2 = 0; q2 < AFUSE; ++q2)
-      w3r[q2] = q2 < a.Ad ? *reinterpret_cast<const f32x4*>(a.W3t + (size_t)256 * q2 + n0 + rrow) : zero4;
-  }
-  auto fetch = [&](int m) {
-    const size_t off = (size_t)a.H * (m - c0 + 4 * sg);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const bool ok = m + 4 * sg + e < c1;
-      f32x4 y = ok ? *reinterpret_cast<const f32x4*>(ybase + off + (size_t)a.H * e) : zero4;
-      if (virt && ok) {
-        const float* dz = a.dZ + (size_t)a.ldd * (m + 4 * sg + e);
-        f32x4 sacc = zero4;
-#pragma unroll
-        for (int q2 = 0; q2 < AFUSE; ++q2)
-          if (q2 < a.Ad) { const float dv = dz[q2]; sacc += w3r[q2] * dv; }
-        y = sacc * (1.0f - y * y);
-      }
-      yr[e] = y;
-      xr[e] = (ok && stage_x) ? *reinterpret_cast<const f32x4*>(xbase + off + (size_t)a.H * e) : zero4;
-    }
-  };
-  if (c0 < c1) fetch(c0);
-  for (int m = c0; m < c1; m += 32) {
-    if (m != c0) __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {          // row rrow + e: its four samples sit in component e of the four loads
-      f32x4 vy;
-      vy[0] = yr[0][e]; vy[1] = yr[1][e]; vy[2] = yr[2][e]; vy[3] = yr[3][e];
-      uint2 h, mm, l;
-      split3x4(vy, h, mm, l);
-      *reinterpret_cast<uint2*>(Yp + (0 * BN + rrow + e) * X3ROW + 4 * sg) = h;
-      *reinterpret_cast<uint2*>(Yp + (1 * BN + rrow + e) * X3ROW + 4 * sg) = mm;
-      *reinterpret_cast<uint2*>(Yp + (2 * BN + rrow + e) * X3ROW + 4 * sg) = l;
-      if (stage_x) {
-        f32x4 vx;
-        vx[0] = xr[0][e]; vx[1] = xr[1][e]; vx[2] = xr[2][e]; vx[3] = xr[3][e];
-        split3x4(vx, h, mm, l);
-        *reinterpret_cast<uint2*>(Xp + (0 * BK + rrow + e) * X3ROW + 4 * sg) = h;
-        *reinterpret_cast<uint2*>(Xp + (1 * BK + rrow + e) * X3ROW + 4 * sg) = mm;
-        *reinterpret_cast<uint2*>(Xp + (2 * BK + rrow + e) * X3ROW + 4 * sg) = l;
-      }
-    }
-    if (do_bias) bacc += (yr[0] + yr[1]) + (yr[2] + yr[3]);
-    __syncthreads();
-    if (m + 32 < c1) fetch(m + 32);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      P3 af[2], bf[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        const int off = ((wn * 2 + x) * 32 + j) * X3ROW + 16 * ks + 8 * hf;
-        af[x].hi = *reinterpret_cast<const bf16x8*>(Yp + 0 * BN * X3ROW + off);
-        af[x].mid = *reinterpret_cast<const bf16x8*>(Yp + 1 * BN * X3ROW + off);
-        af[x].lo = *reinterpret_cast<const bf16x8*>(Yp + 2 * BN * X3ROW + off);
-      }
-#pragma unroll
-      for (int y = 0; y < 2; ++y) {
-        const int off = ((wk * 2 + y) * 32 + j) * X3ROW + 16 * ks + 8 * hf;
-        bf[y].hi = *reinterpret_cast<const bf16x8*>(Xp + 0 * BK * X3ROW + off);
-        bf[y].mid = *reinterpret_cast<const bf16x8*>(Xp + 1 * BK * X3ROW + off);
-        bf[y].lo = *reinterpret_cast<const bf16x8*>(Xp + 2 * BK * X3ROW + off);
-      }
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = mfma_x3(af[x], bf[y], acc[x][y]);
-    }
-  }
-  __syncthreads();
-  float* pw = a.pW + (size_t)blockIdx.x * a.H * a.H;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-      const int k = kk0 + (wk * 2 + y) * 32 + j;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = n0 + (wn * 2 + x) * 32 + 8 * g + 4 * hf;
-        f32x4 o; o[0] = acc[x][y][4 * g]; o[1] = acc[x][y][4 * g + 1]; o[2] = acc[x][y][4 * g + 2]; o[3] = acc[x][y][4 * g + 3];
-        *reinterpret_cast<f32x4*>(pw + (size_t)a.H * k + n) = o;
-      }
-    }
-  if (do_bias) {
-    // fold the 8 sample groups of a row quad (lanes 8·ql + sg) in group order; lanes with sg = 0 own rows rrow..rrow+3
-    float* scr = reinterpret_cast<float*>(smw);
-    *reinterpret_cast<f32x4*>(scr + 4 * tid) = bacc;
-    __syncthreads();
-    if (sg == 0) {
-      f32x4 sacc = bacc;
-      for (int q = 1; q < 8; ++q) sacc += *reinterpret_cast<const f32x4*>(scr + 4 * (tid + q));
-      *reinterpret_cast<f32x4*>(a.pB + (size_t)blockIdx.x * a.H + n0 + rrow) = sacc;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The same weight gradient as fp16x2 (mlp_x2.hpp). The reduction runs over samples, so dY = δ2 needs ONE power-of-two scale
-// for everything a block accumulates — and a block owns one sample chunk whose partial is unscaled before it is written, so
-// the scale is the block's own: G = 2^(14 − ⌈log2 max_m bound_m⌉) over the chunk's samples, bound_m = Σ_a |δ3[a, m]|·wmax[a]
-// (≥ every |δ2[·, m]|; a few KB of reads, no pass over δ2). X = h1 takes the static 2^14.
-// ------------------------------------------------------------------------------------------------------
-template <int WNB, bool GEN = false>
-__global__ void __launch_bounds__(128 * WNB) wide_wgrad_x2_kernel(WgradArgs a) {
-  constexpr int BN = 64 * WNB, BK = 128, NT = 128 * WNB;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smw[];
-  _Float16* Yp = reinterpret_cast<_Float16*>(smw);             // [2][BN][X3ROW]
-  _Float16* Xp = Yp + 2 * BN * X3ROW;                          // [2][BK][X3ROW]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hf = lane >> 5;
-  const int nbn = a.H / BN;
-  const int tnb = blockIdx.y % nbn, tkb = blockIdx.y / nbn;
-  const int n0 = tnb * BN, kk0 = tkb * BK;
-  const int wn = wave % WNB, wk = wave / WNB;
-  const int c0 = blockIdx.x * a.chunk;
-  const int c1 = (c0 + a.chunk) < a.M ? (c0 + a.chunk) : a.M;
-  // the block's scale
-  float G, Ginv;
-  {
-    float bmax = 0.0f;
-    for (int m = c0 + tid; m < c1; m += NT) {
-      float bound = 0.0f;
-      for (int q2 = 0; q2 < a.bA; ++q2) bound = __builtin_fmaf(__builtin_fabsf(a.bz[(size_t)a.bld * m + q2]), a.wmax[q2], bound);
-      bmax = __builtin_fmaxf(bmax, bound);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) bmax = __builtin_fmaxf(bmax, __shfl_xor(bmax, o, 64));
-    float* red = reinterpret_cast<float*>(smw);
-    if (lane == 0) red[wave] = bmax;
-    __syncthreads();
-    bmax = red[0];
-    for (int w8 = 1; w8 < NT / 64; ++w8) bmax = __builtin_fmaxf(bmax, red[w8]);
-    __syncthreads();
-    pow2_scale(bmax, G, Ginv);
-  }
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.0f;
-  const int sg = lane & 7, ql = lane >> 3;
-  const int rrow = 32 * wave + 4 * ql;
-  const bool stage_x = wave < BK / 32;
-  const float* ybase = a.dY + (size_t)a.H * c0 + n0 + rrow;
-  const float* xbase = GEN ? nullptr : a.X + (size_t)a.H * c0 + kk0 + rrow;
-  const bool do_bias = (tkb == 0) && a.pB;
-  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  f32x4 yr[4], xr[4], bacc = zero4;
-  // GEN: waves 0-3 regenerate their 32-unit tile of the h1 slab with one fp16x2 product (see wide_wgrad_gen_kernel): W1ᵀ fragment + bias in registers
-  P2 w1b; float b1u = 0.0f, w1un = 0.0f, xo[8];
-  int src_nx = 0;
-  if (GEN && stage_x) {
-    src_nx = (c0 + j < c1) ? (a.perm ? a.perm[c0 + j] : c0 + j) : 0;
-    const f16x8* wf = reinterpret_cast<const f16x8*>(a.W1f) + ((kk0 / 32 + wave) * 2) * 64 + lane;
-    w1b.hi = wf[0]; w1b.lo = wf[64];
-    b1u = a.W1f[4096 + kk0 + 32 * wave + j]; w1un = a.w1sc[1];
-  }
-  auto fetch = [&](int m) {
-    const size_t off = (size_t)a.H * (m - c0 + 4 * sg);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const bool ok = m + 4 * sg + e < c1;
-      yr[e] = ok ? *reinterpret_cast<const f32x4*>(ybase + off + (size_t)a.H * e) : zero4;
-      if (!GEN) xr[e] = (ok && stage_x) ? *reinterpret_cast<const f32x4*>(xbase + off + (size_t)a.H * e) : zero4;
-    }
-    if (GEN && stage_x) {
-      // the observation row index of this slab's sample was loaded a slab earlier (a dependent perm → obs chain inside one fetch stalls the
-      // wave for a memory round trip before its MFMAs: 497 instead of ≈300 us per launch)
-      const bool ok = m + j < c1;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) xo[c] = 0.0f;
-      load_obs8(a.obs, (size_t)src_nx, a.D, 8 * hf, ok, xo);
-      const int mn = m + 32 + j;
-      src_nx = mn < c1 ? (a.perm ? a.perm[mn] : mn) : 0;
-    }
-  };
-  if (c0 < c1) fetch(c0);
-  for (int m = c0; m < c1; m += 32) {
-    if (m != c0) __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f32x4 vy;
-      vy[0] = yr[0][e]; vy[1] = yr[1][e]; vy[2] = yr[2][e]; vy[3] = yr[3][e];
-      uint2 hh, ll;
-      split2x4(vy, G, hh, ll);
-      *reinterpret_cast<uint2*>(Yp + (0 * BN + rrow + e) * X3ROW + 4 * sg) = hh;
-      *reinterpret_cast<uint2*>(Yp + (1 * BN + rrow + e) * X3ROW + 4 * sg) = ll;
-      if (!GEN && stage_x) {
-        f32x4 vx;
-        vx[0] = xr[0][e]; vx[1] = xr[1][e]; vx[2] = xr[2][e]; vx[3] = xr[3][e];
-        split2x4(vx, X2_ACT_SCALE, hh, ll);
-        *reinterpret_cast<uint2*>(Xp + (0 * BK + rrow + e) * X3ROW + 4 * sg) = hh;
-        *reinterpret_cast<uint2*>(Xp + (1 * BK + rrow + e) * X3ROW + 4 * sg) = ll;
-      }
-    }
-    if (GEN && stage_x) {
-      float mx = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) mx = __builtin_fmaxf(mx, __builtin_fabsf(xo[c]));
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, o, 64));
-      float sx, ix;
-      pow2_scale(mx, sx, ix);
-      float v[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) v[c] = xo[c] * sx;
-      const P2 xa = split2(v);
-      f32x16 c16;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) c16[r] = 0.0f;
-      c16 = mfma_x2(xa, w1b, c16);                              // rows = samples (registers), columns = units (lanes)
-      const float un1 = ix * w1un;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = tanh_exp2_arg(__builtin_fmaf(c16[4 * g + e], un1, b1u), X2_ACT_SCALE);
-        uint2 hh, ll;
-        split2x4(hv, 1.0f, hh, ll);
-        *reinterpret_cast<uint2*>(Xp + (0 * BK + 32 * wave + j) * X3ROW + 8 * g + 4 * hf) = hh;
-        *reinterpret_cast<uint2*>(Xp + (1 * BK + 32 * wave + j) * X3ROW + 8 * g + 4 * hf) = ll;
-      }
-    }
-    if (do_bias) bacc += (yr[0] + yr[1]) + (yr[2] + yr[3]);
-    __syncthreads();
-    if (m + 32 < c1) fetch(m + 32);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      P2 af[2], bf[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        const int off = ((wn * 2 + x) * 32 + j) * X3ROW + 16 * ks + 8 * hf;
-        af[x].hi = *reinterpret_cast<const f16x8*>(Yp + 0 * BN * X3ROW + off);
-        af[x].lo = *reinterpret_cast<const f16x8*>(Yp + 1 * BN * X3ROW + off);
-      }
-#pragma unroll
-      for (int y = 0; y < 2; ++y) {
-        const int off = ((wk * 2 + y) * 32 + j) * X3ROW + 16 * ks + 8 * hf;
-        bf[y].hi = *reinterpret_cast<const f16x8*>(Xp + 0 * BK * X3ROW + off);
-        bf[y].lo = *reinterpret_cast<const f16x8*>(Xp + 1 * BK * X3ROW + off);
-      }
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = mfma_x2(af[x], bf[y], acc[x][y]);
-    }
-  }
-  __syncthreads();
-  const float un = Ginv * (1.0f / X2_ACT_SCALE);
-  float* pw = a.pW + (size_t)blockIdx.x * a.H * a.H;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-      const int k = kk0 + (wk * 2 + y) * 32 + j;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = n0 + (wn * 2 + x) * 32 + 8 * g + 4 * hf;
-        f32x4 o; o[0] = acc[x][y][4 * g] * un; o[1] = acc[x][y][4 * g + 1] * un; o[2] = acc[x][y][4 * g + 2] * un; o[3] = acc[x][y][4 * g + 3] * un;
-        *reinterpret_cast<f32x4*>(pw + (size_t)a.H * k + n) = o;
-      }
-    }
-  if (do_bias) {
-    float* scr = reinterpret_cast<float*>(smw);
-    *reinterpret_cast<f32x4*>(scr + 4 * tid) = bacc;
-    __syncthreads();
-    if (sg == 0) {
-      f32x4 sacc = bacc;
-      for (int q = 1; q < 8; ++q) sacc += *reinterpret_cast<const f32x4*>(scr + 4 * (tid + q));
-      *reinterpret_cast<f32x4*>(a.pB + (size_t)blockIdx.x * a.H + n0 + rrow) = sacc;
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2571,7 +2109,7 @@ static SkinnyArgs dw3_args(const WideWs* w, const WideNet& n, int M, float* D2ou
 static WgradArgs wgrad_args(const WideWs* w, const WideNet& n, const float* dY, const float* X, int M) {
   WgradArgs g;
   g.dY = dY; g.X = X; g.H = w->H; g.M = M; g.chunk = w->chunk2; g.pW = n.pW2; g.pB = n.pB2;
-  g.dZ = nullptr; g.ldd = n.ldd; g.Ad = n.NO; g.W3t = n.w3t; g.bz = n.dout; g.bld = n.ldd; g.bA = n.NO; g.wmax = n.wmax;
+  g.bz = n.dout; g.bld = n.ldd; g.bA = n.NO; g.wmax = n.wmax;
   return g;
 }
 
@@ -2677,7 +2215,6 @@ static int wide_backward(crl_ppo* h, int net, const int32_t* idx) {
     DenseX3Args x;
     x.Wx3 = x2 ? n.x2b : n.x3b; x.X = w->dA; x.K = H; x.bias = nullptr; x.S = n.h1; x.Y = w->dB; x.M = M;
     x.W3t = n.w3t; x.b3 = nullptr; x.Z = nullptr; x.A = 0; x.ldz = 0;
-    x.dZ = nullptr; x.ldd = n.ldd; x.Ad = n.NO;
     x.bz = n.dout; x.bld = n.ldd; x.bA = n.NO; x.wmax = n.wmax; x.wsc = n.wsc;
     if (x2 ? dense_x2_launch<EPI_DTANH>(h->stream, x) : dense_x3_launch<EPI_DTANH>(h->stream, x)) return 1;
   } else {

@@ -165,6 +165,22 @@ def test_every_2x256_kernel_flavour_matches_the_oracle_on_a_576_sample_minibatch
     _flavour_case(crl, opts, D, A, nt, 2304 // nt)
 
 
+WGRAD_FLAVOURS = [
+    {}, {"wide_fuse": 3, "wide_d2_split": 0}, {"wide_fuse": 3, "wide_wgrad_full": 0}, {"wide_fuse": 2}, {"wide_fuse": 0},
+    {"wide_fuse": 0, "wide_gemm": 1}, {"wide_fuse": 0, "wide_gemm": 0}]
+
+
+@pytest.mark.parametrize("opts", WGRAD_FLAVOURS, ids=lambda o: ",".join(f"{a}={b}" for a, b in o.items()) or "default")
+@pytest.mark.parametrize("D,A", [(8, 4), (16, 8), (3, 2)])
+def test_every_2x256_weight_gradient_kernel_matches_the_oracle_over_three_sample_chunks(crl, opts, D, A):
+    """The option sets that differ in their hidden-layer weight-gradient kernel (wide_wgrad_split_kernel, wide_wgrad_gen_kernel,
+    wide_wgrad_x2_kernel<4, true>, wide_wgrad_x2_kernel<4> behind the fused and behind the layer-wise backward, wide_wgrad_x3_kernel,
+    wide_wgrad_kernel<2>) on a minibatch of M = 4352 = 34 x 128 samples: the workspace then holds S2 = 3 sample chunks of 1472, 1472 and 1408
+    samples, so blocks with blockIdx.x > 0 run — the chunk offset in the index prefetch, in the operand base, in the partial's block offset
+    and the clamp at the end of a shorter last chunk — which no smaller case reaches (one chunk up to M = 2048)."""
+    _flavour_case(crl, opts, D, A, 136, 128)
+
+
 def _flavour_case(crl, opts, D, A, nt, k):
     Hd = 256
     rng = np.random.default_rng(nt + D)

@@ -1,6 +1,7 @@
 """Parity of every route of the layer-wise ("wide") path against the CPU oracle, not only the default one. The shapes the library takes
 (obs 1..64, act 2..16, hidden 64 / 128 / 256) are split between kernels by a handful of predicates in wide.hip — those of the rollout
 and of the update pass each written once, in wide_rollout_route and wide_update_route; each case below is sized to reach one of them.
+(The predicates are in wide.hip; the wide_wgrad_* kernels they select live in wide_wgrad.hpp, the tile-resident ones in wide_fused.hpp / wide_rs.hpp.)
 Same bars as test_gpu_wide.py / test_gpu_parity.py: actions, permutations, env fields bit-equal; float32 results within RTOL = 1e-5
 (rel_err / rel_err_s), losses by loss_close, gradients by _grad_close; whole iterations as test_wide_full_iteration_matches_oracle.
 
