@@ -233,6 +233,11 @@ __global__ void __launch_bounds__(256) wide_pack_x3_kernel(const float* __restri
 // The power of two the 256-wide fp16x2 weight pieces are staged with: largest |w|·scale lands in [2^14, 2^15), so W2 fits the fp16
 // window whatever its magnitude (the fused 64-wide kernels use a fixed 2^8 and fall back to bf16x3 for |w| >= 255; round 2 raised an
 // error here instead). A power of two is exact, and the GEMM epilogues take it back out of the f32 accumulator (DenseX3Args::wsc).
+// "Fits" holds for the LARGEST weight and for a layer whose weights are of one size. The scale is one per network: a weight 2^k below the largest
+// is staged at 2^(14 − k); below 2^-2 (k > 16) the lo piece is subnormal and the pair resolves fp16's 2^-24 ABSOLUTE, i.e. 2^(k − 38) of the
+// weight, and past k = 28 the hi piece is subnormal too — silently, there is no fallback and no flag (unlike the 64-wide kernels). One outlier
+// among weights of 0.06, which sit 2^4 further down (tests/test_gpu_wide_range.py, against Float64): 8.9e-7 relative on the
+// gradient at 2^16, 1.2e-5 at 2^20, 1.9e-4 at 2^24, where wide_gemm = 1 / 0 stay at 4e-7. Networks like that belong on wide_gemm = 1.
 __device__ __forceinline__ void wide_w2scale_body(const float* __restrict__ W2, int n, float* __restrict__ wsc) {
   __shared__ float sm[16];
   float m = 0.0f;
@@ -371,11 +376,18 @@ static int ensure_pack(crl_ppo* h) {
 // (128 B), a wave instruction covers 8 whole lines. S (the stored tanh outputs) is read the same way.
 // tanh of the layer-wise path: the reference's rational tanh_fast, or — where nothing is compared bit for bit (the update pass,
 // the critic) — 1 − 2/(2^(2·log2(e)·x) + 1) on v_exp_f32 / v_rcp_f32 (mlp_x2.hpp: 5 instructions instead of 13, ≈1e-7 absolute)
-__device__ __forceinline__ float wide_tanh(float x, bool fast) { return fast ? tanh_exp2(x, TWO_LOG2E, 1.0f) : tanh_fast(x); }
+// The selector (DenseArgs::fast_act): 0 = tanh_fast, 1 = the exp2 form, 2 = tanh_fast that saturates EXACTLY — ±1 at x² >= 66 as NNlib's does, where
+// the clamp inside tanh_fast (common.hpp) returns 0.9999999. The forward of the update pass under wide_tanh_rational = 1 takes 2: its h feeds
+// 1 − h², and the 1.2e-7 the clamp leaves there is multiplied by the next layer's weights on the way back (4e-5 on dW1 next to a weight of 2^12).
+__device__ __forceinline__ float wide_tanh(float x, int act) {
+  if (act == 1) return tanh_exp2(x, TWO_LOG2E, 1.0f);
+  const float t = tanh_fast(x);
+  return act == 2 && x * x >= 66.0f ? __builtin_copysignf(1.0f, x) : t;
+}
 
 template <int EPI>
 __device__ __forceinline__ void tile_out(float* scr, const f32x16& acc, int lane, int n0, int mbase, int M, const float* bias,
-                                         const float* S, int lds, float* Y, int ldy, bool fast = false) {
+                                         const float* S, int lds, float* Y, int ldy, int fast = 0) {
   const int j = lane & 31, hf = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -417,7 +429,7 @@ struct DenseArgs {
   const float* X; int ldx; int Kt; const int32_t* idx;     // sample m's features at X + ldx·(idx ? idx[m] : m), Kt valid
   const float* bias; const float* S; int lds;              // bias[Nt]; S: stored tanh outputs at the Y positions
   float* Y; int ldy; int Nt; int M;
-  int fast_act = 0;   // EPI_TANH: the exp2-based activation of mlp_x2.hpp instead of tanh_fast (update path and critic only)
+  int fast_act = 0;   // EPI_TANH: the selector of wide_tanh — 1 = the exp2-based activation of mlp_x2.hpp instead of tanh_fast (update path and critic only)
 };
 
 template <int WN, int TN, int WM, int TM, int EPI>
@@ -573,7 +585,7 @@ __device__ __forceinline__ void wide_dense_body(const DenseArgs& a) {
     for (int x = 0; x < TN; ++x)
 #pragma unroll
       for (int y = 0; y < TM; ++y)
-        tile_out<EPI>(scr, acc[x][y], lane, (wn * TN + x) * 32, m0 + (wm * TM + y) * 32, a.M, a.bias, a.S, a.lds, a.Y, a.ldy, a.fast_act != 0);
+        tile_out<EPI>(scr, acc[x][y], lane, (wn * TN + x) * 32, m0 + (wm * TM + y) * 32, a.M, a.bias, a.S, a.lds, a.Y, a.ldy, a.fast_act);
     return;
   }
 #pragma unroll
@@ -591,7 +603,7 @@ __device__ __forceinline__ void wide_dense_body(const DenseArgs& a) {
           if (n + e >= a.Nt) continue;
           float o = acc[x][y][4 * g + e];
           if (EPI == EPI_DTANH) { const float sv = a.S[(size_t)a.lds * m + n + e]; o = o * (1.0f - sv * sv); }
-          else { o += a.bias[n + e]; if (EPI == EPI_TANH) o = wide_tanh(o, a.fast_act != 0); }
+          else { o += a.bias[n + e]; if (EPI == EPI_TANH) o = wide_tanh(o, a.fast_act); }
           a.Y[(size_t)a.ldy * m + n + e] = o;
         }
       }
@@ -644,7 +656,7 @@ __device__ __forceinline__ void split3x4(const f32x4 v, uint2& h, uint2& m, uint
 // cross-half exchange per output instead of a lane reduction; the tile is then stored line-coalesced by tile_out.
 __device__ __forceinline__ void tile_tanh_head(float* scr, f32x16 acc, int lane, int n0, int mloc0, int mbase, int M,
                                                const float* bias, float* Y, const float* W3t, int A, float* hp, int hs, float cs = 1.0f,
-                                               bool fast = false) {
+                                               int fast = 0) {
   const int j = lane & 31, hf = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -756,7 +768,7 @@ __global__ void __launch_bounds__(64 * NW) wide_dense_x3_kernel(DenseX3Args a) {
     wave_lds_fence();
 #pragma unroll
     for (int y = 0; y < TM; ++y)
-      tile_tanh_head(scr, acc[0][y], lane, wave * 32, 32 * y, m0 + 32 * y, a.M, a.bias, a.Y, a.W3t, a.A, hp, hs, 1.0f, a.fast_act != 0);
+      tile_tanh_head(scr, acc[0][y], lane, wave * 32, 32 * y, m0 + 32 * y, a.M, a.bias, a.Y, a.W3t, a.A, hp, hs, 1.0f, a.fast_act);
     __syncthreads();
     for (int i = tid; i < MB * a.A; i += NT) {
       const int m = i / a.A, aa = i - m * a.A;
@@ -771,7 +783,7 @@ __global__ void __launch_bounds__(64 * NW) wide_dense_x3_kernel(DenseX3Args a) {
   for (int x = 0; x < TN; ++x)
 #pragma unroll
     for (int y = 0; y < TM; ++y)
-      tile_out<EPI>(scr, acc[x][y], lane, (TN * wave + x) * 32, m0 + 32 * y, a.M, a.bias, a.S, 256, a.Y, 256, a.fast_act != 0);
+      tile_out<EPI>(scr, acc[x][y], lane, (TN * wave + x) * 32, m0 + 32 * y, a.M, a.bias, a.S, 256, a.Y, 256, a.fast_act);
 }
 
 template <int EPI>
@@ -826,7 +838,7 @@ __device__ __forceinline__ void pow2_scale(float bound, float& s, float& inv) {
 // EPI_TANH: tanh(acc·cs + bias); EPI_DTANH: acc·inv[sample]·cs·(1 − S²)
 template <int EPI>
 __device__ __forceinline__ void tile_out_x2(float* scr, const f32x16& acc, int lane, int n0, int mloc0, int mbase, int M, const float* bias,
-                                            const float* S, float* Y, float cs, const float* inv_lds, bool fast = false) {
+                                            const float* S, float* Y, float cs, const float* inv_lds, int fast = 0) {
   const int j = lane & 31, hf = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -961,7 +973,7 @@ __device__ __forceinline__ void wide_dense_x2_body(const DenseX3Args& a) {
     wave_lds_fence();
 #pragma unroll
     for (int y = 0; y < TM; ++y)
-      tile_tanh_head(scr, acc[y], lane, wave * 32, 32 * y, m0 + 32 * y, a.M, a.bias, a.Y, a.W3t, a.A, hp, hs, a.wsc[1] * (1.0f / X2_ACT_SCALE), a.fast_act != 0);
+      tile_tanh_head(scr, acc[y], lane, wave * 32, 32 * y, m0 + 32 * y, a.M, a.bias, a.Y, a.W3t, a.A, hp, hs, a.wsc[1] * (1.0f / X2_ACT_SCALE), a.fast_act);
     __syncthreads();
     for (int i = tid; i < MB * a.A; i += NT) {
       const int m = i / a.A, aa = i - m * a.A;
@@ -975,7 +987,7 @@ __device__ __forceinline__ void wide_dense_x2_body(const DenseX3Args& a) {
 #pragma unroll
   for (int y = 0; y < TM; ++y)
     tile_out_x2<EPI>(scr, acc[y], lane, wave * 32, 32 * y, m0 + 32 * y, a.M, a.bias, a.S, a.Y,
-                     EPI == EPI_TANH ? a.wsc[1] * (1.0f / X2_ACT_SCALE) : a.wsc[1], sc + MB, a.fast_act != 0);
+                     EPI == EPI_TANH ? a.wsc[1] * (1.0f / X2_ACT_SCALE) : a.wsc[1], sc + MB, a.fast_act);
 }
 
 template <int EPI, int TM>
@@ -1049,7 +1061,7 @@ static DenseX3Args dense_x3_fwd_args(const crl_ppo* h, const WideNet& n, int M, 
 static int wide_forward(crl_ppo* h, int net, const float* X, int ldx, const int32_t* idx, int M, float* out, int ldo, bool fast_act = false) {
   WideWs* w = static_cast<WideWs*>(h->wide_ws);
   const WideNet& n = w->net[net];
-  const int H = w->H, fast = fast_act && !opt(h, OPT_WIDE_TANH_RATIONAL) ? 1 : 0;
+  const int H = w->H, fast = fast_act ? (opt(h, OPT_WIDE_TANH_RATIONAL) ? 2 : 1) : 0;
   DenseArgs a = dense_l1_args(w, n, X, ldx, idx, M, fast);
   if (dense_launch<EPI_TANH>(h->stream, H, a)) return 1;
   if (H == 256 && wide_x3(h)) {

@@ -358,8 +358,19 @@ int32_t crl_comm_destroy(crl_ppo* h);
  *                           recomputed (one Philox call per sample and epoch); 0 = gathers through the finished permutations
  *   comm_force              1 = crl_comm_init with world_size 1 still creates an RCCL communicator (1-GPU test of that path)
  *   peer_timeout_ms         in-kernel time-out of the peer all-reduce (20000)
- *   wide_gemm               layer-wise path, 256-wide layers: 2 = fp16x2 (default), 1 = bf16x3, 0 = f32 MFMA
- *   wide_tanh_rational      1 = the layer-wise path evaluates NNlib's rational tanh_fast everywhere (default 0)
+ *   wide_gemm               layer-wise path, 256-wide layers: 2 = fp16x2 (default), 1 = bf16x3, 0 = f32 MFMA. fp16x2 stages W2 under ONE power of two
+ *                           per network, taken from its largest |w|, and the observations of the h1 that wide_fuse = 3 regenerates in the weight gradient
+ *                           under one per 32-sample slab: magnitude is free, DYNAMIC RANGE is not, and nothing detects it (no fallback, no flag). Within
+ *                           1e-5 of Float64 up to a ratio of 2^16 between the largest W2 weight and the bulk, and between a sample's observations and the
+ *                           largest of its slab; measured past that (tests/test_gpu_wide_range.py): 1.2e-5 / 1.9e-4 on the gradient and 6e-5 / 9e-4 on
+ *                           values next to one weight of 2^20 / 2^24 among weights of 0.06, 3.5e-5 / 8e-3 / 1.2 on dW2 at an observation ratio of
+ *                           2^24 / 2^32 / 2^40. wide_gemm = 1 and 0 have no such limit; set one of them for networks or observations like that
+ *   wide_tanh_rational      1 = the layer-wise path evaluates NNlib's rational tanh_fast everywhere (default 0), saturating to exactly ±1 at x² >= 66 in the
+ *                           forward of the update pass, whose 1 − h² the backward multiplies by the next layer's weights. The default is the exp2 form
+ *                           1 − 2 / (2^(2·log2(e)·x) + 1) outside the actor's rollout forward, under every wide_gemm: ≈ 3e-8 ABSOLUTE near 0, where tanh_fast
+ *                           is accurate relative to |x|. A hidden unit of size 2^-k carries that as 2^(k − 25) of itself: with first-layer activations of
+ *                           2^-8 the weight gradient of the second layer is 5.5e-5 from Float64, 8e-4 at 2^-12, 1.5e-2 at 2^-16 (observations that small
+ *                           with zero biases; tests/test_gpu_wide_range.py), and this option is what meets 1e-5 there
  *   gae_seg, gae_tile       standalone GAE kernel: steps per segment (8 / 16; 4 / 8 / 16 = window depth of the streaming kernel) / kernel shape, 0 = automatic:
  *                           gae_tile = 8 / 16 / 32 / 64 the segmented kernel with that many envs per block; 128 / 256 its two-envs-per-thread form (32 / 64 env
  *                           pairs per block, 8-byte accesses: what 4096 envs or more take by themselves when num_envs is even); 4 / 2 / 1 the streaming kernel

@@ -43,12 +43,13 @@ def _base_params(cfgo, seed=5):
 
 
 def _batch(rng, cfgo, params, ret_scale=10.0):
-    """A synthetic rollout buffer in sample order (index i = env + NT·step, the order of the flat GPU fields). The returns sit below every value
-    prediction: the critic's cotangent has one sign, so that dW3 = Σ h2·dv and db3 = Σ dv are not cancelling sums — with the near-constant h2 of a
-    network of tiny hidden weights their float32 rounding (on any summation order) would otherwise be larger than the bar."""
-    B = NT * K
-    b = dict(obs=rng.standard_normal((4, B)).astype(np.float32), action=rng.integers(0, 2, B).astype(np.int32),
-             logprob=(np.log(0.5) + 0.3 * rng.standard_normal(B)).astype(np.float32), value=rng.standard_normal(B).astype(np.float32),
+    """A synthetic rollout buffer in sample order (index i = env + num_envs·step, the order of the flat GPU fields), for any obs_dim / n_act. The
+    returns sit below every value prediction: the critic's cotangent has one sign, so that dW3 = Σ h2·dv and db3 = Σ dv are not cancelling sums —
+    with the near-constant h2 of a network of tiny hidden weights their float32 rounding (on any summation order) would otherwise be larger than
+    the bar."""
+    B, D, A = cfgo.num_envs * cfgo.num_steps, cfgo.obs_dim, cfgo.n_act
+    b = dict(obs=rng.standard_normal((D, B)).astype(np.float32), action=rng.integers(0, A, B).astype(np.int32),
+             logprob=(np.log(1.0 / A) + 0.3 * rng.standard_normal(B)).astype(np.float32), value=rng.standard_normal(B).astype(np.float32),
              adv=(2 * rng.standard_normal(B)).astype(np.float32), ret=(-5.0 - ret_scale * np.abs(rng.standard_normal(B))).astype(np.float32),
              perm=rng.permutation(B).astype(np.int32))
     return b
@@ -83,26 +84,44 @@ def _l2(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
 
 
-def _check_minibatch(crl, h, cfgo, params, b, mb, tag, apply_update=False):
-    """One update launch on minibatch `mb` against the float64 restatement (always) and the float32 oracle (where it is close to float64)."""
+def _reference(cfgo, params, b, mb):
+    """Both references of minibatch `mb`: (oracle gradient, oracle stats, float64 gradient, float64 losses). They depend on the inputs alone:
+    a test that runs several kernel flavours on one minibatch computes them once and hands them to _check_minibatch."""
+    M = cfgo.num_envs * cfgo.num_steps // cfgo.num_minibatches
+    idx = b["perm"][mb * M:(mb + 1) * M]
+    g_o, so = O.loss_grad(cfgo, params, b["obs"], b["action"], b["logprob"], b["value"], b["adv"], b["ret"], idx)
+    return (g_o, so) + _float64(cfgo, params, b, idx)
+
+
+def _minibatch_errors(cfgo, ref, g):
+    """The figures _check_minibatch asserts on, for one launch's gradient `g`: the float64 and oracle losses, per gradient array the relative L2
+    error against float64 ("e64"), the oracle's own ("o64") and the error against the oracle ("eo")."""
+    g_o, so, g64, l64 = ref
+    off = O.param_offsets(cfgo)
+    sl = [slice(off[i], off[i + 1]) for i in range(12)]
+    return {"l64": l64, "lo": {key: so[key] for key in LOSSES}, "e64": [_l2(g[s], g64[s]) for s in sl],
+            "o64": [_l2(g_o[s], g64[s]) for s in sl], "eo": [_l2(g[s], g_o[s]) for s in sl]}
+
+
+def _check_minibatch(crl, h, cfgo, params, b, mb, tag, apply_update=False, rec=None, ref=None):
+    """One update launch on minibatch `mb` against the float64 restatement (always) and the float32 oracle (where it is close to float64).
+    `rec`, a list, receives the launch's figures (_minibatch_errors) before anything is asserted; `ref` is _reference(cfgo, params, b, mb)
+    where the caller already has it."""
     gs = h.update_minibatch(mb, 0.0, apply_update=apply_update)
     g = h.read(crl._lib.F_GRADS)
     assert np.isfinite(g).all(), f"{tag}: non-finite gradient"
-    idx = b["perm"][mb * M:(mb + 1) * M]
-    g_o, so = O.loss_grad(cfgo, params, b["obs"], b["action"], b["logprob"], b["value"], b["adv"], b["ret"], idx)
-    g64, l64 = _float64(cfgo, params, b, idx)
-    off = O.param_offsets(cfgo)
+    e = _minibatch_errors(cfgo, _reference(cfgo, params, b, mb) if ref is None else ref, g)
+    if rec is not None:
+        rec.append(dict(e, gs={key: gs[key] for key in LOSSES}, tag=tag))
+    l64, so = e["l64"], e["lo"]
     for key in LOSSES:
         assert loss_close(key, gs[key], l64[key], RTOL), (tag, key, gs[key], l64[key])
         if loss_close(key, so[key], l64[key], RTOL / 2):
             assert loss_close(key, gs[key], so[key], RTOL), (tag, key, gs[key], so[key])
     for i in range(12):
-        s = slice(off[i], off[i + 1])
-        e64 = _l2(g[s], g64[s])
-        assert e64 < RTOL, f"{tag}: gradient array {i}: rel L2 error {e64:.3e} against float64"
-        if _l2(g_o[s], g64[s]) < RTOL / 2:
-            eo = _l2(g[s], g_o[s])
-            assert eo < RTOL, f"{tag}: gradient array {i}: rel L2 error {eo:.3e} against the oracle"
+        assert e["e64"][i] < RTOL, f"{tag}: gradient array {i}: rel L2 error {e['e64'][i]:.3e} against float64"
+        if e["o64"][i] < RTOL / 2:
+            assert e["eo"][i] < RTOL, f"{tag}: gradient array {i}: rel L2 error {e['eo'][i]:.3e} against the oracle"
     return gs, g
 
 

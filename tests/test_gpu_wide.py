@@ -247,8 +247,10 @@ def test_wide_fp16x2_weight_scale_follows_the_weights(crl):
     """The 256-wide fp16x2 products stage W2 with a power of two taken from the largest |w| of the network at every optimiser step
     (wide_w2scale_kernel), so a weight of 300 — outside the fixed 2^8 window of rounds 1-2, where it raised an error — and a network
     whose weights are all tiny both run on the fp16x2 path at full accuracy: gradient, rollout actions and values match the oracle,
-    nothing raises. (Bars: 1e-5 as everywhere; 3e-5 on the gradient arrays of the 300-weight case, whose pre-activations are 300 times
-    larger and carry float32 summation-order noise in proportion on both sides.)"""
+    nothing raises. Bars: 1e-5 as everywhere, the 300-weight case included: on a ±300 case of its own test_gpu_wide_range.py measures every
+    flavour — fp16x2, bf16x3, f32 MFMA, exp2 or rational activation — at 3.4e-6 … 3.7e-6 from float64 (the oracle: 1.4e-6), so neither float32
+    summation nor the fp16 window nor the activation asks for more. The range of the shared scale — one weight far above the REST — is that
+    file's subject."""
     D, A, Hd, nt, k = 8, 4, 256, 8, 128
     rng = np.random.default_rng(5)
     cfg = ocfg(nt, k, D, A, Hd)
@@ -272,7 +274,7 @@ def test_wide_fp16x2_weight_scale_follows_the_weights(crl):
         g_o, so = O.loss_grad(cfg, params, st.obs.reshape(D, -1, order="F"), st.action, st.logprob, st.value, st.adv, st.ret, st.perm[2 * M:3 * M])
         for key in ("loss", "pg_loss", "v_loss", "entropy_loss"):
             assert loss_close(key, gs[key], so[key], RTOL), (case, key, gs[key], so[key])
-        _grad_close(h.read(F.F_GRADS), g_o, off, tol=3e-5 if case == "big" else RTOL)
+        _grad_close(h.read(F.F_GRADS), g_o, off, tol=RTOL)
         h.sync()                                     # no error is pending
     params = base.copy(); params[off[8] + 7] = 300.0
     agent.set_params(params)
