@@ -89,6 +89,9 @@ EXPORTS = [
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values",
+    "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
+    "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
+    "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
@@ -117,6 +120,34 @@ class CrlDQNStatus(C.Structure):
     _fields_ = [("env_state", C.c_double * 4), ("global_step", C.c_int64), ("rb_size", C.c_int64), ("n_updates", C.c_int64),
                 ("last_loss", C.c_double)]
 
+
+
+DDPG_ENV_PENDULUM, DDPG_ENV_EXTERNAL = 0, 1
+
+
+class CrlDDPGConfig(C.Structure):
+    """crl_ddpg_config — mirror of DDPGConfig (ddpg.jl:1-15) + shapes, env, action bounds and the noise switch."""
+    _fields_ = [("total_timesteps", C.c_int64), ("buffer_size", C.c_int64), ("min_buff_size", C.c_int64), ("batch_size", C.c_int64),
+                ("warmup_steps", C.c_int64), ("log_frequency", C.c_int64),
+                ("lr", C.c_double), ("tau", C.c_double), ("gamma", C.c_double), ("exploration_noise", C.c_double),
+                ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("env_kind", C.c_int32), ("max_steps", C.c_int32),
+                ("act_low", C.c_double), ("act_high", C.c_double), ("noise_in_update", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CrlDDPGEpisode(C.Structure):
+    _fields_ = [("episode_return", C.c_double), ("episode_length", C.c_int64), ("global_step", C.c_int64)]
+
+
+class CrlDDPGLossRecord(C.Structure):
+    _fields_ = [("global_step", C.c_int64), ("actor_loss", C.c_double), ("critic_loss", C.c_double)]
+
+
+class CrlDDPGStatus(C.Structure):
+    _fields_ = [("theta", C.c_double), ("theta_dot", C.c_double), ("env_t", C.c_int64), ("global_step", C.c_int64), ("rb_size", C.c_int64),
+                ("rb_ptr", C.c_int64), ("n_updates", C.c_int64), ("actor_loss", C.c_double), ("critic_loss", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class CrlA2CConfig(C.Structure):
@@ -218,6 +249,21 @@ def load():
     L.crl_dqn_status_read.argtypes = [vp, C.POINTER(CrlDQNStatus)]
     L.crl_dqn_run.argtypes = [vp, C.c_int64, C.POINTER(CrlDQNEpisode), C.c_int32, ip, C.POINTER(CrlDQNLossRecord), C.c_int32, ip, i64p]
     L.crl_dqn_q_values.argtypes = [vp, dp, C.c_int32, dp]
+    L.crl_ddpg_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
+    L.crl_ddpg_create.argtypes = [C.POINTER(CrlDDPGConfig), C.c_int32, C.POINTER(vp)]
+    L.crl_ddpg_destroy.argtypes = [vp]
+    L.crl_ddpg_write_params.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t]
+    L.crl_ddpg_read_params.argtypes = [vp, fp, fp, fp, fp]
+    L.crl_ddpg_make_nn.argtypes = [C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t, fp, C.c_size_t]
+    L.crl_ddpg_init_params.argtypes = [vp, C.c_uint64]
+    L.crl_ddpg_status_read.argtypes = [vp, C.POINTER(CrlDDPGStatus)]
+    L.crl_ddpg_run.argtypes = [vp, C.c_int64, C.POINTER(CrlDDPGEpisode), C.c_int32, ip, C.POINTER(CrlDDPGLossRecord), C.c_int32, ip, i64p]
+    L.crl_ddpg_act.argtypes = [vp, dp, dp]
+    L.crl_ddpg_observe.argtypes = [vp, dp, dp, C.c_double, dp, C.c_int32]
+    L.crl_ddpg_read_losses.argtypes = [vp, C.POINTER(CrlDDPGLossRecord), C.c_int32, ip]
+    L.crl_ddpg_read_buffer.argtypes = [vp, dp, dp, dp, dp, u8p, C.c_int64, i64p, i64p]
+    L.crl_ddpg_actor.argtypes = [vp, dp, C.c_int32, dp]
+    L.crl_ddpg_q_values.argtypes = [vp, dp, dp, C.c_int32, dp]
     L.crl_make_actor_critic.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t]
     L.crl_ppo_init_params.argtypes = [vp, C.c_uint64]
     L.crl_a2c_init_params.argtypes = [vp, C.c_uint64]
@@ -824,3 +870,117 @@ class DQNHandle:
         q = np.zeros((2, n), np.float64, order="F")
         check(self._L.crl_dqn_q_values(self._h, _ptr(obs, C.c_double), n, _ptr(q, C.c_double)))
         return q
+
+
+def ddpg_param_count(obs_dim, act_dim):
+    """crl_ddpg_param_count: (len of Flux.params(actor), len of Flux.params(critic)) flattened."""
+    na, nc = C.c_int64(), C.c_int64()
+    check(load().crl_ddpg_param_count(int(obs_dim), int(act_dim), C.byref(na), C.byref(nc)))
+    return na.value, nc.value
+
+
+def ddpg_make_nn_host(obs_dim, act_dim, seed=0):
+    """crl_ddpg_make_nn: make_ddpg_nn of ddpg.jl:19-37 (glorot-uniform weights, zero biases) as two flat vectors in Flux.params order."""
+    na, nc = ddpg_param_count(obs_dim, act_dim)
+    a = np.zeros(na, np.float32); c = np.zeros(nc, np.float32)
+    check(load().crl_ddpg_make_nn(int(obs_dim), int(act_dim), seed, _ptr(a, C.c_float), a.size, _ptr(c, C.c_float), c.size))
+    return a, c
+
+
+class DDPGHandle:
+    """Owns one crl_ddpg* (include/cleanrl_hip.h, DDPG block)."""
+
+    def __init__(self, cfg: CrlDDPGConfig, device=0):
+        self._L = load()
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        check(self._L.crl_ddpg_create(C.byref(cfg), device, C.byref(self._h)))
+        self.obs_dim, self.act_dim = cfg.obs_dim, cfg.act_dim
+        self.actor_n, self.critic_n = ddpg_param_count(cfg.obs_dim, cfg.act_dim)
+
+    def close(self):
+        if self._h:
+            self._L.crl_ddpg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def write_params(self, actor, critic):
+        a = np.ascontiguousarray(actor, np.float32); c = np.ascontiguousarray(critic, np.float32)
+        check(self._L.crl_ddpg_write_params(self._h, _ptr(a, C.c_float), a.size, _ptr(c, C.c_float), c.size))
+
+    def init_params(self, seed=0):
+        check(self._L.crl_ddpg_init_params(self._h, seed))
+
+    def read_params(self):
+        """(actor, critic, target_actor, target_critic)"""
+        out = [np.zeros(n, np.float32) for n in (self.actor_n, self.critic_n, self.actor_n, self.critic_n)]
+        check(self._L.crl_ddpg_read_params(self._h, *[_ptr(o, C.c_float) for o in out]))
+        return tuple(out)
+
+    def status(self):
+        st = CrlDDPGStatus()
+        check(self._L.crl_ddpg_status_read(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def run(self, max_env_steps, max_eps=8192, max_losses=4096):
+        """crl_ddpg_run: (steps taken, [(episode_return, episode_length, global_step)], [(global_step, actor_loss, critic_loss)])"""
+        eps = (CrlDDPGEpisode * max_eps)(); ls = (CrlDDPGLossRecord * max_losses)(); ne = C.c_int32(); nl = C.c_int32(); taken = C.c_int64()
+        check(self._L.crl_ddpg_run(self._h, max_env_steps, eps, max_eps, C.byref(ne), ls, max_losses, C.byref(nl), C.byref(taken)))
+        return (taken.value, [(eps[i].episode_return, eps[i].episode_length, eps[i].global_step) for i in range(ne.value)],
+                [(ls[i].global_step, ls[i].actor_loss, ls[i].critic_loss) for i in range(nl.value)])
+
+    def act(self, obs):
+        o = np.ascontiguousarray(obs, np.float64)
+        if o.shape != (self.obs_dim,):
+            raise ValueError(f"act: {self.obs_dim} observation components expected, got shape {o.shape}")
+        a = np.zeros(self.act_dim, np.float64)
+        check(self._L.crl_ddpg_act(self._h, _ptr(o, C.c_double), _ptr(a, C.c_double)))
+        return a
+
+    def observe(self, obs, action, reward, next_obs, terminal):
+        o = np.ascontiguousarray(obs, np.float64); a = np.ascontiguousarray(action, np.float64); n = np.ascontiguousarray(next_obs, np.float64)
+        if o.shape != (self.obs_dim,) or n.shape != (self.obs_dim,) or a.shape != (self.act_dim,):
+            raise ValueError("observe: obs / next_obs of obs_dim and action of act_dim components expected")
+        check(self._L.crl_ddpg_observe(self._h, _ptr(o, C.c_double), _ptr(a, C.c_double), float(reward), _ptr(n, C.c_double), int(bool(terminal))))
+
+    def read_losses(self, max_losses=4096):
+        ls = (CrlDDPGLossRecord * max_losses)(); nl = C.c_int32()
+        check(self._L.crl_ddpg_read_losses(self._h, ls, max_losses, C.byref(nl)))
+        return [(ls[i].global_step, ls[i].actor_loss, ls[i].critic_loss) for i in range(nl.value)]
+
+    def buffer(self):
+        """The whole ring: dict(state (obs_dim, cap), action (act_dim, cap), reward, next_state, terminal, ptr, size)."""
+        cap = self.cfg.buffer_size
+        st = np.zeros((self.obs_dim, cap), np.float64, order="F"); nx = np.zeros((self.obs_dim, cap), np.float64, order="F")
+        ac = np.zeros((self.act_dim, cap), np.float64, order="F"); r = np.zeros(cap, np.float64); t = np.zeros(cap, np.uint8)
+        ptr, size = C.c_int64(), C.c_int64()
+        check(self._L.crl_ddpg_read_buffer(self._h, _ptr(st, C.c_double), _ptr(ac, C.c_double), _ptr(r, C.c_double), _ptr(nx, C.c_double),
+                                           _ptr(t, C.c_uint8), cap, C.byref(ptr), C.byref(size)))
+        return dict(state=st, action=ac, reward=r, next_state=nx, terminal=t, ptr=ptr.value, size=size.value)
+
+    def actor(self, obs):
+        """crl_ddpg_actor: the noise-free 2·tanh_fast(·) output, (obs_dim, n) → (act_dim, n)."""
+        obs = np.asfortranarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        n = obs.shape[1]
+        out = np.zeros((self.act_dim, n), np.float64, order="F")
+        check(self._L.crl_ddpg_actor(self._h, _ptr(obs, C.c_double), n, _ptr(out, C.c_double)))
+        return out
+
+    def q_values(self, obs, act):
+        """crl_ddpg_q_values: get_q(critic, obs, act) (ddpg.jl:45), (obs_dim, n), (act_dim, n) → (n,)."""
+        obs = np.asfortranarray(obs, np.float64); act = np.asfortranarray(act, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        if act.ndim == 1:
+            act = act.reshape(self.act_dim, -1, order="F")
+        n = obs.shape[1]
+        out = np.zeros(n, np.float64)
+        check(self._L.crl_ddpg_q_values(self._h, _ptr(obs, C.c_double), _ptr(act, C.c_double), n, _ptr(out, C.c_double)))
+        return out

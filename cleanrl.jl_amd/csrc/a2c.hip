@@ -21,6 +21,7 @@
 #include "env64.hpp"
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
+#include "tanh64.hpp"
 
 struct crl_a2c;
 
@@ -45,24 +46,8 @@ struct A2CDev {
 };
 
 // ------------------------------------------------------------------------------------------------------
-// Float64 pieces (oracle: a2c_tanh_fast; the env — a2c_sin, a2c_cos, a2c_cartpole_step — is env64.hpp)
+// Float64 pieces (tanh_fast64 — oracle: a2c_tanh_fast — is tanh64.hpp; the env — a2c_sin, a2c_cos, a2c_cartpole_step — is env64.hpp)
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double tanh_fast64(double x) {
-#pragma clang fp contract(off)
-  const double exp2x = exp(x + x);
-  const double y = (exp2x - 1.0) / (exp2x + 1.0);
-  const double x2 = x * x;
-  double p = -0.008697141630499953;
-  p = p * x2 + 0.02186660872609521;
-  p = p * x2 + -0.05396823125794372;
-  p = p * x2 + 0.13333333325511604;
-  p = p * x2 + -0.33333333333324583;
-  p = p * x2 + 1.0;
-  const double ypoly = x * p;
-  if (x2 > 900.0) return (double)((x > 0.0) - (x < 0.0));
-  return x2 < 0.017 ? ypoly : y;
-}
-
 // Row `lane` of the first two layers of one network, in registers
 struct NetRow { float w1[AD]; float b1; float w2[AH]; float b2; };
 __device__ __forceinline__ void load_row(const float* __restrict__ P, int lane, NetRow& r) {

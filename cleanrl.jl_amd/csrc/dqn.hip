@@ -18,6 +18,7 @@
 #include "env64.hpp"
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
+#include "replay_sample.hpp"
 
 struct crl_dqn;
 
@@ -145,35 +146,10 @@ __global__ void __launch_bounds__(128) dqn_collect_kernel(DQNDev a) {
   if (tid == 0) *a.ctl = c;
 }
 
-// Buffer.sample(rb, batch_size) (dqn.jl:94): self-avoiding draws, candidates in counter order (oracle: dqn_sample_indices)
+// Buffer.sample(rb, batch_size) (dqn.jl:94): replay_sample.hpp's self-avoiding draws (oracle: dqn_sample_indices)
 __global__ void __launch_bounds__(1024) dqn_sample_kernel(DQNDev a) {
   if (!a.ctl->train_pending) return;
-  __shared__ uint32_t bitmap[DQN_MAX_CAP / 32];
-  __shared__ int cand[1024];
-  __shared__ int got, cbase;
-  const int tid = threadIdx.x, nth = blockDim.x;
-  const int k = (int)a.cfg.batch_size, n = (int)a.ctl->size;
-  const uint64_t gstep = (uint64_t)a.ctl->global_step;
-  for (int w = tid; w < (n + 31) / 32; w += nth) bitmap[w] = 0u;
-  if (tid == 0) { got = 0; cbase = 0; }
-  __syncthreads();
-  while (got < k) {
-    {
-      const uint32_t cc = (uint32_t)(cbase + tid);
-      const u32x4 o = philox(cc, (uint32_t)gstep, (uint32_t)(gstep >> 32), 0xD9u, (uint32_t)a.cfg.seed, (uint32_t)(a.cfg.seed >> 32));
-      cand[tid] = (int)(((uint64_t)o.x * (uint64_t)n) >> 32);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int g = got;
-      for (int i = 0; i < nth && g < k; ++i) {
-        const int j = cand[i];
-        if (!((bitmap[j >> 5] >> (j & 31)) & 1u)) { bitmap[j >> 5] |= 1u << (j & 31); a.idx[g++] = j; }
-      }
-      got = g; cbase += nth;
-    }
-    __syncthreads();
-  }
+  replay_sample<DQN_MAX_CAP>(a.cfg.seed, (uint64_t)a.ctl->global_step, (int)a.ctl->size, (int)a.cfg.batch_size, a.idx);
 }
 
 // forward of target_net(next_state) (net 1) and q_net(state) (net 0), one output element per thread (dqn.jl:99,104)

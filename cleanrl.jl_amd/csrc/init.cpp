@@ -104,4 +104,25 @@ int32_t crl_dqn_make_nn(uint64_t seed, float* out, size_t n) {
   return 0;
 }
 
+int32_t crl_ddpg_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t actor_n, float* critic, size_t critic_n) {
+  int64_t na = 0, nc = 0;
+  if (crl_ddpg_param_count(obs_dim, act_dim, &na, &nc)) return 1;
+  if (!actor || !critic || actor_n != (size_t)na || critic_n != (size_t)nc) {
+    set_error("crl_ddpg_make_nn: expected " + std::to_string(na) + " actor and " + std::to_string(nc) + " critic floats"); return 1;
+  }
+  crl::Rng rng{seed ^ 0xDD96ull};
+  for (size_t i = 0; i < actor_n; ++i) actor[i] = 0.0f;
+  for (size_t i = 0; i < critic_n; ++i) critic[i] = 0.0f;
+  const int D = obs_dim, A = act_dim;
+  float* p = actor;
+  crl::glorot_uniform(rng, 64, D, p); p += 64 * D + 64;        // ddpg.jl:24 Dense(ob_size, 64, tanh_fast)
+  crl::glorot_uniform(rng, 64, 64, p); p += 64 * 64 + 64;      //         25 Dense(64, 64, tanh_fast)
+  crl::glorot_uniform(rng, A, 64, p);                          //         26 Dense(64, ac_size, tanh_fast)
+  p = critic;
+  crl::glorot_uniform(rng, 64, D + A, p); p += 64 * (D + A) + 64;   // :31 Dense(ob_size + ac_size, 64, relu)
+  crl::glorot_uniform(rng, 64, 64, p); p += 64 * 64 + 64;           // :32 Dense(64, 64, relu)
+  crl::glorot_uniform(rng, 1, 64, p);                               // :33 Dense(64, 1)
+  return 0;
+}
+
 }  // extern "C"

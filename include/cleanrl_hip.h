@@ -539,6 +539,77 @@ int32_t crl_dqn_run(crl_dqn* h, int64_t max_env_steps, crl_dqn_episode* eps, int
 /* q_net(obs) for n observations (4, n) Float64 → (2, n) Float64 (dqn.jl:64) */
 int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q);
 
+/* =====================================================================================================
+ * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
+ * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·
+ * exploration_noise (one draw per CALL, broadcast over the batch, ddpg.jl:28), critic Dense(obs+act,64,relu) → Dense(64,64,relu) → Dense(64,1) on
+ * vcat(obs, act). obs_dim 1..64 and act_dim 1..16 are runtime values. Each network is one flat float vector in Flux.params order, (out,in)
+ * column-major. The loop of ddpg.jl:76-135 runs as a fixed six-launch cycle per env step (sample, critic pass, critic step, actor pass, actor
+ * step, collect); a call enqueues the cycles of its chunk and reads nothing back until it ends. The env is either the built-in Float64 Pendulum
+ * (g = 10, m = l = 1, dt = 0.05, torque ±2, obs (cos θ, sin θ, θ̇), reward −(θ² + 0.1·θ̇² + 0.001·u²), done = terminal = t >= max_steps) or lives
+ * in the host process (ddpg.jl:50 is a MuJoCo env there): crl_ddpg_act / crl_ddpg_observe.
+ * ===================================================================================================== */
+#define CRL_DDPG_ENV_PENDULUM 0
+#define CRL_DDPG_ENV_EXTERNAL 1
+typedef struct crl_ddpg_config {   /* DDPGConfig, ddpg.jl:1-15 */
+  int64_t total_timesteps, buffer_size, min_buff_size, batch_size, warmup_steps, log_frequency;
+  double lr, tau, gamma, exploration_noise;
+  int32_t obs_dim, act_dim;       /* Pendulum: 3, 1 */
+  int32_t env_kind;               /* CRL_DDPG_ENV_* */
+  int32_t max_steps;              /* Pendulum episode length: 200 */
+  double act_low, act_high;       /* rand(act_space) of the warm-up (ddpg.jl:79): low + (high − low)·u per component */
+  int32_t noise_in_update;        /* 1 (the reference): target_actor(next_state) (ddpg.jl:108) and actor(state) in the actor loss (:123) each add a
+                                     fresh randn(act)·exploration_noise; 0: those two draws are zero (textbook DDPG). The behaviour draw (:79) stays. */
+  int32_t pad;
+  uint64_t seed;
+} crl_ddpg_config;
+typedef struct crl_ddpg_episode { double episode_return; int64_t episode_length, global_step; } crl_ddpg_episode;   /* ddpg.jl:97 */
+typedef struct crl_ddpg_loss_record { int64_t global_step; double actor_loss, critic_loss; } crl_ddpg_loss_record;  /* ddpg.jl:132 */
+typedef struct crl_ddpg_status {
+  double theta, theta_dot;        /* Pendulum state (zeros on an external handle) */
+  int64_t env_t, global_step, rb_size, rb_ptr, n_updates;   /* rb_ptr: 0-based slot of the next add (replay_buffer.jl:32) */
+  double actor_loss, critic_loss; /* of the last update */
+} crl_ddpg_status;
+typedef struct crl_ddpg crl_ddpg;
+
+/* lengths of Flux.params(actor) = W1(64,obs) b1 W2(64,64) b2 W3(act,64) b3 and Flux.params(critic) = W1(64,obs+act) b1 W2(64,64) b2 W3(1,64) b3 */
+int32_t crl_ddpg_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n);
+/* ddpg.jl:47-74. Rejected with a message that names the field: batch_size outside 1..1024, buffer_size outside batch_size..131072,
+ * max(min_buff_size, warmup_steps) + 1 < batch_size (Buffer.sample asserts n <= size), obs_dim / act_dim out of range (Pendulum: 3 / 1),
+ * act_low >= act_high, tau outside (0, 1]. */
+int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** out);
+int32_t crl_ddpg_destroy(crl_ddpg* h);
+/* actor, critic; the targets are a deepcopy (ddpg.jl:53-54) */
+int32_t crl_ddpg_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic, size_t critic_n);
+/* actor, critic, target_actor, target_critic (any may be NULL) */
+int32_t crl_ddpg_read_params(crl_ddpg* h, float* actor, float* critic, float* target_actor, float* target_critic);
+/* make_ddpg_nn (ddpg.jl:19-37): Flux's default glorot_uniform weights and zero biases; stateless and host-only */
+int32_t crl_ddpg_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t actor_n, float* critic, size_t critic_n);
+/* ddpg.jl:52-54 for a handle. Every call below that computes with the networks returns "parameters not set" on a handle whose parameters were
+ * neither written nor initialised (a fresh handle holds zeros). */
+int32_t crl_ddpg_init_params(crl_ddpg* h, uint64_t seed);
+int32_t crl_ddpg_status_read(crl_ddpg* h, crl_ddpg_status* out);
+/* ddpg.jl:76-135 on the Pendulum: up to max_env_steps iterations (or to total_timesteps). Episode records (ddpg.jl:97) and the losses of the
+ * steps that are multiples of log_frequency (ddpg.jl:131-133) come back in eps / losses (entries beyond max_* are dropped). An error on an
+ * external handle. */
+int32_t crl_ddpg_run(crl_ddpg* h, int64_t max_env_steps, crl_ddpg_episode* eps, int32_t max_eps, int32_t* n_eps,
+                     crl_ddpg_loss_record* losses, int32_t max_losses, int32_t* n_losses, int64_t* steps_taken);
+/* Host-driven env (errors on a Pendulum handle). crl_ddpg_act: the action of step global_step + 1 for `obs` (ddpg.jl:79: rand(act_space) during
+ * the warm-up, else actor(obs) with its noise), unclipped; advances nothing. crl_ddpg_observe: ddpg.jl:76-134 without the env — global_step += 1,
+ * Buffer.add!(state, action, reward, next_state, terminal), and the update when it is due (the same kernels as crl_ddpg_run). Host pointers. */
+int32_t crl_ddpg_act(crl_ddpg* h, const double* obs, double* action_out);
+int32_t crl_ddpg_observe(crl_ddpg* h, const double* obs, const double* action, double reward, const double* next_obs, int32_t terminal);
+/* the loss records (ddpg.jl:131-133) written since the last crl_ddpg_run / crl_ddpg_read_losses, oldest first; reading clears them */
+int32_t crl_ddpg_read_losses(crl_ddpg* h, crl_ddpg_loss_record* losses, int32_t max_losses, int32_t* n_losses);
+/* the ring: state (obs_dim, cap), action (act_dim, cap), reward (cap), next_state (obs_dim, cap), terminal (cap), cap = buffer_size slots;
+ * ptr (0-based) and size as replay_buffer.jl:32-34 leave them */
+int32_t crl_ddpg_read_buffer(crl_ddpg* h, double* state, double* action, double* reward, double* next_state, uint8_t* terminal, int64_t cap,
+                             int64_t* ptr, int64_t* size);
+/* the noise-free actor output 2·tanh_fast(·) for n observations (obs_dim, n) → (act_dim, n) */
+int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out);
+/* get_q(critic, obs, act) (ddpg.jl:45) for n pairs → n values */
+int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif

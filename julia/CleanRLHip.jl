@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -517,6 +517,141 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
     end
     for l in @view losses[1:n_losses[]]
       @info "Training Statistics" loss = l.loss global_step = l.global_step
+    end
+  end
+  agent
+end
+
+# ------------------------------------------------------------------------------------------------------
+# ddpg.jl — same names: DDPGConfig keeps the reference's fields (ddpg.jl:1-15); the loop body runs on the GPU, the env is the library's
+# Pendulum (`ddpg`) or any Julia env the caller steps (`ddpg_external`: the reference's own is GymEnv("HalfCheetah-v3"), ddpg.jl:50)
+# ------------------------------------------------------------------------------------------------------
+struct CrlDDPGConfig      # include/cleanrl_hip.h crl_ddpg_config
+  total_timesteps::Int64; buffer_size::Int64; min_buff_size::Int64; batch_size::Int64; warmup_steps::Int64; log_frequency::Int64
+  lr::Float64; tau::Float64; gamma::Float64; exploration_noise::Float64
+  obs_dim::Int32; act_dim::Int32; env_kind::Int32; max_steps::Int32
+  act_low::Float64; act_high::Float64
+  noise_in_update::Int32; pad::Int32
+  seed::UInt64
+end
+struct CrlDDPGEpisode; episode_return::Float64; episode_length::Int64; global_step::Int64; end                  # ddpg.jl:97
+struct CrlDDPGLossRecord; global_step::Int64; actor_loss::Float64; critic_loss::Float64; end                    # ddpg.jl:132
+struct CrlDDPGStatus
+  theta::Float64; theta_dot::Float64
+  env_t::Int64; global_step::Int64; rb_size::Int64; rb_ptr::Int64; n_updates::Int64
+  actor_loss::Float64; critic_loss::Float64
+end
+const DDPG_ENV_PENDULUM = Int32(0)
+const DDPG_ENV_EXTERNAL = Int32(1)
+
+mutable struct DDPGAgent
+  h::Ptr{Cvoid}
+  obs_dim::Int
+  act_dim::Int
+end
+
+# The package's own builder: make_ddpg_nn(env, exploration_noise) (ddpg.jl:19-37) flattened in Flux.params order — the noise closure at the end
+# of the actor Chain has no parameters. It needs the caller's env (ddpg.jl:20-21 read its spaces), so it is handed over as
+#   init = () -> reference_ddpg_params(CleanRL.make_ddpg_nn, CleanRL.Flux, env, config.exploration_noise)
+# and the default is the library's restatement of the same glorot layers (crl_ddpg_init_params).
+function reference_ddpg_params(make_ddpg_nn, Flux, env, exploration_noise::Float64)
+  actor, critic = make_ddpg_nn(env, exploration_noise)
+  (Vector{Float32}(vcat(vec.(Flux.params(actor))...)), Vector{Float32}(vcat(vec.(Flux.params(critic))...)))
+end
+_default_ddpg_init() = nothing
+
+# ddpg.jl:52-54: `params` = (vcat(vec.(Flux.params(actor))...), vcat(vec.(Flux.params(critic))...)) wins, else `init()` (e.g. the package's
+# make_ddpg_nn flattened), else the library's initialiser (crl_ddpg_init_params). Never the handle's zeros.
+function _ddpg_start!(config, obs_dim, act_dim, env_kind, act_low, act_high, max_steps, noise_in_update, device, seed, params, init, init_seed)
+  cfg = CrlDDPGConfig(config.total_timesteps, config.buffer_size, config.min_buff_size, config.batch_size, config.warmup_steps,
+                      config.log_frequencey, config.lr, config.tau, config.gamma, config.exploration_noise, obs_dim, act_dim, env_kind,
+                      max_steps, act_low, act_high, noise_in_update ? 1 : 0, 0, seed)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:crl_ddpg_create, libcrl), Int32, (Ref{CrlDDPGConfig}, Int32, Ref{Ptr{Cvoid}}), cfg, device, h))
+  agent = DDPGAgent(h[], obs_dim, act_dim)
+  finalizer(x -> ccall((:crl_ddpg_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
+  params === nothing && init !== nothing && (params = init())             # ddpg.jl:52 make_ddpg_nn(env, exploration_noise)
+  if params === nothing
+    check(ccall((:crl_ddpg_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))
+  else
+    actor, critic = params
+    GC.@preserve actor critic check(ccall((:crl_ddpg_write_params, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t),
+                                          agent.h, actor, length(actor), critic, length(critic)))
+  end
+  agent
+end
+
+# the noise-free actor output 2·tanh_fast(·) for observations (obs_dim, n) → (act_dim, n)
+function actor_mean(agent::DDPGAgent, obs::AbstractMatrix{Float64})
+  o = Array(obs); n = size(o, 2); out = Matrix{Float64}(undef, agent.act_dim, n)
+  GC.@preserve o out check(ccall((:crl_ddpg_actor, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, n, out))
+  out
+end
+# get_q(critic, obs, act) (ddpg.jl:45)
+function get_q(agent::DDPGAgent, obs::AbstractMatrix{Float64}, act::AbstractMatrix{Float64})
+  o = Array(obs); a = Array(act); n = size(o, 2); q = Vector{Float64}(undef, n)
+  GC.@preserve o a q check(ccall((:crl_ddpg_q_values, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, a, n, q))
+  q
+end
+
+# ddpg.jl:47 on the library's Pendulum (obs 3, act 1, torque ±2, 200-step episodes)
+function ddpg(config; device=0, seed=UInt64(0x5EED), params=nothing, init=_default_ddpg_init(), init_seed::Integer=0, chunk::Integer=4096,
+              noise_in_update::Bool=true, make_logger=_default_make_logger())
+  make_logger === nothing || make_logger("ddpg|$(config.run_name)")        # ddpg.jl:48
+  agent = _ddpg_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, noise_in_update, device, seed, params, init, init_seed)
+  eps = Vector{CrlDDPGEpisode}(undef, 8192); losses = Vector{CrlDDPGLossRecord}(undef, 4096)
+  n_eps = Ref{Int32}(0); n_losses = Ref{Int32}(0); taken = Ref{Int64}(0)
+  start_time = time(); global_step = 0
+  while global_step < config.total_timesteps
+    GC.@preserve eps losses check(ccall((:crl_ddpg_run, libcrl), Int32,
+      (Ptr{Cvoid}, Int64, Ptr{CrlDDPGEpisode}, Int32, Ref{Int32}, Ptr{CrlDDPGLossRecord}, Int32, Ref{Int32}, Ref{Int64}),
+      agent.h, chunk, eps, length(eps), n_eps, losses, length(losses), n_losses, taken))
+    taken[] == 0 && break
+    global_step += taken[]
+    for e in @view eps[1:n_eps[]]
+      steps_per_sec = trunc(e.global_step / (time() - start_time))
+      @info "Episode Statistics" episode_return = e.episode_return episode_length = e.episode_length steps_per_sec global_step = e.global_step
+    end
+    for l in @view losses[1:n_losses[]]
+      @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
+    end
+  end
+  agent
+end
+
+# ddpg.jl:47 with the env in the caller's process. `env` is driven through three closures-or-methods the caller supplies:
+#   reset_env!(env) -> obs::Vector{Float64},  step_env!(env, action::Vector{Float64}) -> (reward, next_obs::Vector{Float64}, terminal::Bool)
+# (for a ReinforcementLearning.jl env: env -> (reset!(env); state(env)) and (env, a) -> (env(a); (reward(env), state(env), is_terminated(env)))).
+function ddpg_external(config, env; obs_dim::Integer, act_dim::Integer, act_low::Real, act_high::Real, reset_env!, step_env!, device=0,
+                       seed=UInt64(0x5EED), params=nothing, init=_default_ddpg_init(), init_seed::Integer=0, noise_in_update::Bool=true,
+                       make_logger=_default_make_logger())
+  make_logger === nothing || make_logger("ddpg|$(config.run_name)")        # ddpg.jl:48
+  agent = _ddpg_start!(config, obs_dim, act_dim, DDPG_ENV_EXTERNAL, Float64(act_low), Float64(act_high), 200, noise_in_update, device, seed, params,
+                       init, init_seed)
+  action = Vector{Float64}(undef, act_dim); losses = Vector{CrlDDPGLossRecord}(undef, 4096); n_losses = Ref{Int32}(0)
+  episode_return = 0.0; episode_length = 0
+  start_time = time()
+  obs = Vector{Float64}(reset_env!(env))                                   # ddpg.jl:74
+  for global_step in 1:config.total_timesteps
+    GC.@preserve obs action check(ccall((:crl_ddpg_act, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), agent.h, obs, action))   # :79
+    reward, next_obs, terminal = step_env!(env, copy(action))              # :80
+    next_obs = Vector{Float64}(next_obs)
+    GC.@preserve obs action next_obs check(ccall((:crl_ddpg_observe, libcrl), Int32,
+      (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Int32), agent.h, obs, action, Float64(reward), next_obs, terminal ? 1 : 0))   # :83-90, 105-129
+    episode_return += reward; episode_length += 1                          # :93-94
+    obs = next_obs
+    if terminal                                                            # :95-101
+      steps_per_sec = trunc(global_step / (time() - start_time))
+      @info "Episode Statistics" episode_return episode_length steps_per_sec global_step
+      episode_length, episode_return = 0, 0.0
+      obs = Vector{Float64}(reset_env!(env))
+    end
+    if global_step % config.log_frequencey == 0                            # :131-133
+      GC.@preserve losses check(ccall((:crl_ddpg_read_losses, libcrl), Int32, (Ptr{Cvoid}, Ptr{CrlDDPGLossRecord}, Int32, Ref{Int32}),
+                                      agent.h, losses, length(losses), n_losses))
+      for l in @view losses[1:n_losses[]]
+        @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
+      end
     end
   end
   agent

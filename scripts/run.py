@@ -8,6 +8,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
+    python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
 """
 import os
 import sys
@@ -19,7 +20,7 @@ from cleanrl_jl_amd import config_parser  # noqa: E402
 
 
 def main():
-    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg"):
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
     if algo == "ppo":
@@ -35,6 +36,8 @@ def main():
         crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False).close()
+    elif algo == "ddpg":
+        crl.ddpg(config_parser.argparse_struct(crl.DDPGConfig(), argv), "pendulum", to_terminal=True, to_tensorboard=False).close()
     else:
         crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False).close()
 
