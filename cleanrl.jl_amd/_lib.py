@@ -91,7 +91,7 @@ EXPORTS = [
     "crl_dqn_q_values",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
-    "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values",
+    "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
@@ -145,6 +145,20 @@ class CrlDDPGLossRecord(C.Structure):
 class CrlDDPGStatus(C.Structure):
     _fields_ = [("theta", C.c_double), ("theta_dot", C.c_double), ("env_t", C.c_int64), ("global_step", C.c_int64), ("rb_size", C.c_int64),
                 ("rb_ptr", C.c_int64), ("n_updates", C.c_int64), ("actor_loss", C.c_double), ("critic_loss", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class CrlDDPGEvalConfig(C.Structure):
+    """crl_ddpg_eval_config: what crl_ddpg_evaluate runs."""
+    _fields_ = [("num_envs", C.c_int32), ("episodes_per_env", C.c_int32), ("trace_steps", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CrlDDPGEvalReport(C.Structure):
+    """crl_ddpg_eval_report: Float64 summary of the per-episode arrays (population standard deviation; q_bias_mean = mean(q0 - disc_return))."""
+    _fields_ = [("episodes", C.c_int64), ("env_steps", C.c_int64)] + [(n, C.c_double) for n in (
+        "return_mean", "return_std", "return_min", "return_max", "disc_return_mean", "q0_mean", "q_bias_mean")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -264,6 +278,7 @@ def load():
     L.crl_ddpg_read_buffer.argtypes = [vp, dp, dp, dp, dp, u8p, C.c_int64, i64p, i64p]
     L.crl_ddpg_actor.argtypes = [vp, dp, C.c_int32, dp]
     L.crl_ddpg_q_values.argtypes = [vp, dp, dp, C.c_int32, dp]
+    L.crl_ddpg_evaluate.argtypes = [vp, C.POINTER(CrlDDPGEvalConfig), C.POINTER(CrlDDPGEvalReport), dp, dp, dp, dp]
     L.crl_make_actor_critic.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t]
     L.crl_ppo_init_params.argtypes = [vp, C.c_uint64]
     L.crl_a2c_init_params.argtypes = [vp, C.c_uint64]
@@ -983,4 +998,20 @@ class DDPGHandle:
         n = obs.shape[1]
         out = np.zeros(n, np.float64)
         check(self._L.crl_ddpg_q_values(self._h, _ptr(obs, C.c_double), _ptr(act, C.c_double), n, _ptr(out, C.c_double)))
+        return out
+
+    def evaluate(self, num_envs, episodes_per_env=1, seed=0, trace_steps=0):
+        """crl_ddpg_evaluate: the current actor, frozen and without noise, on `num_envs` fresh private Pendulums x `episodes_per_env` episodes (one
+        launch). Returns {"report": {...}, "returns", "disc_returns", "q0": (episodes_per_env, num_envs) float64[, "trace_action": (trace_steps,
+        num_envs) float64]}."""
+        cfg = CrlDDPGEvalConfig(int(num_envs), int(episodes_per_env), int(trace_steps), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        rep = CrlDDPGEvalReport()
+        shape = (max(cfg.episodes_per_env, 0), max(cfg.num_envs, 0))
+        ret, disc, q0 = (np.zeros(shape, np.float64) for _ in range(3))
+        trace = np.zeros((cfg.trace_steps, shape[1]), np.float64) if cfg.trace_steps > 0 else None
+        check(self._L.crl_ddpg_evaluate(self._h, C.byref(cfg), C.byref(rep), _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(q0, C.c_double),
+                                        None if trace is None else _ptr(trace, C.c_double)))
+        out = {"report": rep.as_dict(), "returns": ret, "disc_returns": disc, "q0": q0}
+        if trace is not None:
+            out["trace_action"] = trace
         return out

@@ -18,10 +18,12 @@
 // dot products in input order with the bias last, sums over the batch in sample order ⇒ two runs from one seed are bit-identical.
 //
 // Philox streams (counter = philox_env(seed, component, global_step, stream)): 0x10 behaviour noise (:79), 0x11 warm-up rand(act_space) (:79),
-// 0x12 target-actor noise (:108), 0x13 actor-loss noise (:123), 0x14 Pendulum reset in the loop (:100), 0x15 the first reset (:74), 0xD9 the
-// minibatch draw. A normal is Box–Muller in Float64 from the two u53 halves of ONE Philox block: sqrt(−2·log(1 − u_xy))·cos(2π·u_zw).
+// 0x12 target-actor noise (:108), 0x13 actor-loss noise (:123), 0x14 Pendulum reset in the loop (:100), 0x15 the first reset (:74), 0x16 the
+// resets of crl_ddpg_evaluate's private envs (no reference counterpart), 0xD9 the minibatch draw. A normal is Box–Muller in Float64 from the two
+// u53 halves of ONE Philox block: sqrt(−2·log(1 − u_xy))·cos(2π·u_zw).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -41,7 +43,7 @@ namespace crl {
 constexpr int GH = 64;                          // hidden width, ddpg.jl:24-25,31-32
 constexpr int DDPG_MAX_OBS = 64, DDPG_MAX_ACT = 16, DDPG_MAX_IN = DDPG_MAX_OBS + DDPG_MAX_ACT;
 constexpr int DDPG_MAX_EPS = 8192, DDPG_MAX_LOSSES = 4096, DDPG_MAX_BATCH = 1024, DDPG_MAX_CAP = 1 << 17;   // ring: reference default 1e5
-constexpr uint32_t S_BEHAVE = 0x10u, S_WARMUP = 0x11u, S_TARGET = 0x12u, S_ACTOR = 0x13u, S_RESET = 0x14u, S_RESET0 = 0x15u;
+constexpr uint32_t S_BEHAVE = 0x10u, S_WARMUP = 0x11u, S_TARGET = 0x12u, S_ACTOR = 0x13u, S_RESET = 0x14u, S_RESET0 = 0x15u, S_EVAL = 0x16u;
 
 // Dense(n_in, 64, ·) → Dense(64, 64, ·) → Dense(64, n_out, ·), flat in Flux.params order, (out,in) column-major
 struct NetOff { int W1, b1, W2, b2, W3, b3, N; };
@@ -166,20 +168,27 @@ __device__ __forceinline__ void actor_forward(const float* __restrict__ P, int D
   if (lane < A) ys[lane] = tanh_fast64(head_row(P + o.W3, P + o.b3, A, h2s, lane));
   __syncthreads();
 }
+// what stands between two layers of a forward: the block's barrier where the wave is the whole block; where several waves share a block and each
+// owns its x / h1s / h2s / qs, a wave-private fence (a wave's LDS instructions execute in issue order), so that no wave waits for another
+template <bool BLOCK>
+__device__ __forceinline__ void layer_sync() {
+  if constexpr (BLOCK) __syncthreads(); else wave_lds_fence();
+}
 // critic(vcat(obs, act)) (ddpg.jl:31-33,45): x holds the D + A inputs; the value lands in *qs (LDS) for every lane
+template <bool BLOCK = true>
 __device__ __forceinline__ double critic_forward(const float* __restrict__ P, int n_in, const double* x, double* h1s, double* h2s, double* qs,
                                                  int lane, double& h1, double& h2) {
   const NetOff o = net_off(n_in, 1);
   double z = dense_row(P + o.W1, P + o.b1, n_in, x, lane);
   h1 = z > 0.0 ? z : 0.0;
   h1s[lane] = h1;
-  __syncthreads();
+  layer_sync<BLOCK>();
   z = dense_row(P + o.W2, P + o.b2, GH, h1s, lane);
   h2 = z > 0.0 ? z : 0.0;
   h2s[lane] = h2;
-  __syncthreads();
+  layer_sync<BLOCK>();
   if (lane == 0) *qs = head_row(P + o.W3, P + o.b3, 1, h2s, 0);
-  __syncthreads();
+  layer_sync<BLOCK>();
   return *qs;
 }
 
@@ -518,6 +527,83 @@ __global__ void __launch_bounds__(64) ddpg_q_eval_kernel(DDPGDev a, const double
   if (lane == 0) out[b] = q;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// crl_ddpg_evaluate: the frozen actor on n private Pendulums, `episodes` episodes each, in ONE launch. One wave owns one env from its first reset to
+// its last step, lane = hidden unit, EVAL_WAVES envs per block. The actor stays on the chip for the whole launch: the lane's rows of W1 and W2 and
+// its two biases are registers, W3 / b3 (which every lane reads in input order) are staged once per block into LDS, so the step loop reads no global
+// memory. Env state, sums and the action are computed by every lane alike (wave-uniform: no broadcast). The arithmetic is dense_row's and head_row's
+// — products in input order, bias last, contraction off —, so an action has the bits crl_ddpg_actor gives for the same observation; the critic runs
+// once per episode through critic_forward itself. After the staging barrier a wave never meets a block barrier again (a wave past n leaves there):
+// layers are separated by wave_lds_fence on wave-private h1s / h2s. Pendulum handles only (obs 3, act 1 — crl_ddpg_create pins that shape).
+// ------------------------------------------------------------------------------------------------------
+#ifndef CRL_EVAL_WAVES
+#define CRL_EVAL_WAVES 4      // envs per block; experiment builds (csrc/Makefile, EXTRA=-DCRL_EVAL_WAVES=n) measured 1, 2, 4, 8: DESIGN.md §3e
+#endif
+constexpr int EVAL_WAVES = CRL_EVAL_WAVES, PEND_OBS = 3;
+struct DDPGEvalArgs {
+  int32_t n, episodes, trace_steps; uint64_t seed;
+  double *ret, *disc_ret, *q0, *trace;      // [episodes][n] each, [trace_steps][n]
+};
+__global__ void __launch_bounds__(64 * EVAL_WAVES) ddpg_eval_kernel(DDPGDev a, DDPGEvalArgs ev) {
+#pragma clang fp contract(off)
+  __shared__ float w3s[GH], b3s;
+  __shared__ double xs[EVAL_WAVES][PEND_OBS + 1], h1s[EVAL_WAVES][GH], h2s[EVAL_WAVES][GH], qs[EVAL_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * EVAL_WAVES + w, max_steps = a.cfg.max_steps;
+  const NetOff o = net_off(PEND_OBS, 1);
+  if (threadIdx.x < GH) w3s[threadIdx.x] = a.actor[o.W3 + threadIdx.x];
+  if (threadIdx.x == 0) b3s = a.actor[o.b3];
+  __syncthreads();
+  if (env >= ev.n) return;
+  float w1[PEND_OBS], w2[GH];
+#pragma unroll
+  for (int k = 0; k < PEND_OBS; ++k) w1[k] = a.actor[o.W1 + lane + GH * k];
+#pragma unroll
+  for (int k = 0; k < GH; ++k) w2[k] = a.actor[o.W2 + lane + GH * k];
+  const double b1 = (double)a.actor[o.b1 + lane], b2 = (double)a.actor[o.b2 + lane], gamma = a.cfg.gamma;
+  double* const h1w = h1s[w];
+  double* const h2w = h2s[w];
+  for (int j = 0; j < ev.episodes; ++j) {
+    double s[2], ret = 0.0, disc_ret = 0.0, disc = 1.0;
+    int t = 0;
+    pendulum_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_EVAL);
+    for (int step = 0; step < max_steps; ++step) {
+      const double x[PEND_OBS] = {pend_cos(s[0]), pend_sin(s[0]), s[1]};
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < PEND_OBS; ++k) acc += (double)w1[k] * x[k];
+      acc += b1;
+      h1w[lane] = tanh_fast64(acc);
+      wave_lds_fence();
+      acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < GH; ++k) acc += (double)w2[k] * h1w[k];
+      acc += b2;
+      h2w[lane] = tanh_fast64(acc);
+      wave_lds_fence();
+      acc = 0.0;
+#pragma unroll 8
+      for (int k = 0; k < GH; ++k) acc += (double)w3s[k] * h2w[k];
+      const double act = tanh_fast64(acc + (double)b3s) * 2.0;
+      if (step == 0) {                                                                 // Q(s0, μ(s0)): what crl_ddpg_q_values gives for (x, act)
+        if (lane == 0) { xs[w][0] = x[0]; xs[w][1] = x[1]; xs[w][2] = x[2]; xs[w][3] = act; }
+        wave_lds_fence();
+        double c1, c2;
+        const double q = critic_forward<false>(a.critic, PEND_OBS + 1, xs[w], h1w, h2w, &qs[w], lane, c1, c2);
+        if (lane == 0) ev.q0[(size_t)j * ev.n + env] = q;
+      }
+      const int64_t row = (int64_t)j * max_steps + step;
+      if (lane == 0 && row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = act;
+      double rew;
+      const bool done = pendulum_step64(s, t, act, max_steps, rew);
+      ret += rew;
+      disc_ret += disc * rew;
+      disc = disc * gamma;
+      if (done) break;
+    }
+    if (lane == 0) { ev.ret[(size_t)j * ev.n + env] = ret; ev.disc_ret[(size_t)j * ev.n + env] = disc_ret; }
+  }
+}
+
 }  // namespace crl
 
 struct crl_ddpg {
@@ -839,6 +925,56 @@ int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(out, sq, N * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Held-out evaluation: argument checks, scratch, ONE launch (ddpg_eval_kernel), the per-episode arrays back to the host, the report in Float64
+int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg_eval_report* report, double* returns, double* disc_returns,
+                          double* q0, double* trace_action) {
+#pragma clang fp contract(off)
+  DDPG_GUARD(h);
+  if (!cfg || !report) { set_error("crl_ddpg_evaluate: null cfg or report"); return 1; }
+  if (h->cfg.env_kind != CRL_DDPG_ENV_PENDULUM) {
+    set_error("crl_ddpg_evaluate: the env of this handle lives in the host process — step it there and take the noise-free actions from crl_ddpg_actor");
+    return 1;
+  }
+  if (!h->params_set) { set_error("crl_ddpg_evaluate: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  const int64_t n = cfg->num_envs, E = cfg->episodes_per_env, T = cfg->trace_steps, steps = E * (int64_t)h->cfg.max_steps;
+  if (n < 1 || n > 65536) { set_error("crl_ddpg_evaluate: num_envs must be in 1..65536, got " + std::to_string(n)); return 1; }
+  if (E < 1 || E > 1024) { set_error("crl_ddpg_evaluate: episodes_per_env must be in 1..1024, got " + std::to_string(E)); return 1; }
+  if (n * E > (1 << 20)) { set_error("crl_ddpg_evaluate: num_envs * episodes_per_env must be <= 1048576, got " + std::to_string(n * E)); return 1; }
+  if (T < 0 || T > steps) {
+    set_error("crl_ddpg_evaluate: trace_steps must be in 0..episodes_per_env * max_steps = " + std::to_string(steps) + ", got " + std::to_string(T)); return 1;
+  }
+  if ((T > 0) != (trace_action != nullptr)) { set_error("crl_ddpg_evaluate: trace_action must be given exactly when trace_steps > 0"); return 1; }
+  if (T * n > (1 << 24)) { set_error("crl_ddpg_evaluate: trace_steps * num_envs must be <= 16777216, got " + std::to_string(T * n)); return 1; }
+  const size_t ne = (size_t)(n * E), nt = (size_t)(T * n);
+  if (ddpg_scratch(h, (3 * ne + nt) * 8)) return 1;
+  DDPGEvalArgs ev;
+  ev.n = (int32_t)n; ev.episodes = (int32_t)E; ev.trace_steps = (int32_t)T; ev.seed = cfg->seed;
+  ev.ret = static_cast<double*>(h->scratch); ev.disc_ret = ev.ret + ne; ev.q0 = ev.disc_ret + ne; ev.trace = ev.q0 + ne;
+  // every slot of the four arrays is written: each env runs episodes_per_env episodes of exactly max_steps steps
+  hipLaunchKernelGGL(ddpg_eval_kernel, dim3((unsigned)((n + EVAL_WAVES - 1) / EVAL_WAVES)), dim3(64 * EVAL_WAVES), 0, h->stream, h->d, ev);
+  CRL_HIP_CHECK(hipGetLastError());
+  std::vector<double> host(3 * ne);
+  CRL_HIP_CHECK(hipMemcpyAsync(host.data(), ev.ret, 3 * ne * 8, hipMemcpyDeviceToHost, h->stream));
+  if (T > 0) CRL_HIP_CHECK(hipMemcpyAsync(trace_action, ev.trace, nt * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  const double *ret = host.data(), *disc = ret + ne, *q = disc + ne;
+  double rsum = 0.0, dsum = 0.0, qsum = 0.0, bsum = 0.0, rmin = ret[0], rmax = ret[0];
+  for (size_t i = 0; i < ne; ++i) {
+    rsum += ret[i]; dsum += disc[i]; qsum += q[i]; bsum += q[i] - disc[i];
+    rmin = ret[i] < rmin ? ret[i] : rmin; rmax = ret[i] > rmax ? ret[i] : rmax;
+  }
+  const double mean = rsum / (double)ne;
+  double var = 0.0;
+  for (size_t i = 0; i < ne; ++i) { const double d = ret[i] - mean; var += d * d; }
+  report->episodes = (int64_t)ne; report->env_steps = (int64_t)ne * h->cfg.max_steps;
+  report->return_mean = mean; report->return_std = std::sqrt(var / (double)ne); report->return_min = rmin; report->return_max = rmax;
+  report->disc_return_mean = dsum / (double)ne; report->q0_mean = qsum / (double)ne; report->q_bias_mean = bsum / (double)ne;
+  if (returns) memcpy(returns, ret, ne * 8);
+  if (disc_returns) memcpy(disc_returns, disc, ne * 8);
+  if (q0) memcpy(q0, q, ne * 8);
   return 0;
 }
 

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib as L
 from . import logger as Logger
+from .ppo import EVAL_SEED    # the key of the evaluation envs is its own: a held-out score does not replay the training env's initial states
 
 
 @dataclasses.dataclass
@@ -76,26 +77,123 @@ def _emit(lg, records):
         lg.info(msg, extra={"crl": kv})
 
 
-def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, params=None, chunk=4096, noise_in_update=True, **logger_kw):
+def eval_report(returns, disc_returns, q0, env_steps):
+    """The fields of crl_ddpg_eval_report from per-episode arrays, the library's formulas: Float64, sums in array order, population standard
+    deviation, q_bias_mean = Σ(q0 − disc_return) / episodes."""
+    ret, disc, q = (np.asarray(x, np.float64).reshape(-1) for x in (returns, disc_returns, q0))
+    n = np.float64(ret.size)
+    rsum = dsum = qsum = bsum = var = np.float64(0.0)
+    for r, d, v in zip(ret, disc, q):
+        rsum = rsum + r; dsum = dsum + d; qsum = qsum + v; bsum = bsum + (v - d)
+    mean = rsum / n
+    for r in ret:
+        var = var + (r - mean) * (r - mean)
+    return dict(episodes=int(ret.size), env_steps=int(env_steps), return_mean=float(mean), return_std=float(np.sqrt(var / n)),
+                return_min=float(ret.min()), return_max=float(ret.max()), disc_return_mean=float(dsum / n), q0_mean=float(qsum / n),
+                q_bias_mean=float(bsum / n))
+
+
+def _check_eval_args(who, num_envs, episodes_per_env, seed, trace_steps, max_steps):
+    for name, v, lo, hi in (("num_envs", num_envs, 1, 65536), ("episodes_per_env", episodes_per_env, 1, 1024), ("trace_steps", trace_steps, 0, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{who}: {name} must be an integer, got {type(v).__name__}")
+        if v < lo or (hi is not None and v > hi):
+            raise ValueError(f"{who}: {name} must be in {lo}..{hi}, got {v}" if hi else f"{who}: {name} must be >= {lo}, got {v}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: seed must be an integer in [0, 2^64), got {seed!r}")
+    if num_envs * episodes_per_env > 1 << 20:
+        raise ValueError(f"{who}: num_envs * episodes_per_env must be <= 1048576, got {num_envs * episodes_per_env}")
+    if trace_steps > episodes_per_env * max_steps:
+        raise ValueError(f"{who}: trace_steps must be <= episodes_per_env * max_steps = {episodes_per_env * max_steps}, got {trace_steps}")
+    if trace_steps * num_envs > 1 << 24:
+        raise ValueError(f"{who}: trace_steps * num_envs must be <= 16777216, got {trace_steps * num_envs}")
+
+
+def _evaluate_on_host_env(agent, env, episodes):
+    """ddpg_evaluate's host route: the env is an object in this process, the actions are crl_ddpg_actor's, the sums the library's (Float64, step order)."""
+    h, gamma = agent.handle, np.float64(agent.config.gamma)
+    ret, disc_ret, q0, steps = np.zeros((episodes, 1)), np.zeros((episodes, 1)), np.zeros((episodes, 1)), 0
+    for j in range(episodes):
+        obs = np.asarray(env.reset(), np.float64)
+        r_sum, d_sum, disc, first, terminal = np.float64(0.0), np.float64(0.0), np.float64(1.0), True, False
+        while not terminal:
+            action = h.actor(obs)[:, 0]
+            if first:
+                q0[j, 0] = h.q_values(obs, action)[0]; first = False
+            reward, obs, terminal = env.step(action)
+            obs = np.asarray(obs, np.float64); reward = np.float64(reward)
+            r_sum = r_sum + reward; d_sum = d_sum + disc * reward; disc = disc * gamma; steps += 1
+        ret[j, 0] = r_sum; disc_ret[j, 0] = d_sum
+    return {"report": eval_report(ret, disc_ret, q0, steps), "returns": ret, "disc_returns": disc_ret, "q0": q0}
+
+
+def ddpg_evaluate(agent, *, num_envs=256, episodes_per_env=1, seed=EVAL_SEED, trace_steps=0, env=None):
+    """How good is the current actor, and does the critic over-estimate? crl_ddpg_evaluate: the agent's actor, frozen and WITHOUT the exploration
+    noise, plays `episodes_per_env` whole episodes on each of `num_envs` fresh Pendulums in one launch on the GPU (no reference counterpart: ddpg.jl
+    only logs the returns of its noisy behaviour policy). Training state is not touched. Returns {"report": {episodes, env_steps, return_mean,
+    return_std, return_min, return_max, disc_return_mean, q0_mean, q_bias_mean}, "returns", "disc_returns", "q0"} — the arrays are
+    (episodes_per_env, num_envs) float64; q0 = Q(s0, actor(s0)) and q_bias_mean = mean(q0 − discounted return): positive = the critic promises more
+    than the policy collects — plus "trace_action" (trace_steps, num_envs), the actions of each env's first trace_steps steps, when trace_steps > 0.
+    `env=<host env object>` (the protocol of ddpg(config, env)) serves an agent whose env lives in this process: a host loop over the handle's
+    noise-free actor, episode after episode until `terminal`, through the same report; num_envs is then 1 (leave it alone), and seed / trace_steps
+    belong to the on-device envs and are refused. Arguments are validated here, before the library is touched."""
+    if not isinstance(agent, DDPGAgent):
+        raise TypeError("ddpg_evaluate: agent must be a cleanrl_jl_amd DDPGAgent (PPO agents: evaluate)")
+    if env is not None:
+        if isinstance(env, str):
+            raise ValueError("ddpg_evaluate: env must be a host env object (the built-in Pendulum needs none)")
+        if num_envs not in (1, 256) or isinstance(num_envs, bool):
+            raise ValueError(f"ddpg_evaluate: a host env is one env — num_envs must be left alone (or 1), got {num_envs!r}")
+        if seed != EVAL_SEED or trace_steps != 0:
+            raise ValueError("ddpg_evaluate: seed and trace_steps belong to the on-device envs; a host env is seeded and traced by its owner")
+        _check_eval_args("ddpg_evaluate", 1, episodes_per_env, EVAL_SEED, 0, 1)
+        return _evaluate_on_host_env(agent, env, int(episodes_per_env))
+    _check_eval_args("ddpg_evaluate", num_envs, episodes_per_env, seed, trace_steps, int(agent.crl_cfg.max_steps))
+    return agent.handle.evaluate(num_envs, episodes_per_env, seed, trace_steps)   # an external handle: the library's message points to crl_ddpg_actor
+
+
+def _eval_record(global_step, report):
+    return (global_step, "Evaluation Statistics", dict(eval_return_mean=report["return_mean"], eval_return_std=report["return_std"],
+                                                       eval_q_bias=report["q_bias_mean"], global_step=global_step))
+
+
+def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, params=None, chunk=4096, noise_in_update=True, eval_every=0,
+         eval_envs=256, eval_episodes=1, eval_env=None, **logger_kw):
     """ddpg.jl:47-136. env="pendulum": the library's Pendulum, one library call per `chunk` env steps. Otherwise `env` is a host object with
     obs_dim, act_dim, act_low, act_high, reset() -> obs and step(action) -> (reward, next_obs, terminal): the library picks the action and learns,
     this loop steps the env and keeps the episode statistics of ddpg.jl:92-101. The "CleanRL" logger receives "Episode Statistics"
-    (episode_return, episode_length, steps_per_sec, global_step; ddpg.jl:97) and "Training Statistics" (actor_loss, critic_loss; :132)."""
+    (episode_return, episode_length, steps_per_sec, global_step; ddpg.jl:97) and "Training Statistics" (actor_loss, critic_loss; :132).
+    `eval_every=N > 0` adds an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_q_bias, global_step) after the records of
+    every step that is a multiple of N: ddpg_evaluate of the parameters that step left, on eval_envs fresh Pendulums x eval_episodes episodes (the
+    library calls are cut at multiples of N; chunking changes no bit of the run) or, with a host env, eval_episodes episodes on `eval_env`, a SECOND
+    env object — the training env is in the middle of an episode. 0 (default) keeps the record stream what it was."""
+    if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
+        raise ValueError(f"ddpg: eval_every must be an integer >= 0, got {eval_every!r}")
+    host_env = not isinstance(env, str)
+    if eval_every:
+        if host_env and (eval_env is None or isinstance(eval_env, str) or eval_env is env):
+            raise ValueError("ddpg: eval_every with a host env needs eval_env, a second env object (evaluating on the training env would break its episode)")
+        _check_eval_args("ddpg", 1 if host_env else eval_envs, eval_episodes, EVAL_SEED, 0, 1)
     config = config or DDPGConfig()
     Logger.make_logger(f"ddpg|{config.run_name}", **({"to_terminal": False} | logger_kw))        # ddpg.jl:48
     lg = logging.getLogger("CleanRL")
     start = time.time()
-    if isinstance(env, str):
+    if not host_env:
         if env != "pendulum":
             raise ValueError(f"ddpg: the only built-in env is 'pendulum', got {env!r}")
         agent = DDPGAgent(config, device=device, seed=seed, params=params, noise_in_update=noise_in_update)
+        global_step = 0
         while True:
-            taken, episodes, losses = agent.handle.run(chunk)
+            budget = min(chunk, eval_every - global_step % eval_every) if eval_every else chunk
+            taken, episodes, losses = agent.handle.run(budget)
             records = [(g, "Episode Statistics", dict(episode_return=r, episode_length=n, steps_per_sec=int(g / max(time.time() - start, 1e-9)),
                                                       global_step=g)) for r, n, g in episodes]
             records += [(g, "Training Statistics", dict(actor_loss=a, critic_loss=c)) for g, a, c in losses]
             _emit(lg, records)
-            if taken == 0 or agent.handle.status()["global_step"] >= config.total_timesteps:
+            global_step = agent.handle.status()["global_step"]
+            if eval_every and taken > 0 and global_step % eval_every == 0:
+                _emit(lg, [_eval_record(global_step, agent.handle.evaluate(eval_envs, eval_episodes, EVAL_SEED, 0)["report"])])
+            if taken == 0 or global_step >= config.total_timesteps:
                 break
         return agent
     agent = DDPGAgent(config, obs_dim=env.obs_dim, act_dim=env.act_dim, act_low=env.act_low, act_high=env.act_high, external=True, device=device,
@@ -118,4 +216,6 @@ def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, pa
             obs = np.asarray(env.reset(), np.float64)
         if global_step % config.log_frequencey == 0:                                             # :131-133
             _emit(lg, [(g, "Training Statistics", dict(actor_loss=a, critic_loss=c)) for g, a, c in h.read_losses()])
+        if eval_every and global_step % eval_every == 0:
+            _emit(lg, [_eval_record(global_step, _evaluate_on_host_env(agent, eval_env, int(eval_episodes))["report"])])
     return agent

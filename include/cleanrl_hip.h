@@ -609,6 +609,32 @@ int32_t crl_ddpg_read_buffer(crl_ddpg* h, double* state, double* action, double*
 int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out);
 /* get_q(critic, obs, act) (ddpg.jl:45) for n pairs → n values */
 int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out);
+/* Held-out evaluation of the current actor, and of the critic's bias — no reference counterpart: ddpg.jl puts the exploration noise inside the actor
+ * (:28), so its "Episode Statistics" score the noisy behaviour policy on the one training env. Here the handle's actor (not the target), frozen and
+ * WITHOUT noise, plays cfg->episodes_per_env whole episodes on each of cfg->num_envs fresh, private Pendulums in ONE launch (csrc/ddpg.hip,
+ * ddpg_eval_kernel). The trajectory is defined by public calls. With n = num_envs, E = episodes_per_env and the handle's max_steps and gamma, env e
+ * (0 <= e < n), episode j (0 <= j < E): (θ, θ̇) = the Pendulum reset draw — components 0 and 1 of the Philox draw at (key = cfg->seed, gstep = j·n + e,
+ * stream 0x16, "evaluation reset", beside the loop's 0x10–0x15): θ = −π + 2π·u0, θ̇ = −1 + 2·u1 —, t = 0. Per step: obs = (cos θ, sin θ, θ̇) as the
+ * training loop forms it; a = exactly what crl_ddpg_actor returns for obs (2·tanh_fast(head), bit for bit); the Pendulum step with a (clipped to ±2
+ * inside the step, as in training) gives the reward r; ret += r; disc_ret += disc·r, then disc = disc·gamma, from ret = disc_ret = 0.0 and disc = 1.0
+ * — Float64, in step order, a plain multiply then an add, no contraction. On the first step of the episode q0 = exactly what crl_ddpg_q_values returns
+ * for (obs, a), with the handle's current critic. The episode ends when the step reports terminal (t >= max_steps): every episode has max_steps steps.
+ * returns / disc_returns / q0: (E, n), env fastest (index j·n + e); each may be NULL. trace_action: (trace_steps, n), row s = the action of the s-th
+ * step of each env counted across its episodes (s = j·max_steps + t); NULL exactly when trace_steps = 0, and trace_steps <= E·max_steps (it exists so
+ * that tests can follow the device's trajectory). The report is computed on the host in Float64 from the per-episode arrays, sums in array order:
+ * episodes = n·E, env_steps = n·E·max_steps, return_std the population standard deviation, q0_mean = Σq0 / episodes and
+ * q_bias_mean = Σ(q0 − disc_return) / episodes: positive = the critic promises more than the policy then collects. Reads the actor, the critic and the
+ * handle's config and nothing else — targets, Adam state and β powers, the ring, env state, counters and episode sums, the loss records and the
+ * external staging slot stay bit for bit as they were — and synchronises before it returns. The launch is bounded by E·max_steps steps per env; no
+ * flags, no atomics, no cross-block synchronisation. Errors, each naming the field: NULL cfg / report; a handle whose env is external (step that env
+ * on the host and take the actions from crl_ddpg_actor); parameters never set; num_envs outside 1..65536; episodes_per_env outside 1..1024;
+ * num_envs * episodes_per_env > 1048576; trace_steps < 0 or > E·max_steps; trace_steps > 0 without a trace_action, or a trace_action with
+ * trace_steps = 0; trace_steps * num_envs > 16777216. Device scratch is allocated on first use, kept on the handle and freed by crl_ddpg_destroy. */
+typedef struct crl_ddpg_eval_config { int32_t num_envs, episodes_per_env, trace_steps, pad; uint64_t seed; } crl_ddpg_eval_config;   /* 24 bytes */
+typedef struct crl_ddpg_eval_report { int64_t episodes, env_steps;
+  double return_mean, return_std, return_min, return_max, disc_return_mean, q0_mean, q_bias_mean; } crl_ddpg_eval_report;           /* 72 bytes */
+int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg_eval_report* report,
+                          double* returns, double* disc_returns, double* q0, double* trace_action);
 
 #ifdef __cplusplus
 }

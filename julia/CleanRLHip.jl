@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -541,6 +541,13 @@ struct CrlDDPGStatus
   env_t::Int64; global_step::Int64; rb_size::Int64; rb_ptr::Int64; n_updates::Int64
   actor_loss::Float64; critic_loss::Float64
 end
+struct CrlDDPGEvalConfig  # crl_ddpg_eval_config: what crl_ddpg_evaluate runs
+  num_envs::Int32; episodes_per_env::Int32; trace_steps::Int32; pad::Int32; seed::UInt64
+end
+struct CrlDDPGEvalReport  # crl_ddpg_eval_report: Float64 summary of the per-episode arrays (population standard deviation; q_bias_mean = mean(q0 - disc_return))
+  episodes::Int64; env_steps::Int64
+  return_mean::Float64; return_std::Float64; return_min::Float64; return_max::Float64; disc_return_mean::Float64; q0_mean::Float64; q_bias_mean::Float64
+end
 const DDPG_ENV_PENDULUM = Int32(0)
 const DDPG_ENV_EXTERNAL = Int32(1)
 
@@ -594,18 +601,41 @@ function get_q(agent::DDPGAgent, obs::AbstractMatrix{Float64}, act::AbstractMatr
   q
 end
 
-# ddpg.jl:47 on the library's Pendulum (obs 3, act 1, torque ±2, 200-step episodes)
+# How good is the current actor, and does the critic over-estimate? crl_ddpg_evaluate: the agent's actor, frozen and WITHOUT the exploration noise
+# (ddpg.jl:28 puts it inside the actor, so the reference's "Episode Statistics" score the noisy behaviour policy), plays episodes_per_env whole
+# episodes on each of num_envs fresh on-device Pendulums in one launch; training state is not touched. returns / disc_returns / q0 are
+# (num_envs, episodes_per_env) — the C arrays are env-fastest —, q0 = Q(s0, actor(s0)), report.q_bias_mean = mean(q0 - discounted return);
+# trace_action (num_envs, trace_steps) holds the actions of each env's first trace_steps steps. An agent of ddpg_external has its env in the
+# caller's process: the library refuses it here — step that env and take the actions from actor_mean.
+function ddpg_evaluate(agent::DDPGAgent; num_envs::Integer=256, episodes_per_env::Integer=1, seed::Integer=EVAL_SEED, trace_steps::Integer=0)
+  1 <= num_envs <= 65536 || throw(ArgumentError("ddpg_evaluate: num_envs must be in 1..65536, got $num_envs"))
+  1 <= episodes_per_env <= 1024 || throw(ArgumentError("ddpg_evaluate: episodes_per_env must be in 1..1024, got $episodes_per_env"))
+  trace_steps >= 0 || throw(ArgumentError("ddpg_evaluate: trace_steps must be >= 0, got $trace_steps"))
+  cfg = Ref(CrlDDPGEvalConfig(num_envs, episodes_per_env, trace_steps, 0, UInt64(seed)))
+  report = Ref{CrlDDPGEvalReport}()
+  returns = Matrix{Float64}(undef, num_envs, episodes_per_env); disc_returns = similar(returns); q0 = similar(returns)
+  trace_action = Matrix{Float64}(undef, num_envs, trace_steps)
+  GC.@preserve returns disc_returns q0 trace_action check(ccall((:crl_ddpg_evaluate, libcrl), Int32,
+    (Ptr{Cvoid}, Ref{CrlDDPGEvalConfig}, Ref{CrlDDPGEvalReport}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+    agent.h, cfg, report, returns, disc_returns, q0, trace_steps > 0 ? pointer(trace_action) : Ptr{Float64}(C_NULL)))
+  return (; report = report[], returns, disc_returns, q0, trace_action)
+end
+
+# ddpg.jl:47 on the library's Pendulum (obs 3, act 1, torque ±2, 200-step episodes). eval_every = N > 0: an "Evaluation Statistics" record
+# (eval_return_mean, eval_return_std, eval_q_bias, global_step) after the records of every step that is a multiple of N — the calls are cut there
 function ddpg(config; device=0, seed=UInt64(0x5EED), params=nothing, init=_default_ddpg_init(), init_seed::Integer=0, chunk::Integer=4096,
-              noise_in_update::Bool=true, make_logger=_default_make_logger())
+              noise_in_update::Bool=true, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+  eval_every >= 0 || throw(ArgumentError("ddpg: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("ddpg|$(config.run_name)")        # ddpg.jl:48
   agent = _ddpg_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, noise_in_update, device, seed, params, init, init_seed)
   eps = Vector{CrlDDPGEpisode}(undef, 8192); losses = Vector{CrlDDPGLossRecord}(undef, 4096)
   n_eps = Ref{Int32}(0); n_losses = Ref{Int32}(0); taken = Ref{Int64}(0)
   start_time = time(); global_step = 0
   while global_step < config.total_timesteps
+    budget = eval_every > 0 ? min(chunk, eval_every - global_step % eval_every) : chunk
     GC.@preserve eps losses check(ccall((:crl_ddpg_run, libcrl), Int32,
       (Ptr{Cvoid}, Int64, Ptr{CrlDDPGEpisode}, Int32, Ref{Int32}, Ptr{CrlDDPGLossRecord}, Int32, Ref{Int32}, Ref{Int64}),
-      agent.h, chunk, eps, length(eps), n_eps, losses, length(losses), n_losses, taken))
+      agent.h, budget, eps, length(eps), n_eps, losses, length(losses), n_losses, taken))
     taken[] == 0 && break
     global_step += taken[]
     for e in @view eps[1:n_eps[]]
@@ -614,6 +644,10 @@ function ddpg(config; device=0, seed=UInt64(0x5EED), params=nothing, init=_defau
     end
     for l in @view losses[1:n_losses[]]
       @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
+    end
+    if eval_every > 0 && global_step % eval_every == 0
+      ev = ddpg_evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report
+      @info "Evaluation Statistics" eval_return_mean = ev.return_mean eval_return_std = ev.return_std eval_q_bias = ev.q_bias_mean global_step
     end
   end
   agent

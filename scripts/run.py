@@ -9,6 +9,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
+    python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
 """
 import os
 import sys
@@ -23,21 +24,29 @@ def main():
     if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg"):
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
-    if algo == "ppo":
+
+    def take(flags):
+        """the options that are not fields of the algorithm's config struct: removed from argv, returned as keywords"""
+        nonlocal argv
         kw = {}
-        # not PPOConfig fields: the env of ppo.jl:82, the width of networks.jl:36 and the evaluation / diagnostics cadence (crl_ppo_evaluate, crl_ppo_diagnose)
-        for flag, cast in (("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int), ("--diag_every", int)):
+        for flag, cast in flags:
             if flag in argv:
                 i = argv.index(flag)
                 if i + 1 >= len(argv):
                     raise SystemExit(f"{flag} needs a value")
                 kw[flag[2:]] = cast(argv[i + 1])
                 argv = argv[:i] + argv[i + 2:]
+        return kw
+
+    if algo == "ppo":
+        # not PPOConfig fields: the env of ppo.jl:82, the width of networks.jl:36 and the evaluation / diagnostics cadence (crl_ppo_evaluate, crl_ppo_diagnose)
+        kw = take((("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int), ("--diag_every", int)))
         crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False).close()
     elif algo == "ddpg":
-        crl.ddpg(config_parser.argparse_struct(crl.DDPGConfig(), argv), "pendulum", to_terminal=True, to_tensorboard=False).close()
+        kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate)
+        crl.ddpg(config_parser.argparse_struct(crl.DDPGConfig(), argv), "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
     else:
         crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False).close()
 
