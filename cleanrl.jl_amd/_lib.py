@@ -64,6 +64,15 @@ class CrlEvalReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CrlValueEvalReport(C.Structure):
+    """crl_value_eval_report: what crl_dqn_evaluate / crl_a2c_evaluate report (population standard deviation; v_bias_mean = mean(v0 - disc_return))."""
+    _fields_ = [("episodes", C.c_int64), ("env_steps", C.c_int64)] + [(n, C.c_double) for n in (
+        "return_mean", "return_std", "return_min", "return_max", "length_mean", "disc_return_mean", "v0_mean", "v_bias_mean")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class CrlDiag(C.Structure):
     """crl_ppo_diag: raw Float64 sums of crl_ppo_diagnose over the resident rollout buffer (shards add them field by field; min / max for ratio_*)
     and the fields derived from them (entropy = policy entropy per sample = n_act x the reference's entropy_loss)."""
@@ -88,7 +97,7 @@ EXPORTS = [
     "crl_a2c_create", "crl_a2c_destroy", "crl_a2c_param_count", "crl_a2c_write_params", "crl_a2c_read_params",
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
-    "crl_dqn_q_values",
+    "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -263,6 +272,11 @@ def load():
     L.crl_dqn_status_read.argtypes = [vp, C.POINTER(CrlDQNStatus)]
     L.crl_dqn_run.argtypes = [vp, C.c_int64, C.POINTER(CrlDQNEpisode), C.c_int32, ip, C.POINTER(CrlDQNLossRecord), C.c_int32, ip, i64p]
     L.crl_dqn_q_values.argtypes = [vp, dp, C.c_int32, dp]
+    L.crl_dqn_evaluate.argtypes = [vp, C.POINTER(CrlEvalConfig), C.POINTER(CrlValueEvalReport), dp, ip, dp, dp, ip]
+    L.crl_dqn_eval_envs_per_block.argtypes = []
+    L.crl_a2c_forward.argtypes = [vp, C.c_int32, dp, C.c_int32, dp]
+    L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
+    L.crl_a2c_eval_envs_per_block.argtypes = []
     L.crl_ddpg_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
     L.crl_ddpg_create.argtypes = [C.POINTER(CrlDDPGConfig), C.c_int32, C.POINTER(vp)]
     L.crl_ddpg_destroy.argtypes = [vp]
@@ -824,6 +838,50 @@ class A2CHandle:
         episodes = [(eps[i].episode_return, eps[i].episode_length, eps[i].global_step) for i in range(n.value)]
         return taken.value, dict(actor_loss=ts.actor_loss, critic_loss=ts.critic_loss, n=ts.n, trained=bool(ts.trained)), episodes
 
+    def forward(self, net, obs):
+        """crl_a2c_forward: net 0 = the actor's logits, (4, n) → (2, n); net 1 = the critic, (4, n) → (n,). Float64."""
+        obs = np.asfortranarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        n = obs.shape[1]
+        out = np.zeros(n, np.float64) if net == 1 else np.zeros((2, n), np.float64, order="F")
+        check(self._L.crl_a2c_forward(self._h, int(net), _ptr(obs, C.c_double), n, _ptr(out, C.c_double)))
+        return out
+
+    def evaluate(self, num_envs, episodes_per_env=1, mode=EVAL_GREEDY, seed=0, trace_steps=0):
+        """crl_a2c_evaluate: the current actor, frozen, greedy or sampled, on `num_envs` fresh private CartPoles x `episodes_per_env` episodes (one
+        launch). Returns {"report": {...}, "returns", "disc_returns", "v0": (episodes_per_env, num_envs) float64, "lengths": int32[, "trace_action":
+        (trace_steps, num_envs) int32, −1 after the env's quota]}."""
+        return _value_evaluate(self._L.crl_a2c_evaluate, self._h, num_envs, episodes_per_env, mode, seed, trace_steps, "v0")
+
+
+def _value_evaluate(fn, handle, num_envs, episodes_per_env, mode, seed, trace_steps, v0_name):
+    """crl_dqn_evaluate / crl_a2c_evaluate → {"report", "returns", "lengths", "disc_returns", v0_name[, "trace_action"]}; the report's v0_mean /
+    v_bias_mean carry v0_name's prefix (q0_mean / q_bias_mean for DQN, like DDPG's)."""
+    cfg = CrlEvalConfig(int(num_envs), int(episodes_per_env), int(mode), int(trace_steps), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    rep = CrlValueEvalReport()
+    shape = (max(cfg.episodes_per_env, 0), max(cfg.num_envs, 0))
+    ret, disc, v0 = (np.zeros(shape, np.float64) for _ in range(3))
+    lengths = np.zeros(shape, np.int32)
+    trace = np.zeros((cfg.trace_steps, shape[1]), np.int32) if cfg.trace_steps > 0 else None
+    check(fn(handle, C.byref(cfg), C.byref(rep), _ptr(ret, C.c_double), _ptr(lengths, C.c_int32), _ptr(disc, C.c_double), _ptr(v0, C.c_double),
+             None if trace is None else _ptr(trace, C.c_int32)))
+    report = rep.as_dict()
+    if v0_name != "v0":
+        report = {k.replace("v0_", "q0_").replace("v_bias", "q_bias"): v for k, v in report.items()}
+    out = {"report": report, "returns": ret, "lengths": lengths, "disc_returns": disc, v0_name: v0}
+    if trace is not None:
+        out["trace_action"] = trace
+    return out
+
+
+def dqn_eval_envs_per_block():
+    return load().crl_dqn_eval_envs_per_block()
+
+
+def a2c_eval_envs_per_block():
+    return load().crl_a2c_eval_envs_per_block()
+
 
 def a2c_discounted_future_rewards_host(rewards, terminals, final_value, gamma, device=0):
     r = np.ascontiguousarray(rewards, np.float64); t = np.ascontiguousarray(terminals, np.uint8)
@@ -885,6 +943,12 @@ class DQNHandle:
         q = np.zeros((2, n), np.float64, order="F")
         check(self._L.crl_dqn_q_values(self._h, _ptr(obs, C.c_double), n, _ptr(q, C.c_double)))
         return q
+
+    def evaluate(self, num_envs, episodes_per_env=1, seed=0, trace_steps=0):
+        """crl_dqn_evaluate: the current q_net, frozen and greedy (no ε), on `num_envs` fresh private CartPoles x `episodes_per_env` episodes (one
+        launch). Returns {"report": {..., q0_mean, q_bias_mean}, "returns", "disc_returns", "q0": (episodes_per_env, num_envs) float64, "lengths":
+        int32[, "trace_action": (trace_steps, num_envs) int32, −1 after the env's quota]}."""
+        return _value_evaluate(self._L.crl_dqn_evaluate, self._h, num_envs, episodes_per_env, EVAL_GREEDY, seed, trace_steps, "q0")
 
 
 def ddpg_param_count(obs_dim, act_dim):

@@ -22,6 +22,7 @@
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "tanh64.hpp"
+#include "value_eval.hpp"
 
 struct crl_a2c;
 
@@ -59,27 +60,40 @@ __device__ __forceinline__ void load_row(const float* __restrict__ P, int lane, 
   for (int j = 0; j < AH; ++j) r.w2[j] = W2[lane + AH * j];
   r.b2 = W2[AH * AH + lane];
 }
+// The same row left in memory: w1[k] / w2[j] read the parameter vector where they are used, so nothing of it outlives the forward
+struct StridedCol { const float* p; __device__ __forceinline__ float operator[](int k) const { return p[AH * k]; } };
+struct NetRowRef { StridedCol w1; float b1; StridedCol w2; float b2; };
+__device__ __forceinline__ NetRowRef ref_row(const float* __restrict__ P, int lane) {
+  const float* W2 = P + AH * AD + AH;
+  return NetRowRef{{P + lane}, P[AH * AD + lane], {W2 + lane}, W2[AH * AH + lane]};
+}
+// phases of one sample's LDS scratch: a block barrier where the block is the wave's only one (the training kernels), a wave fence where several waves
+// of a block each work on a private strip and may leave at different times (a2c_eval_kernel)
+template <bool BLOCK>
+__device__ __forceinline__ void a2c_phase() { if constexpr (BLOCK) __syncthreads(); else wave_lds_fence(); }
 // Dense(W, b, tanh_fast) twice for ONE sample, lane = unit; hs is a 64-double LDS scratch (ends holding h2)
-__device__ __forceinline__ void hidden_forward(const NetRow& r, const double (&x)[AD], double* hs, int lane, double& h1, double& h2) {
+template <bool BLOCK = true, typename Row = NetRow>
+__device__ __forceinline__ void hidden_forward(const Row& r, const double (&x)[AD], double* hs, int lane, double& h1, double& h2) {
 #pragma clang fp contract(off)
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < AD; ++k) acc += (double)r.w1[k] * x[k];
   acc += (double)r.b1;
   h1 = tanh_fast64(acc);
-  __syncthreads();
+  a2c_phase<BLOCK>();
   hs[lane] = h1;
-  __syncthreads();
+  a2c_phase<BLOCK>();
   acc = 0.0;
 #pragma unroll
   for (int j = 0; j < AH; ++j) acc += (double)r.w2[j] * hs[j];
   acc += (double)r.b2;
   h2 = tanh_fast64(acc);
-  __syncthreads();
+  a2c_phase<BLOCK>();
   hs[lane] = h2;
-  __syncthreads();
+  a2c_phase<BLOCK>();
 }
 // head: out[a] = Σ_k W3[a, k]·h2[k] + b3[a] in k order, on lane a (a < n_out); results land in zs
+template <bool BLOCK = true>
 __device__ __forceinline__ void head_forward(const float* __restrict__ W3, const float* __restrict__ b3, int n_out, const double* hs,
                                              double* zs, int lane) {
 #pragma clang fp contract(off)
@@ -89,7 +103,7 @@ __device__ __forceinline__ void head_forward(const float* __restrict__ W3, const
     for (int k = 0; k < AH; ++k) acc += (double)W3[lane + n_out * k] * hs[k];   // W3 may live in LDS (collect kernel)
     zs[lane] = acc + (double)b3[lane];
   }
-  __syncthreads();
+  a2c_phase<BLOCK>();
 }
 
 constexpr int NET_SIZE_A = AH * AD + AH + AH * AH + AH + AA * AH + AA;   // actor parameter count
@@ -299,6 +313,88 @@ __global__ void __launch_bounds__(256) a2c_wgrad_kernel(int net, const double* _
   grads[(net ? NET_SIZE_A : 0) + idx] = (float)g;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// crl_a2c_evaluate: the frozen actor, greedy or sampled, on n private CartPoles, `episodes` episodes each, in ONE launch. One wave owns one env from
+// its first reset to its last step, lane = hidden unit, A2C_EVAL_WAVES envs per block. The lane's rows of the actor's W1 and W2 are registers
+// (NetRow), its head sits in LDS as in a2c_collect_kernel, so the step loop reads no global memory; the critic runs once per episode, on the reset
+// state, straight from global memory (NetRowRef: its rows held in registers beside the actor's would cost the second wave per SIMD the launch bound
+// asks for). Env state, sums and the action are computed by every lane alike (wave-uniform: no broadcast). The arithmetic is hidden_forward's
+// and head_forward's, so logits and value have the bits crl_a2c_forward gives for the same observation; greedy mode never evaluates exp. Episodes end at different steps: after the ONE staging barrier no wave meets a block barrier again — a wave past n, or one whose
+// env has played its quota, simply leaves; phases are separated by wave_lds_fence on the wave-private hs / zs strips.
+// ------------------------------------------------------------------------------------------------------
+#ifndef CRL_A2C_EVAL_WAVES
+#define CRL_A2C_EVAL_WAVES 4  // envs per block; experiment builds (csrc/Makefile, EXTRA=-DCRL_A2C_EVAL_WAVES=n) measured 1, 2, 4, 8: DESIGN.md §3f
+#endif
+constexpr int A2C_EVAL_WAVES = CRL_A2C_EVAL_WAVES;
+__global__ void __launch_bounds__(64 * A2C_EVAL_WAVES, 2) a2c_eval_kernel(const float* __restrict__ params, int max_steps, double gamma, ValueEvalArgs ev) {
+#pragma clang fp contract(off)
+  __shared__ float w3s[AA * AH + AA];
+  __shared__ double hs[A2C_EVAL_WAVES][AH], zs[A2C_EVAL_WAVES][AA];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * A2C_EVAL_WAVES + w;
+  const float* P = net_base(params, 0);
+  const float* Pc = net_base(params, 1);
+  {
+    const float* W3g = P + AH * AD + AH + AH * AH + AH;
+    for (int i = threadIdx.x; i < AA * AH + AA; i += 64 * A2C_EVAL_WAVES) w3s[i] = W3g[i];
+  }
+  __syncthreads();                       // the only block barrier of the kernel
+  if (env >= ev.n) return;
+  NetRow r;
+  load_row(P, lane, r);
+  const float* W3 = w3s;
+  const float* b3 = w3s + AA * AH;
+  const float* W3c = Pc + AH * AD + AH + AH * AH + AH;
+  double* const hsw = hs[w];
+  double* const zsw = zs[w];
+  int64_t row = 0;                       // the env's step count across its episodes
+  for (int j = 0; j < ev.episodes; ++j) {
+    double s[AD], ret = 0.0, disc_ret = 0.0, disc = 1.0, h1, h2;
+    int t = 0, length = 0;
+    const size_t slot = (size_t)j * ev.n + env;
+    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
+    {                                    // V(s0): what crl_a2c_forward(net = 1) gives for the reset state
+      // the critic's rows are read from memory where they are used, once per episode, and die here: hoisted out of the episode loop (the pointer is
+      // laundered against that) they would sit beside the actor's for the whole launch and halve the waves a SIMD can hold
+      const float* Pcj = Pc;
+      asm volatile("" : "+s"(Pcj));
+      const NetRowRef rc = ref_row(Pcj, lane);
+      const double x[AD] = {s[0], s[1], s[2], s[3]};
+      hidden_forward<false>(rc, x, hsw, lane, h1, h2);
+      head_forward<false>(W3c, W3c + AH, 1, hsw, zsw, lane);
+      if (lane == 0) ev.v0[slot] = zsw[0];
+      a2c_phase<false>();
+    }
+    while (true) {
+      const double x[AD] = {s[0], s[1], s[2], s[3]};
+      hidden_forward<false>(r, x, hsw, lane, h1, h2);
+      head_forward<false>(W3, b3, AA, hsw, zsw, lane);
+      const double z0 = zsw[0], z1 = zsw[1];
+      int action;
+      if (ev.mode == CRL_EVAL_GREEDY) {
+        action = z1 > z0 ? 1 : 0;                                                     // argmax: first maximum
+      } else {                                                                        // a2c_collect_kernel's softmax and categorical draw
+        const double m = z1 > z0 ? z1 : z0;
+        const double e0 = exp(z0 - m), e1 = exp(z1 - m);
+        const double ssum = e0 + e1;
+        const double p0 = e0 / ssum;
+        const double draw = u53(philox_env(ev.seed, (uint32_t)env, (uint64_t)row, S_VEVAL_DRAW));
+        action = (p0 <= draw) ? 1 : 0;
+      }
+      if (lane == 0 && row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
+      row += 1;
+      const bool done = cartpole_step64(s, t, action, max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      ret += rew;
+      disc_ret += disc * rew;
+      disc = disc * gamma;
+      length += 1;
+      if (done) break;
+    }
+    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
+  }
+  value_eval_trace_tail(ev, env, row, lane);
+}
+
 __global__ void a2c_init_kernel(A2CDev a) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   A2CCtl c;
@@ -324,6 +420,8 @@ struct crl_a2c {
   double *h1[2] = {nullptr, nullptr}, *h2[2] = {nullptr, nullptr}, *d1 = nullptr, *d2 = nullptr;
   double *vout = nullptr, *z = nullptr, *G = nullptr, *adv = nullptr, *dvc = nullptr, *dza = nullptr, *lp_adv = nullptr;
   crl::ParamTable tab;   // the PPO layout at 4 / 2 / 64
+  void* stage = nullptr; size_t stage_bytes = 0;   // crl_a2c_forward
+  crl::ValueEvalScratch eval;                      // crl_a2c_evaluate
 };
 
 namespace crl {
@@ -420,7 +518,7 @@ int32_t crl_a2c_destroy(crl_a2c* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->params, h->grads, h->m, h->v, h->betap, h->ctl, h->eps, h->rb_state, h->rb_action, h->rb_reward, h->rb_terminal,
-                  h->h1[0], h->h1[1], h->h2[0], h->h2[1], h->d1, h->d2, h->vout, h->z, h->G, h->adv, h->dvc, h->dza, h->lp_adv};
+                  h->h1[0], h->h1[1], h->h2[0], h->h2[1], h->d1, h->d2, h->vout, h->z, h->G, h->adv, h->dvc, h->dza, h->lp_adv, h->stage, h->eval.p};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -537,5 +635,47 @@ int32_t crl_a2c_discounted_future_rewards(int32_t device, const double* rewards,
   (void)hipFree(buf);
   return rc;
 }
+
+int32_t crl_a2c_forward(crl_a2c* h, int32_t net, const double* obs, int32_t n, double* out) {
+  A2C_GUARD(h);
+  if (!h->params_set) { set_error("crl_a2c_forward: parameters not set — crl_a2c_write_params or crl_a2c_init_params first (a2c.jl:37)"); return 1; }
+  if (net != 0 && net != 1) { set_error("crl_a2c_forward: net must be 0 (actor) or 1 (critic), got " + std::to_string(net)); return 1; }
+  if (n < 0) { set_error("crl_a2c_forward: n must be >= 0, got " + std::to_string(n)); return 1; }
+  if (n > 0 && (!obs || !out)) { set_error("crl_a2c_forward: null obs or out"); return 1; }
+  if (n == 0) return 0;
+  const size_t N = (size_t)n, n_out = net ? 1 : AA, need = N * (AD + n_out) * 8;
+  if (h->stage_bytes < need) {
+    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
+    h->stage = nullptr; h->stage_bytes = 0;
+    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
+    h->stage_bytes = need;
+  }
+  double* so = static_cast<double*>(h->stage);
+  double* sz = so + N * AD;
+  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * AD * 8, hipMemcpyHostToDevice, h->stream));
+  // a wave per observation: the forward of the training batch without the stored activations
+  hipLaunchKernelGGL(a2c_forward_kernel, dim3(n), dim3(64), 0, h->stream, (const float*)h->params, (int)net, (const double*)so, (int)n,
+                     (double*)nullptr, (double*)nullptr, sz);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(out, sz, N * n_out * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Held-out evaluation: argument checks, scratch, ONE launch (a2c_eval_kernel), the per-episode arrays back to the host, the report in Float64
+int32_t crl_a2c_evaluate(crl_a2c* h, const crl_eval_config* cfg, crl_value_eval_report* report, double* returns, int32_t* lengths,
+                         double* disc_returns, double* v0, int32_t* trace_action) {
+  A2C_GUARD(h);
+  if (value_eval_check("crl_a2c_evaluate", cfg, report, h->params_set, "crl_a2c_write_params or crl_a2c_init_params first (a2c.jl:37)",
+                       h->cfg.max_steps, /*has_sampler=*/true, trace_action)) return 1;
+  ValueEvalArgs ev;
+  if (value_eval_scratch(h->eval, cfg, ev)) return 1;
+  // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
+  hipLaunchKernelGGL(a2c_eval_kernel, dim3((unsigned)((ev.n + A2C_EVAL_WAVES - 1) / A2C_EVAL_WAVES)), dim3(64 * A2C_EVAL_WAVES), 0, h->stream,
+                     (const float*)h->params, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  CRL_HIP_CHECK(hipGetLastError());
+  return value_eval_finish(h->stream, ev, report, returns, lengths, disc_returns, v0, trace_action);
+}
+int32_t crl_a2c_eval_envs_per_block(void) { return A2C_EVAL_WAVES; }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "replay_sample.hpp"
+#include "value_eval.hpp"
 
 struct crl_dqn;
 
@@ -342,6 +343,94 @@ __global__ void __launch_bounds__(128) dqn_q_kernel(const float* __restrict__ q,
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// crl_dqn_evaluate: the frozen q_net, greedy, on n private CartPoles, `episodes` episodes each, in ONE launch. One wave owns one env from its first
+// reset to its last step, DQN_EVAL_WAVES envs per block. The whole q_net (43.7 KB) is staged once per block into LDS as float and widened at use, so
+// the step loop reads no global memory; a wave takes the 120 and the 84 units as two units per lane (lane and lane + 64: two independent chains side by
+// side, which halves the dependent adds of a step) through its private h1 / h2 strips, and every lane forms both head sums, env state, episode sums and the action alike (wave-uniform: no broadcast). Each unit's dot product is
+// dqn_q_kernel's — input order, bias last, contraction off —, so an action has the bits crl_dqn_q_values gives for the same observation.
+// Episodes end at different steps: after the ONE staging barrier no wave meets a block barrier again — a wave past n, or one whose env has played
+// its quota, simply leaves; layers are separated by wave_lds_fence on the wave-private strips.
+// ------------------------------------------------------------------------------------------------------
+#ifndef CRL_DQN_EVAL_WAVES
+#define CRL_DQN_EVAL_WAVES 4  // envs per block; experiment builds (csrc/Makefile, EXTRA=-DCRL_DQN_EVAL_WAVES=n) measured 1, 2, 4, 8: DESIGN.md §3f
+#endif
+constexpr int DQN_EVAL_WAVES = CRL_DQN_EVAL_WAVES;
+static_assert(QP * 4 + DQN_EVAL_WAVES * (QH1 + QH2) * 8 <= 64 * 1024, "q_net + the waves' strips must fit the 64 KB static LDS limit");
+__global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_eval_kernel(const float* __restrict__ q, int max_steps, double gamma, ValueEvalArgs ev) {
+#pragma clang fp contract(off)
+  __shared__ float wq[QP];
+  __shared__ double h1s[DQN_EVAL_WAVES][QH1], h2s[DQN_EVAL_WAVES][QH2];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * DQN_EVAL_WAVES + w;
+  for (int p = threadIdx.x; p < QP; p += 64 * DQN_EVAL_WAVES) wq[p] = q[p];
+  __syncthreads();                       // the only block barrier of the kernel
+  if (env >= ev.n) return;
+  double* const h1w = h1s[w];
+  double* const h2w = h2s[w];
+  // a lane's second unit of each hidden layer; a lane that has none (lane + 64 past the layer) repeats its first and stores nothing
+  const int u1b = lane + 64 < QH1 ? lane + 64 : lane, u2b = lane + 64 < QH2 ? lane + 64 : lane;
+  int64_t row = 0;                       // the env's step count across its episodes
+  for (int j = 0; j < ev.episodes; ++j) {
+    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
+    int t = 0, length = 0;
+    const size_t slot = (size_t)j * ev.n + env;
+    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
+    while (true) {
+      {                                  // layer 1: units `lane` and `lane + 64`, two independent chains side by side
+        double acc = 0.0, acc2 = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < QD; ++kk) {
+          acc += (double)wq[QoW1 + lane + QH1 * kk] * s[kk];
+          acc2 += (double)wq[QoW1 + u1b + QH1 * kk] * s[kk];
+        }
+        acc += (double)wq[Qob1 + lane];
+        acc2 += (double)wq[Qob1 + u1b];
+        h1w[lane] = acc > 0.0 ? acc : 0.0;
+        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
+      }
+      wave_lds_fence();
+      {                                  // layer 2: the same pairing — 120 dependent adds per step, not 240
+        double acc = 0.0, acc2 = 0.0;
+#pragma unroll 8
+        for (int kk = 0; kk < QH1; ++kk) {
+          const double h = h1w[kk];
+          acc += (double)wq[QoW2 + lane + QH2 * kk] * h;
+          acc2 += (double)wq[QoW2 + u2b + QH2 * kk] * h;
+        }
+        acc += (double)wq[Qob2 + lane];
+        acc2 += (double)wq[Qob2 + u2b];
+        h2w[lane] = acc > 0.0 ? acc : 0.0;
+        if (lane + 64 < QH2) h2w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
+      }
+      wave_lds_fence();
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll 4
+      for (int kk = 0; kk < QH2; ++kk) {
+        const double h = h2w[kk];
+        a0 += (double)wq[QoW3 + QA * kk] * h;
+        a1 += (double)wq[QoW3 + 1 + QA * kk] * h;
+      }
+      const double q0 = a0 + (double)wq[Qob3], q1 = a1 + (double)wq[Qob3 + 1];
+      const int action = q1 > q0 ? 1 : 0;                                               // argmax: first maximum, as dqn_collect_kernel
+      if (lane == 0) {
+        if (length == 0) ev.v0[slot] = action ? q1 : q0;
+        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
+      }
+      row += 1;
+      const bool done = cartpole_step64(s, t, action, max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      ret += rew;
+      disc_ret += disc * rew;
+      disc = disc * gamma;
+      length += 1;
+      wave_lds_fence();                  // the next step's strip writes stay behind this step's reads
+      if (done) break;
+    }
+    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
+  }
+  value_eval_trace_tail(ev, env, row, lane);
+}
+
 }  // namespace crl
 
 struct crl_dqn {
@@ -351,6 +440,7 @@ struct crl_dqn {
   hipStream_t stream = nullptr;
   crl::DQNDev d;
   void* stage = nullptr; size_t stage_bytes = 0;
+  crl::ValueEvalScratch eval;   // crl_dqn_evaluate
   hipGraphExec_t cycle_exec = nullptr; bool graph_failed = false;   // CRL_DQN_GRAPH=1 replays the cycle as a hipGraph
 };
 
@@ -430,7 +520,7 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
   if (h->cycle_exec) (void)hipGraphExecDestroy(h->cycle_exec);
   DQNDev& d = h->d;
   void* ptrs[] = {d.q, d.t, d.grads, d.m, d.v, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_reward, d.rb_action,
-                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage};
+                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -544,5 +634,21 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+// Held-out evaluation: argument checks, scratch, ONE launch (dqn_eval_kernel), the per-episode arrays back to the host, the report in Float64
+int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_report* report, double* returns, int32_t* lengths,
+                         double* disc_returns, double* v0, int32_t* trace_action) {
+  DQN_GUARD(h);
+  if (value_eval_check("crl_dqn_evaluate", cfg, report, h->params_set, "crl_dqn_write_params or crl_dqn_init_params first (dqn.jl:39)",
+                       h->cfg.max_steps, /*has_sampler=*/false, trace_action)) return 1;
+  ValueEvalArgs ev;
+  if (value_eval_scratch(h->eval, cfg, ev)) return 1;
+  // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
+  hipLaunchKernelGGL(dqn_eval_kernel, dim3((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), dim3(64 * DQN_EVAL_WAVES), 0, h->stream,
+                     (const float*)h->d.q, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  CRL_HIP_CHECK(hipGetLastError());
+  return value_eval_finish(h->stream, ev, report, returns, lengths, disc_returns, v0, trace_action);
+}
+int32_t crl_dqn_eval_envs_per_block(void) { return DQN_EVAL_WAVES; }
 
 }  // extern "C"

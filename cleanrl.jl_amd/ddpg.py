@@ -93,7 +93,9 @@ def eval_report(returns, disc_returns, q0, env_steps):
                 q_bias_mean=float(bsum / n))
 
 
-def _check_eval_args(who, num_envs, episodes_per_env, seed, trace_steps, max_steps):
+def _check_eval_args(who, num_envs, episodes_per_env, seed, trace_steps, max_steps, last_step=False):
+    """The argument checks of the *_evaluate calls, before the library is touched. last_step: an episode may take max_steps + 1 steps (the CartPole
+    of dqn / a2c ends at t > max_steps), so that is what bounds the trace."""
     for name, v, lo, hi in (("num_envs", num_envs, 1, 65536), ("episodes_per_env", episodes_per_env, 1, 1024), ("trace_steps", trace_steps, 0, None)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError(f"{who}: {name} must be an integer, got {type(v).__name__}")
@@ -103,8 +105,9 @@ def _check_eval_args(who, num_envs, episodes_per_env, seed, trace_steps, max_ste
         raise ValueError(f"{who}: seed must be an integer in [0, 2^64), got {seed!r}")
     if num_envs * episodes_per_env > 1 << 20:
         raise ValueError(f"{who}: num_envs * episodes_per_env must be <= 1048576, got {num_envs * episodes_per_env}")
-    if trace_steps > episodes_per_env * max_steps:
-        raise ValueError(f"{who}: trace_steps must be <= episodes_per_env * max_steps = {episodes_per_env * max_steps}, got {trace_steps}")
+    per_episode, label = (max_steps + 1, "(max_steps + 1)") if last_step else (max_steps, "max_steps")
+    if trace_steps > episodes_per_env * per_episode:
+        raise ValueError(f"{who}: trace_steps must be <= episodes_per_env * {label} = {episodes_per_env * per_episode}, got {trace_steps}")
     if trace_steps * num_envs > 1 << 24:
         raise ValueError(f"{who}: trace_steps * num_envs must be <= 16777216, got {trace_steps * num_envs}")
 

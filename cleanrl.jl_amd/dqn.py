@@ -8,6 +8,8 @@ import numpy as np
 
 from . import _lib as L
 from . import logger as Logger
+from .ddpg import _check_eval_args, _emit
+from .ppo import EVAL_SEED    # the key of the evaluation envs is its own: a held-out score does not replay the training env's initial states
 
 
 @dataclasses.dataclass
@@ -62,21 +64,52 @@ class DQNAgent:
         self.handle.close()
 
 
-def dqn(config: DQNConfig = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, **logger_kw):
+def dqn_evaluate(agent, *, num_envs=256, episodes_per_env=1, seed=EVAL_SEED, trace_steps=0):
+    """How good is the greedy policy, and does q_net over-estimate? crl_dqn_evaluate: the agent's q_net (not the target), frozen and WITHOUT the
+    ε-greedy exploration, plays `episodes_per_env` whole episodes on each of `num_envs` fresh CartPoles in one launch on the GPU (no reference
+    counterpart: dqn.jl only logs the returns of its ε >= 0.05 behaviour policy on the training env). Training state is not touched. Returns
+    {"report": {episodes, env_steps, return_mean, return_std, return_min, return_max, length_mean, disc_return_mean, q0_mean, q_bias_mean},
+    "returns", "lengths", "disc_returns", "q0"} — the arrays are (episodes_per_env, num_envs); q0 = max_a Q(s0, a) and q_bias_mean = mean(q0 −
+    discounted return): positive = q_net promises more than the greedy policy collects — plus "trace_action" (trace_steps, num_envs), the actions
+    of each env's first trace_steps steps (−1 once it has finished), when trace_steps > 0. Arguments are validated here, before the library is
+    touched."""
+    if not isinstance(agent, DQNAgent):
+        raise TypeError("dqn_evaluate: agent must be a cleanrl_jl_amd DQNAgent")
+    _check_eval_args("dqn_evaluate", num_envs, episodes_per_env, seed, trace_steps, int(agent.crl_cfg.max_steps), last_step=True)
+    return agent.handle.evaluate(num_envs, episodes_per_env, seed, trace_steps)
+
+
+def _eval_record(global_step, report):
+    return (global_step, "Evaluation Statistics", dict(eval_return_mean=report["return_mean"], eval_return_std=report["return_std"],
+                                                       eval_q_bias=report["q_bias_mean"], global_step=global_step))
+
+
+def dqn(config: DQNConfig = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256, eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
-    (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116)."""
+    (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
+    `eval_every=N > 0` adds an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_q_bias, global_step) after the records of
+    every env step that is a multiple of N: dqn_evaluate of the parameters that step left, on eval_envs fresh CartPoles x eval_episodes episodes.
+    The library calls are cut at multiples of N (crl_dqn_run takes a step budget; chunking changes no bit of the run). 0 (default) keeps the record
+    stream what it was."""
+    if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
+        raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
+    if eval_every:
+        _check_eval_args("dqn", eval_envs, eval_episodes, EVAL_SEED, 0, 1)
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
     agent = DQNAgent(config, device=device, seed=seed, params=params)
     start = time.time()
+    global_step = 0
     while True:
-        taken, episodes, losses = agent.handle.run(chunk)
+        taken, episodes, losses = agent.handle.run(min(chunk, eval_every - global_step % eval_every) if eval_every else chunk)
         records = [(g, "Episode Statistics", dict(episode_return=r, episode_length=n, global_step=g, **{"ϵ": e},
                                                   steps_per_sec=int(g / max(time.time() - start, 1e-9)))) for r, n, g, e in episodes]
         records += [(g, "Training Statistics", dict(loss=v)) for g, v in losses]
-        for _, msg, kv in sorted(records, key=lambda x: x[0]):
-            lg.info(msg, extra={"crl": kv})
-        if taken == 0 or agent.handle.status()["global_step"] >= config.total_timesteps:
+        _emit(lg, records)
+        global_step = agent.handle.status()["global_step"]
+        if eval_every and taken > 0 and global_step % eval_every == 0:
+            _emit(lg, [_eval_record(global_step, agent.handle.evaluate(eval_envs, eval_episodes, EVAL_SEED, 0)["report"])])
+        if taken == 0 or global_step >= config.total_timesteps:
             break
     return agent

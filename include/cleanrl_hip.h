@@ -473,6 +473,9 @@ typedef struct crl_a2c_config {   /* A2CConfig, a2c.jl:1-10 */
 typedef struct crl_a2c_train_stats { double actor_loss, critic_loss; int32_t n, trained; } crl_a2c_train_stats;  /* a2c.jl:100 */
 typedef struct crl_a2c_episode { double episode_return; int64_t episode_length, global_step; } crl_a2c_episode;  /* a2c.jl:106 */
 typedef struct crl_a2c crl_a2c;
+/* What crl_dqn_evaluate and crl_a2c_evaluate report: Float64 on the host from the per-episode arrays, sums in array order (80 bytes). */
+typedef struct crl_value_eval_report { int64_t episodes, env_steps;
+  double return_mean, return_std, return_min, return_max, length_mean, disc_return_mean, v0_mean, v_bias_mean; } crl_value_eval_report;
 
 /* a2c.jl:32-52: networks (parameters are uploaded by crl_a2c_write_params, same flat layout as PPO: obs 4 / act 2 / 2x64),
  * Optimiser(ClipNorm(0.5), Adam(lr)) state, ReplayBuffer(capacity = 2*min_replay_size), reset!(env). */
@@ -497,6 +500,16 @@ int32_t crl_a2c_run_until_update(crl_a2c* h, int64_t max_env_steps, crl_a2c_trai
 /* discounted_future_rewards(rewards, terminals, final_value, γ) (a2c.jl:13-24) on host vectors */
 int32_t crl_a2c_discounted_future_rewards(int32_t device, const double* rewards, const uint8_t* terminals, int32_t n,
                                           double final_value, double gamma, double* out);
+/* The missing public forward of A2C, the counterpart of crl_dqn_q_values. net 0: the actor's logits, (4, n) -> (2, n); net 1: the critic, (4, n) -> (n).
+ * Float64, a2c.jl:55-56 / :82 arithmetic: Dense(tanh_fast) twice and the head, products in input order, bias last, no contraction — a wave per
+ * observation through the forward kernel of the training batch. Errors: net outside {0, 1}; n < 0; NULL obs or out with n > 0; parameters never set. */
+int32_t crl_a2c_forward(crl_a2c* h, int32_t net, const double* obs, int32_t n, double* out);
+/* Held-out evaluation of the current actor, and of the critic's bias: see crl_dqn_evaluate below, whose definition it shares. A2C reads both networks,
+ * accepts CRL_EVAL_GREEDY and CRL_EVAL_SAMPLE, and v0 is the critic's value of the reset state. csrc/a2c.hip, a2c_eval_kernel. */
+int32_t crl_a2c_evaluate(crl_a2c* h, const crl_eval_config* cfg, crl_value_eval_report* report,
+                         double* returns, int32_t* lengths, double* disc_returns, double* v0, int32_t* trace_action);
+/* envs per block of a2c_eval_kernel (a compile-time constant of the library; tests choose their block-edge sizes from it) */
+int32_t crl_a2c_eval_envs_per_block(void);
 
 /* =====================================================================================================
  * DQN: src/algorithms/dqn.jl on the GPU. One on-device CartPoleEnv{Float64} (max_steps = 200),
@@ -538,6 +551,42 @@ int32_t crl_dqn_run(crl_dqn* h, int64_t max_env_steps, crl_dqn_episode* eps, int
                     crl_dqn_loss_record* losses, int32_t max_losses, int32_t* n_losses, int64_t* steps_taken);
 /* q_net(obs) for n observations (4, n) Float64 → (2, n) Float64 (dqn.jl:64) */
 int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q);
+/* Held-out evaluation of the greedy policy, and of the value function's bias — no reference counterpart: dqn.jl:61-68 acts ε-greedily with
+ * ε >= epsilon_end = 0.05 and a2c.jl:56-58 samples from the softmax, so their "Episode Statistics" score an exploring policy on the one training env,
+ * and neither log can say whether the value function over-estimates — for DQN, whose TD target is a max over target-net Q-values (dqn.jl:99-100),
+ * the first question anyone asks. Here the handle's current network(s), frozen, play cfg->episodes_per_env whole episodes on each of cfg->num_envs
+ * fresh, private CartPoleEnv{Float64} in ONE read-only launch (csrc/dqn.hip dqn_eval_kernel, csrc/a2c.hip a2c_eval_kernel; one wave owns one env).
+ * crl_eval_config is PPO's struct. The trajectory is defined by public calls. With n = num_envs, E = episodes_per_env and the handle's max_steps and
+ * gamma, env e (0 <= e < n), episode j (0 <= j < E):
+ *   reset    s[i] = 0.1·u53(Philox(key = cfg->seed, env = i, gstep = j·n + e, stream 0x20)) − 0.05, i = 0..3 — the loops' reset at the new stream 0x20,
+ *            "evaluation reset" (the loops use 0, 1, 2 and 4, DDPG 0x10–0x16) —, t = 0.
+ *   step     obs = the four doubles of s.
+ *            DQN: q = exactly what crl_dqn_q_values returns for obs; action = q[1] > q[0] ? 1 : 0 (the first maximum, as the training loop's argmax).
+ *                 Only CRL_EVAL_GREEDY is accepted: DQN has no sampling policy.
+ *            A2C: z = exactly what crl_a2c_forward(net = 0) returns for obs. CRL_EVAL_GREEDY: action = z[1] > z[0] ? 1 : 0 (exp is never evaluated).
+ *                 CRL_EVAL_SAMPLE: the training loop's own expressions, m = max(z0, z1), e0 = exp(z0 − m), e1 = exp(z1 − m), p0 = e0 / (e0 + e1),
+ *                 action = p0 <= draw with draw = u53(Philox(key = cfg->seed, env = e, gstep = r, stream 0x21)), r = the env's step count across its
+ *                 episodes; stream 0x21 is new, "evaluation draw".
+ *   v0       on the first step of an episode. DQN: q[action]. A2C: exactly what crl_a2c_forward(net = 1) returns for obs.
+ *   sums     done = the CartPole step with action (terminal by position, angle, or t > max_steps), rew = done ? 0.0 : 1.0 as in both training loops;
+ *            ret += rew; disc_ret += disc·rew; disc = disc·gamma; length += 1, from 0.0, 0.0, 1.0 and 0 — Float64, in step order, a plain multiply
+ *            then an add, no contraction. The episode ends at done: it has at most max_steps + 1 steps.
+ * returns / lengths / disc_returns / v0: (E, n), env fastest (index j·n + e); each may be NULL. trace_action: (trace_steps, n), row r = the action of
+ * the env's r-th step counted across its episodes, or −1 once the env has played its quota; NULL exactly when trace_steps = 0, and trace_steps <=
+ * E·(max_steps + 1) (it exists so that tests can follow the device's trajectory). The report is computed on the host in Float64 from the arrays, sums
+ * in array order: episodes = n·E, env_steps = Σ lengths, return_std the population standard deviation, length_mean = Σ lengths / episodes,
+ * v0_mean = Σ v0 / episodes and v_bias_mean = Σ(v0 − disc_return) / episodes: positive = the value function promises more than the policy collects.
+ * Reads the handle's parameters and config and nothing else — DQN the q-net, not the target; A2C both networks —: the target net, Adam state and β
+ * powers, replay ring, env state and counters, episode sums and pending records stay bit for bit as they were. It synchronises before it returns. The
+ * launch is bounded by E·(max_steps + 1) steps per env; no flags, no atomics, and after one staging barrier no block-wide synchronisation, so waves
+ * whose episodes end early simply leave. Errors, each naming the field: NULL cfg / report; parameters never set; num_envs outside 1..65536;
+ * episodes_per_env outside 1..1024; num_envs * episodes_per_env > 1048576; an unknown mode, or CRL_EVAL_SAMPLE on DQN; trace_steps < 0 or >
+ * E·(max_steps + 1); trace_steps > 0 without a trace_action, or a trace_action with trace_steps = 0; trace_steps * num_envs > 16777216. Device scratch
+ * is allocated on first use, kept on the handle and freed by crl_*_destroy. */
+int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_report* report,
+                         double* returns, int32_t* lengths, double* disc_returns, double* v0, int32_t* trace_action);
+/* envs per block of dqn_eval_kernel (a compile-time constant of the library; tests choose their block-edge sizes from it) */
+int32_t crl_dqn_eval_envs_per_block(void);
 
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,

@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, dqn_evaluate, a2c_evaluate, a2c_forward, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -410,6 +410,50 @@ end
 struct CrlA2CTrainStats; actor_loss::Float64; critic_loss::Float64; n::Int32; trained::Int32; end
 struct CrlA2CEpisode; episode_return::Float64; episode_length::Int64; global_step::Int64; end
 
+struct CrlValueEvalReport # crl_value_eval_report: what crl_dqn_evaluate / crl_a2c_evaluate report (v_bias_mean = mean(v0 - disc_return))
+  episodes::Int64; env_steps::Int64; return_mean::Float64; return_std::Float64; return_min::Float64; return_max::Float64
+  length_mean::Float64; disc_return_mean::Float64; v0_mean::Float64; v_bias_mean::Float64
+end
+
+mutable struct A2CAgent
+  h::Ptr{Cvoid}
+end
+
+# crl_dqn_evaluate / crl_a2c_evaluate (they share their signature): episodes_per_env whole episodes on each of num_envs fresh on-device CartPoles
+# in one read-only launch. returns / lengths / disc_returns / v0 are (num_envs, episodes_per_env) — the C arrays are env-fastest —, trace_action
+# (num_envs, trace_steps) holds the actions of each env's first trace_steps steps, -1 once the env has played its quota.
+function _value_evaluate(sym::Symbol, who::String, h::Ptr{Cvoid}, num_envs, episodes_per_env, mode, seed, trace_steps)
+  1 <= num_envs <= 65536 || throw(ArgumentError("$who: num_envs must be in 1..65536, got $num_envs"))
+  1 <= episodes_per_env <= 1024 || throw(ArgumentError("$who: episodes_per_env must be in 1..1024, got $episodes_per_env"))
+  trace_steps >= 0 || throw(ArgumentError("$who: trace_steps must be >= 0, got $trace_steps"))
+  cfg = Ref(CrlEvalConfig(num_envs, episodes_per_env, mode, trace_steps, UInt64(seed)))
+  report = Ref{CrlValueEvalReport}()
+  returns = Matrix{Float64}(undef, num_envs, episodes_per_env); disc_returns = similar(returns); v0 = similar(returns)
+  lengths = Matrix{Int32}(undef, num_envs, episodes_per_env); trace_action = Matrix{Int32}(undef, num_envs, trace_steps)
+  tp = trace_steps > 0 ? pointer(trace_action) : Ptr{Int32}(C_NULL)
+  GC.@preserve returns lengths disc_returns v0 trace_action check(sym === :dqn ?
+    ccall((:crl_dqn_evaluate, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlEvalConfig}, Ref{CrlValueEvalReport}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+          h, cfg, report, returns, lengths, disc_returns, v0, tp) :
+    ccall((:crl_a2c_evaluate, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlEvalConfig}, Ref{CrlValueEvalReport}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+          h, cfg, report, returns, lengths, disc_returns, v0, tp))
+  return (report[], returns, lengths, disc_returns, v0, trace_action)
+end
+
+# the actor's logits (net = 0: (4, n) → (2, n)) or the critic's values (net = 1: (4, n) → (n,)) for caller-supplied observations: crl_a2c_forward
+function a2c_forward(agent::A2CAgent, net::Integer, obs::AbstractMatrix{Float64})
+  o = Array(obs); n = size(o, 2); out = net == 1 ? Vector{Float64}(undef, n) : Matrix{Float64}(undef, 2, n)
+  GC.@preserve o out check(ccall((:crl_a2c_forward, libcrl), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, net, o, n, out))
+  out
+end
+
+# How good is the current actor, and does the critic over-estimate? crl_a2c_evaluate: the actor, frozen, greedy (the larger logit) or sampled from
+# the softmax as the training loop does; v0 = critic(s0), report.v_bias_mean = mean(v0 - discounted return). Training state is not touched.
+function a2c_evaluate(agent::A2CAgent; num_envs::Integer=256, episodes_per_env::Integer=1, greedy::Bool=true, seed::Integer=EVAL_SEED, trace_steps::Integer=0)
+  report, returns, lengths, disc_returns, v0, trace_action =
+    _value_evaluate(:a2c, "a2c_evaluate", agent.h, num_envs, episodes_per_env, greedy ? 0 : 1, seed, trace_steps)
+  return (; report, returns, lengths, disc_returns, v0, trace_action)
+end
+
 # a2c.jl:13-24 — same signature
 function discounted_future_rewards(rewards::Vector{Float64}, terminals::Vector{Bool}, final_value::Float64, γ::Float64; device=0)
   out = similar(rewards); t = UInt8.(terminals)
@@ -421,12 +465,17 @@ end
 # a2c.jl:29 — same signature; `config` is the reference's A2CConfig. a2c.jl:30 installs the logger (terminal + TensorBoard: make_logger's own
 # defaults), a2c.jl:37 builds the networks: `params` wins, else `init` (the reference's Networks.make_actor_critic inside the package — a2c.jl:37
 # does not pipe through Flux.f32, Flux.orthogonal is Float32 already), else the library's initialiser. Never the handle's zeros.
+# eval_every = N > 0: an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_v_bias, global_step) after the records of every env
+# step that is a multiple of N — the library calls are cut there (chunking changes no bit of the run). Returns the agent (for a2c_evaluate).
 function a2c(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_init(), init_seed::Integer=0,
-             make_logger=_default_make_logger())
+             make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+  eval_every >= 0 || throw(ArgumentError("a2c: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("a2c|$(config.run_name)")         # a2c.jl:30
   cfg = CrlA2CConfig(config.lr, config.total_timesteps, config.min_replay_size, 500, config.gamma, seed)
   h = Ref{Ptr{Cvoid}}(C_NULL)
   check(ccall((:crl_a2c_create, libcrl), Int32, (Ref{CrlA2CConfig}, Int32, Ref{Ptr{Cvoid}}), cfg, device, h))
+  agent = A2CAgent(h[])
+  finalizer(x -> ccall((:crl_a2c_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
   params === nothing && init !== nothing && (params = init(2, 4, 64))      # a2c.jl:37 make_actor_critic(env): CartPole 4 / 2, hidden [64, 64]
   if params === nothing
     check(ccall((:crl_a2c_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), h[], UInt64(init_seed)))
@@ -438,7 +487,7 @@ function a2c(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   while global_step < config.total_timesteps
     GC.@preserve eps check(ccall((:crl_a2c_run_until_update, libcrl), Int32,
       (Ptr{Cvoid}, Int64, Ref{CrlA2CTrainStats}, Ptr{CrlA2CEpisode}, Int32, Ref{Int32}, Ref{Int64}),
-      h[], typemax(Int64), stats, eps, length(eps), n_eps, taken))
+      h[], eval_every > 0 ? Int64(eval_every - global_step % eval_every) : typemax(Int64), stats, eps, length(eps), n_eps, taken))
     taken[] == 0 && break
     global_step += taken[]
     # the episode whose end triggered the update is the call's LAST record, and the reference logs the update first (a2c.jl:100, then :106)
@@ -448,8 +497,12 @@ function a2c(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
       @info "Episode Statistics" episode_return = e.episode_return episode_length = e.episode_length global_step = e.global_step steps_per_sec
     end
     n_eps[] == 0 && stats[].trained == 1 && @info "Training Statistics" actor_loss = stats[].actor_loss critic_loss = stats[].critic_loss
+    if eval_every > 0 && global_step % eval_every == 0
+      ev = a2c_evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report
+      @info "Evaluation Statistics" eval_return_mean = ev.return_mean eval_return_std = ev.return_std eval_v_bias = ev.v_bias_mean global_step
+    end
   end
-  check(ccall((:crl_a2c_destroy, libcrl), Int32, (Ptr{Cvoid},), h[]))
+  agent
 end
 
 # ------------------------------------------------------------------------------------------------------
@@ -477,6 +530,14 @@ function q_values(agent::DQNAgent, obs::AbstractMatrix{Float64})
   q
 end
 
+# How good is the greedy policy, and does q_net over-estimate? crl_dqn_evaluate: q_net (not the target), frozen and WITHOUT the ε-greedy exploration
+# (dqn.jl:61-68 never lets ε below 0.05, so the reference's "Episode Statistics" score an exploring policy); q0 = max_a Q(s0, a),
+# report.v_bias_mean = mean(q0 - discounted return). Training state is not touched.
+function dqn_evaluate(agent::DQNAgent; num_envs::Integer=256, episodes_per_env::Integer=1, seed::Integer=EVAL_SEED, trace_steps::Integer=0)
+  report, returns, lengths, disc_returns, q0, trace_action = _value_evaluate(:dqn, "dqn_evaluate", agent.h, num_envs, episodes_per_env, 0, seed, trace_steps)
+  return (; report, returns, lengths, disc_returns, q0, trace_action)
+end
+
 # dqn.jl:34 — same signature; `config` is the reference's DQNConfig (note its field `log_frequencey`, sic), `params` =
 # vcat(vec.(Flux.params(q_net))...) of make_nn(env) (dqn.jl:22-26: 4 → 120 → 84 → 2, 10,934 parameters)
 # dqn.jl:35 installs the logger, dqn.jl:39 builds q_net: `params` wins, else `init()` (inside the reference package its own make_nn(CartPoleEnv()),
@@ -487,7 +548,8 @@ function _default_dqn_init()
   () -> Vector{Float32}(vcat(vec.(getfield(pm, :Flux).params(getfield(pm, :make_nn)(getfield(pm, :CartPoleEnv)())))...))
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
-             chunk::Integer=10_000, make_logger=_default_make_logger())
+             chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+  eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
                      config.train_freq, config.target_net_freq, config.batch_size, config.gamma, config.epsilon_start,
@@ -508,7 +570,7 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   while global_step < config.total_timesteps
     GC.@preserve eps losses check(ccall((:crl_dqn_run, libcrl), Int32,
       (Ptr{Cvoid}, Int64, Ptr{CrlDQNEpisode}, Int32, Ref{Int32}, Ptr{CrlDQNLossRecord}, Int32, Ref{Int32}, Ref{Int64}),
-      agent.h, chunk, eps, length(eps), n_eps, losses, length(losses), n_losses, taken))
+      agent.h, eval_every > 0 ? min(chunk, eval_every - global_step % eval_every) : chunk, eps, length(eps), n_eps, losses, length(losses), n_losses, taken))
     taken[] == 0 && break
     global_step += taken[]
     for e in @view eps[1:n_eps[]]
@@ -517,6 +579,10 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
     end
     for l in @view losses[1:n_losses[]]
       @info "Training Statistics" loss = l.loss global_step = l.global_step
+    end
+    if eval_every > 0 && global_step % eval_every == 0           # "Evaluation Statistics" after the records of that step; the calls are cut there
+      ev = dqn_evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report
+      @info "Evaluation Statistics" eval_return_mean = ev.return_mean eval_return_std = ev.return_std eval_q_bias = ev.v_bias_mean global_step
     end
   end
   agent

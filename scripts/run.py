@@ -8,6 +8,8 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
+    python scripts/run.py dqn --total_timesteps 50000 --eval_every 5000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the greedy policy's held-out score and q_net's bias every 5000 steps)
+    python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
 """
@@ -43,12 +45,14 @@ def main():
         kw = take((("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int), ("--diag_every", int)))
         crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
-        crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False).close()
+        kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_a2c_evaluate)
+        crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
     elif algo == "ddpg":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate)
         crl.ddpg(config_parser.argparse_struct(crl.DDPGConfig(), argv), "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
     else:
-        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False).close()
+        kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_dqn_evaluate)
+        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
 
 
 if __name__ == "__main__":
