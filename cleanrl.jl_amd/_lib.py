@@ -94,7 +94,7 @@ EXPORTS = [
     "crl_comm_unique_id", "crl_comm_init", "crl_comm_init_external", "crl_comm_peer_export", "crl_comm_peer_attach", "crl_adv_stats_local", "crl_adv_stats_finish",
     "crl_prof_enable", "crl_prof_read", "crl_prof_reset", "crl_ppo_exact_reruns", "crl_episode_ring_enable",
     "crl_episode_ring_read", "crl_comm_destroy", "crl_ppo_set_option", "crl_ppo_get_option", "crl_ppo_option_name", "crl_ppo_option_count", "crl_gae_bench", "crl_gae_opt",
-    "crl_a2c_create", "crl_a2c_destroy", "crl_a2c_param_count", "crl_a2c_write_params", "crl_a2c_read_params",
+    "crl_a2c_create", "crl_a2c_destroy", "crl_a2c_param_count", "crl_a2c_write_params", "crl_a2c_read_params", "crl_a2c_read_grads",
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
@@ -261,6 +261,7 @@ def load():
     L.crl_a2c_param_count.argtypes = [vp, i64p]
     L.crl_a2c_write_params.argtypes = [vp, fp, C.c_size_t]
     L.crl_a2c_read_params.argtypes = [vp, fp, C.c_size_t]
+    L.crl_a2c_read_grads.argtypes = [vp, fp, C.c_size_t]
     L.crl_a2c_read_env.argtypes = [vp, dp, i64p, ip]
     L.crl_a2c_read_buffer.argtypes = [vp, dp, ip, dp, u8p, C.c_int32]
     L.crl_a2c_run_until_update.argtypes = [vp, C.c_int64, C.POINTER(CrlA2CTrainStats), C.POINTER(CrlA2CEpisode), C.c_int32, ip, i64p]
@@ -819,6 +820,12 @@ class A2CHandle:
         p = np.zeros(self.param_count, np.float32)
         check(self._L.crl_a2c_read_params(self._h, _ptr(p, C.c_float), p.size))
         return p
+
+    def read_grads(self):
+        """crl_a2c_read_grads: the last update's Float32 gradients before ClipNorm, in the parameters' layout; an error before the first update."""
+        g = np.zeros(self.param_count, np.float32)
+        check(self._L.crl_a2c_read_grads(self._h, _ptr(g, C.c_float), g.size))
+        return g
 
     def env(self):
         s = np.zeros(4, np.float64); g = C.c_int64(); n = C.c_int32()

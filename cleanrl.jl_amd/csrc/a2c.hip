@@ -412,6 +412,7 @@ struct crl_a2c {
   crl_a2c_config cfg;
   int device = 0; int cap = 0; int64_t P = 0;
   bool params_set = false;   // a2c.jl:37 has happened: parameters were uploaded or crl_a2c_init_params ran (a fresh handle holds zeros)
+  bool grads_set = false;    // a2c_update has run: `grads` holds an update's gradients (crl_a2c_read_grads)
   hipStream_t stream = nullptr;
   float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr; double* betap = nullptr;
   crl::A2CCtl* ctl = nullptr; crl_a2c_episode* eps = nullptr;
@@ -467,6 +468,7 @@ static int a2c_update(crl_a2c* h, int n) {
   if (launch_clipnorm_adam_range(st, oc, h->grads, 0, 6)) return 1;
   hipLaunchKernelGGL(a2c_finish_kernel, dim3(1), dim3(1), 0, st, a);
   CRL_HIP_CHECK(hipGetLastError());
+  h->grads_set = true;
   return 0;
 }
 }  // namespace crl
@@ -549,6 +551,15 @@ int32_t crl_a2c_read_params(crl_a2c* h, float* params, size_t n) {
   A2C_GUARD(h);
   if (!params || n != (size_t)h->P) { set_error("crl_a2c_read_params: expected " + std::to_string(h->P) + " floats"); return 1; }
   CRL_HIP_CHECK(hipMemcpyAsync(params, h->params, n * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// the optimiser reads `grads` as const (launch_clipnorm_adam_range): what the wgrad kernels wrote is still there after the update
+int32_t crl_a2c_read_grads(crl_a2c* h, float* grads, size_t n) {
+  A2C_GUARD(h);
+  if (!grads || n != (size_t)h->P) { set_error("crl_a2c_read_grads: expected " + std::to_string(h->P) + " floats"); return 1; }
+  if (!h->grads_set) { set_error("crl_a2c_read_grads: no update yet — the gradients exist after the first crl_a2c_run_until_update that trained"); return 1; }
+  CRL_HIP_CHECK(hipMemcpyAsync(grads, h->grads, n * 4, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -484,6 +484,11 @@ int32_t crl_a2c_destroy(crl_a2c* h);
 int32_t crl_a2c_param_count(const crl_a2c* h, int64_t* n);
 int32_t crl_a2c_write_params(crl_a2c* h, const float* params, size_t n);
 int32_t crl_a2c_read_params(crl_a2c* h, float* params, size_t n);
+/* The Float32 gradients of the last update (a2c.jl:87,97 `gradient(...)`, projected to the parameters' type) as the optimiser received them:
+ * before ClipNorm, same flat layout as the parameters (the actor's six arrays, then the critic's). The optimiser reads them without changing
+ * them, so they stay until the next update. Read-only; synchronises on the handle's stream. Errors: NULL grads; n != crl_a2c_param_count; no
+ * update yet (no crl_a2c_run_until_update call of this handle has trained). */
+int32_t crl_a2c_read_grads(crl_a2c* h, float* grads, size_t n);
 /* `actor, critic = Networks.make_actor_critic(env)` — a2c.jl:37: crl_make_actor_critic(4, 2, 64, seed) uploaded. crl_a2c_run_until_update
  * on a handle whose parameters were neither written nor initialised is an error (a fresh handle holds zeros). */
 int32_t crl_a2c_init_params(crl_a2c* h, uint64_t seed);

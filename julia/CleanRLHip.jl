@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, dqn_evaluate, a2c_evaluate, a2c_forward, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -445,6 +445,9 @@ function a2c_forward(agent::A2CAgent, net::Integer, obs::AbstractMatrix{Float64}
   GC.@preserve o out check(ccall((:crl_a2c_forward, libcrl), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, net, o, n, out))
   out
 end
+
+# the last update's Float32 gradients before ClipNorm, in the parameters' flat layout (an error before the first update): crl_a2c_read_grads
+a2c_read_grads(agent::A2CAgent) = (g = Vector{Float32}(undef, 9155); GC.@preserve g check(ccall((:crl_a2c_read_grads, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), agent.h, g, length(g))); g)
 
 # How good is the current actor, and does the critic over-estimate? crl_a2c_evaluate: the actor, frozen, greedy (the larger logit) or sampled from
 # the softmax as the training loop does; v0 = critic(s0), report.v_bias_mean = mean(v0 - discounted return). Training state is not touched.
