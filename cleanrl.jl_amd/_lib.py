@@ -101,6 +101,7 @@ EXPORTS = [
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
+    "crl_td3_create", "crl_td3_write_params", "crl_td3_read_params", "crl_td3_init_params", "crl_td3_q_values",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
@@ -141,6 +142,11 @@ class CrlDDPGConfig(C.Structure):
                 ("lr", C.c_double), ("tau", C.c_double), ("gamma", C.c_double), ("exploration_noise", C.c_double),
                 ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("env_kind", C.c_int32), ("max_steps", C.c_int32),
                 ("act_low", C.c_double), ("act_high", C.c_double), ("noise_in_update", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CrlTD3Options(C.Structure):
+    """crl_td3_options: what TD3 adds to crl_ddpg_config."""
+    _fields_ = [("policy_delay", C.c_int32), ("pad", C.c_int32), ("policy_noise", C.c_double), ("noise_clip", C.c_double)]
 
 
 class CrlDDPGEpisode(C.Structure):
@@ -294,6 +300,11 @@ def load():
     L.crl_ddpg_actor.argtypes = [vp, dp, C.c_int32, dp]
     L.crl_ddpg_q_values.argtypes = [vp, dp, dp, C.c_int32, dp]
     L.crl_ddpg_evaluate.argtypes = [vp, C.POINTER(CrlDDPGEvalConfig), C.POINTER(CrlDDPGEvalReport), dp, dp, dp, dp]
+    L.crl_td3_create.argtypes = [C.POINTER(CrlDDPGConfig), C.POINTER(CrlTD3Options), C.c_int32, C.POINTER(vp)]
+    L.crl_td3_write_params.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
+    L.crl_td3_read_params.argtypes = [vp, fp, fp, fp, fp, fp, fp]
+    L.crl_td3_init_params.argtypes = [vp, C.c_uint64]
+    L.crl_td3_q_values.argtypes = [vp, dp, dp, C.c_int32, dp, dp]
     L.crl_make_actor_critic.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t]
     L.crl_ppo_init_params.argtypes = [vp, C.c_uint64]
     L.crl_a2c_init_params.argtypes = [vp, C.c_uint64]
@@ -980,9 +991,12 @@ class DDPGHandle:
         self._L = load()
         self.cfg = cfg
         self._h = C.c_void_p()
-        check(self._L.crl_ddpg_create(C.byref(cfg), device, C.byref(self._h)))
+        self._create(device)
         self.obs_dim, self.act_dim = cfg.obs_dim, cfg.act_dim
         self.actor_n, self.critic_n = ddpg_param_count(cfg.obs_dim, cfg.act_dim)
+
+    def _create(self, device):
+        check(self._L.crl_ddpg_create(C.byref(self.cfg), device, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -1086,3 +1100,40 @@ class DDPGHandle:
         if trace is not None:
             out["trace_action"] = trace
         return out
+
+
+class TD3Handle(DDPGHandle):
+    """Owns one crl_ddpg* made by crl_td3_create (include/cleanrl_hip.h, TD3 block): run / act / observe / status / read_losses / buffer / actor /
+    q_values (critic 1) / evaluate are DDPGHandle's; the parameter calls are the crl_td3_* twins, with two critics."""
+
+    def __init__(self, cfg: CrlDDPGConfig, options: CrlTD3Options, device=0):
+        self.options = options
+        super().__init__(cfg, device)
+
+    def _create(self, device):
+        check(self._L.crl_td3_create(C.byref(self.cfg), None if self.options is None else C.byref(self.options), device, C.byref(self._h)))
+
+    def write_params(self, actor, critic1, critic2):
+        a, c1, c2 = (np.ascontiguousarray(x, np.float32) for x in (actor, critic1, critic2))
+        check(self._L.crl_td3_write_params(self._h, _ptr(a, C.c_float), a.size, _ptr(c1, C.c_float), c1.size, _ptr(c2, C.c_float), c2.size))
+
+    def init_params(self, seed=0):
+        check(self._L.crl_td3_init_params(self._h, seed))
+
+    def read_params(self):
+        """(actor, critic1, critic2, target_actor, target_critic1, target_critic2)"""
+        out = [np.zeros(n, np.float32) for n in (self.actor_n, self.critic_n, self.critic_n) * 2]
+        check(self._L.crl_td3_read_params(self._h, *[_ptr(o, C.c_float) for o in out]))
+        return tuple(out)
+
+    def q_values_both(self, obs, act):
+        """crl_td3_q_values: (Q_1, Q_2), each (n,), for (obs_dim, n), (act_dim, n)."""
+        obs = np.asfortranarray(obs, np.float64); act = np.asfortranarray(act, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        if act.ndim == 1:
+            act = act.reshape(self.act_dim, -1, order="F")
+        n = obs.shape[1]
+        q1, q2 = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        check(self._L.crl_td3_q_values(self._h, _ptr(obs, C.c_double), _ptr(act, C.c_double), n, _ptr(q1, C.c_double), _ptr(q2, C.c_double)))
+        return q1, q2

@@ -19,7 +19,8 @@
 //
 // Philox streams (counter = philox_env(seed, component, global_step, stream)): 0x10 behaviour noise (:79), 0x11 warm-up rand(act_space) (:79),
 // 0x12 target-actor noise (:108), 0x13 actor-loss noise (:123), 0x14 Pendulum reset in the loop (:100), 0x15 the first reset (:74), 0x16 the
-// resets of crl_ddpg_evaluate's private envs (no reference counterpart), 0xD9 the minibatch draw. A normal is Box–Muller in Float64 from the two
+// resets of crl_ddpg_evaluate's private envs (no reference counterpart), 0x17 TD3's target smoothing (per sample: component word 16·b + c), 0xD9 the
+// minibatch draw. A normal is Box–Muller in Float64 from the two
 // u53 halves of ONE Philox block: sqrt(−2·log(1 − u_xy))·cos(2π·u_zw).
 #include <hip/hip_runtime.h>
 
@@ -43,7 +44,7 @@ namespace crl {
 constexpr int GH = 64;                          // hidden width, ddpg.jl:24-25,31-32
 constexpr int DDPG_MAX_OBS = 64, DDPG_MAX_ACT = 16, DDPG_MAX_IN = DDPG_MAX_OBS + DDPG_MAX_ACT;
 constexpr int DDPG_MAX_EPS = 8192, DDPG_MAX_LOSSES = 4096, DDPG_MAX_BATCH = 1024, DDPG_MAX_CAP = 1 << 17;   // ring: reference default 1e5
-constexpr uint32_t S_BEHAVE = 0x10u, S_WARMUP = 0x11u, S_TARGET = 0x12u, S_ACTOR = 0x13u, S_RESET = 0x14u, S_RESET0 = 0x15u, S_EVAL = 0x16u;
+constexpr uint32_t S_BEHAVE = 0x10u, S_WARMUP = 0x11u, S_TARGET = 0x12u, S_ACTOR = 0x13u, S_RESET = 0x14u, S_RESET0 = 0x15u, S_EVAL = 0x16u, S_SMOOTH = 0x17u;
 
 // Dense(n_in, 64, ·) → Dense(64, 64, ·) → Dense(64, n_out, ·), flat in Flux.params order, (out,in) column-major
 struct NetOff { int W1, b1, W2, b2, W3, b3, N; };
@@ -256,6 +257,40 @@ __device__ __forceinline__ void ddpg_step_entry(double g, float* w, float* t, fl
   t[p] = (float)(tau * (double)wi + (1.0 - tau) * (double)t[p]);
 }
 
+// the gradient of critic parameter p from one critic pass's buffers: act = offset of its [k][64] blocks, row = offset of its [k] rows (both 0 for DDPG;
+// TD3's second critic sits one block further). Every loop is unrolled 30x as in dqn_wgrad_kernel: the operands were written by the launch before,
+// 30 loads in flight per round trip; the Float64 adds stay in sample order
+__device__ __forceinline__ double critic_param_grad(const DDPGDev& a, const NetOff& o, int NI, int k, int p, size_t act, size_t row) {
+#pragma clang fp contract(off)
+  const double *cH1 = a.cH1 + act, *cH2 = a.cH2 + act, *cD1 = a.cD1 + act, *cD2 = a.cD2 + act, *dz = a.dz + row;
+  double g = 0.0;
+  if (p < o.b1) {
+    const int i = p % GH, kk = p / GH;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += cD1[(size_t)GH * b + i] * a.X[(size_t)NI * b + kk];
+  } else if (p < o.W2) {
+    const int i = p - o.b1;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += cD1[(size_t)GH * b + i];
+  } else if (p < o.b2) {
+    const int r = p - o.W2, j = r % GH, kk = r / GH;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += cD2[(size_t)GH * b + j] * cH1[(size_t)GH * b + kk];
+  } else if (p < o.W3) {
+    const int j = p - o.b2;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += cD2[(size_t)GH * b + j];
+  } else if (p < o.b3) {
+    const int j = p - o.W3;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += dz[b] * cH2[(size_t)GH * b + j];
+  } else {
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) g += dz[b];
+  }
+  return g;
+}
+
 // C. critic gradient, Adam, polyak: one parameter per thread, samples in sample order
 __global__ void __launch_bounds__(64) ddpg_critic_step(DDPGDev a) {
 #pragma clang fp contract(off)
@@ -268,40 +303,13 @@ __global__ void __launch_bounds__(64) ddpg_critic_step(DDPGDev a) {
     a.ctl->critic_loss = loss / (double)k;
   }
   if (p >= o.N) return;
-  // every loop is unrolled 30x as in dqn_wgrad_kernel: the operands were written by the launch before, 30 loads in flight per round trip; the
-  // Float64 adds stay in sample order
-  double g = 0.0;
-  if (p < o.b1) {
-    const int i = p % GH, kk = p / GH;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.cD1[(size_t)GH * b + i] * a.X[(size_t)NI * b + kk];
-  } else if (p < o.W2) {
-    const int i = p - o.b1;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.cD1[(size_t)GH * b + i];
-  } else if (p < o.b2) {
-    const int r = p - o.W2, j = r % GH, kk = r / GH;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.cD2[(size_t)GH * b + j] * a.cH1[(size_t)GH * b + kk];
-  } else if (p < o.W3) {
-    const int j = p - o.b2;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.cD2[(size_t)GH * b + j];
-  } else if (p < o.b3) {
-    const int j = p - o.W3;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.dz[b] * a.cH2[(size_t)GH * b + j];
-  } else {
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.dz[b];
-  }
+  const double g = critic_param_grad(a, o, NI, k, p, 0, 0);
   ddpg_step_entry(g, a.critic, a.critic_t, a.mc, a.vc, a.betap + 2 * (6 + net_array(o, p)), a.cfg.lr, a.cfg.tau, p);
 }
 
 // D. ddpg.jl:122-124 for sample blockIdx.x: −mean(get_q(critic, state, actor(state))) through the updated critic, gradient w.r.t. the actor
-__global__ void __launch_bounds__(64) ddpg_actor_kernel(DDPGDev a) {
+__device__ __forceinline__ void ddpg_actor_pass(const DDPGDev& a) {
 #pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT], qs, ds[GH], d3s[DDPG_MAX_ACT];
   const int lane = threadIdx.x, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
   const uint64_t gstep = (uint64_t)a.ctl->global_step;
@@ -346,12 +354,15 @@ __global__ void __launch_bounds__(64) ddpg_actor_kernel(DDPGDev a) {
   a.aH1[r] = ah1; a.aH2[r] = ah2; a.aD1[r] = d1; a.aD2[r] = d2;
   if (lane == 0) a.Qa[b] = q;
 }
-
-// E. actor gradient, Adam, polyak
-__global__ void __launch_bounds__(64) ddpg_actor_step(DDPGDev a) {
-#pragma clang fp contract(off)
+__global__ void __launch_bounds__(64) ddpg_actor_kernel(DDPGDev a) {
   if (!a.ctl->train_pending) return;
-  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, p = blockIdx.x * 64 + threadIdx.x;
+  ddpg_actor_pass(a);
+}
+
+// E. actor gradient, Adam, polyak for actor parameter p (p >= the actor's size: only p = 0's loss)
+__device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
+#pragma clang fp contract(off)
+  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
   const NetOff o = net_off(D, A);
   if (p == 0) {                                                                        // actor_loss = −mean(Q) (:123)
     double sum = 0.0;
@@ -387,6 +398,10 @@ __global__ void __launch_bounds__(64) ddpg_actor_step(DDPGDev a) {
   }
   ddpg_step_entry(g, a.actor, a.actor_t, a.ma, a.va, a.betap + 2 * net_array(o, p), a.cfg.lr, a.cfg.tau, p);
 }
+__global__ void __launch_bounds__(64) ddpg_actor_step(DDPGDev a) {
+  if (!a.ctl->train_pending) return;
+  ddpg_actor_step_entry(a, blockIdx.x * 64 + threadIdx.x);
+}
 
 // ddpg.jl:79 for step `gstep` on one wave: act[0..A) = rand(act_space) while gstep <= warmup_steps, else actor(obs) with its noise. obs in xs (LDS).
 __device__ __forceinline__ void ddpg_select_action(const DDPGDev& a, uint64_t gstep, const double* xs, double* h1s, double* h2s, double* ys, double* act,
@@ -419,7 +434,8 @@ __device__ __forceinline__ void ddpg_finish_update(const DDPGDev& a, DDPGCtl& c,
 }
 
 // F. close the pending update, then ddpg.jl:77-105 on the Pendulum until an update is due, the budget or total_timesteps is used up
-__global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
+template <class Finish>
+__device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish) {
 #pragma clang fp contract(off)
   __shared__ DDPGCtl c;
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT], act[DDPG_MAX_ACT];
@@ -427,7 +443,7 @@ __global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
   const int lane = threadIdx.x;
   if (lane == 0) c = *a.ctl;
   __syncthreads();
-  if (c.train_pending) ddpg_finish_update(a, c, lane);
+  if (c.train_pending) finish(c, lane);
   __syncthreads();
   while (a.cfg.env_kind == CRL_DDPG_ENV_PENDULUM) {
     if (lane == 0) {
@@ -464,6 +480,129 @@ __global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
     __syncthreads();
   }
   if (lane == 0) *a.ctl = c;
+}
+__global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
+  ddpg_collect(a, [&a](DDPGCtl& c, int lane) { ddpg_finish_update(a, c, lane); });
+}
+
+// ------------------------------------------------------------------------------------------------------
+// TD3 (the crl_td3_* block of include/cleanrl_hip.h) on the DDPG handle: the same six launches, the same ring, draw, env loop and act / observe
+// kernels. A TD3 handle's critic, critic_t, mc and vc hold [2][nc] floats (critic 1 first, so every DDPG kernel that reads a.critic reads critic 1),
+// its cH1 / cH2 / cD1 / cD2 hold [2][k][64], dz / sq [2][k], betap [18][2]: the actor's six arrays, critic 1's, critic 2's. X is stored once.
+//   A  ddpg_sample_kernel  unchanged
+//   B' td3_critic_kernel   one block per sample, two waves, wave w = critic w: target actor + smoothing noise (both waves, each into its own LDS),
+//                          target critic w, min of the two through LDS, then forward and backward of online critic w on the shared TD target
+//   C' td3_critic_step     one thread per parameter of the 2·nc: gradient in sample order, Adam; no polyak
+//   D' td3_actor_kernel    ddpg_actor_pass (critic 1, no noise: noise_in_update is 0 on a TD3 handle) when the actor is due
+//   E' td3_actor_step      when the actor is due: ddpg_actor_step_entry (gradient, Adam, polyak) in the first blocks, polyak of both critics in the rest
+//   F' td3_collect_kernel  ddpg_collect with TD3's close: 18 β-power pairs, the actor's six only when it stepped
+// "The actor is due" is global_step % policy_delay == 0: global_step is the control block's and no kernel of A–E' writes it, so every block of a
+// cycle takes the same decision (it is the flag a cycle would otherwise carry next to train_pending, derived instead of stored).
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool td3_actor_due(const DDPGCtl* c, const crl_td3_options& o) { return c->global_step % (int64_t)o.policy_delay == 0; }
+
+// B'. Every barrier below is reached by both waves: the one exit is the block-uniform one at the top, and both waves take every call alike.
+__global__ void __launch_bounds__(128) td3_critic_kernel(DDPGDev a, crl_td3_options opt) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  __shared__ double xs[2][DDPG_MAX_IN], h1s[2][GH], h2s[2][GH], ys[2][DDPG_MAX_ACT], qs[2], d2s[2][GH];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const uint64_t gstep = (uint64_t)a.ctl->global_step;
+  const size_t s = (size_t)a.idx[b];
+  const NetOff o = net_off(NI, 1);
+  const float* const critic = a.critic + (size_t)w * o.N;
+  const float* const critic_t = a.critic_t + (size_t)w * o.N;
+  double h1, h2;
+  for (int i = lane; i < D; i += GH) xs[w][i] = a.rb_next[D * s + i];
+  __syncthreads();
+  actor_forward(a.actor_t, D, A, xs[w], h1s[w], h2s[w], ys[w], lane, h1, h2);
+  if (lane < A) {
+    // target policy smoothing: a per-SAMPLE draw, component word 16·b + c
+    const double z = ddpg_normal(a.cfg.seed, (uint32_t)(16 * b + lane), gstep, S_SMOOTH);
+    const double nz0 = opt.policy_noise * z;
+    const double nz = nz0 < -opt.noise_clip ? -opt.noise_clip : (nz0 > opt.noise_clip ? opt.noise_clip : nz0);
+    const double a0 = ys[w][lane] * 2.0 + nz;
+    xs[w][D + lane] = a0 < a.cfg.act_low ? a.cfg.act_low : (a0 > a.cfg.act_high ? a.cfg.act_high : a0);
+  }
+  __syncthreads();
+  critic_forward(critic_t, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, h1, h2);       // its last barrier publishes both qs
+  const double q1 = qs[0], q2 = qs[1];
+  const double next_q = q2 < q1 ? q2 : q1;
+  const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
+  __syncthreads();
+  for (int i = lane; i < NI; i += GH) {
+    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
+    xs[w][i] = v;
+    if (w == 0) a.X[(size_t)NI * b + i] = v;
+  }
+  __syncthreads();
+  const double q = critic_forward(critic, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, h1, h2);
+  const double diff = td - q;
+  const double dq = -2.0 * diff / (double)k;
+  const double d2 = h2 > 0.0 ? (double)critic[o.W3 + lane] * dq : 0.0;
+  d2s[w][lane] = d2;
+  __syncthreads();
+  const double t1 = w2t_row(critic + o.W2, d2s[w], lane);
+  const double d1 = h1 > 0.0 ? t1 : 0.0;
+  const size_t r = (size_t)GH * ((size_t)w * k + b) + lane;
+  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
+  if (lane == 0) { a.sq[(size_t)w * k + b] = diff * diff; a.dz[(size_t)w * k + b] = dq; }
+}
+
+// C'. thread p: parameter p % nc of critic p / nc. critic_loss = loss_1 + loss_2
+__global__ void __launch_bounds__(64) td3_critic_step(DDPGDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, NI = a.cfg.obs_dim + a.cfg.act_dim, t = blockIdx.x * 64 + threadIdx.x;
+  const NetOff o = net_off(NI, 1);
+  if (t == 0) {
+    double l1 = 0.0, l2 = 0.0;
+    for (int b = 0; b < k; ++b) l1 += a.sq[b];
+    for (int b = 0; b < k; ++b) l2 += a.sq[(size_t)k + b];
+    a.ctl->critic_loss = l1 / (double)k + l2 / (double)k;
+  }
+  if (t >= 2 * o.N) return;
+  const int w = t / o.N, p = t - w * o.N;
+  const double g = critic_param_grad(a, o, NI, k, p, (size_t)w * k * GH, (size_t)w * k);
+  const double* bp = a.betap + 2 * (6 + 6 * w + net_array(o, p));
+  float mi, vi, wi;
+  adam_entry((double)(float)g, a.mc[t], a.vc[t], a.critic[t], bp[0], bp[1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, wi);
+  a.mc[t] = mi; a.vc[t] = vi; a.critic[t] = wi;
+}
+
+// D'.
+__global__ void __launch_bounds__(64) td3_actor_kernel(DDPGDev a, crl_td3_options opt) {
+  if (!a.ctl->train_pending || !td3_actor_due(a.ctl, opt)) return;
+  ddpg_actor_pass(a);
+}
+
+// E'. blocks 0..actor_blocks−1: the actor; the blocks after them: polyak_update! of the 2·nc critic elements (the critics stepped in C')
+__global__ void __launch_bounds__(64) td3_actor_step(DDPGDev a, crl_td3_options opt, int actor_blocks, int nc2) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending || !td3_actor_due(a.ctl, opt)) return;
+  if ((int)blockIdx.x < actor_blocks) { ddpg_actor_step_entry(a, blockIdx.x * 64 + threadIdx.x); return; }
+  const int t = ((int)blockIdx.x - actor_blocks) * 64 + threadIdx.x;
+  if (t < nc2) a.critic_t[t] = (float)(a.cfg.tau * (double)a.critic[t] + (1.0 - a.cfg.tau) * (double)a.critic_t[t]);
+}
+
+// closes a TD3 update: critic β powers always, the actor's only when it stepped; the rest is ddpg_finish_update's
+__device__ __forceinline__ void td3_finish_update(const DDPGDev& a, const crl_td3_options& opt, DDPGCtl& c, int lane) {
+  const bool due = td3_actor_due(&c, opt);
+  if (lane < 18 && (lane >= 6 || due)) betap_advance(a.betap, lane, a.betap[2 * lane], a.betap[2 * lane + 1]);
+  if (lane == 0) {
+    c.n_updates += 1;
+    if (c.global_step % a.cfg.log_frequency == 0) {
+      if (c.n_losses < DDPG_MAX_LOSSES) {
+        a.losses[c.n_losses].global_step = c.global_step; a.losses[c.n_losses].actor_loss = c.actor_loss; a.losses[c.n_losses].critic_loss = c.critic_loss;
+      }
+      c.n_losses += 1;
+    }
+    c.train_pending = 0;
+  }
+}
+// F'.
+__global__ void __launch_bounds__(64) td3_collect_kernel(DDPGDev a, crl_td3_options opt) {
+  ddpg_collect(a, [&a, &opt](DDPGCtl& c, int lane) { td3_finish_update(a, opt, c, lane); });
 }
 
 // host-driven env: the action of step global_step + 1 for the staged observation (advances nothing)
@@ -612,6 +751,8 @@ struct crl_ddpg {
   bool params_set = false;       // ddpg.jl:52 has happened (a fresh handle holds zeros)
   int64_t host_step = 0;         // global_step as of the last call (the schedule of ddpg.jl:105 is deterministic)
   int na = 0, nc = 0;
+  bool td3 = false;              // created by crl_td3_create: two critics ([2][nc] in d.critic / critic_t / mc / vc), the TD3 cycle
+  crl_td3_options topt{};
   hipStream_t stream = nullptr;
   crl::DDPGDev d;
   double* pinned = nullptr;      // external env: the staging slot's host side
@@ -631,13 +772,26 @@ static int galloc(T** p, size_t n) {
   return 0;
 }
 
-// launches A–E of one cycle
-static void enqueue_update(hipStream_t st, const DDPGDev& d, int k, int na, int nc) {
+// one cycle: launches A–E, then the collect launch F (which closes the update and, on a Pendulum handle, steps the env)
+static void enqueue_cycle(const crl_ddpg* h) {
+  hipStream_t st = h->stream;
+  const DDPGDev& d = h->d;
+  const int k = (int)h->cfg.batch_size, na = h->na, nc = h->nc;
   hipLaunchKernelGGL(ddpg_sample_kernel, dim3(1), dim3(1024), 0, st, d);
+  if (h->td3) {
+    const int ab = (na + 63) / 64;
+    hipLaunchKernelGGL(td3_critic_kernel, dim3(k), dim3(128), 0, st, d, h->topt);
+    hipLaunchKernelGGL(td3_critic_step, dim3((2 * nc + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(td3_actor_kernel, dim3(k), dim3(64), 0, st, d, h->topt);
+    hipLaunchKernelGGL(td3_actor_step, dim3(ab + (2 * nc + 63) / 64), dim3(64), 0, st, d, h->topt, ab, 2 * nc);
+    hipLaunchKernelGGL(td3_collect_kernel, dim3(1), dim3(64), 0, st, d, h->topt);
+    return;
+  }
   hipLaunchKernelGGL(ddpg_critic_kernel, dim3(k), dim3(64), 0, st, d);
   hipLaunchKernelGGL(ddpg_critic_step, dim3((nc + 63) / 64), dim3(64), 0, st, d);
   hipLaunchKernelGGL(ddpg_actor_kernel, dim3(k), dim3(64), 0, st, d);
   hipLaunchKernelGGL(ddpg_actor_step, dim3((na + 63) / 64), dim3(64), 0, st, d);
+  hipLaunchKernelGGL(ddpg_collect_kernel, dim3(1), dim3(64), 0, st, d);
 }
 
 static int ddpg_scratch(crl_ddpg* h, size_t need) {
@@ -659,9 +813,10 @@ int32_t crl_ddpg_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n,
   return 0;
 }
 
-int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** out) {
-  if (!cfg || !out) { set_error("crl_ddpg_create: null argument"); return 1; }
-  *out = nullptr;
+}  // extern "C"
+
+// crl_ddpg_create (topt = nullptr) and crl_td3_create: a TD3 handle holds two critics and two critic passes' buffers where a DDPG handle holds one
+static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* topt, int32_t device, crl_ddpg** out) {
   if (cfg->obs_dim < 1 || cfg->obs_dim > DDPG_MAX_OBS) { set_error("crl_ddpg_create: obs_dim must be in 1..64"); return 1; }
   if (cfg->act_dim < 1 || cfg->act_dim > DDPG_MAX_ACT) { set_error("crl_ddpg_create: act_dim must be in 1..16"); return 1; }
   if (cfg->env_kind != CRL_DDPG_ENV_PENDULUM && cfg->env_kind != CRL_DDPG_ENV_EXTERNAL) { set_error("crl_ddpg_create: env_kind must be CRL_DDPG_ENV_PENDULUM or CRL_DDPG_ENV_EXTERNAL"); return 1; }
@@ -684,6 +839,8 @@ int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** o
   crl_ddpg* h = new (std::nothrow) crl_ddpg();
   if (!h) { set_error("out of host memory"); return 1; }
   h->cfg = *cfg; h->device = device;
+  if (topt) { h->td3 = true; h->topt = *topt; }
+  const size_t Q = topt ? 2 : 1;   // critics
   memset(&h->d, 0, sizeof(h->d));
   h->d.cfg = *cfg;
   hipError_t se = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -694,12 +851,12 @@ int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** o
   DDPGDev& d = h->d;
   int rc = 0;
   rc |= galloc(&d.actor, na); rc |= galloc(&d.actor_t, na); rc |= galloc(&d.ma, na); rc |= galloc(&d.va, na);
-  rc |= galloc(&d.critic, nc); rc |= galloc(&d.critic_t, nc); rc |= galloc(&d.mc, nc); rc |= galloc(&d.vc, nc);
-  rc |= galloc(&d.betap, 24); rc |= galloc(&d.ctl, 1); rc |= galloc(&d.eps, DDPG_MAX_EPS); rc |= galloc(&d.losses, DDPG_MAX_LOSSES);
+  rc |= galloc(&d.critic, Q * nc); rc |= galloc(&d.critic_t, Q * nc); rc |= galloc(&d.mc, Q * nc); rc |= galloc(&d.vc, Q * nc);
+  rc |= galloc(&d.betap, 12 * (Q + 1)); rc |= galloc(&d.ctl, 1); rc |= galloc(&d.eps, DDPG_MAX_EPS); rc |= galloc(&d.losses, DDPG_MAX_LOSSES);
   rc |= galloc(&d.rb_state, cap * D); rc |= galloc(&d.rb_next, cap * D); rc |= galloc(&d.rb_action, cap * A); rc |= galloc(&d.rb_reward, cap);
   rc |= galloc(&d.rb_terminal, cap); rc |= galloc(&d.idx, k);
-  rc |= galloc(&d.X, k * (D + A)); rc |= galloc(&d.cH1, k * GH); rc |= galloc(&d.cH2, k * GH); rc |= galloc(&d.cD1, k * GH); rc |= galloc(&d.cD2, k * GH);
-  rc |= galloc(&d.dz, k); rc |= galloc(&d.sq, k);
+  rc |= galloc(&d.X, k * (D + A)); rc |= galloc(&d.cH1, Q * k * GH); rc |= galloc(&d.cH2, Q * k * GH);
+  rc |= galloc(&d.cD1, Q * k * GH); rc |= galloc(&d.cD2, Q * k * GH); rc |= galloc(&d.dz, Q * k); rc |= galloc(&d.sq, Q * k);
   rc |= galloc(&d.aH1, k * GH); rc |= galloc(&d.aH2, k * GH); rc |= galloc(&d.aD1, k * GH); rc |= galloc(&d.aD2, k * GH);
   rc |= galloc(&d.aY, k * A); rc |= galloc(&d.aD3, k * A); rc |= galloc(&d.Qa, k);
   rc |= galloc(&d.stage, 2 * D + 2 * A + 2);
@@ -707,13 +864,41 @@ int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** o
     set_error("crl_ddpg_create: hipHostMalloc failed"); h->pinned = nullptr; rc = 1;
   }
   if (rc) { crl_ddpg_destroy(h); return 1; }
-  double bp[24];
-  for (int i = 0; i < 12; ++i) { bp[2 * i] = ADAM_B1; bp[2 * i + 1] = ADAM_B2; }
-  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, sizeof(bp), hipMemcpyHostToDevice));
+  double bp[36];
+  for (int i = 0; i < 18; ++i) { bp[2 * i] = ADAM_B1; bp[2 * i + 1] = ADAM_B2; }
+  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, 12 * (Q + 1) * sizeof(double), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(ddpg_init_kernel, dim3(1), dim3(1), 0, h->stream, d);
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   *out = h;
   return 0;
+}
+
+// the DDPG parameter calls know one critic, the crl_td3_* ones two: each refuses the other kind of handle and names its twin
+static bool wrong_kind(const crl_ddpg* h, bool want_td3, const char* fn, const char* twin) {
+  if (h->td3 == want_td3) return false;
+  set_error(std::string(fn) + (want_td3 ? ": this is a DDPG handle (crl_ddpg_create) — use " : ": this is a TD3 handle (crl_td3_create) — use ") + twin);
+  return true;
+}
+
+extern "C" {
+
+int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** out) {
+  if (!cfg || !out) { set_error("crl_ddpg_create: null argument"); return 1; }
+  *out = nullptr;
+  return ddpg_create(cfg, nullptr, device, out);
+}
+
+int32_t crl_td3_create(const crl_ddpg_config* cfg, const crl_td3_options* opt, int32_t device, crl_ddpg** out) {
+  if (!cfg || !out) { set_error("crl_td3_create: null argument"); return 1; }
+  *out = nullptr;
+  if (!opt) { set_error("crl_td3_create: options must not be NULL (crl_td3_options: policy_delay, policy_noise, noise_clip)"); return 1; }
+  if (opt->policy_delay < 1) { set_error("crl_td3_create: policy_delay must be >= 1"); return 1; }
+  if (!(opt->policy_noise >= 0.0)) { set_error("crl_td3_create: policy_noise must be >= 0"); return 1; }
+  if (!(opt->noise_clip >= 0.0)) { set_error("crl_td3_create: noise_clip must be >= 0"); return 1; }
+  if (cfg->noise_in_update != 0) {
+    set_error("crl_td3_create: noise_in_update must be 0 (TD3 has its own target noise, policy_noise / noise_clip, and none in the actor loss)"); return 1;
+  }
+  return ddpg_create(cfg, opt, device, out);
 }
 
 int32_t crl_ddpg_destroy(crl_ddpg* h) {
@@ -733,6 +918,7 @@ int32_t crl_ddpg_destroy(crl_ddpg* h) {
 
 int32_t crl_ddpg_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic, size_t critic_n) {
   DDPG_GUARD(h);
+  if (wrong_kind(h, false, "crl_ddpg_write_params", "crl_td3_write_params")) return 1;
   if (!actor || !critic || actor_n != (size_t)h->na || critic_n != (size_t)h->nc) {
     set_error("crl_ddpg_write_params: expected " + std::to_string(h->na) + " actor and " + std::to_string(h->nc) + " critic floats"); return 1;
   }
@@ -746,12 +932,14 @@ int32_t crl_ddpg_write_params(crl_ddpg* h, const float* actor, size_t actor_n, c
 }
 int32_t crl_ddpg_init_params(crl_ddpg* h, uint64_t seed) {
   DDPG_GUARD(h);
+  if (wrong_kind(h, false, "crl_ddpg_init_params", "crl_td3_init_params")) return 1;
   std::vector<float> wa((size_t)h->na), wc((size_t)h->nc);
   if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed, wa.data(), wa.size(), wc.data(), wc.size())) return 1;
   return crl_ddpg_write_params(h, wa.data(), wa.size(), wc.data(), wc.size());
 }
 int32_t crl_ddpg_read_params(crl_ddpg* h, float* actor, float* critic, float* target_actor, float* target_critic) {
   DDPG_GUARD(h);
+  if (wrong_kind(h, false, "crl_ddpg_read_params", "crl_td3_read_params")) return 1;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, (size_t)h->na * 4, hipMemcpyDeviceToHost));
   if (critic) CRL_HIP_CHECK(hipMemcpy(critic, h->d.critic, (size_t)h->nc * 4, hipMemcpyDeviceToHost));
@@ -800,7 +988,6 @@ int32_t crl_ddpg_run(crl_ddpg* h, int64_t max_env_steps, crl_ddpg_episode* eps, 
   if (max_env_steps <= 0) return 0;
   const DDPGDev& d = h->d;
   hipStream_t st = h->stream;
-  const int k = (int)h->cfg.batch_size;
   // steps this call can take; the ones up to max(min_buff_size, warmup_steps) run inside ONE collect launch, every later one is a cycle of its own,
   // and one more cycle closes the last update
   const int64_t left = h->cfg.total_timesteps - h->host_step;
@@ -810,8 +997,7 @@ int32_t crl_ddpg_run(crl_ddpg* h, int64_t max_env_steps, crl_ddpg_episode* eps, 
   const int64_t cycles = (limit > quiet ? limit - quiet : 0) + 2;
   hipLaunchKernelGGL(ddpg_begin_kernel, dim3(1), dim3(1), 0, st, d, max_env_steps);
   for (int64_t cy = 0; cy < cycles; ++cy) {
-    enqueue_update(st, d, k, h->na, h->nc);
-    hipLaunchKernelGGL(ddpg_collect_kernel, dim3(1), dim3(64), 0, st, d);
+    enqueue_cycle(h);
     if ((cy & 4095) == 4095) CRL_HIP_CHECK(hipStreamSynchronize(st));   // bound the queue depth of very long calls
   }
   CRL_HIP_CHECK(hipGetLastError());
@@ -857,8 +1043,7 @@ int32_t crl_ddpg_observe(crl_ddpg* h, const double* obs, const double* action, d
   hipLaunchKernelGGL(ddpg_add_kernel, dim3(1), dim3(64), 0, h->stream, h->d);
   h->host_step += 1;
   if (h->host_step > h->cfg.min_buff_size && h->host_step > h->cfg.warmup_steps) {    // ddpg.jl:105 (the kernels check train_pending themselves)
-    enqueue_update(h->stream, h->d, (int)h->cfg.batch_size, h->na, h->nc);
-    hipLaunchKernelGGL(ddpg_collect_kernel, dim3(1), dim3(64), 0, h->stream, h->d);   // external: closes the update only
+    enqueue_cycle(h);                                                                  // external: the collect launch closes the update only
   }
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
@@ -909,11 +1094,10 @@ int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out) {
   return 0;
 }
 
-int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out) {
-  DDPG_GUARD(h);
-  if (!h->params_set) { set_error("crl_ddpg_q_values: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
-  if (n < 0 || (n > 0 && (!obs || !act || !out))) { set_error("crl_ddpg_q_values: bad arguments"); return 1; }
-  if (n == 0) return 0;
+}  // extern "C"
+
+// get_q of critic `which` (0; 1 on a TD3 handle) for n staged pairs
+static int32_t ddpg_q_eval(crl_ddpg* h, int which, const double* obs, const double* act, int32_t n, double* out) {
   const size_t N = (size_t)n, D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
   if (ddpg_scratch(h, N * (D + A + 1) * 8)) return 1;
   double* so = static_cast<double*>(h->scratch);
@@ -921,10 +1105,73 @@ int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int
   double* sq = sa + N * A;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * D * 8, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(sa, act, N * A * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(ddpg_q_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, sa, n, sq);
+  DDPGDev d = h->d;
+  d.critic += (size_t)which * (size_t)h->nc;
+  hipLaunchKernelGGL(ddpg_q_eval_kernel, dim3(n), dim3(64), 0, h->stream, d, so, sa, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(out, sq, N * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" {
+
+int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out) {
+  DDPG_GUARD(h);
+  if (!h->params_set) { set_error("crl_ddpg_q_values: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !act || !out))) { set_error("crl_ddpg_q_values: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  return ddpg_q_eval(h, 0, obs, act, n, out);
+}
+
+int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, true, "crl_td3_q_values", "crl_ddpg_q_values")) return 1;
+  if (!h->params_set) { set_error("crl_td3_q_values: parameters not set — crl_td3_write_params or crl_td3_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !act))) { set_error("crl_td3_q_values: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  if (q1 && ddpg_q_eval(h, 0, obs, act, n, q1)) return 1;
+  if (q2 && ddpg_q_eval(h, 1, obs, act, n, q2)) return 1;
+  return 0;
+}
+
+int32_t crl_td3_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n, const float* critic2,
+                             size_t critic2_n) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, true, "crl_td3_write_params", "crl_ddpg_write_params")) return 1;
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
+    set_error("crl_td3_write_params: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
+  }
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  for (float* dst : {h->d.actor, h->d.actor_t}) CRL_HIP_CHECK(hipMemcpy(dst, actor, na * 4, hipMemcpyHostToDevice));
+  for (float* dst : {h->d.critic, h->d.critic_t}) {                                       // the targets are copies, as ddpg.jl:53-54
+    CRL_HIP_CHECK(hipMemcpy(dst, critic1, nc * 4, hipMemcpyHostToDevice));
+    CRL_HIP_CHECK(hipMemcpy(dst + nc, critic2, nc * 4, hipMemcpyHostToDevice));
+  }
+  h->params_set = true;
+  return 0;
+}
+int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, true, "crl_td3_init_params", "crl_ddpg_init_params")) return 1;
+  std::vector<float> wa((size_t)h->na), wc1((size_t)h->nc), wa2((size_t)h->na), wc2((size_t)h->nc);
+  if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed, wa.data(), wa.size(), wc1.data(), wc1.size())) return 1;
+  if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed + 1, wa2.data(), wa2.size(), wc2.data(), wc2.size())) return 1;   // its actor is dropped
+  return crl_td3_write_params(h, wa.data(), wa.size(), wc1.data(), wc1.size(), wc2.data(), wc2.size());
+}
+int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* target_actor, float* target_critic1,
+                            float* target_critic2) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, true, "crl_td3_read_params", "crl_ddpg_read_params")) return 1;
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
+  if (critic1) CRL_HIP_CHECK(hipMemcpy(critic1, h->d.critic, nc * 4, hipMemcpyDeviceToHost));
+  if (critic2) CRL_HIP_CHECK(hipMemcpy(critic2, h->d.critic + nc, nc * 4, hipMemcpyDeviceToHost));
+  if (target_actor) CRL_HIP_CHECK(hipMemcpy(target_actor, h->d.actor_t, na * 4, hipMemcpyDeviceToHost));
+  if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
+  if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

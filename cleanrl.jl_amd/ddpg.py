@@ -139,7 +139,8 @@ def ddpg_evaluate(agent, *, num_envs=256, episodes_per_env=1, seed=EVAL_SEED, tr
     than the policy collects — plus "trace_action" (trace_steps, num_envs), the actions of each env's first trace_steps steps, when trace_steps > 0.
     `env=<host env object>` (the protocol of ddpg(config, env)) serves an agent whose env lives in this process: a host loop over the handle's
     noise-free actor, episode after episode until `terminal`, through the same report; num_envs is then 1 (leave it alone), and seed / trace_steps
-    belong to the on-device envs and are refused. Arguments are validated here, before the library is touched."""
+    belong to the on-device envs and are refused. Arguments are validated here, before the library is touched. A TD3Agent (td3.py) is served alike:
+    its q0 is critic 1's."""
     if not isinstance(agent, DDPGAgent):
         raise TypeError("ddpg_evaluate: agent must be a cleanrl_jl_amd DDPGAgent (PPO agents: evaluate)")
     if env is not None:
@@ -170,21 +171,28 @@ def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, pa
     every step that is a multiple of N: ddpg_evaluate of the parameters that step left, on eval_envs fresh Pendulums x eval_episodes episodes (the
     library calls are cut at multiples of N; chunking changes no bit of the run) or, with a host env, eval_episodes episodes on `eval_env`, a SECOND
     env object — the training env is in the middle of an episode. 0 (default) keeps the record stream what it was."""
+    return _loop("ddpg", lambda config, **kw: DDPGAgent(config, noise_in_update=noise_in_update, **kw), config or DDPGConfig(), env, device=device,
+                 seed=seed, params=params, chunk=chunk, eval_every=eval_every, eval_envs=eval_envs, eval_episodes=eval_episodes, eval_env=eval_env,
+                 **logger_kw)
+
+
+def _loop(who, make_agent, config, env, *, device, seed, params, chunk, eval_every, eval_envs, eval_episodes, eval_env, **logger_kw):
+    """The loop of ddpg() for any agent on a crl_ddpg handle (td3() runs it too): make_agent(config, device=, seed=, params=[, obs_dim=, act_dim=,
+    act_low=, act_high=, external=True]) builds it; `who` names the caller in messages and in the logger's run name."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
-        raise ValueError(f"ddpg: eval_every must be an integer >= 0, got {eval_every!r}")
+        raise ValueError(f"{who}: eval_every must be an integer >= 0, got {eval_every!r}")
     host_env = not isinstance(env, str)
     if eval_every:
         if host_env and (eval_env is None or isinstance(eval_env, str) or eval_env is env):
-            raise ValueError("ddpg: eval_every with a host env needs eval_env, a second env object (evaluating on the training env would break its episode)")
-        _check_eval_args("ddpg", 1 if host_env else eval_envs, eval_episodes, EVAL_SEED, 0, 1)
-    config = config or DDPGConfig()
-    Logger.make_logger(f"ddpg|{config.run_name}", **({"to_terminal": False} | logger_kw))        # ddpg.jl:48
+            raise ValueError(f"{who}: eval_every with a host env needs eval_env, a second env object (evaluating on the training env would break its episode)")
+        _check_eval_args(who, 1 if host_env else eval_envs, eval_episodes, EVAL_SEED, 0, 1)
+    Logger.make_logger(f"{who}|{config.run_name}", **({"to_terminal": False} | logger_kw))        # ddpg.jl:48
     lg = logging.getLogger("CleanRL")
     start = time.time()
     if not host_env:
         if env != "pendulum":
-            raise ValueError(f"ddpg: the only built-in env is 'pendulum', got {env!r}")
-        agent = DDPGAgent(config, device=device, seed=seed, params=params, noise_in_update=noise_in_update)
+            raise ValueError(f"{who}: the only built-in env is 'pendulum', got {env!r}")
+        agent = make_agent(config, device=device, seed=seed, params=params)
         global_step = 0
         while True:
             budget = min(chunk, eval_every - global_step % eval_every) if eval_every else chunk
@@ -199,8 +207,8 @@ def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, pa
             if taken == 0 or global_step >= config.total_timesteps:
                 break
         return agent
-    agent = DDPGAgent(config, obs_dim=env.obs_dim, act_dim=env.act_dim, act_low=env.act_low, act_high=env.act_high, external=True, device=device,
-                      seed=seed, params=params, noise_in_update=noise_in_update)
+    agent = make_agent(config, obs_dim=env.obs_dim, act_dim=env.act_dim, act_low=env.act_low, act_high=env.act_high, external=True, device=device,
+                       seed=seed, params=params)
     h = agent.handle
     episode_return, episode_length = 0.0, 0
     obs = np.asarray(env.reset(), np.float64)                                                    # ddpg.jl:74

@@ -690,6 +690,44 @@ typedef struct crl_ddpg_eval_report { int64_t episodes, env_steps;
 int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg_eval_report* report,
                           double* returns, double* disc_returns, double* q0, double* trace_action);
 
+/* =====================================================================================================
+ * TD3 (Fujimoto et al. 2018) on the DDPG handle — no reference counterpart (the reference's README lists SAC and Rainbow as to-dos, no TD3). The
+ * networks, the ring, the minibatch draw (stream 0xD9), the behaviour policy (one draw per call on stream 0x10, scaled by exploration_noise,
+ * unclipped), the warm-up (rand(act_space), stream 0x11), the Pendulum, the host-driven mode, the records and the arithmetic conventions are
+ * DDPG's: Float32 weights, Float64 arithmetic, contraction off wherever a sum is formed, dot products in input order with the bias last, sums over
+ * the batch in sample order, gradients projected to Float32 before Adam. There are two critics of the DDPG critic's shape, each with its target,
+ * its Adam(lr) state and its six β-power pairs. An update is due at step g exactly when DDPG's is (g > min_buff_size && g > warmup_steps). With
+ * k = batch_size and the batch positions b = 0..k−1 of the draw:
+ *   target action  a'[c] = clamp(2·tanh_fast(target_actor head)[c] + clamp(policy_noise·z(b, c), −noise_clip, +noise_clip), act_low, act_high), z(b, c)
+ *                  = the Box–Muller normal of the DDPG block on Philox stream 0x17 ("target smoothing") at gstep = g, component word 16·b + c: one
+ *                  draw per SAMPLE and component (not ddpg.jl:28's one draw per call). clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x).
+ *   TD target      next_q = q2 < q1 ? q2 : q1 of target critic 1 / 2 on (next_state, a'); td = r + γ·next_q·(1 − terminal).
+ *   critics        critic i takes mse(td, Q_i(s, a)) = Σ_b (td − q_i)² / k with its own gradient, Adam state and β powers; both step on every update.
+ *                  The logged critic_loss is loss_1 + loss_2.
+ *   actor          exactly when g % policy_delay == 0: −mean(Q_1(s, 2·tanh_fast(actor(s)))) through the UPDATED critic 1, no noise, Adam on the actor,
+ *                  then polyak (tau) of the target actor and of both target critics — the targets move on those steps only, and the actor's β
+ *                  powers advance on those steps only. actor_loss (status and records) is the value of the latest actor step, 0.0 before the first.
+ * policy_delay = 1, policy_noise = 0, critic 2 = critic 1 and bounds that contain ±2 make every number DDPG's with noise_in_update = 0, bit for
+ * bit (critic_loss = 2×). One cycle stays six launches (csrc/ddpg.hip): sample, td3_critic_kernel, td3_critic_step, actor pass, td3_actor_step
+ * (+ all three polyaks), collect; the two actor launches return at once on a step where the actor is not due.
+ * The handle type is crl_ddpg: crl_ddpg_run, _act, _observe, _read_losses, _read_buffer, _status_read, _actor, _q_values, _evaluate and _destroy
+ * take a TD3 handle; crl_ddpg_q_values and the q0 of crl_ddpg_evaluate are critic 1's, and crl_ddpg_evaluate reads nothing of critic 2 (it, its
+ * target and its Adam state stay bit for bit). The parameter calls come in twins, because the number of networks differs: crl_ddpg_write_params /
+ * _init_params / _read_params refuse a TD3 handle and name the crl_td3_* call; every crl_td3_* call refuses a DDPG handle.
+ * ===================================================================================================== */
+typedef struct crl_td3_options { int32_t policy_delay, pad; double policy_noise, noise_clip; } crl_td3_options;  /* 24 bytes */
+/* crl_ddpg_create's checks, and — each message naming its field — policy_delay < 1, policy_noise < 0, noise_clip < 0, noise_in_update != 0 (TD3
+ * has its own target noise and none in the actor loss), NULL options. */
+int32_t crl_td3_create(const crl_ddpg_config* cfg, const crl_td3_options* opt, int32_t device, crl_ddpg** out);
+/* actor, critic 1, critic 2 (nc = nc2 = crl_ddpg_param_count's critic_n); the three targets are copies */
+int32_t crl_td3_write_params(crl_ddpg* h, const float* actor, size_t na, const float* critic1, size_t nc, const float* critic2, size_t nc2);
+/* any may be NULL */
+int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* t_actor, float* t_critic1, float* t_critic2);
+/* actor and critic 1 = crl_ddpg_make_nn(seed); critic 2 = the critic of crl_ddpg_make_nn(seed + 1), whose actor is dropped */
+int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed);
+/* get_q of critic 1 and of critic 2 for n pairs; either of q1 / q2 may be NULL. q1 = what crl_ddpg_q_values returns */
+int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2);
+
 #ifdef __cplusplus
 }
 #endif

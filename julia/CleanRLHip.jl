@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -697,6 +697,10 @@ function ddpg(config; device=0, seed=UInt64(0x5EED), params=nothing, init=_defau
   eval_every >= 0 || throw(ArgumentError("ddpg: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("ddpg|$(config.run_name)")        # ddpg.jl:48
   agent = _ddpg_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, noise_in_update, device, seed, params, init, init_seed)
+  _ddpg_run!(agent, config, chunk, eval_every, eval_envs, eval_episodes)
+end
+# the loop of ddpg() on a started agent (td3() runs it too): one crl_ddpg_run per chunk, the records of ddpg.jl:97 / :132 after each
+function _ddpg_run!(agent::DDPGAgent, config, chunk, eval_every, eval_envs, eval_episodes)
   eps = Vector{CrlDDPGEpisode}(undef, 8192); losses = Vector{CrlDDPGLossRecord}(undef, 4096)
   n_eps = Ref{Int32}(0); n_losses = Ref{Int32}(0); taken = Ref{Int64}(0)
   start_time = time(); global_step = 0
@@ -731,6 +735,10 @@ function ddpg_external(config, env; obs_dim::Integer, act_dim::Integer, act_low:
   make_logger === nothing || make_logger("ddpg|$(config.run_name)")        # ddpg.jl:48
   agent = _ddpg_start!(config, obs_dim, act_dim, DDPG_ENV_EXTERNAL, Float64(act_low), Float64(act_high), 200, noise_in_update, device, seed, params,
                        init, init_seed)
+  _ddpg_run_external!(agent, config, env, act_dim, reset_env!, step_env!)
+end
+# the loop of ddpg_external() on a started agent (td3_external() runs it too)
+function _ddpg_run_external!(agent::DDPGAgent, config, env, act_dim, reset_env!, step_env!)
   action = Vector{Float64}(undef, act_dim); losses = Vector{CrlDDPGLossRecord}(undef, 4096); n_losses = Ref{Int32}(0)
   episode_return = 0.0; episode_length = 0
   start_time = time()
@@ -758,6 +766,61 @@ function ddpg_external(config, env; obs_dim::Integer, act_dim::Integer, act_low:
     end
   end
   agent
+end
+
+# ------------------------------------------------------------------------------------------------------
+# TD3 (Fujimoto et al. 2018) on the same handle — the reference has no TD3. `config` carries DDPGConfig's fields plus policy_delay, policy_noise
+# and noise_clip (defaults of the paper: 2, 0.2, 0.5); the agent is a DDPGAgent: actor_mean, get_q (critic 1) and ddpg_evaluate (q0 = critic 1) serve it.
+# ------------------------------------------------------------------------------------------------------
+struct CrlTD3Options      # include/cleanrl_hip.h crl_td3_options
+  policy_delay::Int32; pad::Int32; policy_noise::Float64; noise_clip::Float64
+end
+
+# `params` = (actor, critic1, critic2) flat in Flux.params order wins, else the library's initialiser (crl_td3_init_params: make_ddpg_nn's glorot
+# layers, critic 2 from a second draw). Never the handle's zeros.
+function _td3_start!(config, obs_dim, act_dim, env_kind, act_low, act_high, max_steps, device, seed, params, init_seed)
+  cfg = CrlDDPGConfig(config.total_timesteps, config.buffer_size, config.min_buff_size, config.batch_size, config.warmup_steps,
+                      config.log_frequencey, config.lr, config.tau, config.gamma, config.exploration_noise, obs_dim, act_dim, env_kind,
+                      max_steps, act_low, act_high, 0, 0, seed)
+  opt = CrlTD3Options(config.policy_delay, 0, config.policy_noise, config.noise_clip)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:crl_td3_create, libcrl), Int32, (Ref{CrlDDPGConfig}, Ref{CrlTD3Options}, Int32, Ref{Ptr{Cvoid}}), cfg, opt, device, h))
+  agent = DDPGAgent(h[], obs_dim, act_dim)
+  finalizer(x -> ccall((:crl_ddpg_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
+  if params === nothing
+    check(ccall((:crl_td3_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))
+  else
+    actor, critic1, critic2 = params
+    GC.@preserve actor critic1 critic2 check(ccall((:crl_td3_write_params, libcrl), Int32,
+      (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t),
+      agent.h, actor, length(actor), critic1, length(critic1), critic2, length(critic2)))
+  end
+  agent
+end
+
+# (Q_1, Q_2) of a td3 agent for (obs_dim, n), (act_dim, n)
+function get_q_both(agent::DDPGAgent, obs::AbstractMatrix{Float64}, act::AbstractMatrix{Float64})
+  o = Array(obs); a = Array(act); n = size(o, 2); q1 = Vector{Float64}(undef, n); q2 = Vector{Float64}(undef, n)
+  GC.@preserve o a q1 q2 check(ccall((:crl_td3_q_values, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                                     agent.h, o, a, n, q1, q2))
+  (q1, q2)
+end
+
+# ddpg()'s loop and records with TD3's update, on the library's Pendulum
+function td3(config; device=0, seed=UInt64(0x5EED), params=nothing, init_seed::Integer=0, chunk::Integer=4096, make_logger=_default_make_logger(),
+             eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+  eval_every >= 0 || throw(ArgumentError("td3: eval_every must be >= 0, got $eval_every"))
+  make_logger === nothing || make_logger("td3|$(config.run_name)")
+  agent = _td3_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, device, seed, params, init_seed)
+  _ddpg_run!(agent, config, chunk, eval_every, eval_envs, eval_episodes)
+end
+
+# ddpg_external()'s loop with TD3's update: the env lives in the caller's process (reset_env! / step_env! as there)
+function td3_external(config, env; obs_dim::Integer, act_dim::Integer, act_low::Real, act_high::Real, reset_env!, step_env!, device=0,
+                      seed=UInt64(0x5EED), params=nothing, init_seed::Integer=0, make_logger=_default_make_logger())
+  make_logger === nothing || make_logger("td3|$(config.run_name)")
+  agent = _td3_start!(config, obs_dim, act_dim, DDPG_ENV_EXTERNAL, Float64(act_low), Float64(act_high), 200, device, seed, params, init_seed)
+  _ddpg_run_external!(agent, config, env, act_dim, reset_env!, step_env!)
 end
 
 end # module

@@ -12,6 +12,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
+    python scripts/run.py td3 --total_timesteps 20000 --warmup_steps 1000 --policy_delay 2 --policy_noise 0.2 --noise_clip 0.5   (TD3 on the same Pendulum; --eval_* as for ddpg)
 """
 import os
 import sys
@@ -23,7 +24,7 @@ from cleanrl_jl_amd import config_parser  # noqa: E402
 
 
 def main():
-    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg", "td3"):
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
 
@@ -50,6 +51,9 @@ def main():
     elif algo == "ddpg":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate)
         crl.ddpg(config_parser.argparse_struct(crl.DDPGConfig(), argv), "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
+    elif algo == "td3":
+        kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate, critic 1)
+        crl.td3(config_parser.argparse_struct(crl.TD3Config(), argv), "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
     else:
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_dqn_evaluate)
         crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
