@@ -8,7 +8,11 @@ action bounds cut) and the distance of every applicable one-line mutant. Then lo
 the eight observables past 10x its bar in every case, and the cases built around an edge met it. The script fails otherwise — then the case, not
 the bar, changes. Everything is seeded: a second run writes the same bytes.
 
-usage: python scripts/td3_bar.py [--jobs N] [--out profiles/td3_bar.json]"""
+--table edges does the same for the second table (EDGE_CASES, with the mutants T10 and T11 next to T1 to T9) and writes profiles/td3_edges_bar.json:
+a loss bar of its own, the same param_bar, and that table's conditions (kmax_a16's clip and clamp bind, bounds_a6's clamp binds on a part, the three
+ring cases draw more than one round of candidates).
+
+usage: python scripts/td3_bar.py [--table cases|edges] [--jobs N] [--out FILE]"""
 import argparse
 import json
 import multiprocessing
@@ -21,22 +25,25 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import td3_bar as B   # noqa: E402
 
 
-def _measure(name):
-    return name, B.measure(B.CASE[name])
+def _measure(job):
+    table, name = job
+    table_cases, mutants, _ = B.TABLES[table]
+    return name, B.measure(next(c for c in table_cases if c["name"] == name), mutants)
 
 
-def build(jobs):
+def build(jobs, table="cases"):
+    table_cases, table_mutants, _ = B.TABLES[table]
     with multiprocessing.Pool(jobs) as pool:
-        cases = dict(pool.map(_measure, [c["name"] for c in B.CASES], chunksize=1))
+        cases = dict(pool.map(_measure, [(table, c["name"]) for c in table_cases], chunksize=1))
     loss_floor = max(cases[n]["floor"][o] for n in cases for o in B.LOSSES)
     loss_bar = B.LOSS_FACTOR * loss_floor
-    for c in B.CASES:
+    for c in table_cases:
         rec = cases[c["name"]]
         d = B.case_cfg(c)
         rec.update(D=c["D"], A=c["A"], batch_size=d["batch_size"], updates=c["T"] - B.threshold(d), policy_delay=d["policy_delay"], edge=c["edge"])
         rec["mutant_ratio"] = {m: B.mutant_ratio(dist, loss_bar) for m, dist in rec["mutants"].items()}
     mutants = {}
-    for m, (what, _, _) in B.MUTANTS.items():
+    for m, (what, _, _) in table_mutants.items():
         ratios = {n: cases[n]["mutant_ratio"][m] for n in cases if m in cases[n]["mutant_ratio"]}
         worst = min(ratios, key=ratios.get)
         mutants[m] = {"what": what, "cases": len(ratios), "worst_ratio": ratios[worst], "worst_case": worst}
@@ -48,13 +55,33 @@ def build(jobs):
     }
 
 
-def check(prof):
+def check_edges(prof):
+    """the edges the second table is built around, on the reference's own statistics; → list of what fails"""
+    bad = []
+    st = prof["cases"]["kmax_a16"]["stats"]
+    if not 0.1 * st["n_noise"] <= st["n_noise_clipped"] <= 0.9 * st["n_noise"]:
+        bad.append(f"kmax_a16: {st['n_noise_clipped']} of {st['n_noise']} draws clipped, not between 10 % and 90 %")
+    if not st["n_target_clamped"] > 0:
+        bad.append("kmax_a16: the clamp of the target action never binds")
+    st = prof["cases"]["bounds_a6"]["stats"]
+    if not 0 < st["n_target_clamped"] < st["n_target_actions"]:
+        bad.append(f"bounds_a6: the clamp binds on {st['n_target_clamped']} of {st['n_target_actions']} target actions")
+    for n in B.EDGE_MULTI_ROUND:
+        most = max(B.case_candidates(B.EDGE_CASE[n]))
+        if not most > 1024:
+            bad.append(f"{n}: no draw needs more than {most} candidates, one round of 1024 is enough")
+    return bad
+
+
+def check(prof, table="cases"):
     """the conditions; → list of what fails"""
     bad = []
     for n, rec in prof["cases"].items():
         bad += [f"{n}: the jitter floor of {o} is {rec['floor'][o]}, not 0.0" for o in B.PARAMS if rec["floor"][o] != 0.0]
         bad += [f"{n}: {m} moves no observable past {prof['mutant_factor']} bars (ratio {r:.3g})" for m, r in rec["mutant_ratio"].items()
                 if not r >= prof["mutant_factor"]]
+    if table == "edges":
+        return bad + check_edges(prof)
     st = prof["cases"]["noise1_clip05"]["stats"]
     if not 0.1 * st["n_noise"] <= st["n_noise_clipped"] <= 0.9 * st["n_noise"]:
         bad.append(f"noise1_clip05: {st['n_noise_clipped']} of {st['n_noise']} draws clipped, not between 10 % and 90 %")
@@ -69,16 +96,17 @@ def check(prof):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
-    ap.add_argument("--out", default=B.BAR_JSON)
+    ap.add_argument("--table", choices=sorted(B.TABLES), default="cases", help="cases: tests/td3_bar.py's CASES; edges: its EDGE_CASES, T10 and T11")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    prof = build(args.jobs)
-    with open(args.out, "w") as f:
+    prof = build(args.jobs, args.table)
+    with open(args.out or B.TABLES[args.table][2], "w") as f:
         json.dump(prof, f, indent=1, sort_keys=True)
         f.write("\n")
     print(f"loss floor {prof['loss_floor']:.3e} -> loss_bar {prof['loss_bar']:.3e}; param_bar {prof['param_bar']:.3e}")
     for m, rec in prof["mutants"].items():
         print(f"{m:4s} worst ratio {rec['worst_ratio']:.3e} ({rec['worst_case']}, {rec['cases']} cases)  {rec['what']}")
-    bad = check(prof)
+    bad = check(prof, args.table)
     for b in bad:
         print("FAILS:", b)
     return 1 if bad else 0

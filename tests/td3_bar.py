@@ -4,7 +4,10 @@ jittered twin of the reference (ddpg_bar.JitterNumpy at the same amplitude and s
 (the MUTANTS). Transitions, parameters, the config dict and the bars' constants are ddpg_bar's.
 
 The bars. loss_bar = LOSS_FACTOR x the largest loss floor over THIS table (scripts/td3_bar.py measures it into profiles/td3_bar.json); PARAM_BAR =
-2^-21 per array and OLD_BAR = 1e-5 as for DDPG."""
+2^-21 per array and OLD_BAR = 1e-5 as for DDPG.
+
+A second table, EDGE_CASES (tests/test_td3_edges_cpu.py, tests/test_gpu_td3_edges.py, scripts/td3_bar.py --table edges), holds the batch, ring and
+logging edges with a loss bar of its own in profiles/td3_edges_bar.json, and two more mutants that only those edges can see."""
 import contextlib
 import json
 import os
@@ -16,6 +19,7 @@ import ddpg_ref as R
 import td3_ref as T
 
 BAR_JSON = os.path.join(B.ROOT, "profiles", "td3_bar.json")
+EDGE_BAR_JSON = os.path.join(B.ROOT, "profiles", "td3_edges_bar.json")
 OLD_BAR, PARAM_BAR, LOSS_FACTOR, MUTANT_FACTOR, JITTER_ULP, JITTER_SEEDS = B.OLD_BAR, B.PARAM_BAR, B.LOSS_FACTOR, B.MUTANT_FACTOR, B.JITTER_ULP, B.JITTER_SEEDS
 LOSSES = ("actor_loss", "critic_loss")
 PARAMS = ("actor", "critic1", "critic2", "target_actor", "target_critic1", "target_critic2")
@@ -51,6 +55,34 @@ CASES = [
 CASE = {c["name"]: c for c in CASES}
 CHEAPEST = ("gamma0", "delay2_off")                      # what tests/test_td3_cpu.py recomputes
 
+# The second table: what the first leaves out. Everything td3_critic_kernel and td3_critic_step add is indexed by the batch position b — the [2][k]
+# blocks of the two critic passes, the component word 16·b + c of the smoothing draw — and the first table stops at k = 61, never lets the ring wrap
+# and logs every step. Measured by scripts/td3_bar.py --table edges into profiles/td3_edges_bar.json, with a loss bar of its own.
+EDGE_CASES = [
+    _case("ni64_k30", 48, 16, 110, "NI exactly 64; one full unrolled round of 30", batch_size=30, min_buff_size=40, warmup_steps=35),
+    _case("d64a1_k7", 64, 1, 100, "the action alone sits in the second pass of the 64-stride loop", batch_size=7, min_buff_size=10, warmup_steps=5),
+    _case("k65", 3, 1, 150, "the first batch position past 63; noise word 1024", batch_size=65, min_buff_size=70, warmup_steps=66),
+    _case("k120_default", 3, 1, 210, "the reference's default batch; four unrolled rounds", batch_size=120, min_buff_size=130, warmup_steps=125),
+    _case("kmax_ring_eq_batch", 3, 1, 1038, "largest k; k = n; the ring wraps; 4 actor steps in 8 updates", batch_size=1024, buffer_size=1024,
+          min_buff_size=1030, warmup_steps=1025),
+    _case("kmax_a16", 17, 16, 1034, "largest k at act_dim 16: noise words up to 16383; policy_noise = 1 so that clip and clamp bind", batch_size=1024,
+          buffer_size=1024, min_buff_size=1030, warmup_steps=1025, policy_noise=1.0),
+    _case("ring200_full", 17, 6, 225, "k = n with several sampling rounds; the ring wraps", batch_size=200, buffer_size=200, min_buff_size=205,
+          warmup_steps=201),
+    _case("ring200_k199", 17, 6, 235, "odd k: the second critic's half starts at 199·64", batch_size=199, buffer_size=200, min_buff_size=205,
+          warmup_steps=201),
+    _case("none_terminal", 3, 1, 110, "no transition is terminal", terminal="none"),
+    _case("logfreq7_delay3", 3, 1, 110, "log_frequency = 7, policy_delay = 3: records at 14, 21, ...; only every third is an actor step",
+          log_frequency=7, policy_delay=3),
+    _case("logfreq4_delay3", 3, 1, 110, "log_frequency = 4, policy_delay = 3: the first record (g = 12) is an actor step, the second (g = 16) is not",
+          log_frequency=4, policy_delay=3),
+    _case("bounds_a6", 17, 6, 110, "act_low = -1, act_high = 0.5, policy_noise = 1: clip and clamp bind on more than half of a six-wide action",
+          act_low=-1.0, act_high=0.5, policy_noise=1.0),
+]
+EDGE_CASE = {c["name"]: c for c in EDGE_CASES}
+EDGE_CHEAPEST = ("none_terminal", "logfreq7_delay3")           # what tests/test_td3_edges_cpu.py recomputes: the shortest reference runs
+EDGE_MULTI_ROUND = ("kmax_ring_eq_batch", "ring200_full", "ring200_k199")   # at least one draw needs more than one round of 1024 candidates
+
 
 def case_cfg(case):
     kw = dict(policy_delay=2, policy_noise=0.2, noise_clip=0.5, noise_in_update=0)
@@ -68,6 +100,7 @@ def case_params(case):
 
 
 case_transitions = B.case_transitions
+case_candidates = B.case_candidates                      # reads the case through ddpg_bar.case_cfg: only fields the two share
 
 
 # ---------------------------------------------------------------------------------------------------- distances
@@ -89,8 +122,8 @@ def distances(losses, params, ref_losses, ref_params, D, A):
     return out
 
 
-def load_bars():
-    prof = json.load(open(BAR_JSON))
+def load_bars(path=BAR_JSON):
+    prof = json.load(open(path))
     return prof["loss_bar"], prof["param_bar"]
 
 
@@ -184,8 +217,40 @@ MUTANTS = {
 }
 
 
-def applicable(case, stats):
-    return [m for m, (_, applies, _) in MUTANTS.items() if applies(case, stats)]
+def _t10():                                                # the component word wraps at 1024: batch position 64 redraws position 0's noise
+    def smoothing_draws(seed, gstep, k, act_dim):
+        comps = (16 * np.arange(k)[None, :] + np.arange(act_dim)[:, None]) % 1024
+        return R.normal(seed, comps, gstep, T.S_SMOOTH)
+    return dict(smoothing_draws=smoothing_draws)
+
+
+def _t11():                                                # the grid of the critics' polyak is one block short: the last 2·nc mod 64 = 2 elements stay
+    orig = T.polyak_targets
+
+    def polyak_targets(agent, tau):
+        kept = agent.critic2_t[-2:].copy()
+        orig(agent, tau)
+        agent.critic2_t[-2:] = kept
+    return dict(polyak_targets=polyak_targets)
+
+
+def _noise_on(c):
+    return _live(c) and case_cfg(c)["policy_noise"] > 0 and case_cfg(c)["noise_clip"] > 0
+
+
+# measured on EDGE_CASES only, together with T1 to T9: T10 is exactly the reference wherever k <= 64, so the first table cannot see it
+EDGE_MUTANTS = {
+    "T10": ("the component word of the smoothing draw wraps at 1024", lambda c, st: _noise_on(c) and case_cfg(c)["batch_size"] > 64, _t10),
+    "T11": ("the last partial block of the critics' polyak is dropped", lambda c, st: st["n_actor_steps"] > 0, _t11),
+}
+ALL_MUTANTS = {**MUTANTS, **EDGE_MUTANTS}
+
+# table → (cases, the mutants measured on it, where its profile goes)
+TABLES = {"cases": (CASES, MUTANTS, BAR_JSON), "edges": (EDGE_CASES, ALL_MUTANTS, EDGE_BAR_JSON)}
+
+
+def applicable(case, stats, mutants=MUTANTS):
+    return [m for m, (_, applies, _) in mutants.items() if applies(case, stats)]
 
 
 # ---------------------------------------------------------------------------------------------------- one case, measured
@@ -200,17 +265,17 @@ def run_ref(case, patch=None):
 
 def variant(case, what, base):
     """what: ("jitter", seed) or a mutant's name → the distances of that variant from the base run"""
-    patch = B.jitter(what[1]) if isinstance(what, tuple) else patched(**MUTANTS[what][2]())
+    patch = B.jitter(what[1]) if isinstance(what, tuple) else patched(**ALL_MUTANTS[what][2]())
     losses, params, _ = run_ref(case, patch)
     return distances(losses, params, base[0], base[1], case["D"], case["A"])
 
 
-def measure(case):
+def measure(case, mutants=MUTANTS):
     """→ {"floor": {observable: max over the jitter seeds}, "mutants": {name: {observable: distance}}, "stats": the base run's}"""
     base = run_ref(case)
     floors = [variant(case, ("jitter", s), base) for s in JITTER_SEEDS]
     return {"floor": {o: max(f[o] for f in floors) for o in OBSERVABLES}, "stats": base[2],
-            "mutants": {m: variant(case, m, base) for m in applicable(case, base[2])}}
+            "mutants": {m: variant(case, m, base) for m in applicable(case, base[2], mutants)}}
 
 
 def mutant_ratio(dist, loss_bar, param_bar=PARAM_BAR):

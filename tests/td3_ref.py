@@ -56,6 +56,13 @@ def actor_loss_critic(agent):
     return agent.critic
 
 
+def polyak_targets(agent, tau):
+    """the three target updates of a due step: polyak_update! of the actor's and of both critics' targets, every element"""
+    agent.actor_t = R.polyak(agent.actor_t, agent.actor, tau)
+    agent.critic_t = R.polyak(agent.critic_t, agent.critic, tau)
+    agent.critic2_t = R.polyak(agent.critic2_t, agent.critic2, tau)
+
+
 class TD3(R.DDPG):
     """cfg: ddpg_ref.DDPG's dict (noise_in_update = 0) plus policy_delay, policy_noise, noise_clip"""
 
@@ -97,9 +104,7 @@ class TD3(R.DDPG):
             self.actor = self.opt_a.step(self.actor, ga)
             self.n_actor_steps += 1
         if targets_due(g, c["policy_delay"]):
-            self.actor_t = R.polyak(self.actor_t, self.actor, c["tau"])
-            self.critic_t = R.polyak(self.critic_t, self.critic, c["tau"])
-            self.critic2_t = R.polyak(self.critic2_t, self.critic2, c["tau"])
+            polyak_targets(self, c["tau"])
         self.n_updates += 1
         if g % c["log_frequency"] == 0:
             self.losses.append((g, float(self.actor_loss), float(self.critic_loss)))

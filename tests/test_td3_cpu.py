@@ -140,7 +140,7 @@ def test_the_bars_follow_their_formulas(prof):
 
 def test_mutants_leave_the_reference_as_it_was():
     names = ("smoothing_draws", "smoothing_noise", "target_action", "next_q", "actor_due", "targets_due", "critic2_cotangent_td", "critic2_step",
-             "actor_loss_critic")
+             "actor_loss_critic", "polyak_targets")
     before = {n: getattr(T, n) for n in names}
     for m, (_, _, make) in B.MUTANTS.items():
         with B.patched(**make()):
