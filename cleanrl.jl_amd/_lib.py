@@ -102,6 +102,8 @@ EXPORTS = [
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
     "crl_td3_create", "crl_td3_write_params", "crl_td3_read_params", "crl_td3_init_params", "crl_td3_q_values",
+    "crl_sac_param_count", "crl_sac_create", "crl_sac_make_nn", "crl_sac_init_params", "crl_sac_write_params", "crl_sac_read_params",
+    "crl_sac_q_values", "crl_sac_status_read", "crl_sac_alpha_records",
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
@@ -147,6 +149,19 @@ class CrlDDPGConfig(C.Structure):
 class CrlTD3Options(C.Structure):
     """crl_td3_options: what TD3 adds to crl_ddpg_config."""
     _fields_ = [("policy_delay", C.c_int32), ("pad", C.c_int32), ("policy_noise", C.c_double), ("noise_clip", C.c_double)]
+
+
+class CrlSACOptions(C.Structure):
+    """crl_sac_options: what SAC adds to crl_ddpg_config (log_alpha starts at float32(log(alpha)))."""
+    _fields_ = [("autotune", C.c_int32), ("pad", C.c_int32), ("alpha", C.c_double), ("target_entropy", C.c_double)]
+
+
+class CrlSACStatus(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("alpha_loss", C.c_double), ("entropy", C.c_double), ("log_alpha", C.c_float), ("pad", C.c_int32)]
+
+
+class CrlSACAlphaRecord(C.Structure):
+    _fields_ = [("global_step", C.c_int64), ("alpha", C.c_double), ("alpha_loss", C.c_double), ("entropy", C.c_double)]
 
 
 class CrlDDPGEpisode(C.Structure):
@@ -305,6 +320,15 @@ def load():
     L.crl_td3_read_params.argtypes = [vp, fp, fp, fp, fp, fp, fp]
     L.crl_td3_init_params.argtypes = [vp, C.c_uint64]
     L.crl_td3_q_values.argtypes = [vp, dp, dp, C.c_int32, dp, dp]
+    L.crl_sac_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
+    L.crl_sac_create.argtypes = [C.POINTER(CrlDDPGConfig), C.POINTER(CrlSACOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_sac_make_nn.argtypes = [C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
+    L.crl_sac_init_params.argtypes = [vp, C.c_uint64]
+    L.crl_sac_write_params.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
+    L.crl_sac_read_params.argtypes = [vp, fp, fp, fp, fp, fp, fp]
+    L.crl_sac_q_values.argtypes = [vp, dp, dp, C.c_int32, dp, dp]
+    L.crl_sac_status_read.argtypes = [vp, C.POINTER(CrlSACStatus)]
+    L.crl_sac_alpha_records.argtypes = [vp, C.POINTER(CrlSACAlphaRecord), C.c_int32, ip]
     L.crl_make_actor_critic.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_size_t]
     L.crl_ppo_init_params.argtypes = [vp, C.c_uint64]
     L.crl_a2c_init_params.argtypes = [vp, C.c_uint64]
@@ -1102,6 +1126,19 @@ class DDPGHandle:
         return out
 
 
+def _twin_q_values(call, handle, obs, act):
+    """crl_td3_q_values / crl_sac_q_values on `handle`: (Q_1, Q_2), each (n,), for (obs_dim, n), (act_dim, n)."""
+    obs = np.asfortranarray(obs, np.float64); act = np.asfortranarray(act, np.float64)
+    if obs.ndim == 1:
+        obs = obs[:, None]
+    if act.ndim == 1:
+        act = act.reshape(handle.act_dim, -1, order="F")
+    n = obs.shape[1]
+    q1, q2 = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    check(call(handle._h, _ptr(obs, C.c_double), _ptr(act, C.c_double), n, _ptr(q1, C.c_double), _ptr(q2, C.c_double)))
+    return q1, q2
+
+
 class TD3Handle(DDPGHandle):
     """Owns one crl_ddpg* made by crl_td3_create (include/cleanrl_hip.h, TD3 block): run / act / observe / status / read_losses / buffer / actor /
     q_values (critic 1) / evaluate are DDPGHandle's; the parameter calls are the crl_td3_* twins, with two critics."""
@@ -1128,12 +1165,60 @@ class TD3Handle(DDPGHandle):
 
     def q_values_both(self, obs, act):
         """crl_td3_q_values: (Q_1, Q_2), each (n,), for (obs_dim, n), (act_dim, n)."""
-        obs = np.asfortranarray(obs, np.float64); act = np.asfortranarray(act, np.float64)
-        if obs.ndim == 1:
-            obs = obs[:, None]
-        if act.ndim == 1:
-            act = act.reshape(self.act_dim, -1, order="F")
-        n = obs.shape[1]
-        q1, q2 = np.zeros(n, np.float64), np.zeros(n, np.float64)
-        check(self._L.crl_td3_q_values(self._h, _ptr(obs, C.c_double), _ptr(act, C.c_double), n, _ptr(q1, C.c_double), _ptr(q2, C.c_double)))
-        return q1, q2
+        return _twin_q_values(self._L.crl_td3_q_values, self, obs, act)
+
+
+def sac_param_count(obs_dim, act_dim):
+    """crl_sac_param_count: (len of the actor with its head of 2·act_dim rows, len of one critic)."""
+    na, nc = C.c_int64(), C.c_int64()
+    check(load().crl_sac_param_count(int(obs_dim), int(act_dim), C.byref(na), C.byref(nc)))
+    return na.value, nc.value
+
+
+def sac_make_nn_host(obs_dim, act_dim, seed=0):
+    """crl_sac_make_nn: (actor, critic1, critic2) — glorot-uniform weights, zero biases; the critics are crl_td3_init_params' for the same seed."""
+    na, nc = sac_param_count(obs_dim, act_dim)
+    a, c1, c2 = np.zeros(na, np.float32), np.zeros(nc, np.float32), np.zeros(nc, np.float32)
+    check(load().crl_sac_make_nn(int(obs_dim), int(act_dim), seed, _ptr(a, C.c_float), a.size, _ptr(c1, C.c_float), c1.size, _ptr(c2, C.c_float), c2.size))
+    return a, c1, c2
+
+
+class SACHandle(DDPGHandle):
+    """Owns one crl_ddpg* made by crl_sac_create (include/cleanrl_hip.h, SAC block): run / act / observe / status / read_losses / buffer / actor (the
+    deterministic action) / q_values (critic 1) / evaluate are DDPGHandle's; the parameter calls are the crl_sac_* twins."""
+
+    def __init__(self, cfg: CrlDDPGConfig, options: CrlSACOptions, device=0):
+        self.options = options
+        super().__init__(cfg, device)
+        self.actor_n, self.critic_n = sac_param_count(cfg.obs_dim, cfg.act_dim)
+
+    def _create(self, device):
+        check(self._L.crl_sac_create(C.byref(self.cfg), None if self.options is None else C.byref(self.options), device, C.byref(self._h)))
+
+    def write_params(self, actor, critic1, critic2):
+        a, c1, c2 = (np.ascontiguousarray(x, np.float32) for x in (actor, critic1, critic2))
+        check(self._L.crl_sac_write_params(self._h, _ptr(a, C.c_float), a.size, _ptr(c1, C.c_float), c1.size, _ptr(c2, C.c_float), c2.size))
+
+    def init_params(self, seed=0):
+        check(self._L.crl_sac_init_params(self._h, seed))
+
+    def read_params(self):
+        """(actor, critic1, critic2, target_critic1, target_critic2, log_alpha: float32 scalar)"""
+        out = [np.zeros(n, np.float32) for n in (self.actor_n, self.critic_n, self.critic_n, self.critic_n, self.critic_n, 1)]
+        check(self._L.crl_sac_read_params(self._h, *[_ptr(o, C.c_float) for o in out]))
+        return tuple(out[:5]) + (out[5][0],)
+
+    def q_values_both(self, obs, act):
+        """crl_sac_q_values: (Q_1, Q_2), each (n,), for (obs_dim, n), (act_dim, n)."""
+        return _twin_q_values(self._L.crl_sac_q_values, self, obs, act)
+
+    def sac_status(self):
+        st = CrlSACStatus()
+        check(self._L.crl_sac_status_read(self._h, C.byref(st)))
+        return dict(alpha=st.alpha, alpha_loss=st.alpha_loss, entropy=st.entropy, log_alpha=np.float32(st.log_alpha))
+
+    def alpha_records(self, max_records=4096):
+        """crl_sac_alpha_records: [(global_step, alpha, alpha_loss, entropy)], one per loss record the last run() / read_losses() returned."""
+        rs = (CrlSACAlphaRecord * max_records)(); n = C.c_int32()
+        check(self._L.crl_sac_alpha_records(self._h, rs, max_records, C.byref(n)))
+        return [(rs[i].global_step, rs[i].alpha, rs[i].alpha_loss, rs[i].entropy) for i in range(n.value)]

@@ -19,8 +19,8 @@
 //
 // Philox streams (counter = philox_env(seed, component, global_step, stream)): 0x10 behaviour noise (:79), 0x11 warm-up rand(act_space) (:79),
 // 0x12 target-actor noise (:108), 0x13 actor-loss noise (:123), 0x14 Pendulum reset in the loop (:100), 0x15 the first reset (:74), 0x16 the
-// resets of crl_ddpg_evaluate's private envs (no reference counterpart), 0x17 TD3's target smoothing (per sample: component word 16·b + c), 0xD9 the
-// minibatch draw. A normal is Box–Muller in Float64 from the two
+// resets of crl_ddpg_evaluate's private envs (no reference counterpart), 0x17 TD3's target smoothing (per sample: component word 16·b + c), 0x18 / 0x19 the
+// ε of SAC's next action / actor pass (sac.hpp, the same component word), 0xD9 the minibatch draw. A normal is Box–Muller in Float64 from the two
 // u53 halves of ONE Philox block: sqrt(−2·log(1 − u_xy))·cos(2π·u_zw).
 #include <hip/hip_runtime.h>
 
@@ -156,16 +156,21 @@ __device__ __forceinline__ double w2t_row(const float* __restrict__ W2, const do
   for (int j = 0; j < GH; ++j) s += (double)W2[j + GH * lane] * d[j];
   return s;
 }
-// actor(x) without the ·2 + noise: h1, h2 (returned per lane and left in h1s / h2s), ys[a] = tanh_fast(z3[a])   (ddpg.jl:24-26)
-__device__ __forceinline__ void actor_forward(const float* __restrict__ P, int D, int A, const double* x, double* h1s, double* h2s, double* ys,
-                                              int lane, double& h1, double& h2) {
-  const NetOff o = net_off(D, A);
+// the two tanh_fast layers of an actor whose offsets are o (ddpg.jl:24-25): h1, h2 returned per lane and left in h1s / h2s
+__device__ __forceinline__ void actor_hidden(const float* __restrict__ P, const NetOff& o, int D, const double* x, double* h1s, double* h2s, int lane,
+                                             double& h1, double& h2) {
   h1 = tanh_fast64(dense_row(P + o.W1, P + o.b1, D, x, lane));
   h1s[lane] = h1;
   __syncthreads();
   h2 = tanh_fast64(dense_row(P + o.W2, P + o.b2, GH, h1s, lane));
   h2s[lane] = h2;
   __syncthreads();
+}
+// actor(x) without the ·2 + noise: h1, h2 (returned per lane and left in h1s / h2s), ys[a] = tanh_fast(z3[a])   (ddpg.jl:24-26)
+__device__ __forceinline__ void actor_forward(const float* __restrict__ P, int D, int A, const double* x, double* h1s, double* h2s, double* ys,
+                                              int lane, double& h1, double& h2) {
+  const NetOff o = net_off(D, A);
+  actor_hidden(P, o, D, x, h1s, h2s, lane, h1, h2);
   if (lane < A) ys[lane] = tanh_fast64(head_row(P + o.W3, P + o.b3, A, h2s, lane));
   __syncthreads();
 }
@@ -359,17 +364,10 @@ __global__ void __launch_bounds__(64) ddpg_actor_kernel(DDPGDev a) {
   ddpg_actor_pass(a);
 }
 
-// E. actor gradient, Adam, polyak for actor parameter p (p >= the actor's size: only p = 0's loss)
-__device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
+// the gradient of actor parameter p from the actor pass's buffers, samples in sample order; HR = head rows (o = net_off(D, HR), aD3 is [k][HR]:
+// act_dim for DDPG and TD3, 2·act_dim for SAC), NI = the row length of X
+__device__ __forceinline__ double actor_param_grad(const DDPGDev& a, const NetOff& o, int NI, int HR, int k, int p) {
 #pragma clang fp contract(off)
-  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
-  const NetOff o = net_off(D, A);
-  if (p == 0) {                                                                        // actor_loss = −mean(Q) (:123)
-    double sum = 0.0;
-    for (int b = 0; b < k; ++b) sum += a.Qa[b];
-    a.ctl->actor_loss = -(sum / (double)k);
-  }
-  if (p >= o.N) return;
   double g = 0.0;
   if (p < o.b1) {
     const int i = p % GH, kk = p / GH;
@@ -388,14 +386,29 @@ __device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
 #pragma unroll 30
     for (int b = 0; b < k; ++b) g += a.aD2[(size_t)GH * b + j];
   } else if (p < o.b3) {
-    const int r = p - o.W3, c = r % A, j = r / A;
+    const int r = p - o.W3, c = r % HR, j = r / HR;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)A * b + c] * a.aH2[(size_t)GH * b + j];
+    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)HR * b + c] * a.aH2[(size_t)GH * b + j];
   } else {
     const int c = p - o.b3;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)A * b + c];
+    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)HR * b + c];
   }
+  return g;
+}
+
+// E. actor gradient, Adam, polyak for actor parameter p (p >= the actor's size: only p = 0's loss)
+__device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
+#pragma clang fp contract(off)
+  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
+  const NetOff o = net_off(D, A);
+  if (p == 0) {                                                                        // actor_loss = −mean(Q) (:123)
+    double sum = 0.0;
+    for (int b = 0; b < k; ++b) sum += a.Qa[b];
+    a.ctl->actor_loss = -(sum / (double)k);
+  }
+  if (p >= o.N) return;
+  const double g = actor_param_grad(a, o, NI, A, k, p);
   ddpg_step_entry(g, a.actor, a.actor_t, a.ma, a.va, a.betap + 2 * net_array(o, p), a.cfg.lr, a.cfg.tau, p);
 }
 __global__ void __launch_bounds__(64) ddpg_actor_step(DDPGDev a) {
@@ -418,24 +431,37 @@ __device__ __forceinline__ void ddpg_select_action(const DDPGDev& a, uint64_t gs
   __syncthreads();
 }
 
+// ddpg_select_action as the `select` of ddpg_collect / ddpg_act: DDPG's and TD3's behaviour policy
+__device__ __forceinline__ auto ddpg_selector(const DDPGDev& a) {
+  return [&a](uint64_t gstep, const double* xs, double* h1s, double* h2s, double* ys, double* act, int lane) {
+    ddpg_select_action(a, gstep, xs, h1s, h2s, ys, act, lane);
+  };
+}
+
+// one thread: counts the update, writes its loss record when the step is a multiple of log_frequency (ddpg.jl:131-133) and clears train_pending;
+// → the index of the record it wrote, −1 if none
+__device__ __forceinline__ int ddpg_log_update(const DDPGDev& a, DDPGCtl& c) {
+  int rec = -1;
+  c.n_updates += 1;
+  if (c.global_step % a.cfg.log_frequency == 0) {
+    if (c.n_losses < DDPG_MAX_LOSSES) {
+      rec = c.n_losses;
+      a.losses[rec].global_step = c.global_step; a.losses[rec].actor_loss = c.actor_loss; a.losses[rec].critic_loss = c.critic_loss;
+    }
+    c.n_losses += 1;
+  }
+  c.train_pending = 0;
+  return rec;
+}
 // closes the update the launches before this one ran: the only writer of the β powers, n_updates, the loss records and train_pending
 __device__ __forceinline__ void ddpg_finish_update(const DDPGDev& a, DDPGCtl& c, int lane) {
   if (lane < 12) betap_advance(a.betap, lane, a.betap[2 * lane], a.betap[2 * lane + 1]);
-  if (lane == 0) {
-    c.n_updates += 1;
-    if (c.global_step % a.cfg.log_frequency == 0) {                                    // ddpg.jl:131-133
-      if (c.n_losses < DDPG_MAX_LOSSES) {
-        a.losses[c.n_losses].global_step = c.global_step; a.losses[c.n_losses].actor_loss = c.actor_loss; a.losses[c.n_losses].critic_loss = c.critic_loss;
-      }
-      c.n_losses += 1;
-    }
-    c.train_pending = 0;
-  }
+  if (lane == 0) ddpg_log_update(a, c);
 }
 
 // F. close the pending update, then ddpg.jl:77-105 on the Pendulum until an update is due, the budget or total_timesteps is used up
-template <class Finish>
-__device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish) {
+template <class Finish, class Select>
+__device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish, Select select) {
 #pragma clang fp contract(off)
   __shared__ DDPGCtl c;
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT], act[DDPG_MAX_ACT];
@@ -456,7 +482,7 @@ __device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish) {
     __syncthreads();
     if (!go) break;
     const uint64_t gstep = (uint64_t)c.global_step;
-    ddpg_select_action(a, gstep, xs, h1s, h2s, ys, act, lane);                         // :79
+    select(gstep, xs, h1s, h2s, ys, act, lane);                                        // :79
     if (lane == 0) {
       double rew;
       const bool done = pendulum_step64(c.env, c.env_t, act[0], a.cfg.max_steps, rew); // :80
@@ -482,7 +508,7 @@ __device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish) {
   if (lane == 0) *a.ctl = c;
 }
 __global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
-  ddpg_collect(a, [&a](DDPGCtl& c, int lane) { ddpg_finish_update(a, c, lane); });
+  ddpg_collect(a, [&a](DDPGCtl& c, int lane) { ddpg_finish_update(a, c, lane); }, ddpg_selector(a));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -501,12 +527,39 @@ __global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool td3_actor_due(const DDPGCtl* c, const crl_td3_options& o) { return c->global_step % (int64_t)o.policy_delay == 0; }
 
+// forward and backward of online critic w (wave w of a two-wave block) on the shared TD target, for sample b = ring slot s: what the critic pass of
+// a twin-critic update (TD3, SAC) does once td is known. Both waves take every barrier alike; each wave's x / h1s / h2s / qs / d2s are its own.
+__device__ __forceinline__ void twin_critic_pass(const DDPGDev& a, const float* __restrict__ critic, double td, double* x, double* h1s, double* h2s,
+                                                 double* qs, double* d2s, int lane, int w, int b, size_t s) {
+#pragma clang fp contract(off)
+  const int D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const NetOff o = net_off(NI, 1);
+  double h1, h2;
+  for (int i = lane; i < NI; i += GH) {
+    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
+    x[i] = v;
+    if (w == 0) a.X[(size_t)NI * b + i] = v;
+  }
+  __syncthreads();
+  const double q = critic_forward(critic, NI, x, h1s, h2s, qs, lane, h1, h2);
+  const double diff = td - q;
+  const double dq = -2.0 * diff / (double)k;
+  const double d2 = h2 > 0.0 ? (double)critic[o.W3 + lane] * dq : 0.0;
+  d2s[lane] = d2;
+  __syncthreads();
+  const double t1 = w2t_row(critic + o.W2, d2s, lane);
+  const double d1 = h1 > 0.0 ? t1 : 0.0;
+  const size_t r = (size_t)GH * ((size_t)w * k + b) + lane;
+  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
+  if (lane == 0) { a.sq[(size_t)w * k + b] = diff * diff; a.dz[(size_t)w * k + b] = dq; }
+}
+
 // B'. Every barrier below is reached by both waves: the one exit is the block-uniform one at the top, and both waves take every call alike.
 __global__ void __launch_bounds__(128) td3_critic_kernel(DDPGDev a, crl_td3_options opt) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   __shared__ double xs[2][DDPG_MAX_IN], h1s[2][GH], h2s[2][GH], ys[2][DDPG_MAX_ACT], qs[2], d2s[2][GH];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
   const uint64_t gstep = (uint64_t)a.ctl->global_step;
   const size_t s = (size_t)a.idx[b];
   const NetOff o = net_off(NI, 1);
@@ -530,23 +583,7 @@ __global__ void __launch_bounds__(128) td3_critic_kernel(DDPGDev a, crl_td3_opti
   const double next_q = q2 < q1 ? q2 : q1;
   const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
   __syncthreads();
-  for (int i = lane; i < NI; i += GH) {
-    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
-    xs[w][i] = v;
-    if (w == 0) a.X[(size_t)NI * b + i] = v;
-  }
-  __syncthreads();
-  const double q = critic_forward(critic, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, h1, h2);
-  const double diff = td - q;
-  const double dq = -2.0 * diff / (double)k;
-  const double d2 = h2 > 0.0 ? (double)critic[o.W3 + lane] * dq : 0.0;
-  d2s[w][lane] = d2;
-  __syncthreads();
-  const double t1 = w2t_row(critic + o.W2, d2s[w], lane);
-  const double d1 = h1 > 0.0 ? t1 : 0.0;
-  const size_t r = (size_t)GH * ((size_t)w * k + b) + lane;
-  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
-  if (lane == 0) { a.sq[(size_t)w * k + b] = diff * diff; a.dz[(size_t)w * k + b] = dq; }
+  twin_critic_pass(a, critic, td, xs[w], h1s[w], h2s[w], &qs[w], d2s[w], lane, w, b, s);
 }
 
 // C'. thread p: parameter p % nc of critic p / nc. critic_loss = loss_1 + loss_2
@@ -589,31 +626,24 @@ __global__ void __launch_bounds__(64) td3_actor_step(DDPGDev a, crl_td3_options 
 __device__ __forceinline__ void td3_finish_update(const DDPGDev& a, const crl_td3_options& opt, DDPGCtl& c, int lane) {
   const bool due = td3_actor_due(&c, opt);
   if (lane < 18 && (lane >= 6 || due)) betap_advance(a.betap, lane, a.betap[2 * lane], a.betap[2 * lane + 1]);
-  if (lane == 0) {
-    c.n_updates += 1;
-    if (c.global_step % a.cfg.log_frequency == 0) {
-      if (c.n_losses < DDPG_MAX_LOSSES) {
-        a.losses[c.n_losses].global_step = c.global_step; a.losses[c.n_losses].actor_loss = c.actor_loss; a.losses[c.n_losses].critic_loss = c.critic_loss;
-      }
-      c.n_losses += 1;
-    }
-    c.train_pending = 0;
-  }
+  if (lane == 0) ddpg_log_update(a, c);
 }
 // F'.
 __global__ void __launch_bounds__(64) td3_collect_kernel(DDPGDev a, crl_td3_options opt) {
-  ddpg_collect(a, [&a, &opt](DDPGCtl& c, int lane) { td3_finish_update(a, opt, c, lane); });
+  ddpg_collect(a, [&a, &opt](DDPGCtl& c, int lane) { td3_finish_update(a, opt, c, lane); }, ddpg_selector(a));
 }
 
 // host-driven env: the action of step global_step + 1 for the staged observation (advances nothing)
-__global__ void __launch_bounds__(64) ddpg_act_kernel(DDPGDev a) {
+template <class Select>
+__device__ __forceinline__ void ddpg_act(const DDPGDev& a, Select select) {
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT], act[DDPG_MAX_ACT];
   const int lane = threadIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim;
   for (int i = lane; i < D; i += GH) xs[i] = a.stage[i];
   __syncthreads();
-  ddpg_select_action(a, (uint64_t)(a.ctl->global_step + 1), xs, h1s, h2s, ys, act, lane);
+  select((uint64_t)(a.ctl->global_step + 1), xs, h1s, h2s, ys, act, lane);
   if (lane < A) a.stage[2 * D + A + 2 + lane] = act[lane];
 }
+__global__ void __launch_bounds__(64) ddpg_act_kernel(DDPGDev a) { ddpg_act(a, ddpg_selector(a)); }
 // host-driven env: global_step += 1, Buffer.add! of the staged transition (ddpg.jl:76,83-90), is an update due (:105)
 __global__ void __launch_bounds__(64) ddpg_add_kernel(DDPGDev a) {
   __shared__ int64_t ptr;
@@ -666,6 +696,12 @@ __global__ void __launch_bounds__(64) ddpg_q_eval_kernel(DDPGDev a, const double
   if (lane == 0) out[b] = q;
 }
 
+}  // namespace crl
+
+#include "sac.hpp"   // SAC on this handle: its kernels, built from the pieces above
+
+namespace crl {
+
 // ------------------------------------------------------------------------------------------------------
 // crl_ddpg_evaluate: the frozen actor on n private Pendulums, `episodes` episodes each, in ONE launch. One wave owns one env from its first reset to
 // its last step, lane = hidden unit, EVAL_WAVES envs per block. The actor stays on the chip for the whole launch: the lane's rows of W1 and W2 and
@@ -674,13 +710,15 @@ __global__ void __launch_bounds__(64) ddpg_q_eval_kernel(DDPGDev a, const double
 // — products in input order, bias last, contraction off —, so an action has the bits crl_ddpg_actor gives for the same observation; the critic runs
 // once per episode through critic_forward itself. After the staging barrier a wave never meets a block barrier again (a wave past n leaves there):
 // layers are separated by wave_lds_fence on wave-private h1s / h2s. Pendulum handles only (obs 3, act 1 — crl_ddpg_create pins that shape).
+// head_rows = 1: DDPG's and TD3's actor, action 2·tanh_fast(head). head_rows = 2: SAC's, whose head row 0 is μ: action scale·tanh_fast(μ) + bias, what
+// sac_actor_eval_kernel gives.
 // ------------------------------------------------------------------------------------------------------
 #ifndef CRL_EVAL_WAVES
 #define CRL_EVAL_WAVES 4      // envs per block; experiment builds (csrc/Makefile, EXTRA=-DCRL_EVAL_WAVES=n) measured 1, 2, 4, 8: DESIGN.md §3e
 #endif
 constexpr int EVAL_WAVES = CRL_EVAL_WAVES, PEND_OBS = 3;
 struct DDPGEvalArgs {
-  int32_t n, episodes, trace_steps; uint64_t seed;
+  int32_t n, episodes, trace_steps, head_rows; uint64_t seed;
   double *ret, *disc_ret, *q0, *trace;      // [episodes][n] each, [trace_steps][n]
 };
 __global__ void __launch_bounds__(64 * EVAL_WAVES) ddpg_eval_kernel(DDPGDev a, DDPGEvalArgs ev) {
@@ -688,8 +726,9 @@ __global__ void __launch_bounds__(64 * EVAL_WAVES) ddpg_eval_kernel(DDPGDev a, D
   __shared__ float w3s[GH], b3s;
   __shared__ double xs[EVAL_WAVES][PEND_OBS + 1], h1s[EVAL_WAVES][GH], h2s[EVAL_WAVES][GH], qs[EVAL_WAVES];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * EVAL_WAVES + w, max_steps = a.cfg.max_steps;
-  const NetOff o = net_off(PEND_OBS, 1);
-  if (threadIdx.x < GH) w3s[threadIdx.x] = a.actor[o.W3 + threadIdx.x];
+  const int HR = ev.head_rows;
+  const NetOff o = net_off(PEND_OBS, HR);
+  if (threadIdx.x < GH) w3s[threadIdx.x] = a.actor[o.W3 + HR * threadIdx.x];
   if (threadIdx.x == 0) b3s = a.actor[o.b3];
   __syncthreads();
   if (env >= ev.n) return;
@@ -722,7 +761,8 @@ __global__ void __launch_bounds__(64 * EVAL_WAVES) ddpg_eval_kernel(DDPGDev a, D
       acc = 0.0;
 #pragma unroll 8
       for (int k = 0; k < GH; ++k) acc += (double)w3s[k] * h2w[k];
-      const double act = tanh_fast64(acc + (double)b3s) * 2.0;
+      const double y = tanh_fast64(acc + (double)b3s);
+      const double act = HR == 2 ? sac_scale(a.cfg) * y + sac_bias(a.cfg) : y * 2.0;
       if (step == 0) {                                                                 // Q(s0, μ(s0)): what crl_ddpg_q_values gives for (x, act)
         if (lane == 0) { xs[w][0] = x[0]; xs[w][1] = x[1]; xs[w][2] = x[2]; xs[w][3] = act; }
         wave_lds_fence();
@@ -753,6 +793,9 @@ struct crl_ddpg {
   int na = 0, nc = 0;
   bool td3 = false;              // created by crl_td3_create: two critics ([2][nc] in d.critic / critic_t / mc / vc), the TD3 cycle
   crl_td3_options topt{};
+  bool sac = false;              // created by crl_sac_create: critics as a TD3 handle's, an actor with a head of 2·act_dim rows, the SAC cycle
+  crl::SACDev sd{};
+  std::vector<crl_sac_alpha_record> arecs;   // the alpha records of the loss records the last crl_ddpg_run / crl_ddpg_read_losses returned
   hipStream_t stream = nullptr;
   crl::DDPGDev d;
   double* pinned = nullptr;      // external env: the staging slot's host side
@@ -778,6 +821,15 @@ static void enqueue_cycle(const crl_ddpg* h) {
   const DDPGDev& d = h->d;
   const int k = (int)h->cfg.batch_size, na = h->na, nc = h->nc;
   hipLaunchKernelGGL(ddpg_sample_kernel, dim3(1), dim3(1024), 0, st, d);
+  if (h->sac) {
+    const int ab = (na + 63) / 64;
+    hipLaunchKernelGGL(sac_critic_kernel, dim3(k), dim3(128), 0, st, d, h->sd);
+    hipLaunchKernelGGL(td3_critic_step, dim3((2 * nc + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(sac_actor_kernel, dim3(k), dim3(128), 0, st, d, h->sd);
+    hipLaunchKernelGGL(sac_actor_step, dim3(ab + (2 * nc + 63) / 64), dim3(64), 0, st, d, h->sd, ab, 2 * nc);
+    hipLaunchKernelGGL(sac_collect_kernel, dim3(1), dim3(64), 0, st, d, h->sd);
+    return;
+  }
   if (h->td3) {
     const int ab = (na + 63) / 64;
     hipLaunchKernelGGL(td3_critic_kernel, dim3(k), dim3(128), 0, st, d, h->topt);
@@ -815,8 +867,9 @@ int32_t crl_ddpg_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n,
 
 }  // extern "C"
 
-// crl_ddpg_create (topt = nullptr) and crl_td3_create: a TD3 handle holds two critics and two critic passes' buffers where a DDPG handle holds one
-static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* topt, int32_t device, crl_ddpg** out) {
+// crl_ddpg_create (topt = sopt = nullptr), crl_td3_create and crl_sac_create: a TD3 or SAC handle holds two critics and two critic passes' buffers
+// where a DDPG handle holds one; a SAC handle's actor has a head of 2·act_dim rows, and it owns log_alpha, its β-power pair and the alpha records
+static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* topt, const crl_sac_options* sopt, int32_t device, crl_ddpg** out) {
   if (cfg->obs_dim < 1 || cfg->obs_dim > DDPG_MAX_OBS) { set_error("crl_ddpg_create: obs_dim must be in 1..64"); return 1; }
   if (cfg->act_dim < 1 || cfg->act_dim > DDPG_MAX_ACT) { set_error("crl_ddpg_create: act_dim must be in 1..16"); return 1; }
   if (cfg->env_kind != CRL_DDPG_ENV_PENDULUM && cfg->env_kind != CRL_DDPG_ENV_EXTERNAL) { set_error("crl_ddpg_create: env_kind must be CRL_DDPG_ENV_PENDULUM or CRL_DDPG_ENV_EXTERNAL"); return 1; }
@@ -840,43 +893,73 @@ static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* to
   if (!h) { set_error("out of host memory"); return 1; }
   h->cfg = *cfg; h->device = device;
   if (topt) { h->td3 = true; h->topt = *topt; }
-  const size_t Q = topt ? 2 : 1;   // critics
+  if (sopt) { h->sac = true; h->sd.opt = *sopt; }
+  const size_t Q = topt || sopt ? 2 : 1;   // critics
   memset(&h->d, 0, sizeof(h->d));
   h->d.cfg = *cfg;
   hipError_t se = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   if (se != hipSuccess) { set_error(std::string("hipStreamCreate: ") + hipGetErrorString(se)); delete h; return 1; }
   const size_t cap = (size_t)cfg->buffer_size, k = (size_t)cfg->batch_size, D = (size_t)cfg->obs_dim, A = (size_t)cfg->act_dim;
-  h->na = net_off((int)D, (int)A).N; h->nc = net_off((int)(D + A), 1).N;
+  const size_t HR = sopt ? 2 * A : A;   // head rows of the actor
+  h->na = net_off((int)D, (int)HR).N; h->nc = net_off((int)(D + A), 1).N;
   const size_t na = (size_t)h->na, nc = (size_t)h->nc;
   DDPGDev& d = h->d;
   int rc = 0;
-  rc |= galloc(&d.actor, na); rc |= galloc(&d.actor_t, na); rc |= galloc(&d.ma, na); rc |= galloc(&d.va, na);
+  rc |= galloc(&d.actor, na); rc |= galloc(&d.ma, na); rc |= galloc(&d.va, na);
   rc |= galloc(&d.critic, Q * nc); rc |= galloc(&d.critic_t, Q * nc); rc |= galloc(&d.mc, Q * nc); rc |= galloc(&d.vc, Q * nc);
-  rc |= galloc(&d.betap, 12 * (Q + 1)); rc |= galloc(&d.ctl, 1); rc |= galloc(&d.eps, DDPG_MAX_EPS); rc |= galloc(&d.losses, DDPG_MAX_LOSSES);
+  rc |= galloc(&d.betap, 12 * (Q + 1) + (sopt ? 2 : 0)); rc |= galloc(&d.ctl, 1); rc |= galloc(&d.eps, DDPG_MAX_EPS); rc |= galloc(&d.losses, DDPG_MAX_LOSSES);
   rc |= galloc(&d.rb_state, cap * D); rc |= galloc(&d.rb_next, cap * D); rc |= galloc(&d.rb_action, cap * A); rc |= galloc(&d.rb_reward, cap);
   rc |= galloc(&d.rb_terminal, cap); rc |= galloc(&d.idx, k);
   rc |= galloc(&d.X, k * (D + A)); rc |= galloc(&d.cH1, Q * k * GH); rc |= galloc(&d.cH2, Q * k * GH);
   rc |= galloc(&d.cD1, Q * k * GH); rc |= galloc(&d.cD2, Q * k * GH); rc |= galloc(&d.dz, Q * k); rc |= galloc(&d.sq, Q * k);
   rc |= galloc(&d.aH1, k * GH); rc |= galloc(&d.aH2, k * GH); rc |= galloc(&d.aD1, k * GH); rc |= galloc(&d.aD2, k * GH);
-  rc |= galloc(&d.aY, k * A); rc |= galloc(&d.aD3, k * A); rc |= galloc(&d.Qa, k);
+  rc |= galloc(&d.aD3, k * HR); rc |= galloc(&d.Qa, k);
+  if (!sopt) { rc |= galloc(&d.actor_t, na); rc |= galloc(&d.aY, k * A); }   // SAC has no target actor and keeps no tanh outputs: both stay null
+  if (sopt) {
+    rc |= galloc(&h->sd.log_alpha, 3); rc |= galloc(&h->sd.lp, k); rc |= galloc(&h->sd.sctl, 1); rc |= galloc(&h->sd.arecs, DDPG_MAX_LOSSES);
+  }
   rc |= galloc(&d.stage, 2 * D + 2 * A + 2);
   if (!rc && hipHostMalloc(reinterpret_cast<void**>(&h->pinned), (2 * D + 2 * A + 2) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
     set_error("crl_ddpg_create: hipHostMalloc failed"); h->pinned = nullptr; rc = 1;
   }
   if (rc) { crl_ddpg_destroy(h); return 1; }
-  double bp[36];
-  for (int i = 0; i < 18; ++i) { bp[2 * i] = ADAM_B1; bp[2 * i + 1] = ADAM_B2; }
-  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, 12 * (Q + 1) * sizeof(double), hipMemcpyHostToDevice));
+  double bp[38];
+  for (int i = 0; i < 19; ++i) { bp[2 * i] = ADAM_B1; bp[2 * i + 1] = ADAM_B2; }
+  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, (12 * (Q + 1) + (sopt ? 2 : 0)) * sizeof(double), hipMemcpyHostToDevice));
+  if (sopt) {
+    const float la = (float)std::log(sopt->alpha);
+    const SACCtl sc{sopt->alpha, 0.0, 0.0};
+    CRL_HIP_CHECK(hipMemcpy(h->sd.log_alpha, &la, sizeof(la), hipMemcpyHostToDevice));
+    CRL_HIP_CHECK(hipMemcpy(h->sd.sctl, &sc, sizeof(sc), hipMemcpyHostToDevice));
+  }
   hipLaunchKernelGGL(ddpg_init_kernel, dim3(1), dim3(1), 0, h->stream, d);
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   *out = h;
   return 0;
 }
 
-// the DDPG parameter calls know one critic, the crl_td3_* ones two: each refuses the other kind of handle and names its twin
-static bool wrong_kind(const crl_ddpg* h, bool want_td3, const char* fn, const char* twin) {
-  if (h->td3 == want_td3) return false;
-  set_error(std::string(fn) + (want_td3 ? ": this is a DDPG handle (crl_ddpg_create) — use " : ": this is a TD3 handle (crl_td3_create) — use ") + twin);
+// the three kinds of handle: 0 DDPG, 1 TD3, 2 SAC
+static const char* const KIND[3] = {"ddpg", "td3", "sac"};
+static int kind_of(const crl_ddpg* h) { return h->sac ? 2 : h->td3 ? 1 : 0; }
+static const char NO_TWIN[] = "";
+// the DDPG parameter calls know one critic, the crl_td3_* ones two, the crl_sac_* ones two and another actor: each refuses the other kinds of handle
+// and names its twin: the call of the same name for the handle's kind, or `twin` where that call has another name (NO_TWIN: a call only SAC has).
+// fn = "crl_<kind>_<call>"; want: the kind the call is for
+static bool wrong_kind(const crl_ddpg* h, int want, const char* fn, const char* twin = nullptr) {
+  static const char* const names[3] = {"DDPG", "TD3", "SAC"};
+  const int is = kind_of(h);
+  if (is == want) return false;
+  const std::string call = std::string(fn).substr(4 + strlen(KIND[want]));           // "_<call>"
+  const std::string what = std::string(fn) + ": this is a " + names[is] + " handle (crl_" + KIND[is] + "_create) — ";
+  if (twin == NO_TWIN) set_error(what + "only a " + names[want] + " handle (crl_" + KIND[want] + "_create) has this call");
+  else set_error(what + "use " + (twin ? std::string(twin) : std::string("crl_") + KIND[is] + call));
+  return true;
+}
+// the calls every kind of handle takes refuse one whose parameters were never written, and name the parameter calls of the handle's own kind
+static bool params_unset(const crl_ddpg* h, const char* fn, const char* more = "") {
+  if (h->params_set) return false;
+  const std::string k = std::string("crl_") + KIND[kind_of(h)];
+  set_error(std::string(fn) + ": parameters not set — " + k + "_write_params or " + k + "_init_params first (ddpg.jl:52" + more + ")");
   return true;
 }
 
@@ -885,7 +968,7 @@ extern "C" {
 int32_t crl_ddpg_create(const crl_ddpg_config* cfg, int32_t device, crl_ddpg** out) {
   if (!cfg || !out) { set_error("crl_ddpg_create: null argument"); return 1; }
   *out = nullptr;
-  return ddpg_create(cfg, nullptr, device, out);
+  return ddpg_create(cfg, nullptr, nullptr, device, out);
 }
 
 int32_t crl_td3_create(const crl_ddpg_config* cfg, const crl_td3_options* opt, int32_t device, crl_ddpg** out) {
@@ -898,7 +981,7 @@ int32_t crl_td3_create(const crl_ddpg_config* cfg, const crl_td3_options* opt, i
   if (cfg->noise_in_update != 0) {
     set_error("crl_td3_create: noise_in_update must be 0 (TD3 has its own target noise, policy_noise / noise_clip, and none in the actor loss)"); return 1;
   }
-  return ddpg_create(cfg, opt, device, out);
+  return ddpg_create(cfg, opt, nullptr, device, out);
 }
 
 int32_t crl_ddpg_destroy(crl_ddpg* h) {
@@ -908,7 +991,7 @@ int32_t crl_ddpg_destroy(crl_ddpg* h) {
   DDPGDev& d = h->d;
   void* ptrs[] = {d.actor, d.actor_t, d.ma, d.va, d.critic, d.critic_t, d.mc, d.vc, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_action,
                   d.rb_reward, d.rb_terminal, d.idx, d.X, d.cH1, d.cH2, d.cD1, d.cD2, d.dz, d.sq, d.aH1, d.aH2, d.aD1, d.aD2, d.aY, d.aD3, d.Qa, d.stage,
-                  h->scratch};
+                  h->scratch, h->sd.log_alpha, h->sd.lp, h->sd.sctl, h->sd.arecs};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->pinned) (void)hipHostFree(h->pinned);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -918,7 +1001,7 @@ int32_t crl_ddpg_destroy(crl_ddpg* h) {
 
 int32_t crl_ddpg_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic, size_t critic_n) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, false, "crl_ddpg_write_params", "crl_td3_write_params")) return 1;
+  if (wrong_kind(h, 0, "crl_ddpg_write_params")) return 1;
   if (!actor || !critic || actor_n != (size_t)h->na || critic_n != (size_t)h->nc) {
     set_error("crl_ddpg_write_params: expected " + std::to_string(h->na) + " actor and " + std::to_string(h->nc) + " critic floats"); return 1;
   }
@@ -932,14 +1015,14 @@ int32_t crl_ddpg_write_params(crl_ddpg* h, const float* actor, size_t actor_n, c
 }
 int32_t crl_ddpg_init_params(crl_ddpg* h, uint64_t seed) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, false, "crl_ddpg_init_params", "crl_td3_init_params")) return 1;
+  if (wrong_kind(h, 0, "crl_ddpg_init_params")) return 1;
   std::vector<float> wa((size_t)h->na), wc((size_t)h->nc);
   if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed, wa.data(), wa.size(), wc.data(), wc.size())) return 1;
   return crl_ddpg_write_params(h, wa.data(), wa.size(), wc.data(), wc.size());
 }
 int32_t crl_ddpg_read_params(crl_ddpg* h, float* actor, float* critic, float* target_actor, float* target_critic) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, false, "crl_ddpg_read_params", "crl_td3_read_params")) return 1;
+  if (wrong_kind(h, 0, "crl_ddpg_read_params")) return 1;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, (size_t)h->na * 4, hipMemcpyDeviceToHost));
   if (critic) CRL_HIP_CHECK(hipMemcpy(critic, h->d.critic, (size_t)h->nc * 4, hipMemcpyDeviceToHost));
@@ -971,6 +1054,10 @@ static int ddpg_copy_losses(crl_ddpg* h, const DDPGCtl& c, crl_ddpg_loss_record*
     CRL_HIP_CHECK(hipMemcpyAsync(losses, h->d.losses, sizeof(crl_ddpg_loss_record) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
     CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   }
+  if (h->sac) {                                                                        // what crl_sac_alpha_records hands out
+    h->arecs.resize((size_t)(nl > 0 ? nl : 0));
+    if (nl > 0) CRL_HIP_CHECK(hipMemcpy(h->arecs.data(), h->sd.arecs, sizeof(crl_sac_alpha_record) * (size_t)nl, hipMemcpyDeviceToHost));
+  }
   *n_losses = nl;
   return 0;
 }
@@ -979,11 +1066,12 @@ int32_t crl_ddpg_run(crl_ddpg* h, int64_t max_env_steps, crl_ddpg_episode* eps, 
                      crl_ddpg_loss_record* losses, int32_t max_losses, int32_t* n_losses, int64_t* steps_taken) {
   DDPG_GUARD(h);
   if (h->cfg.env_kind != CRL_DDPG_ENV_PENDULUM) { set_error("crl_ddpg_run: the env of this handle lives in the host process — crl_ddpg_act / crl_ddpg_observe"); return 1; }
-  if (!h->params_set) { set_error("crl_ddpg_run: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52; a fresh handle holds zeros)"); return 1; }
+  if (params_unset(h, "crl_ddpg_run", "; a fresh handle holds zeros")) return 1;
   if (!n_eps || !n_losses || max_eps < 0 || max_losses < 0 || (max_eps > 0 && !eps) || (max_losses > 0 && !losses)) {
     set_error("crl_ddpg_run: bad arguments"); return 1;
   }
   *n_eps = 0; *n_losses = 0;
+  h->arecs.clear();
   if (steps_taken) *steps_taken = 0;
   if (max_env_steps <= 0) return 0;
   const DDPGDev& d = h->d;
@@ -1015,13 +1103,14 @@ int32_t crl_ddpg_run(crl_ddpg* h, int64_t max_env_steps, crl_ddpg_episode* eps, 
 int32_t crl_ddpg_act(crl_ddpg* h, const double* obs, double* action_out) {
   DDPG_GUARD(h);
   if (h->cfg.env_kind != CRL_DDPG_ENV_EXTERNAL) { set_error("crl_ddpg_act: this handle steps its own Pendulum — crl_ddpg_run"); return 1; }
-  if (!h->params_set) { set_error("crl_ddpg_act: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (params_unset(h, "crl_ddpg_act")) return 1;
   if (!obs || !action_out) { set_error("crl_ddpg_act: null argument"); return 1; }
   const size_t D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));                      // the pinned slot is free again
   memcpy(h->pinned, obs, D * 8);
   CRL_HIP_CHECK(hipMemcpyAsync(h->d.stage, h->pinned, D * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(ddpg_act_kernel, dim3(1), dim3(64), 0, h->stream, h->d);
+  if (h->sac) hipLaunchKernelGGL(sac_act_kernel, dim3(1), dim3(64), 0, h->stream, h->d);
+  else hipLaunchKernelGGL(ddpg_act_kernel, dim3(1), dim3(64), 0, h->stream, h->d);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(h->pinned + 2 * D + A + 2, h->d.stage + 2 * D + A + 2, A * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1032,7 +1121,7 @@ int32_t crl_ddpg_act(crl_ddpg* h, const double* obs, double* action_out) {
 int32_t crl_ddpg_observe(crl_ddpg* h, const double* obs, const double* action, double reward, const double* next_obs, int32_t terminal) {
   DDPG_GUARD(h);
   if (h->cfg.env_kind != CRL_DDPG_ENV_EXTERNAL) { set_error("crl_ddpg_observe: this handle steps its own Pendulum — crl_ddpg_run"); return 1; }
-  if (!h->params_set) { set_error("crl_ddpg_observe: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (params_unset(h, "crl_ddpg_observe")) return 1;
   if (!obs || !action || !next_obs) { set_error("crl_ddpg_observe: null argument"); return 1; }
   if (h->host_step >= h->cfg.total_timesteps) { set_error("crl_ddpg_observe: total_timesteps steps were already taken"); return 1; }
   const size_t D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
@@ -1079,7 +1168,7 @@ int32_t crl_ddpg_read_buffer(crl_ddpg* h, double* state, double* action, double*
 
 int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out) {
   DDPG_GUARD(h);
-  if (!h->params_set) { set_error("crl_ddpg_actor: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (params_unset(h, "crl_ddpg_actor")) return 1;
   if (n < 0 || (n > 0 && (!obs || !out))) { set_error("crl_ddpg_actor: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t N = (size_t)n, D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
@@ -1087,7 +1176,8 @@ int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out) {
   double* so = static_cast<double*>(h->scratch);
   double* sa = so + N * D;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * D * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(ddpg_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, n, sa);
+  if (h->sac) hipLaunchKernelGGL(sac_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, n, sa);
+  else hipLaunchKernelGGL(ddpg_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, n, sa);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(out, sa, N * A * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1118,7 +1208,7 @@ extern "C" {
 
 int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out) {
   DDPG_GUARD(h);
-  if (!h->params_set) { set_error("crl_ddpg_q_values: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (params_unset(h, "crl_ddpg_q_values")) return 1;
   if (n < 0 || (n > 0 && (!obs || !act || !out))) { set_error("crl_ddpg_q_values: bad arguments"); return 1; }
   if (n == 0) return 0;
   return ddpg_q_eval(h, 0, obs, act, n, out);
@@ -1126,7 +1216,7 @@ int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int
 
 int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, true, "crl_td3_q_values", "crl_ddpg_q_values")) return 1;
+  if (wrong_kind(h, 1, "crl_td3_q_values")) return 1;
   if (!h->params_set) { set_error("crl_td3_q_values: parameters not set — crl_td3_write_params or crl_td3_init_params first"); return 1; }
   if (n < 0 || (n > 0 && (!obs || !act))) { set_error("crl_td3_q_values: bad arguments"); return 1; }
   if (n == 0) return 0;
@@ -1138,7 +1228,7 @@ int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int3
 int32_t crl_td3_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n, const float* critic2,
                              size_t critic2_n) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, true, "crl_td3_write_params", "crl_ddpg_write_params")) return 1;
+  if (wrong_kind(h, 1, "crl_td3_write_params")) return 1;
   const size_t na = (size_t)h->na, nc = (size_t)h->nc;
   if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
     set_error("crl_td3_write_params: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
@@ -1154,7 +1244,7 @@ int32_t crl_td3_write_params(crl_ddpg* h, const float* actor, size_t actor_n, co
 }
 int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, true, "crl_td3_init_params", "crl_ddpg_init_params")) return 1;
+  if (wrong_kind(h, 1, "crl_td3_init_params")) return 1;
   std::vector<float> wa((size_t)h->na), wc1((size_t)h->nc), wa2((size_t)h->na), wc2((size_t)h->nc);
   if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed, wa.data(), wa.size(), wc1.data(), wc1.size())) return 1;
   if (crl_ddpg_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed + 1, wa2.data(), wa2.size(), wc2.data(), wc2.size())) return 1;   // its actor is dropped
@@ -1163,7 +1253,7 @@ int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed) {
 int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* target_actor, float* target_critic1,
                             float* target_critic2) {
   DDPG_GUARD(h);
-  if (wrong_kind(h, true, "crl_td3_read_params", "crl_ddpg_read_params")) return 1;
+  if (wrong_kind(h, 1, "crl_td3_read_params")) return 1;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   const size_t na = (size_t)h->na, nc = (size_t)h->nc;
   if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
@@ -1172,6 +1262,96 @@ int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* cr
   if (target_actor) CRL_HIP_CHECK(hipMemcpy(target_actor, h->d.actor_t, na * 4, hipMemcpyDeviceToHost));
   if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
   if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- SAC: the crl_sac_* block
+int32_t crl_sac_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n) {
+  if (obs_dim < 1 || obs_dim > DDPG_MAX_OBS) { set_error("crl_sac_param_count: obs_dim must be in 1..64"); return 1; }
+  if (act_dim < 1 || act_dim > DDPG_MAX_ACT) { set_error("crl_sac_param_count: act_dim must be in 1..16"); return 1; }
+  if (actor_n) *actor_n = net_off(obs_dim, 2 * act_dim).N;
+  if (critic_n) *critic_n = net_off(obs_dim + act_dim, 1).N;
+  return 0;
+}
+
+int32_t crl_sac_create(const crl_ddpg_config* cfg, const crl_sac_options* opt, int32_t device, crl_ddpg** out) {
+  if (!cfg || !out) { set_error("crl_sac_create: null argument"); return 1; }
+  *out = nullptr;
+  if (!opt) { set_error("crl_sac_create: options must not be NULL (crl_sac_options: autotune, alpha, target_entropy)"); return 1; }
+  if (opt->autotune != 0 && opt->autotune != 1) { set_error("crl_sac_create: autotune must be 0 or 1"); return 1; }
+  if (!(opt->alpha > 0.0) || !std::isfinite(opt->alpha)) { set_error("crl_sac_create: alpha must be > 0 and finite"); return 1; }
+  if (!std::isfinite(opt->target_entropy)) { set_error("crl_sac_create: target_entropy must be finite"); return 1; }
+  if (cfg->noise_in_update != 0) {
+    set_error("crl_sac_create: noise_in_update must be 0 (SAC samples its actions from the policy; exploration_noise is not read)"); return 1;
+  }
+  return ddpg_create(cfg, nullptr, opt, device, out);
+}
+
+int32_t crl_sac_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n, const float* critic2,
+                             size_t critic2_n) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_write_params")) return 1;
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
+    set_error("crl_sac_write_params: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
+  }
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  CRL_HIP_CHECK(hipMemcpy(h->d.actor, actor, na * 4, hipMemcpyHostToDevice));
+  for (float* dst : {h->d.critic, h->d.critic_t}) {                                       // the targets are copies
+    CRL_HIP_CHECK(hipMemcpy(dst, critic1, nc * 4, hipMemcpyHostToDevice));
+    CRL_HIP_CHECK(hipMemcpy(dst + nc, critic2, nc * 4, hipMemcpyHostToDevice));
+  }
+  h->params_set = true;
+  return 0;
+}
+int32_t crl_sac_init_params(crl_ddpg* h, uint64_t seed) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_init_params")) return 1;
+  std::vector<float> wa((size_t)h->na), wc1((size_t)h->nc), wc2((size_t)h->nc);
+  if (crl_sac_make_nn(h->cfg.obs_dim, h->cfg.act_dim, seed, wa.data(), wa.size(), wc1.data(), wc1.size(), wc2.data(), wc2.size())) return 1;
+  return crl_sac_write_params(h, wa.data(), wa.size(), wc1.data(), wc1.size(), wc2.data(), wc2.size());
+}
+int32_t crl_sac_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* target_critic1, float* target_critic2, float* log_alpha) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_read_params")) return 1;
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
+  if (critic1) CRL_HIP_CHECK(hipMemcpy(critic1, h->d.critic, nc * 4, hipMemcpyDeviceToHost));
+  if (critic2) CRL_HIP_CHECK(hipMemcpy(critic2, h->d.critic + nc, nc * 4, hipMemcpyDeviceToHost));
+  if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
+  if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
+  if (log_alpha) CRL_HIP_CHECK(hipMemcpy(log_alpha, h->sd.log_alpha, 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+int32_t crl_sac_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_q_values")) return 1;
+  if (!h->params_set) { set_error("crl_sac_q_values: parameters not set — crl_sac_write_params or crl_sac_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !act))) { set_error("crl_sac_q_values: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  if (q1 && ddpg_q_eval(h, 0, obs, act, n, q1)) return 1;
+  if (q2 && ddpg_q_eval(h, 1, obs, act, n, q2)) return 1;
+  return 0;
+}
+int32_t crl_sac_status_read(crl_ddpg* h, crl_sac_status* out) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_status_read", "crl_ddpg_status_read")) return 1;
+  if (!out) { set_error("crl_sac_status_read: null argument"); return 1; }
+  SACCtl sc;
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  CRL_HIP_CHECK(hipMemcpy(&sc, h->sd.sctl, sizeof(sc), hipMemcpyDeviceToHost));
+  CRL_HIP_CHECK(hipMemcpy(&out->log_alpha, h->sd.log_alpha, 4, hipMemcpyDeviceToHost));
+  out->alpha = sc.alpha; out->alpha_loss = sc.alpha_loss; out->entropy = sc.entropy; out->pad = 0;
+  return 0;
+}
+int32_t crl_sac_alpha_records(crl_ddpg* h, crl_sac_alpha_record* records, int32_t max_records, int32_t* n_records) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, 2, "crl_sac_alpha_records", NO_TWIN)) return 1;
+  if (!n_records || max_records < 0 || (max_records > 0 && !records)) { set_error("crl_sac_alpha_records: bad arguments"); return 1; }
+  const size_t n = h->arecs.size() < (size_t)max_records ? h->arecs.size() : (size_t)max_records;
+  if (n > 0) memcpy(records, h->arecs.data(), n * sizeof(crl_sac_alpha_record));
+  *n_records = (int32_t)n;
   return 0;
 }
 
@@ -1185,7 +1365,7 @@ int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg
     set_error("crl_ddpg_evaluate: the env of this handle lives in the host process — step it there and take the noise-free actions from crl_ddpg_actor");
     return 1;
   }
-  if (!h->params_set) { set_error("crl_ddpg_evaluate: parameters not set — crl_ddpg_write_params or crl_ddpg_init_params first (ddpg.jl:52)"); return 1; }
+  if (params_unset(h, "crl_ddpg_evaluate")) return 1;
   const int64_t n = cfg->num_envs, E = cfg->episodes_per_env, T = cfg->trace_steps, steps = E * (int64_t)h->cfg.max_steps;
   if (n < 1 || n > 65536) { set_error("crl_ddpg_evaluate: num_envs must be in 1..65536, got " + std::to_string(n)); return 1; }
   if (E < 1 || E > 1024) { set_error("crl_ddpg_evaluate: episodes_per_env must be in 1..1024, got " + std::to_string(E)); return 1; }
@@ -1198,7 +1378,7 @@ int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg
   const size_t ne = (size_t)(n * E), nt = (size_t)(T * n);
   if (ddpg_scratch(h, (3 * ne + nt) * 8)) return 1;
   DDPGEvalArgs ev;
-  ev.n = (int32_t)n; ev.episodes = (int32_t)E; ev.trace_steps = (int32_t)T; ev.seed = cfg->seed;
+  ev.n = (int32_t)n; ev.episodes = (int32_t)E; ev.trace_steps = (int32_t)T; ev.head_rows = h->sac ? 2 : 1; ev.seed = cfg->seed;
   ev.ret = static_cast<double*>(h->scratch); ev.disc_ret = ev.ret + ne; ev.q0 = ev.disc_ret + ne; ev.trace = ev.q0 + ne;
   // every slot of the four arrays is written: each env runs episodes_per_env episodes of exactly max_steps steps
   hipLaunchKernelGGL(ddpg_eval_kernel, dim3((unsigned)((n + EVAL_WAVES - 1) / EVAL_WAVES)), dim3(64 * EVAL_WAVES), 0, h->stream, h->d, ev);

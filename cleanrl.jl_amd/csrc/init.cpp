@@ -125,4 +125,24 @@ int32_t crl_ddpg_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float*
   return 0;
 }
 
+// SAC's networks: the critics are the two TD3 draws for `seed`; the actor (head of 2·act_dim rows) has a generator of its own
+int32_t crl_sac_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t actor_n, float* critic1, size_t critic1_n, float* critic2,
+                        size_t critic2_n) {
+  int64_t na = 0, nc = 0, nda = 0;
+  if (crl_sac_param_count(obs_dim, act_dim, &na, &nc) || crl_ddpg_param_count(obs_dim, act_dim, &nda, nullptr)) return 1;
+  if (!actor || !critic1 || !critic2 || actor_n != (size_t)na || critic1_n != (size_t)nc || critic2_n != (size_t)nc) {
+    set_error("crl_sac_make_nn: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
+  }
+  std::vector<float> dropped((size_t)nda);                         // the DDPG-shaped actors of the two draws
+  if (crl_ddpg_make_nn(obs_dim, act_dim, seed, dropped.data(), dropped.size(), critic1, critic1_n)) return 1;
+  if (crl_ddpg_make_nn(obs_dim, act_dim, seed + 1, dropped.data(), dropped.size(), critic2, critic2_n)) return 1;
+  crl::Rng rng{seed ^ 0x5ACull};
+  for (size_t i = 0; i < actor_n; ++i) actor[i] = 0.0f;
+  float* p = actor;
+  crl::glorot_uniform(rng, 64, obs_dim, p); p += 64 * obs_dim + 64;
+  crl::glorot_uniform(rng, 64, 64, p); p += 64 * 64 + 64;
+  crl::glorot_uniform(rng, 2 * act_dim, 64, p);
+  return 0;
+}
+
 }  // extern "C"

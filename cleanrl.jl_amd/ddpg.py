@@ -176,9 +176,17 @@ def ddpg(config: DDPGConfig = None, env="pendulum", *, device=0, seed=0x5EED, pa
                  **logger_kw)
 
 
-def _loop(who, make_agent, config, env, *, device, seed, params, chunk, eval_every, eval_envs, eval_episodes, eval_env, **logger_kw):
-    """The loop of ddpg() for any agent on a crl_ddpg handle (td3() runs it too): make_agent(config, device=, seed=, params=[, obs_dim=, act_dim=,
-    act_low=, act_high=, external=True]) builds it; `who` names the caller in messages and in the logger's run name."""
+def _training_records(handle, losses, train_extra):
+    """the "Training Statistics" records of the loss records a run() / read_losses() call just returned"""
+    extras = train_extra(handle, losses) if train_extra is not None else [{}] * len(losses)
+    return [(g, "Training Statistics", dict(actor_loss=a, critic_loss=c, **extra)) for (g, a, c), extra in zip(losses, extras)]
+
+
+def _loop(who, make_agent, config, env, *, device, seed, params, chunk, eval_every, eval_envs, eval_episodes, eval_env, train_extra=None, **logger_kw):
+    """The loop of ddpg() for any agent on a crl_ddpg handle (td3() and sac() run it too): make_agent(config, device=, seed=, params=[, obs_dim=,
+    act_dim=, act_low=, act_high=, external=True]) builds it; `who` names the caller in messages and in the logger's run name. train_extra(handle,
+    losses) -> one dict per loss record just read: further fields of that step's "Training Statistics" record (sac(): alpha, alpha_loss, entropy);
+    None leaves the record what ddpg.jl:132 logs."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"{who}: eval_every must be an integer >= 0, got {eval_every!r}")
     host_env = not isinstance(env, str)
@@ -199,7 +207,7 @@ def _loop(who, make_agent, config, env, *, device, seed, params, chunk, eval_eve
             taken, episodes, losses = agent.handle.run(budget)
             records = [(g, "Episode Statistics", dict(episode_return=r, episode_length=n, steps_per_sec=int(g / max(time.time() - start, 1e-9)),
                                                       global_step=g)) for r, n, g in episodes]
-            records += [(g, "Training Statistics", dict(actor_loss=a, critic_loss=c)) for g, a, c in losses]
+            records += _training_records(agent.handle, losses, train_extra)
             _emit(lg, records)
             global_step = agent.handle.status()["global_step"]
             if eval_every and taken > 0 and global_step % eval_every == 0:
@@ -226,7 +234,7 @@ def _loop(who, make_agent, config, env, *, device, seed, params, chunk, eval_eve
             episode_return, episode_length = 0.0, 0
             obs = np.asarray(env.reset(), np.float64)
         if global_step % config.log_frequencey == 0:                                             # :131-133
-            _emit(lg, [(g, "Training Statistics", dict(actor_loss=a, critic_loss=c)) for g, a, c in h.read_losses()])
+            _emit(lg, _training_records(h, h.read_losses(), train_extra))
         if eval_every and global_step % eval_every == 0:
             _emit(lg, [_eval_record(global_step, _evaluate_on_host_env(agent, eval_env, int(eval_episodes))["report"])])
     return agent

@@ -691,7 +691,7 @@ int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg
                           double* returns, double* disc_returns, double* q0, double* trace_action);
 
 /* =====================================================================================================
- * TD3 (Fujimoto et al. 2018) on the DDPG handle — no reference counterpart (the reference's README lists SAC and Rainbow as to-dos, no TD3). The
+ * TD3 (Fujimoto et al. 2018) on the DDPG handle — no reference counterpart (the reference's README lists SAC and Rainbow as to-dos, no TD3; SAC: the block below). The
  * networks, the ring, the minibatch draw (stream 0xD9), the behaviour policy (one draw per call on stream 0x10, scaled by exploration_noise,
  * unclipped), the warm-up (rand(act_space), stream 0x11), the Pendulum, the host-driven mode, the records and the arithmetic conventions are
  * DDPG's: Float32 weights, Float64 arithmetic, contraction off wherever a sum is formed, dot products in input order with the bias last, sums over
@@ -727,6 +727,71 @@ int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* cr
 int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed);
 /* get_q of critic 1 and of critic 2 for n pairs; either of q1 / q2 may be NULL. q1 = what crl_ddpg_q_values returns */
 int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2);
+
+/* =====================================================================================================
+ * SAC (Haarnoja et al. 2018: squashed-Gaussian actor, twin critics, entropy bonus, tuned temperature) on the DDPG handle — no reference
+ * counterpart (the reference's README lists SAC as a to-do). The ring, the minibatch draw (stream 0xD9), the warm-up (rand(act_space), stream
+ * 0x11), the Pendulum, the host-driven mode, the loss records, the critics' shape and the arithmetic conventions are DDPG's and TD3's: Float32
+ * parameters, Float64 arithmetic, contraction off wherever a sum is formed, dot products in input order with the bias last, sums over the batch in
+ * sample order, gradients projected to Float32 before Adam(lr). An update is due at step g exactly when DDPG's is. exploration_noise and
+ * noise_in_update are not read (noise_in_update must be 0). With D = obs_dim, A = act_dim, k = batch_size, batch positions b = 0..k−1:
+ *   actor          Dense(D,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,2A), the head LINEAR; flat in Flux.params order like every network
+ *                  (W3 is (2A, 64) column-major). Head rows 0..A−1 are the mean μ, rows A..2A−1 the raw s. Per component c, in this order:
+ *                    t = tanh_fast(s); log_std = −5 + 3.5·(t + 1)  ∈ [−5, 2]; σ = exp(log_std);
+ *                    for a normal ε: u = μ + σ·ε; y = tanh_fast(u); a = scale·y + bias, scale = (act_high − act_low)/2, bias = (act_high + act_low)/2;
+ *                    lp_c = ((−0.5·(ε·ε) − log_std) − 0.9189385332046727) − log(scale·(1 − y·y) + 1e-6);
+ *                  logπ = Σ_c lp_c, c ascending, from 0.0. tanh_fast returns exactly ±1 past |x| > 30: 1 − y·y is then exactly 0 and the log sees 1e-6.
+ *                  The deterministic action is scale·tanh_fast(μ) + bias. There is no target actor.
+ *   temperature    log_alpha: one Float32 scalar with its own Adam(lr) moments and β-power pair. α of an update = exp((double)log_alpha) as it
+ *                  stands BEFORE that update's alpha step; the critic pass, the actor pass, both logged losses and the alpha record use that α.
+ *   next action    a', logπ' from the CURRENT actor on next_state, ε = the Box–Muller normal of the DDPG block on Philox stream 0x18 at gstep = g,
+ *                  component word 16·b + c (one draw per sample and component).
+ *   TD target      qmin' = q2 < q1 ? q2 : q1 of target critic 1 / 2 on (next_state, a'); td = r + (γ·(1 − terminal))·(qmin' − α·logπ').
+ *   critics        as TD3: critic i takes Σ_b (td − q_i)² / k, both step on every update; critic_loss = loss_1 + loss_2.
+ *   actor          on every update: a, logπ on state with ε on stream 0x19, same component word; q1, q2 of the UPDATED critics on (state, a);
+ *                  qmin = q2 < q1 ? q2 : q1; actor_loss = (Σ_b (α·logπ_b − qmin_b)) / k. Its gradient, per sample: ga[c] = ∂(−Q_sel/k)/∂a[c] through the
+ *                  selected critic (critic 2 where q2 < q1, else critic 1) by DDPG's pullback (cotangent −1/k, relu masks, Σ_i W1[i, D + c]·δ1[i]);
+ *                    omy = 1 − y·y; den = scale·omy + 1e-6; ak = α/k;
+ *                    dy = ga·scale + ak·((2·scale·y)/den); du = dy·omy;
+ *                    δ3[c] = du (the μ row); dls = du·(σ·ε) − ak; δ3[A + c] = (dls·3.5)·(1 − t·t) (the s row);
+ *                  δ2[j] = (Σ_r W3[r, j]·δ3[r], r = 0..2A−1 ascending)·(1 − h2[j]²), δ1 as DDPG's actor; Adam on the actor.
+ *   alpha          alpha_loss = −(α·((Σ_b (logπ_b + target_entropy)) / k)) with the actor pass's logπ (no resampling); it is also its own derivative
+ *                  with respect to log_alpha. With autotune = 1: Adam on log_alpha with that gradient (projected to Float32) — after the passes of
+ *                  this update have read α. With autotune = 0 log_alpha, its moments and its β powers never change a bit; alpha_loss is still
+ *                  reported. entropy = −((Σ_b logπ_b) / k).
+ *   targets        polyak(tau) of both critic targets from the updated critics, on every update.
+ *   behaviour      while global_step <= warmup_steps: the rand(act_space) draw; after that a sample a from the actor with ε on stream 0x10,
+ *                  component word c, unclipped (it lies inside the bounds).
+ * One cycle stays six launches (csrc/ddpg.hip, csrc/sac.hpp): sample, sac_critic_kernel, td3_critic_step, sac_actor_kernel, sac_actor_step (actor
+ * Adam, both polyaks, the alpha step), sac_collect_kernel (19 β-power pairs, the alpha pair only with autotune = 1; the loss and alpha records).
+ * crl_ddpg_run, _act, _observe, _read_losses, _read_buffer, _status_read, _actor (scale·tanh_fast(μ) + bias), _q_values (critic 1), _evaluate
+ * (actions = crl_ddpg_actor's, q0 = critic 1's, bit for bit) and _destroy take a SAC handle. The crl_ddpg_* and crl_td3_* parameter calls refuse a
+ * SAC handle and name the crl_sac_* twin; every crl_sac_* call refuses the other two kinds.
+ * ===================================================================================================== */
+typedef struct crl_sac_options { int32_t autotune, pad; double alpha, target_entropy; } crl_sac_options;   /* 24 bytes; log_alpha = (float)log(alpha) */
+typedef struct crl_sac_status { double alpha, alpha_loss, entropy; float log_alpha; int32_t pad; } crl_sac_status;   /* α, losses of the last update (α =
+                                     the option's alpha, the others 0.0 before the first); log_alpha as it stands now */
+typedef struct crl_sac_alpha_record { int64_t global_step; double alpha, alpha_loss, entropy; } crl_sac_alpha_record;
+/* lengths of the actor (head of 2·act_dim rows) and of one critic */
+int32_t crl_sac_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n);
+/* crl_ddpg_create's checks, and — each message naming its field — NULL options, alpha <= 0 (or not finite), a non-finite target_entropy, autotune
+ * outside {0, 1}, noise_in_update != 0. */
+int32_t crl_sac_create(const crl_ddpg_config* cfg, const crl_sac_options* opt, int32_t device, crl_ddpg** out);
+/* host-only: glorot_uniform weights and zero biases. Critic 1 and critic 2 are crl_td3_init_params' for the same seed (the critics of
+ * crl_ddpg_make_nn(seed) and of crl_ddpg_make_nn(seed + 1)); the actor is drawn layer by layer (64×D, 64×64, 2A×64) from the generator
+ * crl_ddpg_make_nn uses, seeded with seed ^ 0x5AC. */
+int32_t crl_sac_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t na, float* critic1, size_t nc, float* critic2, size_t nc2);
+int32_t crl_sac_init_params(crl_ddpg* h, uint64_t seed);
+/* actor, critic 1, critic 2; the two critic targets are copies */
+int32_t crl_sac_write_params(crl_ddpg* h, const float* actor, size_t na, const float* critic1, size_t nc, const float* critic2, size_t nc2);
+/* any may be NULL */
+int32_t crl_sac_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* t_critic1, float* t_critic2, float* log_alpha);
+/* crl_td3_q_values' twin */
+int32_t crl_sac_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2);
+int32_t crl_sac_status_read(crl_ddpg* h, crl_sac_status* out);
+/* one record for each loss record that the last crl_ddpg_run / crl_ddpg_read_losses call on this handle returned: same order, same count, same
+ * global_step (entries beyond max_records are dropped) */
+int32_t crl_sac_alpha_records(crl_ddpg* h, crl_sac_alpha_record* records, int32_t max_records, int32_t* n_records);
 
 #ifdef __cplusplus
 }

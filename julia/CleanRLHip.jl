@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -605,6 +605,7 @@ struct CrlDDPGConfig      # include/cleanrl_hip.h crl_ddpg_config
 end
 struct CrlDDPGEpisode; episode_return::Float64; episode_length::Int64; global_step::Int64; end                  # ddpg.jl:97
 struct CrlDDPGLossRecord; global_step::Int64; actor_loss::Float64; critic_loss::Float64; end                    # ddpg.jl:132
+struct CrlSACAlphaRecord; global_step::Int64; alpha::Float64; alpha_loss::Float64; entropy::Float64; end   # crl_sac_alpha_record: beside each loss record of a SAC handle; here, above _log_training's ccall that names it
 struct CrlDDPGStatus
   theta::Float64; theta_dot::Float64
   env_t::Int64; global_step::Int64; rb_size::Int64; rb_ptr::Int64; n_updates::Int64
@@ -699,8 +700,24 @@ function ddpg(config; device=0, seed=UInt64(0x5EED), params=nothing, init=_defau
   agent = _ddpg_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, noise_in_update, device, seed, params, init, init_seed)
   _ddpg_run!(agent, config, chunk, eval_every, eval_envs, eval_episodes)
 end
-# the loop of ddpg() on a started agent (td3() runs it too): one crl_ddpg_run per chunk, the records of ddpg.jl:97 / :132 after each
-function _ddpg_run!(agent::DDPGAgent, config, chunk, eval_every, eval_envs, eval_episodes)
+# the "Training Statistics" records of the loss records a crl_ddpg_run / crl_ddpg_read_losses call just returned; sac: with the alpha records beside them
+function _log_training(agent, losses, n, sac::Bool)
+  if !sac
+    for l in @view losses[1:n]
+      @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
+    end
+    return
+  end
+  recs = Vector{CrlSACAlphaRecord}(undef, max(n, 1)); n_recs = Ref{Int32}(0)
+  GC.@preserve recs check(ccall((:crl_sac_alpha_records, libcrl), Int32, (Ptr{Cvoid}, Ptr{CrlSACAlphaRecord}, Int32, Ref{Int32}), agent.h, recs, n, n_recs))
+  n_recs[] == n || error("crl_sac_alpha_records: $(n_recs[]) records for $n loss records")
+  for (l, r) in zip(@view(losses[1:n]), @view(recs[1:n]))
+    @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss alpha = r.alpha alpha_loss = r.alpha_loss entropy = r.entropy
+  end
+end
+
+# the loop of ddpg() on a started agent (td3() and sac() run it too): one crl_ddpg_run per chunk, the records of ddpg.jl:97 / :132 after each
+function _ddpg_run!(agent::DDPGAgent, config, chunk, eval_every, eval_envs, eval_episodes; sac::Bool=false)
   eps = Vector{CrlDDPGEpisode}(undef, 8192); losses = Vector{CrlDDPGLossRecord}(undef, 4096)
   n_eps = Ref{Int32}(0); n_losses = Ref{Int32}(0); taken = Ref{Int64}(0)
   start_time = time(); global_step = 0
@@ -715,9 +732,7 @@ function _ddpg_run!(agent::DDPGAgent, config, chunk, eval_every, eval_envs, eval
       steps_per_sec = trunc(e.global_step / (time() - start_time))
       @info "Episode Statistics" episode_return = e.episode_return episode_length = e.episode_length steps_per_sec global_step = e.global_step
     end
-    for l in @view losses[1:n_losses[]]
-      @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
-    end
+    _log_training(agent, losses, n_losses[], sac)
     if eval_every > 0 && global_step % eval_every == 0
       ev = ddpg_evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report
       @info "Evaluation Statistics" eval_return_mean = ev.return_mean eval_return_std = ev.return_std eval_q_bias = ev.q_bias_mean global_step
@@ -737,8 +752,8 @@ function ddpg_external(config, env; obs_dim::Integer, act_dim::Integer, act_low:
                        init, init_seed)
   _ddpg_run_external!(agent, config, env, act_dim, reset_env!, step_env!)
 end
-# the loop of ddpg_external() on a started agent (td3_external() runs it too)
-function _ddpg_run_external!(agent::DDPGAgent, config, env, act_dim, reset_env!, step_env!)
+# the loop of ddpg_external() on a started agent (td3_external() and sac_external() run it too)
+function _ddpg_run_external!(agent::DDPGAgent, config, env, act_dim, reset_env!, step_env!; sac::Bool=false)
   action = Vector{Float64}(undef, act_dim); losses = Vector{CrlDDPGLossRecord}(undef, 4096); n_losses = Ref{Int32}(0)
   episode_return = 0.0; episode_length = 0
   start_time = time()
@@ -760,9 +775,7 @@ function _ddpg_run_external!(agent::DDPGAgent, config, env, act_dim, reset_env!,
     if global_step % config.log_frequencey == 0                            # :131-133
       GC.@preserve losses check(ccall((:crl_ddpg_read_losses, libcrl), Int32, (Ptr{Cvoid}, Ptr{CrlDDPGLossRecord}, Int32, Ref{Int32}),
                                       agent.h, losses, length(losses), n_losses))
-      for l in @view losses[1:n_losses[]]
-        @info "Training Statistics" actor_loss = l.actor_loss critic_loss = l.critic_loss
-      end
+      _log_training(agent, losses, n_losses[], sac)
     end
   end
   agent
@@ -821,6 +834,64 @@ function td3_external(config, env; obs_dim::Integer, act_dim::Integer, act_low::
   make_logger === nothing || make_logger("td3|$(config.run_name)")
   agent = _td3_start!(config, obs_dim, act_dim, DDPG_ENV_EXTERNAL, Float64(act_low), Float64(act_high), 200, device, seed, params, init_seed)
   _ddpg_run_external!(agent, config, env, act_dim, reset_env!, step_env!)
+end
+
+# ------------------------------------------------------------------------------------------------------
+# SAC (Haarnoja et al. 2018) on the same handle — the reference lists it as a to-do. `config` carries DDPGConfig's fields (exploration_noise is not
+# read) plus autotune::Bool, alpha and target_entropy (`nothing`: -act_dim); the agent is a DDPGAgent: actor_mean (the deterministic action
+# scale·tanh(μ) + bias), get_q (critic 1) and ddpg_evaluate (q0 = critic 1) serve it. "Training Statistics" carry alpha, alpha_loss and entropy.
+# ------------------------------------------------------------------------------------------------------
+struct CrlSACOptions      # include/cleanrl_hip.h crl_sac_options
+  autotune::Int32; pad::Int32; alpha::Float64; target_entropy::Float64
+end
+struct CrlSACStatus       # crl_sac_status
+  alpha::Float64; alpha_loss::Float64; entropy::Float64; log_alpha::Float32; pad::Int32
+end
+
+# `params` = (actor, critic1, critic2) flat in Flux.params order (the actor's head has 2·act_dim rows) wins, else crl_sac_init_params
+function _sac_start!(config, obs_dim, act_dim, env_kind, act_low, act_high, max_steps, device, seed, params, init_seed)
+  cfg = CrlDDPGConfig(config.total_timesteps, config.buffer_size, config.min_buff_size, config.batch_size, config.warmup_steps,
+                      config.log_frequencey, config.lr, config.tau, config.gamma, config.exploration_noise, obs_dim, act_dim, env_kind,
+                      max_steps, act_low, act_high, 0, 0, seed)
+  target_entropy = config.target_entropy === nothing ? -Float64(act_dim) : Float64(config.target_entropy)
+  opt = CrlSACOptions(config.autotune ? 1 : 0, 0, config.alpha, target_entropy)
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:crl_sac_create, libcrl), Int32, (Ref{CrlDDPGConfig}, Ref{CrlSACOptions}, Int32, Ref{Ptr{Cvoid}}), cfg, opt, device, h))
+  agent = DDPGAgent(h[], obs_dim, act_dim)
+  finalizer(x -> ccall((:crl_ddpg_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
+  if params === nothing
+    check(ccall((:crl_sac_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))
+  else
+    actor, critic1, critic2 = params
+    GC.@preserve actor critic1 critic2 check(ccall((:crl_sac_write_params, libcrl), Int32,
+      (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t),
+      agent.h, actor, length(actor), critic1, length(critic1), critic2, length(critic2)))
+  end
+  agent
+end
+
+# (alpha, alpha_loss, entropy) of the last update and log_alpha as it stands
+function sac_status(agent::DDPGAgent)
+  st = Ref(CrlSACStatus(0.0, 0.0, 0.0, 0.0f0, 0))
+  check(ccall((:crl_sac_status_read, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlSACStatus}), agent.h, st))
+  (alpha = st[].alpha, alpha_loss = st[].alpha_loss, entropy = st[].entropy, log_alpha = st[].log_alpha)
+end
+
+# ddpg()'s loop and records with SAC's update, on the library's Pendulum
+function sac(config; device=0, seed=UInt64(0x5EED), params=nothing, init_seed::Integer=0, chunk::Integer=4096, make_logger=_default_make_logger(),
+             eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+  eval_every >= 0 || throw(ArgumentError("sac: eval_every must be >= 0, got $eval_every"))
+  make_logger === nothing || make_logger("sac|$(config.run_name)")
+  agent = _sac_start!(config, 3, 1, DDPG_ENV_PENDULUM, -2.0, 2.0, 200, device, seed, params, init_seed)
+  _ddpg_run!(agent, config, chunk, eval_every, eval_envs, eval_episodes; sac=true)
+end
+
+# ddpg_external()'s loop with SAC's update: the env lives in the caller's process (reset_env! / step_env! as there)
+function sac_external(config, env; obs_dim::Integer, act_dim::Integer, act_low::Real, act_high::Real, reset_env!, step_env!, device=0,
+                      seed=UInt64(0x5EED), params=nothing, init_seed::Integer=0, make_logger=_default_make_logger())
+  make_logger === nothing || make_logger("sac|$(config.run_name)")
+  agent = _sac_start!(config, obs_dim, act_dim, DDPG_ENV_EXTERNAL, Float64(act_low), Float64(act_high), 200, device, seed, params, init_seed)
+  _ddpg_run_external!(agent, config, env, act_dim, reset_env!, step_env!; sac=true)
 end
 
 end # module

@@ -13,7 +13,9 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
     python scripts/run.py td3 --total_timesteps 20000 --warmup_steps 1000 --policy_delay 2 --policy_noise 0.2 --noise_clip 0.5   (TD3 on the same Pendulum; --eval_* as for ddpg)
+    python scripts/run.py sac --total_timesteps 20000 --warmup_steps 1000 --alpha 1.0 --autotune true --target_entropy -1   (SAC on the same Pendulum; --eval_* as for ddpg)
 """
+import dataclasses
 import os
 import sys
 
@@ -24,7 +26,7 @@ from cleanrl_jl_amd import config_parser  # noqa: E402
 
 
 def main():
-    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg", "td3"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg", "td3", "sac"):
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
 
@@ -54,6 +56,12 @@ def main():
     elif algo == "td3":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate, critic 1)
         crl.td3(config_parser.argparse_struct(crl.TD3Config(), argv), "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
+    elif algo == "sac":
+        kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_ddpg_evaluate, critic 1)
+        te = take((("--target_entropy", float),))                                               # None (= -act_dim) unless given: no type to parse it by
+        cfg = config_parser.argparse_struct(dataclasses.replace(crl.SACConfig(), target_entropy=0.0), argv)
+        cfg.target_entropy = te.get("target_entropy")
+        crl.sac(cfg, "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
     else:
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_dqn_evaluate)
         crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
