@@ -97,7 +97,8 @@ EXPORTS = [
     "crl_a2c_create", "crl_a2c_destroy", "crl_a2c_param_count", "crl_a2c_write_params", "crl_a2c_read_params", "crl_a2c_read_grads",
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
-    "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_dqn_per_create", "crl_dqn_per_status_read", "crl_dqn_per_read",
+    "crl_dqn_per_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -131,6 +132,15 @@ class CrlDQNLossRecord(C.Structure):
 class CrlDQNStatus(C.Structure):
     _fields_ = [("env_state", C.c_double * 4), ("global_step", C.c_int64), ("rb_size", C.c_int64), ("n_updates", C.c_int64),
                 ("last_loss", C.c_double)]
+
+
+class CrlDQNPEROptions(C.Structure):
+    """crl_dqn_per_options: what prioritized replay adds to crl_dqn_config (40 bytes)."""
+    _fields_ = [("alpha", C.c_double), ("beta_start", C.c_double), ("beta_end", C.c_double), ("beta_duration", C.c_double), ("eps", C.c_double)]
+
+
+class CrlDQNPERStatus(C.Structure):
+    _fields_ = [("beta", C.c_double), ("total", C.c_double), ("max_leaf", C.c_float), ("tree_leaves", C.c_int32)]
 
 
 
@@ -296,6 +306,10 @@ def load():
     L.crl_dqn_q_values.argtypes = [vp, dp, C.c_int32, dp]
     L.crl_dqn_evaluate.argtypes = [vp, C.POINTER(CrlEvalConfig), C.POINTER(CrlValueEvalReport), dp, ip, dp, dp, ip]
     L.crl_dqn_eval_envs_per_block.argtypes = []
+    L.crl_dqn_per_create.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNPEROptions), C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_per_status_read.argtypes = [vp, C.POINTER(CrlDQNPERStatus)]
+    L.crl_dqn_per_read.argtypes = [vp, fp, dp, ip, dp, dp]
+    L.crl_dqn_per_probe.argtypes = [vp, fp, C.c_int32, C.c_uint64, C.c_int32, C.c_double, ip, dp, dp]
     L.crl_a2c_forward.argtypes = [vp, C.c_int32, dp, C.c_int32, dp]
     L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
     L.crl_a2c_eval_envs_per_block.argtypes = []
@@ -934,13 +948,18 @@ def a2c_discounted_future_rewards_host(rewards, terminals, final_value, gamma, d
 
 
 class DQNHandle:
-    """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block)."""
+    """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block). `per` (a CrlDQNPEROptions) makes it a prioritized-replay handle (crl_dqn_per_create):
+    every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None):
         self._L = load()
         self.cfg = cfg
+        self.per = per
         self._h = C.c_void_p()
-        check(self._L.crl_dqn_create(C.byref(cfg), device, C.byref(self._h)))
+        if per is None:
+            check(self._L.crl_dqn_create(C.byref(cfg), device, C.byref(self._h)))
+        else:
+            check(self._L.crl_dqn_per_create(C.byref(cfg), C.byref(per), device, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -991,6 +1010,37 @@ class DQNHandle:
         launch). Returns {"report": {..., q0_mean, q_bias_mean}, "returns", "disc_returns", "q0": (episodes_per_env, num_envs) float64, "lengths":
         int32[, "trace_action": (trace_steps, num_envs) int32, −1 after the env's quota]}."""
         return _value_evaluate(self._L.crl_dqn_evaluate, self._h, num_envs, episodes_per_env, EVAL_GREEDY, seed, trace_steps, "q0")
+
+    def per_status(self):
+        """crl_dqn_per_status_read → {beta, total, max_leaf, tree_leaves}"""
+        st = CrlDQNPERStatus()
+        check(self._L.crl_dqn_per_status_read(self._h, C.byref(st)))
+        return dict(beta=st.beta, total=st.total, max_leaf=np.float32(st.max_leaf), tree_leaves=st.tree_leaves)
+
+    def per_read(self):
+        """crl_dqn_per_read → {leaves float32 [buffer_size], tree float64 [2·C], idx int32 [k], weight, abs_td float64 [k]} after the last update"""
+        cap, k = int(self.cfg.buffer_size), int(self.cfg.batch_size)
+        c = 1
+        while c < cap:
+            c *= 2
+        out = dict(leaves=np.zeros(cap, np.float32), tree=np.zeros(2 * c, np.float64), idx=np.zeros(k, np.int32), weight=np.zeros(k, np.float64),
+                   abs_td=np.zeros(k, np.float64))
+        check(self._L.crl_dqn_per_read(self._h, _ptr(out["leaves"], C.c_float), _ptr(out["tree"], C.c_double), _ptr(out["idx"], C.c_int32),
+                                       _ptr(out["weight"], C.c_double), _ptr(out["abs_td"], C.c_double)))
+        return out
+
+    def per_probe(self, leaves, gstep, k, beta, want_tree=True):
+        """crl_dqn_per_probe: the device's sampler on `leaves` (float32, n of them) → (idx int32 [k], weight float64 [k], tree float64 [2·C(n)] or None)"""
+        leaves = np.ascontiguousarray(leaves, np.float32)
+        n = leaves.size
+        c = 1
+        while c < n:
+            c *= 2
+        idx, w = np.zeros(max(int(k), 1), np.int32), np.zeros(max(int(k), 1), np.float64)
+        tree = np.zeros(2 * c, np.float64) if want_tree else None
+        check(self._L.crl_dqn_per_probe(self._h, _ptr(leaves, C.c_float), n, int(gstep), int(k), float(beta), _ptr(idx, C.c_int32), _ptr(w, C.c_double),
+                                        None if tree is None else _ptr(tree, C.c_double)))
+        return idx, w, tree
 
 
 def ddpg_param_count(obs_dim, act_dim):

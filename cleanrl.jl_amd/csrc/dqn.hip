@@ -18,6 +18,7 @@
 #include "env64.hpp"
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
+#include "dqn_per.hpp"
 #include "replay_sample.hpp"
 #include "value_eval.hpp"
 
@@ -44,6 +45,7 @@ struct DQNDev {
   double *rb_state, *rb_next, *rb_reward; int32_t* rb_action; uint8_t* rb_terminal;
   double *H1, *H2, *Q, *dz, *sq, *d2, *d1;   // [2][120·k], [2][84·k], [2][2·k], [k], [k], [84·k], [120·k]
   int32_t* idx;                               // [k] minibatch indices into the ring
+  PerDev per;                                 // prioritized replay (crl_dqn_per_create); all zero on a crl_dqn_create handle
 };
 
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
@@ -215,6 +217,75 @@ __global__ void __launch_bounds__(1024) dqn_td_kernel(DQNDev a) {
     a.ctl->last_loss = loss / (double)k;
   }
 }
+
+// ------------------------------------------------------------------------------------------------------
+// Prioritized replay (crl_dqn_per_create; dqn_per.hpp): these two take the places of dqn_sample_kernel and dqn_td_kernel in the cycle, which stays ten
+// launches. One block of 1024 each.
+// ------------------------------------------------------------------------------------------------------
+// Add (the slots the ring took since the last update get max_leaf, their ancestors are repaired), beta(g), the draw, the weights
+__global__ void __launch_bounds__(1024) dqn_per_sample_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const PerDev& p = a.per;
+  const int C = p.C, cap = (int)a.cfg.buffer_size, k = (int)a.cfg.batch_size, n = (int)a.ctl->size, ptr = (int)a.ctl->ptr;
+  const int64_t g = a.ctl->global_step, behind = g - p.ctl->synced_step;
+  const int fresh = behind < (int64_t)cap ? (int)behind : cap;
+  const double fill = (double)p.ctl->max_leaf;              // as of the last completed update
+  const auto slot_of = [=](int i) { const int s = ptr - 1 - i; return s < 0 ? s + cap : s; };   // the i-th slot behind ptr
+  for (int i = threadIdx.x; i < fresh; i += blockDim.x) p.tree[C + slot_of(i)] = fill;
+  per_repair(p.tree, C, fresh, slot_of);
+  const double beta = per_beta(p.beta_start, p.beta_end, p.beta_duration, (double)g);
+  per_draw(p.tree, C, k, a.cfg.seed, (uint64_t)g, a.idx);
+  per_weights(p.tree, C, n, k, beta, a.idx, p.w);
+  if (threadIdx.x == 0) { p.ctl->synced_step = g; p.ctl->beta = beta; }
+}
+// dqn_td_kernel with importance weights, plus the priority write-back: loss = (Σ_b w_b·δ_b², sample order)/k, dz_b = −2·w_b·δ_b/k, the new leaves of
+// idx_b (duplicates write identical values: the same slot has the same δ), max_leaf raised to the batch's largest new leaf, the ancestors repaired
+__global__ void __launch_bounds__(1024) dqn_per_td_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  __shared__ float lmax[16];
+  const PerDev& p = a.per;
+  const int k = (int)a.cfg.batch_size, C = p.C;
+  float mine = 0.0f;
+  for (int b = threadIdx.x; b < k; b += blockDim.x) {
+    const double tq0 = a.Q[(size_t)QA * k + QA * b], tq1 = a.Q[(size_t)QA * k + QA * b + 1];
+    const double next_q = tq1 > tq0 ? tq1 : tq0;
+    const int s = a.idx[b];
+    const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
+    const double diff = td - a.Q[QA * b + a.rb_action[s]];
+    const double w = p.w[b];
+    a.sq[b] = w * (diff * diff);
+    a.dz[b] = -2.0 * w * diff / (double)k;
+    const double ad = diff < 0.0 ? -diff : diff;
+    const float leaf = per_leaf(ad, p.eps, p.alpha);
+    p.abs_td[b] = ad;
+    p.tree[C + s] = (double)leaf;
+    mine = leaf > mine ? leaf : mine;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
+  if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double loss = 0.0;
+    for (int b = 0; b < k; ++b) loss += a.sq[b];
+    a.ctl->last_loss = loss / (double)k;
+    float top = p.ctl->max_leaf;
+    for (int i = 0; i < (int)(blockDim.x + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
+    p.ctl->max_leaf = top;
+  }
+  const int32_t* idx = a.idx;
+  per_repair(p.tree, C, k, [=](int i) { return (int)idx[i]; });
+}
+// crl_dqn_per_probe: the sampler alone on a scratch tree whose leaves the host wrote (every inner node is rebuilt first)
+__global__ void __launch_bounds__(1024) dqn_per_probe_kernel(double* tree, int C, int n, int k, uint64_t seed, uint64_t g, double beta, int32_t* idx,
+                                                             double* w) {
+  per_repair(tree, C, C, [](int i) { return i; });
+  per_draw(tree, C, k, seed, g, idx);
+  per_weights(tree, C, n, k, beta, idx, w);
+}
+
 __global__ void __launch_bounds__(256) dqn_bwd2_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
@@ -442,6 +513,8 @@ struct crl_dqn {
   void* stage = nullptr; size_t stage_bytes = 0;
   crl::ValueEvalScratch eval;   // crl_dqn_evaluate
   hipGraphExec_t cycle_exec = nullptr; bool graph_failed = false;   // CRL_DQN_GRAPH=1 replays the cycle as a hipGraph
+  bool per = false;                                                 // made by crl_dqn_per_create
+  double* probe_tree = nullptr; int32_t* probe_idx = nullptr; double* probe_w = nullptr;   // crl_dqn_per_probe's scratch
 };
 
 using namespace crl;
@@ -459,22 +532,21 @@ static int qalloc(T** p, size_t n) {
 
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_collect_kernel, dim3(1), dim3(128), 0, st, d);
-  hipLaunchKernelGGL(dqn_sample_kernel, dim3(1), dim3(1024), 0, st, d);
+  if (d.per.on) hipLaunchKernelGGL(dqn_per_sample_kernel, dim3(1), dim3(1024), 0, st, d);
+  else hipLaunchKernelGGL(dqn_sample_kernel, dim3(1), dim3(1024), 0, st, d);
   hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((2 * QH1 * k + 255) / 256), dim3(256), 0, st, d);
   hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((2 * QH2 * k + 255) / 256), dim3(256), 0, st, d);
   hipLaunchKernelGGL(dqn_fwd3_kernel, dim3((2 * QA * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_td_kernel, dim3(1), dim3(1024), 0, st, d);
+  if (d.per.on) hipLaunchKernelGGL(dqn_per_td_kernel, dim3(1), dim3(1024), 0, st, d);
+  else hipLaunchKernelGGL(dqn_td_kernel, dim3(1), dim3(1024), 0, st, d);
   hipLaunchKernelGGL(dqn_bwd2_kernel, dim3((QH2 * k + 255) / 256), dim3(256), 0, st, d);
   hipLaunchKernelGGL(dqn_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
   hipLaunchKernelGGL(dqn_wgrad_kernel, dim3((QP + 63) / 64), dim3(64), 0, st, d);
   hipLaunchKernelGGL(dqn_adam_kernel, dim3(1), dim3(1024), 0, st, d);
 }
 
-extern "C" {
-
-int32_t crl_dqn_create(const crl_dqn_config* cfg, int32_t device, crl_dqn** out) {
-  if (!cfg || !out) { set_error("crl_dqn_create: null argument"); return 1; }
-  *out = nullptr;
+// crl_dqn_create and crl_dqn_per_create: one body; `per` is null for uniform replay
+static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, int32_t device, crl_dqn** out) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -503,6 +575,19 @@ int32_t crl_dqn_create(const crl_dqn_config* cfg, int32_t device, crl_dqn** out)
   rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
   rc |= qalloc(&d.H1, 2 * QH1 * k); rc |= qalloc(&d.H2, 2 * QH2 * k); rc |= qalloc(&d.Q, 2 * QA * k);
   rc |= qalloc(&d.dz, k); rc |= qalloc(&d.sq, k); rc |= qalloc(&d.d2, QH2 * k); rc |= qalloc(&d.d1, QH1 * k); rc |= qalloc(&d.idx, k);
+  if (per) {
+    h->per = true;
+    PerDev& p = d.per;
+    p.on = 1; p.C = per_tree_leaves(cfg->buffer_size);
+    p.alpha = per->alpha; p.beta_start = per->beta_start; p.beta_end = per->beta_end; p.beta_duration = per->beta_duration; p.eps = per->eps;
+    rc |= qalloc(&p.tree, 2 * (size_t)p.C); rc |= qalloc(&p.ctl, 1); rc |= qalloc(&p.w, k); rc |= qalloc(&p.abs_td, k);
+    if (!rc) {
+      PerCtl pc;
+      memset(&pc, 0, sizeof(pc));
+      pc.beta = per->beta_start; pc.max_leaf = 1.0f;
+      if (hipMemcpy(p.ctl, &pc, sizeof(pc), hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the PER control block failed"); rc = 1; }
+    }
+  }
   if (rc) { crl_dqn_destroy(h); return 1; }
   double bp[12];
   for (int i = 0; i < 6; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
@@ -513,6 +598,86 @@ int32_t crl_dqn_create(const crl_dqn_config* cfg, int32_t device, crl_dqn** out)
   return 0;
 }
 
+#define DQN_PER_GUARD(h, name)                                                                                           \
+  DQN_GUARD(h);                                                                                                          \
+  if (!(h)->per) { set_error(name ": the handle was made by crl_dqn_create (uniform replay); crl_dqn_per_create makes a PER handle"); return 1; }
+
+extern "C" {
+
+int32_t crl_dqn_create(const crl_dqn_config* cfg, int32_t device, crl_dqn** out) {
+  if (!cfg || !out) { set_error("crl_dqn_create: null argument"); return 1; }
+  *out = nullptr;
+  return dqn_create(cfg, nullptr, device, out);
+}
+
+int32_t crl_dqn_per_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, int32_t device, crl_dqn** out) {
+  if (!cfg || !per || !out) { set_error("crl_dqn_per_create: null argument"); return 1; }
+  *out = nullptr;
+  if (!(per->alpha >= 0.0 && per->alpha <= 1.0)) { set_error("crl_dqn_per_create: alpha must be in 0..1"); return 1; }
+  if (!(per->beta_start >= 0.0 && per->beta_start <= 1.0)) { set_error("crl_dqn_per_create: beta_start must be in 0..1"); return 1; }
+  if (!(per->beta_end >= 0.0 && per->beta_end <= 1.0)) { set_error("crl_dqn_per_create: beta_end must be in 0..1"); return 1; }
+  if (!(per->beta_duration > 0.0) || !(per->beta_duration < 1e300)) { set_error("crl_dqn_per_create: beta_duration must be > 0 and finite"); return 1; }
+  if (!(per->eps >= 1e-6 && per->eps <= 1.0)) { set_error("crl_dqn_per_create: eps must be in 1e-6..1"); return 1; }
+  return dqn_create(cfg, per, device, out);
+}
+
+int32_t crl_dqn_per_status_read(crl_dqn* h, crl_dqn_per_status* out) {
+  DQN_PER_GUARD(h, "crl_dqn_per_status_read");
+  if (!out) { set_error("crl_dqn_per_status_read: null argument"); return 1; }
+  PerCtl pc; double total = 0.0;
+  CRL_HIP_CHECK(hipMemcpyAsync(&pc, h->d.per.ctl, sizeof(pc), hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(&total, h->d.per.tree + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  out->beta = pc.beta; out->total = total; out->max_leaf = pc.max_leaf; out->tree_leaves = h->d.per.C;
+  return 0;
+}
+
+int32_t crl_dqn_per_read(crl_dqn* h, float* leaves, double* tree, int32_t* idx, double* weight, double* abs_td) {
+  DQN_PER_GUARD(h, "crl_dqn_per_read");
+  const PerDev& p = h->d.per;
+  const size_t C = (size_t)p.C, cap = (size_t)h->cfg.buffer_size, k = (size_t)h->cfg.batch_size;
+  std::vector<double> t;
+  if (leaves) {
+    t.resize(cap);
+    CRL_HIP_CHECK(hipMemcpyAsync(t.data(), p.tree + C, cap * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (tree) CRL_HIP_CHECK(hipMemcpyAsync(tree, p.tree, 2 * C * 8, hipMemcpyDeviceToHost, h->stream));
+  if (idx) CRL_HIP_CHECK(hipMemcpyAsync(idx, h->d.idx, k * 4, hipMemcpyDeviceToHost, h->stream));
+  if (weight) CRL_HIP_CHECK(hipMemcpyAsync(weight, p.w, k * 8, hipMemcpyDeviceToHost, h->stream));
+  if (abs_td) CRL_HIP_CHECK(hipMemcpyAsync(abs_td, p.abs_td, k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if (leaves) for (size_t s = 0; s < cap; ++s) leaves[s] = (float)t[s];   // stored widened: the conversion back is exact
+  return 0;
+}
+
+int32_t crl_dqn_per_probe(crl_dqn* h, const float* leaves, int32_t n, uint64_t gstep, int32_t k, double beta, int32_t* idx, double* weight,
+                          double* tree) {
+  DQN_PER_GUARD(h, "crl_dqn_per_probe");
+  if (!leaves || !idx || !weight) { set_error("crl_dqn_per_probe: null argument (leaves, idx and weight are required)"); return 1; }
+  if (n < 1 || n > DQN_MAX_CAP) { set_error("crl_dqn_per_probe: n must be in 1..65536"); return 1; }
+  if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_per_probe: k must be in 1..1024"); return 1; }
+  if (!(beta >= 0.0 && beta <= 1.0)) { set_error("crl_dqn_per_probe: beta must be in 0..1"); return 1; }
+  for (int32_t i = 0; i < n; ++i)
+    if (!((double)leaves[i] >= PER_LEAF_MIN && (double)leaves[i] <= PER_LEAF_MAX)) { set_error("crl_dqn_per_probe: every leaf must be in 2^-100..2^100"); return 1; }
+  if (!h->probe_tree) {
+    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_tree), 2 * (size_t)DQN_MAX_CAP * 8));
+    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_idx), (size_t)DQN_MAX_BATCH * 4));
+    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_w), (size_t)DQN_MAX_BATCH * 8));
+  }
+  const int C = per_tree_leaves(n);
+  std::vector<double> t(2 * (size_t)C, 0.0);                 // leaves widened, slots >= n and the inner nodes 0.0 (the kernel rebuilds the inner nodes)
+  for (int32_t i = 0; i < n; ++i) t[(size_t)C + (size_t)i] = (double)leaves[i];
+  CRL_HIP_CHECK(hipMemcpyAsync(h->probe_tree, t.data(), t.size() * 8, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_per_probe_kernel, dim3(1), dim3(1024), 0, h->stream, h->probe_tree, C, (int)n, (int)k, h->cfg.seed, gstep, beta, h->probe_idx,
+                     h->probe_w);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(idx, h->probe_idx, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(weight, h->probe_w, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
+  if (tree) CRL_HIP_CHECK(hipMemcpyAsync(tree, h->probe_tree, t.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int32_t crl_dqn_destroy(crl_dqn* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
@@ -520,7 +685,8 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
   if (h->cycle_exec) (void)hipGraphExecDestroy(h->cycle_exec);
   DQNDev& d = h->d;
   void* ptrs[] = {d.q, d.t, d.grads, d.m, d.v, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_reward, d.rb_action,
-                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p};
+                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p,
+                  d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -30,6 +30,40 @@ class DQNConfig:
     epsilon_duration: float = 10_000
 
 
+@dataclasses.dataclass
+class PEROptions:
+    """Prioritized experience replay (Schaul et al. 2016, proportional; crl_dqn_per_options) — not in dqn.jl, so not in DQNConfig. beta_duration =
+    None means config.total_timesteps."""
+    alpha: float = 0.6
+    beta_start: float = 0.4
+    beta_end: float = 1.0
+    beta_duration: float = None
+    eps: float = 1e-6
+
+
+def per_beta(per, global_step):
+    """beta(g) as include/cleanrl_hip.h pins it (host-side helper for the logger; the update evaluates the same expression on the device)."""
+    slope = (per.beta_end - per.beta_start) / per.beta_duration
+    v = slope * float(global_step) + per.beta_start
+    if slope < 0.0:
+        return per.beta_end if v < per.beta_end else v
+    return per.beta_end if v > per.beta_end else v
+
+
+def _check_per(per, config):
+    """→ a PEROptions with beta_duration filled in, validated before the library is touched"""
+    if not isinstance(per, PEROptions):
+        raise TypeError(f"per must be a PEROptions or None, got {type(per).__name__}")
+    per = dataclasses.replace(per, beta_duration=float(config.total_timesteps if per.beta_duration is None else per.beta_duration))
+    for name, lo, hi in (("alpha", 0.0, 1.0), ("beta_start", 0.0, 1.0), ("beta_end", 0.0, 1.0), ("eps", 1e-6, 1.0)):
+        v = getattr(per, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (lo <= v <= hi):
+            raise ValueError(f"PEROptions.{name} must be in {lo}..{hi}, got {v!r}")
+    if not (per.beta_duration > 0.0) or not np.isfinite(per.beta_duration):
+        raise ValueError(f"PEROptions.beta_duration must be > 0, got {per.beta_duration!r}")
+    return per
+
+
 def linear_schedule(start_e, end_e, duration, t):
     """dqn.jl:28-31 (host-side helper; the loop evaluates the same expression on the device)."""
     slope = (end_e - start_e) / duration
@@ -51,13 +85,17 @@ def make_nn(seed=0):
 class DQNAgent:
     """q_net, target_net, Adam state, ReplayBuffer(buffer_size) and the CartPoleEnv of one dqn(config) run, on one GPU."""
 
-    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200):
+    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None):
         self.config = config
+        self.per = None if per is None else _check_per(per, config)
         self.crl_cfg = L.CrlDQNConfig(int(config.log_frequencey), int(config.total_timesteps), int(config.buffer_size),
                                       int(config.min_buff_size), float(config.lr), int(config.train_freq), int(config.target_net_freq),
                                       int(config.batch_size), float(config.gamma), float(config.epsilon_start), float(config.epsilon_end),
                                       float(config.epsilon_duration), int(max_steps), 0, seed)
-        self.handle = L.DQNHandle(self.crl_cfg, device)
+        p = self.per
+        self.handle = L.DQNHandle(self.crl_cfg, device, per=None if p is None else L.CrlDQNPEROptions(float(p.alpha), float(p.beta_start),
+                                                                                                      float(p.beta_end), float(p.beta_duration),
+                                                                                                      float(p.eps)))
         self.handle.write_params(make_nn(init_seed) if params is None else params)
 
     def close(self):
@@ -84,13 +122,15 @@ def _eval_record(global_step, report):
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256, eval_episodes=1, **logger_kw):
+def dqn(config: DQNConfig = None, per: PEROptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+        eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
     `eval_every=N > 0` adds an "Evaluation Statistics" record (eval_return_mean, eval_return_std, eval_q_bias, global_step) after the records of
     every env step that is a multiple of N: dqn_evaluate of the parameters that step left, on eval_envs fresh CartPoles x eval_episodes episodes.
     The library calls are cut at multiples of N (crl_dqn_run takes a step budget; chunking changes no bit of the run). 0 (default) keeps the record
-    stream what it was."""
+    stream what it was. `per` (a PEROptions) replays with proportional priorities instead of uniformly (crl_dqn_per_create); "Training Statistics" then
+    carries beta, the importance exponent of that update, next to the loss (the importance-weighted one). None (default) is dqn.jl."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
     if eval_every:
@@ -98,14 +138,14 @@ def dqn(config: DQNConfig = None, *, device=0, seed=0x5EED, params=None, chunk=1
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
-    agent = DQNAgent(config, device=device, seed=seed, params=params)
+    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per)
     start = time.time()
     global_step = 0
     while True:
         taken, episodes, losses = agent.handle.run(min(chunk, eval_every - global_step % eval_every) if eval_every else chunk)
         records = [(g, "Episode Statistics", dict(episode_return=r, episode_length=n, global_step=g, **{"ϵ": e},
                                                   steps_per_sec=int(g / max(time.time() - start, 1e-9)))) for r, n, g, e in episodes]
-        records += [(g, "Training Statistics", dict(loss=v)) for g, v in losses]
+        records += [(g, "Training Statistics", dict(loss=v) if agent.per is None else dict(loss=v, beta=per_beta(agent.per, g))) for g, v in losses]
         _emit(lg, records)
         global_step = agent.handle.status()["global_step"]
         if eval_every and taken > 0 and global_step % eval_every == 0:

@@ -593,6 +593,52 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
 /* envs per block of dqn_eval_kernel (a compile-time constant of the library; tests choose their block-edge sizes from it) */
 int32_t crl_dqn_eval_envs_per_block(void);
 
+/* -----------------------------------------------------------------------------------------------------
+ * Prioritized experience replay for DQN (Schaul et al. 2016, proportional variant) — no reference counterpart: dqn.jl replays uniformly. A handle
+ * made by crl_dqn_per_create runs the same ten-launch cycle with two kernels of its own in the places of the uniform draw and of the TD kernel
+ * (csrc/dqn_per.hpp, csrc/dqn.hip: dqn_per_sample_kernel, dqn_per_td_kernel); collect, the forwards, the pullbacks, the weight gradients, Adam and the
+ * target copy are shared. crl_dqn_run, crl_dqn_status_read, crl_dqn_read_params / crl_dqn_write_params / crl_dqn_init_params, crl_dqn_q_values,
+ * crl_dqn_evaluate and crl_dqn_destroy work on it unchanged; a crl_dqn_create handle is what it was, bit for bit, and the three per_* calls below fail
+ * on it with a message. Everything is on the device; no call in between reads anything back.
+ *
+ * All arithmetic below is Float64, one operation per written operator, no contraction, unless a cast is written. n = the ring's size, k = batch_size,
+ * g = the global step of the update, δ_j = td_j − Q(s_j, a_j) exactly as in the uniform loop (dqn.jl:99-107).
+ *   Tree     C = the smallest power of two >= buffer_size. tree[1 .. 2C) in heap order (tree[0] is unused and 0.0); the leaf of ring slot s is
+ *            tree[C + s]; leaves of slots >= n are 0.0; every inner node is exactly tree[2i] + tree[2i+1], one add, the left operand first. The tree is
+ *            therefore a pure function of its leaves: any repair order gives the same bits, and a restatement may rebuild it whole.
+ *   Leaves   are Float32 values, stored widened, so that the last bits of a Float64 pow do not reach the sampler:
+ *            leaf = (float)clamp(pow(|δ| + eps, alpha), 2^-100, 2^100), clamp(p) = p >= 2^-100 ? (p > 2^100 ? 2^100 : p) : 2^-100 (a NaN becomes 2^-100).
+ *            max_leaf starts at 1.0f and is the largest leaf any update has written.
+ *   Add      A transition added to slot p gets leaf[p] = max_leaf, the value as of the last completed update. The collect kernel is not involved: the
+ *            sample kernel keeps synced_step (0 on a fresh handle) and, before drawing, writes max_leaf into the min(g − synced_step, buffer_size) slots
+ *            behind the ring's write pointer (ptr − 1, ptr − 2, … modulo buffer_size), repairs their ancestors and sets synced_step = g.
+ *   Draw     seg = tree[1] / (double)k. For j = 0 .. k − 1: u_j = u53(Philox(counter (j, g lo, g hi, 0xDA), key = cfg.seed)) — stream 0xDA is new,
+ *            "prioritized draw" (the uniform draw uses 0xD9) —, target = ((double)j + u_j) · seg. Descend from i = 1 while i < C: l = tree[2i]; go
+ *            left (i = 2i) if target < l || tree[2i+1] == 0.0, otherwise target = target − l and go right (i = 2i + 1). idx[j] = i − C. Draws are
+ *            with replacement. The zero test keeps every visited node positive, so no slot >= n and no empty leaf is ever returned.
+ *   Weights  slope = (beta_end − beta_start) / beta_duration; v = slope · (double)g + beta_start; beta(g) = beta_end once v has passed it — v >
+ *            beta_end for slope >= 0, v < beta_end for slope < 0 —, otherwise v. w_j = pow((double)n · leaf[idx_j] / tree[1], −beta(g)) (the product
+ *            first), then w_j = w_j / max_j w_j: the batch maximum; there is no min tree.
+ *   Update   sq_j = w_j · (δ_j · δ_j); loss = (Σ_j sq_j, in sample order from 0.0) / (double)k — this is what crl_dqn_run logs and last_loss holds;
+ *            dz_j = −2.0 · w_j · δ_j / (double)k, evaluated left to right. The rest of the backward pass is the uniform one. The new leaf of idx_j
+ *            follows the leaf expression (duplicate indices write identical values); max_leaf is raised to the batch's largest new leaf; the ancestors
+ *            are repaired in the same launch. With beta = 0 every weight is exactly 1.0 and loss and gradient are the uniform loop's on that batch.
+ * Errors of crl_dqn_per_create, beyond crl_dqn_create's: a NULL argument; alpha, beta_start or beta_end outside 0..1; beta_duration not > 0; eps
+ * outside 1e-6..1.
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct crl_dqn_per_options { double alpha, beta_start, beta_end, beta_duration, eps; } crl_dqn_per_options;   /* 40 bytes */
+int32_t crl_dqn_per_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, int32_t device, crl_dqn** out);
+/* beta = beta(g) of the last update (beta_start before the first), total = tree[1], tree_leaves = C */
+typedef struct crl_dqn_per_status { double beta, total; float max_leaf; int32_t tree_leaves; } crl_dqn_per_status;
+int32_t crl_dqn_per_status_read(crl_dqn* h, crl_dqn_per_status* out);
+/* The state after the last update; any pointer may be NULL: leaves[buffer_size], tree[2·C], idx[k], weight[k] (normalised), abs_td[k] (|δ_j|). */
+int32_t crl_dqn_per_read(crl_dqn* h, float* leaves, double* tree, int32_t* idx, double* weight, double* abs_td);
+/* The sampler alone, on the caller's leaves and a scratch tree (training state untouched): the tree of leaves[0 .. n) with C(n) = the smallest power
+ * of two >= n is built, k draws are taken at update step gstep with the handle's seed, and their weights at beta — the same __device__ functions the
+ * cycle runs. 1 <= n <= 65536, 1 <= k <= 1024, 0 <= beta <= 1, every leaf in 2^-100..2^100; tree receives 2·C(n) doubles and may be NULL. */
+int32_t crl_dqn_per_probe(crl_dqn* h, const float* leaves, int32_t n, uint64_t gstep, int32_t k, double beta,
+                          int32_t* idx, double* weight, double* tree);
+
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
  * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·

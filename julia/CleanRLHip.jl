@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -526,6 +526,30 @@ mutable struct DQNAgent
   h::Ptr{Cvoid}
 end
 
+# Prioritized experience replay (Schaul et al. 2016, proportional; include/cleanrl_hip.h crl_dqn_per_options) — not in dqn.jl, so not a DQNConfig
+# field: `dqn(config; per = PEROptions())`. beta_duration = nothing means config.total_timesteps. Like the rest of this file, not executed here.
+Base.@kwdef struct PEROptions
+  alpha::Float64 = 0.6
+  beta_start::Float64 = 0.4
+  beta_end::Float64 = 1.0
+  beta_duration::Union{Nothing,Float64} = nothing
+  eps::Float64 = 1e-6
+end
+struct CrlDQNPEROptions; alpha::Float64; beta_start::Float64; beta_end::Float64; beta_duration::Float64; eps::Float64; end   # crl_dqn_per_options
+struct CrlDQNPERStatus; beta::Float64; total::Float64; max_leaf::Float32; tree_leaves::Int32; end                            # crl_dqn_per_status
+# beta(g) as the header pins it: the "Training Statistics" record of a PER run carries it
+function _per_beta(p::CrlDQNPEROptions, g)
+  slope = (p.beta_end - p.beta_start) / p.beta_duration
+  v = slope * Float64(g) + p.beta_start
+  slope < 0 ? (v < p.beta_end ? p.beta_end : v) : (v > p.beta_end ? p.beta_end : v)
+end
+# crl_dqn_per_status_read: (beta, total, max_leaf, tree_leaves) of a PER agent; an error on a uniform one
+function per_status(agent::DQNAgent)
+  st = Ref(CrlDQNPERStatus(0, 0, 0, 0))
+  check(ccall((:crl_dqn_per_status_read, libcrl), Int32, (Ptr{Cvoid}, Ref{CrlDQNPERStatus}), agent.h, st))
+  st[]
+end
+
 # q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64
 function q_values(agent::DQNAgent, obs::AbstractMatrix{Float64})
   o = Array(obs); n = size(o, 2); q = Matrix{Float64}(undef, 2, n)
@@ -551,14 +575,21 @@ function _default_dqn_init()
   () -> Vector{Float32}(vcat(vec.(getfield(pm, :Flux).params(getfield(pm, :make_nn)(getfield(pm, :CartPoleEnv)())))...))
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
-             chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1)
+             chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
+             per::Union{Nothing,PEROptions}=nothing)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
                      config.train_freq, config.target_net_freq, config.batch_size, config.gamma, config.epsilon_start,
                      config.epsilon_end, config.epsilon_duration, 200, 0, seed)
   h = Ref{Ptr{Cvoid}}(C_NULL)
-  check(ccall((:crl_dqn_create, libcrl), Int32, (Ref{CrlDQNConfig}, Int32, Ref{Ptr{Cvoid}}), cfg, device, h))
+  popt = per === nothing ? nothing :
+         CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
+  if popt === nothing
+    check(ccall((:crl_dqn_create, libcrl), Int32, (Ref{CrlDQNConfig}, Int32, Ref{Ptr{Cvoid}}), cfg, device, h))
+  else       # prioritized replay: the same handle type and the same calls from here on; the library validates the options
+    check(ccall((:crl_dqn_per_create, libcrl), Int32, (Ref{CrlDQNConfig}, Ref{CrlDQNPEROptions}, Int32, Ref{Ptr{Cvoid}}), cfg, popt, device, h))
+  end
   agent = DQNAgent(h[])
   finalizer(x -> ccall((:crl_dqn_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
   params === nothing && init !== nothing && (params = init())             # dqn.jl:39 make_nn(env)
@@ -581,7 +612,11 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
       @info "Episode Statistics" episode_return = e.episode_return episode_length = e.episode_length global_step = e.global_step steps_per_sec ϵ = e.epsilon
     end
     for l in @view losses[1:n_losses[]]
-      @info "Training Statistics" loss = l.loss global_step = l.global_step
+      if popt === nothing
+        @info "Training Statistics" loss = l.loss global_step = l.global_step
+      else
+        @info "Training Statistics" loss = l.loss beta = _per_beta(popt, l.global_step) global_step = l.global_step
+      end
     end
     if eval_every > 0 && global_step % eval_every == 0           # "Evaluation Statistics" after the records of that step; the calls are cut there
       ev = dqn_evaluate(agent; num_envs=eval_envs, episodes_per_env=eval_episodes).report

@@ -9,6 +9,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py a2c --total_timesteps 100000
     python scripts/run.py dqn --total_timesteps 50000
     python scripts/run.py dqn --total_timesteps 50000 --eval_every 5000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the greedy policy's held-out score and q_net's bias every 5000 steps)
+    python scripts/run.py dqn --total_timesteps 50000 --per --per_alpha 0.6 --per_beta_start 0.4 --per_beta_end 1.0 --per_beta_duration 50000 --per_eps 1e-6   (prioritized replay; --per alone takes the defaults, beta_duration = total_timesteps)
     python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
@@ -64,7 +65,13 @@ def main():
         crl.sac(cfg, "pendulum", to_terminal=True, to_tensorboard=False, **kw).close()
     else:
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_dqn_evaluate)
-        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
+        # prioritized replay (crl_dqn_per_create): --per switches it on, the --per_* options are PEROptions' fields and imply it
+        po = take((("--per_alpha", float), ("--per_beta_start", float), ("--per_beta_end", float), ("--per_beta_duration", float), ("--per_eps", float)))
+        per = None
+        if "--per" in argv or po:
+            argv = [a for a in argv if a != "--per"]
+            per = crl.PEROptions(**{name[4:]: v for name, v in po.items()})
+        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, to_terminal=True, to_tensorboard=False, **kw).close()
 
 
 if __name__ == "__main__":
