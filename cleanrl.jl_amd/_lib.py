@@ -98,7 +98,7 @@ EXPORTS = [
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_dqn_per_create", "crl_dqn_per_status_read", "crl_dqn_per_read",
-    "crl_dqn_per_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -141,6 +141,11 @@ class CrlDQNPEROptions(C.Structure):
 
 class CrlDQNPERStatus(C.Structure):
     _fields_ = [("beta", C.c_double), ("total", C.c_double), ("max_leaf", C.c_float), ("tree_leaves", C.c_int32)]
+
+
+class CrlDQNTargetOptions(C.Structure):
+    """crl_dqn_target_options: how the TD target is formed (8 bytes); {1, 0} is dqn.jl's 1-step max over target_net."""
+    _fields_ = [("n_step", C.c_int32), ("double_q", C.c_int32)]
 
 
 
@@ -310,6 +315,9 @@ def load():
     L.crl_dqn_per_status_read.argtypes = [vp, C.POINTER(CrlDQNPERStatus)]
     L.crl_dqn_per_read.argtypes = [vp, fp, dp, ip, dp, dp]
     L.crl_dqn_per_probe.argtypes = [vp, fp, C.c_int32, C.c_uint64, C.c_int32, C.c_double, ip, dp, dp]
+    L.crl_dqn_create_with.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNPEROptions), C.POINTER(CrlDQNTargetOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_target_read.argtypes = [vp, ip, ip, dp, dp, ip, dp]
+    L.crl_dqn_nstep_probe.argtypes = [vp, dp, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_double, ip, ip, dp, dp]
     L.crl_a2c_forward.argtypes = [vp, C.c_int32, dp, C.c_int32, dp]
     L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
     L.crl_a2c_eval_envs_per_block.argtypes = []
@@ -949,14 +957,19 @@ def a2c_discounted_future_rewards_host(rewards, terminals, final_value, gamma, d
 
 class DQNHandle:
     """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block). `per` (a CrlDQNPEROptions) makes it a prioritized-replay handle (crl_dqn_per_create):
-    every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available."""
+    every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available.
+    `target` (a CrlDQNTargetOptions) makes it a crl_dqn_create_with handle, with either replay: n-step / double-Q targets, and target_read /
+    nstep_probe, which are errors on the other handles."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0, per=None):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None):
         self._L = load()
         self.cfg = cfg
         self.per = per
+        self.target = target
         self._h = C.c_void_p()
-        if per is None:
+        if target is not None:
+            check(self._L.crl_dqn_create_with(C.byref(cfg), None if per is None else C.byref(per), C.byref(target), device, C.byref(self._h)))
+        elif per is None:
             check(self._L.crl_dqn_create(C.byref(cfg), device, C.byref(self._h)))
         else:
             check(self._L.crl_dqn_per_create(C.byref(cfg), C.byref(per), device, C.byref(self._h)))
@@ -1041,6 +1054,29 @@ class DQNHandle:
         check(self._L.crl_dqn_per_probe(self._h, _ptr(leaves, C.c_float), n, int(gstep), int(k), float(beta), _ptr(idx, C.c_int32), _ptr(w, C.c_double),
                                         None if tree is None else _ptr(tree, C.c_double)))
         return idx, w, tree
+
+    def target_read(self):
+        """crl_dqn_target_read → {last, m, astar int32 [k], nret, ndisc, td float64 [k]} of the last completed update"""
+        k = int(self.cfg.batch_size)
+        out = dict(last=np.zeros(k, np.int32), m=np.zeros(k, np.int32), nret=np.zeros(k, np.float64), ndisc=np.zeros(k, np.float64),
+                   astar=np.zeros(k, np.int32), td=np.zeros(k, np.float64))
+        check(self._L.crl_dqn_target_read(self._h, _ptr(out["last"], C.c_int32), _ptr(out["m"], C.c_int32), _ptr(out["nret"], C.c_double),
+                                          _ptr(out["ndisc"], C.c_double), _ptr(out["astar"], C.c_int32), _ptr(out["td"], C.c_double)))
+        return out
+
+    def nstep_probe(self, reward, terminal, ptr, idx, n_step, gamma):
+        """crl_dqn_nstep_probe: the device's n-step walk on a ring of len(reward) slots → {last, m int32 [k], nret, ndisc float64 [k]}"""
+        reward = np.ascontiguousarray(reward, np.float64); terminal = np.ascontiguousarray(terminal, np.uint8)
+        idx = np.ascontiguousarray(idx, np.int32)
+        if terminal.size != reward.size:
+            raise ValueError("nstep_probe: reward and terminal must have the same length")
+        k = idx.size
+        out = dict(last=np.zeros(max(k, 1), np.int32), m=np.zeros(max(k, 1), np.int32), nret=np.zeros(max(k, 1), np.float64),
+                   ndisc=np.zeros(max(k, 1), np.float64))
+        check(self._L.crl_dqn_nstep_probe(self._h, _ptr(reward, C.c_double), _ptr(terminal, C.c_uint8), reward.size, int(ptr), _ptr(idx, C.c_int32), k,
+                                          int(n_step), float(gamma), _ptr(out["last"], C.c_int32), _ptr(out["m"], C.c_int32),
+                                          _ptr(out["nret"], C.c_double), _ptr(out["ndisc"], C.c_double)))
+        return out
 
 
 def ddpg_param_count(obs_dim, act_dim):

@@ -19,6 +19,7 @@
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "dqn_per.hpp"
+#include "dqn_target.hpp"
 #include "replay_sample.hpp"
 #include "value_eval.hpp"
 
@@ -43,9 +44,12 @@ struct DQNDev {
   float *q, *t, *grads, *m, *v; double* betap;
   DQNCtl* ctl; crl_dqn_episode* eps; crl_dqn_loss_record* losses;
   double *rb_state, *rb_next, *rb_reward; int32_t* rb_action; uint8_t* rb_terminal;
-  double *H1, *H2, *Q, *dz, *sq, *d2, *d1;   // [2][120·k], [2][84·k], [2][2·k], [k], [k], [84·k], [120·k]
+  double *H1, *H2, *Q, *dz, *sq, *d2, *d1;   // [nets][120·k], [nets][84·k], [nets][2·k], [k], [k], [84·k], [120·k]
   int32_t* idx;                               // [k] minibatch indices into the ring
+  const int32_t* boot;                        // [k] the slots whose next_state the target bootstraps from: idx, or tgt.last on a crl_dqn_create_with handle
+  int32_t nets, pad;                          // forward passes per update: q_net(state), target_net(x) and, under double_q, q_net(x)
   PerDev per;                                 // prioritized replay (crl_dqn_per_create); all zero on a crl_dqn_create handle
+  TgtDev tgt;                                 // n-step / double-Q targets (crl_dqn_create_with); all zero on the other handles
 };
 
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
@@ -155,15 +159,16 @@ __global__ void __launch_bounds__(1024) dqn_sample_kernel(DQNDev a) {
   replay_sample<DQN_MAX_CAP>(a.cfg.seed, (uint64_t)a.ctl->global_step, (int)a.ctl->size, (int)a.cfg.batch_size, a.idx);
 }
 
-// forward of target_net(next_state) (net 1) and q_net(state) (net 0), one output element per thread (dqn.jl:99,104)
+// forward of q_net(state) (net 0), target_net(x) (net 1) and, on a double_q handle, q_net(x) (net 2), x = next_state[boot], one output element per
+// thread (dqn.jl:99,104)
 __global__ void __launch_bounds__(256) dqn_fwd1_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= 2 * QH1 * k) return;
+  if (o >= a.nets * QH1 * k) return;
   const int net = o / (QH1 * k), r = o - net * (QH1 * k), b = r / QH1, i = r - b * QH1;
-  const float* p = net ? a.t : a.q;
-  const double* x = (net ? a.rb_next : a.rb_state) + (size_t)QD * a.idx[b];
+  const float* p = net == 1 ? a.t : a.q;
+  const double* x = net ? a.rb_next + (size_t)QD * a.boot[b] : a.rb_state + (size_t)QD * a.idx[b];
   double acc = 0.0;
   for (int kk = 0; kk < QD; ++kk) acc += (double)p[QoW1 + i + QH1 * kk] * x[kk];
   acc += (double)p[Qob1 + i];
@@ -173,9 +178,9 @@ __global__ void __launch_bounds__(256) dqn_fwd2_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= 2 * QH2 * k) return;
+  if (o >= a.nets * QH2 * k) return;
   const int net = o / (QH2 * k), r = o - net * (QH2 * k), b = r / QH2, j = r - b * QH2;
-  const float* p = net ? a.t : a.q;
+  const float* p = net == 1 ? a.t : a.q;
   const double* h = a.H1 + (size_t)net * QH1 * k + (size_t)QH1 * b;
   double acc = 0.0;
 #pragma unroll 8
@@ -187,9 +192,9 @@ __global__ void __launch_bounds__(256) dqn_fwd3_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= 2 * QA * k) return;
+  if (o >= a.nets * QA * k) return;
   const int net = o / (QA * k), r = o - net * (QA * k), b = r / QA, aa = r - b * QA;
-  const float* p = net ? a.t : a.q;
+  const float* p = net == 1 ? a.t : a.q;
   const double* h = a.H2 + (size_t)net * QH2 * k + (size_t)QH2 * b;
   double acc = 0.0;
 #pragma unroll 4
@@ -223,9 +228,8 @@ __global__ void __launch_bounds__(1024) dqn_td_kernel(DQNDev a) {
 // launches. One block of 1024 each.
 // ------------------------------------------------------------------------------------------------------
 // Add (the slots the ring took since the last update get max_leaf, their ancestors are repaired), beta(g), the draw, the weights
-__global__ void __launch_bounds__(1024) dqn_per_sample_kernel(DQNDev a) {
+__device__ __forceinline__ void dqn_per_sample_body(const DQNDev& a) {
 #pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
   const PerDev& p = a.per;
   const int C = p.C, cap = (int)a.cfg.buffer_size, k = (int)a.cfg.batch_size, n = (int)a.ctl->size, ptr = (int)a.ctl->ptr;
   const int64_t g = a.ctl->global_step, behind = g - p.ctl->synced_step;
@@ -238,6 +242,10 @@ __global__ void __launch_bounds__(1024) dqn_per_sample_kernel(DQNDev a) {
   per_draw(p.tree, C, k, a.cfg.seed, (uint64_t)g, a.idx);
   per_weights(p.tree, C, n, k, beta, a.idx, p.w);
   if (threadIdx.x == 0) { p.ctl->synced_step = g; p.ctl->beta = beta; }
+}
+__global__ void __launch_bounds__(1024) dqn_per_sample_kernel(DQNDev a) {
+  if (!a.ctl->train_pending) return;
+  dqn_per_sample_body(a);
 }
 // dqn_td_kernel with importance weights, plus the priority write-back: loss = (Σ_b w_b·δ_b², sample order)/k, dz_b = −2·w_b·δ_b/k, the new leaves of
 // idx_b (duplicates write identical values: the same slot has the same δ), max_leaf raised to the batch's largest new leaf, the ancestors repaired
@@ -284,6 +292,82 @@ __global__ void __launch_bounds__(1024) dqn_per_probe_kernel(double* tree, int C
   per_repair(tree, C, C, [](int i) { return i; });
   per_draw(tree, C, k, seed, g, idx);
   per_weights(tree, C, n, k, beta, idx, w);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// n-step / double-Q targets (crl_dqn_create_with; dqn_target.hpp): these two take the places of the sampling launch and of the TD launch, PER or
+// uniform, so the cycle stays ten launches. One block of 1024 each.
+// ------------------------------------------------------------------------------------------------------
+// The draw of the handle's replay, then each sample's n-step walk in the block that drew: both samplers end on a block barrier, after which idx is
+// visible to every thread; the ring and its write pointer are those the collect launch left.
+template <bool PER>
+__global__ void __launch_bounds__(1024) dqn_tgt_sample_kernel(DQNDev a) {
+  if (!a.ctl->train_pending) return;
+  if constexpr (PER) dqn_per_sample_body(a);
+  else replay_sample<DQN_MAX_CAP>(a.cfg.seed, (uint64_t)a.ctl->global_step, (int)a.ctl->size, (int)a.cfg.batch_size, a.idx);
+  __syncthreads();
+  const TgtDev& t = a.tgt;
+  const int k = (int)a.cfg.batch_size, cap = (int)a.cfg.buffer_size, ptr = (int)a.ctl->ptr;
+  for (int j = threadIdx.x; j < k; j += blockDim.x) {
+    int last, m; double R, disc;
+    nstep_walk(a.rb_reward, a.rb_terminal, cap, ptr, (int)a.idx[j], t.n_step, a.cfg.gamma, last, m, R, disc);
+    t.last[j] = last; t.m[j] = m; t.nret[j] = R; t.ndisc[j] = disc;
+  }
+}
+// dqn_td_kernel / dqn_per_td_kernel with the target of dqn_target.hpp: a* from q_net(x) (plane 2) under double_q, next_q = target_net(x)[a*],
+// td = R + disc·next_q·(1 − terminal[last]); mse or the importance-weighted mse, dz and the PER write-back are the originals'
+template <bool PER>
+__global__ void __launch_bounds__(1024) dqn_tgt_td_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  __shared__ float lmax[16];
+  const PerDev& p = a.per;
+  const TgtDev& t = a.tgt;
+  const int k = (int)a.cfg.batch_size, C = p.C;
+  float mine = 0.0f;
+  for (int b = threadIdx.x; b < k; b += blockDim.x) {
+    const double tq0 = a.Q[(size_t)QA * k + QA * b], tq1 = a.Q[(size_t)QA * k + QA * b + 1];
+    const double sq0 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b] : 0.0, sq1 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b + 1] : 0.0;
+    const int astar = tgt_astar(t.double_q, sq0, sq1, tq0, tq1);
+    const double next_q = astar ? tq1 : tq0;
+    const int s = a.idx[b];
+    const double td = tgt_td(t.nret[b], t.ndisc[b], next_q, a.rb_terminal[t.last[b]]);
+    const double diff = td - a.Q[QA * b + a.rb_action[s]];
+    t.astar[b] = astar; t.td[b] = td;
+    if constexpr (PER) {
+      const double w = p.w[b];
+      a.sq[b] = w * (diff * diff);
+      a.dz[b] = -2.0 * w * diff / (double)k;
+      const double ad = diff < 0.0 ? -diff : diff;
+      const float leaf = per_leaf(ad, p.eps, p.alpha);
+      p.abs_td[b] = ad;
+      p.tree[C + s] = (double)leaf;
+      mine = leaf > mine ? leaf : mine;
+    } else {
+      a.sq[b] = diff * diff;
+      a.dz[b] = -2.0 * diff / (double)k;
+    }
+  }
+  if constexpr (PER) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
+    if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = mine;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double loss = 0.0;
+    for (int b = 0; b < k; ++b) loss += a.sq[b];
+    a.ctl->last_loss = loss / (double)k;
+    if constexpr (PER) {
+      float top = p.ctl->max_leaf;
+      for (int i = 0; i < (int)(blockDim.x + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
+      p.ctl->max_leaf = top;
+    }
+  }
+  if constexpr (PER) {
+    const int32_t* idx = a.idx;
+    per_repair(p.tree, C, k, [=](int i) { return (int)idx[i]; });
+  }
 }
 
 __global__ void __launch_bounds__(256) dqn_bwd2_kernel(DQNDev a) {
@@ -515,6 +599,8 @@ struct crl_dqn {
   hipGraphExec_t cycle_exec = nullptr; bool graph_failed = false;   // CRL_DQN_GRAPH=1 replays the cycle as a hipGraph
   bool per = false;                                                 // made by crl_dqn_per_create
   double* probe_tree = nullptr; int32_t* probe_idx = nullptr; double* probe_w = nullptr;   // crl_dqn_per_probe's scratch
+  bool tgt = false;                                                 // made by crl_dqn_create_with
+  void* walk_scratch = nullptr;                                     // crl_dqn_nstep_probe's scratch
 };
 
 using namespace crl;
@@ -532,12 +618,17 @@ static int qalloc(T** p, size_t n) {
 
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_collect_kernel, dim3(1), dim3(128), 0, st, d);
-  if (d.per.on) hipLaunchKernelGGL(dqn_per_sample_kernel, dim3(1), dim3(1024), 0, st, d);
+  const int nets = d.nets;
+  if (d.tgt.on && d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
+  else if (d.tgt.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
+  else if (d.per.on) hipLaunchKernelGGL(dqn_per_sample_kernel, dim3(1), dim3(1024), 0, st, d);
   else hipLaunchKernelGGL(dqn_sample_kernel, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((2 * QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((2 * QH2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd3_kernel, dim3((2 * QA * k + 255) / 256), dim3(256), 0, st, d);
-  if (d.per.on) hipLaunchKernelGGL(dqn_per_td_kernel, dim3(1), dim3(1024), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((nets * QH2 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd3_kernel, dim3((nets * QA * k + 255) / 256), dim3(256), 0, st, d);
+  if (d.tgt.on && d.per.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<true>, dim3(1), dim3(1024), 0, st, d);
+  else if (d.tgt.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<false>, dim3(1), dim3(1024), 0, st, d);
+  else if (d.per.on) hipLaunchKernelGGL(dqn_per_td_kernel, dim3(1), dim3(1024), 0, st, d);
   else hipLaunchKernelGGL(dqn_td_kernel, dim3(1), dim3(1024), 0, st, d);
   hipLaunchKernelGGL(dqn_bwd2_kernel, dim3((QH2 * k + 255) / 256), dim3(256), 0, st, d);
   hipLaunchKernelGGL(dqn_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
@@ -545,8 +636,8 @@ static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_adam_kernel, dim3(1), dim3(1024), 0, st, d);
 }
 
-// crl_dqn_create and crl_dqn_per_create: one body; `per` is null for uniform replay
-static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, int32_t device, crl_dqn** out) {
+// crl_dqn_create, crl_dqn_per_create and crl_dqn_create_with: one body; `per` is null for uniform replay, `tgt` for the 1-step max target of dqn.jl
+static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -573,8 +664,18 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   rc |= qalloc(&d.betap, 12); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
   rc |= qalloc(&d.rb_state, cap * QD); rc |= qalloc(&d.rb_next, cap * QD); rc |= qalloc(&d.rb_reward, cap);
   rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
-  rc |= qalloc(&d.H1, 2 * QH1 * k); rc |= qalloc(&d.H2, 2 * QH2 * k); rc |= qalloc(&d.Q, 2 * QA * k);
+  const size_t nets = tgt && tgt->double_q ? 3 : 2;
+  d.nets = (int32_t)nets;
+  rc |= qalloc(&d.H1, nets * QH1 * k); rc |= qalloc(&d.H2, nets * QH2 * k); rc |= qalloc(&d.Q, nets * QA * k);
   rc |= qalloc(&d.dz, k); rc |= qalloc(&d.sq, k); rc |= qalloc(&d.d2, QH2 * k); rc |= qalloc(&d.d1, QH1 * k); rc |= qalloc(&d.idx, k);
+  d.boot = d.idx;
+  if (tgt) {
+    h->tgt = true;
+    TgtDev& t = d.tgt;
+    t.on = 1; t.n_step = tgt->n_step; t.double_q = tgt->double_q;
+    rc |= qalloc(&t.last, k); rc |= qalloc(&t.m, k); rc |= qalloc(&t.astar, k); rc |= qalloc(&t.nret, k); rc |= qalloc(&t.ndisc, k); rc |= qalloc(&t.td, k);
+    d.boot = t.last;
+  }
   if (per) {
     h->per = true;
     PerDev& p = d.per;
@@ -598,6 +699,20 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   return 0;
 }
 
+#define DQN_TGT_GUARD(h, name)                                                                                           \
+  DQN_GUARD(h);                                                                                                          \
+  if (!(h)->tgt) { set_error(name ": the handle was not made by crl_dqn_create_with (only such a handle forms n-step / double-Q targets)"); return 1; }
+
+static int per_options_check(const char* who, const crl_dqn_per_options* per) {
+  const std::string w(who);
+  if (!(per->alpha >= 0.0 && per->alpha <= 1.0)) { set_error(w + ": alpha must be in 0..1"); return 1; }
+  if (!(per->beta_start >= 0.0 && per->beta_start <= 1.0)) { set_error(w + ": beta_start must be in 0..1"); return 1; }
+  if (!(per->beta_end >= 0.0 && per->beta_end <= 1.0)) { set_error(w + ": beta_end must be in 0..1"); return 1; }
+  if (!(per->beta_duration > 0.0) || !(per->beta_duration < 1e300)) { set_error(w + ": beta_duration must be > 0 and finite"); return 1; }
+  if (!(per->eps >= 1e-6 && per->eps <= 1.0)) { set_error(w + ": eps must be in 1e-6..1"); return 1; }
+  return 0;
+}
+
 #define DQN_PER_GUARD(h, name)                                                                                           \
   DQN_GUARD(h);                                                                                                          \
   if (!(h)->per) { set_error(name ": the handle was made by crl_dqn_create (uniform replay); crl_dqn_per_create makes a PER handle"); return 1; }
@@ -607,18 +722,71 @@ extern "C" {
 int32_t crl_dqn_create(const crl_dqn_config* cfg, int32_t device, crl_dqn** out) {
   if (!cfg || !out) { set_error("crl_dqn_create: null argument"); return 1; }
   *out = nullptr;
-  return dqn_create(cfg, nullptr, device, out);
+  return dqn_create(cfg, nullptr, nullptr, device, out);
 }
 
 int32_t crl_dqn_per_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, int32_t device, crl_dqn** out) {
   if (!cfg || !per || !out) { set_error("crl_dqn_per_create: null argument"); return 1; }
   *out = nullptr;
-  if (!(per->alpha >= 0.0 && per->alpha <= 1.0)) { set_error("crl_dqn_per_create: alpha must be in 0..1"); return 1; }
-  if (!(per->beta_start >= 0.0 && per->beta_start <= 1.0)) { set_error("crl_dqn_per_create: beta_start must be in 0..1"); return 1; }
-  if (!(per->beta_end >= 0.0 && per->beta_end <= 1.0)) { set_error("crl_dqn_per_create: beta_end must be in 0..1"); return 1; }
-  if (!(per->beta_duration > 0.0) || !(per->beta_duration < 1e300)) { set_error("crl_dqn_per_create: beta_duration must be > 0 and finite"); return 1; }
-  if (!(per->eps >= 1e-6 && per->eps <= 1.0)) { set_error("crl_dqn_per_create: eps must be in 1e-6..1"); return 1; }
-  return dqn_create(cfg, per, device, out);
+  if (per_options_check("crl_dqn_per_create", per)) return 1;
+  return dqn_create(cfg, per, nullptr, device, out);
+}
+
+int32_t crl_dqn_create_with(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out) {
+  if (!cfg || !out) { set_error("crl_dqn_create_with: null argument (cfg and out are required)"); return 1; }
+  *out = nullptr;
+  if (per && per_options_check("crl_dqn_create_with", per)) return 1;
+  crl_dqn_target_options t = {1, 0};
+  if (tgt) t = *tgt;
+  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_create_with: n_step must be in 1..16"); return 1; }
+  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_create_with: double_q must be 0 or 1"); return 1; }
+  return dqn_create(cfg, per, &t, device, out);
+}
+
+int32_t crl_dqn_target_read(crl_dqn* h, int32_t* last, int32_t* m, double* nret, double* ndisc, int32_t* astar, double* td) {
+  DQN_TGT_GUARD(h, "crl_dqn_target_read");
+  const TgtDev& t = h->d.tgt;
+  const size_t k = (size_t)h->cfg.batch_size;
+  if (last) CRL_HIP_CHECK(hipMemcpyAsync(last, t.last, k * 4, hipMemcpyDeviceToHost, h->stream));
+  if (m) CRL_HIP_CHECK(hipMemcpyAsync(m, t.m, k * 4, hipMemcpyDeviceToHost, h->stream));
+  if (nret) CRL_HIP_CHECK(hipMemcpyAsync(nret, t.nret, k * 8, hipMemcpyDeviceToHost, h->stream));
+  if (ndisc) CRL_HIP_CHECK(hipMemcpyAsync(ndisc, t.ndisc, k * 8, hipMemcpyDeviceToHost, h->stream));
+  if (astar) CRL_HIP_CHECK(hipMemcpyAsync(astar, t.astar, k * 4, hipMemcpyDeviceToHost, h->stream));
+  if (td) CRL_HIP_CHECK(hipMemcpyAsync(td, t.td, k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_nstep_probe(crl_dqn* h, const double* reward, const uint8_t* terminal, int32_t cap, int32_t ptr, const int32_t* idx, int32_t k,
+                            int32_t n_step, double gamma, int32_t* last, int32_t* m, double* nret, double* ndisc) {
+  DQN_TGT_GUARD(h, "crl_dqn_nstep_probe");
+  if (!reward || !terminal || !idx || !last || !m || !nret || !ndisc) { set_error("crl_dqn_nstep_probe: null argument"); return 1; }
+  if (cap < 1 || cap > DQN_MAX_CAP) { set_error("crl_dqn_nstep_probe: cap must be in 1..65536"); return 1; }
+  if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_nstep_probe: k must be in 1..1024"); return 1; }
+  if (ptr < 0 || ptr >= cap) { set_error("crl_dqn_nstep_probe: ptr must be in 0..cap-1"); return 1; }
+  if (n_step < 1 || n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_nstep_probe: n_step must be in 1..16"); return 1; }
+  for (int32_t j = 0; j < k; ++j)
+    if (idx[j] < 0 || idx[j] >= cap) { set_error("crl_dqn_nstep_probe: every idx must be in 0..cap-1"); return 1; }
+  // one allocation: reward [65536] f64 | nret [1024] f64 | ndisc [1024] f64 | idx, last, m [1024] i32 each | terminal [65536] u8
+  constexpr size_t oR = 0, oN = oR + (size_t)DQN_MAX_CAP * 8, oD = oN + (size_t)DQN_MAX_BATCH * 8, oI = oD + (size_t)DQN_MAX_BATCH * 8,
+                   oL = oI + (size_t)DQN_MAX_BATCH * 4, oM = oL + (size_t)DQN_MAX_BATCH * 4, oT = oM + (size_t)DQN_MAX_BATCH * 4, total = oT + DQN_MAX_CAP;
+  if (!h->walk_scratch) CRL_HIP_CHECK(hipMalloc(&h->walk_scratch, total));
+  char* base = static_cast<char*>(h->walk_scratch);
+  double *dR = reinterpret_cast<double*>(base + oR), *dN = reinterpret_cast<double*>(base + oN), *dD = reinterpret_cast<double*>(base + oD);
+  int32_t *dI = reinterpret_cast<int32_t*>(base + oI), *dL = reinterpret_cast<int32_t*>(base + oL), *dM = reinterpret_cast<int32_t*>(base + oM);
+  uint8_t* dT = reinterpret_cast<uint8_t*>(base + oT);
+  CRL_HIP_CHECK(hipMemcpyAsync(dR, reward, (size_t)cap * 8, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dT, terminal, (size_t)cap, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dI, idx, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_nstep_probe_kernel, dim3(1), dim3(1024), 0, h->stream, (const double*)dR, (const uint8_t*)dT, (int)cap, (int)ptr, (const int32_t*)dI,
+                     (int)k, (int)n_step, gamma, dL, dM, dN, dD);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(last, dL, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(m, dM, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(nret, dN, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(ndisc, dD, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 int32_t crl_dqn_per_status_read(crl_dqn* h, crl_dqn_per_status* out) {
@@ -686,7 +854,8 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
   DQNDev& d = h->d;
   void* ptrs[] = {d.q, d.t, d.grads, d.m, d.v, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_reward, d.rb_action,
                   d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p,
-                  d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w};
+                  d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w,
+                  d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td, h->walk_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -64,6 +64,26 @@ def _check_per(per, config):
     return per
 
 
+@dataclasses.dataclass
+class DQNTargetOptions:
+    """How the TD target is formed (crl_dqn_target_options) — not in dqn.jl, so not in DQNConfig: uncorrected n-step returns (n_step in 1..16) and
+    double Q-learning (the bootstrap action is q_net's, its value target_net's). The defaults are dqn.jl's 1-step max over target_net."""
+    n_step: int = 1
+    double_q: bool = False
+
+
+def _check_target(target):
+    """→ the DQNTargetOptions, validated before the library is touched"""
+    if not isinstance(target, DQNTargetOptions):
+        raise TypeError(f"target must be a DQNTargetOptions or None, got {type(target).__name__}")
+    n = target.n_step
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (1 <= n <= 16):
+        raise ValueError(f"DQNTargetOptions.n_step must be an integer in 1..16, got {n!r}")
+    if not isinstance(target.double_q, (bool, np.bool_)):
+        raise ValueError(f"DQNTargetOptions.double_q must be True or False, got {target.double_q!r}")
+    return target
+
+
 def linear_schedule(start_e, end_e, duration, t):
     """dqn.jl:28-31 (host-side helper; the loop evaluates the same expression on the device)."""
     slope = (end_e - start_e) / duration
@@ -85,9 +105,10 @@ def make_nn(seed=0):
 class DQNAgent:
     """q_net, target_net, Adam state, ReplayBuffer(buffer_size) and the CartPoleEnv of one dqn(config) run, on one GPU."""
 
-    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None):
+    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None):
         self.config = config
         self.per = None if per is None else _check_per(per, config)
+        self.target = None if target is None else _check_target(target)
         self.crl_cfg = L.CrlDQNConfig(int(config.log_frequencey), int(config.total_timesteps), int(config.buffer_size),
                                       int(config.min_buff_size), float(config.lr), int(config.train_freq), int(config.target_net_freq),
                                       int(config.batch_size), float(config.gamma), float(config.epsilon_start), float(config.epsilon_end),
@@ -95,7 +116,8 @@ class DQNAgent:
         p = self.per
         self.handle = L.DQNHandle(self.crl_cfg, device, per=None if p is None else L.CrlDQNPEROptions(float(p.alpha), float(p.beta_start),
                                                                                                       float(p.beta_end), float(p.beta_duration),
-                                                                                                      float(p.eps)))
+                                                                                                      float(p.eps)),
+                                  target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)))
         self.handle.write_params(make_nn(init_seed) if params is None else params)
 
     def close(self):
@@ -122,7 +144,7 @@ def _eval_record(global_step, report):
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, per: PEROptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
         eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
@@ -130,7 +152,9 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, *, device=0, seed=0x5E
     every env step that is a multiple of N: dqn_evaluate of the parameters that step left, on eval_envs fresh CartPoles x eval_episodes episodes.
     The library calls are cut at multiples of N (crl_dqn_run takes a step budget; chunking changes no bit of the run). 0 (default) keeps the record
     stream what it was. `per` (a PEROptions) replays with proportional priorities instead of uniformly (crl_dqn_per_create); "Training Statistics" then
-    carries beta, the importance exponent of that update, next to the loss (the importance-weighted one). None (default) is dqn.jl."""
+    carries beta, the importance exponent of that update, next to the loss (the importance-weighted one). None (default) is dqn.jl. `target` (a
+    DQNTargetOptions) forms the TD target from n-step returns and / or with double Q-learning (crl_dqn_create_with), with either replay; the log records
+    are unchanged, and None (default) is dqn.jl's 1-step max."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
     if eval_every:
@@ -138,7 +162,7 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, *, device=0, seed=0x5E
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
-    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per)
+    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target)
     start = time.time()
     global_step = 0
     while True:

@@ -639,6 +639,45 @@ int32_t crl_dqn_per_read(crl_dqn* h, float* leaves, double* tree, int32_t* idx, 
 int32_t crl_dqn_per_probe(crl_dqn* h, const float* leaves, int32_t n, uint64_t gstep, int32_t k, double beta,
                           int32_t* idx, double* weight, double* tree);
 
+/* -----------------------------------------------------------------------------------------------------
+ * DQN target options: double Q-learning (van Hasselt et al. 2016) and uncorrected n-step returns (as Rainbow uses them) — no reference counterpart:
+ * dqn.jl:99-100 forms a 1-step max over target_net. Both change how the TD target is formed and nothing else: the parameter layout, crl_dqn_q_values,
+ * crl_dqn_evaluate and the collect kernel are what they were, and they compose with prioritized replay, whose priority is |δ| of the new target. A
+ * handle made by crl_dqn_create_with runs the same ten-launch cycle with two kernels of its own in the places of the sampling launch and of the TD
+ * launch (csrc/dqn_target.hpp, csrc/dqn.hip: dqn_tgt_sample_kernel, dqn_tgt_td_kernel); with double_q the three forward launches carry a third pass.
+ * crl_dqn_create and crl_dqn_per_create handles keep every bit of their behaviour; the two calls below fail on them with a message naming
+ * crl_dqn_create_with. With per != NULL the handle is also a PER handle: the crl_dqn_per_* calls work on it.
+ *
+ * For sample j with slot s = idx[j], ring capacity cap = buffer_size and ptr the slot the next add will take, all as of this update; all Float64, one
+ * operation per written operator, no contraction:
+ *   R = 0.0; disc = 1.0; c = s; m = 0
+ *   repeat:  R = R + disc * reward[c];  disc = disc * gamma;  m = m + 1;  last = c
+ *            stop if terminal[last] != 0 or m == n_step
+ *            nx = (last + 1 == cap) ? 0 : last + 1
+ *            stop if nx == ptr                 (`last` is the newest transition: the horizon is cut, never wrapped into the oldest)
+ *            c = nx
+ *   x      = next_state[last]
+ *   a*     = double_q ? (q_net(x)[1] > q_net(x)[0] ? 1 : 0) : (target_net(x)[1] > target_net(x)[0] ? 1 : 0)      (the first maximum)
+ *   next_q = target_net(x)[a*]
+ *   td     = R + disc * next_q * (1.0 - (double)terminal[last])      (((disc·next_q)·(1−t)), then added to R)
+ *   δ      = td - q_net(state[s])[action[s]]
+ * disc is gamma^m by repeated multiplication; no pow is involved. Everything downstream is unchanged: the mse or the importance-weighted mse, dz, the
+ * backward pass, the Float32 gradient projection, Adam, the target copy, the PER leaf from |δ|. Episodes never mix: the env stores terminal = 1 for
+ * failure and for the step limit alike. With {n_step = 1, double_q = 0} the expressions reduce bit for bit to dqn.jl's: 0.0 + 1.0·r = r, 1.0·γ = γ.
+ * Errors of crl_dqn_create_with, beyond crl_dqn_create's and (with per) crl_dqn_per_create's: cfg or out NULL; n_step outside 1..16; double_q not 0
+ * or 1 — each names the field.
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct crl_dqn_target_options { int32_t n_step; int32_t double_q; } crl_dqn_target_options;   /* 8 bytes */
+int32_t crl_dqn_create_with(const crl_dqn_config* cfg, const crl_dqn_per_options* per /* NULL = uniform */,
+                            const crl_dqn_target_options* tgt /* NULL = {1, 0} */, int32_t device, crl_dqn** out);
+/* The k values of the last completed update (zeros before the first); any pointer may be NULL: last[k] (the slot x was read from), m[k] (the steps
+ * summed), nret[k] (R), ndisc[k] (disc), astar[k], td[k]. */
+int32_t crl_dqn_target_read(crl_dqn* h, int32_t* last, int32_t* m, double* nret, double* ndisc, int32_t* astar, double* td);
+/* The walk alone, on a ring the host wrote into scratch (training state untouched): the same __device__ function the update runs. reward[cap],
+ * terminal[cap], idx[k]; 1 <= cap <= 65536, 0 <= ptr < cap, 1 <= k <= 1024, every idx in 0..cap-1, 1 <= n_step <= 16; no pointer may be NULL. */
+int32_t crl_dqn_nstep_probe(crl_dqn* h, const double* reward, const uint8_t* terminal, int32_t cap, int32_t ptr, const int32_t* idx, int32_t k,
+                            int32_t n_step, double gamma, int32_t* last, int32_t* m, double* nret, double* ndisc);
+
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
  * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·

@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, DQNTargetOptions, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -550,6 +550,15 @@ function per_status(agent::DQNAgent)
   st[]
 end
 
+# How the TD target is formed (include/cleanrl_hip.h crl_dqn_target_options) — not in dqn.jl, so not a DQNConfig field: `dqn(config; target =
+# DQNTargetOptions(n_step = 3, double_q = true))`, with either replay. n_step in 1..16 (uncorrected n-step returns), double_q: the bootstrap action is
+# q_net's, its value target_net's. The defaults are dqn.jl's 1-step max. Like the rest of this file, not executed here.
+Base.@kwdef struct DQNTargetOptions
+  n_step::Int = 1
+  double_q::Bool = false
+end
+struct CrlDQNTargetOptions; n_step::Int32; double_q::Int32; end                                                              # crl_dqn_target_options
+
 # q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64
 function q_values(agent::DQNAgent, obs::AbstractMatrix{Float64})
   o = Array(obs); n = size(o, 2); q = Matrix{Float64}(undef, 2, n)
@@ -576,7 +585,7 @@ function _default_dqn_init()
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
              chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
-             per::Union{Nothing,PEROptions}=nothing)
+             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
@@ -585,7 +594,17 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   h = Ref{Ptr{Cvoid}}(C_NULL)
   popt = per === nothing ? nothing :
          CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
-  if popt === nothing
+  if target !== nothing     # n-step / double-Q targets, uniform or prioritized replay (a NULL per is uniform); the library validates the options
+    1 <= target.n_step <= 16 || throw(ArgumentError("dqn: target.n_step must be in 1..16, got $(target.n_step)"))
+    topt = CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0)
+    if popt === nothing
+      check(ccall((:crl_dqn_create_with, libcrl), Int32, (Ref{CrlDQNConfig}, Ptr{Cvoid}, Ref{CrlDQNTargetOptions}, Int32, Ref{Ptr{Cvoid}}),
+                  cfg, C_NULL, topt, device, h))
+    else
+      check(ccall((:crl_dqn_create_with, libcrl), Int32, (Ref{CrlDQNConfig}, Ref{CrlDQNPEROptions}, Ref{CrlDQNTargetOptions}, Int32, Ref{Ptr{Cvoid}}),
+                  cfg, popt, topt, device, h))
+    end
+  elseif popt === nothing
     check(ccall((:crl_dqn_create, libcrl), Int32, (Ref{CrlDQNConfig}, Int32, Ref{Ptr{Cvoid}}), cfg, device, h))
   else       # prioritized replay: the same handle type and the same calls from here on; the library validates the options
     check(ccall((:crl_dqn_per_create, libcrl), Int32, (Ref{CrlDQNConfig}, Ref{CrlDQNPEROptions}, Int32, Ref{Ptr{Cvoid}}), cfg, popt, device, h))
