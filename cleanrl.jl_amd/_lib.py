@@ -98,7 +98,8 @@ EXPORTS = [
     "crl_a2c_read_env", "crl_a2c_read_buffer", "crl_a2c_run_until_update", "crl_a2c_discounted_future_rewards",
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_dqn_per_create", "crl_dqn_per_status_read", "crl_dqn_per_read",
-    "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe",
+    "crl_dqn_c51_create", "crl_dqn_param_count", "crl_dqn_c51_make_nn", "crl_dqn_c51_probs", "crl_dqn_c51_read", "crl_dqn_c51_project_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -146,6 +147,16 @@ class CrlDQNPERStatus(C.Structure):
 class CrlDQNTargetOptions(C.Structure):
     """crl_dqn_target_options: how the TD target is formed (8 bytes); {1, 0} is dqn.jl's 1-step max over target_net."""
     _fields_ = [("n_step", C.c_int32), ("double_q", C.c_int32)]
+
+
+class CrlDQNC51Options(C.Structure):
+    """crl_dqn_c51_options: the categorical head's support (24 bytes): n_atoms in 2..64 on [v_min, v_max]."""
+    _fields_ = [("n_atoms", C.c_int32), ("pad", C.c_int32), ("v_min", C.c_double), ("v_max", C.c_double)]
+
+
+def dqn_c51_param_count(n_atoms):
+    """10764 + 85·2N: the trunk W1 b1 W2 b2 and the head W3(2N, 84) b3(2N)"""
+    return 10764 + 85 * 2 * int(n_atoms)
 
 
 
@@ -319,6 +330,13 @@ def load():
     L.crl_dqn_target_read.argtypes = [vp, ip, ip, dp, dp, ip, dp]
     L.crl_dqn_nstep_probe.argtypes = [vp, dp, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_double, ip, ip, dp, dp]
     L.crl_a2c_forward.argtypes = [vp, C.c_int32, dp, C.c_int32, dp]
+    L.crl_dqn_c51_create.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNC51Options), C.POINTER(CrlDQNPEROptions), C.POINTER(CrlDQNTargetOptions),
+                                     C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_param_count.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.crl_dqn_c51_make_nn.argtypes = [C.c_uint64, C.c_int32, fp, C.c_size_t]
+    L.crl_dqn_c51_probs.argtypes = [vp, dp, C.c_int32, dp]
+    L.crl_dqn_c51_read.argtypes = [vp, dp, dp]
+    L.crl_dqn_c51_project_probe.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_uint8), C.c_int32, dp]
     L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
     L.crl_a2c_eval_envs_per_block.argtypes = []
     L.crl_ddpg_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
@@ -955,19 +973,32 @@ def a2c_discounted_future_rewards_host(rewards, terminals, final_value, gamma, d
     return out
 
 
+def dqn_c51_make_nn_host(seed=0, n_atoms=51):
+    """crl_dqn_c51_make_nn: crl_dqn_make_nn's rule on the C51 shapes (the same trunk for the same seed)."""
+    out = np.zeros(dqn_c51_param_count(n_atoms), np.float32)
+    check(load().crl_dqn_c51_make_nn(seed, int(n_atoms), _ptr(out, C.c_float), out.size))
+    return out
+
+
 class DQNHandle:
     """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block). `per` (a CrlDQNPEROptions) makes it a prioritized-replay handle (crl_dqn_per_create):
     every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available.
     `target` (a CrlDQNTargetOptions) makes it a crl_dqn_create_with handle, with either replay: n-step / double-Q targets, and target_read /
-    nstep_probe, which are errors on the other handles."""
+    nstep_probe, which are errors on the other handles. `c51` (a CrlDQNC51Options) makes it a crl_dqn_c51_create handle, with either replay and any
+    target options: the head is categorical, param_count is its own, q_values are expected values, and c51_probs / c51_read / c51_project_probe
+    become available."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None):
         self._L = load()
         self.cfg = cfg
         self.per = per
         self.target = target
+        self.c51 = c51
         self._h = C.c_void_p()
-        if target is not None:
+        if c51 is not None:
+            check(self._L.crl_dqn_c51_create(C.byref(cfg), C.byref(c51), None if per is None else C.byref(per),
+                                             None if target is None else C.byref(target), device, C.byref(self._h)))
+        elif target is not None:
             check(self._L.crl_dqn_create_with(C.byref(cfg), None if per is None else C.byref(per), C.byref(target), device, C.byref(self._h)))
         elif per is None:
             check(self._L.crl_dqn_create(C.byref(cfg), device, C.byref(self._h)))
@@ -992,8 +1023,15 @@ class DQNHandle:
     def init_params(self, seed=0):
         check(self._L.crl_dqn_init_params(self._h, seed))
 
+    def param_count(self):
+        """crl_dqn_param_count: 10934, or 10764 + 85·2N on a C51 handle"""
+        n = C.c_size_t()
+        check(self._L.crl_dqn_param_count(self._h, C.byref(n)))
+        return int(n.value)
+
     def read_params(self):
-        q = np.zeros(DQN_PARAM_COUNT, np.float32); t = np.zeros(DQN_PARAM_COUNT, np.float32)
+        n = DQN_PARAM_COUNT if self.c51 is None else self.param_count()
+        q = np.zeros(n, np.float32); t = np.zeros(n, np.float32)
         check(self._L.crl_dqn_read_params(self._h, _ptr(q, C.c_float), _ptr(t, C.c_float), q.size))
         return q, t
 
@@ -1063,6 +1101,38 @@ class DQNHandle:
         check(self._L.crl_dqn_target_read(self._h, _ptr(out["last"], C.c_int32), _ptr(out["m"], C.c_int32), _ptr(out["nret"], C.c_double),
                                           _ptr(out["ndisc"], C.c_double), _ptr(out["astar"], C.c_int32), _ptr(out["td"], C.c_double)))
         return out
+
+    def c51_probs(self, obs):
+        """crl_dqn_c51_probs: softmax of q_net(obs) per action, (4, n) → (N, 2, n) float64"""
+        obs = np.asfortranarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        n = obs.shape[1]
+        N = 0 if self.c51 is None else int(self.c51.n_atoms)
+        probs = np.zeros((max(N, 1), 2, n), np.float64, order="F")
+        check(self._L.crl_dqn_c51_probs(self._h, _ptr(obs, C.c_double), n, _ptr(probs, C.c_double)))
+        return probs
+
+    def c51_read(self):
+        """crl_dqn_c51_read → {proj float64 (N, k) the projected targets, sample_loss float64 [k]} of the last completed update"""
+        k = int(self.cfg.batch_size)
+        N = 1 if self.c51 is None else int(self.c51.n_atoms)
+        out = dict(proj=np.zeros((N, k), np.float64, order="F"), sample_loss=np.zeros(k, np.float64))
+        check(self._L.crl_dqn_c51_read(self._h, _ptr(out["proj"], C.c_double), _ptr(out["sample_loss"], C.c_double)))
+        return out
+
+    def c51_project_probe(self, probs, nret, ndisc, terminal):
+        """crl_dqn_c51_project_probe: the device's projection of the rows probs (N, k) → proj (N, k)"""
+        probs = np.asfortranarray(probs, np.float64)
+        nret = np.ascontiguousarray(nret, np.float64); ndisc = np.ascontiguousarray(ndisc, np.float64)
+        terminal = np.ascontiguousarray(terminal, np.uint8)
+        k = nret.size
+        if self.c51 is not None and (probs.shape != (int(self.c51.n_atoms), k) or ndisc.size != k or terminal.size != k):
+            raise ValueError("c51_project_probe: probs must be (n_atoms, k) and nret, ndisc, terminal of length k")
+        proj = np.zeros(probs.shape, np.float64, order="F")
+        check(self._L.crl_dqn_c51_project_probe(self._h, _ptr(probs, C.c_double), _ptr(nret, C.c_double), _ptr(ndisc, C.c_double),
+                                                _ptr(terminal, C.c_uint8), k, _ptr(proj, C.c_double)))
+        return proj
 
     def nstep_probe(self, reward, terminal, ptr, idx, n_step, gamma):
         """crl_dqn_nstep_probe: the device's n-step walk on a ring of len(reward) slots → {last, m int32 [k], nret, ndisc float64 [k]}"""

@@ -20,6 +20,7 @@
 #include "ppo_ctx.hpp"
 #include "dqn_per.hpp"
 #include "dqn_target.hpp"
+#include "dqn_c51.hpp"
 #include "replay_sample.hpp"
 #include "value_eval.hpp"
 
@@ -50,6 +51,7 @@ struct DQNDev {
   int32_t nets, pad;                          // forward passes per update: q_net(state), target_net(x) and, under double_q, q_net(x)
   PerDev per;                                 // prioritized replay (crl_dqn_per_create); all zero on a crl_dqn_create handle
   TgtDev tgt;                                 // n-step / double-Q targets (crl_dqn_create_with); all zero on the other handles
+  C51Dev c51;                                 // the categorical head (crl_dqn_c51_create; such a handle also has tgt.on); all zero on the other handles
 };
 
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
@@ -391,15 +393,12 @@ __global__ void __launch_bounds__(256) dqn_bwd1_kernel(DQNDev a) {
   for (int j = 0; j < QH2; ++j) s += (double)a.q[QoW2 + j + QH2 * kk] * dd[j];
   a.d1[o] = a.H1[o] > 0.0 ? s : 0.0;
 }
-// one parameter per thread, samples summed in sample order, Float32 projection
-__global__ void __launch_bounds__(64) dqn_wgrad_kernel(DQNDev a) {
+// the weight gradients of the trunk (W1 b1 W2 b2, p < QoW3): shared by dqn_wgrad_kernel and dqn_c51_wgrad_kernel, whose trunks are the same arrays
+// every loop is unrolled 30x: the operands were written by the previous launches, so they come from the Infinity Cache
+// at ≈2 µs per dependent round trip — 4 rounds of 60 loads in flight instead of 15 of 16. The Float64 adds stay in
+// sample order.
+__device__ __forceinline__ double dqn_wgrad_trunk(const DQNDev& a, int p, int k) {
 #pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
-  const int k = (int)a.cfg.batch_size, p = blockIdx.x * 64 + threadIdx.x;
-  if (p >= QP) return;
-  // every loop is unrolled 30x: the operands were written by the previous launches, so they come from the Infinity Cache
-  // at ≈2 µs per dependent round trip — 4 rounds of 60 loads in flight instead of 15 of 16. The Float64 adds stay in
-  // sample order. Adding an exact 0.0 for samples of the other action leaves the sum unchanged.
   double g = 0.0;
   if (p < Qob1) {
     const int i = p % QH1, kk = p / QH1;
@@ -413,10 +412,23 @@ __global__ void __launch_bounds__(64) dqn_wgrad_kernel(DQNDev a) {
     const int r = p - QoW2, j = r % QH2, kk = r / QH2;
 #pragma unroll 30
     for (int b = 0; b < k; ++b) g += a.d2[(size_t)QH2 * b + j] * a.H1[(size_t)QH1 * b + kk];
-  } else if (p < QoW3) {
+  } else {
     const int j = p - Qob2;
 #pragma unroll 30
     for (int b = 0; b < k; ++b) g += a.d2[(size_t)QH2 * b + j];
+  }
+  return g;
+}
+// one parameter per thread, samples summed in sample order, Float32 projection
+__global__ void __launch_bounds__(64) dqn_wgrad_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= QP) return;
+  // Adding an exact 0.0 for samples of the other action leaves the sum unchanged.
+  double g = 0.0;
+  if (p < QoW3) {
+    g = dqn_wgrad_trunk(a, p, k);
   } else if (p < Qob3) {
     const int r = p - QoW3, aa = r % QA, j = r / QA;
 #pragma unroll 30
@@ -460,6 +472,303 @@ __global__ void __launch_bounds__(1024) dqn_adam_kernel(DQNDev a) {
     }
     c->train_pending = 0;
   }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Categorical DQN (crl_dqn_c51_create; dqn_c51.hpp). The trunk W1 b1 W2 b2 sits at the scalar net's offsets, so dqn_fwd1_kernel, dqn_fwd2_kernel and
+// dqn_bwd1_kernel run unchanged; the sampling launch is dqn_tgt_sample_kernel (a C51 handle always carries target options, {1, 0} by default). The
+// head W3(2N, 84) b3(2N) starts at QoW3; its kernels below take the places of collect, fwd3, TD, bwd2, wgrad and Adam: the cycle stays ten launches.
+// ------------------------------------------------------------------------------------------------------
+// What the collect kernel keeps in LDS besides the weights. All of it lives in the dynamic region (the weights alone pass the 64 KB static limit at
+// N >= 36), the struct first so that the float image behind it starts 16-byte aligned.
+struct C51CollectLds {
+  DQNCtl c;
+  double obs[QD], h1s[QH1], h2s[QH2], ls[2 * C51_MAX_ATOMS], qs[QA], eps_s;
+  int go, need_q, action_s, pad;
+};
+constexpr size_t C51_COLLECT_LDS = (sizeof(C51CollectLds) + 15) / 16 * 16;
+extern __shared__ __attribute__((aligned(16))) char c51_smem[];
+
+// Q(a) = Σ z·softmax(ls[a·N ..]) for both actions by a block of 128 = two waves, wave a taking action a; ends on a block barrier
+__device__ __forceinline__ void c51_block_q(const double* ls, double* qs, const C51Dev& c, double* probs) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const double delta = c51_delta(c.v_min, c.v_max, c.N);
+  double p, logp;
+  c51_softmax(lane < c.N ? ls[w * c.N + lane] : 0.0, c.N, lane, p, logp);
+  const double Q = c51_expect(p, c.v_min, delta, lane);
+  if (lane == 0) qs[w] = Q;
+  if (probs && lane < c.N) probs[w * c.N + lane] = p;
+  __syncthreads();
+}
+
+// dqn_collect_kernel with the categorical head: a greedy step forms the 2N logits (one row per thread), then Q(a) as above
+__global__ void __launch_bounds__(128) dqn_c51_collect_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  C51CollectLds& s = *reinterpret_cast<C51CollectLds*>(c51_smem);
+  float* const wq = reinterpret_cast<float*>(c51_smem + C51_COLLECT_LDS);
+  DQNCtl& c = s.c;
+  const int tid = threadIdx.x, P = a.c51.P, NA = 2 * a.c51.N, ob3 = QoW3 + NA * QH2;
+  if (tid == 0) c = *a.ctl;
+  __syncthreads();
+  if (c.train_pending || c.taken >= c.budget || c.global_step >= a.cfg.total_timesteps) return;
+  for (int p = tid; p < P; p += 128) wq[p] = a.q[p];
+  __syncthreads();
+  while (true) {
+    if (tid == 0) {
+      s.go = (!c.train_pending && c.taken < c.budget && c.global_step < a.cfg.total_timesteps) ? 1 : 0;
+      if (s.go) {
+        c.global_step += 1; c.taken += 1;
+        const uint64_t gstep = (uint64_t)c.global_step;
+        for (int i = 0; i < QD; ++i) s.obs[i] = c.env[i];
+        s.eps_s = dq_linear_schedule(a.cfg.epsilon_start, a.cfg.epsilon_end, a.cfg.epsilon_duration, (double)c.global_step);
+        if (u53(philox_env(a.cfg.seed, 0u, gstep, 0u)) < s.eps_s) {
+          s.need_q = 0;
+          s.action_s = (int)(philox_env(a.cfg.seed, 0u, gstep, 4u).x >> 31);
+        } else s.need_q = 1;
+      }
+    }
+    __syncthreads();
+    if (!s.go) break;
+    if (s.need_q) {
+      if (tid < QH1) {
+        double acc = 0.0;
+        for (int kk = 0; kk < QD; ++kk) acc += (double)wq[QoW1 + tid + QH1 * kk] * s.obs[kk];
+        acc += (double)wq[Qob1 + tid];
+        s.h1s[tid] = acc > 0.0 ? acc : 0.0;
+      }
+      __syncthreads();
+      if (tid < QH2) {
+        double acc = 0.0;
+#pragma unroll 8
+        for (int kk = 0; kk < QH1; ++kk) acc += (double)wq[QoW2 + tid + QH2 * kk] * s.h1s[kk];
+        acc += (double)wq[Qob2 + tid];
+        s.h2s[tid] = acc > 0.0 ? acc : 0.0;
+      }
+      __syncthreads();
+      if (tid < NA) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int kk = 0; kk < QH2; ++kk) acc += (double)wq[QoW3 + tid + NA * kk] * s.h2s[kk];
+        s.ls[tid] = acc + (double)wq[ob3 + tid];
+      }
+      __syncthreads();
+      c51_block_q(s.ls, s.qs, a.c51, nullptr);
+    }
+    if (tid == 0) {
+      const uint64_t gstep = (uint64_t)c.global_step;
+      const int action = s.need_q ? (s.qs[1] > s.qs[0] ? 1 : 0) : s.action_s;
+      const bool done = cartpole_step64(c.env, c.env_t, action, a.cfg.max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      const size_t p = (size_t)c.ptr;
+      for (int i = 0; i < QD; ++i) { a.rb_state[QD * p + i] = s.obs[i]; a.rb_next[QD * p + i] = c.env[i]; }
+      a.rb_action[p] = action; a.rb_reward[p] = rew; a.rb_terminal[p] = done ? 1 : 0;
+      c.ptr = c.ptr + 1 >= a.cfg.buffer_size ? 0 : c.ptr + 1;
+      c.size = c.size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c.size + 1;
+      c.episode_return += rew; c.episode_length += 1;
+      if (done) {
+        if (c.n_eps < DQN_MAX_EPS) {
+          a.eps[c.n_eps].episode_return = c.episode_return; a.eps[c.n_eps].episode_length = c.episode_length;
+          a.eps[c.n_eps].global_step = c.global_step; a.eps[c.n_eps].epsilon = s.eps_s;
+        }
+        c.n_eps += 1;
+        c.episode_length = 0; c.episode_return = 0.0;
+        env_reset64(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
+      }
+      c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step % a.cfg.train_freq == 0) ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *a.ctl = c;
+}
+
+// the 2N logits of every pass: one output element per thread, input order, bias last
+__global__ void __launch_bounds__(256) dqn_c51_fwd3_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, NA = 2 * a.c51.N, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= a.nets * NA * k) return;
+  const int net = o / (NA * k), r = o - net * (NA * k), b = r / NA, row = r - b * NA;
+  const float* p = net == 1 ? a.t : a.q;
+  const double* h = a.H2 + (size_t)net * QH2 * k + (size_t)QH2 * b;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int kk = 0; kk < QH2; ++kk) acc += (double)p[QoW3 + row + NA * kk] * h[kk];
+  a.c51.L[(size_t)net * NA * k + r] = acc + (double)p[QoW3 + NA * QH2 + row];
+}
+
+// The TD launch of a C51 handle: one wave per sample, one lane per atom, C51_TD_WAVES samples per block, ⌈k / C51_TD_WAVES⌉ blocks — the per-sample work
+// is a few thousand wave instructions that all 64 lanes issue alike, so one CU would be bound by issue slots while the others idle. Per sample: Q of
+// both actions at x from the a* net, a*, p' = softmax(target_net(x)[a*]), the projection m, softmax of the taken action's logits, loss_j = −Σ m·logp,
+// dl; under PER the new leaf from loss_j (duplicates write identical values). What needs the whole batch — the loss in sample order, max_leaf, the
+// tree's repair — is dqn_c51_adam_kernel's, the cycle's one-block launch: a launch boundary orders it behind every block here at no extra cost.
+template <bool PER>
+__global__ void __launch_bounds__(64 * C51_TD_WAVES) dqn_c51_td_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const PerDev& p = a.per;
+  const TgtDev& t = a.tgt;
+  const C51Dev& c = a.c51;
+  const int k = (int)a.cfg.batch_size, N = c.N, lane = threadIdx.x & 63, b = blockIdx.x * C51_TD_WAVES + (threadIdx.x >> 6);
+  if (b >= k) return;                                                        // whole waves leave: the wave functions below see all 64 lanes
+  const size_t plane = (size_t)2 * N * k;
+  const double delta = c51_delta(c.v_min, c.v_max, N);
+  const int s = a.idx[b], act = a.rb_action[s];
+  const double* Lt = c.L + plane + (size_t)2 * N * b;                        // target_net(x)
+  const double* Lx = t.double_q ? c.L + 2 * plane + (size_t)2 * N * b : Lt;   // the net a* is taken from
+  double p0, p1, lp;
+  c51_softmax(lane < N ? Lx[lane] : 0.0, N, lane, p0, lp);
+  const double Q0 = c51_expect(p0, c.v_min, delta, lane);
+  c51_softmax(lane < N ? Lx[N + lane] : 0.0, N, lane, p1, lp);
+  const double Q1 = c51_expect(p1, c.v_min, delta, lane);
+  const int astar = Q1 > Q0 ? 1 : 0;
+  double pp = astar ? p1 : p0, Qt = astar ? Q1 : Q0;
+  if (t.double_q) {
+    c51_softmax(lane < N ? Lt[astar * N + lane] : 0.0, N, lane, pp, lp);
+    Qt = c51_expect(pp, c.v_min, delta, lane);
+  }
+  const int last = t.last[b];
+  const double m = c51_project(pp, t.nret[b], t.ndisc[b], a.rb_terminal[last], c.v_min, c.v_max, delta, N, lane);
+  double pi, logp;
+  c51_softmax(lane < N ? c.L[(size_t)2 * N * b + act * N + lane] : 0.0, N, lane, pi, logp);
+  const double loss_j = -c51_sum(m * logp);
+  const double wj = PER ? p.w[b] : 1.0;
+  if (lane < N) {
+    c.dl[(size_t)N * b + lane] = wj * (pi - m) / (double)k;
+    c.proj[(size_t)N * b + lane] = m;
+  }
+  if (lane == 0) {
+    c.sloss[b] = loss_j;
+    a.sq[b] = wj * loss_j;
+    t.astar[b] = astar; t.td[b] = tgt_td(t.nret[b], t.ndisc[b], Qt, a.rb_terminal[last]);
+    if constexpr (PER) {
+      p.abs_td[b] = loss_j;
+      p.tree[p.C + s] = (double)per_leaf(loss_j, p.eps, p.alpha);
+    }
+  }
+}
+
+// d2_j = relu'(H2_j) · Σ_i W3[a·N + i, j] · dl_i, atoms ascending
+__global__ void __launch_bounds__(256) dqn_c51_bwd2_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, N = a.c51.N, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= QH2 * k) return;
+  const int b = o / QH2, j = o - b * QH2;
+  const float* w3 = a.q + QoW3 + a.rb_action[a.idx[b]] * N + 2 * N * j;
+  const double* dl = a.c51.dl + (size_t)N * b;
+  double s = 0.0;
+#pragma unroll 4
+  for (int i = 0; i < N; ++i) s += (double)w3[i] * dl[i];
+  a.d2[o] = a.H2[o] > 0.0 ? s : 0.0;
+}
+// dqn_wgrad_kernel with the head's 2N rows: row a·N + i takes dl_i of the samples whose action is a, an exact 0.0 of the others
+__global__ void __launch_bounds__(64) dqn_c51_wgrad_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, N = a.c51.N, NA = 2 * N, ob3 = QoW3 + NA * QH2, p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.c51.P) return;
+  double g = 0.0;
+  if (p < QoW3) {
+    g = dqn_wgrad_trunk(a, p, k);
+  } else if (p < ob3) {
+    const int r = p - QoW3, row = r % NA, j = r / NA, aa = row / N, i = row - aa * N;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) {
+      const double t = a.c51.dl[(size_t)N * b + i] * a.H2[(size_t)QH2 * b + j];
+      if (a.rb_action[a.idx[b]] == aa) g += t;
+    }
+  } else {
+    const int row = p - ob3, aa = row / N, i = row - aa * N;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) {
+      const double t = a.c51.dl[(size_t)N * b + i];
+      if (a.rb_action[a.idx[b]] == aa) g += t;
+    }
+  }
+  a.grads[p] = (float)g;
+}
+// dqn_adam_kernel over the C51 handle's P parameters: the same six arrays, the head's two being longer. Being the cycle's one-block launch behind the
+// TD launch, it first does what needs the whole batch: loss = (Σ_b sq_b, sample order) / k, and under PER max_leaf raised to the batch's largest new
+// leaf and the ancestors of the written leaves repaired (dqn_tgt_td_kernel's tail).
+__global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int tid = threadIdx.x, nth = blockDim.x, P = a.c51.P, ob3 = QoW3 + 2 * a.c51.N * QH2;
+  if (tid == 0) {
+    const int k = (int)a.cfg.batch_size;
+    double loss = 0.0;
+    for (int b = 0; b < k; ++b) loss += a.sq[b];
+    a.ctl->last_loss = loss / (double)k;
+  }
+  if (a.per.on) {
+    __shared__ float lmax[16];
+    const PerDev& p = a.per;
+    const int k = (int)a.cfg.batch_size;
+    const int32_t* idx = a.idx;
+    float mine = 0.0f;
+    for (int b = tid; b < k; b += nth) { const float leaf = (float)p.tree[p.C + idx[b]]; mine = leaf > mine ? leaf : mine; }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
+    if ((tid & 63) == 0) lmax[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+      float top = p.ctl->max_leaf;
+      for (int i = 0; i < (nth + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
+      p.ctl->max_leaf = top;
+    }
+    per_repair(p.tree, p.C, k, [=](int i) { return (int)idx[i]; });
+  }
+  const int64_t gstep = a.ctl->global_step;
+  const bool copy = gstep % a.cfg.target_net_freq == 0;
+  for (int p = tid; p < P; p += nth) {
+    const int arr = p < Qob1 ? 0 : p < QoW2 ? 1 : p < Qob2 ? 2 : p < QoW3 ? 3 : p < ob3 ? 4 : 5;
+    float mi, vi, w;
+    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
+    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
+    if (copy) a.t[p] = w;
+  }
+  __syncthreads();
+  if (tid < 6) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
+  if (tid == 0) {
+    DQNCtl* c = a.ctl;
+    c->n_updates += 1;
+    if (gstep % a.cfg.log_frequency == 0) {
+      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
+      c->n_losses += 1;
+    }
+    c->train_pending = 0;
+  }
+}
+
+// crl_dqn_q_values and crl_dqn_c51_probs on a C51 handle: dqn_q_kernel's trunk, the 2N logits, then Q(a) and / or the probabilities (N, 2, n)
+__global__ void __launch_bounds__(128) dqn_c51_q_kernel(const float* __restrict__ q, C51Dev c, const double* __restrict__ obs, int n,
+                                                        double* __restrict__ out_q, double* __restrict__ out_p) {
+#pragma clang fp contract(off)
+  __shared__ double h1s[QH1], h2s[QH2], ls[2 * C51_MAX_ATOMS], qs[QA];
+  const int b = blockIdx.x, tid = threadIdx.x, NA = 2 * c.N;
+  if (b >= n) return;
+  if (tid < QH1) {
+    double acc = 0.0;
+    for (int kk = 0; kk < QD; ++kk) acc += (double)q[QoW1 + tid + QH1 * kk] * obs[(size_t)QD * b + kk];
+    acc += (double)q[Qob1 + tid];
+    h1s[tid] = acc > 0.0 ? acc : 0.0;
+  }
+  __syncthreads();
+  if (tid < QH2) {
+    double acc = 0.0;
+    for (int kk = 0; kk < QH1; ++kk) acc += (double)q[QoW2 + tid + QH2 * kk] * h1s[kk];
+    acc += (double)q[Qob2 + tid];
+    h2s[tid] = acc > 0.0 ? acc : 0.0;
+  }
+  __syncthreads();
+  if (tid < NA) {
+    double acc = 0.0;
+    for (int kk = 0; kk < QH2; ++kk) acc += (double)q[QoW3 + tid + NA * kk] * h2s[kk];
+    ls[tid] = acc + (double)q[QoW3 + NA * QH2 + tid];
+  }
+  __syncthreads();
+  c51_block_q(ls, qs, c, out_p ? out_p + (size_t)NA * b : nullptr);
+  if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
 }
 
 __global__ void dqn_init_kernel(DQNDev a) {
@@ -586,6 +895,92 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_eval_kernel(const flo
   value_eval_trace_tail(ev, env, row, lane);
 }
 
+// dqn_eval_kernel with the categorical head: the same one-wave-per-env structure with ONE staging barrier. The net (up to 86.6 KB at N = 64) and the
+// waves' strips live in dynamic LDS. Lane i < N forms the logits of atom i for both actions (rows i and N + i: two chains side by side), then the two
+// softmaxes and expectations run wave-wide (dqn_c51.hpp: no LDS in them); Q(a) has the bits crl_dqn_q_values gives.
+struct C51EvalWaveLds { double h1[QH1], h2[QH2]; };
+__global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_c51_eval_kernel(const float* __restrict__ q, C51Dev c, int max_steps, double gamma,
+                                                                           ValueEvalArgs ev) {
+#pragma clang fp contract(off)
+  C51EvalWaveLds* const wl = reinterpret_cast<C51EvalWaveLds*>(c51_smem);
+  float* const wq = reinterpret_cast<float*>(c51_smem + sizeof(C51EvalWaveLds) * DQN_EVAL_WAVES);
+  static_assert(sizeof(C51EvalWaveLds) % 16 == 0, "the weight image starts 16-byte aligned");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * DQN_EVAL_WAVES + w, N = c.N, NA = 2 * N, ob3 = QoW3 + NA * QH2;
+  for (int p = threadIdx.x; p < c.P; p += 64 * DQN_EVAL_WAVES) wq[p] = q[p];
+  __syncthreads();                       // the only block barrier of the kernel
+  if (env >= ev.n) return;
+  double* const h1w = wl[w].h1;
+  double* const h2w = wl[w].h2;
+  const double delta = c51_delta(c.v_min, c.v_max, N);
+  const int u1b = lane + 64 < QH1 ? lane + 64 : lane, u2b = lane + 64 < QH2 ? lane + 64 : lane;
+  const int r0 = lane < N ? lane : 0, r1 = N + r0;   // a lane past N repeats atom 0 and its results are masked by the wave functions
+  int64_t row = 0;
+  for (int j = 0; j < ev.episodes; ++j) {
+    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
+    int t = 0, length = 0;
+    const size_t slot = (size_t)j * ev.n + env;
+    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
+    while (true) {
+      {
+        double acc = 0.0, acc2 = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < QD; ++kk) {
+          acc += (double)wq[QoW1 + lane + QH1 * kk] * s[kk];
+          acc2 += (double)wq[QoW1 + u1b + QH1 * kk] * s[kk];
+        }
+        acc += (double)wq[Qob1 + lane];
+        acc2 += (double)wq[Qob1 + u1b];
+        h1w[lane] = acc > 0.0 ? acc : 0.0;
+        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
+      }
+      wave_lds_fence();
+      {
+        double acc = 0.0, acc2 = 0.0;
+#pragma unroll 8
+        for (int kk = 0; kk < QH1; ++kk) {
+          const double h = h1w[kk];
+          acc += (double)wq[QoW2 + lane + QH2 * kk] * h;
+          acc2 += (double)wq[QoW2 + u2b + QH2 * kk] * h;
+        }
+        acc += (double)wq[Qob2 + lane];
+        acc2 += (double)wq[Qob2 + u2b];
+        h2w[lane] = acc > 0.0 ? acc : 0.0;
+        if (lane + 64 < QH2) h2w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
+      }
+      wave_lds_fence();
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll 4
+      for (int kk = 0; kk < QH2; ++kk) {
+        const double h = h2w[kk];
+        a0 += (double)wq[QoW3 + r0 + NA * kk] * h;
+        a1 += (double)wq[QoW3 + r1 + NA * kk] * h;
+      }
+      const double l0 = a0 + (double)wq[ob3 + r0], l1 = a1 + (double)wq[ob3 + r1];
+      double p0, p1, lp;
+      c51_softmax(l0, N, lane, p0, lp);
+      const double q0 = c51_expect(p0, c.v_min, delta, lane);
+      c51_softmax(l1, N, lane, p1, lp);
+      const double q1 = c51_expect(p1, c.v_min, delta, lane);
+      const int action = q1 > q0 ? 1 : 0;
+      if (lane == 0) {
+        if (length == 0) ev.v0[slot] = action ? q1 : q0;
+        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
+      }
+      row += 1;
+      const bool done = cartpole_step64(s, t, action, max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      ret += rew;
+      disc_ret += disc * rew;
+      disc = disc * gamma;
+      length += 1;
+      wave_lds_fence();
+      if (done) break;
+    }
+    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
+  }
+  value_eval_trace_tail(ev, env, row, lane);
+}
+
 }  // namespace crl
 
 struct crl_dqn {
@@ -601,6 +996,9 @@ struct crl_dqn {
   double* probe_tree = nullptr; int32_t* probe_idx = nullptr; double* probe_w = nullptr;   // crl_dqn_per_probe's scratch
   bool tgt = false;                                                 // made by crl_dqn_create_with
   void* walk_scratch = nullptr;                                     // crl_dqn_nstep_probe's scratch
+  bool c51 = false;                                                 // made by crl_dqn_c51_create
+  size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, or 10764 + 85·2N on a C51 handle
+  void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's scratch
 };
 
 using namespace crl;
@@ -616,7 +1014,29 @@ static int qalloc(T** p, size_t n) {
   return 0;
 }
 
+static size_t c51_collect_lds(int P) { return C51_COLLECT_LDS + (size_t)P * 4; }
+static size_t c51_eval_lds(int P) { return sizeof(C51EvalWaveLds) * DQN_EVAL_WAVES + (size_t)P * 4; }
+
+// the ten launches of a crl_dqn_c51_create handle: the sampling launch, fwd1, fwd2 and bwd1 are the scalar handles' kernels
+static void enqueue_c51_cycle(hipStream_t st, const DQNDev& d, int k) {
+  const int nets = d.nets, NA = 2 * d.c51.N, P = d.c51.P;
+  hipLaunchKernelGGL(dqn_c51_collect_kernel, dim3(1), dim3(128), c51_collect_lds(P), st, d);
+  if (d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
+  else hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((nets * QH2 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_c51_fwd3_kernel, dim3((nets * NA * k + 255) / 256), dim3(256), 0, st, d);
+  const dim3 td_grid((k + C51_TD_WAVES - 1) / C51_TD_WAVES), td_block(64 * C51_TD_WAVES);
+  if (d.per.on) hipLaunchKernelGGL(dqn_c51_td_kernel<true>, td_grid, td_block, 0, st, d);
+  else hipLaunchKernelGGL(dqn_c51_td_kernel<false>, td_grid, td_block, 0, st, d);
+  hipLaunchKernelGGL(dqn_c51_bwd2_kernel, dim3((QH2 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_c51_wgrad_kernel, dim3((P + 63) / 64), dim3(64), 0, st, d);
+  hipLaunchKernelGGL(dqn_c51_adam_kernel, dim3(1), dim3(1024), 0, st, d);
+}
+
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
+  if (d.c51.on) { enqueue_c51_cycle(st, d, k); return; }
   hipLaunchKernelGGL(dqn_collect_kernel, dim3(1), dim3(128), 0, st, d);
   const int nets = d.nets;
   if (d.tgt.on && d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
@@ -636,8 +1056,10 @@ static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_adam_kernel, dim3(1), dim3(1024), 0, st, d);
 }
 
-// crl_dqn_create, crl_dqn_per_create and crl_dqn_create_with: one body; `per` is null for uniform replay, `tgt` for the 1-step max target of dqn.jl
-static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out) {
+// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with and crl_dqn_c51_create: one body; `per` is null for uniform replay, `tgt` for the 1-step max
+// target of dqn.jl, `c51` for the scalar head
+static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out,
+                          const crl_dqn_c51_options* c51 = nullptr) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -660,7 +1082,9 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   const size_t cap = (size_t)cfg->buffer_size, k = (size_t)cfg->batch_size;
   DQNDev& d = h->d;
   int rc = 0;
-  rc |= qalloc(&d.q, QP); rc |= qalloc(&d.t, QP); rc |= qalloc(&d.grads, QP); rc |= qalloc(&d.m, QP); rc |= qalloc(&d.v, QP);
+  const size_t NP = c51 ? (size_t)QoW3 + 85 * 2 * (size_t)c51->n_atoms : (size_t)QP;
+  h->P = NP;
+  rc |= qalloc(&d.q, NP); rc |= qalloc(&d.t, NP); rc |= qalloc(&d.grads, NP); rc |= qalloc(&d.m, NP); rc |= qalloc(&d.v, NP);
   rc |= qalloc(&d.betap, 12); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
   rc |= qalloc(&d.rb_state, cap * QD); rc |= qalloc(&d.rb_next, cap * QD); rc |= qalloc(&d.rb_reward, cap);
   rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
@@ -689,6 +1113,22 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
       if (hipMemcpy(p.ctl, &pc, sizeof(pc), hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of the PER control block failed"); rc = 1; }
     }
   }
+  if (c51) {
+    h->c51 = true;
+    C51Dev& c = d.c51;
+    const size_t N = (size_t)c51->n_atoms;
+    c.on = 1; c.N = c51->n_atoms; c.P = (int32_t)NP; c.v_min = c51->v_min; c.v_max = c51->v_max;
+    rc |= qalloc(&c.L, nets * 2 * N * k); rc |= qalloc(&c.dl, N * k); rc |= qalloc(&c.proj, N * k); rc |= qalloc(&c.sloss, k);
+    // the net in LDS passes the 64 KB a launch gets without asking at N >= 36; the CU has 160 KB. The attribute belongs to the kernel, not to the
+    // handle, so it is set to what the largest head needs: handles of different N live side by side.
+    constexpr int PMAX = QoW3 + 85 * 2 * C51_MAX_ATOMS;
+    if (!rc && (hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_c51_collect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c51_collect_lds(PMAX)) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_c51_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)c51_eval_lds(PMAX)) != hipSuccess)) {
+      set_error("crl_dqn_c51_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
+    }
+  }
   if (rc) { crl_dqn_destroy(h); return 1; }
   double bp[12];
   for (int i = 0; i < 6; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
@@ -712,6 +1152,10 @@ static int per_options_check(const char* who, const crl_dqn_per_options* per) {
   if (!(per->eps >= 1e-6 && per->eps <= 1.0)) { set_error(w + ": eps must be in 1e-6..1"); return 1; }
   return 0;
 }
+
+#define DQN_C51_GUARD(h, name)                                                                                           \
+  DQN_GUARD(h);                                                                                                          \
+  if (!(h)->c51) { set_error(name ": the handle has a scalar head; crl_dqn_c51_create makes a categorical (C51) handle"); return 1; }
 
 #define DQN_PER_GUARD(h, name)                                                                                           \
   DQN_GUARD(h);                                                                                                          \
@@ -741,6 +1185,87 @@ int32_t crl_dqn_create_with(const crl_dqn_config* cfg, const crl_dqn_per_options
   if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_create_with: n_step must be in 1..16"); return 1; }
   if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_create_with: double_q must be 0 or 1"); return 1; }
   return dqn_create(cfg, per, &t, device, out);
+}
+
+int32_t crl_dqn_c51_create(const crl_dqn_config* cfg, const crl_dqn_c51_options* c51, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt,
+                           int32_t device, crl_dqn** out) {
+  if (!cfg || !c51 || !out) { set_error("crl_dqn_c51_create: null argument (cfg, c51 and out are required)"); return 1; }
+  *out = nullptr;
+  if (c51->n_atoms < 2 || c51->n_atoms > C51_MAX_ATOMS) { set_error("crl_dqn_c51_create: n_atoms must be in 2..64"); return 1; }
+  if (!(c51->v_min > -1e300 && c51->v_min < 1e300)) { set_error("crl_dqn_c51_create: v_min must be finite"); return 1; }
+  if (!(c51->v_max > -1e300 && c51->v_max < 1e300)) { set_error("crl_dqn_c51_create: v_max must be finite"); return 1; }
+  if (!(c51->v_min < c51->v_max)) { set_error("crl_dqn_c51_create: v_min must be < v_max"); return 1; }
+  if (per && per_options_check("crl_dqn_c51_create", per)) return 1;
+  crl_dqn_target_options t = {1, 0};
+  if (tgt) t = *tgt;
+  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_c51_create: n_step must be in 1..16"); return 1; }
+  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_c51_create: double_q must be 0 or 1"); return 1; }
+  return dqn_create(cfg, per, &t, device, out, c51);
+}
+
+int32_t crl_dqn_param_count(crl_dqn* h, size_t* n) {
+  DQN_GUARD(h);
+  if (!n) { set_error("crl_dqn_param_count: null argument"); return 1; }
+  *n = h->P;
+  return 0;
+}
+
+int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* probs) {
+  DQN_C51_GUARD(h, "crl_dqn_c51_probs");
+  if (!h->params_set) { set_error("crl_dqn_c51_probs: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !probs))) { set_error("crl_dqn_c51_probs: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  const size_t N = (size_t)n, NA = 2 * (size_t)h->d.c51.N, need = N * (QD + NA) * 8;
+  if (h->stage_bytes < need) {
+    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
+    h->stage = nullptr; h->stage_bytes = 0;
+    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
+    h->stage_bytes = need;
+  }
+  double* so = static_cast<double*>(h->stage);
+  double* sp = so + N * QD;
+  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_c51_read(crl_dqn* h, double* proj, double* sample_loss) {
+  DQN_C51_GUARD(h, "crl_dqn_c51_read");
+  const size_t k = (size_t)h->cfg.batch_size, N = (size_t)h->d.c51.N;
+  if (proj) CRL_HIP_CHECK(hipMemcpyAsync(proj, h->d.c51.proj, k * N * 8, hipMemcpyDeviceToHost, h->stream));
+  if (sample_loss) CRL_HIP_CHECK(hipMemcpyAsync(sample_loss, h->d.c51.sloss, k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_c51_project_probe(crl_dqn* h, const double* probs, const double* nret, const double* ndisc, const uint8_t* terminal, int32_t k,
+                                  double* proj) {
+  DQN_C51_GUARD(h, "crl_dqn_c51_project_probe");
+  if (!probs || !nret || !ndisc || !terminal || !proj) { set_error("crl_dqn_c51_project_probe: null argument"); return 1; }
+  if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_c51_project_probe: k must be in 1..1024"); return 1; }
+  // one allocation: probs [1024·64] f64 | proj [1024·64] f64 | nret [1024] f64 | ndisc [1024] f64 | terminal [1024] u8
+  constexpr size_t rows = (size_t)DQN_MAX_BATCH * C51_MAX_ATOMS * 8, oP = 0, oM = oP + rows, oR = oM + rows, oD = oR + (size_t)DQN_MAX_BATCH * 8,
+                   oT = oD + (size_t)DQN_MAX_BATCH * 8, total = oT + DQN_MAX_BATCH;
+  if (!h->proj_scratch) CRL_HIP_CHECK(hipMalloc(&h->proj_scratch, total));
+  char* base = static_cast<char*>(h->proj_scratch);
+  double *dP = reinterpret_cast<double*>(base + oP), *dM = reinterpret_cast<double*>(base + oM), *dR = reinterpret_cast<double*>(base + oR),
+         *dD = reinterpret_cast<double*>(base + oD);
+  uint8_t* dT = reinterpret_cast<uint8_t*>(base + oT);
+  const C51Dev& c = h->d.c51;
+  const size_t K = (size_t)k, N = (size_t)c.N;
+  CRL_HIP_CHECK(hipMemcpyAsync(dP, probs, K * N * 8, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dR, nret, K * 8, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dD, ndisc, K * 8, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dT, terminal, K, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_c51_project_probe_kernel, dim3(1), dim3(64 * C51_TD_WAVES), 0, h->stream, (const double*)dP, (const double*)dR, (const double*)dD,
+                     (const uint8_t*)dT, (int)k, (int)c.N, c.v_min, c.v_max, dM);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(proj, dM, K * N * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 int32_t crl_dqn_target_read(crl_dqn* h, int32_t* last, int32_t* m, double* nret, double* ndisc, int32_t* astar, double* td) {
@@ -855,7 +1380,8 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
   void* ptrs[] = {d.q, d.t, d.grads, d.m, d.v, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_reward, d.rb_action,
                   d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p,
                   d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w,
-                  d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td, h->walk_scratch};
+                  d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td, h->walk_scratch,
+                  d.c51.L, d.c51.dl, d.c51.proj, d.c51.sloss, h->proj_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -864,7 +1390,7 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
 
 int32_t crl_dqn_write_params(crl_dqn* h, const float* q_params, size_t n) {
   DQN_GUARD(h);
-  if (!q_params || n != (size_t)QP) { set_error("crl_dqn_write_params: expected 10934 floats"); return 1; }
+  if (!q_params || n != h->P) { set_error("crl_dqn_write_params: expected " + std::to_string(h->P) + " floats"); return 1; }
   CRL_HIP_CHECK(hipMemcpyAsync(h->d.q, q_params, n * 4, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(h->d.t, q_params, n * 4, hipMemcpyHostToDevice, h->stream));   // dqn.jl:40 deepcopy(q_net)
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -873,14 +1399,14 @@ int32_t crl_dqn_write_params(crl_dqn* h, const float* q_params, size_t n) {
 }
 int32_t crl_dqn_init_params(crl_dqn* h, uint64_t seed) {
   DQN_GUARD(h);
-  std::vector<float> w((size_t)QP);
-  if (crl_dqn_make_nn(seed, w.data(), w.size())) return 1;
+  std::vector<float> w(h->P);
+  if (h->c51 ? crl_dqn_c51_make_nn(seed, h->d.c51.N, w.data(), w.size()) : crl_dqn_make_nn(seed, w.data(), w.size())) return 1;
   return crl_dqn_write_params(h, w.data(), w.size());
 }
 
 int32_t crl_dqn_read_params(crl_dqn* h, float* q_params, float* target_params, size_t n) {
   DQN_GUARD(h);
-  if (!q_params || n != (size_t)QP) { set_error("crl_dqn_read_params: expected 10934 floats"); return 1; }
+  if (!q_params || n != h->P) { set_error("crl_dqn_read_params: expected " + std::to_string(h->P) + " floats"); return 1; }
   CRL_HIP_CHECK(hipMemcpyAsync(q_params, h->d.q, n * 4, hipMemcpyDeviceToHost, h->stream));
   if (target_params) CRL_HIP_CHECK(hipMemcpyAsync(target_params, h->d.t, n * 4, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -963,7 +1489,8 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   double* so = static_cast<double*>(h->stage);
   double* sq = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(128), 0, h->stream, h->d.q, so, n, sq);
+  if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
+  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(128), 0, h->stream, h->d.q, so, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -979,8 +1506,10 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
   ValueEvalArgs ev;
   if (value_eval_scratch(h->eval, cfg, ev)) return 1;
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
-  hipLaunchKernelGGL(dqn_eval_kernel, dim3((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), dim3(64 * DQN_EVAL_WAVES), 0, h->stream,
-                     (const float*)h->d.q, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  const dim3 grid((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), block(64 * DQN_EVAL_WAVES);
+  if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.c51,
+                                 (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  else hipLaunchKernelGGL(dqn_eval_kernel, grid, block, 0, h->stream, (const float*)h->d.q, (int)h->cfg.max_steps, h->cfg.gamma, ev);
   CRL_HIP_CHECK(hipGetLastError());
   return value_eval_finish(h->stream, ev, report, returns, lengths, disc_returns, v0, trace_action);
 }

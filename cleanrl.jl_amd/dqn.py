@@ -84,6 +84,31 @@ def _check_target(target):
     return target
 
 
+@dataclasses.dataclass
+class C51Options:
+    """The categorical value distribution of Bellemare et al. 2017 (crl_dqn_c51_options) — not in dqn.jl, so not in DQNConfig: n_atoms atoms (2..64)
+    evenly spaced on [v_min, v_max]. CartPole at max_steps = 200 and gamma = 0.99 returns at most 86.6, so the default support covers it."""
+    n_atoms: int = 51
+    v_min: float = 0.0
+    v_max: float = 100.0
+
+
+def _check_c51(dist):
+    """→ the C51Options, validated before the library is touched"""
+    if not isinstance(dist, C51Options):
+        raise TypeError(f"dist must be a C51Options or None, got {type(dist).__name__}")
+    n = dist.n_atoms
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (2 <= n <= 64):
+        raise ValueError(f"C51Options.n_atoms must be an integer in 2..64, got {n!r}")
+    for name in ("v_min", "v_max"):
+        v = getattr(dist, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"C51Options.{name} must be a finite number, got {v!r}")
+    if not (dist.v_min < dist.v_max):
+        raise ValueError(f"C51Options.v_min must be < v_max, got {dist.v_min!r} >= {dist.v_max!r}")
+    return dist
+
+
 def linear_schedule(start_e, end_e, duration, t):
     """dqn.jl:28-31 (host-side helper; the loop evaluates the same expression on the device)."""
     slope = (end_e - start_e) / duration
@@ -102,11 +127,25 @@ def make_nn(seed=0):
     return out
 
 
+def make_nn_c51(seed=0, n_atoms=51):
+    """make_nn with the categorical head Dense(84, 2·n_atoms) (row a·n_atoms + i = atom i of action a): the same rule, and for the same seed the same
+    trunk draws, on 10764 + 85·2·n_atoms numbers."""
+    rng = np.random.default_rng(seed)
+    rows3 = 2 * int(n_atoms)
+    out = np.zeros(L.dqn_c51_param_count(n_atoms), np.float32)
+    off = np.cumsum([0, 480, 120, 10080, 84, 84 * rows3, rows3])
+    for i, (rows, cols) in zip((0, 2, 4), ((120, 4), (84, 120), (rows3, 84))):
+        lim = np.sqrt(6.0 / (rows + cols))
+        out[off[i]:off[i + 1]] = rng.uniform(-lim, lim, rows * cols).astype(np.float32)
+    return out
+
+
 class DQNAgent:
     """q_net, target_net, Adam state, ReplayBuffer(buffer_size) and the CartPoleEnv of one dqn(config) run, on one GPU."""
 
-    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None):
+    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None, dist=None):
         self.config = config
+        self.dist = None if dist is None else _check_c51(dist)
         self.per = None if per is None else _check_per(per, config)
         self.target = None if target is None else _check_target(target)
         self.crl_cfg = L.CrlDQNConfig(int(config.log_frequencey), int(config.total_timesteps), int(config.buffer_size),
@@ -117,8 +156,12 @@ class DQNAgent:
         self.handle = L.DQNHandle(self.crl_cfg, device, per=None if p is None else L.CrlDQNPEROptions(float(p.alpha), float(p.beta_start),
                                                                                                       float(p.beta_end), float(p.beta_duration),
                                                                                                       float(p.eps)),
-                                  target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)))
-        self.handle.write_params(make_nn(init_seed) if params is None else params)
+                                  target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)),
+                                  c51=None if self.dist is None else L.CrlDQNC51Options(int(self.dist.n_atoms), 0, float(self.dist.v_min),
+                                                                                        float(self.dist.v_max)))
+        if params is None:
+            params = make_nn(init_seed) if self.dist is None else make_nn_c51(init_seed, self.dist.n_atoms)
+        self.handle.write_params(params)
 
     def close(self):
         self.handle.close()
@@ -144,7 +187,7 @@ def _eval_record(global_step, report):
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
         eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
@@ -154,7 +197,9 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     stream what it was. `per` (a PEROptions) replays with proportional priorities instead of uniformly (crl_dqn_per_create); "Training Statistics" then
     carries beta, the importance exponent of that update, next to the loss (the importance-weighted one). None (default) is dqn.jl. `target` (a
     DQNTargetOptions) forms the TD target from n-step returns and / or with double Q-learning (crl_dqn_create_with), with either replay; the log records
-    are unchanged, and None (default) is dqn.jl's 1-step max."""
+    are unchanged, and None (default) is dqn.jl's 1-step max. `dist` (a C51Options) makes the critic categorical (crl_dqn_c51_create), with either
+    replay and any target options: "Training Statistics".loss is then the cross-entropy against the projected target distribution, and the evaluation
+    record's eval_q_bias is that of the expected value. None (default) is the scalar critic, bit for bit what it was."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
     if eval_every:
@@ -162,7 +207,7 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
-    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target)
+    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target, dist=dist)
     start = time.time()
     global_step = 0
     while True:

@@ -678,6 +678,55 @@ int32_t crl_dqn_target_read(crl_dqn* h, int32_t* last, int32_t* m, double* nret,
 int32_t crl_dqn_nstep_probe(crl_dqn* h, const double* reward, const uint8_t* terminal, int32_t cap, int32_t ptr, const int32_t* idx, int32_t k,
                             int32_t n_step, double gamma, int32_t* last, int32_t* m, double* nret, double* ndisc);
 
+/* -----------------------------------------------------------------------------------------------------
+ * Categorical DQN (C51, Bellemare et al. 2017) — no reference counterpart: dqn.jl's critic is a scalar. A handle made by crl_dqn_c51_create learns,
+ * per action, a distribution over N fixed atoms instead of one number. The trunk is dqn.jl's, W1(120,4) b1 W2(84,120) b2; the head is W3(2N, 84)
+ * b3(2N), row a·N + i = atom i of action a (Flux's reshape(…, N, 2, :) of a Dense(84, 2N)); one flat float vector, (out,in) column-major, 10764 +
+ * 85·2N numbers (19434 at N = 51) — crl_dqn_param_count gives it, and crl_dqn_write_params / crl_dqn_read_params / crl_dqn_init_params take that n on
+ * such a handle. The cycle stays ten launches (csrc/dqn_c51.hpp, csrc/dqn.hip: dqn_c51_*_kernel); sampler, ring, n-step walk, PER tree, Adam, target copy
+ * and the loss record are the other handles', so crl_dqn_run, crl_dqn_status_read, crl_dqn_target_read and — with per != NULL — the crl_dqn_per_* calls
+ * work unchanged. crl_dqn_q_values returns the expected values Q(a), (2, n); crl_dqn_evaluate acts greedily on them and reports q0 = Q(a): the bits
+ * of crl_dqn_q_values for the same observation. crl_dqn_create, crl_dqn_per_create and crl_dqn_create_with handles keep every bit of their behaviour;
+ * the c51_* calls below fail on them with a message naming crl_dqn_c51_create.
+ *
+ * All Float64, one operation per written operator, no contraction; every Σ starts from 0.0 and runs in ascending index order:
+ *   Atoms     Δ = (v_max − v_min) / (double)(N − 1);  z_i = v_min + (double)i · Δ
+ *   Softmax   of a row of N logits l:  mx = max_i l_i;  d_i = l_i − mx;  e_i = exp(d_i);  S = Σ_i e_i;  p_i = e_i / S;  logp_i = d_i − log(S)
+ *   Value     Q(a) = Σ_i z_i · p_i; greedy = the first maximum (Q(1) > Q(0) ? 1 : 0) — in collect, in evaluation and for a*
+ *   Target    for sample j: R, disc, last from the n-step walk above (n_step = 1: R = reward, disc = gamma, last = idx_j); x = next_state[last];
+ *             a* = the first maximum of Q over q_net(x) under double_q, else over target_net(x);  p' = softmax(target_net(x)[a*])
+ *   Project   for each source atom s = 0..N−1:  Tz = R + ((disc · z_s) · (1.0 − (double)terminal[last]));
+ *             Tz = Tz < v_min ? v_min : (Tz > v_max ? v_max : Tz);  b = (Tz − v_min) / Δ;  b = b > (double)(N−1) ? (double)(N−1) : b;
+ *             lo = floor(b); up = ceil(b); if lo == up atom lo receives p'_s, otherwise lo receives p'_s · ((double)up − b) and up receives
+ *             p'_s · (b − (double)lo).  m_i = Σ of what atom i receives, over s ascending (each target atom gathers: no atomics)
+ *   Loss      loss_j = −Σ_i m_i · logp_i(state_j, action_j)  (>= 0 exactly);  loss = (Σ_j w_j · loss_j, in sample order) / (double)k, w_j = 1.0 under
+ *             uniform replay — what crl_dqn_run logs and last_loss holds;  dl_i = w_j · (p_i − m_i) / (double)k, left to right, on the taken action's
+ *             logits; the other action's logits get exactly 0.0
+ *   PER       the priority input is loss_j where the scalar handles use |δ_j|: leaf, max_leaf, repair and weights are PER's own; abs_td holds loss_j
+ *   Backward  d2_j = relu'(H2_j) · Σ_i W3[a·N+i, j] · dl_i in atom order; weight gradients one parameter at a time over the samples in sample order,
+ *             an exact 0.0 for samples of the other action, then the Float32 projection; Adam with six arrays, one β-power pair each
+ * crl_dqn_target_read's td on such a handle is R + ((disc · Q_target(x)[a*]) · (1 − terminal[last])), the scalar the distribution's mean moves towards;
+ * it enters nothing. exp and log are the device library's; how far they lie from a correctly rounded result has not been measured (tests/c51_bar.py).
+ * n_atoms in 2..64 (a wavefront's lane owns an atom); v_min < v_max, both finite. Errors of crl_dqn_c51_create, beyond crl_dqn_create_with's: cfg, c51
+ * or out NULL; n_atoms outside 2..64; v_min or v_max not finite; v_min >= v_max — each names the field.
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct crl_dqn_c51_options { int32_t n_atoms; int32_t pad; double v_min, v_max; } crl_dqn_c51_options;   /* 24 bytes */
+int32_t crl_dqn_c51_create(const crl_dqn_config* cfg, const crl_dqn_c51_options* c51, const crl_dqn_per_options* per /* NULL = uniform */,
+                           const crl_dqn_target_options* tgt /* NULL = {1, 0} */, int32_t device, crl_dqn** out);
+/* the handle's parameter count: CRL_DQN_PARAM_COUNT on every handle but a C51 one */
+int32_t crl_dqn_param_count(crl_dqn* h, size_t* n);
+/* crl_dqn_make_nn's rule (glorot_uniform weights, zero biases; the same trunk for the same seed) on the C51 shapes; n must be 10764 + 85·2·n_atoms */
+int32_t crl_dqn_c51_make_nn(uint64_t seed, int32_t n_atoms, float* out, size_t n);
+/* softmax of q_net(obs) per action for n observations (4, n) → (N, 2, n), atom fastest; crl_dqn_q_values is Σ_i z_i · probs[i, a, ·] of it, bit for bit */
+int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* probs);
+/* the last completed update (zeros before the first): proj[k·N] the projected targets m, sample by sample, atom fastest; sample_loss[k] the loss_j.
+ * Either may be NULL. */
+int32_t crl_dqn_c51_read(crl_dqn* h, double* proj, double* sample_loss);
+/* The projection alone with the handle's N, v_min, v_max on caller-supplied rows (training state untouched): the same __device__ function the update
+ * runs. probs (N, k) p' rows, nret[k] R, ndisc[k] disc, terminal[k]; 1 <= k <= 1024; no pointer may be NULL. */
+int32_t crl_dqn_c51_project_probe(crl_dqn* h, const double* probs, const double* nret, const double* ndisc, const uint8_t* terminal, int32_t k,
+                                  double* proj);
+
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
  * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·

@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, DQNTargetOptions, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, DQNTargetOptions, C51Options, c51_probs, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -559,7 +559,25 @@ Base.@kwdef struct DQNTargetOptions
 end
 struct CrlDQNTargetOptions; n_step::Int32; double_q::Int32; end                                                              # crl_dqn_target_options
 
-# q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64
+# The categorical critic of Bellemare et al. 2017 (include/cleanrl_hip.h crl_dqn_c51_options) — not in dqn.jl, so not a DQNConfig field: `dqn(config;
+# dist = C51Options())`, with either replay and any target options. n_atoms in 2..64 atoms evenly spaced on [v_min, v_max]; the head becomes
+# Dense(84, 2·n_atoms) and the parameter vector 10764 + 85·2·n_atoms long (crl_dqn_param_count). q_values then returns the expected values, and
+# "Training Statistics".loss is the cross-entropy. Like the rest of this file, not executed here.
+Base.@kwdef struct C51Options
+  n_atoms::Int = 51
+  v_min::Float64 = 0.0
+  v_max::Float64 = 100.0
+end
+struct CrlDQNC51Options; n_atoms::Int32; pad::Int32; v_min::Float64; v_max::Float64; end                                     # crl_dqn_c51_options
+
+# crl_dqn_c51_probs: softmax of q_net(obs) per action, (4, n) → (n_atoms, 2, n); an error on an agent with the scalar critic
+function c51_probs(agent::DQNAgent, obs::AbstractMatrix{Float64}, n_atoms::Integer)
+  o = Array(obs); n = size(o, 2); p = Array{Float64}(undef, n_atoms, 2, n)
+  GC.@preserve o p check(ccall((:crl_dqn_c51_probs, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, n, p))
+  p
+end
+
+# q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64; the expected values on a C51 agent
 function q_values(agent::DQNAgent, obs::AbstractMatrix{Float64})
   o = Array(obs); n = size(o, 2); q = Matrix{Float64}(undef, 2, n)
   GC.@preserve o q check(ccall((:crl_dqn_q_values, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, n, q))
@@ -585,7 +603,7 @@ function _default_dqn_init()
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
              chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
-             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing)
+             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options}=nothing)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
@@ -594,7 +612,17 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   h = Ref{Ptr{Cvoid}}(C_NULL)
   popt = per === nothing ? nothing :
          CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
-  if target !== nothing     # n-step / double-Q targets, uniform or prioritized replay (a NULL per is uniform); the library validates the options
+  if dist !== nothing       # the categorical critic, with either replay and any target options (NULL = uniform, NULL = {1, 0})
+    2 <= dist.n_atoms <= 64 || throw(ArgumentError("dqn: dist.n_atoms must be in 2..64, got $(dist.n_atoms)"))
+    (isfinite(dist.v_min) && isfinite(dist.v_max) && dist.v_min < dist.v_max) || throw(ArgumentError("dqn: dist needs finite v_min < v_max"))
+    target === nothing || 1 <= target.n_step <= 16 || throw(ArgumentError("dqn: target.n_step must be in 1..16, got $(target.n_step)"))
+    copt = Ref(CrlDQNC51Options(dist.n_atoms, 0, dist.v_min, dist.v_max))
+    pref = popt === nothing ? C_NULL : Ref(popt)
+    tref = target === nothing ? C_NULL : Ref(CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0))
+    GC.@preserve copt pref tref check(ccall((:crl_dqn_c51_create, libcrl), Int32, (Ref{CrlDQNConfig}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}),
+      cfg, Base.unsafe_convert(Ptr{Cvoid}, copt), pref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, pref),
+      tref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tref), device, h))
+  elseif target !== nothing     # n-step / double-Q targets, uniform or prioritized replay (a NULL per is uniform); the library validates the options
     1 <= target.n_step <= 16 || throw(ArgumentError("dqn: target.n_step must be in 1..16, got $(target.n_step)"))
     topt = CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0)
     if popt === nothing
@@ -611,7 +639,8 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   end
   agent = DQNAgent(h[])
   finalizer(x -> ccall((:crl_dqn_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
-  params === nothing && init !== nothing && (params = init())             # dqn.jl:39 make_nn(env)
+  params === nothing && init !== nothing && dist === nothing && (params = init())   # dqn.jl:39 make_nn(env); its head is the scalar one, so a C51
+                                                                                    # agent without `params` takes the library's initialiser
   if params === nothing
     check(ccall((:crl_dqn_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))
   else

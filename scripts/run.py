@@ -11,6 +11,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py dqn --total_timesteps 50000 --eval_every 5000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the greedy policy's held-out score and q_net's bias every 5000 steps)
     python scripts/run.py dqn --total_timesteps 50000 --per --per_alpha 0.6 --per_beta_start 0.4 --per_beta_end 1.0 --per_beta_duration 50000 --per_eps 1e-6   (prioritized replay; --per alone takes the defaults, beta_duration = total_timesteps)
     python scripts/run.py dqn --total_timesteps 50000 --double_q --n_step 3 [--per]   (double Q-learning and 3-step returns; either alone, both combine with --per)
+    python scripts/run.py dqn --total_timesteps 50000 --c51 [--n_atoms 51 --v_min 0 --v_max 100] [--per] [--double_q --n_step 3]   (categorical C51 critic; combines with all of the above)
     python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
@@ -78,7 +79,13 @@ def main():
         if "--double_q" in argv or to:
             target = crl.DQNTargetOptions(n_step=to.get("n_step", 1), double_q="--double_q" in argv)
             argv = [a for a in argv if a != "--double_q"]
-        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, target, to_terminal=True, to_tensorboard=False, **kw).close()
+        # the categorical critic (crl_dqn_c51_create): --c51 switches it on, --n_atoms / --v_min / --v_max are C51Options' fields and imply it
+        co = take((("--n_atoms", int), ("--v_min", float), ("--v_max", float)))
+        dist = None
+        if "--c51" in argv or co:
+            argv = [a for a in argv if a != "--c51"]
+            dist = crl.C51Options(**co)
+        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, target, dist, to_terminal=True, to_tensorboard=False, **kw).close()
 
 
 if __name__ == "__main__":
