@@ -99,7 +99,8 @@ EXPORTS = [
     "crl_dqn_create", "crl_dqn_destroy", "crl_dqn_write_params", "crl_dqn_read_params", "crl_dqn_status_read", "crl_dqn_run",
     "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_dqn_per_create", "crl_dqn_per_status_read", "crl_dqn_per_read",
     "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe",
-    "crl_dqn_c51_create", "crl_dqn_param_count", "crl_dqn_c51_make_nn", "crl_dqn_c51_probs", "crl_dqn_c51_read", "crl_dqn_c51_project_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_c51_create", "crl_dqn_param_count", "crl_dqn_c51_make_nn", "crl_dqn_c51_probs", "crl_dqn_c51_read", "crl_dqn_c51_project_probe",
+    "crl_dqn_dueling_create", "crl_dqn_dueling_make_nn", "crl_dqn_dueling_streams", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -337,6 +338,9 @@ def load():
     L.crl_dqn_c51_probs.argtypes = [vp, dp, C.c_int32, dp]
     L.crl_dqn_c51_read.argtypes = [vp, dp, dp]
     L.crl_dqn_c51_project_probe.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_uint8), C.c_int32, dp]
+    L.crl_dqn_dueling_create.argtypes = L.crl_dqn_c51_create.argtypes
+    L.crl_dqn_dueling_make_nn.argtypes = [C.c_uint64, C.c_int32, fp, C.c_size_t]
+    L.crl_dqn_dueling_streams.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
     L.crl_a2c_eval_envs_per_block.argtypes = []
     L.crl_ddpg_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
@@ -980,22 +984,39 @@ def dqn_c51_make_nn_host(seed=0, n_atoms=51):
     return out
 
 
+def dqn_dueling_param_count(n_atoms=None):
+    """20928 + 255·R floats: R = 1 on a scalar dueling handle (n_atoms None or 0), R = n_atoms on a categorical one"""
+    return 20928 + 255 * (int(n_atoms) if n_atoms else 1)
+
+
+def dqn_dueling_make_nn_host(seed=0, n_atoms=None):
+    """crl_dqn_dueling_make_nn: crl_dqn_make_nn's rule on the ten arrays of a dueling net (the same W1 and W2v draws for the same seed)."""
+    out = np.zeros(dqn_dueling_param_count(n_atoms), np.float32)
+    check(load().crl_dqn_dueling_make_nn(seed, int(n_atoms) if n_atoms else 0, _ptr(out, C.c_float), out.size))
+    return out
+
+
 class DQNHandle:
     """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block). `per` (a CrlDQNPEROptions) makes it a prioritized-replay handle (crl_dqn_per_create):
     every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available.
     `target` (a CrlDQNTargetOptions) makes it a crl_dqn_create_with handle, with either replay: n-step / double-Q targets, and target_read /
     nstep_probe, which are errors on the other handles. `c51` (a CrlDQNC51Options) makes it a crl_dqn_c51_create handle, with either replay and any
     target options: the head is categorical, param_count is its own, q_values are expected values, and c51_probs / c51_read / c51_project_probe
-    become available."""
+    become available. `dueling=True` makes it a crl_dqn_dueling_create handle, with either head, either replay and any target options: layers 2 and 3
+    are a value and an advantage stream (ten arrays, param_count is its own), and dueling_streams becomes available."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None, dueling=False):
         self._L = load()
         self.cfg = cfg
         self.per = per
         self.target = target
         self.c51 = c51
+        self.dueling = bool(dueling)
         self._h = C.c_void_p()
-        if c51 is not None:
+        if self.dueling:
+            check(self._L.crl_dqn_dueling_create(C.byref(cfg), None if c51 is None else C.byref(c51), None if per is None else C.byref(per),
+                                                 None if target is None else C.byref(target), device, C.byref(self._h)))
+        elif c51 is not None:
             check(self._L.crl_dqn_c51_create(C.byref(cfg), C.byref(c51), None if per is None else C.byref(per),
                                              None if target is None else C.byref(target), device, C.byref(self._h)))
         elif target is not None:
@@ -1024,13 +1045,13 @@ class DQNHandle:
         check(self._L.crl_dqn_init_params(self._h, seed))
 
     def param_count(self):
-        """crl_dqn_param_count: 10934, or 10764 + 85·2N on a C51 handle"""
+        """crl_dqn_param_count: 10934, 10764 + 85·2N on a C51 handle, 20928 + 255·R on a dueling one"""
         n = C.c_size_t()
         check(self._L.crl_dqn_param_count(self._h, C.byref(n)))
         return int(n.value)
 
     def read_params(self):
-        n = DQN_PARAM_COUNT if self.c51 is None else self.param_count()
+        n = DQN_PARAM_COUNT if self.c51 is None and not self.dueling else self.param_count()
         q = np.zeros(n, np.float32); t = np.zeros(n, np.float32)
         check(self._L.crl_dqn_read_params(self._h, _ptr(q, C.c_float), _ptr(t, C.c_float), q.size))
         return q, t
@@ -1101,6 +1122,17 @@ class DQNHandle:
         check(self._L.crl_dqn_target_read(self._h, _ptr(out["last"], C.c_int32), _ptr(out["m"], C.c_int32), _ptr(out["nret"], C.c_double),
                                           _ptr(out["ndisc"], C.c_double), _ptr(out["astar"], C.c_int32), _ptr(out["td"], C.c_double)))
         return out
+
+    def dueling_streams(self, obs):
+        """crl_dqn_dueling_streams: the two streams before they are combined, (4, n) → {value (R, n), adv (R, 2, n)} float64"""
+        obs = np.asfortranarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        n = obs.shape[1]
+        R = 1 if self.c51 is None else int(self.c51.n_atoms)
+        value = np.zeros((R, n), np.float64, order="F"); adv = np.zeros((R, 2, n), np.float64, order="F")
+        check(self._L.crl_dqn_dueling_streams(self._h, _ptr(obs, C.c_double), n, _ptr(value, C.c_double), _ptr(adv, C.c_double)))
+        return dict(value=value, adv=adv)
 
     def c51_probs(self, obs):
         """crl_dqn_c51_probs: softmax of q_net(obs) per action, (4, n) → (N, 2, n) float64"""

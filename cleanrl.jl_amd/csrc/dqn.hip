@@ -21,6 +21,7 @@
 #include "dqn_per.hpp"
 #include "dqn_target.hpp"
 #include "dqn_c51.hpp"
+#include "dqn_duel.hpp"
 #include "replay_sample.hpp"
 #include "value_eval.hpp"
 
@@ -52,6 +53,8 @@ struct DQNDev {
   PerDev per;                                 // prioritized replay (crl_dqn_per_create); all zero on a crl_dqn_create handle
   TgtDev tgt;                                 // n-step / double-Q targets (crl_dqn_create_with); all zero on the other handles
   C51Dev c51;                                 // the categorical head (crl_dqn_c51_create; such a handle also has tgt.on); all zero on the other handles
+  DuelDev duel;                               // the dueling heads (crl_dqn_dueling_create; such a handle also has tgt.on, and c51.on if categorical): then H2
+                                              // and d2 hold 168 units per sample; all zero on the other handles
 };
 
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
@@ -689,11 +692,10 @@ __global__ void __launch_bounds__(64) dqn_c51_wgrad_kernel(DQNDev a) {
 }
 // dqn_adam_kernel over the C51 handle's P parameters: the same six arrays, the head's two being longer. Being the cycle's one-block launch behind the
 // TD launch, it first does what needs the whole batch: loss = (Σ_b sq_b, sample order) / k, and under PER max_leaf raised to the batch's largest new
-// leaf and the ancestors of the written leaves repaired (dqn_tgt_td_kernel's tail).
-__global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
+// leaf and the ancestors of the written leaves repaired (dqn_tgt_td_kernel's tail): dqn_c51_batch_tail, which dqn_duel_adam_kernel runs as well.
+__device__ __forceinline__ void dqn_c51_batch_tail(const DQNDev& a) {
 #pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
-  const int tid = threadIdx.x, nth = blockDim.x, P = a.c51.P, ob3 = QoW3 + 2 * a.c51.N * QH2;
+  const int tid = threadIdx.x, nth = blockDim.x;
   if (tid == 0) {
     const int k = (int)a.cfg.batch_size;
     double loss = 0.0;
@@ -718,6 +720,12 @@ __global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
     }
     per_repair(p.tree, p.C, k, [=](int i) { return (int)idx[i]; });
   }
+}
+__global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int tid = threadIdx.x, nth = blockDim.x, P = a.c51.P, ob3 = QoW3 + 2 * a.c51.N * QH2;
+  dqn_c51_batch_tail(a);
   const int64_t gstep = a.ctl->global_step;
   const bool copy = gstep % a.cfg.target_net_freq == 0;
   for (int p = tid; p < P; p += nth) {
@@ -981,6 +989,364 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_c51_eval_kernel(const
   value_eval_trace_tail(ev, env, row, lane);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Dueling heads (crl_dqn_dueling_create; dqn_duel.hpp). One family for both heads, R = 1 (scalar) or N (categorical) at run time. W1 b1 sit at the
+// plain net's offsets, so dqn_fwd1_kernel runs unchanged, and such a handle always carries target options, so the sampling launch is
+// dqn_tgt_sample_kernel. The two streams are combined where the head's output is written (dqn_duel_fwd3_kernel): the combined Q or logits land in the
+// buffers the TD kernels read (Q, c51.L), so dqn_tgt_td_kernel / dqn_c51_td_kernel run as they are and what they leave (dz, c51.dl) is the cotangent g
+// of out_{act,·}. The kernels below take the places of collect, fwd2, fwd3, bwd2, bwd1, wgrad and Adam: the cycle stays ten launches.
+// ------------------------------------------------------------------------------------------------------
+struct DuelCollectLds {
+  DQNCtl c;
+  double obs[QD], h1s[DUEL_H1], h2s[DUEL_U2], raw[3 * DUEL_MAX_R], ls[2 * DUEL_MAX_R], qs[QA], eps_s;   // raw: V (R), then A (2R), before they are combined
+  int go, need_q, action_s, pad;
+};
+constexpr size_t DUEL_COLLECT_LDS = (sizeof(DuelCollectLds) + 15) / 16 * 16;
+struct DuelEvalWaveLds { double h1[DUEL_H1], h2[DUEL_U2]; };
+constexpr int DUEL_EVAL_WAVES = DQN_EVAL_WAVES < 4 ? DQN_EVAL_WAVES : 4;   // four waves' strips beside the largest net are what the CU's LDS holds
+constexpr size_t DUEL_LDS_LIMIT = 160 * 1024;                              // one workgroup may take the whole CU's LDS
+static_assert(DUEL_MAX_R == C51_MAX_ATOMS && DUEL_H1 == QH1 && DUEL_H2 == QH2 && DUEL_D == QD, "one net shape");
+static_assert(DUEL_COLLECT_LDS + (size_t)duel_param_count(DUEL_MAX_R) * 4 <= DUEL_LDS_LIMIT, "collect: the largest net + the block's strips fit the CU's LDS");
+static_assert(sizeof(DuelEvalWaveLds) * DUEL_EVAL_WAVES + (size_t)duel_param_count(DUEL_MAX_R) * 4 <= DUEL_LDS_LIMIT,
+              "evaluation: the largest net + the waves' strips fit the CU's LDS");
+static_assert(sizeof(DuelEvalWaveLds) % 16 == 0, "the weight image starts 16-byte aligned");
+
+// the block's forward for one observation, layers separated by block barriers: h1 (120), h2 (168), raw (V then A), ls = the combined head (2R). Ends on
+// a block barrier. The q kernel and the collect kernel run it, 128 threads each.
+__device__ __forceinline__ void duel_block_forward(const float* W, const DuelOff& o, int R, const double* obs, double* h1s, double* h2s, double* raw,
+                                                   double* ls) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, nth = blockDim.x;
+  for (int i = tid; i < DUEL_H1; i += nth) {
+    double acc = 0.0;
+    for (int kk = 0; kk < QD; ++kk) acc += (double)W[o.W1 + i + QH1 * kk] * obs[kk];
+    acc += (double)W[o.b1 + i];
+    h1s[i] = acc > 0.0 ? acc : 0.0;
+  }
+  __syncthreads();
+  for (int u = tid; u < DUEL_U2; u += nth) h2s[u] = duel_hidden2(W, o, u, h1s);
+  __syncthreads();
+  for (int r = tid; r < 3 * R; r += nth) raw[r] = duel_head_row(W, o, R, r, h2s);
+  __syncthreads();
+  for (int i = tid; i < R; i += nth) duel_combine(raw[i], raw[R + i], raw[2 * R + i], ls[i], ls[R + i]);
+  __syncthreads();
+}
+
+// dqn_c51_collect_kernel with the dueling heads: the whole net in dynamic LDS (84.7 KB at R = 1, 149.0 KB at R = 64)
+__global__ void __launch_bounds__(128) dqn_duel_collect_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  DuelCollectLds& s = *reinterpret_cast<DuelCollectLds*>(c51_smem);
+  float* const wq = reinterpret_cast<float*>(c51_smem + DUEL_COLLECT_LDS);
+  DQNCtl& c = s.c;
+  const int tid = threadIdx.x, P = a.duel.P, R = a.duel.R;
+  const DuelOff o = duel_off(R);
+  if (tid == 0) c = *a.ctl;
+  __syncthreads();
+  if (c.train_pending || c.taken >= c.budget || c.global_step >= a.cfg.total_timesteps) return;
+  for (int p = tid; p < P; p += 128) wq[p] = a.q[p];
+  __syncthreads();
+  while (true) {
+    if (tid == 0) {
+      s.go = (!c.train_pending && c.taken < c.budget && c.global_step < a.cfg.total_timesteps) ? 1 : 0;
+      if (s.go) {
+        c.global_step += 1; c.taken += 1;
+        const uint64_t gstep = (uint64_t)c.global_step;
+        for (int i = 0; i < QD; ++i) s.obs[i] = c.env[i];
+        s.eps_s = dq_linear_schedule(a.cfg.epsilon_start, a.cfg.epsilon_end, a.cfg.epsilon_duration, (double)c.global_step);
+        if (u53(philox_env(a.cfg.seed, 0u, gstep, 0u)) < s.eps_s) {
+          s.need_q = 0;
+          s.action_s = (int)(philox_env(a.cfg.seed, 0u, gstep, 4u).x >> 31);
+        } else s.need_q = 1;
+      }
+    }
+    __syncthreads();
+    if (!s.go) break;
+    if (s.need_q) {
+      duel_block_forward(wq, o, R, s.obs, s.h1s, s.h2s, s.raw, s.ls);
+      if (a.c51.on) c51_block_q(s.ls, s.qs, a.c51, nullptr);
+      else {
+        if (tid < QA) s.qs[tid] = s.ls[tid];
+        __syncthreads();
+      }
+    }
+    if (tid == 0) {
+      const uint64_t gstep = (uint64_t)c.global_step;
+      const int action = s.need_q ? (s.qs[1] > s.qs[0] ? 1 : 0) : s.action_s;
+      const bool done = cartpole_step64(c.env, c.env_t, action, a.cfg.max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      const size_t p = (size_t)c.ptr;
+      for (int i = 0; i < QD; ++i) { a.rb_state[QD * p + i] = s.obs[i]; a.rb_next[QD * p + i] = c.env[i]; }
+      a.rb_action[p] = action; a.rb_reward[p] = rew; a.rb_terminal[p] = done ? 1 : 0;
+      c.ptr = c.ptr + 1 >= a.cfg.buffer_size ? 0 : c.ptr + 1;
+      c.size = c.size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c.size + 1;
+      c.episode_return += rew; c.episode_length += 1;
+      if (done) {
+        if (c.n_eps < DQN_MAX_EPS) {
+          a.eps[c.n_eps].episode_return = c.episode_return; a.eps[c.n_eps].episode_length = c.episode_length;
+          a.eps[c.n_eps].global_step = c.global_step; a.eps[c.n_eps].epsilon = s.eps_s;
+        }
+        c.n_eps += 1;
+        c.episode_length = 0; c.episode_return = 0.0;
+        env_reset64(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
+      }
+      c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step % a.cfg.train_freq == 0) ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *a.ctl = c;
+}
+
+// the two-stream hidden layer of every pass: 168 units per sample, one per thread
+__global__ void __launch_bounds__(256) dqn_duel_fwd2_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= a.nets * DUEL_U2 * k) return;
+  const int net = o / (DUEL_U2 * k), r = o - net * (DUEL_U2 * k), b = r / DUEL_U2, u = r - b * DUEL_U2;
+  const float* p = net == 1 ? a.t : a.q;
+  a.H2[(size_t)net * DUEL_U2 * k + r] = duel_hidden2(p, duel_off(a.duel.R), u, a.H1 + (size_t)net * QH1 * k + (size_t)QH1 * b);
+}
+// V_i, A_{0,i}, A_{1,i} and the combined out_{a,i} of every pass, one i per thread, written where the TD kernels read: Q (R = 1) or c51.L (R = N)
+__global__ void __launch_bounds__(256) dqn_duel_fwd3_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, R = a.duel.R, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= a.nets * R * k) return;
+  const int net = o / (R * k), r = o - net * (R * k), b = r / R, i = r - b * R;
+  const float* p = net == 1 ? a.t : a.q;
+  const DuelOff off = duel_off(R);
+  const double* h = a.H2 + (size_t)net * DUEL_U2 * k + (size_t)DUEL_U2 * b;
+  const double V = duel_head_row(p, off, R, i, h), A0 = duel_head_row(p, off, R, R + i, h), A1 = duel_head_row(p, off, R, 2 * R + i, h);
+  double* dst = (a.c51.on ? a.c51.L : a.Q) + (size_t)net * 2 * R * k + (size_t)2 * R * b;
+  duel_combine(V, A0, A1, dst[i], dst[R + i]);
+}
+// d2v_j = relu'(h2v_j) · Σ_i W3v[i,j]·g_i; d2a_j = relu'(h2a_j) · Σ_row W3a[row,j]·dA_row, row = a·R + i ascending; g = dz (R = 1) or dl (R = N)
+__global__ void __launch_bounds__(256) dqn_duel_bwd2_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, R = a.duel.R, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= DUEL_U2 * k) return;
+  const int b = o / DUEL_U2, u = o - b * DUEL_U2, act = a.rb_action[a.idx[b]];
+  const DuelOff off = duel_off(R);
+  const double* g = a.c51.on ? a.c51.dl + (size_t)R * b : a.dz + b;
+  double s = 0.0;
+  if (u < QH2) {
+    const float* w = a.q + off.W3v + R * u;
+#pragma unroll 4
+    for (int i = 0; i < R; ++i) s += (double)w[i] * g[i];
+  } else {
+    const float* w = a.q + off.W3a + 2 * R * (u - QH2);
+    for (int aa = 0; aa < QA; ++aa) {
+#pragma unroll 4
+      for (int i = 0; i < R; ++i) s += (double)w[aa * R + i] * duel_dadv(g[i], act, aa);
+    }
+  }
+  a.d2[o] = a.H2[o] > 0.0 ? s : 0.0;
+}
+// d1_k = relu'(h1_k) · (Σ_j W2v[j,k]·d2v_j, then the same accumulator on with Σ_j W2a[j,k]·d2a_j)
+__global__ void __launch_bounds__(256) dqn_duel_bwd1_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= QH1 * k) return;
+  const int b = o / QH1, kk = o - b * QH1;
+  const DuelOff off = duel_off(a.duel.R);
+  const double* dd = a.d2 + (size_t)DUEL_U2 * b;
+  double s = 0.0;
+#pragma unroll 6
+  for (int j = 0; j < QH2; ++j) s += (double)a.q[off.W2v + j + QH2 * kk] * dd[j];
+#pragma unroll 6
+  for (int j = 0; j < QH2; ++j) s += (double)a.q[off.W2a + j + QH2 * kk] * dd[QH2 + j];
+  a.d1[o] = a.H1[o] > 0.0 ? s : 0.0;
+}
+// dqn_wgrad_kernel over the ten arrays: one parameter per thread, samples in sample order, Float32 projection. Both rows of W3a / b3a get a term
+// from every sample (±g·0.5), unlike the plain head.
+__global__ void __launch_bounds__(64) dqn_duel_wgrad_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int k = (int)a.cfg.batch_size, R = a.duel.R, p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.duel.P) return;
+  const DuelOff off = duel_off(R);
+  const double* g = a.c51.on ? a.c51.dl : a.dz;       // [k][R]
+  double s = 0.0;
+  if (p < off.W2v) {
+    s = dqn_wgrad_trunk(a, p, k);                      // W1 b1: the plain trunk's offsets and sums
+  } else if (p < off.W3v || (p >= off.W2a && p < off.W3a)) {
+    const bool adv = p >= off.W2a;
+    const int r = p - (adv ? off.W2a : off.W2v), u0 = adv ? QH2 : 0;
+    if (r < QH2 * QH1) {
+      const int j = r % QH2, kk = r / QH2;
+#pragma unroll 30
+      for (int b = 0; b < k; ++b) s += a.d2[(size_t)DUEL_U2 * b + u0 + j] * a.H1[(size_t)QH1 * b + kk];
+    } else {
+      const int j = r - QH2 * QH1;
+#pragma unroll 30
+      for (int b = 0; b < k; ++b) s += a.d2[(size_t)DUEL_U2 * b + u0 + j];
+    }
+  } else if (p < off.b3v) {
+    const int r = p - off.W3v, i = r % R, j = r / R;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) s += g[(size_t)R * b + i] * a.H2[(size_t)DUEL_U2 * b + j];
+  } else if (p < off.W2a) {
+    const int i = p - off.b3v;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) s += g[(size_t)R * b + i];
+  } else if (p < off.b3a) {
+    const int r = p - off.W3a, row = r % (2 * R), j = r / (2 * R), aa = row / R, i = row - aa * R;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) s += duel_dadv(g[(size_t)R * b + i], a.rb_action[a.idx[b]], aa) * a.H2[(size_t)DUEL_U2 * b + QH2 + j];
+  } else {
+    const int row = p - off.b3a, aa = row / R, i = row - aa * R;
+#pragma unroll 30
+    for (int b = 0; b < k; ++b) s += duel_dadv(g[(size_t)R * b + i], a.rb_action[a.idx[b]], aa);
+  }
+  a.grads[p] = (float)s;
+}
+// dqn_adam_kernel over ten arrays, one β-power pair each; on a categorical handle it first does what needs the whole batch, as dqn_c51_adam_kernel
+__global__ void __launch_bounds__(1024) dqn_duel_adam_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const int tid = threadIdx.x, nth = blockDim.x, P = a.duel.P;
+  const DuelOff off = duel_off(a.duel.R);
+  if (a.c51.on) dqn_c51_batch_tail(a);
+  const int64_t gstep = a.ctl->global_step;
+  const bool copy = gstep % a.cfg.target_net_freq == 0;
+  for (int p = tid; p < P; p += nth) {
+    const int arr = duel_array_of(off, p);
+    float mi, vi, w;
+    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
+    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
+    if (copy) a.t[p] = w;
+  }
+  __syncthreads();
+  if (tid < DUEL_ARRAYS) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
+  if (tid == 0) {
+    DQNCtl* c = a.ctl;
+    c->n_updates += 1;
+    if (gstep % a.cfg.log_frequency == 0) {
+      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
+      c->n_losses += 1;
+    }
+    c->train_pending = 0;
+  }
+}
+
+// crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams on a dueling handle: the block's forward, then whichever outputs are asked for.
+// out_q (2, n); out_p (N, 2, n); out_v (R, n); out_a (R, 2, n), i fastest
+__global__ void __launch_bounds__(128) dqn_duel_q_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, const double* __restrict__ obs, int n,
+                                                         double* __restrict__ out_q, double* __restrict__ out_p, double* __restrict__ out_v,
+                                                         double* __restrict__ out_a) {
+#pragma clang fp contract(off)
+  __shared__ double h1s[DUEL_H1], h2s[DUEL_U2], raw[3 * DUEL_MAX_R], ls[2 * DUEL_MAX_R], qs[QA];
+  const int b = blockIdx.x, tid = threadIdx.x, R = du.R;
+  if (b >= n) return;
+  duel_block_forward(q, duel_off(R), R, obs + (size_t)QD * b, h1s, h2s, raw, ls);
+  if (out_v && tid < R) out_v[(size_t)R * b + tid] = raw[tid];
+  if (out_a) for (int r = tid; r < 2 * R; r += 128) out_a[(size_t)2 * R * b + r] = raw[R + r];
+  if (c.on) {
+    c51_block_q(ls, qs, c, out_p ? out_p + (size_t)2 * R * b : nullptr);
+    if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
+  } else if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = ls[tid];
+}
+
+// dqn_c51_eval_kernel with the dueling heads: one wave per env, ONE staging barrier, the net (up to 149.0 KB) and the waves' strips in dynamic LDS.
+// The 168 hidden units are three per lane (lane, lane + 64, lane + 128: three chains side by side); lane i < R forms V_i, A_{0,i} and A_{1,i} side by
+// side and combines them, then on a categorical handle the two softmaxes and expectations run wave-wide. With R = 1 every lane forms row 0 alike.
+__global__ void __launch_bounds__(64 * DUEL_EVAL_WAVES) dqn_duel_eval_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, int max_steps, double gamma,
+                                                                             ValueEvalArgs ev) {
+#pragma clang fp contract(off)
+  DuelEvalWaveLds* const wl = reinterpret_cast<DuelEvalWaveLds*>(c51_smem);
+  float* const wq = reinterpret_cast<float*>(c51_smem + sizeof(DuelEvalWaveLds) * DUEL_EVAL_WAVES);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * DUEL_EVAL_WAVES + w, R = du.R;
+  const DuelOff o = duel_off(R);
+  for (int p = threadIdx.x; p < du.P; p += 64 * DUEL_EVAL_WAVES) wq[p] = q[p];
+  __syncthreads();                       // the only block barrier of the kernel
+  if (env >= ev.n) return;
+  double* const h1w = wl[w].h1;
+  double* const h2w = wl[w].h2;
+  const double delta = c.on ? c51_delta(c.v_min, c.v_max, R) : 0.0;
+  const int u1b = lane + 64 < QH1 ? lane + 64 : lane;
+  // the lane's three units of the two-stream layer: lane is a value unit, lane + 64 one of either stream, lane + 128 an advantage unit (lanes 0..39)
+  const int ua = lane, ub = lane + 64, uc = lane + 128 < DUEL_U2 ? lane + 128 : lane;
+  const auto wof = [&](int u) { return u >= QH2 ? o.W2a + u - QH2 : o.W2v + u; };
+  const auto bof = [&](int u) { return u >= QH2 ? o.b2a + u - QH2 : o.b2v + u; };
+  const int wa = wof(ua), wb = wof(ub), wc = wof(uc), ba = bof(ua), bb = bof(ub), bc = bof(uc);
+  const int r0 = lane < R ? lane : 0;    // a lane past R repeats row 0; on a categorical handle its results are masked by the wave functions
+  int64_t row = 0;
+  for (int j = 0; j < ev.episodes; ++j) {
+    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
+    int t = 0, length = 0;
+    const size_t slot = (size_t)j * ev.n + env;
+    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
+    while (true) {
+      {
+        double acc = 0.0, acc2 = 0.0;
+#pragma unroll
+        for (int kk = 0; kk < QD; ++kk) {
+          acc += (double)wq[o.W1 + lane + QH1 * kk] * s[kk];
+          acc2 += (double)wq[o.W1 + u1b + QH1 * kk] * s[kk];
+        }
+        acc += (double)wq[o.b1 + lane];
+        acc2 += (double)wq[o.b1 + u1b];
+        h1w[lane] = acc > 0.0 ? acc : 0.0;
+        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
+      }
+      wave_lds_fence();
+      {
+        double acc = 0.0, acc2 = 0.0, acc3 = 0.0;
+#pragma unroll 8
+        for (int kk = 0; kk < QH1; ++kk) {
+          const double h = h1w[kk];
+          acc += (double)wq[wa + QH2 * kk] * h;
+          acc2 += (double)wq[wb + QH2 * kk] * h;
+          acc3 += (double)wq[wc + QH2 * kk] * h;
+        }
+        acc += (double)wq[ba];
+        acc2 += (double)wq[bb];
+        acc3 += (double)wq[bc];
+        h2w[ua] = acc > 0.0 ? acc : 0.0;
+        h2w[ub] = acc2 > 0.0 ? acc2 : 0.0;
+        if (lane + 128 < DUEL_U2) h2w[lane + 128] = acc3 > 0.0 ? acc3 : 0.0;
+      }
+      wave_lds_fence();
+      double av = 0.0, a0 = 0.0, a1 = 0.0;
+#pragma unroll 4
+      for (int kk = 0; kk < QH2; ++kk) {
+        const double hv = h2w[kk], ha = h2w[QH2 + kk];
+        av += (double)wq[o.W3v + r0 + R * kk] * hv;
+        a0 += (double)wq[o.W3a + r0 + 2 * R * kk] * ha;
+        a1 += (double)wq[o.W3a + R + r0 + 2 * R * kk] * ha;
+      }
+      double q0, q1;
+      duel_combine(av + (double)wq[o.b3v + r0], a0 + (double)wq[o.b3a + r0], a1 + (double)wq[o.b3a + R + r0], q0, q1);
+      if (c.on) {                        // q0, q1 are the logits of atom `lane`
+        double p0, p1, lp;
+        c51_softmax(q0, R, lane, p0, lp);
+        const double e0 = c51_expect(p0, c.v_min, delta, lane);
+        c51_softmax(q1, R, lane, p1, lp);
+        q1 = c51_expect(p1, c.v_min, delta, lane);
+        q0 = e0;
+      }
+      const int action = q1 > q0 ? 1 : 0;
+      if (lane == 0) {
+        if (length == 0) ev.v0[slot] = action ? q1 : q0;
+        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
+      }
+      row += 1;
+      const bool done = cartpole_step64(s, t, action, max_steps);
+      const double rew = done ? 0.0 : 1.0;
+      ret += rew;
+      disc_ret += disc * rew;
+      disc = disc * gamma;
+      length += 1;
+      wave_lds_fence();
+      if (done) break;
+    }
+    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
+  }
+  value_eval_trace_tail(ev, env, row, lane);
+}
+
 }  // namespace crl
 
 struct crl_dqn {
@@ -997,8 +1363,9 @@ struct crl_dqn {
   bool tgt = false;                                                 // made by crl_dqn_create_with
   void* walk_scratch = nullptr;                                     // crl_dqn_nstep_probe's scratch
   bool c51 = false;                                                 // made by crl_dqn_c51_create
-  size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, or 10764 + 85·2N on a C51 handle
+  size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, 10764 + 85·2N on a C51 handle, 20928 + 255·R on a dueling one
   void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's scratch
+  bool duel = false;                                                // made by crl_dqn_dueling_create: P = 20928 + 255·R, R = 1 or n_atoms
 };
 
 using namespace crl;
@@ -1035,7 +1402,32 @@ static void enqueue_c51_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_c51_adam_kernel, dim3(1), dim3(1024), 0, st, d);
 }
 
+static size_t duel_collect_lds(int P) { return DUEL_COLLECT_LDS + (size_t)P * 4; }
+static size_t duel_eval_lds(int P) { return sizeof(DuelEvalWaveLds) * DUEL_EVAL_WAVES + (size_t)P * 4; }
+
+// the ten launches of a crl_dqn_dueling_create handle: the sampling launch, fwd1 and the TD launch are the other handles' kernels
+static void enqueue_duel_cycle(hipStream_t st, const DQNDev& d, int k) {
+  const int nets = d.nets, R = d.duel.R, P = d.duel.P;
+  hipLaunchKernelGGL(dqn_duel_collect_kernel, dim3(1), dim3(128), duel_collect_lds(P), st, d);
+  if (d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
+  else hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
+  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_fwd2_kernel, dim3((nets * DUEL_U2 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_fwd3_kernel, dim3((nets * R * k + 255) / 256), dim3(256), 0, st, d);
+  if (d.c51.on) {
+    const dim3 td_grid((k + C51_TD_WAVES - 1) / C51_TD_WAVES), td_block(64 * C51_TD_WAVES);
+    if (d.per.on) hipLaunchKernelGGL(dqn_c51_td_kernel<true>, td_grid, td_block, 0, st, d);
+    else hipLaunchKernelGGL(dqn_c51_td_kernel<false>, td_grid, td_block, 0, st, d);
+  } else if (d.per.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<true>, dim3(1), dim3(1024), 0, st, d);
+  else hipLaunchKernelGGL(dqn_tgt_td_kernel<false>, dim3(1), dim3(1024), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_bwd2_kernel, dim3((DUEL_U2 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_wgrad_kernel, dim3((P + 63) / 64), dim3(64), 0, st, d);
+  hipLaunchKernelGGL(dqn_duel_adam_kernel, dim3(1), dim3(1024), 0, st, d);
+}
+
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
+  if (d.duel.on) { enqueue_duel_cycle(st, d, k); return; }
   if (d.c51.on) { enqueue_c51_cycle(st, d, k); return; }
   hipLaunchKernelGGL(dqn_collect_kernel, dim3(1), dim3(128), 0, st, d);
   const int nets = d.nets;
@@ -1056,10 +1448,10 @@ static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   hipLaunchKernelGGL(dqn_adam_kernel, dim3(1), dim3(1024), 0, st, d);
 }
 
-// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with and crl_dqn_c51_create: one body; `per` is null for uniform replay, `tgt` for the 1-step max
-// target of dqn.jl, `c51` for the scalar head
+// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create and crl_dqn_dueling_create: one body; `per` is null for uniform replay,
+// `tgt` for the 1-step max target of dqn.jl, `c51` for the scalar head; `duel` splits layers 2 and 3 into a value and an advantage stream
 static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out,
-                          const crl_dqn_c51_options* c51 = nullptr) {
+                          const crl_dqn_c51_options* c51 = nullptr, bool duel = false) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -1082,16 +1474,17 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   const size_t cap = (size_t)cfg->buffer_size, k = (size_t)cfg->batch_size;
   DQNDev& d = h->d;
   int rc = 0;
-  const size_t NP = c51 ? (size_t)QoW3 + 85 * 2 * (size_t)c51->n_atoms : (size_t)QP;
+  const size_t NP = duel ? (size_t)duel_param_count(c51 ? c51->n_atoms : 1) : c51 ? (size_t)QoW3 + 85 * 2 * (size_t)c51->n_atoms : (size_t)QP;
+  const size_t U2 = duel ? DUEL_U2 : QH2, NARR = duel ? DUEL_ARRAYS : 6;   // hidden units of layer 2 per sample; arrays Adam keeps a β-power pair for
   h->P = NP;
   rc |= qalloc(&d.q, NP); rc |= qalloc(&d.t, NP); rc |= qalloc(&d.grads, NP); rc |= qalloc(&d.m, NP); rc |= qalloc(&d.v, NP);
-  rc |= qalloc(&d.betap, 12); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
+  rc |= qalloc(&d.betap, 2 * NARR); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
   rc |= qalloc(&d.rb_state, cap * QD); rc |= qalloc(&d.rb_next, cap * QD); rc |= qalloc(&d.rb_reward, cap);
   rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
   const size_t nets = tgt && tgt->double_q ? 3 : 2;
   d.nets = (int32_t)nets;
-  rc |= qalloc(&d.H1, nets * QH1 * k); rc |= qalloc(&d.H2, nets * QH2 * k); rc |= qalloc(&d.Q, nets * QA * k);
-  rc |= qalloc(&d.dz, k); rc |= qalloc(&d.sq, k); rc |= qalloc(&d.d2, QH2 * k); rc |= qalloc(&d.d1, QH1 * k); rc |= qalloc(&d.idx, k);
+  rc |= qalloc(&d.H1, nets * QH1 * k); rc |= qalloc(&d.H2, nets * U2 * k); rc |= qalloc(&d.Q, nets * QA * k);
+  rc |= qalloc(&d.dz, k); rc |= qalloc(&d.sq, k); rc |= qalloc(&d.d2, U2 * k); rc |= qalloc(&d.d1, QH1 * k); rc |= qalloc(&d.idx, k);
   d.boot = d.idx;
   if (tgt) {
     h->tgt = true;
@@ -1129,10 +1522,22 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
       set_error("crl_dqn_c51_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
+  if (duel) {
+    h->duel = true;
+    d.duel.on = 1; d.duel.R = c51 ? c51->n_atoms : 1; d.duel.P = (int32_t)NP;
+    // both kernels keep the whole net in LDS, past the 64 KB a launch gets without asking at every R; set for the largest head, as above
+    constexpr int PMAX = duel_param_count(DUEL_MAX_R);
+    if (!rc && (hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_duel_collect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)duel_collect_lds(PMAX)) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_duel_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)duel_eval_lds(PMAX)) != hipSuccess)) {
+      set_error("crl_dqn_dueling_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
+    }
+  }
   if (rc) { crl_dqn_destroy(h); return 1; }
-  double bp[12];
-  for (int i = 0; i < 6; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
-  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, sizeof(bp), hipMemcpyHostToDevice));
+  double bp[2 * DUEL_ARRAYS];
+  for (size_t i = 0; i < NARR; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
+  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, 2 * NARR * sizeof(double), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(dqn_init_kernel, dim3(1), dim3(1), 0, h->stream, d);
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   *out = h;
@@ -1203,6 +1608,55 @@ int32_t crl_dqn_c51_create(const crl_dqn_config* cfg, const crl_dqn_c51_options*
   return dqn_create(cfg, per, &t, device, out, c51);
 }
 
+int32_t crl_dqn_dueling_create(const crl_dqn_config* cfg, const crl_dqn_c51_options* c51, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt,
+                               int32_t device, crl_dqn** out) {
+  if (!cfg || !out) { set_error("crl_dqn_dueling_create: null argument (cfg and out are required)"); return 1; }
+  *out = nullptr;
+  if (c51) {
+    if (c51->n_atoms < 2 || c51->n_atoms > C51_MAX_ATOMS) { set_error("crl_dqn_dueling_create: n_atoms must be in 2..64"); return 1; }
+    if (!(c51->v_min > -1e300 && c51->v_min < 1e300)) { set_error("crl_dqn_dueling_create: v_min must be finite"); return 1; }
+    if (!(c51->v_max > -1e300 && c51->v_max < 1e300)) { set_error("crl_dqn_dueling_create: v_max must be finite"); return 1; }
+    if (!(c51->v_min < c51->v_max)) { set_error("crl_dqn_dueling_create: v_min must be < v_max"); return 1; }
+  }
+  if (per && per_options_check("crl_dqn_dueling_create", per)) return 1;
+  crl_dqn_target_options t = {1, 0};
+  if (tgt) t = *tgt;
+  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_dueling_create: n_step must be in 1..16"); return 1; }
+  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_dueling_create: double_q must be 0 or 1"); return 1; }
+  return dqn_create(cfg, per, &t, device, out, c51, /*duel=*/true);
+}
+
+// the stage buffer of the forward-only calls, grown on demand
+static int dqn_stage(crl_dqn* h, size_t need) {
+  if (h->stage_bytes < need) {
+    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
+    h->stage = nullptr; h->stage_bytes = 0;
+    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
+    h->stage_bytes = need;
+  }
+  return 0;
+}
+
+int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double* value, double* adv) {
+  DQN_GUARD(h);
+  if (!h->duel) { set_error("crl_dqn_dueling_streams: the handle has one head; crl_dqn_dueling_create makes a dueling handle"); return 1; }
+  if (!h->params_set) { set_error("crl_dqn_dueling_streams: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && !obs)) { set_error("crl_dqn_dueling_streams: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  const size_t N = (size_t)n, R = (size_t)h->d.duel.R;
+  if (dqn_stage(h, N * (QD + 3 * R) * 8)) return 1;
+  double* so = static_cast<double*>(h->stage);
+  double *sv = so + N * QD, *sa = sv + N * R;
+  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
+                     (double*)nullptr, sv, sa);
+  CRL_HIP_CHECK(hipGetLastError());
+  if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, sv, N * R * 8, hipMemcpyDeviceToHost, h->stream));
+  if (adv) CRL_HIP_CHECK(hipMemcpyAsync(adv, sa, N * 2 * R * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int32_t crl_dqn_param_count(crl_dqn* h, size_t* n) {
   DQN_GUARD(h);
   if (!n) { set_error("crl_dqn_param_count: null argument"); return 1; }
@@ -1216,16 +1670,13 @@ int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* prob
   if (n < 0 || (n > 0 && (!obs || !probs))) { set_error("crl_dqn_c51_probs: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t N = (size_t)n, NA = 2 * (size_t)h->d.c51.N, need = N * (QD + NA) * 8;
-  if (h->stage_bytes < need) {
-    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
-    h->stage = nullptr; h->stage_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
-    h->stage_bytes = need;
-  }
+  if (dqn_stage(h, need)) return 1;
   double* so = static_cast<double*>(h->stage);
   double* sp = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n,
+                                  (double*)nullptr, sp, (double*)nullptr, (double*)nullptr);
+  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1400,7 +1851,8 @@ int32_t crl_dqn_write_params(crl_dqn* h, const float* q_params, size_t n) {
 int32_t crl_dqn_init_params(crl_dqn* h, uint64_t seed) {
   DQN_GUARD(h);
   std::vector<float> w(h->P);
-  if (h->c51 ? crl_dqn_c51_make_nn(seed, h->d.c51.N, w.data(), w.size()) : crl_dqn_make_nn(seed, w.data(), w.size())) return 1;
+  if (h->duel ? crl_dqn_dueling_make_nn(seed, h->c51 ? h->d.c51.N : 0, w.data(), w.size())
+              : h->c51 ? crl_dqn_c51_make_nn(seed, h->d.c51.N, w.data(), w.size()) : crl_dqn_make_nn(seed, w.data(), w.size())) return 1;
   return crl_dqn_write_params(h, w.data(), w.size());
 }
 
@@ -1480,16 +1932,13 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   if (n < 0 || (n > 0 && (!obs || !q))) { set_error("crl_dqn_q_values: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t N = (size_t)n, need = N * (QD + QA) * 8;
-  if (h->stage_bytes < need) {
-    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
-    h->stage = nullptr; h->stage_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
-    h->stage_bytes = need;
-  }
+  if (dqn_stage(h, need)) return 1;
   double* so = static_cast<double*>(h->stage);
   double* sq = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, sq,
+                                  (double*)nullptr, (double*)nullptr, (double*)nullptr);
+  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
   else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(128), 0, h->stream, h->d.q, so, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1507,7 +1956,9 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
   if (value_eval_scratch(h->eval, cfg, ev)) return 1;
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
   const dim3 grid((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), block(64 * DQN_EVAL_WAVES);
-  if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.c51,
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_eval_kernel, dim3((unsigned)((ev.n + DUEL_EVAL_WAVES - 1) / DUEL_EVAL_WAVES)), dim3(64 * DUEL_EVAL_WAVES),
+                                  duel_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  else if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.c51,
                                  (int)h->cfg.max_steps, h->cfg.gamma, ev);
   else hipLaunchKernelGGL(dqn_eval_kernel, grid, block, 0, h->stream, (const float*)h->d.q, (int)h->cfg.max_steps, h->cfg.gamma, ev);
   CRL_HIP_CHECK(hipGetLastError());

@@ -118,6 +118,23 @@ int32_t crl_dqn_c51_make_nn(uint64_t seed, int32_t n_atoms, float* out, size_t n
   return 0;
 }
 
+// the dueling net: crl_dqn_make_nn's W1 and W2 draws go to W1 and W2v, then the arrays draw in layout order: W3v(R, 84), W2a(84, 120), W3a(2R, 84)
+int32_t crl_dqn_dueling_make_nn(uint64_t seed, int32_t n_atoms, float* out, size_t n) {
+  if (n_atoms != 0 && (n_atoms < 2 || n_atoms > 64)) { set_error("crl_dqn_dueling_make_nn: n_atoms must be 0 (scalar) or in 2..64"); return 1; }
+  const int R = n_atoms == 0 ? 1 : n_atoms;
+  const size_t need = 20928 + 255 * (size_t)R;
+  if (!out || n != need) { set_error("crl_dqn_dueling_make_nn: expected " + std::to_string(need) + " floats"); return 1; }
+  crl::Rng rng{seed ^ 0xD09ull};
+  for (size_t i = 0; i < n; ++i) out[i] = 0.0f;
+  float* p = out;
+  crl::glorot_uniform(rng, 120, 4, p); p += 120 * 4 + 120;
+  crl::glorot_uniform(rng, 84, 120, p); p += 84 * 120 + 84;
+  crl::glorot_uniform(rng, R, 84, p); p += R * 84 + R;
+  crl::glorot_uniform(rng, 84, 120, p); p += 84 * 120 + 84;
+  crl::glorot_uniform(rng, 2 * R, 84, p);
+  return 0;
+}
+
 int32_t crl_ddpg_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t actor_n, float* critic, size_t critic_n) {
   int64_t na = 0, nc = 0;
   if (crl_ddpg_param_count(obs_dim, act_dim, &na, &nc)) return 1;

@@ -140,11 +140,29 @@ def make_nn_c51(seed=0, n_atoms=51):
     return out
 
 
+def make_nn_dueling(seed=0, n_atoms=None):
+    """make_nn for the dueling net (Wang et al. 2016): ten arrays W1 b1 W2v b2v W3v b3v W2a b2a W3a b3a with R = 1 (n_atoms None: scalar head) or
+    R = n_atoms rows per stream output, 20928 + 255·R numbers; the same rule, the arrays drawing in that order, so W1 and W2v get make_nn's W1 and
+    W2 draws for the same seed."""
+    rng = np.random.default_rng(seed)
+    R = 1 if n_atoms is None else int(n_atoms)
+    out = np.zeros(L.dqn_dueling_param_count(R), np.float32)
+    o = 0
+    for rows, cols in ((120, 4), (84, 120), (R, 84), (84, 120), (2 * R, 84)):
+        lim = np.sqrt(6.0 / (rows + cols))
+        out[o:o + rows * cols] = rng.uniform(-lim, lim, rows * cols).astype(np.float32)
+        o += rows * cols + rows
+    return out
+
+
 class DQNAgent:
     """q_net, target_net, Adam state, ReplayBuffer(buffer_size) and the CartPoleEnv of one dqn(config) run, on one GPU."""
 
-    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None, dist=None):
+    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None, dist=None, dueling=False):
+        if not isinstance(dueling, (bool, np.bool_)):
+            raise ValueError(f"dueling must be True or False, got {dueling!r}")
         self.config = config
+        self.dueling = bool(dueling)
         self.dist = None if dist is None else _check_c51(dist)
         self.per = None if per is None else _check_per(per, config)
         self.target = None if target is None else _check_target(target)
@@ -158,8 +176,11 @@ class DQNAgent:
                                                                                                       float(p.eps)),
                                   target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)),
                                   c51=None if self.dist is None else L.CrlDQNC51Options(int(self.dist.n_atoms), 0, float(self.dist.v_min),
-                                                                                        float(self.dist.v_max)))
-        if params is None:
+                                                                                        float(self.dist.v_max)),
+                                  dueling=self.dueling)
+        if params is None and self.dueling:
+            params = make_nn_dueling(init_seed, None if self.dist is None else self.dist.n_atoms)
+        elif params is None:
             params = make_nn(init_seed) if self.dist is None else make_nn_c51(init_seed, self.dist.n_atoms)
         self.handle.write_params(params)
 
@@ -187,7 +208,7 @@ def _eval_record(global_step, report):
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, dueling=False, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
         eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
@@ -199,7 +220,9 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     DQNTargetOptions) forms the TD target from n-step returns and / or with double Q-learning (crl_dqn_create_with), with either replay; the log records
     are unchanged, and None (default) is dqn.jl's 1-step max. `dist` (a C51Options) makes the critic categorical (crl_dqn_c51_create), with either
     replay and any target options: "Training Statistics".loss is then the cross-entropy against the projected target distribution, and the evaluation
-    record's eval_q_bias is that of the expected value. None (default) is the scalar critic, bit for bit what it was."""
+    record's eval_q_bias is that of the expected value. None (default) is the scalar critic, bit for bit what it was. `dueling=True` splits layers 2 and 3 into a value and an
+    advantage stream (crl_dqn_dueling_create), with either head, either replay and any target options; the records are unchanged, and False (default)
+    is the one-headed net, bit for bit what it was."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
     if eval_every:
@@ -207,7 +230,7 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
-    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target, dist=dist)
+    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target, dist=dist, dueling=dueling)
     start = time.time()
     global_step = 0
     while True:

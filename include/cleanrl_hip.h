@@ -713,7 +713,7 @@ int32_t crl_dqn_nstep_probe(crl_dqn* h, const double* reward, const uint8_t* ter
 typedef struct crl_dqn_c51_options { int32_t n_atoms; int32_t pad; double v_min, v_max; } crl_dqn_c51_options;   /* 24 bytes */
 int32_t crl_dqn_c51_create(const crl_dqn_config* cfg, const crl_dqn_c51_options* c51, const crl_dqn_per_options* per /* NULL = uniform */,
                            const crl_dqn_target_options* tgt /* NULL = {1, 0} */, int32_t device, crl_dqn** out);
-/* the handle's parameter count: CRL_DQN_PARAM_COUNT on every handle but a C51 one */
+/* the handle's parameter count: CRL_DQN_PARAM_COUNT on every handle but a C51 one (above) and a dueling one (20928 + 255·R, below) */
 int32_t crl_dqn_param_count(crl_dqn* h, size_t* n);
 /* crl_dqn_make_nn's rule (glorot_uniform weights, zero biases; the same trunk for the same seed) on the C51 shapes; n must be 10764 + 85·2·n_atoms */
 int32_t crl_dqn_c51_make_nn(uint64_t seed, int32_t n_atoms, float* out, size_t n);
@@ -726,6 +726,42 @@ int32_t crl_dqn_c51_read(crl_dqn* h, double* proj, double* sample_loss);
  * runs. probs (N, k) p' rows, nret[k] R, ndisc[k] disc, terminal[k]; 1 <= k <= 1024; no pointer may be NULL. */
 int32_t crl_dqn_c51_project_probe(crl_dqn* h, const double* probs, const double* nret, const double* ndisc, const uint8_t* terminal, int32_t k,
                                   double* proj);
+
+/* -----------------------------------------------------------------------------------------------------
+ * Dueling heads (Wang et al. 2016) — no reference counterpart: dqn.jl's critic has one head. A handle made by crl_dqn_dueling_create splits layers 2
+ * and 3 into a state-value stream and an advantage stream and combines them where the head's output is written. R = 1 on a scalar handle (c51 NULL),
+ * R = n_atoms on a categorical one (Rainbow's form: the combined rows are the logits the Softmax above takes, per action over i). Ten arrays, one flat
+ * float vector, each (out,in) column-major, in this order:
+ *   W1(120,4) b1  W2v(84,120) b2v  W3v(R,84) b3v  W2a(84,120) b2a  W3a(2R,84) b3a      20928 + 255·R numbers (21183 at R = 1, 33933 at R = 51)
+ * crl_dqn_param_count gives it, and crl_dqn_write_params / crl_dqn_read_params / crl_dqn_init_params take that n on such a handle. Such a handle always
+ * carries target options ({1, 0} by default), so crl_dqn_target_read works on it; the crl_dqn_c51_* calls work when c51 was given, the crl_dqn_per_*
+ * calls when per was. The cycle stays ten launches (csrc/dqn_duel.hpp, csrc/dqn.hip: dqn_duel_*_kernel); sampler, ring, n-step walk, PER tree, the TD
+ * kernels and the loss record are the other handles'. Every other crl_dqn_* call works unchanged; crl_dqn_create, crl_dqn_per_create,
+ * crl_dqn_create_with and crl_dqn_c51_create handles keep every bit of their behaviour, and crl_dqn_dueling_streams fails on them with a message naming
+ * crl_dqn_dueling_create.
+ *
+ * All Float64, one operation per written operator, no contraction; every dot product starts from 0.0, runs in input order and adds the bias last:
+ *   Forward   h1 = relu(W1·x + b1);  h2v = relu(W2v·h1 + b2v);  h2a = relu(W2a·h1 + b2a)
+ *             V_i = W3v[i,:]·h2v + b3v[i], i < R;  A_{a,i} = W3a[a·R+i,:]·h2a + b3a[a·R+i], a in {0, 1}
+ *             mean_i = (A_{0,i} + A_{1,i}) * 0.5;  out_{a,i} = V_i + (A_{a,i} − mean_i)
+ *             out is Q(a) on a scalar handle — halving is exact, so that path still runs no transcendental — and the logits on a categorical one.
+ *             crl_dqn_q_values, crl_dqn_c51_probs, the collect step and crl_dqn_evaluate all act on these bits.
+ *   Backward  g_i = the cotangent on out_{act,i} of the taken action (dz of the scalar update, dl_i of the categorical one, as pinned above):
+ *             dV_i = g_i;  dA_{act,i} = g_i * 0.5;  dA_{1−act,i} = −(g_i * 0.5)
+ *             d2v_j = relu'(h2v_j) · Σ_i W3v[i,j]·dV_i, i ascending;  d2a_j = relu'(h2a_j) · Σ_row W3a[row,j]·dA_row, row = a·R + i ascending
+ *             d1_k = relu'(h1_k) · s, s = Σ_j W2v[j,k]·d2v_j (j ascending) and then, the same accumulator on, Σ_j W2a[j,k]·d2a_j (j ascending)
+ *             weight gradients one parameter at a time over the samples in sample order from 0.0, then the Float32 projection; both rows of W3a
+ *             and b3a receive a term from every sample. Adam with ten arrays, one β-power pair each.
+ * Errors of crl_dqn_dueling_create are crl_dqn_c51_create's with c51 optional: cfg or out NULL; with c51, n_atoms outside 2..64, v_min or v_max not
+ * finite, v_min >= v_max; bad per or tgt options — each names the field.
+ * ----------------------------------------------------------------------------------------------------- */
+int32_t crl_dqn_dueling_create(const crl_dqn_config* cfg, const crl_dqn_c51_options* c51 /* NULL = scalar */, const crl_dqn_per_options* per /* NULL = uniform */,
+                               const crl_dqn_target_options* tgt /* NULL = {1, 0} */, int32_t device, crl_dqn** out);
+/* crl_dqn_make_nn's rule (glorot_uniform weights, zero biases) on the ten arrays; for the same seed W1 and W2v get the draws crl_dqn_make_nn gives W1
+ * and W2, then W3v, W2a, W3a draw in that order. n_atoms 0 = scalar (R = 1), else 2..64; n must be 20928 + 255·R. Stateless and host-only. */
+int32_t crl_dqn_dueling_make_nn(uint64_t seed, int32_t n_atoms /* 0 = scalar */, float* out, size_t n);
+/* the two streams before they are combined, for n observations (4, n): value (R, n), adv (R, 2, n) with i fastest. Either output may be NULL. */
+int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double* value, double* adv);
 
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,

@@ -603,7 +603,8 @@ function _default_dqn_init()
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
              chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
-             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options}=nothing)
+             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options}=nothing,
+             dueling::Bool=false)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
@@ -612,7 +613,15 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   h = Ref{Ptr{Cvoid}}(C_NULL)
   popt = per === nothing ? nothing :
          CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
-  if dist !== nothing       # the categorical critic, with either replay and any target options (NULL = uniform, NULL = {1, 0})
+  if dueling                # the dueling heads (Wang et al. 2016; crl_dqn_dueling_create), with either head (NULL = scalar), either replay and any target
+                            # options: ten arrays, 20928 + 255·R parameters (crl_dqn_param_count). Like the rest of this file, never executed.
+    copt = dist === nothing ? C_NULL : Ref(CrlDQNC51Options(dist.n_atoms, 0, dist.v_min, dist.v_max))
+    pref = popt === nothing ? C_NULL : Ref(popt)
+    tref = target === nothing ? C_NULL : Ref(CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0))
+    GC.@preserve copt pref tref check(ccall((:crl_dqn_dueling_create, libcrl), Int32, (Ref{CrlDQNConfig}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}),
+      cfg, copt === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, copt), pref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, pref),
+      tref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tref), device, h))
+  elseif dist !== nothing   # the categorical critic, with either replay and any target options (NULL = uniform, NULL = {1, 0})
     2 <= dist.n_atoms <= 64 || throw(ArgumentError("dqn: dist.n_atoms must be in 2..64, got $(dist.n_atoms)"))
     (isfinite(dist.v_min) && isfinite(dist.v_max) && dist.v_min < dist.v_max) || throw(ArgumentError("dqn: dist needs finite v_min < v_max"))
     target === nothing || 1 <= target.n_step <= 16 || throw(ArgumentError("dqn: target.n_step must be in 1..16, got $(target.n_step)"))
@@ -639,7 +648,7 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   end
   agent = DQNAgent(h[])
   finalizer(x -> ccall((:crl_dqn_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
-  params === nothing && init !== nothing && dist === nothing && (params = init())   # dqn.jl:39 make_nn(env); its head is the scalar one, so a C51
+  params === nothing && init !== nothing && dist === nothing && !dueling && (params = init())   # dqn.jl:39 make_nn(env); its head is the scalar one, so a C51
                                                                                     # agent without `params` takes the library's initialiser
   if params === nothing
     check(ccall((:crl_dqn_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))

@@ -85,7 +85,10 @@ def main():
         if "--c51" in argv or co:
             argv = [a for a in argv if a != "--c51"]
             dist = crl.C51Options(**co)
-        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, target, dist, to_terminal=True, to_tensorboard=False, **kw).close()
+        # the dueling heads (crl_dqn_dueling_create): --dueling combines with --per, --double_q / --n_step and --c51
+        dueling = "--dueling" in argv
+        argv = [a for a in argv if a != "--dueling"]
+        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, target, dist, dueling, to_terminal=True, to_tensorboard=False, **kw).close()
 
 
 if __name__ == "__main__":
