@@ -22,47 +22,13 @@
 #include "dqn_target.hpp"
 #include "dqn_c51.hpp"
 #include "dqn_duel.hpp"
+#include "dqn_loops.hpp"   // the net's shape, DQNCtl, DQNDev, and the loops the heads share
 #include "replay_sample.hpp"
 #include "value_eval.hpp"
 
 struct crl_dqn;
 
 namespace crl {
-
-constexpr int QH1 = 120, QH2 = 84, QD = 4, QA = 2;
-constexpr int QoW1 = 0, Qob1 = QH1 * QD, QoW2 = Qob1 + QH1, Qob2 = QoW2 + QH2 * QH1, QoW3 = Qob2 + QH2, Qob3 = QoW3 + QA * QH2;
-constexpr int QP = Qob3 + QA;
-static_assert(QP == CRL_DQN_PARAM_COUNT, "parameter count");
-constexpr int DQN_MAX_EPS = 8192, DQN_MAX_LOSSES = 4096, DQN_MAX_BATCH = 1024, DQN_MAX_CAP = 1 << 16;
-
-struct DQNCtl {
-  double env[4]; double episode_return, last_loss;
-  int64_t global_step, episode_length, n_updates, taken, ptr, size, budget;
-  int32_t env_t, n_eps, n_losses, train_pending;
-};
-
-struct DQNDev {
-  crl_dqn_config cfg;
-  float *q, *t, *grads, *m, *v; double* betap;
-  DQNCtl* ctl; crl_dqn_episode* eps; crl_dqn_loss_record* losses;
-  double *rb_state, *rb_next, *rb_reward; int32_t* rb_action; uint8_t* rb_terminal;
-  double *H1, *H2, *Q, *dz, *sq, *d2, *d1;   // [nets][120·k], [nets][84·k], [nets][2·k], [k], [k], [84·k], [120·k]
-  int32_t* idx;                               // [k] minibatch indices into the ring
-  const int32_t* boot;                        // [k] the slots whose next_state the target bootstraps from: idx, or tgt.last on a crl_dqn_create_with handle
-  int32_t nets, pad;                          // forward passes per update: q_net(state), target_net(x) and, under double_q, q_net(x)
-  PerDev per;                                 // prioritized replay (crl_dqn_per_create); all zero on a crl_dqn_create handle
-  TgtDev tgt;                                 // n-step / double-Q targets (crl_dqn_create_with); all zero on the other handles
-  C51Dev c51;                                 // the categorical head (crl_dqn_c51_create; such a handle also has tgt.on); all zero on the other handles
-  DuelDev duel;                               // the dueling heads (crl_dqn_dueling_create; such a handle also has tgt.on, and c51.on if categorical): then H2
-                                              // and d2 hold 168 units per sample; all zero on the other handles
-};
-
-__device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
-#pragma clang fp contract(off)
-  const double slope = (end_e - start_e) / duration;
-  const double v = slope * t + start_e;
-  return v > end_e ? v : end_e;
-}
 
 // ------------------------------------------------------------------------------------------------------
 // One cycle = [collect: env steps up to and including the next training step] → [update phases]. The schedule is
@@ -76,7 +42,11 @@ __global__ void dqn_begin_kernel(DQNDev a, int64_t max_env_steps) {
   a.ctl->n_eps = 0; a.ctl->n_losses = 0; a.ctl->taken = 0; a.ctl->budget = max_env_steps;
 }
 
-// dqn.jl:57-93: env steps until a training step is due (train_pending = 1), the budget or total_timesteps is used up
+// dqn.jl:57-93: env steps until a training step is due (train_pending = 1), the budget or total_timesteps is used up. This kernel keeps ITS OWN text of
+// the loop that dqn_collect_loop (dqn_loops.hpp) states for the categorical and the dueling head, and its own static arrays: around the shared loop,
+// with the scratch gathered into one DQNCollectLds, it measured 44.2 us per launch against 43.1 us (the plain cycle 172.3 us against the parent's
+// 170.0-170.4: DESIGN.md §3k). A change to the ring, the episode record or the train_pending rule is made here AND in dqn_collect_loop. The greedy
+// forward is the shared dqn_block_trunk + dqn_head_row: with them the kernel's instructions are the parent's but for where one loop base is folded.
 __global__ void __launch_bounds__(128) dqn_collect_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   __shared__ DQNCtl c;
@@ -108,27 +78,8 @@ __global__ void __launch_bounds__(128) dqn_collect_kernel(DQNDev a) {
     __syncthreads();
     if (!go) break;
     if (need_q) {                                                                    // dqn.jl:64 qs = q_net(obs)
-      if (tid < QH1) {
-        double acc = 0.0;
-        for (int kk = 0; kk < QD; ++kk) acc += (double)wq[QoW1 + tid + QH1 * kk] * obs[kk];
-        acc += (double)wq[Qob1 + tid];
-        h1s[tid] = acc > 0.0 ? acc : 0.0;
-      }
-      __syncthreads();
-      if (tid < QH2) {
-        double acc = 0.0;
-#pragma unroll 8
-        for (int kk = 0; kk < QH1; ++kk) acc += (double)wq[QoW2 + tid + QH2 * kk] * h1s[kk];
-        acc += (double)wq[Qob2 + tid];
-        h2s[tid] = acc > 0.0 ? acc : 0.0;
-      }
-      __syncthreads();
-      if (tid < QA) {
-        double acc = 0.0;
-#pragma unroll 4
-        for (int kk = 0; kk < QH2; ++kk) acc += (double)wq[QoW3 + tid + QA * kk] * h2s[kk];
-        qs[tid] = acc + (double)wq[Qob3 + tid];
-      }
+      dqn_block_trunk(wq, obs, h1s, h2s);
+      if (tid < QA) qs[tid] = dqn_head_row(wq, QA, tid, h2s);
       __syncthreads();
     }
     if (tid == 0) {
@@ -193,44 +144,67 @@ __global__ void __launch_bounds__(256) dqn_fwd2_kernel(DQNDev a) {
   acc += (double)p[Qob2 + j];
   a.H2[(size_t)net * QH2 * k + r] = acc > 0.0 ? acc : 0.0;
 }
-__global__ void __launch_bounds__(256) dqn_fwd3_kernel(DQNDev a) {
+// the head's `rows` outputs of every pass → dst [nets][k][rows]: one output element per thread, input order, bias last. The scalar head's two Q(a)
+// go to Q (rows is a compile-time 2 there), the categorical head's 2N logits to c51.L: two kernels, so that neither branches on its caller.
+__device__ __forceinline__ void dqn_fwd3_rows(const DQNDev& a, int rows, double* dst) {
 #pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
   const int k = (int)a.cfg.batch_size, o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= a.nets * QA * k) return;
-  const int net = o / (QA * k), r = o - net * (QA * k), b = r / QA, aa = r - b * QA;
-  const float* p = net == 1 ? a.t : a.q;
-  const double* h = a.H2 + (size_t)net * QH2 * k + (size_t)QH2 * b;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int kk = 0; kk < QH2; ++kk) acc += (double)p[QoW3 + aa + QA * kk] * h[kk];
-  a.Q[(size_t)net * QA * k + r] = acc + (double)p[Qob3 + aa];
+  if (o >= a.nets * rows * k) return;
+  const int net = o / (rows * k), r = o - net * (rows * k), b = r / rows, row = r - b * rows;
+  dst[(size_t)net * rows * k + r] = dqn_head_row(net == 1 ? a.t : a.q, rows, row, a.H2 + (size_t)net * QH2 * k + (size_t)QH2 * b);
 }
-// TD target, mse, output cotangent (dqn.jl:99-107); one block, the loss is summed in sample order by thread 0
+__global__ void __launch_bounds__(256) dqn_fwd3_kernel(DQNDev a) {
+  if (!a.ctl->train_pending) return;
+  dqn_fwd3_rows(a, QA, a.Q);
+}
+// The TD launch of the scalar heads, one block: TD target, mse, output cotangent (dqn.jl:99-107), the loss summed in sample order by thread 0.
+// TGT = false is dqn.jl's target, td = reward + gamma·max target_net(x)·(1 − terminal) at the sampled slot, and touches nothing of a.tgt. TGT = true
+// (crl_dqn_create_with and the scalar dueling handles) is dqn_target.hpp's: a* from q_net(x) (plane 2) under double_q, next_q = target_net(x)[a*],
+// td = R + disc·next_q·(1 − terminal[last]); at n_step = 1 without double_q that is the same arithmetic. PER = true takes the place of the mse by the
+// importance-weighted one, loss = (Σ_b w_b·δ_b², sample order)/k, dz_b = −2·w_b·δ_b/k, and adds the priority write-back of dqn_per.hpp: the new
+// leaves of idx_b, max_leaf raised to the batch's largest new leaf, the ancestors repaired.
+template <bool TGT, bool PER>
 __global__ void __launch_bounds__(1024) dqn_td_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
+  __shared__ float lmax[16];
+  const PerDev& p = a.per;
   const int k = (int)a.cfg.batch_size;
+  float mine = 0.0f;
   for (int b = threadIdx.x; b < k; b += blockDim.x) {
     const double tq0 = a.Q[(size_t)QA * k + QA * b], tq1 = a.Q[(size_t)QA * k + QA * b + 1];
-    const double next_q = tq1 > tq0 ? tq1 : tq0;
     const int s = a.idx[b];
-    const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
+    double td;
+    if constexpr (TGT) {
+      const TgtDev& t = a.tgt;
+      const double sq0 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b] : 0.0, sq1 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b + 1] : 0.0;
+      const int astar = tgt_astar(t.double_q, sq0, sq1, tq0, tq1);
+      td = tgt_td(t.nret[b], t.ndisc[b], astar ? tq1 : tq0, a.rb_terminal[t.last[b]]);
+      t.astar[b] = astar; t.td[b] = td;
+    } else {
+      const double next_q = tq1 > tq0 ? tq1 : tq0;
+      td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
+    }
     const double diff = td - a.Q[QA * b + a.rb_action[s]];
-    a.sq[b] = diff * diff;
-    a.dz[b] = -2.0 * diff / (double)k;
+    if constexpr (PER) {
+      const double w = p.w[b];
+      a.sq[b] = w * (diff * diff);
+      a.dz[b] = -2.0 * w * diff / (double)k;
+      per_td_writeback(p, b, s, diff < 0.0 ? -diff : diff, mine);
+    } else {
+      a.sq[b] = diff * diff;
+      a.dz[b] = -2.0 * diff / (double)k;
+    }
   }
+  if constexpr (PER) per_block_max(mine, lmax);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double loss = 0.0;
-    for (int b = 0; b < k; ++b) loss += a.sq[b];
-    a.ctl->last_loss = loss / (double)k;
-  }
+  if (threadIdx.x == 0) dqn_loss_in_sample_order(a);
+  if constexpr (PER) per_batch_tail(p, a.idx, k, lmax);
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Prioritized replay (crl_dqn_per_create; dqn_per.hpp): these two take the places of dqn_sample_kernel and dqn_td_kernel in the cycle, which stays ten
-// launches. One block of 1024 each.
+// Prioritized replay (crl_dqn_per_create; dqn_per.hpp): dqn_per_sample_kernel takes the place of dqn_sample_kernel and the TD launch is a PER = true
+// instantiation of dqn_td_kernel, so the cycle stays ten launches. One block of 1024 each.
 // ------------------------------------------------------------------------------------------------------
 // Add (the slots the ring took since the last update get max_leaf, their ancestors are repaired), beta(g), the draw, the weights
 __device__ __forceinline__ void dqn_per_sample_body(const DQNDev& a) {
@@ -252,45 +226,6 @@ __global__ void __launch_bounds__(1024) dqn_per_sample_kernel(DQNDev a) {
   if (!a.ctl->train_pending) return;
   dqn_per_sample_body(a);
 }
-// dqn_td_kernel with importance weights, plus the priority write-back: loss = (Σ_b w_b·δ_b², sample order)/k, dz_b = −2·w_b·δ_b/k, the new leaves of
-// idx_b (duplicates write identical values: the same slot has the same δ), max_leaf raised to the batch's largest new leaf, the ancestors repaired
-__global__ void __launch_bounds__(1024) dqn_per_td_kernel(DQNDev a) {
-#pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
-  __shared__ float lmax[16];
-  const PerDev& p = a.per;
-  const int k = (int)a.cfg.batch_size, C = p.C;
-  float mine = 0.0f;
-  for (int b = threadIdx.x; b < k; b += blockDim.x) {
-    const double tq0 = a.Q[(size_t)QA * k + QA * b], tq1 = a.Q[(size_t)QA * k + QA * b + 1];
-    const double next_q = tq1 > tq0 ? tq1 : tq0;
-    const int s = a.idx[b];
-    const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
-    const double diff = td - a.Q[QA * b + a.rb_action[s]];
-    const double w = p.w[b];
-    a.sq[b] = w * (diff * diff);
-    a.dz[b] = -2.0 * w * diff / (double)k;
-    const double ad = diff < 0.0 ? -diff : diff;
-    const float leaf = per_leaf(ad, p.eps, p.alpha);
-    p.abs_td[b] = ad;
-    p.tree[C + s] = (double)leaf;
-    mine = leaf > mine ? leaf : mine;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
-  if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double loss = 0.0;
-    for (int b = 0; b < k; ++b) loss += a.sq[b];
-    a.ctl->last_loss = loss / (double)k;
-    float top = p.ctl->max_leaf;
-    for (int i = 0; i < (int)(blockDim.x + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
-    p.ctl->max_leaf = top;
-  }
-  const int32_t* idx = a.idx;
-  per_repair(p.tree, C, k, [=](int i) { return (int)idx[i]; });
-}
 // crl_dqn_per_probe: the sampler alone on a scratch tree whose leaves the host wrote (every inner node is rebuilt first)
 __global__ void __launch_bounds__(1024) dqn_per_probe_kernel(double* tree, int C, int n, int k, uint64_t seed, uint64_t g, double beta, int32_t* idx,
                                                              double* w) {
@@ -300,8 +235,8 @@ __global__ void __launch_bounds__(1024) dqn_per_probe_kernel(double* tree, int C
 }
 
 // ------------------------------------------------------------------------------------------------------
-// n-step / double-Q targets (crl_dqn_create_with; dqn_target.hpp): these two take the places of the sampling launch and of the TD launch, PER or
-// uniform, so the cycle stays ten launches. One block of 1024 each.
+// n-step / double-Q targets (crl_dqn_create_with; dqn_target.hpp): dqn_tgt_sample_kernel takes the place of the sampling launch and the TD launch is
+// a TGT = true instantiation of dqn_td_kernel, PER or uniform, so the cycle stays ten launches. One block of 1024 each.
 // ------------------------------------------------------------------------------------------------------
 // The draw of the handle's replay, then each sample's n-step walk in the block that drew: both samplers end on a block barrier, after which idx is
 // visible to every thread; the ring and its write pointer are those the collect launch left.
@@ -317,61 +252,6 @@ __global__ void __launch_bounds__(1024) dqn_tgt_sample_kernel(DQNDev a) {
     int last, m; double R, disc;
     nstep_walk(a.rb_reward, a.rb_terminal, cap, ptr, (int)a.idx[j], t.n_step, a.cfg.gamma, last, m, R, disc);
     t.last[j] = last; t.m[j] = m; t.nret[j] = R; t.ndisc[j] = disc;
-  }
-}
-// dqn_td_kernel / dqn_per_td_kernel with the target of dqn_target.hpp: a* from q_net(x) (plane 2) under double_q, next_q = target_net(x)[a*],
-// td = R + disc·next_q·(1 − terminal[last]); mse or the importance-weighted mse, dz and the PER write-back are the originals'
-template <bool PER>
-__global__ void __launch_bounds__(1024) dqn_tgt_td_kernel(DQNDev a) {
-#pragma clang fp contract(off)
-  if (!a.ctl->train_pending) return;
-  __shared__ float lmax[16];
-  const PerDev& p = a.per;
-  const TgtDev& t = a.tgt;
-  const int k = (int)a.cfg.batch_size, C = p.C;
-  float mine = 0.0f;
-  for (int b = threadIdx.x; b < k; b += blockDim.x) {
-    const double tq0 = a.Q[(size_t)QA * k + QA * b], tq1 = a.Q[(size_t)QA * k + QA * b + 1];
-    const double sq0 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b] : 0.0, sq1 = t.double_q ? a.Q[(size_t)2 * QA * k + QA * b + 1] : 0.0;
-    const int astar = tgt_astar(t.double_q, sq0, sq1, tq0, tq1);
-    const double next_q = astar ? tq1 : tq0;
-    const int s = a.idx[b];
-    const double td = tgt_td(t.nret[b], t.ndisc[b], next_q, a.rb_terminal[t.last[b]]);
-    const double diff = td - a.Q[QA * b + a.rb_action[s]];
-    t.astar[b] = astar; t.td[b] = td;
-    if constexpr (PER) {
-      const double w = p.w[b];
-      a.sq[b] = w * (diff * diff);
-      a.dz[b] = -2.0 * w * diff / (double)k;
-      const double ad = diff < 0.0 ? -diff : diff;
-      const float leaf = per_leaf(ad, p.eps, p.alpha);
-      p.abs_td[b] = ad;
-      p.tree[C + s] = (double)leaf;
-      mine = leaf > mine ? leaf : mine;
-    } else {
-      a.sq[b] = diff * diff;
-      a.dz[b] = -2.0 * diff / (double)k;
-    }
-  }
-  if constexpr (PER) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
-    if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = mine;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double loss = 0.0;
-    for (int b = 0; b < k; ++b) loss += a.sq[b];
-    a.ctl->last_loss = loss / (double)k;
-    if constexpr (PER) {
-      float top = p.ctl->max_leaf;
-      for (int i = 0; i < (int)(blockDim.x + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
-      p.ctl->max_leaf = top;
-    }
-  }
-  if constexpr (PER) {
-    const int32_t* idx = a.idx;
-    per_repair(p.tree, C, k, [=](int i) { return (int)idx[i]; });
   }
 }
 
@@ -449,32 +329,10 @@ __global__ void __launch_bounds__(64) dqn_wgrad_kernel(DQNDev a) {
   }
   a.grads[p] = (float)g;
 }
-// Flux Adam(lr) (dqn.jl:41,109: optim.hpp's entry step without the clip, one β-power pair per array) + hard target copy (dqn.jl:111-113) + loss record
-// (dqn.jl:115-117); one block
+// the Adam launch of the plain net: dqn_adam_step over the six arrays W1 b1 W2 b2 W3 b3, whose bounds are compile-time here; one block
 __global__ void __launch_bounds__(1024) dqn_adam_kernel(DQNDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int tid = threadIdx.x, nth = blockDim.x;
-  const int64_t gstep = a.ctl->global_step;
-  const bool copy = gstep % a.cfg.target_net_freq == 0;
-  for (int p = tid; p < QP; p += nth) {
-    const int arr = p < Qob1 ? 0 : p < QoW2 ? 1 : p < Qob2 ? 2 : p < QoW3 ? 3 : p < Qob3 ? 4 : 5;
-    float mi, vi, w;
-    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
-    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
-    if (copy) a.t[p] = w;
-  }
-  __syncthreads();
-  if (tid < 6) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
-  if (tid == 0) {
-    DQNCtl* c = a.ctl;
-    c->n_updates += 1;
-    if (gstep % a.cfg.log_frequency == 0) {
-      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
-      c->n_losses += 1;
-    }
-    c->train_pending = 0;
-  }
+  dqn_adam_step(a, QP, 6, [](int p) { return dqn_array_of(p, Qob3); });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -485,9 +343,8 @@ __global__ void __launch_bounds__(1024) dqn_adam_kernel(DQNDev a) {
 // What the collect kernel keeps in LDS besides the weights. All of it lives in the dynamic region (the weights alone pass the 64 KB static limit at
 // N >= 36), the struct first so that the float image behind it starts 16-byte aligned.
 struct C51CollectLds {
-  DQNCtl c;
-  double obs[QD], h1s[QH1], h2s[QH2], ls[2 * C51_MAX_ATOMS], qs[QA], eps_s;
-  int go, need_q, action_s, pad;
+  DQNCollectLds s;
+  double h1s[QH1], h2s[QH2], ls[2 * C51_MAX_ATOMS];
 };
 constexpr size_t C51_COLLECT_LDS = (sizeof(C51CollectLds) + 15) / 16 * 16;
 extern __shared__ __attribute__((aligned(16))) char c51_smem[];
@@ -505,98 +362,31 @@ __device__ __forceinline__ void c51_block_q(const double* ls, double* qs, const 
 }
 
 // dqn_collect_kernel with the categorical head: a greedy step forms the 2N logits (one row per thread), then Q(a) as above
-__global__ void __launch_bounds__(128) dqn_c51_collect_kernel(DQNDev a) {
+__global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_collect_kernel(DQNDev a) {
 #pragma clang fp contract(off)
-  C51CollectLds& s = *reinterpret_cast<C51CollectLds*>(c51_smem);
+  C51CollectLds& l = *reinterpret_cast<C51CollectLds*>(c51_smem);
+  DQNCollectLds& s = l.s;
   float* const wq = reinterpret_cast<float*>(c51_smem + C51_COLLECT_LDS);
-  DQNCtl& c = s.c;
-  const int tid = threadIdx.x, P = a.c51.P, NA = 2 * a.c51.N, ob3 = QoW3 + NA * QH2;
-  if (tid == 0) c = *a.ctl;
+  const int tid = threadIdx.x, P = a.c51.P, NA = 2 * a.c51.N;
+  if (tid == 0) s.c = *a.ctl;
   __syncthreads();
-  if (c.train_pending || c.taken >= c.budget || c.global_step >= a.cfg.total_timesteps) return;
-  for (int p = tid; p < P; p += 128) wq[p] = a.q[p];
+  if (s.c.train_pending || s.c.taken >= s.c.budget || s.c.global_step >= a.cfg.total_timesteps) return;   // as dqn_collect_kernel: no weight load
+  for (int p = tid; p < P; p += DQN_OBS_BLOCK) wq[p] = a.q[p];
   __syncthreads();
-  while (true) {
-    if (tid == 0) {
-      s.go = (!c.train_pending && c.taken < c.budget && c.global_step < a.cfg.total_timesteps) ? 1 : 0;
-      if (s.go) {
-        c.global_step += 1; c.taken += 1;
-        const uint64_t gstep = (uint64_t)c.global_step;
-        for (int i = 0; i < QD; ++i) s.obs[i] = c.env[i];
-        s.eps_s = dq_linear_schedule(a.cfg.epsilon_start, a.cfg.epsilon_end, a.cfg.epsilon_duration, (double)c.global_step);
-        if (u53(philox_env(a.cfg.seed, 0u, gstep, 0u)) < s.eps_s) {
-          s.need_q = 0;
-          s.action_s = (int)(philox_env(a.cfg.seed, 0u, gstep, 4u).x >> 31);
-        } else s.need_q = 1;
-      }
-    }
+  dqn_collect_loop(a, s, [&] {
+#pragma clang fp contract(off)
+    dqn_block_trunk(wq, s.obs, l.h1s, l.h2s);
+    if (tid < NA) l.ls[tid] = dqn_head_row(wq, NA, tid, l.h2s);
     __syncthreads();
-    if (!s.go) break;
-    if (s.need_q) {
-      if (tid < QH1) {
-        double acc = 0.0;
-        for (int kk = 0; kk < QD; ++kk) acc += (double)wq[QoW1 + tid + QH1 * kk] * s.obs[kk];
-        acc += (double)wq[Qob1 + tid];
-        s.h1s[tid] = acc > 0.0 ? acc : 0.0;
-      }
-      __syncthreads();
-      if (tid < QH2) {
-        double acc = 0.0;
-#pragma unroll 8
-        for (int kk = 0; kk < QH1; ++kk) acc += (double)wq[QoW2 + tid + QH2 * kk] * s.h1s[kk];
-        acc += (double)wq[Qob2 + tid];
-        s.h2s[tid] = acc > 0.0 ? acc : 0.0;
-      }
-      __syncthreads();
-      if (tid < NA) {
-        double acc = 0.0;
-#pragma unroll 4
-        for (int kk = 0; kk < QH2; ++kk) acc += (double)wq[QoW3 + tid + NA * kk] * s.h2s[kk];
-        s.ls[tid] = acc + (double)wq[ob3 + tid];
-      }
-      __syncthreads();
-      c51_block_q(s.ls, s.qs, a.c51, nullptr);
-    }
-    if (tid == 0) {
-      const uint64_t gstep = (uint64_t)c.global_step;
-      const int action = s.need_q ? (s.qs[1] > s.qs[0] ? 1 : 0) : s.action_s;
-      const bool done = cartpole_step64(c.env, c.env_t, action, a.cfg.max_steps);
-      const double rew = done ? 0.0 : 1.0;
-      const size_t p = (size_t)c.ptr;
-      for (int i = 0; i < QD; ++i) { a.rb_state[QD * p + i] = s.obs[i]; a.rb_next[QD * p + i] = c.env[i]; }
-      a.rb_action[p] = action; a.rb_reward[p] = rew; a.rb_terminal[p] = done ? 1 : 0;
-      c.ptr = c.ptr + 1 >= a.cfg.buffer_size ? 0 : c.ptr + 1;
-      c.size = c.size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c.size + 1;
-      c.episode_return += rew; c.episode_length += 1;
-      if (done) {
-        if (c.n_eps < DQN_MAX_EPS) {
-          a.eps[c.n_eps].episode_return = c.episode_return; a.eps[c.n_eps].episode_length = c.episode_length;
-          a.eps[c.n_eps].global_step = c.global_step; a.eps[c.n_eps].epsilon = s.eps_s;
-        }
-        c.n_eps += 1;
-        c.episode_length = 0; c.episode_return = 0.0;
-        env_reset64(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
-      }
-      c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step % a.cfg.train_freq == 0) ? 1 : 0;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) *a.ctl = c;
+    c51_block_q(l.ls, s.qs, a.c51, nullptr);
+  });
+  if (tid == 0) *a.ctl = s.c;
 }
 
-// the 2N logits of every pass: one output element per thread, input order, bias last
+// the 2N logits of every pass → c51.L: dqn_fwd3_rows with the categorical head's row count
 __global__ void __launch_bounds__(256) dqn_c51_fwd3_kernel(DQNDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int k = (int)a.cfg.batch_size, NA = 2 * a.c51.N, o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= a.nets * NA * k) return;
-  const int net = o / (NA * k), r = o - net * (NA * k), b = r / NA, row = r - b * NA;
-  const float* p = net == 1 ? a.t : a.q;
-  const double* h = a.H2 + (size_t)net * QH2 * k + (size_t)QH2 * b;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int kk = 0; kk < QH2; ++kk) acc += (double)p[QoW3 + row + NA * kk] * h[kk];
-  a.c51.L[(size_t)net * NA * k + r] = acc + (double)p[QoW3 + NA * QH2 + row];
+  dqn_fwd3_rows(a, 2 * a.c51.N, a.c51.L);
 }
 
 // The TD launch of a C51 handle: one wave per sample, one lane per atom, C51_TD_WAVES samples per block, ⌈k / C51_TD_WAVES⌉ blocks — the per-sample work
@@ -692,88 +482,38 @@ __global__ void __launch_bounds__(64) dqn_c51_wgrad_kernel(DQNDev a) {
 }
 // dqn_adam_kernel over the C51 handle's P parameters: the same six arrays, the head's two being longer. Being the cycle's one-block launch behind the
 // TD launch, it first does what needs the whole batch: loss = (Σ_b sq_b, sample order) / k, and under PER max_leaf raised to the batch's largest new
-// leaf and the ancestors of the written leaves repaired (dqn_tgt_td_kernel's tail): dqn_c51_batch_tail, which dqn_duel_adam_kernel runs as well.
+// leaf and the ancestors of the written leaves repaired (dqn_td_kernel<·, true>'s tail; here the maximum is taken over the leaves that
+// dqn_c51_td_kernel wrote): dqn_c51_batch_tail, which dqn_duel_adam_kernel runs as well.
 __device__ __forceinline__ void dqn_c51_batch_tail(const DQNDev& a) {
 #pragma clang fp contract(off)
-  const int tid = threadIdx.x, nth = blockDim.x;
-  if (tid == 0) {
-    const int k = (int)a.cfg.batch_size;
-    double loss = 0.0;
-    for (int b = 0; b < k; ++b) loss += a.sq[b];
-    a.ctl->last_loss = loss / (double)k;
-  }
+  if (threadIdx.x == 0) dqn_loss_in_sample_order(a);
   if (a.per.on) {
     __shared__ float lmax[16];
     const PerDev& p = a.per;
     const int k = (int)a.cfg.batch_size;
-    const int32_t* idx = a.idx;
     float mine = 0.0f;
-    for (int b = tid; b < k; b += nth) { const float leaf = (float)p.tree[p.C + idx[b]]; mine = leaf > mine ? leaf : mine; }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
-    if ((tid & 63) == 0) lmax[tid >> 6] = mine;
+    for (int b = threadIdx.x; b < k; b += blockDim.x) { const float leaf = (float)p.tree[p.C + a.idx[b]]; mine = leaf > mine ? leaf : mine; }
+    per_block_max(mine, lmax);
     __syncthreads();
-    if (tid == 0) {
-      float top = p.ctl->max_leaf;
-      for (int i = 0; i < (nth + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
-      p.ctl->max_leaf = top;
-    }
-    per_repair(p.tree, p.C, k, [=](int i) { return (int)idx[i]; });
+    per_batch_tail(p, a.idx, k, lmax);
   }
 }
 __global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int tid = threadIdx.x, nth = blockDim.x, P = a.c51.P, ob3 = QoW3 + 2 * a.c51.N * QH2;
   dqn_c51_batch_tail(a);
-  const int64_t gstep = a.ctl->global_step;
-  const bool copy = gstep % a.cfg.target_net_freq == 0;
-  for (int p = tid; p < P; p += nth) {
-    const int arr = p < Qob1 ? 0 : p < QoW2 ? 1 : p < Qob2 ? 2 : p < QoW3 ? 3 : p < ob3 ? 4 : 5;
-    float mi, vi, w;
-    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
-    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
-    if (copy) a.t[p] = w;
-  }
-  __syncthreads();
-  if (tid < 6) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
-  if (tid == 0) {
-    DQNCtl* c = a.ctl;
-    c->n_updates += 1;
-    if (gstep % a.cfg.log_frequency == 0) {
-      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
-      c->n_losses += 1;
-    }
-    c->train_pending = 0;
-  }
+  const int ob3 = QoW3 + 2 * a.c51.N * QH2;
+  dqn_adam_step(a, a.c51.P, 6, [=](int p) { return dqn_array_of(p, ob3); });
 }
 
 // crl_dqn_q_values and crl_dqn_c51_probs on a C51 handle: dqn_q_kernel's trunk, the 2N logits, then Q(a) and / or the probabilities (N, 2, n)
-__global__ void __launch_bounds__(128) dqn_c51_q_kernel(const float* __restrict__ q, C51Dev c, const double* __restrict__ obs, int n,
+__global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_q_kernel(const float* __restrict__ q, C51Dev c, const double* __restrict__ obs, int n,
                                                         double* __restrict__ out_q, double* __restrict__ out_p) {
 #pragma clang fp contract(off)
   __shared__ double h1s[QH1], h2s[QH2], ls[2 * C51_MAX_ATOMS], qs[QA];
   const int b = blockIdx.x, tid = threadIdx.x, NA = 2 * c.N;
   if (b >= n) return;
-  if (tid < QH1) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QD; ++kk) acc += (double)q[QoW1 + tid + QH1 * kk] * obs[(size_t)QD * b + kk];
-    acc += (double)q[Qob1 + tid];
-    h1s[tid] = acc > 0.0 ? acc : 0.0;
-  }
-  __syncthreads();
-  if (tid < QH2) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QH1; ++kk) acc += (double)q[QoW2 + tid + QH2 * kk] * h1s[kk];
-    acc += (double)q[Qob2 + tid];
-    h2s[tid] = acc > 0.0 ? acc : 0.0;
-  }
-  __syncthreads();
-  if (tid < NA) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QH2; ++kk) acc += (double)q[QoW3 + tid + NA * kk] * h2s[kk];
-    ls[tid] = acc + (double)q[QoW3 + NA * QH2 + tid];
-  }
+  dqn_block_trunk(q, obs + (size_t)QD * b, h1s, h2s);
+  if (tid < NA) ls[tid] = dqn_head_row(q, NA, tid, h2s);
   __syncthreads();
   c51_block_q(ls, qs, c, out_p ? out_p + (size_t)NA * b : nullptr);
   if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
@@ -789,30 +529,13 @@ __global__ void dqn_init_kernel(DQNDev a) {
 
 // q_net(obs) on caller-supplied observations: one thread per (observation, layer unit) would be overkill — a wave per
 // observation, lanes striding the units
-__global__ void __launch_bounds__(128) dqn_q_kernel(const float* __restrict__ q, const double* __restrict__ obs, int n, double* __restrict__ out) {
+__global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_q_kernel(const float* __restrict__ q, const double* __restrict__ obs, int n, double* __restrict__ out) {
 #pragma clang fp contract(off)
   __shared__ double h1s[QH1], h2s[QH2];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= n) return;
-  if (tid < QH1) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QD; ++kk) acc += (double)q[QoW1 + tid + QH1 * kk] * obs[(size_t)QD * b + kk];
-    acc += (double)q[Qob1 + tid];
-    h1s[tid] = acc > 0.0 ? acc : 0.0;
-  }
-  __syncthreads();
-  if (tid < QH2) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QH1; ++kk) acc += (double)q[QoW2 + tid + QH2 * kk] * h1s[kk];
-    acc += (double)q[Qob2 + tid];
-    h2s[tid] = acc > 0.0 ? acc : 0.0;
-  }
-  __syncthreads();
-  if (tid < QA) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QH2; ++kk) acc += (double)q[QoW3 + tid + QA * kk] * h2s[kk];
-    out[(size_t)QA * b + tid] = acc + (double)q[Qob3 + tid];
-  }
+  dqn_block_trunk(q, obs + (size_t)QD * b, h1s, h2s);
+  if (tid < QA) out[(size_t)QA * b + tid] = dqn_head_row(q, QA, tid, h2s);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -839,68 +562,14 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_eval_kernel(const flo
   if (env >= ev.n) return;
   double* const h1w = h1s[w];
   double* const h2w = h2s[w];
-  // a lane's second unit of each hidden layer; a lane that has none (lane + 64 past the layer) repeats its first and stores nothing
-  const int u1b = lane + 64 < QH1 ? lane + 64 : lane, u2b = lane + 64 < QH2 ? lane + 64 : lane;
-  int64_t row = 0;                       // the env's step count across its episodes
-  for (int j = 0; j < ev.episodes; ++j) {
-    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
-    int t = 0, length = 0;
-    const size_t slot = (size_t)j * ev.n + env;
-    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
-    while (true) {
-      {                                  // layer 1: units `lane` and `lane + 64`, two independent chains side by side
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < QD; ++kk) {
-          acc += (double)wq[QoW1 + lane + QH1 * kk] * s[kk];
-          acc2 += (double)wq[QoW1 + u1b + QH1 * kk] * s[kk];
-        }
-        acc += (double)wq[Qob1 + lane];
-        acc2 += (double)wq[Qob1 + u1b];
-        h1w[lane] = acc > 0.0 ? acc : 0.0;
-        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
-      }
-      wave_lds_fence();
-      {                                  // layer 2: the same pairing — 120 dependent adds per step, not 240
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll 8
-        for (int kk = 0; kk < QH1; ++kk) {
-          const double h = h1w[kk];
-          acc += (double)wq[QoW2 + lane + QH2 * kk] * h;
-          acc2 += (double)wq[QoW2 + u2b + QH2 * kk] * h;
-        }
-        acc += (double)wq[Qob2 + lane];
-        acc2 += (double)wq[Qob2 + u2b];
-        h2w[lane] = acc > 0.0 ? acc : 0.0;
-        if (lane + 64 < QH2) h2w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
-      }
-      wave_lds_fence();
-      double a0 = 0.0, a1 = 0.0;
-#pragma unroll 4
-      for (int kk = 0; kk < QH2; ++kk) {
-        const double h = h2w[kk];
-        a0 += (double)wq[QoW3 + QA * kk] * h;
-        a1 += (double)wq[QoW3 + 1 + QA * kk] * h;
-      }
-      const double q0 = a0 + (double)wq[Qob3], q1 = a1 + (double)wq[Qob3 + 1];
-      const int action = q1 > q0 ? 1 : 0;                                               // argmax: first maximum, as dqn_collect_kernel
-      if (lane == 0) {
-        if (length == 0) ev.v0[slot] = action ? q1 : q0;
-        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
-      }
-      row += 1;
-      const bool done = cartpole_step64(s, t, action, max_steps);
-      const double rew = done ? 0.0 : 1.0;
-      ret += rew;
-      disc_ret += disc * rew;
-      disc = disc * gamma;
-      length += 1;
-      wave_lds_fence();                  // the next step's strip writes stay behind this step's reads
-      if (done) break;
-    }
-    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
-  }
-  value_eval_trace_tail(ev, env, row, lane);
+  dqn_eval_episodes(ev, env, lane, max_steps, gamma, [&](const double* s, double& q0, double& q1) {
+#pragma clang fp contract(off)
+    eval_layer1_pair(wq, QoW1, Qob1, s, h1w, lane);
+    wave_lds_fence();
+    eval_layer2_pair(wq, h1w, h2w, lane);
+    wave_lds_fence();
+    eval_head_pair(wq, QA, 0, 1, h2w, q0, q1);   // every lane forms both head sums alike
+  });
 }
 
 // dqn_eval_kernel with the categorical head: the same one-wave-per-env structure with ONE staging barrier. The net (up to 86.6 KB at N = 64) and the
@@ -913,93 +582,39 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_c51_eval_kernel(const
   C51EvalWaveLds* const wl = reinterpret_cast<C51EvalWaveLds*>(c51_smem);
   float* const wq = reinterpret_cast<float*>(c51_smem + sizeof(C51EvalWaveLds) * DQN_EVAL_WAVES);
   static_assert(sizeof(C51EvalWaveLds) % 16 == 0, "the weight image starts 16-byte aligned");
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * DQN_EVAL_WAVES + w, N = c.N, NA = 2 * N, ob3 = QoW3 + NA * QH2;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, env = blockIdx.x * DQN_EVAL_WAVES + w, N = c.N;
   for (int p = threadIdx.x; p < c.P; p += 64 * DQN_EVAL_WAVES) wq[p] = q[p];
   __syncthreads();                       // the only block barrier of the kernel
   if (env >= ev.n) return;
   double* const h1w = wl[w].h1;
   double* const h2w = wl[w].h2;
   const double delta = c51_delta(c.v_min, c.v_max, N);
-  const int u1b = lane + 64 < QH1 ? lane + 64 : lane, u2b = lane + 64 < QH2 ? lane + 64 : lane;
   const int r0 = lane < N ? lane : 0, r1 = N + r0;   // a lane past N repeats atom 0 and its results are masked by the wave functions
-  int64_t row = 0;
-  for (int j = 0; j < ev.episodes; ++j) {
-    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
-    int t = 0, length = 0;
-    const size_t slot = (size_t)j * ev.n + env;
-    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
-    while (true) {
-      {
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < QD; ++kk) {
-          acc += (double)wq[QoW1 + lane + QH1 * kk] * s[kk];
-          acc2 += (double)wq[QoW1 + u1b + QH1 * kk] * s[kk];
-        }
-        acc += (double)wq[Qob1 + lane];
-        acc2 += (double)wq[Qob1 + u1b];
-        h1w[lane] = acc > 0.0 ? acc : 0.0;
-        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
-      }
-      wave_lds_fence();
-      {
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll 8
-        for (int kk = 0; kk < QH1; ++kk) {
-          const double h = h1w[kk];
-          acc += (double)wq[QoW2 + lane + QH2 * kk] * h;
-          acc2 += (double)wq[QoW2 + u2b + QH2 * kk] * h;
-        }
-        acc += (double)wq[Qob2 + lane];
-        acc2 += (double)wq[Qob2 + u2b];
-        h2w[lane] = acc > 0.0 ? acc : 0.0;
-        if (lane + 64 < QH2) h2w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
-      }
-      wave_lds_fence();
-      double a0 = 0.0, a1 = 0.0;
-#pragma unroll 4
-      for (int kk = 0; kk < QH2; ++kk) {
-        const double h = h2w[kk];
-        a0 += (double)wq[QoW3 + r0 + NA * kk] * h;
-        a1 += (double)wq[QoW3 + r1 + NA * kk] * h;
-      }
-      const double l0 = a0 + (double)wq[ob3 + r0], l1 = a1 + (double)wq[ob3 + r1];
-      double p0, p1, lp;
-      c51_softmax(l0, N, lane, p0, lp);
-      const double q0 = c51_expect(p0, c.v_min, delta, lane);
-      c51_softmax(l1, N, lane, p1, lp);
-      const double q1 = c51_expect(p1, c.v_min, delta, lane);
-      const int action = q1 > q0 ? 1 : 0;
-      if (lane == 0) {
-        if (length == 0) ev.v0[slot] = action ? q1 : q0;
-        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
-      }
-      row += 1;
-      const bool done = cartpole_step64(s, t, action, max_steps);
-      const double rew = done ? 0.0 : 1.0;
-      ret += rew;
-      disc_ret += disc * rew;
-      disc = disc * gamma;
-      length += 1;
-      wave_lds_fence();
-      if (done) break;
-    }
-    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
-  }
-  value_eval_trace_tail(ev, env, row, lane);
+  dqn_eval_episodes(ev, env, lane, max_steps, gamma, [&](const double* s, double& q0, double& q1) {
+#pragma clang fp contract(off)
+    eval_layer1_pair(wq, QoW1, Qob1, s, h1w, lane);
+    wave_lds_fence();
+    eval_layer2_pair(wq, h1w, h2w, lane);
+    wave_lds_fence();
+    double l0, l1, p0, p1, lp;
+    eval_head_pair(wq, 2 * N, r0, r1, h2w, l0, l1);
+    c51_softmax(l0, N, lane, p0, lp);
+    q0 = c51_expect(p0, c.v_min, delta, lane);
+    c51_softmax(l1, N, lane, p1, lp);
+    q1 = c51_expect(p1, c.v_min, delta, lane);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------
 // Dueling heads (crl_dqn_dueling_create; dqn_duel.hpp). One family for both heads, R = 1 (scalar) or N (categorical) at run time. W1 b1 sit at the
 // plain net's offsets, so dqn_fwd1_kernel runs unchanged, and such a handle always carries target options, so the sampling launch is
 // dqn_tgt_sample_kernel. The two streams are combined where the head's output is written (dqn_duel_fwd3_kernel): the combined Q or logits land in the
-// buffers the TD kernels read (Q, c51.L), so dqn_tgt_td_kernel / dqn_c51_td_kernel run as they are and what they leave (dz, c51.dl) is the cotangent g
+// buffers the TD kernels read (Q, c51.L), so dqn_td_kernel<true, ·> / dqn_c51_td_kernel run as they are and what they leave (dz, c51.dl) is the cotangent g
 // of out_{act,·}. The kernels below take the places of collect, fwd2, fwd3, bwd2, bwd1, wgrad and Adam: the cycle stays ten launches.
 // ------------------------------------------------------------------------------------------------------
 struct DuelCollectLds {
-  DQNCtl c;
-  double obs[QD], h1s[DUEL_H1], h2s[DUEL_U2], raw[3 * DUEL_MAX_R], ls[2 * DUEL_MAX_R], qs[QA], eps_s;   // raw: V (R), then A (2R), before they are combined
-  int go, need_q, action_s, pad;
+  DQNCollectLds s;
+  double h1s[DUEL_H1], h2s[DUEL_U2], raw[3 * DUEL_MAX_R], ls[2 * DUEL_MAX_R];   // raw: V (R), then A (2R), before they are combined
 };
 constexpr size_t DUEL_COLLECT_LDS = (sizeof(DuelCollectLds) + 15) / 16 * 16;
 struct DuelEvalWaveLds { double h1[DUEL_H1], h2[DUEL_U2]; };
@@ -1017,13 +632,7 @@ __device__ __forceinline__ void duel_block_forward(const float* W, const DuelOff
                                                    double* ls) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x, nth = blockDim.x;
-  for (int i = tid; i < DUEL_H1; i += nth) {
-    double acc = 0.0;
-    for (int kk = 0; kk < QD; ++kk) acc += (double)W[o.W1 + i + QH1 * kk] * obs[kk];
-    acc += (double)W[o.b1 + i];
-    h1s[i] = acc > 0.0 ? acc : 0.0;
-  }
-  __syncthreads();
+  dqn_block_layer1(W, obs, h1s);   // W1 b1 sit at the plain net's offsets; one unit per thread: both callers are DQN_OBS_BLOCK-thread kernels
   for (int u = tid; u < DUEL_U2; u += nth) h2s[u] = duel_hidden2(W, o, u, h1s);
   __syncthreads();
   for (int r = tid; r < 3 * R; r += nth) raw[r] = duel_head_row(W, o, R, r, h2s);
@@ -1033,67 +642,28 @@ __device__ __forceinline__ void duel_block_forward(const float* W, const DuelOff
 }
 
 // dqn_c51_collect_kernel with the dueling heads: the whole net in dynamic LDS (84.7 KB at R = 1, 149.0 KB at R = 64)
-__global__ void __launch_bounds__(128) dqn_duel_collect_kernel(DQNDev a) {
+__global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_collect_kernel(DQNDev a) {
 #pragma clang fp contract(off)
-  DuelCollectLds& s = *reinterpret_cast<DuelCollectLds*>(c51_smem);
+  DuelCollectLds& l = *reinterpret_cast<DuelCollectLds*>(c51_smem);
+  DQNCollectLds& s = l.s;
   float* const wq = reinterpret_cast<float*>(c51_smem + DUEL_COLLECT_LDS);
-  DQNCtl& c = s.c;
   const int tid = threadIdx.x, P = a.duel.P, R = a.duel.R;
   const DuelOff o = duel_off(R);
-  if (tid == 0) c = *a.ctl;
+  if (tid == 0) s.c = *a.ctl;
   __syncthreads();
-  if (c.train_pending || c.taken >= c.budget || c.global_step >= a.cfg.total_timesteps) return;
-  for (int p = tid; p < P; p += 128) wq[p] = a.q[p];
+  if (s.c.train_pending || s.c.taken >= s.c.budget || s.c.global_step >= a.cfg.total_timesteps) return;   // as dqn_collect_kernel: no weight load
+  for (int p = tid; p < P; p += DQN_OBS_BLOCK) wq[p] = a.q[p];
   __syncthreads();
-  while (true) {
-    if (tid == 0) {
-      s.go = (!c.train_pending && c.taken < c.budget && c.global_step < a.cfg.total_timesteps) ? 1 : 0;
-      if (s.go) {
-        c.global_step += 1; c.taken += 1;
-        const uint64_t gstep = (uint64_t)c.global_step;
-        for (int i = 0; i < QD; ++i) s.obs[i] = c.env[i];
-        s.eps_s = dq_linear_schedule(a.cfg.epsilon_start, a.cfg.epsilon_end, a.cfg.epsilon_duration, (double)c.global_step);
-        if (u53(philox_env(a.cfg.seed, 0u, gstep, 0u)) < s.eps_s) {
-          s.need_q = 0;
-          s.action_s = (int)(philox_env(a.cfg.seed, 0u, gstep, 4u).x >> 31);
-        } else s.need_q = 1;
-      }
+  dqn_collect_loop(a, s, [&] {
+#pragma clang fp contract(off)
+    duel_block_forward(wq, o, R, s.obs, l.h1s, l.h2s, l.raw, l.ls);
+    if (a.c51.on) c51_block_q(l.ls, s.qs, a.c51, nullptr);
+    else {
+      if (tid < QA) s.qs[tid] = l.ls[tid];
+      __syncthreads();
     }
-    __syncthreads();
-    if (!s.go) break;
-    if (s.need_q) {
-      duel_block_forward(wq, o, R, s.obs, s.h1s, s.h2s, s.raw, s.ls);
-      if (a.c51.on) c51_block_q(s.ls, s.qs, a.c51, nullptr);
-      else {
-        if (tid < QA) s.qs[tid] = s.ls[tid];
-        __syncthreads();
-      }
-    }
-    if (tid == 0) {
-      const uint64_t gstep = (uint64_t)c.global_step;
-      const int action = s.need_q ? (s.qs[1] > s.qs[0] ? 1 : 0) : s.action_s;
-      const bool done = cartpole_step64(c.env, c.env_t, action, a.cfg.max_steps);
-      const double rew = done ? 0.0 : 1.0;
-      const size_t p = (size_t)c.ptr;
-      for (int i = 0; i < QD; ++i) { a.rb_state[QD * p + i] = s.obs[i]; a.rb_next[QD * p + i] = c.env[i]; }
-      a.rb_action[p] = action; a.rb_reward[p] = rew; a.rb_terminal[p] = done ? 1 : 0;
-      c.ptr = c.ptr + 1 >= a.cfg.buffer_size ? 0 : c.ptr + 1;
-      c.size = c.size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c.size + 1;
-      c.episode_return += rew; c.episode_length += 1;
-      if (done) {
-        if (c.n_eps < DQN_MAX_EPS) {
-          a.eps[c.n_eps].episode_return = c.episode_return; a.eps[c.n_eps].episode_length = c.episode_length;
-          a.eps[c.n_eps].global_step = c.global_step; a.eps[c.n_eps].epsilon = s.eps_s;
-        }
-        c.n_eps += 1;
-        c.episode_length = 0; c.episode_return = 0.0;
-        env_reset64(c.env, a.cfg.seed, gstep, 1); c.env_t = 0;
-      }
-      c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step % a.cfg.train_freq == 0) ? 1 : 0;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) *a.ctl = c;
+  });
+  if (tid == 0) *a.ctl = s.c;
 }
 
 // the two-stream hidden layer of every pass: 168 units per sample, one per thread
@@ -1204,36 +774,15 @@ __global__ void __launch_bounds__(64) dqn_duel_wgrad_kernel(DQNDev a) {
 }
 // dqn_adam_kernel over ten arrays, one β-power pair each; on a categorical handle it first does what needs the whole batch, as dqn_c51_adam_kernel
 __global__ void __launch_bounds__(1024) dqn_duel_adam_kernel(DQNDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int tid = threadIdx.x, nth = blockDim.x, P = a.duel.P;
-  const DuelOff off = duel_off(a.duel.R);
   if (a.c51.on) dqn_c51_batch_tail(a);
-  const int64_t gstep = a.ctl->global_step;
-  const bool copy = gstep % a.cfg.target_net_freq == 0;
-  for (int p = tid; p < P; p += nth) {
-    const int arr = duel_array_of(off, p);
-    float mi, vi, w;
-    adam_entry((double)a.grads[p], a.m[p], a.v[p], a.q[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
-    a.m[p] = mi; a.v[p] = vi; a.q[p] = w;
-    if (copy) a.t[p] = w;
-  }
-  __syncthreads();
-  if (tid < DUEL_ARRAYS) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
-  if (tid == 0) {
-    DQNCtl* c = a.ctl;
-    c->n_updates += 1;
-    if (gstep % a.cfg.log_frequency == 0) {
-      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
-      c->n_losses += 1;
-    }
-    c->train_pending = 0;
-  }
+  const DuelOff off = duel_off(a.duel.R);
+  dqn_adam_step(a, a.duel.P, DUEL_ARRAYS, [&](int p) { return duel_array_of(off, p); });
 }
 
 // crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams on a dueling handle: the block's forward, then whichever outputs are asked for.
 // out_q (2, n); out_p (N, 2, n); out_v (R, n); out_a (R, 2, n), i fastest
-__global__ void __launch_bounds__(128) dqn_duel_q_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, const double* __restrict__ obs, int n,
+__global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_q_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, const double* __restrict__ obs, int n,
                                                          double* __restrict__ out_q, double* __restrict__ out_p, double* __restrict__ out_v,
                                                          double* __restrict__ out_a) {
 #pragma clang fp contract(off)
@@ -1242,7 +791,7 @@ __global__ void __launch_bounds__(128) dqn_duel_q_kernel(const float* __restrict
   if (b >= n) return;
   duel_block_forward(q, duel_off(R), R, obs + (size_t)QD * b, h1s, h2s, raw, ls);
   if (out_v && tid < R) out_v[(size_t)R * b + tid] = raw[tid];
-  if (out_a) for (int r = tid; r < 2 * R; r += 128) out_a[(size_t)2 * R * b + r] = raw[R + r];
+  if (out_a) for (int r = tid; r < 2 * R; r += DQN_OBS_BLOCK) out_a[(size_t)2 * R * b + r] = raw[R + r];
   if (c.on) {
     c51_block_q(ls, qs, c, out_p ? out_p + (size_t)2 * R * b : nullptr);
     if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
@@ -1265,86 +814,51 @@ __global__ void __launch_bounds__(64 * DUEL_EVAL_WAVES) dqn_duel_eval_kernel(con
   double* const h1w = wl[w].h1;
   double* const h2w = wl[w].h2;
   const double delta = c.on ? c51_delta(c.v_min, c.v_max, R) : 0.0;
-  const int u1b = lane + 64 < QH1 ? lane + 64 : lane;
   // the lane's three units of the two-stream layer: lane is a value unit, lane + 64 one of either stream, lane + 128 an advantage unit (lanes 0..39)
   const int ua = lane, ub = lane + 64, uc = lane + 128 < DUEL_U2 ? lane + 128 : lane;
   const auto wof = [&](int u) { return u >= QH2 ? o.W2a + u - QH2 : o.W2v + u; };
   const auto bof = [&](int u) { return u >= QH2 ? o.b2a + u - QH2 : o.b2v + u; };
   const int wa = wof(ua), wb = wof(ub), wc = wof(uc), ba = bof(ua), bb = bof(ub), bc = bof(uc);
   const int r0 = lane < R ? lane : 0;    // a lane past R repeats row 0; on a categorical handle its results are masked by the wave functions
-  int64_t row = 0;
-  for (int j = 0; j < ev.episodes; ++j) {
-    double s[QD], ret = 0.0, disc_ret = 0.0, disc = 1.0;
-    int t = 0, length = 0;
-    const size_t slot = (size_t)j * ev.n + env;
-    env_reset64(s, ev.seed, (uint64_t)j * (uint64_t)ev.n + (uint64_t)env, S_VEVAL_RESET);
-    while (true) {
-      {
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll
-        for (int kk = 0; kk < QD; ++kk) {
-          acc += (double)wq[o.W1 + lane + QH1 * kk] * s[kk];
-          acc2 += (double)wq[o.W1 + u1b + QH1 * kk] * s[kk];
-        }
-        acc += (double)wq[o.b1 + lane];
-        acc2 += (double)wq[o.b1 + u1b];
-        h1w[lane] = acc > 0.0 ? acc : 0.0;
-        if (lane + 64 < QH1) h1w[lane + 64] = acc2 > 0.0 ? acc2 : 0.0;
-      }
-      wave_lds_fence();
-      {
-        double acc = 0.0, acc2 = 0.0, acc3 = 0.0;
+  dqn_eval_episodes(ev, env, lane, max_steps, gamma, [&](const double* s, double& q0, double& q1) {
+#pragma clang fp contract(off)
+    eval_layer1_pair(wq, o.W1, o.b1, s, h1w, lane);
+    wave_lds_fence();
+    {
+      double acc = 0.0, acc2 = 0.0, acc3 = 0.0;
 #pragma unroll 8
-        for (int kk = 0; kk < QH1; ++kk) {
-          const double h = h1w[kk];
-          acc += (double)wq[wa + QH2 * kk] * h;
-          acc2 += (double)wq[wb + QH2 * kk] * h;
-          acc3 += (double)wq[wc + QH2 * kk] * h;
-        }
-        acc += (double)wq[ba];
-        acc2 += (double)wq[bb];
-        acc3 += (double)wq[bc];
-        h2w[ua] = acc > 0.0 ? acc : 0.0;
-        h2w[ub] = acc2 > 0.0 ? acc2 : 0.0;
-        if (lane + 128 < DUEL_U2) h2w[lane + 128] = acc3 > 0.0 ? acc3 : 0.0;
+      for (int kk = 0; kk < QH1; ++kk) {
+        const double h = h1w[kk];
+        acc += (double)wq[wa + QH2 * kk] * h;
+        acc2 += (double)wq[wb + QH2 * kk] * h;
+        acc3 += (double)wq[wc + QH2 * kk] * h;
       }
-      wave_lds_fence();
-      double av = 0.0, a0 = 0.0, a1 = 0.0;
-#pragma unroll 4
-      for (int kk = 0; kk < QH2; ++kk) {
-        const double hv = h2w[kk], ha = h2w[QH2 + kk];
-        av += (double)wq[o.W3v + r0 + R * kk] * hv;
-        a0 += (double)wq[o.W3a + r0 + 2 * R * kk] * ha;
-        a1 += (double)wq[o.W3a + R + r0 + 2 * R * kk] * ha;
-      }
-      double q0, q1;
-      duel_combine(av + (double)wq[o.b3v + r0], a0 + (double)wq[o.b3a + r0], a1 + (double)wq[o.b3a + R + r0], q0, q1);
-      if (c.on) {                        // q0, q1 are the logits of atom `lane`
-        double p0, p1, lp;
-        c51_softmax(q0, R, lane, p0, lp);
-        const double e0 = c51_expect(p0, c.v_min, delta, lane);
-        c51_softmax(q1, R, lane, p1, lp);
-        q1 = c51_expect(p1, c.v_min, delta, lane);
-        q0 = e0;
-      }
-      const int action = q1 > q0 ? 1 : 0;
-      if (lane == 0) {
-        if (length == 0) ev.v0[slot] = action ? q1 : q0;
-        if (row < ev.trace_steps) ev.trace[(size_t)row * ev.n + env] = action;
-      }
-      row += 1;
-      const bool done = cartpole_step64(s, t, action, max_steps);
-      const double rew = done ? 0.0 : 1.0;
-      ret += rew;
-      disc_ret += disc * rew;
-      disc = disc * gamma;
-      length += 1;
-      wave_lds_fence();
-      if (done) break;
+      acc += (double)wq[ba];
+      acc2 += (double)wq[bb];
+      acc3 += (double)wq[bc];
+      h2w[ua] = acc > 0.0 ? acc : 0.0;
+      h2w[ub] = acc2 > 0.0 ? acc2 : 0.0;
+      if (lane + 128 < DUEL_U2) h2w[lane + 128] = acc3 > 0.0 ? acc3 : 0.0;
     }
-    if (lane == 0) { ev.ret[slot] = ret; ev.disc_ret[slot] = disc_ret; ev.len[slot] = length; }
-  }
-  value_eval_trace_tail(ev, env, row, lane);
+    wave_lds_fence();
+    double av = 0.0, a0 = 0.0, a1 = 0.0;
+#pragma unroll 4
+    for (int kk = 0; kk < QH2; ++kk) {
+      const double hv = h2w[kk], ha = h2w[QH2 + kk];
+      av += (double)wq[o.W3v + r0 + R * kk] * hv;
+      a0 += (double)wq[o.W3a + r0 + 2 * R * kk] * ha;
+      a1 += (double)wq[o.W3a + R + r0 + 2 * R * kk] * ha;
+    }
+    duel_combine(av + (double)wq[o.b3v + r0], a0 + (double)wq[o.b3a + r0], a1 + (double)wq[o.b3a + R + r0], q0, q1);
+    if (c.on) {                          // q0, q1 are the logits of atom `lane`
+      double p0, p1, lp;
+      c51_softmax(q0, R, lane, p0, lp);
+      const double e0 = c51_expect(p0, c.v_min, delta, lane);
+      c51_softmax(q1, R, lane, p1, lp);
+      q1 = c51_expect(p1, c.v_min, delta, lane);
+      q0 = e0;
+    }
+  });
 }
 
 }  // namespace crl
@@ -1381,71 +895,42 @@ static int qalloc(T** p, size_t n) {
   return 0;
 }
 
+// dynamic LDS of the collect and the evaluation launch of a categorical / a dueling handle with P parameters
 static size_t c51_collect_lds(int P) { return C51_COLLECT_LDS + (size_t)P * 4; }
 static size_t c51_eval_lds(int P) { return sizeof(C51EvalWaveLds) * DQN_EVAL_WAVES + (size_t)P * 4; }
-
-// the ten launches of a crl_dqn_c51_create handle: the sampling launch, fwd1, fwd2 and bwd1 are the scalar handles' kernels
-static void enqueue_c51_cycle(hipStream_t st, const DQNDev& d, int k) {
-  const int nets = d.nets, NA = 2 * d.c51.N, P = d.c51.P;
-  hipLaunchKernelGGL(dqn_c51_collect_kernel, dim3(1), dim3(128), c51_collect_lds(P), st, d);
-  if (d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
-  else hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((nets * QH2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_c51_fwd3_kernel, dim3((nets * NA * k + 255) / 256), dim3(256), 0, st, d);
-  const dim3 td_grid((k + C51_TD_WAVES - 1) / C51_TD_WAVES), td_block(64 * C51_TD_WAVES);
-  if (d.per.on) hipLaunchKernelGGL(dqn_c51_td_kernel<true>, td_grid, td_block, 0, st, d);
-  else hipLaunchKernelGGL(dqn_c51_td_kernel<false>, td_grid, td_block, 0, st, d);
-  hipLaunchKernelGGL(dqn_c51_bwd2_kernel, dim3((QH2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_c51_wgrad_kernel, dim3((P + 63) / 64), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(dqn_c51_adam_kernel, dim3(1), dim3(1024), 0, st, d);
-}
-
 static size_t duel_collect_lds(int P) { return DUEL_COLLECT_LDS + (size_t)P * 4; }
 static size_t duel_eval_lds(int P) { return sizeof(DuelEvalWaveLds) * DUEL_EVAL_WAVES + (size_t)P * 4; }
-
-// the ten launches of a crl_dqn_dueling_create handle: the sampling launch, fwd1 and the TD launch are the other handles' kernels
-static void enqueue_duel_cycle(hipStream_t st, const DQNDev& d, int k) {
-  const int nets = d.nets, R = d.duel.R, P = d.duel.P;
-  hipLaunchKernelGGL(dqn_duel_collect_kernel, dim3(1), dim3(128), duel_collect_lds(P), st, d);
-  if (d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
-  else hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_fwd2_kernel, dim3((nets * DUEL_U2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_fwd3_kernel, dim3((nets * R * k + 255) / 256), dim3(256), 0, st, d);
-  if (d.c51.on) {
-    const dim3 td_grid((k + C51_TD_WAVES - 1) / C51_TD_WAVES), td_block(64 * C51_TD_WAVES);
-    if (d.per.on) hipLaunchKernelGGL(dqn_c51_td_kernel<true>, td_grid, td_block, 0, st, d);
-    else hipLaunchKernelGGL(dqn_c51_td_kernel<false>, td_grid, td_block, 0, st, d);
-  } else if (d.per.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<true>, dim3(1), dim3(1024), 0, st, d);
-  else hipLaunchKernelGGL(dqn_tgt_td_kernel<false>, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_bwd2_kernel, dim3((DUEL_U2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_wgrad_kernel, dim3((P + 63) / 64), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(dqn_duel_adam_kernel, dim3(1), dim3(1024), 0, st, d);
+// The attribute belongs to the kernel, not to the handle, so callers set it to what the largest head needs: handles of different sizes live side by side.
+template <typename K>
+static bool set_dyn_lds(K* kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
+// The ten launches of a cycle, each slot named once with the kernel the handle's head puts there. The trunk's kernels (fwd1, fwd2, bwd1) are shared
+// where the arrays sit at the plain offsets; a categorical or a dueling handle always carries target options, so tgt.on holds for them.
+using DQNKernel = void (*)(DQNDev);
+// the sampling launch and the TD launch come as a uniform-replay and a PER instantiation
+static DQNKernel by_replay(const DQNDev& d, DQNKernel uniform, DQNKernel per) { return d.per.on ? per : uniform; }
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
-  if (d.duel.on) { enqueue_duel_cycle(st, d, k); return; }
-  if (d.c51.on) { enqueue_c51_cycle(st, d, k); return; }
-  hipLaunchKernelGGL(dqn_collect_kernel, dim3(1), dim3(128), 0, st, d);
-  const int nets = d.nets;
-  if (d.tgt.on && d.per.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<true>, dim3(1), dim3(1024), 0, st, d);
-  else if (d.tgt.on) hipLaunchKernelGGL(dqn_tgt_sample_kernel<false>, dim3(1), dim3(1024), 0, st, d);
-  else if (d.per.on) hipLaunchKernelGGL(dqn_per_sample_kernel, dim3(1), dim3(1024), 0, st, d);
-  else hipLaunchKernelGGL(dqn_sample_kernel, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd1_kernel, dim3((nets * QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd2_kernel, dim3((nets * QH2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_fwd3_kernel, dim3((nets * QA * k + 255) / 256), dim3(256), 0, st, d);
-  if (d.tgt.on && d.per.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<true>, dim3(1), dim3(1024), 0, st, d);
-  else if (d.tgt.on) hipLaunchKernelGGL(dqn_tgt_td_kernel<false>, dim3(1), dim3(1024), 0, st, d);
-  else if (d.per.on) hipLaunchKernelGGL(dqn_per_td_kernel, dim3(1), dim3(1024), 0, st, d);
-  else hipLaunchKernelGGL(dqn_td_kernel, dim3(1), dim3(1024), 0, st, d);
-  hipLaunchKernelGGL(dqn_bwd2_kernel, dim3((QH2 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_bwd1_kernel, dim3((QH1 * k + 255) / 256), dim3(256), 0, st, d);
-  hipLaunchKernelGGL(dqn_wgrad_kernel, dim3((QP + 63) / 64), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(dqn_adam_kernel, dim3(1), dim3(1024), 0, st, d);
+  const bool duel = d.duel.on, c51 = d.c51.on, tgt = d.tgt.on;
+  const int nets = d.nets, U2 = duel ? DUEL_U2 : QH2, P = duel ? d.duel.P : c51 ? d.c51.P : QP;
+  const int rows3 = duel ? d.duel.R : c51 ? 2 * d.c51.N : QA;   // threads per sample and pass of the fwd3 slot
+  const auto launch = [&](DQNKernel kernel, int threads, int block, size_t lds = 0) {   // ⌈threads / block⌉ blocks
+    hipLaunchKernelGGL(kernel, dim3((threads + block - 1) / block), dim3(block), lds, st, d);
+  };
+  launch(duel ? dqn_duel_collect_kernel : c51 ? dqn_c51_collect_kernel : dqn_collect_kernel, DQN_OBS_BLOCK, DQN_OBS_BLOCK,
+         duel ? duel_collect_lds(P) : c51 ? c51_collect_lds(P) : 0);
+  launch(tgt ? by_replay(d, dqn_tgt_sample_kernel<false>, dqn_tgt_sample_kernel<true>) : by_replay(d, dqn_sample_kernel, dqn_per_sample_kernel), 1024, 1024);
+  launch(dqn_fwd1_kernel, nets * QH1 * k, 256);
+  launch(duel ? dqn_duel_fwd2_kernel : dqn_fwd2_kernel, nets * U2 * k, 256);
+  launch(duel ? dqn_duel_fwd3_kernel : c51 ? dqn_c51_fwd3_kernel : dqn_fwd3_kernel, nets * rows3 * k, 256);
+  if (c51) launch(by_replay(d, dqn_c51_td_kernel<false>, dqn_c51_td_kernel<true>), 64 * k, 64 * C51_TD_WAVES);   // one wave per sample
+  else launch(tgt ? by_replay(d, dqn_td_kernel<true, false>, dqn_td_kernel<true, true>) : by_replay(d, dqn_td_kernel<false, false>, dqn_td_kernel<false, true>),
+              1024, 1024);
+  launch(duel ? dqn_duel_bwd2_kernel : c51 ? dqn_c51_bwd2_kernel : dqn_bwd2_kernel, U2 * k, 256);
+  launch(duel ? dqn_duel_bwd1_kernel : dqn_bwd1_kernel, QH1 * k, 256);
+  launch(duel ? dqn_duel_wgrad_kernel : c51 ? dqn_c51_wgrad_kernel : dqn_wgrad_kernel, P, 64);
+  launch(duel ? dqn_duel_adam_kernel : c51 ? dqn_c51_adam_kernel : dqn_adam_kernel, 1024, 1024);
 }
 
 // crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create and crl_dqn_dueling_create: one body; `per` is null for uniform replay,
@@ -1512,13 +997,9 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     const size_t N = (size_t)c51->n_atoms;
     c.on = 1; c.N = c51->n_atoms; c.P = (int32_t)NP; c.v_min = c51->v_min; c.v_max = c51->v_max;
     rc |= qalloc(&c.L, nets * 2 * N * k); rc |= qalloc(&c.dl, N * k); rc |= qalloc(&c.proj, N * k); rc |= qalloc(&c.sloss, k);
-    // the net in LDS passes the 64 KB a launch gets without asking at N >= 36; the CU has 160 KB. The attribute belongs to the kernel, not to the
-    // handle, so it is set to what the largest head needs: handles of different N live side by side.
+    // the net in LDS passes the 64 KB a launch gets without asking at N >= 36; the CU has 160 KB. Set for the largest head (set_dyn_lds).
     constexpr int PMAX = QoW3 + 85 * 2 * C51_MAX_ATOMS;
-    if (!rc && (hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_c51_collect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c51_collect_lds(PMAX)) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_c51_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c51_eval_lds(PMAX)) != hipSuccess)) {
+    if (!rc && !(set_dyn_lds(dqn_c51_collect_kernel, c51_collect_lds(PMAX)) && set_dyn_lds(dqn_c51_eval_kernel, c51_eval_lds(PMAX)))) {
       set_error("crl_dqn_c51_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
@@ -1527,10 +1008,7 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     d.duel.on = 1; d.duel.R = c51 ? c51->n_atoms : 1; d.duel.P = (int32_t)NP;
     // both kernels keep the whole net in LDS, past the 64 KB a launch gets without asking at every R; set for the largest head, as above
     constexpr int PMAX = duel_param_count(DUEL_MAX_R);
-    if (!rc && (hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_duel_collect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)duel_collect_lds(PMAX)) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(dqn_duel_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)duel_eval_lds(PMAX)) != hipSuccess)) {
+    if (!rc && !(set_dyn_lds(dqn_duel_collect_kernel, duel_collect_lds(PMAX)) && set_dyn_lds(dqn_duel_eval_kernel, duel_eval_lds(PMAX)))) {
       set_error("crl_dqn_dueling_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
@@ -1648,7 +1126,7 @@ int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double
   double* so = static_cast<double*>(h->stage);
   double *sv = so + N * QD, *sa = sv + N * R;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
+  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
                      (double*)nullptr, sv, sa);
   CRL_HIP_CHECK(hipGetLastError());
   if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, sv, N * R * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1674,9 +1152,9 @@ int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* prob
   double* so = static_cast<double*>(h->stage);
   double* sp = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n,
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n,
                                   (double*)nullptr, sp, (double*)nullptr, (double*)nullptr);
-  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
+  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1936,10 +1414,10 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   double* so = static_cast<double*>(h->stage);
   double* sq = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, sq,
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, sq,
                                   (double*)nullptr, (double*)nullptr, (double*)nullptr);
-  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(128), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
-  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(128), 0, h->stream, h->d.q, so, n, sq);
+  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
+  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->d.q, so, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));

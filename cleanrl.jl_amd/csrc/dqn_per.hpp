@@ -5,8 +5,8 @@
 // tree[1 .. 2C) with C = the smallest power of two >= buffer_size; leaf of ring slot s = tree[C + s]; every inner node is tree[2i] + tree[2i+1], one
 // add, left operand first — the tree is a pure function of its leaves, so any repair order gives the same bits.
 //
-// per_repair, per_draw and per_weights are called by EVERY thread of ONE block (at most 1024 threads): dqn_per_sample_kernel and dqn_per_td_kernel in
-// dqn.hip and the probe kernel run the same functions.
+// per_repair, per_draw, per_weights, per_block_max and per_batch_tail are called by EVERY thread of ONE block (at most 1024 threads): the sampling
+// launches, dqn_td_kernel<·, true> and the categorical handles' Adam launch in dqn.hip and the probe kernel run the same functions.
 #pragma once
 #include "common.hpp"
 
@@ -136,6 +136,34 @@ __device__ __forceinline__ void per_weights(const double* tree, int C, int n, in
   const double t = top_w;
   for (int j = tid; j < k; j += nth) w[j] = w[j] / t;
   __syncthreads();
+}
+
+// The priority write-back of an update, in three steps. Per sample (ONE thread, slot s = idx_b, ad = |δ_b| or the categorical loss_b): abs_td_b, the
+// new leaf of s (duplicates write identical values: the same slot has the same δ), and the thread's running maximum `mine` of the leaves it wrote.
+__device__ __forceinline__ void per_td_writeback(const PerDev& p, int b, int s, double ad, float& mine) {
+#pragma clang fp contract(off)
+  const float leaf = per_leaf(ad, p.eps, p.alpha);
+  p.abs_td[b] = ad;
+  p.tree[p.C + s] = (double)leaf;
+  mine = leaf > mine ? leaf : mine;
+}
+// Every thread's `mine` → one maximum per wave in lmax[tid / 64] (the caller's __shared__ float[16]: a block has at most 16 waves). The caller's
+// block barrier follows; a maximum is exact in any order.
+__device__ __forceinline__ void per_block_max(float mine, float* lmax) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const float u = __shfl_xor(mine, o, 64); mine = u > mine ? u : mine; }
+  if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = mine;
+}
+// Behind that barrier: max_leaf raised to the batch's largest new leaf, then the ancestors of the k written leaves repaired
+__device__ __forceinline__ void per_batch_tail(const PerDev& p, const int32_t* idx, int k, const float* lmax) {
+#pragma clang fp contract(off)
+  if (threadIdx.x == 0) {
+    float top = p.ctl->max_leaf;
+    for (int i = 0; i < (int)(blockDim.x + 63) / 64; ++i) top = lmax[i] > top ? lmax[i] : top;
+    p.ctl->max_leaf = top;
+  }
+  per_repair(p.tree, p.C, k, [=](int i) { return (int)idx[i]; });
 }
 
 }  // namespace crl

@@ -596,7 +596,7 @@ int32_t crl_dqn_eval_envs_per_block(void);
 /* -----------------------------------------------------------------------------------------------------
  * Prioritized experience replay for DQN (Schaul et al. 2016, proportional variant) — no reference counterpart: dqn.jl replays uniformly. A handle
  * made by crl_dqn_per_create runs the same ten-launch cycle with two kernels of its own in the places of the uniform draw and of the TD kernel
- * (csrc/dqn_per.hpp, csrc/dqn.hip: dqn_per_sample_kernel, dqn_per_td_kernel); collect, the forwards, the pullbacks, the weight gradients, Adam and the
+ * (csrc/dqn_per.hpp, csrc/dqn.hip: dqn_per_sample_kernel, dqn_td_kernel<false, true>); collect, the forwards, the pullbacks, the weight gradients, Adam and the
  * target copy are shared. crl_dqn_run, crl_dqn_status_read, crl_dqn_read_params / crl_dqn_write_params / crl_dqn_init_params, crl_dqn_q_values,
  * crl_dqn_evaluate and crl_dqn_destroy work on it unchanged; a crl_dqn_create handle is what it was, bit for bit, and the three per_* calls below fail
  * on it with a message. Everything is on the device; no call in between reads anything back.
@@ -644,7 +644,7 @@ int32_t crl_dqn_per_probe(crl_dqn* h, const float* leaves, int32_t n, uint64_t g
  * dqn.jl:99-100 forms a 1-step max over target_net. Both change how the TD target is formed and nothing else: the parameter layout, crl_dqn_q_values,
  * crl_dqn_evaluate and the collect kernel are what they were, and they compose with prioritized replay, whose priority is |δ| of the new target. A
  * handle made by crl_dqn_create_with runs the same ten-launch cycle with two kernels of its own in the places of the sampling launch and of the TD
- * launch (csrc/dqn_target.hpp, csrc/dqn.hip: dqn_tgt_sample_kernel, dqn_tgt_td_kernel); with double_q the three forward launches carry a third pass.
+ * launch (csrc/dqn_target.hpp, csrc/dqn.hip: dqn_tgt_sample_kernel, dqn_td_kernel<true, PER>); with double_q the three forward launches carry a third pass.
  * crl_dqn_create and crl_dqn_per_create handles keep every bit of their behaviour; the two calls below fail on them with a message naming
  * crl_dqn_create_with. With per != NULL the handle is also a PER handle: the crl_dqn_per_* calls work on it.
  *

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a held-out DQN / A2C evaluation costs, on one box (→ profiles/value_eval_cost.json):
 
-    (a) crl_dqn_evaluate and crl_a2c_evaluate at 256 x 1 and at 4096 x 1 episodes (csrc/dqn.hip dqn_eval_kernel, csrc/a2c.hip a2c_eval_kernel: one
+    (a) crl_dqn_evaluate and crl_a2c_evaluate at 256 x 1 and at 4096 x 1 episodes (csrc/dqn.hip dqn_eval_kernel around csrc/dqn_loops.hpp dqn_eval_episodes, csrc/a2c.hip a2c_eval_kernel: one
         launch, the network on the chip), for two policies, because the policy decides how many steps the launch runs: a fresh glorot / orthogonal
         net, whose episodes are short, and the hand-made balancer of tests/value_eval_ref.py, whose episodes all run into the step limit
         (201 steps for DQN's max_steps = 200, 501 for A2C's 500); A2C also sampled

@@ -1,6 +1,6 @@
 """The DQN update kernels (csrc/dqn.hip) and the minibatch draw (csrc/replay_sample.hpp) at the edges of what crl_dqn_create accepts, under the bar of
 tests/test_gpu_dqn.py — BIT-EXACT against oracle/dqn_oracle.c: batch sizes 1 and 1024 (the `o / (QH·k)` decompositions of dqn_fwd* / dqn_bwd*, the
-block of dqn_td_kernel), remainders 29, 1 and 1 + two rounds of dqn_wgrad_kernel's 30-wide unrolled sample loops, draws of the whole ring and of all
+block of dqn_td_kernel<false, false>), remainders 29, 1 and 1 + two rounds of dqn_wgrad_kernel's 30-wide unrolled sample loops, draws of the whole ring and of all
 but one slot that need several rounds of 1024 candidates, a ring of 65536 slots (the high words of the draw's bitmap), gamma 0, a greedy-only run.
 Then the per-call record buffers, filled past their ends: 4096 loss records and 8192 episode records."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""crl_dqn_evaluate (csrc/dqn.hip, dqn_eval_kernel) against its definition in include/cleanrl_hip.h: the device's trace is replayed through the
+"""crl_dqn_evaluate (csrc/dqn.hip, dqn_eval_kernel; its episode loop is dqn_eval_episodes of csrc/dqn_loops.hpp) against its definition in include/cleanrl_hip.h: the device's trace is replayed through the
 oracle's CartPole and every output is held bit for bit — actions against the argmax of h.q_values, sums against the replay, q0 against h.q_values,
 the report against the formulas on the returned arrays (tests/value_eval_gpu.py). The Q-net has no transcendental in it and h.q_values is the
 oracle's dqn_forward bit for bit, so the reference's own rollout (tests/value_eval_ref.py) must give the identical trace too."""

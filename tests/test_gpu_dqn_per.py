@@ -1,4 +1,4 @@
-"""Prioritized replay for DQN on the GPU (crl_dqn_per_*; csrc/dqn_per.hpp, dqn_per_sample_kernel and dqn_per_td_kernel in csrc/dqn.hip) against the
+"""Prioritized replay for DQN on the GPU (crl_dqn_per_*; csrc/dqn_per.hpp, dqn_per_sample_kernel and dqn_td_kernel<false, true> in csrc/dqn.hip) against the
 numpy restatement tests/dqn_per_ref.py, under the bars of tests/dqn_per_bar.py (profiles/dqn_per_bar.json).
 
 What is bit-equal and what is under a bar. Everything that does not pass through a pow is the restatement's bit for bit: the tree, idx, the Float32

@@ -1,5 +1,5 @@
-"""n-step returns and double Q-learning for DQN on the GPU (crl_dqn_create_with; csrc/dqn_target.hpp, dqn_tgt_sample_kernel and dqn_tgt_td_kernel in
-csrc/dqn.hip) against the numpy restatement tests/dqn_target_ref.py, on the case table of tests/dqn_target_bar.py.
+"""n-step returns and double Q-learning for DQN on the GPU (crl_dqn_create_with; csrc/dqn_target.hpp, dqn_tgt_sample_kernel and dqn_td_kernel<true, PER>
+in csrc/dqn.hip) against the numpy restatement tests/dqn_target_ref.py, on the case table of tests/dqn_target_bar.py.
 
 What is bit-equal and what is under a bar. A uniform case holds no transcendental anywhere: the episodes, the status with last_loss, every loss
 record, both parameter arrays and target_read's arrays are the restatement's bit for bit. A PER case has one rounding freedom, PER's pow, so it sits
