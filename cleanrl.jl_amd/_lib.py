@@ -100,7 +100,8 @@ EXPORTS = [
     "crl_dqn_q_values", "crl_dqn_evaluate", "crl_dqn_eval_envs_per_block", "crl_dqn_per_create", "crl_dqn_per_status_read", "crl_dqn_per_read",
     "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe",
     "crl_dqn_c51_create", "crl_dqn_param_count", "crl_dqn_c51_make_nn", "crl_dqn_c51_probs", "crl_dqn_c51_read", "crl_dqn_c51_project_probe",
-    "crl_dqn_dueling_create", "crl_dqn_dueling_make_nn", "crl_dqn_dueling_streams", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_dueling_create", "crl_dqn_dueling_make_nn", "crl_dqn_dueling_streams",
+    "crl_dqn_noisy_create", "crl_dqn_noisy_make_nn", "crl_dqn_noisy_weights", "crl_dqn_noisy_noise_count", "crl_dqn_noisy_noise", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -158,6 +159,11 @@ class CrlDQNC51Options(C.Structure):
 def dqn_c51_param_count(n_atoms):
     """10764 + 85·2N: the trunk W1 b1 W2 b2 and the head W3(2N, 84) b3(2N)"""
     return 10764 + 85 * 2 * int(n_atoms)
+
+
+class CrlDQNNoisyOptions(C.Structure):
+    """crl_dqn_noisy_options: noisy linear layers (8 bytes): sigma = sigma0 / sqrt(in) at init, sigma0 in 0..10."""
+    _fields_ = [("sigma0", C.c_double)]
 
 
 
@@ -341,6 +347,12 @@ def load():
     L.crl_dqn_dueling_create.argtypes = L.crl_dqn_c51_create.argtypes
     L.crl_dqn_dueling_make_nn.argtypes = [C.c_uint64, C.c_int32, fp, C.c_size_t]
     L.crl_dqn_dueling_streams.argtypes = [vp, dp, C.c_int32, dp, dp]
+    L.crl_dqn_noisy_create.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNNoisyOptions), C.c_int32, C.POINTER(CrlDQNC51Options),
+                                       C.POINTER(CrlDQNPEROptions), C.POINTER(CrlDQNTargetOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_noisy_make_nn.argtypes = [C.c_uint64, C.c_double, C.c_int32, C.c_int32, fp, C.c_size_t]
+    L.crl_dqn_noisy_weights.argtypes = [vp, C.c_int32, fp, C.c_size_t]
+    L.crl_dqn_noisy_noise_count.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.crl_dqn_noisy_noise.argtypes = [vp, C.c_uint64, C.c_int32, fp, C.c_size_t]
     L.crl_a2c_evaluate.argtypes = L.crl_dqn_evaluate.argtypes
     L.crl_a2c_eval_envs_per_block.argtypes = []
     L.crl_ddpg_param_count.argtypes = [C.c_int32, C.c_int32, i64p, i64p]
@@ -996,6 +1008,14 @@ def dqn_dueling_make_nn_host(seed=0, n_atoms=None):
     return out
 
 
+def dqn_noisy_make_nn_host(seed=0, sigma0=0.5, dueling=False, n_atoms=None):
+    """crl_dqn_noisy_make_nn: Fortunato's factorised init, mu (P) then sigma (P) of the twin with these options."""
+    P = dqn_dueling_param_count(n_atoms) if dueling else (dqn_c51_param_count(n_atoms) if n_atoms else DQN_PARAM_COUNT)
+    out = np.zeros(2 * P, np.float32)
+    check(load().crl_dqn_noisy_make_nn(seed, float(sigma0), int(bool(dueling)), int(n_atoms) if n_atoms else 0, _ptr(out, C.c_float), out.size))
+    return out
+
+
 class DQNHandle:
     """Owns one crl_dqn* (include/cleanrl_hip.h, DQN block). `per` (a CrlDQNPEROptions) makes it a prioritized-replay handle (crl_dqn_per_create):
     every method below works on it unchanged, and per_status / per_read / per_probe, which are errors on a uniform handle, become available.
@@ -1003,17 +1023,24 @@ class DQNHandle:
     nstep_probe, which are errors on the other handles. `c51` (a CrlDQNC51Options) makes it a crl_dqn_c51_create handle, with either replay and any
     target options: the head is categorical, param_count is its own, q_values are expected values, and c51_probs / c51_read / c51_project_probe
     become available. `dueling=True` makes it a crl_dqn_dueling_create handle, with either head, either replay and any target options: layers 2 and 3
-    are a value and an advantage stream (ten arrays, param_count is its own), and dueling_streams becomes available."""
+    are a value and an advantage stream (ten arrays, param_count is its own), and dueling_streams becomes available. `noisy` (a CrlDQNNoisyOptions)
+    makes it a crl_dqn_noisy_create handle on top of any of the above: its parameters are mu then sigma (param_count is twice the twin's), q_values /
+    evaluate / c51_probs / dueling_streams run with the noise off, and noisy_weights / noisy_noise become available."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None, dueling=False):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None, dueling=False, noisy=None):
         self._L = load()
         self.cfg = cfg
         self.per = per
         self.target = target
         self.c51 = c51
         self.dueling = bool(dueling)
+        self.noisy = noisy
         self._h = C.c_void_p()
-        if self.dueling:
+        if noisy is not None:
+            check(self._L.crl_dqn_noisy_create(C.byref(cfg), C.byref(noisy), int(self.dueling), None if c51 is None else C.byref(c51),
+                                               None if per is None else C.byref(per), None if target is None else C.byref(target), device,
+                                               C.byref(self._h)))
+        elif self.dueling:
             check(self._L.crl_dqn_dueling_create(C.byref(cfg), None if c51 is None else C.byref(c51), None if per is None else C.byref(per),
                                                  None if target is None else C.byref(target), device, C.byref(self._h)))
         elif c51 is not None:
@@ -1051,7 +1078,7 @@ class DQNHandle:
         return int(n.value)
 
     def read_params(self):
-        n = DQN_PARAM_COUNT if self.c51 is None and not self.dueling else self.param_count()
+        n = DQN_PARAM_COUNT if self.c51 is None and not self.dueling and self.noisy is None else self.param_count()
         q = np.zeros(n, np.float32); t = np.zeros(n, np.float32)
         check(self._L.crl_dqn_read_params(self._h, _ptr(q, C.c_float), _ptr(t, C.c_float), q.size))
         return q, t
@@ -1121,6 +1148,20 @@ class DQNHandle:
                    astar=np.zeros(k, np.int32), td=np.zeros(k, np.float64))
         check(self._L.crl_dqn_target_read(self._h, _ptr(out["last"], C.c_int32), _ptr(out["m"], C.c_int32), _ptr(out["nret"], C.c_double),
                                           _ptr(out["ndisc"], C.c_double), _ptr(out["astar"], C.c_int32), _ptr(out["td"], C.c_double)))
+        return out
+
+    def noisy_weights(self, net=0):
+        """crl_dqn_noisy_weights: the effective image mu + sigma·eps in use, net 0 = q_net, 1 = target_net → float32 [P]"""
+        out = np.zeros(self.param_count() // 2 if self.noisy is not None else self.param_count(), np.float32)
+        check(self._L.crl_dqn_noisy_weights(self._h, int(net), _ptr(out, C.c_float), out.size))
+        return out
+
+    def noisy_noise(self, gen, net=0):
+        """crl_dqn_noisy_noise: the xi table of generation `gen` of either net (stateless) → float32 [412 + rows3, or 700 + 3R]"""
+        n = C.c_size_t()
+        check(self._L.crl_dqn_noisy_noise_count(self._h, C.byref(n)))
+        out = np.zeros(int(n.value), np.float32)
+        check(self._L.crl_dqn_noisy_noise(self._h, int(gen), int(net), _ptr(out, C.c_float), out.size))
         return out
 
     def dueling_streams(self, obs):

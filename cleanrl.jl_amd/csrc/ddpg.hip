@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "normal_bm.hpp"
 #include "optim.hpp"
 #include "ppo_ctx.hpp"
 #include "replay_sample.hpp"
@@ -125,10 +126,7 @@ __device__ __forceinline__ void pendulum_reset64(double* s, uint64_t seed, uint6
 // randn() for component `comp` of the draw (gstep, stream)
 __device__ __forceinline__ double ddpg_normal(uint64_t seed, uint32_t comp, uint64_t gstep, uint32_t stream) {
 #pragma clang fp contract(off)
-  const u32x4 o = philox_env(seed, comp, gstep, stream);
-  const double u1 = u53(o);
-  const double u2 = (double)((((uint64_t)o.z << 32) | o.w) >> 11) * 0x1.0p-53;
-  return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+  return box_muller(philox_env(seed, comp, gstep, stream));   // normal_bm.hpp
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -780,6 +780,39 @@ __global__ void __launch_bounds__(1024) dqn_duel_adam_kernel(DQNDev a) {
   dqn_adam_step(a, a.duel.P, DUEL_ARRAYS, [&](int p) { return duel_array_of(off, p); });
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Noisy linear layers (crl_dqn_noisy_create; dqn_noisy.hpp). a.q / a.t are the effective images of the current generation, so the first nine launches
+// of the cycle, the collect kernels among them, are the twin's with nothing changed. The Adam slot is dqn_noisy_adam_kernel, one kernel for all heads:
+// dqn_noisy_adam_step with the head's array table and layer table. Evaluation, crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams get the
+// mu half (noisy.pq, the twin's layout) as their image: the noise is off there. The images of the next generation are formed by an eleventh launch,
+// dqn_noisy_materialise_kernel, on every CU: in the Adam launch's one block they measured slower, so a noisy cycle is eleven launches.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ NoisyTable dqn_noisy_table(const DQNDev& a) {
+  return noisy_table(a.duel.on != 0, a.duel.R, a.c51.on ? 2 * a.c51.N : QA);
+}
+__global__ void __launch_bounds__(1024) dqn_noisy_adam_kernel(DQNDev a) {
+  if (!a.ctl->train_pending) return;
+  __shared__ float xs[(CRL_NOISY_SPLIT_TAIL ? 1 : 2) * NOISY_MAX_XI];   // generation u's online table; the one-block experiment build adds the next generation's two
+  if (a.c51.on) dqn_c51_batch_tail(a);   // as dqn_c51_adam_kernel / dqn_duel_adam_kernel: what needs the whole batch
+  const NoisyTable tab = dqn_noisy_table(a);
+  if (a.duel.on) {
+    const DuelOff off = duel_off(a.duel.R);
+    dqn_noisy_adam_step(a, DUEL_ARRAYS, [&](int p) { return duel_array_of(off, p); }, tab, xs);
+  } else {
+    const int ob3 = tab.l[2].ob;
+    dqn_noisy_adam_step(a, 6, [=](int p) { return dqn_array_of(p, ob3); }, tab, xs);
+  }
+}
+// create, crl_dqn_write_params and crl_dqn_init_params: both images at the current generation (n_updates) from mu and sigma
+__global__ void __launch_bounds__(256) dqn_noisy_materialise_kernel(DQNDev a) {
+  __shared__ float xs[2 * NOISY_MAX_XI];
+  dqn_noisy_materialise(a, dqn_noisy_table(a), (uint64_t)a.ctl->n_updates, xs);
+}
+// crl_dqn_noisy_noise: the xi table of any generation and either net, by the function the Adam launch builds its tables with; one block
+__global__ void __launch_bounds__(256) dqn_noisy_noise_kernel(DQNDev a, uint64_t gen, uint32_t stream, float* out) {
+  noisy_build_xi(out, dqn_noisy_table(a).n_xi, a.cfg.seed, gen, stream);
+}
+
 // crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams on a dueling handle: the block's forward, then whichever outputs are asked for.
 // out_q (2, n); out_p (N, 2, n); out_v (R, n); out_a (R, 2, n), i fastest
 __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_q_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, const double* __restrict__ obs, int n,
@@ -880,6 +913,12 @@ struct crl_dqn {
   size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, 10764 + 85·2N on a C51 handle, 20928 + 255·R on a dueling one
   void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's scratch
   bool duel = false;                                                // made by crl_dqn_dueling_create: P = 20928 + 255·R, R = 1 or n_atoms
+  bool noisy = false;                                               // made by crl_dqn_noisy_create: P is still the twin's count = the images' length
+  size_t n_params = (size_t)crl::QP;                                // what crl_dqn_param_count reports and write / read take: P, or 2P (mu, sigma) on a noisy handle
+  double sigma0 = 0.5;                                              // crl_dqn_init_params on a noisy handle
+  float* xi_scratch = nullptr;                                      // crl_dqn_noisy_noise's table, NOISY_MAX_XI floats
+  // the image the noise-free calls read (crl_dqn_q_values, crl_dqn_c51_probs, crl_dqn_dueling_streams, crl_dqn_evaluate): q_net, or its mu half
+  const float* greedy_image() const { return noisy ? d.noisy.pq : d.q; }
 };
 
 using namespace crl;
@@ -906,7 +945,7 @@ static bool set_dyn_lds(K* kernel, size_t bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-// The ten launches of a cycle, each slot named once with the kernel the handle's head puts there. The trunk's kernels (fwd1, fwd2, bwd1) are shared
+// The ten launches of a cycle (eleven on a noisy handle), each slot named once with the kernel the handle's head puts there. The trunk's kernels (fwd1, fwd2, bwd1) are shared
 // where the arrays sit at the plain offsets; a categorical or a dueling handle always carries target options, so tgt.on holds for them.
 using DQNKernel = void (*)(DQNDev);
 // the sampling launch and the TD launch come as a uniform-replay and a PER instantiation
@@ -930,13 +969,16 @@ static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   launch(duel ? dqn_duel_bwd2_kernel : c51 ? dqn_c51_bwd2_kernel : dqn_bwd2_kernel, U2 * k, 256);
   launch(duel ? dqn_duel_bwd1_kernel : dqn_bwd1_kernel, QH1 * k, 256);
   launch(duel ? dqn_duel_wgrad_kernel : c51 ? dqn_c51_wgrad_kernel : dqn_wgrad_kernel, P, 64);
-  launch(duel ? dqn_duel_adam_kernel : c51 ? dqn_c51_adam_kernel : dqn_adam_kernel, 1024, 1024);
+  launch(d.noisy.on ? dqn_noisy_adam_kernel : duel ? dqn_duel_adam_kernel : c51 ? dqn_c51_adam_kernel : dqn_adam_kernel, 1024, 1024);
+  // a noisy handle's eleventh launch: both images at generation n_updates on every CU (idempotent, so a cycle without an update rewrites the same
+  // bits); in dqn_noisy_adam_kernel's one block the same work measured 12 us (plain net) to 53 us (dueling + C51) slower per cycle: DESIGN.md §3l
+  if (CRL_NOISY_SPLIT_TAIL && d.noisy.on) launch(dqn_noisy_materialise_kernel, P, 256);
 }
 
-// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create and crl_dqn_dueling_create: one body; `per` is null for uniform replay,
+// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create, crl_dqn_dueling_create and crl_dqn_noisy_create: one body; `per` is null for uniform replay,
 // `tgt` for the 1-step max target of dqn.jl, `c51` for the scalar head; `duel` splits layers 2 and 3 into a value and an advantage stream
 static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out,
-                          const crl_dqn_c51_options* c51 = nullptr, bool duel = false) {
+                          const crl_dqn_c51_options* c51 = nullptr, bool duel = false, const crl_dqn_noisy_options* noisy = nullptr) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -961,9 +1003,10 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   int rc = 0;
   const size_t NP = duel ? (size_t)duel_param_count(c51 ? c51->n_atoms : 1) : c51 ? (size_t)QoW3 + 85 * 2 * (size_t)c51->n_atoms : (size_t)QP;
   const size_t U2 = duel ? DUEL_U2 : QH2, NARR = duel ? DUEL_ARRAYS : 6;   // hidden units of layer 2 per sample; arrays Adam keeps a β-power pair for
-  h->P = NP;
-  rc |= qalloc(&d.q, NP); rc |= qalloc(&d.t, NP); rc |= qalloc(&d.grads, NP); rc |= qalloc(&d.m, NP); rc |= qalloc(&d.v, NP);
-  rc |= qalloc(&d.betap, 2 * NARR); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
+  const size_t NZ = noisy ? 2 : 1;   // a noisy handle keeps Adam state for mu and sigma: 2P entries, twice the arrays
+  h->P = NP; h->n_params = NZ * NP;
+  rc |= qalloc(&d.q, NP); rc |= qalloc(&d.t, NP); rc |= qalloc(&d.grads, NP); rc |= qalloc(&d.m, NZ * NP); rc |= qalloc(&d.v, NZ * NP);
+  rc |= qalloc(&d.betap, 2 * NZ * NARR); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
   rc |= qalloc(&d.rb_state, cap * QD); rc |= qalloc(&d.rb_next, cap * QD); rc |= qalloc(&d.rb_reward, cap);
   rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
   const size_t nets = tgt && tgt->double_q ? 3 : 2;
@@ -1012,10 +1055,15 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
       set_error("crl_dqn_dueling_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
+  if (noisy) {
+    h->noisy = true; h->sigma0 = noisy->sigma0;
+    d.noisy.on = 1; d.noisy.P = (int32_t)NP;
+    rc |= qalloc(&d.noisy.pq, 2 * NP); rc |= qalloc(&d.noisy.pt, 2 * NP); rc |= qalloc(&h->xi_scratch, (size_t)NOISY_MAX_XI);
+  }
   if (rc) { crl_dqn_destroy(h); return 1; }
-  double bp[2 * DUEL_ARRAYS];
-  for (size_t i = 0; i < NARR; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
-  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, 2 * NARR * sizeof(double), hipMemcpyHostToDevice));
+  double bp[2 * 2 * DUEL_ARRAYS];
+  for (size_t i = 0; i < NZ * NARR; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
+  CRL_HIP_CHECK(hipMemcpy(d.betap, bp, 2 * NZ * NARR * sizeof(double), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(dqn_init_kernel, dim3(1), dim3(1), 0, h->stream, d);
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   *out = h;
@@ -1033,6 +1081,36 @@ static int per_options_check(const char* who, const crl_dqn_per_options* per) {
   if (!(per->beta_end >= 0.0 && per->beta_end <= 1.0)) { set_error(w + ": beta_end must be in 0..1"); return 1; }
   if (!(per->beta_duration > 0.0) || !(per->beta_duration < 1e300)) { set_error(w + ": beta_duration must be > 0 and finite"); return 1; }
   if (!(per->eps >= 1e-6 && per->eps <= 1.0)) { set_error(w + ": eps must be in 1e-6..1"); return 1; }
+  return 0;
+}
+
+#define DQN_NOISY_GUARD(h, name)                                                                                         \
+  DQN_GUARD(h);                                                                                                          \
+  if (!(h)->noisy) { set_error(name ": the handle's layers are not noisy; crl_dqn_noisy_create makes a NoisyNet handle"); return 1; }
+
+// both images of a noisy handle at its current generation, from the mu and sigma it holds
+static int noisy_materialise(crl_dqn* h) {
+  hipLaunchKernelGGL(dqn_noisy_materialise_kernel, dim3((unsigned)((h->P + 255) / 256)), dim3(256), 0, h->stream, h->d);
+  CRL_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// the categorical head's options and the target options, checked once for every creator that takes them; `who` names the creator in the message
+static int c51_options_check(const char* who, const crl_dqn_c51_options* c51) {
+  const std::string w(who);
+  if (c51->n_atoms < 2 || c51->n_atoms > C51_MAX_ATOMS) { set_error(w + ": n_atoms must be in 2..64"); return 1; }
+  if (!(c51->v_min > -1e300 && c51->v_min < 1e300)) { set_error(w + ": v_min must be finite"); return 1; }
+  if (!(c51->v_max > -1e300 && c51->v_max < 1e300)) { set_error(w + ": v_max must be finite"); return 1; }
+  if (!(c51->v_min < c51->v_max)) { set_error(w + ": v_min must be < v_max"); return 1; }
+  return 0;
+}
+// t = *tgt, or {1, 0} (dqn.jl's 1-step max) for NULL
+static int target_options_check(const char* who, const crl_dqn_target_options* tgt, crl_dqn_target_options& t) {
+  const std::string w(who);
+  t = {1, 0};
+  if (tgt) t = *tgt;
+  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error(w + ": n_step must be in 1..16"); return 1; }
+  if (t.double_q != 0 && t.double_q != 1) { set_error(w + ": double_q must be 0 or 1"); return 1; }
   return 0;
 }
 
@@ -1063,10 +1141,8 @@ int32_t crl_dqn_create_with(const crl_dqn_config* cfg, const crl_dqn_per_options
   if (!cfg || !out) { set_error("crl_dqn_create_with: null argument (cfg and out are required)"); return 1; }
   *out = nullptr;
   if (per && per_options_check("crl_dqn_create_with", per)) return 1;
-  crl_dqn_target_options t = {1, 0};
-  if (tgt) t = *tgt;
-  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_create_with: n_step must be in 1..16"); return 1; }
-  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_create_with: double_q must be 0 or 1"); return 1; }
+  crl_dqn_target_options t;
+  if (target_options_check("crl_dqn_create_with", tgt, t)) return 1;
   return dqn_create(cfg, per, &t, device, out);
 }
 
@@ -1074,15 +1150,10 @@ int32_t crl_dqn_c51_create(const crl_dqn_config* cfg, const crl_dqn_c51_options*
                            int32_t device, crl_dqn** out) {
   if (!cfg || !c51 || !out) { set_error("crl_dqn_c51_create: null argument (cfg, c51 and out are required)"); return 1; }
   *out = nullptr;
-  if (c51->n_atoms < 2 || c51->n_atoms > C51_MAX_ATOMS) { set_error("crl_dqn_c51_create: n_atoms must be in 2..64"); return 1; }
-  if (!(c51->v_min > -1e300 && c51->v_min < 1e300)) { set_error("crl_dqn_c51_create: v_min must be finite"); return 1; }
-  if (!(c51->v_max > -1e300 && c51->v_max < 1e300)) { set_error("crl_dqn_c51_create: v_max must be finite"); return 1; }
-  if (!(c51->v_min < c51->v_max)) { set_error("crl_dqn_c51_create: v_min must be < v_max"); return 1; }
+  if (c51_options_check("crl_dqn_c51_create", c51)) return 1;
   if (per && per_options_check("crl_dqn_c51_create", per)) return 1;
-  crl_dqn_target_options t = {1, 0};
-  if (tgt) t = *tgt;
-  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_c51_create: n_step must be in 1..16"); return 1; }
-  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_c51_create: double_q must be 0 or 1"); return 1; }
+  crl_dqn_target_options t;
+  if (target_options_check("crl_dqn_c51_create", tgt, t)) return 1;
   return dqn_create(cfg, per, &t, device, out, c51);
 }
 
@@ -1090,18 +1161,57 @@ int32_t crl_dqn_dueling_create(const crl_dqn_config* cfg, const crl_dqn_c51_opti
                                int32_t device, crl_dqn** out) {
   if (!cfg || !out) { set_error("crl_dqn_dueling_create: null argument (cfg and out are required)"); return 1; }
   *out = nullptr;
-  if (c51) {
-    if (c51->n_atoms < 2 || c51->n_atoms > C51_MAX_ATOMS) { set_error("crl_dqn_dueling_create: n_atoms must be in 2..64"); return 1; }
-    if (!(c51->v_min > -1e300 && c51->v_min < 1e300)) { set_error("crl_dqn_dueling_create: v_min must be finite"); return 1; }
-    if (!(c51->v_max > -1e300 && c51->v_max < 1e300)) { set_error("crl_dqn_dueling_create: v_max must be finite"); return 1; }
-    if (!(c51->v_min < c51->v_max)) { set_error("crl_dqn_dueling_create: v_min must be < v_max"); return 1; }
-  }
+  if (c51 && c51_options_check("crl_dqn_dueling_create", c51)) return 1;
   if (per && per_options_check("crl_dqn_dueling_create", per)) return 1;
-  crl_dqn_target_options t = {1, 0};
-  if (tgt) t = *tgt;
-  if (t.n_step < 1 || t.n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_dueling_create: n_step must be in 1..16"); return 1; }
-  if (t.double_q != 0 && t.double_q != 1) { set_error("crl_dqn_dueling_create: double_q must be 0 or 1"); return 1; }
+  crl_dqn_target_options t;
+  if (target_options_check("crl_dqn_dueling_create", tgt, t)) return 1;
   return dqn_create(cfg, per, &t, device, out, c51, /*duel=*/true);
+}
+
+int32_t crl_dqn_noisy_create(const crl_dqn_config* cfg, const crl_dqn_noisy_options* noisy, int32_t dueling, const crl_dqn_c51_options* c51,
+                             const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out) {
+  if (!cfg || !noisy || !out) { set_error("crl_dqn_noisy_create: null argument (cfg, noisy and out are required)"); return 1; }
+  *out = nullptr;
+  if (!(noisy->sigma0 >= 0.0 && noisy->sigma0 <= 10.0)) { set_error("crl_dqn_noisy_create: sigma0 must be in 0..10"); return 1; }
+  if (dueling != 0 && dueling != 1) { set_error("crl_dqn_noisy_create: dueling must be 0 or 1"); return 1; }
+  if (c51 && c51_options_check("crl_dqn_noisy_create", c51)) return 1;
+  if (per && per_options_check("crl_dqn_noisy_create", per)) return 1;
+  crl_dqn_target_options t;
+  if (target_options_check("crl_dqn_noisy_create", tgt, t)) return 1;
+  // the twin's kind: a categorical or a dueling handle always carries target options; the plain one only when they were given
+  if (dqn_create(cfg, per, (tgt || c51 || dueling) ? &t : nullptr, device, out, c51, dueling != 0, noisy)) return 1;
+  if (noisy_materialise(*out) || hipStreamSynchronize((*out)->stream) != hipSuccess) {
+    set_error("crl_dqn_noisy_create: the materialise launch failed"); crl_dqn_destroy(*out); *out = nullptr; return 1;
+  }
+  return 0;
+}
+
+int32_t crl_dqn_noisy_weights(crl_dqn* h, int32_t net, float* out, size_t n) {
+  DQN_NOISY_GUARD(h, "crl_dqn_noisy_weights");
+  if (net != 0 && net != 1) { set_error("crl_dqn_noisy_weights: net must be 0 (q_net) or 1 (target_net)"); return 1; }
+  if (!out || n != h->P) { set_error("crl_dqn_noisy_weights: expected " + std::to_string(h->P) + " floats"); return 1; }
+  CRL_HIP_CHECK(hipMemcpyAsync(out, net ? h->d.t : h->d.q, n * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_noisy_noise_count(crl_dqn* h, size_t* n) {
+  DQN_NOISY_GUARD(h, "crl_dqn_noisy_noise_count");
+  if (!n) { set_error("crl_dqn_noisy_noise_count: null argument"); return 1; }
+  *n = (size_t)noisy_table(h->duel, h->d.duel.R, h->c51 ? 2 * h->d.c51.N : QA).n_xi;
+  return 0;
+}
+
+int32_t crl_dqn_noisy_noise(crl_dqn* h, uint64_t gen, int32_t net, float* xi, size_t n) {
+  DQN_NOISY_GUARD(h, "crl_dqn_noisy_noise");
+  if (net != 0 && net != 1) { set_error("crl_dqn_noisy_noise: net must be 0 (q_net) or 1 (target_net)"); return 1; }
+  const size_t want = (size_t)noisy_table(h->duel, h->d.duel.R, h->c51 ? 2 * h->d.c51.N : QA).n_xi;
+  if (!xi || n != want) { set_error("crl_dqn_noisy_noise: expected " + std::to_string(want) + " floats"); return 1; }
+  hipLaunchKernelGGL(dqn_noisy_noise_kernel, dim3(1), dim3(256), 0, h->stream, h->d, gen, net ? S_NOISY_T : S_NOISY_Q, h->xi_scratch);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(xi, h->xi_scratch, n * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // the stage buffer of the forward-only calls, grown on demand
@@ -1126,7 +1236,7 @@ int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double
   double* so = static_cast<double*>(h->stage);
   double *sv = so + N * QD, *sa = sv + N * R;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
+  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
                      (double*)nullptr, sv, sa);
   CRL_HIP_CHECK(hipGetLastError());
   if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, sv, N * R * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1138,7 +1248,7 @@ int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double
 int32_t crl_dqn_param_count(crl_dqn* h, size_t* n) {
   DQN_GUARD(h);
   if (!n) { set_error("crl_dqn_param_count: null argument"); return 1; }
-  *n = h->P;
+  *n = h->n_params;
   return 0;
 }
 
@@ -1152,9 +1262,9 @@ int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* prob
   double* so = static_cast<double*>(h->stage);
   double* sp = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n,
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n,
                                   (double*)nullptr, sp, (double*)nullptr, (double*)nullptr);
-  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, (double*)nullptr, sp);
+  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.c51, (const double*)so, n, (double*)nullptr, sp);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1310,7 +1420,7 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
                   d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p,
                   d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w,
                   d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td, h->walk_scratch,
-                  d.c51.L, d.c51.dl, d.c51.proj, d.c51.sloss, h->proj_scratch};
+                  d.c51.L, d.c51.dl, d.c51.proj, d.c51.sloss, h->proj_scratch, d.noisy.pq, d.noisy.pt, h->xi_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1319,26 +1429,29 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
 
 int32_t crl_dqn_write_params(crl_dqn* h, const float* q_params, size_t n) {
   DQN_GUARD(h);
-  if (!q_params || n != h->P) { set_error("crl_dqn_write_params: expected " + std::to_string(h->P) + " floats"); return 1; }
-  CRL_HIP_CHECK(hipMemcpyAsync(h->d.q, q_params, n * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->d.t, q_params, n * 4, hipMemcpyHostToDevice, h->stream));   // dqn.jl:40 deepcopy(q_net)
+  if (!q_params || n != h->n_params) { set_error("crl_dqn_write_params: expected " + std::to_string(h->n_params) + " floats"); return 1; }
+  // dqn.jl:40 deepcopy(q_net); a noisy handle takes mu then sigma for both nets and rebuilds both images at its current generation
+  CRL_HIP_CHECK(hipMemcpyAsync(h->noisy ? h->d.noisy.pq : h->d.q, q_params, n * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->noisy ? h->d.noisy.pt : h->d.t, q_params, n * 4, hipMemcpyHostToDevice, h->stream));
+  if (h->noisy && noisy_materialise(h)) return 1;
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   h->params_set = true;
   return 0;
 }
 int32_t crl_dqn_init_params(crl_dqn* h, uint64_t seed) {
   DQN_GUARD(h);
-  std::vector<float> w(h->P);
-  if (h->duel ? crl_dqn_dueling_make_nn(seed, h->c51 ? h->d.c51.N : 0, w.data(), w.size())
+  std::vector<float> w(h->n_params);
+  if (h->noisy ? crl_dqn_noisy_make_nn(seed, h->sigma0, h->duel ? 1 : 0, h->c51 ? h->d.c51.N : 0, w.data(), w.size())
+      : h->duel ? crl_dqn_dueling_make_nn(seed, h->c51 ? h->d.c51.N : 0, w.data(), w.size())
               : h->c51 ? crl_dqn_c51_make_nn(seed, h->d.c51.N, w.data(), w.size()) : crl_dqn_make_nn(seed, w.data(), w.size())) return 1;
   return crl_dqn_write_params(h, w.data(), w.size());
 }
 
 int32_t crl_dqn_read_params(crl_dqn* h, float* q_params, float* target_params, size_t n) {
   DQN_GUARD(h);
-  if (!q_params || n != h->P) { set_error("crl_dqn_read_params: expected " + std::to_string(h->P) + " floats"); return 1; }
-  CRL_HIP_CHECK(hipMemcpyAsync(q_params, h->d.q, n * 4, hipMemcpyDeviceToHost, h->stream));
-  if (target_params) CRL_HIP_CHECK(hipMemcpyAsync(target_params, h->d.t, n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (!q_params || n != h->n_params) { set_error("crl_dqn_read_params: expected " + std::to_string(h->n_params) + " floats"); return 1; }
+  CRL_HIP_CHECK(hipMemcpyAsync(q_params, h->noisy ? h->d.noisy.pq : h->d.q, n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (target_params) CRL_HIP_CHECK(hipMemcpyAsync(target_params, h->noisy ? h->d.noisy.pt : h->d.t, n * 4, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -1372,7 +1485,7 @@ int32_t crl_dqn_run(crl_dqn* h, int64_t max_env_steps, crl_dqn_episode* eps, int
     const int64_t cycles = limit / h->cfg.train_freq + 2;
     hipLaunchKernelGGL(dqn_begin_kernel, dim3(1), dim3(1), 0, st, d, max_env_steps);
     if (!h->cycle_exec && !h->graph_failed) {
-      // one cycle = ten dependent launches with constant arguments: captured once, replayed as a hipGraph (the cycle is
+      // one cycle = ten (a noisy handle: eleven) dependent launches with constant arguments: captured once, replayed as a hipGraph (the cycle is
       // bound by the dependent kernels themselves — 52.7 K vs 53.1 K steps/s without the graph — so this stays opt-in)
       hipGraph_t g = nullptr;
       bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -1414,10 +1527,10 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   double* so = static_cast<double*>(h->stage);
   double* sq = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (const double*)so, n, sq,
+  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n, sq,
                                   (double*)nullptr, (double*)nullptr, (double*)nullptr);
-  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, (const float*)h->d.q, h->d.c51, (const double*)so, n, sq, (double*)nullptr);
-  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->d.q, so, n, sq);
+  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.c51, (const double*)so, n, sq, (double*)nullptr);
+  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), (const double*)so, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1435,10 +1548,10 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
   const dim3 grid((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), block(64 * DQN_EVAL_WAVES);
   if (h->duel) hipLaunchKernelGGL(dqn_duel_eval_kernel, dim3((unsigned)((ev.n + DUEL_EVAL_WAVES - 1) / DUEL_EVAL_WAVES)), dim3(64 * DUEL_EVAL_WAVES),
-                                  duel_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.duel, h->d.c51, (int)h->cfg.max_steps, h->cfg.gamma, ev);
-  else if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, (const float*)h->d.q, h->d.c51,
+                                  duel_eval_lds((int)h->P), h->stream, h->greedy_image(), h->d.duel, h->d.c51, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  else if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, h->greedy_image(), h->d.c51,
                                  (int)h->cfg.max_steps, h->cfg.gamma, ev);
-  else hipLaunchKernelGGL(dqn_eval_kernel, grid, block, 0, h->stream, (const float*)h->d.q, (int)h->cfg.max_steps, h->cfg.gamma, ev);
+  else hipLaunchKernelGGL(dqn_eval_kernel, grid, block, 0, h->stream, h->greedy_image(), (int)h->cfg.max_steps, h->cfg.gamma, ev);
   CRL_HIP_CHECK(hipGetLastError());
   return value_eval_finish(h->stream, ev, report, returns, lengths, disc_returns, v0, trace_action);
 }

@@ -11,6 +11,7 @@
 #include "dqn_target.hpp"
 #include "dqn_c51.hpp"
 #include "dqn_duel.hpp"
+#include "dqn_noisy.hpp"
 #include "value_eval.hpp"
 
 namespace crl {
@@ -41,6 +42,8 @@ struct DQNDev {
   C51Dev c51;                                 // the categorical head (crl_dqn_c51_create; such a handle also has tgt.on); all zero on the other handles
   DuelDev duel;                               // the dueling heads (crl_dqn_dueling_create; such a handle also has tgt.on, and c51.on if categorical): then H2
                                               // and d2 hold 168 units per sample; all zero on the other handles
+  NoisyDev noisy;                             // noisy linear layers (crl_dqn_noisy_create): q / t are then the effective images mu + sigma·eps of the current
+                                              // generation, m / v hold 2P entries and betap twice the twin's pairs; all zero on the other handles
 };
 
 __device__ __forceinline__ double dq_linear_schedule(double start_e, double end_e, double duration, double t) {
@@ -279,6 +282,73 @@ __device__ __forceinline__ void dqn_adam_step(const DQNDev& a, int P, int n_arra
       c->n_losses += 1;
     }
     c->train_pending = 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// dqn_adam_step on a noisy handle (dqn_noisy.hpp), one block: the update that is now completing was update u = n_updates, run on the images of generation
+// u. (1) that generation's xi table of the online net is rebuilt in LDS; (2) adam_entry on mu[p] with g = grads[p] and on sigma[p] with g·eps_p, sigma's
+// arrays taking the β-power pairs n_arrays + arr; (3) the hard copy of mu and sigma to the target; (4) β powers, loss record, train_pending as
+// dqn_adam_step; (5) the xi tables of generation u + 1 for both nets; (6) both images. xs: 2·NOISY_MAX_XI floats of LDS. Steps 5 and 6 are what
+// dqn_noisy_materialise does; by default the cycle runs them as a launch of their own over every CU (CRL_NOISY_SPLIT_TAIL), which the launch
+// boundary orders behind the n_updates this block leaves.
+// ------------------------------------------------------------------------------------------------------
+#ifndef CRL_NOISY_SPLIT_TAIL
+#define CRL_NOISY_SPLIT_TAIL 1   // 1: steps 5-6 are an eleventh, multi-block launch (dqn_noisy_materialise_kernel); 0 (experiment build, csrc/Makefile EXTRA=-DCRL_NOISY_SPLIT_TAIL=0): they run here, in the one block — measured slower, DESIGN.md §3l
+#endif
+template <typename ArrayOf>
+__device__ __forceinline__ void dqn_noisy_adam_step(const DQNDev& a, int n_arrays, ArrayOf array_of, const NoisyTable& tab, float* xs) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, nth = blockDim.x, P = a.noisy.P;
+  const int64_t gstep = a.ctl->global_step;
+  const uint64_t u = (uint64_t)a.ctl->n_updates;
+  const bool copy = gstep % a.cfg.target_net_freq == 0;
+  float* const pq = a.noisy.pq;
+  float* const pt = a.noisy.pt;
+  noisy_build_xi(xs, tab.n_xi, a.cfg.seed, u, S_NOISY_Q);
+  __syncthreads();
+  for (int p = tid; p < P; p += nth) {
+    const int arr = array_of(p);
+    const float g = a.grads[p], gs = g * noisy_eps(tab, xs, p);
+    float mi, vi, w;
+    adam_entry((double)g, a.m[p], a.v[p], pq[p], a.betap[2 * arr], a.betap[2 * arr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
+    a.m[p] = mi; a.v[p] = vi; pq[p] = w;
+    if (copy) pt[p] = w;
+    const int sarr = n_arrays + arr;
+    adam_entry((double)gs, a.m[P + p], a.v[P + p], pq[P + p], a.betap[2 * sarr], a.betap[2 * sarr + 1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, w);
+    a.m[P + p] = mi; a.v[P + p] = vi; pq[P + p] = w;
+    if (copy) pt[P + p] = w;
+  }
+  __syncthreads();                       // every read of the β powers and of generation u's table is done
+  if (tid < 2 * n_arrays) betap_advance(a.betap, tid, a.betap[2 * tid], a.betap[2 * tid + 1]);
+  if (tid == 0) {
+    DQNCtl* c = a.ctl;
+    c->n_updates += 1;
+    if (gstep % a.cfg.log_frequency == 0) {
+      if (c->n_losses < DQN_MAX_LOSSES) { a.losses[c->n_losses].global_step = gstep; a.losses[c->n_losses].loss = c->last_loss; }
+      c->n_losses += 1;
+    }
+    c->train_pending = 0;
+  }
+#if !CRL_NOISY_SPLIT_TAIL                // the experiment build; by default the cycle's eleventh launch (dqn_noisy_materialise_kernel) does this on every CU
+  noisy_build_xi(xs, tab.n_xi, a.cfg.seed, u + 1, S_NOISY_Q);
+  noisy_build_xi(xs + NOISY_MAX_XI, tab.n_xi, a.cfg.seed, u + 1, S_NOISY_T);
+  __syncthreads();
+  for (int p = tid; p < P; p += nth) {   // the thread that wrote mu[p] / sigma[p] above reads them here
+    a.q[p] = noisy_weight(pq[p], pq[P + p], noisy_eps(tab, xs, p));
+    a.t[p] = noisy_weight(pt[p], pt[P + p], noisy_eps(tab, xs + NOISY_MAX_XI, p));
+  }
+#endif
+}
+// both images of generation gen from mu and sigma, any grid: every block builds the two tables in its LDS (xs: 2·NOISY_MAX_XI floats)
+__device__ __forceinline__ void dqn_noisy_materialise(const DQNDev& a, const NoisyTable& tab, uint64_t gen, float* xs) {
+  const int P = a.noisy.P;
+  noisy_build_xi(xs, tab.n_xi, a.cfg.seed, gen, S_NOISY_Q);
+  noisy_build_xi(xs + NOISY_MAX_XI, tab.n_xi, a.cfg.seed, gen, S_NOISY_T);
+  __syncthreads();
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
+    a.q[p] = noisy_weight(a.noisy.pq[p], a.noisy.pq[P + p], noisy_eps(tab, xs, p));
+    a.t[p] = noisy_weight(a.noisy.pt[p], a.noisy.pt[P + p], noisy_eps(tab, xs + NOISY_MAX_XI, p));
   }
 }
 

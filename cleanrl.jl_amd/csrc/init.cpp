@@ -135,6 +135,31 @@ int32_t crl_dqn_dueling_make_nn(uint64_t seed, int32_t n_atoms, float* out, size
   return 0;
 }
 
+// a noisy net (Fortunato et al. 2018, factorised rule): per layer (in, out), in the twin's array order, lim = 1/sqrt(in); mu of the weights, then of the
+// biases, = (float)((u − 0.5)·(2·lim)), u one draw each in storage order; sigma = (float)(sigma0·lim) everywhere. out = mu (P) then sigma (P).
+int32_t crl_dqn_noisy_make_nn(uint64_t seed, double sigma0, int32_t dueling, int32_t n_atoms, float* out, size_t n) {
+  if (!(sigma0 >= 0.0 && sigma0 <= 10.0)) { set_error("crl_dqn_noisy_make_nn: sigma0 must be in 0..10"); return 1; }
+  if (dueling != 0 && dueling != 1) { set_error("crl_dqn_noisy_make_nn: dueling must be 0 or 1"); return 1; }
+  if (n_atoms != 0 && (n_atoms < 2 || n_atoms > 64)) { set_error("crl_dqn_noisy_make_nn: n_atoms must be 0 (scalar) or in 2..64"); return 1; }
+  const int R = n_atoms == 0 ? 1 : n_atoms, rows3 = n_atoms == 0 ? 2 : 2 * n_atoms;
+  const int plain[3][2] = {{4, 120}, {120, 84}, {84, rows3}}, duel[5][2] = {{4, 120}, {120, 84}, {84, R}, {120, 84}, {84, 2 * R}};
+  const int (*layers)[2] = dueling ? duel : plain;
+  const int nl = dueling ? 5 : 3;
+  size_t P = 0;
+  for (int l = 0; l < nl; ++l) P += (size_t)layers[l][1] * (size_t)(layers[l][0] + 1);
+  if (!out || n != 2 * P) { set_error("crl_dqn_noisy_make_nn: expected " + std::to_string(2 * P) + " floats"); return 1; }
+  crl::Rng rng{seed ^ 0x2015ull};
+  float* p = out;
+  for (int l = 0; l < nl; ++l) {
+    const size_t cnt = (size_t)layers[l][1] * (size_t)(layers[l][0] + 1);
+    const double lim = 1.0 / std::sqrt((double)layers[l][0]);
+    const float sigma = (float)(sigma0 * lim);
+    for (size_t i = 0; i < cnt; ++i) { p[i] = (float)((rng.uniform() - 0.5) * (2.0 * lim)); p[P + i] = sigma; }
+    p += cnt;
+  }
+  return 0;
+}
+
 int32_t crl_ddpg_make_nn(int32_t obs_dim, int32_t act_dim, uint64_t seed, float* actor, size_t actor_n, float* critic, size_t critic_n) {
   int64_t na = 0, nc = 0;
   if (crl_ddpg_param_count(obs_dim, act_dim, &na, &nc)) return 1;

@@ -109,6 +109,52 @@ def _check_c51(dist):
     return dist
 
 
+@dataclasses.dataclass
+class NoisyOptions:
+    """Noisy linear layers (NoisyNets, Fortunato et al. 2018; crl_dqn_noisy_options) — not in dqn.jl, so not in DQNConfig: every dense layer learns
+    mu and sigma per parameter and acts on mu + sigma·eps with factorised Gaussian eps, redrawn after every update; sigma starts at sigma0 / sqrt(in).
+    The ε-greedy schedule is honoured as configured: the NoisyNet setting is DQNConfig(epsilon_start=0.0, epsilon_end=0.0), exploration by the noise
+    alone."""
+    sigma0: float = 0.5
+
+
+def _check_noisy(noisy):
+    """→ the NoisyOptions, validated before the library is touched"""
+    if not isinstance(noisy, NoisyOptions):
+        raise TypeError(f"noisy must be a NoisyOptions or None, got {type(noisy).__name__}")
+    v = noisy.sigma0
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 <= v <= 10.0):
+        raise ValueError(f"NoisyOptions.sigma0 must be in 0..10, got {v!r}")
+    return noisy
+
+
+NOISY_PLAIN_LAYERS = ((4, 120), (120, 84))                # (in, out) of the trunk; the head follows: (84, 2) or (84, 2N)
+
+
+def noisy_layers(dueling=False, n_atoms=None):
+    """(in, out) of a net's dense layers in parameter-array order: the rows of the noise table and of noisy_sigma"""
+    if dueling:
+        R = 1 if n_atoms is None else int(n_atoms)
+        return ((4, 120), (120, 84), (84, R), (120, 84), (84, 2 * R))
+    return NOISY_PLAIN_LAYERS + ((84, 2 if n_atoms is None else 2 * int(n_atoms)),)
+
+
+def make_nn_noisy(seed=0, sigma0=0.5, dueling=False, n_atoms=None):
+    """A noisy net's 2P numbers, mu (P, the twin's layout) then sigma (P): Fortunato's factorised rule, mu ~ U(−1/√in, +1/√in) for weights and biases
+    and sigma = sigma0/√in, with a numpy stream — weights are an input."""
+    rng = np.random.default_rng(seed)
+    layers = noisy_layers(dueling, n_atoms)
+    P = sum(o * (i + 1) for i, o in layers)
+    out = np.zeros(2 * P, np.float32)
+    at = 0
+    for i, o in layers:
+        n, lim = o * (i + 1), 1.0 / np.sqrt(float(i))
+        out[at:at + n] = rng.uniform(-lim, lim, n).astype(np.float32)
+        out[P + at:P + at + n] = np.float32(float(sigma0) * lim)
+        at += n
+    return out
+
+
 def linear_schedule(start_e, end_e, duration, t):
     """dqn.jl:28-31 (host-side helper; the loop evaluates the same expression on the device)."""
     slope = (end_e - start_e) / duration
@@ -158,10 +204,12 @@ def make_nn_dueling(seed=0, n_atoms=None):
 class DQNAgent:
     """q_net, target_net, Adam state, ReplayBuffer(buffer_size) and the CartPoleEnv of one dqn(config) run, on one GPU."""
 
-    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None, dist=None, dueling=False):
+    def __init__(self, config: DQNConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, max_steps=200, per=None, target=None, dist=None, dueling=False,
+                 noisy=None):
         if not isinstance(dueling, (bool, np.bool_)):
             raise ValueError(f"dueling must be True or False, got {dueling!r}")
         self.config = config
+        self.noisy = None if noisy is None else _check_noisy(noisy)
         self.dueling = bool(dueling)
         self.dist = None if dist is None else _check_c51(dist)
         self.per = None if per is None else _check_per(per, config)
@@ -177,8 +225,10 @@ class DQNAgent:
                                   target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)),
                                   c51=None if self.dist is None else L.CrlDQNC51Options(int(self.dist.n_atoms), 0, float(self.dist.v_min),
                                                                                         float(self.dist.v_max)),
-                                  dueling=self.dueling)
-        if params is None and self.dueling:
+                                  dueling=self.dueling, noisy=None if self.noisy is None else L.CrlDQNNoisyOptions(float(self.noisy.sigma0)))
+        if params is None and self.noisy is not None:
+            params = make_nn_noisy(init_seed, self.noisy.sigma0, self.dueling, None if self.dist is None else self.dist.n_atoms)
+        elif params is None and self.dueling:
             params = make_nn_dueling(init_seed, None if self.dist is None else self.dist.n_atoms)
         elif params is None:
             params = make_nn(init_seed) if self.dist is None else make_nn_c51(init_seed, self.dist.n_atoms)
@@ -203,12 +253,26 @@ def dqn_evaluate(agent, *, num_envs=256, episodes_per_env=1, seed=EVAL_SEED, tra
     return agent.handle.evaluate(num_envs, episodes_per_env, seed, trace_steps)
 
 
+def noisy_sigma(agent):
+    """The mean |sigma| of each parameter array of the agent's q_net, read from the handle, in array order (W1 b1 W2 b2 W3 b3, or the dueling net's
+    ten): how much noise the layers have kept. NoisyNets anneal their own exploration, so this is the curve to watch where ε would be."""
+    if not isinstance(agent, DQNAgent) or agent.noisy is None:
+        raise TypeError("noisy_sigma: agent must be a DQNAgent made with noisy=NoisyOptions(...)")
+    q, _ = agent.handle.read_params()
+    sigma = q[q.size // 2:]
+    out, at = [], 0
+    for i, o in noisy_layers(agent.dueling, None if agent.dist is None else agent.dist.n_atoms):
+        out.append(float(np.abs(sigma[at:at + o * i]).mean())); at += o * i
+        out.append(float(np.abs(sigma[at:at + o]).mean())); at += o
+    return out
+
+
 def _eval_record(global_step, report):
     return (global_step, "Evaluation Statistics", dict(eval_return_mean=report["return_mean"], eval_return_std=report["return_std"],
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, dueling=False, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, dueling=False, noisy: NoisyOptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
         eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
@@ -222,7 +286,9 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     replay and any target options: "Training Statistics".loss is then the cross-entropy against the projected target distribution, and the evaluation
     record's eval_q_bias is that of the expected value. None (default) is the scalar critic, bit for bit what it was. `dueling=True` splits layers 2 and 3 into a value and an
     advantage stream (crl_dqn_dueling_create), with either head, either replay and any target options; the records are unchanged, and False (default)
-    is the one-headed net, bit for bit what it was."""
+    is the one-headed net, bit for bit what it was. `noisy` (a NoisyOptions) makes every dense layer a noisy one (crl_dqn_noisy_create), with every
+    option above; the records are unchanged (ϵ is logged as configured: set epsilon_start = epsilon_end = 0 to explore by the noise alone), evaluation
+    runs with the noise off, and None (default) is the log stream it was."""
     if isinstance(eval_every, bool) or not isinstance(eval_every, (int, np.integer)) or eval_every < 0:
         raise ValueError(f"dqn: eval_every must be an integer >= 0, got {eval_every!r}")
     if eval_every:
@@ -230,7 +296,7 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     config = config or DQNConfig()
     Logger.make_logger(f"dqn|{config.run_name}", **({"to_terminal": False} | logger_kw))         # dqn.jl:35
     lg = logging.getLogger("CleanRL")
-    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target, dist=dist, dueling=dueling)
+    agent = DQNAgent(config, device=device, seed=seed, params=params, per=per, target=target, dist=dist, dueling=dueling, noisy=noisy)
     start = time.time()
     global_step = 0
     while True:

@@ -763,6 +763,61 @@ int32_t crl_dqn_dueling_make_nn(uint64_t seed, int32_t n_atoms /* 0 = scalar */,
 /* the two streams before they are combined, for n observations (4, n): value (R, n), adv (R, 2, n) with i fastest. Either output may be NULL. */
 int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double* value, double* adv);
 
+/* -----------------------------------------------------------------------------------------------------
+ * Noisy linear layers (NoisyNets, Fortunato et al. 2018, factorised Gaussian noise) — no reference counterpart: dqn.jl explores ε-greedily. A handle
+ * made by crl_dqn_noisy_create learns mu and sigma for every parameter of all its dense layers; its "twin" is the handle the other creators would make
+ * from the same dueling / c51 / per / tgt arguments (crl_dqn_create when all are off; crl_dqn_per_create; crl_dqn_create_with when tgt is given;
+ * crl_dqn_c51_create; crl_dqn_dueling_create), with P parameters. The effective image w = mu + sigma·eps of each net is materialised on the device,
+ * and every kernel of the twin's cycle — collect, the forwards, the TD launch, the pullbacks, the weight gradients — runs on that image unchanged
+ * (csrc/dqn_noisy.hpp, csrc/dqn.hip: the Adam slot is dqn_noisy_adam_kernel, and an eleventh launch, dqn_noisy_materialise_kernel, forms the next
+ * generation's images on every CU: in the Adam launch's one block that measured slower). It composes with both heads,
+ * dueling, both replays and every target option. The five older kinds of handle keep every bit of their behaviour; the crl_dqn_noisy_* calls below
+ * fail on them with a message naming crl_dqn_noisy_create.
+ *
+ *   Table     The noise table lists the net's layers in parameter-array order — plain and categorical: (in, out) = (4,120) (120,84) (84,rows3), rows3 =
+ *             2 or 2N; dueling: (4,120) (120,84) (84,R) (120,84) (84,2R) for W1, W2v, W3v, W2a, W3a — and each layer contributes xi_in[in] then
+ *             xi_out[out]: 412 + rows3 or 700 + 3R floats (at most 892). The position c in the table is the Philox component word.
+ *   Noise     z = sqrt(−2.0·log(1.0 − u_xy))·cos(6.283185307179586·u_zw), Float64, u_xy / u_zw the two 53-bit halves of ONE Philox block with counter
+ *             (c, gen lo, gen hi, stream) and key cfg.seed — the Box–Muller form of DDPG's noise (csrc/normal_bm.hpp) —; stream 0x22 for q_net, 0x23
+ *             for target_net (new: the loop uses 0, 1, 2, 4, evaluation 0x20 / 0x21, the draws 0xD9 / 0xDA).
+ *             xi_c = (float)(z < 0.0 ? −sqrt(−z) : sqrt(z))                                      (f(x) = sgn(x)·sqrt|x|, rounded to Float32 once)
+ *   eps       weight (i, j) of a layer: eps = xi_out[i] * xi_in[j], one Float32 multiply; bias i: eps = xi_out[i]
+ *   Image     w = mu + sigma * eps: a Float32 multiply, then a Float32 add, no fma
+ *   Gradient  g = the Float32 the twin's weight-gradient kernel leaves for parameter p (computed on the noisy image); g_mu = g;
+ *             g_sigma = g * eps, one Float32 multiply. Adam (Flux's, as everywhere) runs over 2P entries, m and v likewise, with one β-power pair
+ *             per array: the twin's arrays for mu, then as many again for sigma.
+ *   Generations  The images in use after u completed updates (crl_dqn_status.n_updates) are generation gen = u, for both nets, each on its own
+ *             stream word. The online image of generation u serves the collect steps up to the next update, that update's q_net(state) pass and its
+ *             double-Q q_net(x) pass; the target image serves its target_net(x) pass. After the Adam step of that update (mu and sigma of q_net; the
+ *             hard copy of mu and sigma to target_net when global_step % target_net_freq == 0) both images are rebuilt with generation u + 1 — the
+ *             target image is redrawn every update, whether or not a copy happened. g_sigma of update u uses eps of generation u.
+ *   Layout    2P floats: mu in the twin's layout, then sigma in the same layout. crl_dqn_param_count reports 2P; crl_dqn_write_params (mu, sigma of
+ *             both nets, then both images rebuilt at the current generation), crl_dqn_read_params (mu, sigma of q_net / target_net) and
+ *             crl_dqn_init_params take n = 2P.
+ *   Init      per layer lim = 1.0 / sqrt((double)in); mu = (float)((u − 0.5) · (2.0 · lim)) ~ U(−1/√in, +1/√in) for weights, then biases, u in storage
+ *             order from init.cpp's generator; sigma = (float)(sigma0 · lim).
+ *   Noise off crl_dqn_evaluate, crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams read the mu half as their image: they are the twin's
+ *             kernels on the twin's layout, so every evaluated action is still the argmax of crl_dqn_q_values on that observation, bit for bit.
+ *             Collect acts on the noisy image.
+ *   ε-greedy  is honoured as configured. The NoisyNet setting is epsilon_start = epsilon_end = 0: the draw u53 < 0 never fires and the agent explores
+ *             by its noise alone.
+ * Errors of crl_dqn_noisy_create: cfg, noisy or out NULL; sigma0 negative, not finite or above 10; dueling not 0 or 1; and the composed creators' own
+ * (c51, per, tgt fields, crl_dqn_create's) — each names the field.
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct crl_dqn_noisy_options { double sigma0; } crl_dqn_noisy_options;   /* 8 bytes; Fortunato's default is 0.5 */
+int32_t crl_dqn_noisy_create(const crl_dqn_config* cfg, const crl_dqn_noisy_options* noisy, int32_t dueling /* 0 | 1 */,
+                             const crl_dqn_c51_options* c51 /* NULL = scalar */, const crl_dqn_per_options* per /* NULL = uniform */,
+                             const crl_dqn_target_options* tgt /* NULL = the twin's default */, int32_t device, crl_dqn** out);
+/* the Init rule above; n_atoms 0 = scalar, else 2..64; n must be 2P of that twin. Stateless and host-only. */
+int32_t crl_dqn_noisy_make_nn(uint64_t seed, double sigma0, int32_t dueling, int32_t n_atoms /* 0 = scalar */, float* out, size_t n);
+/* the effective image in use, net 0 = q_net, 1 = target_net; n must be P (half of crl_dqn_param_count) */
+int32_t crl_dqn_noisy_weights(crl_dqn* h, int32_t net, float* out, size_t n);
+/* the length of the handle's noise table: 412 + rows3, or 700 + 3R on a dueling handle */
+int32_t crl_dqn_noisy_noise_count(crl_dqn* h, size_t* n);
+/* the xi table of any generation and either net (stateless: training state untouched): one small launch of the __device__ function the Adam launch
+ * builds its tables with. n must be crl_dqn_noisy_noise_count's. */
+int32_t crl_dqn_noisy_noise(crl_dqn* h, uint64_t gen, int32_t net, float* xi, size_t n);
+
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
  * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·

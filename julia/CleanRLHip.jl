@@ -7,7 +7,7 @@
 # tests/test_host_cpu.py::test_config_struct_matches_header_and_reference_defaults pins (104 bytes).
 module CleanRLHip
 
-export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, DQNTargetOptions, C51Options, c51_probs, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
+export PPOConfig, ppo, get_action, logprob_actions, gae, a2c, dqn, PEROptions, DQNTargetOptions, C51Options, NoisyOptions, c51_probs, per_status, q_values, ddpg, ddpg_external, ddpg_evaluate, td3, td3_external, sac, sac_external, sac_status, get_q_both, dqn_evaluate, a2c_evaluate, a2c_forward, a2c_read_grads, get_q, actor_mean, reference_ddpg_params, reference_params, init_params!, comm_unique_id, comm_init!, comm_peer_export!, comm_peer_attach!, env_step!, act_device!, record_device!, update!, stream, ppo_external,
        comm_destroy!, set_option!, get_option, evaluate, diagnose
 
 const libcrl = get(ENV, "CLEANRL_HIP_LIB", joinpath(@__DIR__, "..", "cleanrl.jl_amd", "libcleanrl_hip.so"))
@@ -570,6 +570,15 @@ Base.@kwdef struct C51Options
 end
 struct CrlDQNC51Options; n_atoms::Int32; pad::Int32; v_min::Float64; v_max::Float64; end                                     # crl_dqn_c51_options
 
+# Noisy linear layers (NoisyNets, Fortunato et al. 2018; include/cleanrl_hip.h crl_dqn_noisy_options) — not in dqn.jl, so not a DQNConfig field:
+# `dqn(config; noisy = NoisyOptions())`, with every other option. Every dense layer learns mu and sigma (the parameter vector is twice the twin's: mu,
+# then sigma; crl_dqn_param_count) and acts on mu + sigma·eps with factorised Gaussian eps, redrawn after every update; evaluation and q_values run with
+# the noise off. ε-greedy is honoured as configured: the NoisyNet setting is epsilon_start = epsilon_end = 0. Like the rest of this file, not executed here.
+Base.@kwdef struct NoisyOptions
+  sigma0::Float64 = 0.5
+end
+struct CrlDQNNoisyOptions; sigma0::Float64; end                                                                              # crl_dqn_noisy_options
+
 # crl_dqn_c51_probs: softmax of q_net(obs) per action, (4, n) → (n_atoms, 2, n); an error on an agent with the scalar critic
 function c51_probs(agent::DQNAgent, obs::AbstractMatrix{Float64}, n_atoms::Integer)
   o = Array(obs); n = size(o, 2); p = Array{Float64}(undef, n_atoms, 2, n)
@@ -604,7 +613,7 @@ end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
              chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
              per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options}=nothing,
-             dueling::Bool=false)
+             dueling::Bool=false, noisy::Union{Nothing,NoisyOptions}=nothing)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
   cfg = CrlDQNConfig(config.log_frequencey, config.total_timesteps, config.buffer_size, config.min_buff_size, config.lr,
@@ -613,7 +622,17 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   h = Ref{Ptr{Cvoid}}(C_NULL)
   popt = per === nothing ? nothing :
          CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
-  if dueling                # the dueling heads (Wang et al. 2016; crl_dqn_dueling_create), with either head (NULL = scalar), either replay and any target
+  if noisy !== nothing      # noisy linear layers (crl_dqn_noisy_create) on top of any of the kinds below. Like the rest of this file, never executed.
+    0.0 <= noisy.sigma0 <= 10.0 || throw(ArgumentError("dqn: noisy.sigma0 must be in 0..10, got $(noisy.sigma0)"))
+    nopt = Ref(CrlDQNNoisyOptions(noisy.sigma0))
+    copt = dist === nothing ? C_NULL : Ref(CrlDQNC51Options(dist.n_atoms, 0, dist.v_min, dist.v_max))
+    pref = popt === nothing ? C_NULL : Ref(popt)
+    tref = target === nothing ? C_NULL : Ref(CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0))
+    GC.@preserve nopt copt pref tref check(ccall((:crl_dqn_noisy_create, libcrl), Int32,
+      (Ref{CrlDQNConfig}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}),
+      cfg, Base.unsafe_convert(Ptr{Cvoid}, nopt), dueling ? 1 : 0, copt === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, copt),
+      pref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, pref), tref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tref), device, h))
+  elseif dueling            # the dueling heads (Wang et al. 2016; crl_dqn_dueling_create), with either head (NULL = scalar), either replay and any target
                             # options: ten arrays, 20928 + 255·R parameters (crl_dqn_param_count). Like the rest of this file, never executed.
     copt = dist === nothing ? C_NULL : Ref(CrlDQNC51Options(dist.n_atoms, 0, dist.v_min, dist.v_max))
     pref = popt === nothing ? C_NULL : Ref(popt)
@@ -648,7 +667,7 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   end
   agent = DQNAgent(h[])
   finalizer(x -> ccall((:crl_dqn_destroy, libcrl), Int32, (Ptr{Cvoid},), x.h), agent)
-  params === nothing && init !== nothing && dist === nothing && !dueling && (params = init())   # dqn.jl:39 make_nn(env); its head is the scalar one, so a C51
+  params === nothing && init !== nothing && dist === nothing && !dueling && noisy === nothing && (params = init())   # dqn.jl:39 make_nn(env); its head is the scalar one, so a C51
                                                                                     # agent without `params` takes the library's initialiser
   if params === nothing
     check(ccall((:crl_dqn_init_params, libcrl), Int32, (Ptr{Cvoid}, UInt64), agent.h, UInt64(init_seed)))

@@ -12,6 +12,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py dqn --total_timesteps 50000 --per --per_alpha 0.6 --per_beta_start 0.4 --per_beta_end 1.0 --per_beta_duration 50000 --per_eps 1e-6   (prioritized replay; --per alone takes the defaults, beta_duration = total_timesteps)
     python scripts/run.py dqn --total_timesteps 50000 --double_q --n_step 3 [--per]   (double Q-learning and 3-step returns; either alone, both combine with --per)
     python scripts/run.py dqn --total_timesteps 50000 --c51 [--n_atoms 51 --v_min 0 --v_max 100] [--per] [--double_q --n_step 3]   (categorical C51 critic; combines with all of the above)
+    python scripts/run.py dqn --total_timesteps 50000 --noisy [--sigma0 0.5] [--dueling --c51 --per --double_q --n_step 3]   (noisy linear layers; epsilon_start / epsilon_end default to 0 with --noisy; with all the others: Rainbow)
     python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
     python scripts/run.py ddpg --total_timesteps 20000 --eval_every 2000 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": the noise-free actor's held-out score and the critic's bias every 2000 steps)
@@ -88,7 +89,16 @@ def main():
         # the dueling heads (crl_dqn_dueling_create): --dueling combines with --per, --double_q / --n_step and --c51
         dueling = "--dueling" in argv
         argv = [a for a in argv if a != "--dueling"]
-        crl.dqn(config_parser.argparse_struct(crl.DQNConfig(), argv), per, target, dist, dueling, to_terminal=True, to_tensorboard=False, **kw).close()
+        # noisy linear layers (crl_dqn_noisy_create): --noisy switches them on, --sigma0 is NoisyOptions' field and implies it; combines with all of
+        # the above. NoisyNets explore by their noise, so epsilon_start / epsilon_end default to 0 here unless they are given.
+        no = take((("--sigma0", float),))
+        noisy = None
+        base = crl.DQNConfig()
+        if "--noisy" in argv or no:
+            argv = [a for a in argv if a != "--noisy"]
+            noisy = crl.NoisyOptions(**no)
+            base = dataclasses.replace(base, epsilon_start=0.0, epsilon_end=0.0)
+        crl.dqn(config_parser.argparse_struct(base, argv), per, target, dist, dueling, noisy, to_terminal=True, to_tensorboard=False, **kw).close()
 
 
 if __name__ == "__main__":
