@@ -101,7 +101,7 @@ EXPORTS = [
     "crl_dqn_per_probe", "crl_dqn_create_with", "crl_dqn_target_read", "crl_dqn_nstep_probe",
     "crl_dqn_c51_create", "crl_dqn_param_count", "crl_dqn_c51_make_nn", "crl_dqn_c51_probs", "crl_dqn_c51_read", "crl_dqn_c51_project_probe",
     "crl_dqn_dueling_create", "crl_dqn_dueling_make_nn", "crl_dqn_dueling_streams",
-    "crl_dqn_noisy_create", "crl_dqn_noisy_make_nn", "crl_dqn_noisy_weights", "crl_dqn_noisy_noise_count", "crl_dqn_noisy_noise", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
+    "crl_dqn_noisy_create", "crl_dqn_noisy_make_nn", "crl_dqn_noisy_weights", "crl_dqn_noisy_noise_count", "crl_dqn_noisy_noise", "crl_dqn_qr_create", "crl_dqn_qr_quantiles", "crl_dqn_qr_read", "crl_dqn_qr_loss_probe", "crl_a2c_forward", "crl_a2c_evaluate", "crl_a2c_eval_envs_per_block",
     "crl_ddpg_param_count", "crl_ddpg_create", "crl_ddpg_destroy", "crl_ddpg_write_params", "crl_ddpg_read_params", "crl_ddpg_make_nn",
     "crl_ddpg_init_params", "crl_ddpg_status_read", "crl_ddpg_run", "crl_ddpg_act", "crl_ddpg_observe", "crl_ddpg_read_losses",
     "crl_ddpg_read_buffer", "crl_ddpg_actor", "crl_ddpg_q_values", "crl_ddpg_evaluate",
@@ -159,6 +159,11 @@ class CrlDQNC51Options(C.Structure):
 def dqn_c51_param_count(n_atoms):
     """10764 + 85·2N: the trunk W1 b1 W2 b2 and the head W3(2N, 84) b3(2N)"""
     return 10764 + 85 * 2 * int(n_atoms)
+
+
+class CrlDQNQROptions(C.Structure):
+    """crl_dqn_qr_options: the quantile head (16 bytes): n_quantiles in 2..64 fixed fractions, Huber threshold kappa > 0."""
+    _fields_ = [("n_quantiles", C.c_int32), ("pad", C.c_int32), ("kappa", C.c_double)]
 
 
 class CrlDQNNoisyOptions(C.Structure):
@@ -349,6 +354,11 @@ def load():
     L.crl_dqn_dueling_streams.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.crl_dqn_noisy_create.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNNoisyOptions), C.c_int32, C.POINTER(CrlDQNC51Options),
                                        C.POINTER(CrlDQNPEROptions), C.POINTER(CrlDQNTargetOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_qr_create.argtypes = [C.POINTER(CrlDQNConfig), C.POINTER(CrlDQNQROptions), C.c_int32, C.POINTER(CrlDQNNoisyOptions),
+                                    C.POINTER(CrlDQNPEROptions), C.POINTER(CrlDQNTargetOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_dqn_qr_quantiles.argtypes = [vp, dp, C.c_int32, dp]
+    L.crl_dqn_qr_read.argtypes = [vp, dp, dp]
+    L.crl_dqn_qr_loss_probe.argtypes = [vp, dp, dp, C.c_int32, dp, dp]
     L.crl_dqn_noisy_make_nn.argtypes = [C.c_uint64, C.c_double, C.c_int32, C.c_int32, fp, C.c_size_t]
     L.crl_dqn_noisy_weights.argtypes = [vp, C.c_int32, fp, C.c_size_t]
     L.crl_dqn_noisy_noise_count.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -1025,9 +1035,12 @@ class DQNHandle:
     become available. `dueling=True` makes it a crl_dqn_dueling_create handle, with either head, either replay and any target options: layers 2 and 3
     are a value and an advantage stream (ten arrays, param_count is its own), and dueling_streams becomes available. `noisy` (a CrlDQNNoisyOptions)
     makes it a crl_dqn_noisy_create handle on top of any of the above: its parameters are mu then sigma (param_count is twice the twin's), q_values /
-    evaluate / c51_probs / dueling_streams run with the noise off, and noisy_weights / noisy_noise become available."""
+    evaluate / c51_probs / dueling_streams run with the noise off, and noisy_weights / noisy_noise become available. `qr` (a CrlDQNQROptions, instead
+    of c51) makes it a crl_dqn_qr_create handle with any of dueling / noisy / per / target: the head holds n_quantiles quantile locations per action,
+    param_count is the categorical twin's with n_atoms = n_quantiles, q_values are their means, and qr_quantiles / qr_read / qr_loss_probe become
+    available (the c51_* calls are errors on it)."""
 
-    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None, dueling=False, noisy=None):
+    def __init__(self, cfg: CrlDQNConfig, device=0, per=None, target=None, c51=None, dueling=False, noisy=None, qr=None):
         self._L = load()
         self.cfg = cfg
         self.per = per
@@ -1035,8 +1048,15 @@ class DQNHandle:
         self.c51 = c51
         self.dueling = bool(dueling)
         self.noisy = noisy
+        self.qr = qr
         self._h = C.c_void_p()
-        if noisy is not None:
+        if qr is not None:
+            if c51 is not None:
+                raise ValueError("DQNHandle: c51 and qr are two kinds of head; give one")
+            check(self._L.crl_dqn_qr_create(C.byref(cfg), C.byref(qr), int(self.dueling), None if noisy is None else C.byref(noisy),
+                                            None if per is None else C.byref(per), None if target is None else C.byref(target), device,
+                                            C.byref(self._h)))
+        elif noisy is not None:
             check(self._L.crl_dqn_noisy_create(C.byref(cfg), C.byref(noisy), int(self.dueling), None if c51 is None else C.byref(c51),
                                                None if per is None else C.byref(per), None if target is None else C.byref(target), device,
                                                C.byref(self._h)))
@@ -1078,7 +1098,7 @@ class DQNHandle:
         return int(n.value)
 
     def read_params(self):
-        n = DQN_PARAM_COUNT if self.c51 is None and not self.dueling and self.noisy is None else self.param_count()
+        n = DQN_PARAM_COUNT if self.c51 is None and self.qr is None and not self.dueling and self.noisy is None else self.param_count()
         q = np.zeros(n, np.float32); t = np.zeros(n, np.float32)
         check(self._L.crl_dqn_read_params(self._h, _ptr(q, C.c_float), _ptr(t, C.c_float), q.size))
         return q, t
@@ -1170,7 +1190,7 @@ class DQNHandle:
         if obs.ndim == 1:
             obs = obs[:, None]
         n = obs.shape[1]
-        R = 1 if self.c51 is None else int(self.c51.n_atoms)
+        R = int(self.qr.n_quantiles) if self.qr is not None else 1 if self.c51 is None else int(self.c51.n_atoms)
         value = np.zeros((R, n), np.float64, order="F"); adv = np.zeros((R, 2, n), np.float64, order="F")
         check(self._L.crl_dqn_dueling_streams(self._h, _ptr(obs, C.c_double), n, _ptr(value, C.c_double), _ptr(adv, C.c_double)))
         return dict(value=value, adv=adv)
@@ -1206,6 +1226,36 @@ class DQNHandle:
         check(self._L.crl_dqn_c51_project_probe(self._h, _ptr(probs, C.c_double), _ptr(nret, C.c_double), _ptr(ndisc, C.c_double),
                                                 _ptr(terminal, C.c_uint8), k, _ptr(proj, C.c_double)))
         return proj
+
+    def qr_quantiles(self, obs):
+        """crl_dqn_qr_quantiles: the quantile locations of q_net(obs) per action, (4, n) → (N, 2, n) float64; q_values is their ascending mean"""
+        obs = np.asfortranarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs[:, None]
+        n = obs.shape[1]
+        N = 1 if self.qr is None else int(self.qr.n_quantiles)
+        theta = np.zeros((N, 2, n), np.float64, order="F")
+        check(self._L.crl_dqn_qr_quantiles(self._h, _ptr(obs, C.c_double), n, _ptr(theta, C.c_double)))
+        return theta
+
+    def qr_read(self):
+        """crl_dqn_qr_read → {target float64 (N, k) the T_j, sample_loss float64 [k]} of the last completed update"""
+        k = int(self.cfg.batch_size)
+        N = 1 if self.qr is None else int(self.qr.n_quantiles)
+        out = dict(target=np.zeros((N, k), np.float64, order="F"), sample_loss=np.zeros(k, np.float64))
+        check(self._L.crl_dqn_qr_read(self._h, _ptr(out["target"], C.c_double), _ptr(out["sample_loss"], C.c_double)))
+        return out
+
+    def qr_loss_probe(self, theta, target):
+        """crl_dqn_qr_loss_probe: the device's pair loss of the rows theta, target (N, k) → (loss float64 [k], dtheta float64 (N, k))"""
+        theta = np.asfortranarray(theta, np.float64); target = np.asfortranarray(target, np.float64)
+        if theta.ndim != 2 or theta.shape != target.shape or (self.qr is not None and theta.shape[0] != int(self.qr.n_quantiles)):
+            raise ValueError("qr_loss_probe: theta and target must both be (n_quantiles, k)")
+        k = theta.shape[1]
+        loss = np.zeros(max(k, 1), np.float64); dtheta = np.zeros(theta.shape, np.float64, order="F")
+        check(self._L.crl_dqn_qr_loss_probe(self._h, _ptr(theta, C.c_double), _ptr(target, C.c_double), k, _ptr(loss, C.c_double),
+                                            _ptr(dtheta, C.c_double)))
+        return loss[:k], dtheta
 
     def nstep_probe(self, reward, terminal, ptr, idx, n_step, gamma):
         """crl_dqn_nstep_probe: the device's n-step walk on a ring of len(reward) slots → {last, m int32 [k], nret, ndisc float64 [k]}"""

@@ -21,6 +21,7 @@
 #include "dqn_per.hpp"
 #include "dqn_target.hpp"
 #include "dqn_c51.hpp"
+#include "dqn_qr.hpp"
 #include "dqn_duel.hpp"
 #include "dqn_loops.hpp"   // the net's shape, DQNCtl, DQNDev, and the loops the heads share
 #include "replay_sample.hpp"
@@ -361,7 +362,25 @@ __device__ __forceinline__ void c51_block_q(const double* ls, double* qs, const 
   __syncthreads();
 }
 
+// The quantile head's twin (dqn_qr.hpp): Q(a) = mean_i ls[a·N + i], wave a taking action a; `quant` receives the 2N locations; ends on a block barrier
+__device__ __forceinline__ void qr_block_q(const double* ls, double* qs, const C51Dev& c, double* quant) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const double th = lane < c.N ? ls[w * c.N + lane] : 0.0;
+  const double Q = qr_value(th, c.N);
+  if (lane == 0) qs[w] = Q;
+  if (quant && lane < c.N) quant[w * c.N + lane] = th;
+  __syncthreads();
+}
+// QR is the handle's head kind (C51Dev.kind), decided on the host once per launch: every kernel that turns 2N head rows into Q(a) comes as a
+// categorical and a quantile instantiation, and the categorical one holds the instructions it held before the quantile head existed.
+template <bool QR>
+__device__ __forceinline__ void dist_block_q(const double* ls, double* qs, const C51Dev& c, double* rows_out) {
+  if constexpr (QR) qr_block_q(ls, qs, c, rows_out);
+  else c51_block_q(ls, qs, c, rows_out);
+}
+
 // dqn_collect_kernel with the categorical head: a greedy step forms the 2N logits (one row per thread), then Q(a) as above
+template <bool QR>
 __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_collect_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   C51CollectLds& l = *reinterpret_cast<C51CollectLds*>(c51_smem);
@@ -378,7 +397,7 @@ __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_collect_kernel(DQNDev a
     dqn_block_trunk(wq, s.obs, l.h1s, l.h2s);
     if (tid < NA) l.ls[tid] = dqn_head_row(wq, NA, tid, l.h2s);
     __syncthreads();
-    c51_block_q(l.ls, s.qs, a.c51, nullptr);
+    dist_block_q<QR>(l.ls, s.qs, a.c51, nullptr);
   });
   if (tid == 0) *a.ctl = s.c;
 }
@@ -436,6 +455,57 @@ __global__ void __launch_bounds__(64 * C51_TD_WAVES) dqn_c51_td_kernel(DQNDev a)
     if constexpr (PER) {
       p.abs_td[b] = loss_j;
       p.tree[p.C + s] = (double)per_leaf(loss_j, p.eps, p.alpha);
+    }
+  }
+}
+
+// The TD launch of a quantile handle (crl_dqn_qr_create; dqn_qr.hpp): dqn_c51_td_kernel's split — one wave per sample, one lane per quantile,
+// ⌈k / C51_TD_WAVES⌉ blocks — around an N × N pair loss instead of a projection. Lane j reads its two rows of the a* net once; Q(a) = mean_i θ_i(a)
+// by two lane-ordered sums; a*; lane j forms T_j ONCE from target_net(x)[a*·N + j]; then lane i walks j ascending with θ_i and τ_i in registers
+// (qr_pair: T_j comes through a scalar register, nothing through LDS, no barrier, no atomics). It leaves dl where dqn_c51_bwd2_kernel /
+// dqn_c51_wgrad_kernel and their dueling counterparts read it, the targets T in proj, and sloss, sq, astar, td and the new PER leaf exactly as the
+// categorical kernel does, so everything behind this launch is that head's, dqn_c51_batch_tail included.
+template <bool PER>
+__global__ void __launch_bounds__(64 * C51_TD_WAVES) dqn_qr_td_kernel(DQNDev a) {
+#pragma clang fp contract(off)
+  if (!a.ctl->train_pending) return;
+  const PerDev& p = a.per;
+  const TgtDev& t = a.tgt;
+  const C51Dev& c = a.c51;
+  const int k = (int)a.cfg.batch_size, N = c.N, lane = threadIdx.x & 63, b = blockIdx.x * C51_TD_WAVES + (threadIdx.x >> 6);
+  if (b >= k) return;                                                        // whole waves leave: the wave functions below see all 64 lanes
+  const size_t plane = (size_t)2 * N * k;
+  const int s = a.idx[b], act = a.rb_action[s], r = lane < N ? lane : 0;     // a lane past N re-reads row 0 (in bounds) and is masked below
+  const double* Lt = c.L + plane + (size_t)2 * N * b;                        // target_net(x)
+  const double* Lx = t.double_q ? c.L + 2 * plane + (size_t)2 * N * b : Lt;   // the net a* is taken from
+  const double theta = c.L[(size_t)2 * N * b + act * N + r];                 // issued early: independent of everything up to the pair loop
+  const double x0 = lane < N ? Lx[r] : 0.0, x1 = lane < N ? Lx[N + r] : 0.0;
+  const double Q0 = qr_value(x0, N), Q1 = qr_value(x1, N);
+  const int astar = Q1 > Q0 ? 1 : 0;
+  double tn = astar ? x1 : x0, Qt = astar ? Q1 : Q0;
+  if (t.double_q) {
+    tn = lane < N ? Lt[astar * N + r] : 0.0;
+    Qt = qr_value(tn, N);
+  }
+  const int last = t.last[b];
+  const uint8_t term = a.rb_terminal[last];
+  const double R = t.nret[b], disc = t.ndisc[b];
+  const double T = qr_target(R, disc, tn, term);
+  double rho, G;
+  qr_pair(theta, T, c.kappa, N, lane, rho, G);
+  const double loss_s = c51_sum(rho);
+  const double ws = PER ? p.w[b] : 1.0;
+  if (lane < N) {
+    c.dl[(size_t)N * b + lane] = qr_dtheta(G, c.kappa, N, ws) / (double)k;
+    c.proj[(size_t)N * b + lane] = T;
+  }
+  if (lane == 0) {
+    c.sloss[b] = loss_s;
+    a.sq[b] = ws * loss_s;
+    t.astar[b] = astar; t.td[b] = tgt_td(R, disc, Qt, term);
+    if constexpr (PER) {
+      p.abs_td[b] = loss_s;
+      p.tree[p.C + s] = (double)per_leaf(loss_s, p.eps, p.alpha);
     }
   }
 }
@@ -506,6 +576,7 @@ __global__ void __launch_bounds__(1024) dqn_c51_adam_kernel(DQNDev a) {
 }
 
 // crl_dqn_q_values and crl_dqn_c51_probs on a C51 handle: dqn_q_kernel's trunk, the 2N logits, then Q(a) and / or the probabilities (N, 2, n)
+template <bool QR>   // QR: out_p receives the quantile locations (crl_dqn_qr_quantiles), Q(a) is their mean
 __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_q_kernel(const float* __restrict__ q, C51Dev c, const double* __restrict__ obs, int n,
                                                         double* __restrict__ out_q, double* __restrict__ out_p) {
 #pragma clang fp contract(off)
@@ -515,7 +586,7 @@ __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_c51_q_kernel(const float* _
   dqn_block_trunk(q, obs + (size_t)QD * b, h1s, h2s);
   if (tid < NA) ls[tid] = dqn_head_row(q, NA, tid, h2s);
   __syncthreads();
-  c51_block_q(ls, qs, c, out_p ? out_p + (size_t)NA * b : nullptr);
+  dist_block_q<QR>(ls, qs, c, out_p ? out_p + (size_t)NA * b : nullptr);
   if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
 }
 
@@ -576,6 +647,7 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_eval_kernel(const flo
 // waves' strips live in dynamic LDS. Lane i < N forms the logits of atom i for both actions (rows i and N + i: two chains side by side), then the two
 // softmaxes and expectations run wave-wide (dqn_c51.hpp: no LDS in them); Q(a) has the bits crl_dqn_q_values gives.
 struct C51EvalWaveLds { double h1[QH1], h2[QH2]; };
+template <bool QR>   // QR: the two rows of lane i are quantile locations and Q(a) their lane-ordered mean (qr_value): the functor's last lines differ
 __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_c51_eval_kernel(const float* __restrict__ q, C51Dev c, int max_steps, double gamma,
                                                                            ValueEvalArgs ev) {
 #pragma clang fp contract(off)
@@ -598,10 +670,15 @@ __global__ void __launch_bounds__(64 * DQN_EVAL_WAVES) dqn_c51_eval_kernel(const
     wave_lds_fence();
     double l0, l1, p0, p1, lp;
     eval_head_pair(wq, 2 * N, r0, r1, h2w, l0, l1);
-    c51_softmax(l0, N, lane, p0, lp);
-    q0 = c51_expect(p0, c.v_min, delta, lane);
-    c51_softmax(l1, N, lane, p1, lp);
-    q1 = c51_expect(p1, c.v_min, delta, lane);
+    if constexpr (QR) {
+      q0 = qr_value(lane < N ? l0 : 0.0, N);
+      q1 = qr_value(lane < N ? l1 : 0.0, N);
+    } else {
+      c51_softmax(l0, N, lane, p0, lp);
+      q0 = c51_expect(p0, c.v_min, delta, lane);
+      c51_softmax(l1, N, lane, p1, lp);
+      q1 = c51_expect(p1, c.v_min, delta, lane);
+    }
   });
 }
 
@@ -642,6 +719,7 @@ __device__ __forceinline__ void duel_block_forward(const float* W, const DuelOff
 }
 
 // dqn_c51_collect_kernel with the dueling heads: the whole net in dynamic LDS (84.7 KB at R = 1, 149.0 KB at R = 64)
+template <bool QR>
 __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_collect_kernel(DQNDev a) {
 #pragma clang fp contract(off)
   DuelCollectLds& l = *reinterpret_cast<DuelCollectLds*>(c51_smem);
@@ -657,7 +735,7 @@ __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_collect_kernel(DQNDev 
   dqn_collect_loop(a, s, [&] {
 #pragma clang fp contract(off)
     duel_block_forward(wq, o, R, s.obs, l.h1s, l.h2s, l.raw, l.ls);
-    if (a.c51.on) c51_block_q(l.ls, s.qs, a.c51, nullptr);
+    if (QR || a.c51.on) dist_block_q<QR>(l.ls, s.qs, a.c51, nullptr);
     else {
       if (tid < QA) s.qs[tid] = l.ls[tid];
       __syncthreads();
@@ -815,6 +893,7 @@ __global__ void __launch_bounds__(256) dqn_noisy_noise_kernel(DQNDev a, uint64_t
 
 // crl_dqn_q_values, crl_dqn_c51_probs and crl_dqn_dueling_streams on a dueling handle: the block's forward, then whichever outputs are asked for.
 // out_q (2, n); out_p (N, 2, n); out_v (R, n); out_a (R, 2, n), i fastest
+template <bool QR>
 __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_q_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, const double* __restrict__ obs, int n,
                                                          double* __restrict__ out_q, double* __restrict__ out_p, double* __restrict__ out_v,
                                                          double* __restrict__ out_a) {
@@ -825,8 +904,8 @@ __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_q_kernel(const float* 
   duel_block_forward(q, duel_off(R), R, obs + (size_t)QD * b, h1s, h2s, raw, ls);
   if (out_v && tid < R) out_v[(size_t)R * b + tid] = raw[tid];
   if (out_a) for (int r = tid; r < 2 * R; r += DQN_OBS_BLOCK) out_a[(size_t)2 * R * b + r] = raw[R + r];
-  if (c.on) {
-    c51_block_q(ls, qs, c, out_p ? out_p + (size_t)2 * R * b : nullptr);
+  if (QR || c.on) {
+    dist_block_q<QR>(ls, qs, c, out_p ? out_p + (size_t)2 * R * b : nullptr);
     if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = qs[tid];
   } else if (out_q && tid < QA) out_q[(size_t)QA * b + tid] = ls[tid];
 }
@@ -834,6 +913,7 @@ __global__ void __launch_bounds__(DQN_OBS_BLOCK) dqn_duel_q_kernel(const float* 
 // dqn_c51_eval_kernel with the dueling heads: one wave per env, ONE staging barrier, the net (up to 149.0 KB) and the waves' strips in dynamic LDS.
 // The 168 hidden units are three per lane (lane, lane + 64, lane + 128: three chains side by side); lane i < R forms V_i, A_{0,i} and A_{1,i} side by
 // side and combines them, then on a categorical handle the two softmaxes and expectations run wave-wide. With R = 1 every lane forms row 0 alike.
+template <bool QR>
 __global__ void __launch_bounds__(64 * DUEL_EVAL_WAVES) dqn_duel_eval_kernel(const float* __restrict__ q, DuelDev du, C51Dev c, int max_steps, double gamma,
                                                                              ValueEvalArgs ev) {
 #pragma clang fp contract(off)
@@ -846,7 +926,7 @@ __global__ void __launch_bounds__(64 * DUEL_EVAL_WAVES) dqn_duel_eval_kernel(con
   if (env >= ev.n) return;
   double* const h1w = wl[w].h1;
   double* const h2w = wl[w].h2;
-  const double delta = c.on ? c51_delta(c.v_min, c.v_max, R) : 0.0;
+  const double delta = !QR && c.on ? c51_delta(c.v_min, c.v_max, R) : 0.0;
   // the lane's three units of the two-stream layer: lane is a value unit, lane + 64 one of either stream, lane + 128 an advantage unit (lanes 0..39)
   const int ua = lane, ub = lane + 64, uc = lane + 128 < DUEL_U2 ? lane + 128 : lane;
   const auto wof = [&](int u) { return u >= QH2 ? o.W2a + u - QH2 : o.W2v + u; };
@@ -883,7 +963,11 @@ __global__ void __launch_bounds__(64 * DUEL_EVAL_WAVES) dqn_duel_eval_kernel(con
       a1 += (double)wq[o.W3a + R + r0 + 2 * R * kk] * ha;
     }
     duel_combine(av + (double)wq[o.b3v + r0], a0 + (double)wq[o.b3a + r0], a1 + (double)wq[o.b3a + R + r0], q0, q1);
-    if (c.on) {                          // q0, q1 are the logits of atom `lane`
+    if constexpr (QR) {                  // q0, q1 are the locations of quantile `lane`
+      const double e0 = qr_value(lane < R ? q0 : 0.0, R);
+      q1 = qr_value(lane < R ? q1 : 0.0, R);
+      q0 = e0;
+    } else if (c.on) {                   // q0, q1 are the logits of atom `lane`
       double p0, p1, lp;
       c51_softmax(q0, R, lane, p0, lp);
       const double e0 = c51_expect(p0, c.v_min, delta, lane);
@@ -909,9 +993,10 @@ struct crl_dqn {
   double* probe_tree = nullptr; int32_t* probe_idx = nullptr; double* probe_w = nullptr;   // crl_dqn_per_probe's scratch
   bool tgt = false;                                                 // made by crl_dqn_create_with
   void* walk_scratch = nullptr;                                     // crl_dqn_nstep_probe's scratch
-  bool c51 = false;                                                 // made by crl_dqn_c51_create
+  bool c51 = false;                                                 // the head has 2N rows: made with crl_dqn_c51_options, or with crl_dqn_qr_options (then qr holds too)
+  bool qr = false;                                                  // made by crl_dqn_qr_create: the 2N rows are quantile locations (d.c51.kind == HEAD_QR)
   size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, 10764 + 85·2N on a C51 handle, 20928 + 255·R on a dueling one
-  void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's scratch
+  void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's / crl_dqn_qr_loss_probe's scratch
   bool duel = false;                                                // made by crl_dqn_dueling_create: P = 20928 + 255·R, R = 1 or n_atoms
   bool noisy = false;                                               // made by crl_dqn_noisy_create: P is still the twin's count = the images' length
   size_t n_params = (size_t)crl::QP;                                // what crl_dqn_param_count reports and write / read take: P, or 2P (mu, sigma) on a noisy handle
@@ -951,19 +1036,21 @@ using DQNKernel = void (*)(DQNDev);
 // the sampling launch and the TD launch come as a uniform-replay and a PER instantiation
 static DQNKernel by_replay(const DQNDev& d, DQNKernel uniform, DQNKernel per) { return d.per.on ? per : uniform; }
 static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
-  const bool duel = d.duel.on, c51 = d.c51.on, tgt = d.tgt.on;
+  const bool duel = d.duel.on, c51 = d.c51.on, qr = d.c51.kind == HEAD_QR, tgt = d.tgt.on;   // qr implies c51: the head kind is decided here, once per launch
   const int nets = d.nets, U2 = duel ? DUEL_U2 : QH2, P = duel ? d.duel.P : c51 ? d.c51.P : QP;
   const int rows3 = duel ? d.duel.R : c51 ? 2 * d.c51.N : QA;   // threads per sample and pass of the fwd3 slot
   const auto launch = [&](DQNKernel kernel, int threads, int block, size_t lds = 0) {   // ⌈threads / block⌉ blocks
     hipLaunchKernelGGL(kernel, dim3((threads + block - 1) / block), dim3(block), lds, st, d);
   };
-  launch(duel ? dqn_duel_collect_kernel : c51 ? dqn_c51_collect_kernel : dqn_collect_kernel, DQN_OBS_BLOCK, DQN_OBS_BLOCK,
-         duel ? duel_collect_lds(P) : c51 ? c51_collect_lds(P) : 0);
+  launch(duel ? (qr ? dqn_duel_collect_kernel<true> : dqn_duel_collect_kernel<false>)
+              : c51 ? (qr ? dqn_c51_collect_kernel<true> : dqn_c51_collect_kernel<false>) : dqn_collect_kernel,
+         DQN_OBS_BLOCK, DQN_OBS_BLOCK, duel ? duel_collect_lds(P) : c51 ? c51_collect_lds(P) : 0);
   launch(tgt ? by_replay(d, dqn_tgt_sample_kernel<false>, dqn_tgt_sample_kernel<true>) : by_replay(d, dqn_sample_kernel, dqn_per_sample_kernel), 1024, 1024);
   launch(dqn_fwd1_kernel, nets * QH1 * k, 256);
   launch(duel ? dqn_duel_fwd2_kernel : dqn_fwd2_kernel, nets * U2 * k, 256);
   launch(duel ? dqn_duel_fwd3_kernel : c51 ? dqn_c51_fwd3_kernel : dqn_fwd3_kernel, nets * rows3 * k, 256);
-  if (c51) launch(by_replay(d, dqn_c51_td_kernel<false>, dqn_c51_td_kernel<true>), 64 * k, 64 * C51_TD_WAVES);   // one wave per sample
+  if (qr) launch(by_replay(d, dqn_qr_td_kernel<false>, dqn_qr_td_kernel<true>), 64 * k, 64 * C51_TD_WAVES);           // one wave per sample
+  else if (c51) launch(by_replay(d, dqn_c51_td_kernel<false>, dqn_c51_td_kernel<true>), 64 * k, 64 * C51_TD_WAVES);   // one wave per sample
   else launch(tgt ? by_replay(d, dqn_td_kernel<true, false>, dqn_td_kernel<true, true>) : by_replay(d, dqn_td_kernel<false, false>, dqn_td_kernel<false, true>),
               1024, 1024);
   launch(duel ? dqn_duel_bwd2_kernel : c51 ? dqn_c51_bwd2_kernel : dqn_bwd2_kernel, U2 * k, 256);
@@ -975,10 +1062,12 @@ static void enqueue_cycle(hipStream_t st, const DQNDev& d, int k) {
   if (CRL_NOISY_SPLIT_TAIL && d.noisy.on) launch(dqn_noisy_materialise_kernel, P, 256);
 }
 
-// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create, crl_dqn_dueling_create and crl_dqn_noisy_create: one body; `per` is null for uniform replay,
-// `tgt` for the 1-step max target of dqn.jl, `c51` for the scalar head; `duel` splits layers 2 and 3 into a value and an advantage stream
+// crl_dqn_create, crl_dqn_per_create, crl_dqn_create_with, crl_dqn_c51_create, crl_dqn_dueling_create, crl_dqn_noisy_create and crl_dqn_qr_create: one body; `per` is null for uniform replay,
+// `tgt` for the 1-step max target of dqn.jl, `c51` for the scalar head; `duel` splits layers 2 and 3 into a value and an advantage stream. `qr` makes
+// the 2N-row head a quantile one: crl_dqn_qr_create passes it together with a c51 whose n_atoms is n_quantiles (the support is never read).
 static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out,
-                          const crl_dqn_c51_options* c51 = nullptr, bool duel = false, const crl_dqn_noisy_options* noisy = nullptr) {
+                          const crl_dqn_c51_options* c51 = nullptr, bool duel = false, const crl_dqn_noisy_options* noisy = nullptr,
+                          const crl_dqn_qr_options* qr = nullptr) {
   if (cfg->batch_size < 1 || cfg->batch_size > DQN_MAX_BATCH) { set_error("crl_dqn_create: batch_size must be in 1..1024"); return 1; }
   if (cfg->buffer_size < cfg->batch_size || cfg->buffer_size > DQN_MAX_CAP) { set_error("crl_dqn_create: buffer_size must be in batch_size..65536"); return 1; }
   if (cfg->min_buff_size < cfg->batch_size) {
@@ -1039,10 +1128,12 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     C51Dev& c = d.c51;
     const size_t N = (size_t)c51->n_atoms;
     c.on = 1; c.N = c51->n_atoms; c.P = (int32_t)NP; c.v_min = c51->v_min; c.v_max = c51->v_max;
+    if (qr) { h->qr = true; c.kind = HEAD_QR; c.kappa = qr->kappa; }
     rc |= qalloc(&c.L, nets * 2 * N * k); rc |= qalloc(&c.dl, N * k); rc |= qalloc(&c.proj, N * k); rc |= qalloc(&c.sloss, k);
     // the net in LDS passes the 64 KB a launch gets without asking at N >= 36; the CU has 160 KB. Set for the largest head (set_dyn_lds).
     constexpr int PMAX = QoW3 + 85 * 2 * C51_MAX_ATOMS;
-    if (!rc && !(set_dyn_lds(dqn_c51_collect_kernel, c51_collect_lds(PMAX)) && set_dyn_lds(dqn_c51_eval_kernel, c51_eval_lds(PMAX)))) {
+    if (!rc && !(qr ? set_dyn_lds(dqn_c51_collect_kernel<true>, c51_collect_lds(PMAX)) && set_dyn_lds(dqn_c51_eval_kernel<true>, c51_eval_lds(PMAX))
+                    : set_dyn_lds(dqn_c51_collect_kernel<false>, c51_collect_lds(PMAX)) && set_dyn_lds(dqn_c51_eval_kernel<false>, c51_eval_lds(PMAX)))) {
       set_error("crl_dqn_c51_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
@@ -1051,7 +1142,8 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     d.duel.on = 1; d.duel.R = c51 ? c51->n_atoms : 1; d.duel.P = (int32_t)NP;
     // both kernels keep the whole net in LDS, past the 64 KB a launch gets without asking at every R; set for the largest head, as above
     constexpr int PMAX = duel_param_count(DUEL_MAX_R);
-    if (!rc && !(set_dyn_lds(dqn_duel_collect_kernel, duel_collect_lds(PMAX)) && set_dyn_lds(dqn_duel_eval_kernel, duel_eval_lds(PMAX)))) {
+    if (!rc && !(qr ? set_dyn_lds(dqn_duel_collect_kernel<true>, duel_collect_lds(PMAX)) && set_dyn_lds(dqn_duel_eval_kernel<true>, duel_eval_lds(PMAX))
+                    : set_dyn_lds(dqn_duel_collect_kernel<false>, duel_collect_lds(PMAX)) && set_dyn_lds(dqn_duel_eval_kernel<false>, duel_eval_lds(PMAX)))) {
       set_error("crl_dqn_dueling_create: the device refused the dynamic LDS size of the collect / evaluation kernels"); rc = 1;
     }
   }
@@ -1116,7 +1208,12 @@ static int target_options_check(const char* who, const crl_dqn_target_options* t
 
 #define DQN_C51_GUARD(h, name)                                                                                           \
   DQN_GUARD(h);                                                                                                          \
-  if (!(h)->c51) { set_error(name ": the handle has a scalar head; crl_dqn_c51_create makes a categorical (C51) handle"); return 1; }
+  if (!(h)->c51) { set_error(name ": the handle has a scalar head; crl_dqn_c51_create makes a categorical (C51) handle"); return 1; } \
+  if ((h)->qr) { set_error(name ": the handle has a quantile head; crl_dqn_c51_create makes a categorical (C51) handle"); return 1; }
+
+#define DQN_QR_GUARD(h, name)                                                                                            \
+  DQN_GUARD(h);                                                                                                          \
+  if (!(h)->qr) { set_error(name ": the handle has no quantile head; crl_dqn_qr_create makes a quantile-regression (QR-DQN) handle"); return 1; }
 
 #define DQN_PER_GUARD(h, name)                                                                                           \
   DQN_GUARD(h);                                                                                                          \
@@ -1225,6 +1322,16 @@ static int dqn_stage(crl_dqn* h, size_t need) {
   return 0;
 }
 
+// the one-observation-per-block launch of a handle with a 2N-row or a dueling head: Q(a), the head's rows (probabilities or quantile locations), the
+// streams — whichever pointers are given; the head kind picks the instantiation
+static void launch_obs_kernel(crl_dqn* h, const double* so, int32_t n, double* out_q, double* out_rows, double* out_v, double* out_a) {
+  const dim3 grid((unsigned)n), block(DQN_OBS_BLOCK);
+  if (h->duel) hipLaunchKernelGGL(h->qr ? dqn_duel_q_kernel<true> : dqn_duel_q_kernel<false>, grid, block, 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51,
+                                  so, (int)n, out_q, out_rows, out_v, out_a);
+  else hipLaunchKernelGGL(h->qr ? dqn_c51_q_kernel<true> : dqn_c51_q_kernel<false>, grid, block, 0, h->stream, h->greedy_image(), h->d.c51, so, (int)n, out_q,
+                          out_rows);
+}
+
 int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double* value, double* adv) {
   DQN_GUARD(h);
   if (!h->duel) { set_error("crl_dqn_dueling_streams: the handle has one head; crl_dqn_dueling_create makes a dueling handle"); return 1; }
@@ -1236,8 +1343,7 @@ int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double
   double* so = static_cast<double*>(h->stage);
   double *sv = so + N * QD, *sa = sv + N * R;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n, (double*)nullptr,
-                     (double*)nullptr, sv, sa);
+  launch_obs_kernel(h, so, n, nullptr, nullptr, sv, sa);
   CRL_HIP_CHECK(hipGetLastError());
   if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, sv, N * R * 8, hipMemcpyDeviceToHost, h->stream));
   if (adv) CRL_HIP_CHECK(hipMemcpyAsync(adv, sa, N * 2 * R * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1252,6 +1358,74 @@ int32_t crl_dqn_param_count(crl_dqn* h, size_t* n) {
   return 0;
 }
 
+int32_t crl_dqn_qr_create(const crl_dqn_config* cfg, const crl_dqn_qr_options* qr, int32_t dueling, const crl_dqn_noisy_options* noisy,
+                          const crl_dqn_per_options* per, const crl_dqn_target_options* tgt, int32_t device, crl_dqn** out) {
+  if (!cfg || !qr || !out) { set_error("crl_dqn_qr_create: null argument (cfg, qr and out are required)"); return 1; }
+  *out = nullptr;
+  if (qr->n_quantiles < 2 || qr->n_quantiles > C51_MAX_ATOMS) { set_error("crl_dqn_qr_create: n_quantiles must be in 2..64"); return 1; }
+  if (!(qr->kappa > 0.0 && qr->kappa < 1e300)) { set_error("crl_dqn_qr_create: kappa must be finite and > 0"); return 1; }
+  if (dueling != 0 && dueling != 1) { set_error("crl_dqn_qr_create: dueling must be 0 or 1"); return 1; }
+  if (noisy && !(noisy->sigma0 >= 0.0 && noisy->sigma0 <= 10.0)) { set_error("crl_dqn_qr_create: sigma0 must be in 0..10"); return 1; }
+  if (per && per_options_check("crl_dqn_qr_create", per)) return 1;
+  crl_dqn_target_options t;
+  if (target_options_check("crl_dqn_qr_create", tgt, t)) return 1;
+  const crl_dqn_c51_options rows = {qr->n_quantiles, 0, 0.0, 0.0};   // the head's shape; a quantile head has no support
+  if (dqn_create(cfg, per, &t, device, out, &rows, dueling != 0, noisy, qr)) return 1;
+  if (noisy && (noisy_materialise(*out) || hipStreamSynchronize((*out)->stream) != hipSuccess)) {
+    set_error("crl_dqn_qr_create: the materialise launch failed"); crl_dqn_destroy(*out); *out = nullptr; return 1;
+  }
+  return 0;
+}
+
+int32_t crl_dqn_qr_quantiles(crl_dqn* h, const double* obs, int32_t n, double* theta) {
+  DQN_QR_GUARD(h, "crl_dqn_qr_quantiles");
+  if (!h->params_set) { set_error("crl_dqn_qr_quantiles: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !theta))) { set_error("crl_dqn_qr_quantiles: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  const size_t N = (size_t)n, NA = 2 * (size_t)h->d.c51.N;
+  if (dqn_stage(h, N * (QD + NA) * 8)) return 1;
+  double* so = static_cast<double*>(h->stage);
+  double* sp = so + N * QD;
+  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
+  launch_obs_kernel(h, so, n, nullptr, sp, nullptr, nullptr);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(theta, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_qr_read(crl_dqn* h, double* target, double* sample_loss) {
+  DQN_QR_GUARD(h, "crl_dqn_qr_read");
+  const size_t k = (size_t)h->cfg.batch_size, N = (size_t)h->d.c51.N;
+  if (target) CRL_HIP_CHECK(hipMemcpyAsync(target, h->d.c51.proj, k * N * 8, hipMemcpyDeviceToHost, h->stream));
+  if (sample_loss) CRL_HIP_CHECK(hipMemcpyAsync(sample_loss, h->d.c51.sloss, k * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_dqn_qr_loss_probe(crl_dqn* h, const double* theta, const double* target, int32_t k, double* loss, double* dtheta) {
+  DQN_QR_GUARD(h, "crl_dqn_qr_loss_probe");
+  if (!theta || !target || !loss || !dtheta) { set_error("crl_dqn_qr_loss_probe: null argument"); return 1; }
+  if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_qr_loss_probe: k must be in 1..1024"); return 1; }
+  // one allocation: theta | target | dtheta [1024·64] f64 each | loss [1024] f64
+  constexpr size_t rows = (size_t)DQN_MAX_BATCH * C51_MAX_ATOMS * 8, total = 3 * rows + (size_t)DQN_MAX_BATCH * 8;
+  if (!h->proj_scratch) CRL_HIP_CHECK(hipMalloc(&h->proj_scratch, total));
+  char* base = static_cast<char*>(h->proj_scratch);
+  double *dTh = reinterpret_cast<double*>(base), *dT = reinterpret_cast<double*>(base + rows), *dG = reinterpret_cast<double*>(base + 2 * rows),
+         *dL = reinterpret_cast<double*>(base + 3 * rows);
+  const C51Dev& c = h->d.c51;
+  const size_t K = (size_t)k, N = (size_t)c.N;
+  CRL_HIP_CHECK(hipMemcpyAsync(dTh, theta, K * N * 8, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dT, target, K * N * 8, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dqn_qr_loss_probe_kernel, dim3((unsigned)((k + C51_TD_WAVES - 1) / C51_TD_WAVES)), dim3(64 * C51_TD_WAVES), 0, h->stream,
+                     (const double*)dTh, (const double*)dT, (int)k, (int)c.N, c.kappa, dL, dG);
+  CRL_HIP_CHECK(hipGetLastError());
+  CRL_HIP_CHECK(hipMemcpyAsync(loss, dL, K * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(dtheta, dG, K * N * 8, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* probs) {
   DQN_C51_GUARD(h, "crl_dqn_c51_probs");
   if (!h->params_set) { set_error("crl_dqn_c51_probs: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
@@ -1262,9 +1436,7 @@ int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* prob
   double* so = static_cast<double*>(h->stage);
   double* sp = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n,
-                                  (double*)nullptr, sp, (double*)nullptr, (double*)nullptr);
-  else hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.c51, (const double*)so, n, (double*)nullptr, sp);
+  launch_obs_kernel(h, so, n, nullptr, sp, nullptr, nullptr);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
   CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1527,9 +1699,7 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   double* so = static_cast<double*>(h->stage);
   double* sq = so + N * QD;
   CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.duel, h->d.c51, (const double*)so, n, sq,
-                                  (double*)nullptr, (double*)nullptr, (double*)nullptr);
-  else if (h->c51) hipLaunchKernelGGL(dqn_c51_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), h->d.c51, (const double*)so, n, sq, (double*)nullptr);
+  if (h->duel || h->c51) launch_obs_kernel(h, so, n, sq, nullptr, nullptr, nullptr);
   else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), (const double*)so, n, sq);
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1547,9 +1717,9 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
   if (value_eval_scratch(h->eval, cfg, ev)) return 1;
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
   const dim3 grid((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), block(64 * DQN_EVAL_WAVES);
-  if (h->duel) hipLaunchKernelGGL(dqn_duel_eval_kernel, dim3((unsigned)((ev.n + DUEL_EVAL_WAVES - 1) / DUEL_EVAL_WAVES)), dim3(64 * DUEL_EVAL_WAVES),
+  if (h->duel) hipLaunchKernelGGL(h->qr ? dqn_duel_eval_kernel<true> : dqn_duel_eval_kernel<false>, dim3((unsigned)((ev.n + DUEL_EVAL_WAVES - 1) / DUEL_EVAL_WAVES)), dim3(64 * DUEL_EVAL_WAVES),
                                   duel_eval_lds((int)h->P), h->stream, h->greedy_image(), h->d.duel, h->d.c51, (int)h->cfg.max_steps, h->cfg.gamma, ev);
-  else if (h->c51) hipLaunchKernelGGL(dqn_c51_eval_kernel, grid, block, c51_eval_lds((int)h->P), h->stream, h->greedy_image(), h->d.c51,
+  else if (h->c51) hipLaunchKernelGGL(h->qr ? dqn_c51_eval_kernel<true> : dqn_c51_eval_kernel<false>, grid, block, c51_eval_lds((int)h->P), h->stream, h->greedy_image(), h->d.c51,
                                  (int)h->cfg.max_steps, h->cfg.gamma, ev);
   else hipLaunchKernelGGL(dqn_eval_kernel, grid, block, 0, h->stream, h->greedy_image(), (int)h->cfg.max_steps, h->cfg.gamma, ev);
   CRL_HIP_CHECK(hipGetLastError());

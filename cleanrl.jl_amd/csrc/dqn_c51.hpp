@@ -17,9 +17,12 @@ namespace crl {
 constexpr int C51_MAX_ATOMS = 64;      // a lane owns an atom
 constexpr int C51_TD_WAVES = 4;        // samples per block of the TD kernel: one wave per SIMD, ⌈k / 4⌉ blocks
 
+constexpr int HEAD_C51 = 0, HEAD_QR = 1;   // C51Dev.kind: what the 2N rows are — logits over N atoms, or N quantile locations (dqn_qr.hpp)
+
 struct C51Dev {
-  int32_t on, N, P, pad;               // P = 10764 + 85·2N parameters
+  int32_t on, N, P, kind;              // P = 10764 + 85·2N parameters; kind is decided once per handle
   double v_min, v_max;
+  double kappa;                        // HEAD_QR: the Huber threshold; v_min, v_max are unused there, and proj holds the targets T_j
   double* L;                           // [nets][k][2N] logits, row a·N + i = atom i of action a
   double *dl, *proj;                   // [k][N] cotangent on the taken action's logits, projected target m
   double* sloss;                       // [k] loss_j

@@ -110,6 +110,31 @@ def _check_c51(dist):
 
 
 @dataclasses.dataclass
+class QROptions:
+    """The quantile-regression value distribution of Dabney et al. 2018 (QR-DQN; crl_dqn_qr_options) — not in dqn.jl, so not in DQNConfig: the critic
+    learns where n_quantiles (2..64) fixed quantile fractions of the return lie, under the quantile Huber loss with threshold kappa. Unlike
+    C51Options it states no support, so it stays right when max_steps or gamma change. It needs a lagging target: with DQNConfig's default
+    target_net_freq = 100 (ten updates between hard copies) and the 1-step max target its top quantiles run away and the agent does not learn
+    CartPole; target_net_freq = 1000, or DQNTargetOptions(3, True), does (profiles/qr_learn.json)."""
+    n_quantiles: int = 51
+    kappa: float = 1.0
+
+
+def _check_dist(dist):
+    """→ the C51Options or QROptions, validated before the library is touched"""
+    if isinstance(dist, C51Options):
+        return _check_c51(dist)
+    if not isinstance(dist, QROptions):
+        raise TypeError(f"dist must be a C51Options, a QROptions or None, got {type(dist).__name__}")
+    n, v = dist.n_quantiles, dist.kappa
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (2 <= n <= 64):
+        raise ValueError(f"QROptions.n_quantiles must be an integer in 2..64, got {n!r}")
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not (v > 0.0):
+        raise ValueError(f"QROptions.kappa must be finite and > 0, got {v!r}")
+    return dist
+
+
+@dataclasses.dataclass
 class NoisyOptions:
     """Noisy linear layers (NoisyNets, Fortunato et al. 2018; crl_dqn_noisy_options) — not in dqn.jl, so not in DQNConfig: every dense layer learns
     mu and sigma per parameter and acts on mu + sigma·eps with factorised Gaussian eps, redrawn after every update; sigma starts at sigma0 / sqrt(in).
@@ -211,7 +236,9 @@ class DQNAgent:
         self.config = config
         self.noisy = None if noisy is None else _check_noisy(noisy)
         self.dueling = bool(dueling)
-        self.dist = None if dist is None else _check_c51(dist)
+        self.dist = None if dist is None else _check_dist(dist)
+        qr = isinstance(self.dist, QROptions)
+        rows = None if self.dist is None else int(self.dist.n_quantiles if qr else self.dist.n_atoms)   # per action: the head has 2·rows of them
         self.per = None if per is None else _check_per(per, config)
         self.target = None if target is None else _check_target(target)
         self.crl_cfg = L.CrlDQNConfig(int(config.log_frequencey), int(config.total_timesteps), int(config.buffer_size),
@@ -223,15 +250,15 @@ class DQNAgent:
                                                                                                       float(p.beta_end), float(p.beta_duration),
                                                                                                       float(p.eps)),
                                   target=None if self.target is None else L.CrlDQNTargetOptions(int(self.target.n_step), int(self.target.double_q)),
-                                  c51=None if self.dist is None else L.CrlDQNC51Options(int(self.dist.n_atoms), 0, float(self.dist.v_min),
-                                                                                        float(self.dist.v_max)),
+                                  c51=None if self.dist is None or qr else L.CrlDQNC51Options(rows, 0, float(self.dist.v_min), float(self.dist.v_max)),
+                                  qr=L.CrlDQNQROptions(rows, 0, float(self.dist.kappa)) if qr else None,
                                   dueling=self.dueling, noisy=None if self.noisy is None else L.CrlDQNNoisyOptions(float(self.noisy.sigma0)))
         if params is None and self.noisy is not None:
-            params = make_nn_noisy(init_seed, self.noisy.sigma0, self.dueling, None if self.dist is None else self.dist.n_atoms)
+            params = make_nn_noisy(init_seed, self.noisy.sigma0, self.dueling, rows)
         elif params is None and self.dueling:
-            params = make_nn_dueling(init_seed, None if self.dist is None else self.dist.n_atoms)
+            params = make_nn_dueling(init_seed, rows)
         elif params is None:
-            params = make_nn(init_seed) if self.dist is None else make_nn_c51(init_seed, self.dist.n_atoms)
+            params = make_nn(init_seed) if self.dist is None else make_nn_c51(init_seed, rows)   # the quantile head has the categorical head's shape
         self.handle.write_params(params)
 
     def close(self):
@@ -261,7 +288,7 @@ def noisy_sigma(agent):
     q, _ = agent.handle.read_params()
     sigma = q[q.size // 2:]
     out, at = [], 0
-    for i, o in noisy_layers(agent.dueling, None if agent.dist is None else agent.dist.n_atoms):
+    for i, o in noisy_layers(agent.dueling, None if agent.dist is None else getattr(agent.dist, "n_quantiles", None) or agent.dist.n_atoms):
         out.append(float(np.abs(sigma[at:at + o * i]).mean())); at += o * i
         out.append(float(np.abs(sigma[at:at + o]).mean())); at += o
     return out
@@ -272,7 +299,7 @@ def _eval_record(global_step, report):
                                                        eval_q_bias=report["q_bias_mean"], global_step=global_step))
 
 
-def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist: C51Options = None, dueling=False, noisy: NoisyOptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
+def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptions = None, dist=None, dueling=False, noisy: NoisyOptions = None, *, device=0, seed=0x5EED, params=None, chunk=10_000, eval_every=0, eval_envs=256,
         eval_episodes=1, **logger_kw):
     """dqn.jl:34-120. One library call per `chunk` env steps; the "CleanRL" logger receives "Episode Statistics"
     (episode_return, episode_length, global_step, ϵ, steps_per_sec; dqn.jl:88) and "Training Statistics" (loss; dqn.jl:116).
@@ -284,7 +311,8 @@ def dqn(config: DQNConfig = None, per: PEROptions = None, target: DQNTargetOptio
     DQNTargetOptions) forms the TD target from n-step returns and / or with double Q-learning (crl_dqn_create_with), with either replay; the log records
     are unchanged, and None (default) is dqn.jl's 1-step max. `dist` (a C51Options) makes the critic categorical (crl_dqn_c51_create), with either
     replay and any target options: "Training Statistics".loss is then the cross-entropy against the projected target distribution, and the evaluation
-    record's eval_q_bias is that of the expected value. None (default) is the scalar critic, bit for bit what it was. `dueling=True` splits layers 2 and 3 into a value and an
+    record's eval_q_bias is that of the expected value; a QROptions makes it a quantile-regression critic instead (crl_dqn_qr_create), whose loss is the
+    quantile Huber loss and whose value is the mean of the quantile locations. None (default) is the scalar critic, bit for bit what it was. `dueling=True` splits layers 2 and 3 into a value and an
     advantage stream (crl_dqn_dueling_create), with either head, either replay and any target options; the records are unchanged, and False (default)
     is the one-headed net, bit for bit what it was. `noisy` (a NoisyOptions) makes every dense layer a noisy one (crl_dqn_noisy_create), with every
     option above; the records are unchanged (ϵ is logged as configured: set epsilon_start = epsilon_end = 0 to explore by the noise alone), evaluation

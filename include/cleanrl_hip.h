@@ -818,6 +818,53 @@ int32_t crl_dqn_noisy_noise_count(crl_dqn* h, size_t* n);
  * builds its tables with. n must be crl_dqn_noisy_noise_count's. */
 int32_t crl_dqn_noisy_noise(crl_dqn* h, uint64_t gen, int32_t net, float* xi, size_t n);
 
+/* -----------------------------------------------------------------------------------------------------
+ * Quantile-regression DQN (QR-DQN, Dabney et al. 2018) — no reference counterpart. A handle made by crl_dqn_qr_create learns, per action, WHERE N
+ * fixed quantile fractions of the return distribution lie: a distributional critic with no support to state (no v_min / v_max) and no projection.
+ * The head has the categorical head's shape, W3(2N, 84) b3(2N), row a·N + i = quantile i of action a, so the parameter count (10764 + 85·2N, or the
+ * dueling / noisy count with n_atoms = n_quantiles), the layout and crl_dqn_c51_make_nn's rule carry over; crl_dqn_param_count, write / read / init
+ * params, crl_dqn_run, crl_dqn_evaluate, crl_dqn_status_read and crl_dqn_target_read work as on the categorical twin, the crl_dqn_per_* calls with
+ * per != NULL, crl_dqn_dueling_streams with dueling = 1, crl_dqn_noisy_weights / crl_dqn_noisy_noise with noisy != NULL. The cycle stays ten launches
+ * (eleven with noisy layers; csrc/dqn_qr.hpp, csrc/dqn.hip: dqn_qr_td_kernel takes the TD slot, everything behind it reads the cotangent dl as it does
+ * on a categorical handle). crl_dqn_q_values returns Q(a), (2, n); crl_dqn_evaluate acts greedily on those bits. The crl_dqn_c51_* calls fail on such
+ * a handle with a message naming crl_dqn_c51_create; the crl_dqn_qr_* calls below fail on every other handle with a message naming crl_dqn_qr_create.
+ * Every other creator keeps every bit of its behaviour.
+ *
+ * All Float64, one operation per written operator, no contraction; every Σ starts from 0.0 and runs in ascending index order. Nothing here is
+ * transcendental (+ − × ÷ |·| and comparisons), so under uniform replay a whole run has no rounding freedom:
+ *   Fractions  τ_i = ((double)i + 0.5) / (double)N,  i = 0..N−1
+ *   Value      Q(a) = (Σ_i θ_i(a)) / (double)N;  greedy = the first maximum (Q(1) > Q(0) ? 1 : 0) — in collect, in evaluation and for a*
+ *   Target     R, disc, last from the n-step walk above (n_step = 1: R = reward, disc = gamma, last = idx);  x = next_state[last];
+ *              a* = the first maximum of Q over q_net(x) under double_q, else over target_net(x);  θ'_j = target_net(x)[a*·N + j];
+ *              T_j = R + ((disc · θ'_j) · (1.0 − (double)terminal[last]))
+ *   Pair       θ_i = q_net(state)[action·N + i];  u = T_j − θ_i;  au = |u|;
+ *              h  = au <= κ ? (0.5 · u) · u : κ · (au − 0.5 · κ)
+ *              c  = au <= κ ? u : (u < 0.0 ? −κ : κ)
+ *              wt = |τ_i − (u < 0.0 ? 1.0 : 0.0)|
+ *   Loss       ρ_i = (Σ_j (wt · h) / κ, j ascending) / (double)N;   loss_s = Σ_i ρ_i  (>= 0 exactly);
+ *              loss = (Σ_s w_s · loss_s, in sample order) / (double)k,  w_s = 1.0 under uniform replay — what crl_dqn_run logs and last_loss holds
+ *   Cotangent  G_i = Σ_j wt · c (j ascending);  dl_i = ((w_s · (−(G_i / κ))) / (double)N) / (double)k on the taken action's rows; the other action's
+ *              rows get exactly 0.0
+ *   PER        the priority input is loss_s, as on a categorical handle (abs_td holds it)
+ * This is the paper's ρ^κ_τ divided by κ (its eq. 10); at κ = 1 it is what the common implementations compute. The indicator is constant in the
+ * derivative. Backward, weight gradients, the Float32 projection and Adam are the categorical head's text with dl above; dueling combines rows as it
+ * does for logits, θ_i(a) = V_i + (A_i(a) − mean_a A_i(a)), R = N. crl_dqn_target_read's td is R + ((disc · Q_target(x)[a*]) · (1 − terminal[last])),
+ * as on a categorical handle; it enters nothing.
+ * Errors of crl_dqn_qr_create: cfg, qr or out NULL; n_quantiles outside 2..64 (a wavefront's lane owns a quantile); kappa not finite or <= 0; dueling
+ * not 0 or 1; sigma0 outside 0..10; bad per or tgt options; crl_dqn_create's — each names the field.
+ * ----------------------------------------------------------------------------------------------------- */
+typedef struct crl_dqn_qr_options { int32_t n_quantiles; int32_t pad; double kappa; } crl_dqn_qr_options;   /* 16 bytes; n_quantiles 2..64, kappa finite and > 0 */
+int32_t crl_dqn_qr_create(const crl_dqn_config* cfg, const crl_dqn_qr_options* qr, int32_t dueling /* 0 | 1 */, const crl_dqn_noisy_options* noisy /* NULL = off */,
+                          const crl_dqn_per_options* per /* NULL = uniform */, const crl_dqn_target_options* tgt /* NULL = {1, 0} */, int32_t device, crl_dqn** out);
+/* the quantile locations of q_net(obs) for n observations (4, n) → (N, 2, n), quantile fastest; crl_dqn_q_values is their ascending mean, bit for
+ * bit. The noise is off on a noisy handle. */
+int32_t crl_dqn_qr_quantiles(crl_dqn* h, const double* obs, int32_t n, double* theta);
+/* the last completed update (zeros before the first): target[k·N] the T_j, sample by sample, j fastest; sample_loss[k] the loss_s. Either may be NULL. */
+int32_t crl_dqn_qr_read(crl_dqn* h, double* target, double* sample_loss);
+/* The pair loss alone with the handle's N and kappa on caller-supplied rows (training state untouched): the same __device__ function the update runs.
+ * theta (N, k), target (N, k) → loss[k] the loss_s, dtheta (N, k) = (−(G_i / κ)) / (double)N; 1 <= k <= 1024; no pointer may be NULL. */
+int32_t crl_dqn_qr_loss_probe(crl_dqn* h, const double* theta, const double* target, int32_t k, double* loss, double* dtheta);
+
 /* =====================================================================================================
  * DDPG: src/algorithms/ddpg.jl on the GPU — the reference's one continuous-action algorithm. Networks of ddpg.jl:19-37 with hidden width 64,
  * Float32 weights and Float64 arithmetic: actor Dense(obs,64,tanh_fast) → Dense(64,64,tanh_fast) → Dense(64,act,tanh_fast) → x·2 + randn(act)·

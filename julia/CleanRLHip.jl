@@ -570,6 +570,17 @@ Base.@kwdef struct C51Options
 end
 struct CrlDQNC51Options; n_atoms::Int32; pad::Int32; v_min::Float64; v_max::Float64; end                                     # crl_dqn_c51_options
 
+# The quantile-regression critic of Dabney et al. 2018 (QR-DQN; include/cleanrl_hip.h crl_dqn_qr_options) — not in dqn.jl, so not a DQNConfig field:
+# `dqn(config; dist = QROptions())`, with dueling, noisy, either replay and any target options. The head has the categorical head's shape
+# (Dense(84, 2·n_quantiles)) but holds quantile locations, states no support, and is trained by the quantile Huber loss with threshold kappa;
+# q_values returns their means. It needs a lagging target: raise target_net_freq above dqn.jl's 100 (or use 3-step double-Q targets) when it is used
+# alone (profiles/qr_learn.json). Like the rest of this file, not executed here.
+Base.@kwdef struct QROptions
+  n_quantiles::Int = 51
+  kappa::Float64 = 1.0
+end
+struct CrlDQNQROptions; n_quantiles::Int32; pad::Int32; kappa::Float64; end                                                  # crl_dqn_qr_options
+
 # Noisy linear layers (NoisyNets, Fortunato et al. 2018; include/cleanrl_hip.h crl_dqn_noisy_options) — not in dqn.jl, so not a DQNConfig field:
 # `dqn(config; noisy = NoisyOptions())`, with every other option. Every dense layer learns mu and sigma (the parameter vector is twice the twin's: mu,
 # then sigma; crl_dqn_param_count) and acts on mu + sigma·eps with factorised Gaussian eps, redrawn after every update; evaluation and q_values run with
@@ -586,7 +597,14 @@ function c51_probs(agent::DQNAgent, obs::AbstractMatrix{Float64}, n_atoms::Integ
   p
 end
 
-# q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64; the expected values on a C51 agent
+# crl_dqn_qr_quantiles: the quantile locations of q_net(obs) per action, (4, n) → (n_quantiles, 2, n); an error on every agent but a QROptions one
+function qr_quantiles(agent::DQNAgent, obs::AbstractMatrix{Float64}, n_quantiles::Integer)
+  o = Array(obs); n = size(o, 2); t = Array{Float64}(undef, n_quantiles, 2, n)
+  GC.@preserve o t check(ccall((:crl_dqn_qr_quantiles, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, n, t))
+  t
+end
+
+# q_net(obs) (dqn.jl:64) for observations (4, n) Float64 → (2, n) Float64; the expected values on a C51 agent, the quantile means on a QR agent
 function q_values(agent::DQNAgent, obs::AbstractMatrix{Float64})
   o = Array(obs); n = size(o, 2); q = Matrix{Float64}(undef, 2, n)
   GC.@preserve o q check(ccall((:crl_dqn_q_values, libcrl), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), agent.h, o, n, q))
@@ -612,7 +630,7 @@ function _default_dqn_init()
 end
 function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector{Float32}}=nothing, init=_default_dqn_init(), init_seed::Integer=0,
              chunk::Integer=10_000, make_logger=_default_make_logger(), eval_every::Integer=0, eval_envs::Integer=256, eval_episodes::Integer=1,
-             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options}=nothing,
+             per::Union{Nothing,PEROptions}=nothing, target::Union{Nothing,DQNTargetOptions}=nothing, dist::Union{Nothing,C51Options,QROptions}=nothing,
              dueling::Bool=false, noisy::Union{Nothing,NoisyOptions}=nothing)
   eval_every >= 0 || throw(ArgumentError("dqn: eval_every must be >= 0, got $eval_every"))
   make_logger === nothing || make_logger("dqn|$(config.run_name)")         # dqn.jl:35
@@ -622,7 +640,18 @@ function dqn(config; device=0, seed=UInt64(0x5EED), params::Union{Nothing,Vector
   h = Ref{Ptr{Cvoid}}(C_NULL)
   popt = per === nothing ? nothing :
          CrlDQNPEROptions(per.alpha, per.beta_start, per.beta_end, something(per.beta_duration, Float64(config.total_timesteps)), per.eps)
-  if noisy !== nothing      # noisy linear layers (crl_dqn_noisy_create) on top of any of the kinds below. Like the rest of this file, never executed.
+  if dist isa QROptions     # the quantile-regression critic (crl_dqn_qr_create): one creator for every composition. Like the rest of this file, never executed.
+    2 <= dist.n_quantiles <= 64 || throw(ArgumentError("dqn: dist.n_quantiles must be in 2..64, got $(dist.n_quantiles)"))
+    (isfinite(dist.kappa) && dist.kappa > 0.0) || throw(ArgumentError("dqn: dist.kappa must be finite and > 0, got $(dist.kappa)"))
+    qopt = Ref(CrlDQNQROptions(dist.n_quantiles, 0, dist.kappa))
+    nref = noisy === nothing ? C_NULL : Ref(CrlDQNNoisyOptions(noisy.sigma0))
+    pref = popt === nothing ? C_NULL : Ref(popt)
+    tref = target === nothing ? C_NULL : Ref(CrlDQNTargetOptions(target.n_step, target.double_q ? 1 : 0))
+    GC.@preserve qopt nref pref tref check(ccall((:crl_dqn_qr_create, libcrl), Int32,
+      (Ref{CrlDQNConfig}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}),
+      cfg, Base.unsafe_convert(Ptr{Cvoid}, qopt), dueling ? 1 : 0, nref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, nref),
+      pref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, pref), tref === C_NULL ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tref), device, h))
+  elseif noisy !== nothing  # noisy linear layers (crl_dqn_noisy_create) on top of any of the kinds below. Like the rest of this file, never executed.
     0.0 <= noisy.sigma0 <= 10.0 || throw(ArgumentError("dqn: noisy.sigma0 must be in 0..10, got $(noisy.sigma0)"))
     nopt = Ref(CrlDQNNoisyOptions(noisy.sigma0))
     copt = dist === nothing ? C_NULL : Ref(CrlDQNC51Options(dist.n_atoms, 0, dist.v_min, dist.v_max))

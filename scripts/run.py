@@ -12,6 +12,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py dqn --total_timesteps 50000 --per --per_alpha 0.6 --per_beta_start 0.4 --per_beta_end 1.0 --per_beta_duration 50000 --per_eps 1e-6   (prioritized replay; --per alone takes the defaults, beta_duration = total_timesteps)
     python scripts/run.py dqn --total_timesteps 50000 --double_q --n_step 3 [--per]   (double Q-learning and 3-step returns; either alone, both combine with --per)
     python scripts/run.py dqn --total_timesteps 50000 --c51 [--n_atoms 51 --v_min 0 --v_max 100] [--per] [--double_q --n_step 3]   (categorical C51 critic; combines with all of the above)
+    python scripts/run.py dqn --total_timesteps 50000 --qr [--n_quantiles 51 --kappa 1.0] [--dueling --noisy --per --double_q --n_step 3]   (quantile-regression critic, no support to state; not together with --c51)
     python scripts/run.py dqn --total_timesteps 50000 --noisy [--sigma0 0.5] [--dueling --c51 --per --double_q --n_step 3]   (noisy linear layers; epsilon_start / epsilon_end default to 0 with --noisy; with all the others: Rainbow)
     python scripts/run.py a2c --total_timesteps 100000 --eval_every 10000   (the same for the actor's argmax and the critic's bias)
     python scripts/run.py ddpg --total_timesteps 20000 --warmup_steps 1000      (the library's Pendulum)
@@ -86,6 +87,13 @@ def main():
         if "--c51" in argv or co:
             argv = [a for a in argv if a != "--c51"]
             dist = crl.C51Options(**co)
+        # the quantile-regression critic (crl_dqn_qr_create): --qr switches it on, --n_quantiles / --kappa are QROptions' fields and imply it
+        qo = take((("--n_quantiles", int), ("--kappa", float)))
+        if "--qr" in argv or qo:
+            if dist is not None:
+                raise SystemExit("--qr and --c51 are two kinds of critic: give one")
+            argv = [a for a in argv if a != "--qr"]
+            dist = crl.QROptions(**qo)
         # the dueling heads (crl_dqn_dueling_create): --dueling combines with --per, --double_q / --n_step and --c51
         dueling = "--dueling" in argv
         argv = [a for a in argv if a != "--dueling"]
