@@ -210,12 +210,41 @@ __global__ void __launch_bounds__(1024) ddpg_sample_kernel(DDPGDev a) {
   replay_sample<DDPG_MAX_CAP>(a.cfg.seed, (uint64_t)a.ctl->global_step, (int)a.ctl->size, (int)a.cfg.batch_size, a.idx);
 }
 
+// forward and backward of an online critic on a known TD target, for sample b = ring slot s: q = get_q(critic, state, action), Flux.mse(td, q)
+// (ddpg.jl:114-117), ∂loss/∂q, δ2, δ1, all stored for the step kernel. w = 0: the only critic (DDPG) or critic 1; w = 1: critic 2 on wave 1 of a
+// two-wave block (TD3, SAC), whose buffers sit one [k] block further. X is stored once, by w = 0. In a two-wave block both waves take every barrier
+// alike; each wave's x / h1s / h2s / qs / d2s are its own.
+__device__ __forceinline__ void critic_td_pass(const DDPGDev& a, const float* __restrict__ critic, double td, double* x, double* h1s, double* h2s,
+                                               double* qs, double* d2s, int lane, int w, int b, size_t s) {
+#pragma clang fp contract(off)
+  const int D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const NetOff o = net_off(NI, 1);
+  double h1, h2;
+  for (int i = lane; i < NI; i += GH) {
+    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
+    x[i] = v;
+    if (w == 0) a.X[(size_t)NI * b + i] = v;
+  }
+  __syncthreads();
+  const double q = critic_forward(critic, NI, x, h1s, h2s, qs, lane, h1, h2);
+  const double diff = td - q;
+  const double dq = -2.0 * diff / (double)k;
+  const double d2 = h2 > 0.0 ? (double)critic[o.W3 + lane] * dq : 0.0;
+  d2s[lane] = d2;
+  __syncthreads();
+  const double t1 = w2t_row(critic + o.W2, d2s, lane);
+  const double d1 = h1 > 0.0 ? t1 : 0.0;
+  const size_t r = (size_t)GH * ((size_t)w * k + b) + lane;
+  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
+  if (lane == 0) { a.sq[(size_t)w * k + b] = diff * diff; a.dz[(size_t)w * k + b] = dq; }
+}
+
 // B. ddpg.jl:108-117 for sample blockIdx.x
 __global__ void __launch_bounds__(64) ddpg_critic_kernel(DDPGDev a) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT], qs, d2s[GH];
-  const int lane = threadIdx.x, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const int lane = threadIdx.x, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
   const uint64_t gstep = (uint64_t)a.ctl->global_step;
   const size_t s = (size_t)a.idx[b];
   double h1, h2;
@@ -231,83 +260,121 @@ __global__ void __launch_bounds__(64) ddpg_critic_kernel(DDPGDev a) {
   const double next_q = critic_forward(a.critic_t, NI, xs, h1s, h2s, &qs, lane, h1, h2);
   const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);   // :110
   __syncthreads();
-  // q = get_q(critic, state, action); Flux.mse(td_target, q) (:115-116)
-  for (int i = lane; i < NI; i += GH) {
-    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
-    xs[i] = v; a.X[(size_t)NI * b + i] = v;
-  }
-  __syncthreads();
-  const double q = critic_forward(a.critic, NI, xs, h1s, h2s, &qs, lane, h1, h2);
-  const double diff = td - q;
-  const double dq = -2.0 * diff / (double)k;
-  const NetOff o = net_off(NI, 1);
-  const double d2 = h2 > 0.0 ? (double)a.critic[o.W3 + lane] * dq : 0.0;
-  d2s[lane] = d2;
-  __syncthreads();
-  const double t1 = w2t_row(a.critic + o.W2, d2s, lane);
-  const double d1 = h1 > 0.0 ? t1 : 0.0;
-  const size_t r = (size_t)GH * b + lane;
-  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
-  if (lane == 0) { a.sq[b] = diff * diff; a.dz[b] = dq; }
+  critic_td_pass(a, a.critic, td, xs, h1s, h2s, &qs, d2s, lane, 0, b, s);
 }
 
-// Adam(lr) on element p (ddpg.jl:55-56,118,125: optim.hpp's entry step without the clip) and polyak_update! on the same element (:39-43)
-__device__ __forceinline__ void ddpg_step_entry(double g, float* w, float* t, float* m, float* v, const double* bp, double lr, double tau, int p) {
+// Adam(lr) on element p (ddpg.jl:55-56,118,125: optim.hpp's entry step without the clip), m, v and w written back; → the stepped weight
+__device__ __forceinline__ float adam_step_entry(double g, float* w, float* m, float* v, const double* bp, double lr, int p) {
 #pragma clang fp contract(off)
   float mi, vi, wi;
   adam_entry((double)(float)g, m[p], v[p], w[p], bp[0], bp[1], lr, /*clip=*/false, 1.0, mi, vi, wi);
   m[p] = mi; v[p] = vi; w[p] = wi;
-  t[p] = (float)(tau * (double)wi + (1.0 - tau) * (double)t[p]);
+  return wi;
+}
+// polyak_update! on element p (ddpg.jl:39-43) towards the online weight w
+__device__ __forceinline__ void polyak_entry(float* t, float w, double tau, int p) {
+#pragma clang fp contract(off)
+  t[p] = (float)(tau * (double)w + (1.0 - tau) * (double)t[p]);
 }
 
-// the gradient of critic parameter p from one critic pass's buffers: act = offset of its [k][64] blocks, row = offset of its [k] rows (both 0 for DDPG;
-// TD3's second critic sits one block further). Every loop is unrolled 30x as in dqn_wgrad_kernel: the operands were written by the launch before,
-// 30 loads in flight per round trip; the Float64 adds stay in sample order
-__device__ __forceinline__ double critic_param_grad(const DDPGDev& a, const NetOff& o, int NI, int k, int p, size_t act, size_t row) {
+// the gradient of parameter p of a three-layer net (offsets o, a head of HR rows) from one pass's stored buffers, samples in sample order:
+// X [k][NI] inputs, H1, H2 [k][64] activations, D1, D2 [k][64] and D3 [k][HR] the δ of the three layers. A critic passes the literal 1 for HR and dz
+// for D3; the actor act_dim (DDPG, TD3) or 2·act_dim (SAC). Every loop is unrolled 30x as in dqn_wgrad_kernel: the operands were written by the
+// launch before, 30 loads in flight per round trip; the Float64 adds stay in sample order
+__device__ __forceinline__ double net_param_grad(const NetOff& o, int HR, int p, int k, const double* X, int NI, const double* H1, const double* H2,
+                                                 const double* D1, const double* D2, const double* D3) {
 #pragma clang fp contract(off)
-  const double *cH1 = a.cH1 + act, *cH2 = a.cH2 + act, *cD1 = a.cD1 + act, *cD2 = a.cD2 + act, *dz = a.dz + row;
   double g = 0.0;
   if (p < o.b1) {
     const int i = p % GH, kk = p / GH;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += cD1[(size_t)GH * b + i] * a.X[(size_t)NI * b + kk];
+    for (int b = 0; b < k; ++b) g += D1[(size_t)GH * b + i] * X[(size_t)NI * b + kk];
   } else if (p < o.W2) {
     const int i = p - o.b1;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += cD1[(size_t)GH * b + i];
+    for (int b = 0; b < k; ++b) g += D1[(size_t)GH * b + i];
   } else if (p < o.b2) {
     const int r = p - o.W2, j = r % GH, kk = r / GH;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += cD2[(size_t)GH * b + j] * cH1[(size_t)GH * b + kk];
+    for (int b = 0; b < k; ++b) g += D2[(size_t)GH * b + j] * H1[(size_t)GH * b + kk];
   } else if (p < o.W3) {
     const int j = p - o.b2;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += cD2[(size_t)GH * b + j];
+    for (int b = 0; b < k; ++b) g += D2[(size_t)GH * b + j];
   } else if (p < o.b3) {
-    const int j = p - o.W3;
+    const int r = p - o.W3, c = r % HR, j = r / HR;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += dz[b] * cH2[(size_t)GH * b + j];
+    for (int b = 0; b < k; ++b) g += D3[(size_t)HR * b + c] * H2[(size_t)GH * b + j];
   } else {
+    const int c = p - o.b3;
 #pragma unroll 30
-    for (int b = 0; b < k; ++b) g += dz[b];
+    for (int b = 0; b < k; ++b) g += D3[(size_t)HR * b + c];
   }
   return g;
 }
 
+// the critic step of NQ critics for thread t: parameter t % nc of critic t / nc — thread 0 sums each critic's loss in sample order
+// (critic_loss = mean((td − q)²) (:114-116), the two means added for twin critics), then the gradient from that critic's pass and Adam on the
+// element; → whether t is a parameter, wi its stepped weight
+template <int NQ>
+__device__ __forceinline__ bool critic_step_entry(const DDPGDev& a, int t, float& wi) {
+#pragma clang fp contract(off)
+  const int k = (int)a.cfg.batch_size, NI = a.cfg.obs_dim + a.cfg.act_dim;
+  const NetOff o = net_off(NI, 1);
+  if (t == 0) {
+    double l[NQ];
+    for (int w = 0; w < NQ; ++w) {
+      l[w] = 0.0;
+      for (int b = 0; b < k; ++b) l[w] += a.sq[(size_t)w * k + b];
+    }
+    if constexpr (NQ == 1) a.ctl->critic_loss = l[0] / (double)k;
+    else a.ctl->critic_loss = l[0] / (double)k + l[1] / (double)k;
+  }
+  if (t >= NQ * o.N) return false;
+  const int w = NQ == 1 ? 0 : t / o.N, p = t - w * o.N;
+  const size_t act = (size_t)w * k * GH;
+  const double g = net_param_grad(o, 1, p, k, a.X, NI, a.cH1 + act, a.cH2 + act, a.cD1 + act, a.cD2 + act, a.dz + (size_t)w * k);
+  wi = adam_step_entry(g, a.critic, a.mc, a.vc, a.betap + 2 * (6 + 6 * w + net_array(o, p)), a.cfg.lr, t);
+  return true;
+}
+
 // C. critic gradient, Adam, polyak: one parameter per thread, samples in sample order
 __global__ void __launch_bounds__(64) ddpg_critic_step(DDPGDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int k = (int)a.cfg.batch_size, NI = a.cfg.obs_dim + a.cfg.act_dim, p = blockIdx.x * 64 + threadIdx.x;
-  const NetOff o = net_off(NI, 1);
-  if (p == 0) {                                                                        // critic_loss = mean((td − q)²) (:114-116)
-    double loss = 0.0;
-    for (int b = 0; b < k; ++b) loss += a.sq[b];
-    a.ctl->critic_loss = loss / (double)k;
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  float wi;
+  if (critic_step_entry<1>(a, p, wi)) polyak_entry(a.critic_t, wi, a.cfg.tau, p);
+}
+
+// back through a critic whose forward left ch1, ch2 on the lanes: δ2 = W3·dq where h2 > 0, δ1 = (Σ_j W2[j, i]·δ2[j]) where h1 > 0, both through ds, then
+// ∂/∂a[c] = Σ_i W1[i, D + c]·δ1[i], i ascending, on lanes c < A (0 on the others). Three block barriers; the caller's barrier follows before ds is reused.
+__device__ __forceinline__ double critic_action_grad(const float* __restrict__ critic, const NetOff& oc, int D, int A, double dq, double ch1, double ch2,
+                                                     double* ds, int lane) {
+#pragma clang fp contract(off)
+  ds[lane] = ch2 > 0.0 ? (double)critic[oc.W3 + lane] * dq : 0.0;
+  __syncthreads();
+  const double t1 = w2t_row(critic + oc.W2, ds, lane);
+  __syncthreads();
+  ds[lane] = ch1 > 0.0 ? t1 : 0.0;
+  __syncthreads();
+  double ga = 0.0;
+  if (lane < A) {
+#pragma unroll 8
+    for (int i = 0; i < GH; ++i) ga += (double)critic[oc.W1 + i + GH * (D + lane)] * ds[i];
   }
-  if (p >= o.N) return;
-  const double g = critic_param_grad(a, o, NI, k, p, 0, 0);
-  ddpg_step_entry(g, a.critic, a.critic_t, a.mc, a.vc, a.betap + 2 * (6 + net_array(o, p)), a.cfg.lr, a.cfg.tau, p);
+  return ga;
+}
+// the actor's δ2[j] = (Σ_r W3[r, j]·δ3[r])·(1 − h2[j]²), r ascending over the HR head rows in d3s, and δ1[i] = (Σ_j W2[j, i]·δ2[j])·(1 − h1[i]²) through
+// ds: tanh_fast' = 1 − y² from the activations ah1, ah2 the forward left on the lanes. One block barrier.
+__device__ __forceinline__ void actor_backprop(const float* __restrict__ actor, const NetOff& oa, int HR, const double* d3s, double ah1, double ah2,
+                                               double* ds, int lane, double& d1, double& d2) {
+#pragma clang fp contract(off)
+  double s2 = 0.0;
+  for (int r = 0; r < HR; ++r) s2 += (double)actor[oa.W3 + r + HR * lane] * d3s[r];
+  d2 = s2 * (1.0 - ah2 * ah2);
+  ds[lane] = d2;
+  __syncthreads();
+  d1 = w2t_row(actor + oa.W2, ds, lane) * (1.0 - ah1 * ah1);
 }
 
 // D. ddpg.jl:122-124 for sample blockIdx.x: −mean(get_q(critic, state, actor(state))) through the updated critic, gradient w.r.t. the actor
@@ -329,30 +396,15 @@ __device__ __forceinline__ void ddpg_actor_pass(const DDPGDev& a) {
   }
   __syncthreads();
   const double q = critic_forward(a.critic, NI, xs, h1s, h2s, &qs, lane, ch1, ch2);
-  // back through the critic: ∂loss/∂Q = −1/k, δ2, δ1, then ∂loss/∂a[c] = Σ_i W1[i, D + c]·δ1[i], i ascending
-  const double dq = -1.0 / (double)k;
-  ds[lane] = ch2 > 0.0 ? (double)a.critic[oc.W3 + lane] * dq : 0.0;
-  __syncthreads();
-  const double t1 = w2t_row(a.critic + oc.W2, ds, lane);
-  __syncthreads();
-  ds[lane] = ch1 > 0.0 ? t1 : 0.0;
-  __syncthreads();
+  const double ga = critic_action_grad(a.critic, oc, D, A, -1.0 / (double)k, ch1, ch2, ds, lane);   // ∂loss/∂Q = −1/k
   if (lane < A) {
-    double ga = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < GH; ++i) ga += (double)a.critic[oc.W1 + i + GH * (D + lane)] * ds[i];
     const double d3 = (ga * 2.0) * (1.0 - y3 * y3);                                   // x·2, then tanh_fast' = 1 − y²
     d3s[lane] = d3;
     a.aD3[(size_t)A * b + lane] = d3; a.aY[(size_t)A * b + lane] = y3;
   }
   __syncthreads();
-  // actor δ2[j] = (Σ_c W3[c, j]·δ3[c])·(1 − h2[j]²), δ1[i] = (Σ_j W2[j, i]·δ2[j])·(1 − h1[i]²)
-  double s2 = 0.0;
-  for (int c = 0; c < A; ++c) s2 += (double)a.actor[oa.W3 + c + A * lane] * d3s[c];
-  const double d2 = s2 * (1.0 - ah2 * ah2);
-  ds[lane] = d2;
-  __syncthreads();
-  const double d1 = w2t_row(a.actor + oa.W2, ds, lane) * (1.0 - ah1 * ah1);
+  double d1, d2;
+  actor_backprop(a.actor, oa, A, d3s, ah1, ah2, ds, lane, d1, d2);
   const size_t r = (size_t)GH * b + lane;
   a.aH1[r] = ah1; a.aH2[r] = ah2; a.aD1[r] = d1; a.aD2[r] = d2;
   if (lane == 0) a.Qa[b] = q;
@@ -362,43 +414,17 @@ __global__ void __launch_bounds__(64) ddpg_actor_kernel(DDPGDev a) {
   ddpg_actor_pass(a);
 }
 
-// the gradient of actor parameter p from the actor pass's buffers, samples in sample order; HR = head rows (o = net_off(D, HR), aD3 is [k][HR]:
-// act_dim for DDPG and TD3, 2·act_dim for SAC), NI = the row length of X
-__device__ __forceinline__ double actor_param_grad(const DDPGDev& a, const NetOff& o, int NI, int HR, int k, int p) {
+// gradient and Adam for parameter p of an actor whose head has HR rows, from the actor pass's buffers; → the stepped weight
+__device__ __forceinline__ float actor_adam_entry(const DDPGDev& a, const NetOff& o, int HR, int p) {
 #pragma clang fp contract(off)
-  double g = 0.0;
-  if (p < o.b1) {
-    const int i = p % GH, kk = p / GH;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD1[(size_t)GH * b + i] * a.X[(size_t)NI * b + kk];
-  } else if (p < o.W2) {
-    const int i = p - o.b1;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD1[(size_t)GH * b + i];
-  } else if (p < o.b2) {
-    const int r = p - o.W2, j = r % GH, kk = r / GH;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD2[(size_t)GH * b + j] * a.aH1[(size_t)GH * b + kk];
-  } else if (p < o.W3) {
-    const int j = p - o.b2;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD2[(size_t)GH * b + j];
-  } else if (p < o.b3) {
-    const int r = p - o.W3, c = r % HR, j = r / HR;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)HR * b + c] * a.aH2[(size_t)GH * b + j];
-  } else {
-    const int c = p - o.b3;
-#pragma unroll 30
-    for (int b = 0; b < k; ++b) g += a.aD3[(size_t)HR * b + c];
-  }
-  return g;
+  const double g = net_param_grad(o, HR, p, (int)a.cfg.batch_size, a.X, a.cfg.obs_dim + a.cfg.act_dim, a.aH1, a.aH2, a.aD1, a.aD2, a.aD3);
+  return adam_step_entry(g, a.actor, a.ma, a.va, a.betap + 2 * net_array(o, p), a.cfg.lr, p);
 }
 
 // E. actor gradient, Adam, polyak for actor parameter p (p >= the actor's size: only p = 0's loss)
 __device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
 #pragma clang fp contract(off)
-  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
+  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim;
   const NetOff o = net_off(D, A);
   if (p == 0) {                                                                        // actor_loss = −mean(Q) (:123)
     double sum = 0.0;
@@ -406,8 +432,7 @@ __device__ __forceinline__ void ddpg_actor_step_entry(const DDPGDev& a, int p) {
     a.ctl->actor_loss = -(sum / (double)k);
   }
   if (p >= o.N) return;
-  const double g = actor_param_grad(a, o, NI, A, k, p);
-  ddpg_step_entry(g, a.actor, a.actor_t, a.ma, a.va, a.betap + 2 * net_array(o, p), a.cfg.lr, a.cfg.tau, p);
+  polyak_entry(a.actor_t, actor_adam_entry(a, o, A, p), a.cfg.tau, p);
 }
 __global__ void __launch_bounds__(64) ddpg_actor_step(DDPGDev a) {
   if (!a.ctl->train_pending) return;
@@ -457,6 +482,13 @@ __device__ __forceinline__ void ddpg_finish_update(const DDPGDev& a, DDPGCtl& c,
   if (lane == 0) ddpg_log_update(a, c);
 }
 
+// one thread, after step c.global_step went into slot c.ptr: Buffer.add!'s ring advance and whether an update is due (ddpg.jl:105)
+__device__ __forceinline__ void ddpg_ring_advance(const crl_ddpg_config& cfg, DDPGCtl& c) {
+  c.ptr = c.ptr + 1 >= cfg.buffer_size ? 0 : c.ptr + 1;
+  c.size = c.size + 1 > cfg.buffer_size ? cfg.buffer_size : c.size + 1;
+  c.train_pending = (c.global_step > cfg.min_buff_size && c.global_step > cfg.warmup_steps) ? 1 : 0;
+}
+
 // F. close the pending update, then ddpg.jl:77-105 on the Pendulum until an update is due, the budget or total_timesteps is used up
 template <class Finish, class Select>
 __device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish, Select select) {
@@ -488,8 +520,6 @@ __device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish, Se
       for (int i = 0; i < 3; ++i) a.rb_state[3 * p + i] = xs[i];
       a.rb_action[p] = act[0]; a.rb_reward[p] = rew; a.rb_terminal[p] = done ? 1 : 0;
       a.rb_next[3 * p + 0] = pend_cos(c.env[0]); a.rb_next[3 * p + 1] = pend_sin(c.env[0]); a.rb_next[3 * p + 2] = c.env[1];
-      c.ptr = c.ptr + 1 >= a.cfg.buffer_size ? 0 : c.ptr + 1;
-      c.size = c.size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c.size + 1;
       c.episode_return += rew; c.episode_length += 1;                                  // :93-94
       if (done) {                                                                      // :95-101
         if (c.n_eps < DDPG_MAX_EPS) {
@@ -499,7 +529,7 @@ __device__ __forceinline__ void ddpg_collect(const DDPGDev& a, Finish finish, Se
         c.episode_length = 0; c.episode_return = 0.0;
         pendulum_reset64(c.env, a.cfg.seed, gstep, S_RESET); c.env_t = 0;
       }
-      c.train_pending = (c.global_step > a.cfg.min_buff_size && c.global_step > a.cfg.warmup_steps) ? 1 : 0;   // :105
+      ddpg_ring_advance(a.cfg, c);                                                     // the ring's ptr and size, :105
     }
     __syncthreads();
   }
@@ -514,95 +544,70 @@ __global__ void __launch_bounds__(64) ddpg_collect_kernel(DDPGDev a) {
 // kernels. A TD3 handle's critic, critic_t, mc and vc hold [2][nc] floats (critic 1 first, so every DDPG kernel that reads a.critic reads critic 1),
 // its cH1 / cH2 / cD1 / cD2 hold [2][k][64], dz / sq [2][k], betap [18][2]: the actor's six arrays, critic 1's, critic 2's. X is stored once.
 //   A  ddpg_sample_kernel  unchanged
-//   B' td3_critic_kernel   one block per sample, two waves, wave w = critic w: target actor + smoothing noise (both waves, each into its own LDS),
-//                          target critic w, min of the two through LDS, then forward and backward of online critic w on the shared TD target
-//   C' td3_critic_step     one thread per parameter of the 2·nc: gradient in sample order, Adam; no polyak
+//   B' td3_critic_kernel   one block per sample, two waves, wave w = critic w: twin_target_pass — target actor + smoothing noise (both waves, each into
+//                          its own LDS), target critic w, min of the two through LDS, then critic_td_pass of online critic w on the shared TD target
+//   C' td3_critic_step     critic_step_entry<2>, one thread per parameter of the 2·nc: net_param_grad in sample order, adam_step_entry; no polyak
 //   D' td3_actor_kernel    ddpg_actor_pass (critic 1, no noise: noise_in_update is 0 on a TD3 handle) when the actor is due
-//   E' td3_actor_step      when the actor is due: ddpg_actor_step_entry (gradient, Adam, polyak) in the first blocks, polyak of both critics in the rest
+//   E' td3_actor_step      when the actor is due: ddpg_actor_step_entry (gradient, Adam, polyak) in the first blocks, twin_polyak_tail in the rest
 //   F' td3_collect_kernel  ddpg_collect with TD3's close: 18 β-power pairs, the actor's six only when it stepped
 // "The actor is due" is global_step % policy_delay == 0: global_step is the control block's and no kernel of A–E' writes it, so every block of a
 // cycle takes the same decision (it is the flag a cycle would otherwise carry next to train_pending, derived instead of stored).
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool td3_actor_due(const DDPGCtl* c, const crl_td3_options& o) { return c->global_step % (int64_t)o.policy_delay == 0; }
 
-// forward and backward of online critic w (wave w of a two-wave block) on the shared TD target, for sample b = ring slot s: what the critic pass of
-// a twin-critic update (TD3, SAC) does once td is known. Both waves take every barrier alike; each wave's x / h1s / h2s / qs / d2s are its own.
-__device__ __forceinline__ void twin_critic_pass(const DDPGDev& a, const float* __restrict__ critic, double td, double* x, double* h1s, double* h2s,
-                                                 double* qs, double* d2s, int lane, int w, int b, size_t s) {
+// the critic pass of a twin-critic update (TD3, SAC) for sample blockIdx.x on a two-wave block, wave w = critic w, every array argument the wave's
+// own but qs, which is both waves' [2]: next_state into x, next_action(b) (block-wide, ends on a block barrier with the next action in x[D..D+A)),
+// target critic w, the min of the two through LDS, td_target(next_q, s), then critic_td_pass. Every barrier is reached by both waves: the callers'
+// one exit is the block-uniform one at their top, and both waves take every call alike.
+template <class NextAction, class TdTarget>
+__device__ __forceinline__ void twin_target_pass(const DDPGDev& a, double* x, double* h1s, double* h2s, double* qs, double* d2s, int lane, int w,
+                                                 NextAction next_action, TdTarget td_target) {
 #pragma clang fp contract(off)
-  const int D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A, k = (int)a.cfg.batch_size;
+  const int b = blockIdx.x, D = a.cfg.obs_dim, NI = D + a.cfg.act_dim;
+  const size_t s = (size_t)a.idx[b];
   const NetOff o = net_off(NI, 1);
   double h1, h2;
-  for (int i = lane; i < NI; i += GH) {
-    const double v = i < D ? a.rb_state[D * s + i] : a.rb_action[A * s + (i - D)];
-    x[i] = v;
-    if (w == 0) a.X[(size_t)NI * b + i] = v;
-  }
+  for (int i = lane; i < D; i += GH) x[i] = a.rb_next[D * s + i];
   __syncthreads();
-  const double q = critic_forward(critic, NI, x, h1s, h2s, qs, lane, h1, h2);
-  const double diff = td - q;
-  const double dq = -2.0 * diff / (double)k;
-  const double d2 = h2 > 0.0 ? (double)critic[o.W3 + lane] * dq : 0.0;
-  d2s[lane] = d2;
+  next_action(b);
+  critic_forward(a.critic_t + (size_t)w * o.N, NI, x, h1s, h2s, qs + w, lane, h1, h2);   // its last barrier publishes both qs
+  const double q1 = qs[0], q2 = qs[1];
+  const double td = td_target(q2 < q1 ? q2 : q1, s);
   __syncthreads();
-  const double t1 = w2t_row(critic + o.W2, d2s, lane);
-  const double d1 = h1 > 0.0 ? t1 : 0.0;
-  const size_t r = (size_t)GH * ((size_t)w * k + b) + lane;
-  a.cH1[r] = h1; a.cH2[r] = h2; a.cD1[r] = d1; a.cD2[r] = d2;
-  if (lane == 0) { a.sq[(size_t)w * k + b] = diff * diff; a.dz[(size_t)w * k + b] = dq; }
+  critic_td_pass(a, a.critic + (size_t)w * o.N, td, x, h1s, h2s, qs + w, d2s, lane, w, b, s);
 }
 
-// B'. Every barrier below is reached by both waves: the one exit is the block-uniform one at the top, and both waves take every call alike.
+// B'.
 __global__ void __launch_bounds__(128) td3_critic_kernel(DDPGDev a, crl_td3_options opt) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   __shared__ double xs[2][DDPG_MAX_IN], h1s[2][GH], h2s[2][GH], ys[2][DDPG_MAX_ACT], qs[2], d2s[2][GH];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim, NI = D + A;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, D = a.cfg.obs_dim, A = a.cfg.act_dim;
   const uint64_t gstep = (uint64_t)a.ctl->global_step;
-  const size_t s = (size_t)a.idx[b];
-  const NetOff o = net_off(NI, 1);
-  const float* const critic = a.critic + (size_t)w * o.N;
-  const float* const critic_t = a.critic_t + (size_t)w * o.N;
-  double h1, h2;
-  for (int i = lane; i < D; i += GH) xs[w][i] = a.rb_next[D * s + i];
-  __syncthreads();
-  actor_forward(a.actor_t, D, A, xs[w], h1s[w], h2s[w], ys[w], lane, h1, h2);
-  if (lane < A) {
-    // target policy smoothing: a per-SAMPLE draw, component word 16·b + c
-    const double z = ddpg_normal(a.cfg.seed, (uint32_t)(16 * b + lane), gstep, S_SMOOTH);
-    const double nz0 = opt.policy_noise * z;
-    const double nz = nz0 < -opt.noise_clip ? -opt.noise_clip : (nz0 > opt.noise_clip ? opt.noise_clip : nz0);
-    const double a0 = ys[w][lane] * 2.0 + nz;
-    xs[w][D + lane] = a0 < a.cfg.act_low ? a.cfg.act_low : (a0 > a.cfg.act_high ? a.cfg.act_high : a0);
-  }
-  __syncthreads();
-  critic_forward(critic_t, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, h1, h2);       // its last barrier publishes both qs
-  const double q1 = qs[0], q2 = qs[1];
-  const double next_q = q2 < q1 ? q2 : q1;
-  const double td = a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
-  __syncthreads();
-  twin_critic_pass(a, critic, td, xs[w], h1s[w], h2s[w], &qs[w], d2s[w], lane, w, b, s);
+  twin_target_pass(a, xs[w], h1s[w], h2s[w], qs, d2s[w], lane, w, [&](int b) {
+#pragma clang fp contract(off)
+    double h1, h2;
+    actor_forward(a.actor_t, D, A, xs[w], h1s[w], h2s[w], ys[w], lane, h1, h2);
+    if (lane < A) {
+      // target policy smoothing: a per-SAMPLE draw, component word 16·b + c
+      const double z = ddpg_normal(a.cfg.seed, (uint32_t)(16 * b + lane), gstep, S_SMOOTH);
+      const double nz0 = opt.policy_noise * z;
+      const double nz = nz0 < -opt.noise_clip ? -opt.noise_clip : (nz0 > opt.noise_clip ? opt.noise_clip : nz0);
+      const double a0 = ys[w][lane] * 2.0 + nz;
+      xs[w][D + lane] = a0 < a.cfg.act_low ? a.cfg.act_low : (a0 > a.cfg.act_high ? a.cfg.act_high : a0);
+    }
+    __syncthreads();
+  }, [&](double next_q, size_t s) {
+#pragma clang fp contract(off)
+    return a.rb_reward[s] + a.cfg.gamma * next_q * (1.0 - (double)a.rb_terminal[s]);
+  });
 }
 
-// C'. thread p: parameter p % nc of critic p / nc. critic_loss = loss_1 + loss_2
+// C'. thread t: parameter t % nc of critic t / nc. critic_loss = loss_1 + loss_2; no polyak (E' does it when the actor is due)
 __global__ void __launch_bounds__(64) td3_critic_step(DDPGDev a) {
-#pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  const int k = (int)a.cfg.batch_size, NI = a.cfg.obs_dim + a.cfg.act_dim, t = blockIdx.x * 64 + threadIdx.x;
-  const NetOff o = net_off(NI, 1);
-  if (t == 0) {
-    double l1 = 0.0, l2 = 0.0;
-    for (int b = 0; b < k; ++b) l1 += a.sq[b];
-    for (int b = 0; b < k; ++b) l2 += a.sq[(size_t)k + b];
-    a.ctl->critic_loss = l1 / (double)k + l2 / (double)k;
-  }
-  if (t >= 2 * o.N) return;
-  const int w = t / o.N, p = t - w * o.N;
-  const double g = critic_param_grad(a, o, NI, k, p, (size_t)w * k * GH, (size_t)w * k);
-  const double* bp = a.betap + 2 * (6 + 6 * w + net_array(o, p));
-  float mi, vi, wi;
-  adam_entry((double)(float)g, a.mc[t], a.vc[t], a.critic[t], bp[0], bp[1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, wi);
-  a.mc[t] = mi; a.vc[t] = vi; a.critic[t] = wi;
+  float wi;
+  critic_step_entry<2>(a, blockIdx.x * 64 + threadIdx.x, wi);
 }
 
 // D'.
@@ -611,13 +616,17 @@ __global__ void __launch_bounds__(64) td3_actor_kernel(DDPGDev a, crl_td3_option
   ddpg_actor_pass(a);
 }
 
-// E'. blocks 0..actor_blocks−1: the actor; the blocks after them: polyak_update! of the 2·nc critic elements (the critics stepped in C')
-__global__ void __launch_bounds__(64) td3_actor_step(DDPGDev a, crl_td3_options opt, int actor_blocks, int nc2) {
-#pragma clang fp contract(off)
-  if (!a.ctl->train_pending || !td3_actor_due(a.ctl, opt)) return;
-  if ((int)blockIdx.x < actor_blocks) { ddpg_actor_step_entry(a, blockIdx.x * 64 + threadIdx.x); return; }
+// the blocks behind the actor's in an actor-step launch of a twin-critic handle: polyak_update! of the 2·nc critic elements (the critics stepped in C')
+__device__ __forceinline__ void twin_polyak_tail(const DDPGDev& a, int actor_blocks, int nc2) {
   const int t = ((int)blockIdx.x - actor_blocks) * 64 + threadIdx.x;
-  if (t < nc2) a.critic_t[t] = (float)(a.cfg.tau * (double)a.critic[t] + (1.0 - a.cfg.tau) * (double)a.critic_t[t]);
+  if (t < nc2) polyak_entry(a.critic_t, a.critic[t], a.cfg.tau, t);
+}
+
+// E'. blocks 0..actor_blocks−1: the actor; the blocks after them: twin_polyak_tail
+__global__ void __launch_bounds__(64) td3_actor_step(DDPGDev a, crl_td3_options opt, int actor_blocks, int nc2) {
+  if (!a.ctl->train_pending || !td3_actor_due(a.ctl, opt)) return;
+  if ((int)blockIdx.x < actor_blocks) ddpg_actor_step_entry(a, blockIdx.x * 64 + threadIdx.x);
+  else twin_polyak_tail(a, actor_blocks, nc2);
 }
 
 // closes a TD3 update: critic β powers always, the actor's only when it stepped; the rest is ddpg_finish_update's
@@ -653,12 +662,9 @@ __global__ void __launch_bounds__(64) ddpg_add_kernel(DDPGDev a) {
   for (int i = lane; i < D; i += GH) { a.rb_state[D * p + i] = s[i]; a.rb_next[D * p + i] = s[D + A + 1 + i]; }
   if (lane < A) a.rb_action[A * p + lane] = s[D + lane];
   if (lane == 0) {
-    DDPGCtl* c = a.ctl;
     a.rb_reward[p] = s[D + A]; a.rb_terminal[p] = s[2 * D + A + 1] != 0.0 ? 1 : 0;
-    c->global_step += 1;
-    c->ptr = ptr + 1 >= a.cfg.buffer_size ? 0 : ptr + 1;
-    c->size = c->size + 1 > a.cfg.buffer_size ? a.cfg.buffer_size : c->size + 1;
-    c->train_pending = (c->global_step > a.cfg.min_buff_size && c->global_step > a.cfg.warmup_steps) ? 1 : 0;
+    a.ctl->global_step += 1;
+    ddpg_ring_advance(a.cfg, *a.ctl);
   }
 }
 
@@ -670,17 +676,27 @@ __global__ void ddpg_init_kernel(DDPGDev a) {
   *a.ctl = c;
 }
 
-// the noise-free 2·tanh_fast(·) of actor(obs) / get_q(critic, obs, act) on caller-supplied inputs, one wave per column
-__global__ void __launch_bounds__(64) ddpg_actor_eval_kernel(DDPGDev a, const double* __restrict__ obs, int n, double* __restrict__ out) {
-#pragma clang fp contract(off)
-  __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT];
+// crl_ddpg_actor for column blockIdx.x of caller-supplied observations, one wave per column: the column into xs, then action(lane), the handle's
+// noise-free actor on xs (block-wide; → the action on lanes < act_dim)
+template <class Action>
+__device__ __forceinline__ void actor_eval_column(const DDPGDev& a, const double* __restrict__ obs, int n, double* __restrict__ out, double* xs,
+                                                  Action action) {
   const int lane = threadIdx.x, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim;
   if (b >= n) return;
   for (int i = lane; i < D; i += GH) xs[i] = obs[(size_t)D * b + i];
   __syncthreads();
-  double h1, h2;
-  actor_forward(a.actor, D, A, xs, h1s, h2s, ys, lane, h1, h2);
-  if (lane < A) out[(size_t)A * b + lane] = ys[lane] * 2.0;
+  const double act = action(lane);
+  if (lane < A) out[(size_t)A * b + lane] = act;
+}
+// the noise-free 2·tanh_fast(·) of actor(obs) / get_q(critic, obs, act) on caller-supplied inputs, one wave per column
+__global__ void __launch_bounds__(64) ddpg_actor_eval_kernel(DDPGDev a, const double* __restrict__ obs, int n, double* __restrict__ out) {
+  __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], ys[DDPG_MAX_ACT];
+  actor_eval_column(a, obs, n, out, xs, [&](int lane) {
+#pragma clang fp contract(off)
+    double h1, h2;
+    actor_forward(a.actor, a.cfg.obs_dim, a.cfg.act_dim, xs, h1s, h2s, ys, lane, h1, h2);
+    return lane < a.cfg.act_dim ? ys[lane] * 2.0 : 0.0;
+  });
 }
 __global__ void __launch_bounds__(64) ddpg_q_eval_kernel(DDPGDev a, const double* __restrict__ obs, const double* __restrict__ act, int n,
                                                          double* __restrict__ out) {
@@ -813,35 +829,33 @@ static int galloc(T** p, size_t n) {
   return 0;
 }
 
-// one cycle: launches A–E, then the collect launch F (which closes the update and, on a Pendulum handle, steps the env)
+// the three kinds of handle: 0 DDPG, 1 TD3, 2 SAC
+static const char* const KIND[3] = {"ddpg", "td3", "sac"};
+static int kind_of(const crl_ddpg* h) { return h->sac ? 2 : h->td3 ? 1 : 0; }
+
+// one cycle: launches A–E, then the collect launch F (which closes the update and, on a Pendulum handle, steps the env). Each slot has the kernel of
+// the handle's kind, with that kind's options behind d
 static void enqueue_cycle(const crl_ddpg* h) {
-  hipStream_t st = h->stream;
-  const DDPGDev& d = h->d;
-  const int k = (int)h->cfg.batch_size, na = h->na, nc = h->nc;
-  hipLaunchKernelGGL(ddpg_sample_kernel, dim3(1), dim3(1024), 0, st, d);
-  if (h->sac) {
-    const int ab = (na + 63) / 64;
-    hipLaunchKernelGGL(sac_critic_kernel, dim3(k), dim3(128), 0, st, d, h->sd);
-    hipLaunchKernelGGL(td3_critic_step, dim3((2 * nc + 63) / 64), dim3(64), 0, st, d);
-    hipLaunchKernelGGL(sac_actor_kernel, dim3(k), dim3(128), 0, st, d, h->sd);
-    hipLaunchKernelGGL(sac_actor_step, dim3(ab + (2 * nc + 63) / 64), dim3(64), 0, st, d, h->sd, ab, 2 * nc);
-    hipLaunchKernelGGL(sac_collect_kernel, dim3(1), dim3(64), 0, st, d, h->sd);
-    return;
-  }
-  if (h->td3) {
-    const int ab = (na + 63) / 64;
-    hipLaunchKernelGGL(td3_critic_kernel, dim3(k), dim3(128), 0, st, d, h->topt);
-    hipLaunchKernelGGL(td3_critic_step, dim3((2 * nc + 63) / 64), dim3(64), 0, st, d);
-    hipLaunchKernelGGL(td3_actor_kernel, dim3(k), dim3(64), 0, st, d, h->topt);
-    hipLaunchKernelGGL(td3_actor_step, dim3(ab + (2 * nc + 63) / 64), dim3(64), 0, st, d, h->topt, ab, 2 * nc);
-    hipLaunchKernelGGL(td3_collect_kernel, dim3(1), dim3(64), 0, st, d, h->topt);
-    return;
-  }
-  hipLaunchKernelGGL(ddpg_critic_kernel, dim3(k), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(ddpg_critic_step, dim3((nc + 63) / 64), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(ddpg_actor_kernel, dim3(k), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(ddpg_actor_step, dim3((na + 63) / 64), dim3(64), 0, st, d);
-  hipLaunchKernelGGL(ddpg_collect_kernel, dim3(1), dim3(64), 0, st, d);
+  const int kind = kind_of(h), k = (int)h->cfg.batch_size;
+  const int ab = (h->na + 63) / 64, nc2 = 2 * h->nc, cb = ((kind ? nc2 : h->nc) + 63) / 64;   // blocks of the actor's and of the critics' parameters
+  auto launch = [h](auto kernel, int grid, int block, auto... more) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, h->stream, h->d, more...);
+  };
+  launch(ddpg_sample_kernel, 1, 1024);                                                   // A
+  if (kind == 2) launch(sac_critic_kernel, k, 128, h->sd);                               // B
+  else if (kind == 1) launch(td3_critic_kernel, k, 128, h->topt);
+  else launch(ddpg_critic_kernel, k, 64);
+  if (kind) launch(td3_critic_step, cb, 64);                                             // C
+  else launch(ddpg_critic_step, cb, 64);
+  if (kind == 2) launch(sac_actor_kernel, k, 128, h->sd);                                // D
+  else if (kind == 1) launch(td3_actor_kernel, k, 64, h->topt);
+  else launch(ddpg_actor_kernel, k, 64);
+  if (kind == 2) launch(sac_actor_step, ab + cb, 64, h->sd, ab, nc2);                    // E
+  else if (kind == 1) launch(td3_actor_step, ab + cb, 64, h->topt, ab, nc2);
+  else launch(ddpg_actor_step, ab, 64);
+  if (kind == 2) launch(sac_collect_kernel, 1, 64, h->sd);                               // F
+  else if (kind == 1) launch(td3_collect_kernel, 1, 64, h->topt);
+  else launch(ddpg_collect_kernel, 1, 64);
 }
 
 static int ddpg_scratch(crl_ddpg* h, size_t need) {
@@ -853,17 +867,18 @@ static int ddpg_scratch(crl_ddpg* h, size_t need) {
   return 0;
 }
 
-extern "C" {
-
-int32_t crl_ddpg_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n) {
-  if (obs_dim < 1 || obs_dim > DDPG_MAX_OBS) { set_error("crl_ddpg_param_count: obs_dim must be in 1..64"); return 1; }
-  if (act_dim < 1 || act_dim > DDPG_MAX_ACT) { set_error("crl_ddpg_param_count: act_dim must be in 1..16"); return 1; }
-  if (actor_n) *actor_n = net_off(obs_dim, act_dim).N;
+// crl_ddpg_param_count (head_rows_per_act = 1) and crl_sac_param_count (2), fn the caller's name
+static int32_t param_count(const char* fn, int32_t obs_dim, int32_t act_dim, int head_rows_per_act, int64_t* actor_n, int64_t* critic_n) {
+  if (obs_dim < 1 || obs_dim > DDPG_MAX_OBS) { set_error(std::string(fn) + ": obs_dim must be in 1..64"); return 1; }
+  if (act_dim < 1 || act_dim > DDPG_MAX_ACT) { set_error(std::string(fn) + ": act_dim must be in 1..16"); return 1; }
+  if (actor_n) *actor_n = net_off(obs_dim, head_rows_per_act * act_dim).N;
   if (critic_n) *critic_n = net_off(obs_dim + act_dim, 1).N;
   return 0;
 }
 
-}  // extern "C"
+extern "C" int32_t crl_ddpg_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n) {
+  return param_count("crl_ddpg_param_count", obs_dim, act_dim, 1, actor_n, critic_n);
+}
 
 // crl_ddpg_create (topt = sopt = nullptr), crl_td3_create and crl_sac_create: a TD3 or SAC handle holds two critics and two critic passes' buffers
 // where a DDPG handle holds one; a SAC handle's actor has a head of 2·act_dim rows, and it owns log_alpha, its β-power pair and the alpha records
@@ -936,9 +951,6 @@ static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* to
   return 0;
 }
 
-// the three kinds of handle: 0 DDPG, 1 TD3, 2 SAC
-static const char* const KIND[3] = {"ddpg", "td3", "sac"};
-static int kind_of(const crl_ddpg* h) { return h->sac ? 2 : h->td3 ? 1 : 0; }
 static const char NO_TWIN[] = "";
 // the DDPG parameter calls know one critic, the crl_td3_* ones two, the crl_sac_* ones two and another actor: each refuses the other kinds of handle
 // and names its twin: the call of the same name for the handle's kind, or `twin` where that call has another name (NO_TWIN: a call only SAC has).
@@ -1202,6 +1214,53 @@ static int32_t ddpg_q_eval(crl_ddpg* h, int which, const double* obs, const doub
   return 0;
 }
 
+// the parameter calls of a two-critic handle, behind crl_td3_* (want = 1) and crl_sac_* (want = 2); fn = the caller's name
+static int32_t twin_q_values(crl_ddpg* h, int want, const char* fn, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, want, fn)) return 1;
+  const std::string k = std::string("crl_") + KIND[want];
+  if (!h->params_set) { set_error(std::string(fn) + ": parameters not set — " + k + "_write_params or " + k + "_init_params first"); return 1; }
+  if (n < 0 || (n > 0 && (!obs || !act))) { set_error(std::string(fn) + ": bad arguments"); return 1; }
+  if (n == 0) return 0;
+  if (q1 && ddpg_q_eval(h, 0, obs, act, n, q1)) return 1;
+  if (q2 && ddpg_q_eval(h, 1, obs, act, n, q2)) return 1;
+  return 0;
+}
+// the targets are copies, as ddpg.jl:53-54; a SAC handle has no target actor
+static int32_t twin_write_params(crl_ddpg* h, int want, const char* fn, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n,
+                                 const float* critic2, size_t critic2_n) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, want, fn)) return 1;
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
+    set_error(std::string(fn) + ": expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
+  }
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  for (float* dst : {h->d.actor, h->d.actor_t}) if (dst) CRL_HIP_CHECK(hipMemcpy(dst, actor, na * 4, hipMemcpyHostToDevice));
+  for (float* dst : {h->d.critic, h->d.critic_t}) {
+    CRL_HIP_CHECK(hipMemcpy(dst, critic1, nc * 4, hipMemcpyHostToDevice));
+    CRL_HIP_CHECK(hipMemcpy(dst + nc, critic2, nc * 4, hipMemcpyHostToDevice));
+  }
+  h->params_set = true;
+  return 0;
+}
+// every pointer may be NULL; target_actor is one of TD3's, log_alpha one of SAC's
+static int32_t twin_read_params(crl_ddpg* h, int want, const char* fn, float* actor, float* critic1, float* critic2, float* target_actor,
+                                float* target_critic1, float* target_critic2, float* log_alpha) {
+  DDPG_GUARD(h);
+  if (wrong_kind(h, want, fn)) return 1;
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
+  if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
+  if (critic1) CRL_HIP_CHECK(hipMemcpy(critic1, h->d.critic, nc * 4, hipMemcpyDeviceToHost));
+  if (critic2) CRL_HIP_CHECK(hipMemcpy(critic2, h->d.critic + nc, nc * 4, hipMemcpyDeviceToHost));
+  if (target_actor) CRL_HIP_CHECK(hipMemcpy(target_actor, h->d.actor_t, na * 4, hipMemcpyDeviceToHost));
+  if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
+  if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
+  if (log_alpha) CRL_HIP_CHECK(hipMemcpy(log_alpha, h->sd.log_alpha, 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 extern "C" {
 
 int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* out) {
@@ -1213,32 +1272,12 @@ int32_t crl_ddpg_q_values(crl_ddpg* h, const double* obs, const double* act, int
 }
 
 int32_t crl_td3_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 1, "crl_td3_q_values")) return 1;
-  if (!h->params_set) { set_error("crl_td3_q_values: parameters not set — crl_td3_write_params or crl_td3_init_params first"); return 1; }
-  if (n < 0 || (n > 0 && (!obs || !act))) { set_error("crl_td3_q_values: bad arguments"); return 1; }
-  if (n == 0) return 0;
-  if (q1 && ddpg_q_eval(h, 0, obs, act, n, q1)) return 1;
-  if (q2 && ddpg_q_eval(h, 1, obs, act, n, q2)) return 1;
-  return 0;
+  return twin_q_values(h, 1, "crl_td3_q_values", obs, act, n, q1, q2);
 }
 
 int32_t crl_td3_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n, const float* critic2,
                              size_t critic2_n) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 1, "crl_td3_write_params")) return 1;
-  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
-  if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
-    set_error("crl_td3_write_params: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
-  }
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  for (float* dst : {h->d.actor, h->d.actor_t}) CRL_HIP_CHECK(hipMemcpy(dst, actor, na * 4, hipMemcpyHostToDevice));
-  for (float* dst : {h->d.critic, h->d.critic_t}) {                                       // the targets are copies, as ddpg.jl:53-54
-    CRL_HIP_CHECK(hipMemcpy(dst, critic1, nc * 4, hipMemcpyHostToDevice));
-    CRL_HIP_CHECK(hipMemcpy(dst + nc, critic2, nc * 4, hipMemcpyHostToDevice));
-  }
-  h->params_set = true;
-  return 0;
+  return twin_write_params(h, 1, "crl_td3_write_params", actor, actor_n, critic1, critic1_n, critic2, critic2_n);
 }
 int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed) {
   DDPG_GUARD(h);
@@ -1250,26 +1289,12 @@ int32_t crl_td3_init_params(crl_ddpg* h, uint64_t seed) {
 }
 int32_t crl_td3_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* target_actor, float* target_critic1,
                             float* target_critic2) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 1, "crl_td3_read_params")) return 1;
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
-  if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
-  if (critic1) CRL_HIP_CHECK(hipMemcpy(critic1, h->d.critic, nc * 4, hipMemcpyDeviceToHost));
-  if (critic2) CRL_HIP_CHECK(hipMemcpy(critic2, h->d.critic + nc, nc * 4, hipMemcpyDeviceToHost));
-  if (target_actor) CRL_HIP_CHECK(hipMemcpy(target_actor, h->d.actor_t, na * 4, hipMemcpyDeviceToHost));
-  if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
-  if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return twin_read_params(h, 1, "crl_td3_read_params", actor, critic1, critic2, target_actor, target_critic1, target_critic2, nullptr);
 }
 
 // ---- SAC: the crl_sac_* block
 int32_t crl_sac_param_count(int32_t obs_dim, int32_t act_dim, int64_t* actor_n, int64_t* critic_n) {
-  if (obs_dim < 1 || obs_dim > DDPG_MAX_OBS) { set_error("crl_sac_param_count: obs_dim must be in 1..64"); return 1; }
-  if (act_dim < 1 || act_dim > DDPG_MAX_ACT) { set_error("crl_sac_param_count: act_dim must be in 1..16"); return 1; }
-  if (actor_n) *actor_n = net_off(obs_dim, 2 * act_dim).N;
-  if (critic_n) *critic_n = net_off(obs_dim + act_dim, 1).N;
-  return 0;
+  return param_count("crl_sac_param_count", obs_dim, act_dim, 2, actor_n, critic_n);
 }
 
 int32_t crl_sac_create(const crl_ddpg_config* cfg, const crl_sac_options* opt, int32_t device, crl_ddpg** out) {
@@ -1287,20 +1312,7 @@ int32_t crl_sac_create(const crl_ddpg_config* cfg, const crl_sac_options* opt, i
 
 int32_t crl_sac_write_params(crl_ddpg* h, const float* actor, size_t actor_n, const float* critic1, size_t critic1_n, const float* critic2,
                              size_t critic2_n) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 2, "crl_sac_write_params")) return 1;
-  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
-  if (!actor || !critic1 || !critic2 || actor_n != na || critic1_n != nc || critic2_n != nc) {
-    set_error("crl_sac_write_params: expected " + std::to_string(na) + " actor floats and " + std::to_string(nc) + " floats for each critic"); return 1;
-  }
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  CRL_HIP_CHECK(hipMemcpy(h->d.actor, actor, na * 4, hipMemcpyHostToDevice));
-  for (float* dst : {h->d.critic, h->d.critic_t}) {                                       // the targets are copies
-    CRL_HIP_CHECK(hipMemcpy(dst, critic1, nc * 4, hipMemcpyHostToDevice));
-    CRL_HIP_CHECK(hipMemcpy(dst + nc, critic2, nc * 4, hipMemcpyHostToDevice));
-  }
-  h->params_set = true;
-  return 0;
+  return twin_write_params(h, 2, "crl_sac_write_params", actor, actor_n, critic1, critic1_n, critic2, critic2_n);
 }
 int32_t crl_sac_init_params(crl_ddpg* h, uint64_t seed) {
   DDPG_GUARD(h);
@@ -1310,27 +1322,10 @@ int32_t crl_sac_init_params(crl_ddpg* h, uint64_t seed) {
   return crl_sac_write_params(h, wa.data(), wa.size(), wc1.data(), wc1.size(), wc2.data(), wc2.size());
 }
 int32_t crl_sac_read_params(crl_ddpg* h, float* actor, float* critic1, float* critic2, float* target_critic1, float* target_critic2, float* log_alpha) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 2, "crl_sac_read_params")) return 1;
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  const size_t na = (size_t)h->na, nc = (size_t)h->nc;
-  if (actor) CRL_HIP_CHECK(hipMemcpy(actor, h->d.actor, na * 4, hipMemcpyDeviceToHost));
-  if (critic1) CRL_HIP_CHECK(hipMemcpy(critic1, h->d.critic, nc * 4, hipMemcpyDeviceToHost));
-  if (critic2) CRL_HIP_CHECK(hipMemcpy(critic2, h->d.critic + nc, nc * 4, hipMemcpyDeviceToHost));
-  if (target_critic1) CRL_HIP_CHECK(hipMemcpy(target_critic1, h->d.critic_t, nc * 4, hipMemcpyDeviceToHost));
-  if (target_critic2) CRL_HIP_CHECK(hipMemcpy(target_critic2, h->d.critic_t + nc, nc * 4, hipMemcpyDeviceToHost));
-  if (log_alpha) CRL_HIP_CHECK(hipMemcpy(log_alpha, h->sd.log_alpha, 4, hipMemcpyDeviceToHost));
-  return 0;
+  return twin_read_params(h, 2, "crl_sac_read_params", actor, critic1, critic2, nullptr, target_critic1, target_critic2, log_alpha);
 }
 int32_t crl_sac_q_values(crl_ddpg* h, const double* obs, const double* act, int32_t n, double* q1, double* q2) {
-  DDPG_GUARD(h);
-  if (wrong_kind(h, 2, "crl_sac_q_values")) return 1;
-  if (!h->params_set) { set_error("crl_sac_q_values: parameters not set — crl_sac_write_params or crl_sac_init_params first"); return 1; }
-  if (n < 0 || (n > 0 && (!obs || !act))) { set_error("crl_sac_q_values: bad arguments"); return 1; }
-  if (n == 0) return 0;
-  if (q1 && ddpg_q_eval(h, 0, obs, act, n, q1)) return 1;
-  if (q2 && ddpg_q_eval(h, 1, obs, act, n, q2)) return 1;
-  return 0;
+  return twin_q_values(h, 2, "crl_sac_q_values", obs, act, n, q1, q2);
 }
 int32_t crl_sac_status_read(crl_ddpg* h, crl_sac_status* out) {
   DDPG_GUARD(h);

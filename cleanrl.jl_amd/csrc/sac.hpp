@@ -1,11 +1,13 @@
 // sac.hpp — SAC on the DDPG handle (the crl_sac_* block of include/cleanrl_hip.h), included by ddpg.hip: the kernels of what SAC adds. The ring, the
-// draw, the env loop, the act / add kernels, the critic step and every building block (actor_hidden, head_row, critic_forward, w2t_row,
-// twin_critic_pass, critic_param_grad, actor_param_grad, adam_entry, ddpg_collect, ddpg_act) are ddpg.hip's, called here. A SAC handle's critic,
+// draw, the env loop, the act / add kernels, the critic step and every building block (actor_hidden, head_row, critic_forward, twin_target_pass and
+// its critic_td_pass, critic_action_grad, actor_backprop, actor_adam_entry = net_param_grad + adam_step_entry, twin_polyak_tail, actor_eval_column,
+// ddpg_collect, ddpg_act) are ddpg.hip's, called here ("One function per job"). A SAC handle's critic,
 // critic_t, mc, vc, cH1 .. sq are laid out as a TD3 handle's ([2][...]); its actor has a head of 2·act_dim rows (aD3 is [k][2A]); actor_t and aY are not allocated;
 // betap holds 19 pairs: the actor's six arrays, critic 1's, critic 2's, log_alpha's. One cycle:
 //   A   ddpg_sample_kernel  unchanged
 //   B'' sac_critic_kernel   one block per sample, two waves, wave w = critic w: the actor on next_state and the sampled a', logπ' (both waves, each
-//                           into its own LDS), target critic w, the min through LDS, the entropy term, then twin_critic_pass
+//                           into its own LDS), target critic w, the min through LDS, the entropy term, then critic_td_pass: twin_target_pass with
+//                           SAC's two functors
 //   C'' td3_critic_step     unchanged
 //   D'' sac_actor_kernel    one block per sample, two waves: the actor on state and the sampled a, logπ (both waves); wave w runs the UPDATED critic w
 //                           and its pullback to ∂(−Q_w/k)/∂a; the selected one goes through LDS; then δ3 (2A wide), δ2, δ1 (both waves alike, wave 0
@@ -81,25 +83,20 @@ __global__ void __launch_bounds__(128) sac_critic_kernel(DDPGDev a, SACDev sd) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
   __shared__ double xs[2][DDPG_MAX_IN], h1s[2][GH], h2s[2][GH], zs[2][SAC_MAX_HEAD], lps[2][DDPG_MAX_ACT], qs[2], d2s[2][GH];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.x, D = a.cfg.obs_dim, NI = D + a.cfg.act_dim;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, D = a.cfg.obs_dim;
   const uint64_t gstep = (uint64_t)a.ctl->global_step;
-  const size_t s = (size_t)a.idx[b];
-  const NetOff o = net_off(NI, 1);
-  const float* const critic = a.critic + (size_t)w * o.N;
-  const float* const critic_t = a.critic_t + (size_t)w * o.N;
   const double alpha = sac_alpha(sd);
-  double h1, h2, eps = 0.0;
-  SacDraw d{};
-  for (int i = lane; i < D; i += GH) xs[w][i] = a.rb_next[D * s + i];
-  __syncthreads();
-  sac_actor_head(a.actor, D, a.cfg.act_dim, xs[w], h1s[w], h2s[w], zs[w], lane, h1, h2);
-  const double lp = sac_sample(a, zs[w], (uint32_t)(16 * b), gstep, S_SAC_NEXT, xs[w] + D, lps[w], lane, d, eps);
-  critic_forward(critic_t, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, h1, h2);          // its last barrier publishes both qs
-  const double q1 = qs[0], q2 = qs[1];
-  const double next_q = q2 < q1 ? q2 : q1;
-  const double td = a.rb_reward[s] + (a.cfg.gamma * (1.0 - (double)a.rb_terminal[s])) * (next_q - alpha * lp);
-  __syncthreads();
-  twin_critic_pass(a, critic, td, xs[w], h1s[w], h2s[w], &qs[w], d2s[w], lane, w, b, s);
+  double lp = 0.0;                                                                    // logπ(a' | next_state), from the first functor to the second
+  twin_target_pass(a, xs[w], h1s[w], h2s[w], qs, d2s[w], lane, w, [&](int b) {
+#pragma clang fp contract(off)
+    double h1, h2, eps = 0.0;
+    SacDraw d{};
+    sac_actor_head(a.actor, D, a.cfg.act_dim, xs[w], h1s[w], h2s[w], zs[w], lane, h1, h2);
+    lp = sac_sample(a, zs[w], (uint32_t)(16 * b), gstep, S_SAC_NEXT, xs[w] + D, lps[w], lane, d, eps);
+  }, [&](double next_q, size_t s) {
+#pragma clang fp contract(off)
+    return a.rb_reward[s] + (a.cfg.gamma * (1.0 - (double)a.rb_terminal[s])) * (next_q - alpha * lp);
+  });
 }
 
 // D''.
@@ -122,20 +119,8 @@ __global__ void __launch_bounds__(128) sac_actor_kernel(DDPGDev a, SACDev sd) {
   critic_forward(critic, NI, xs[w], h1s[w], h2s[w], &qs[w], lane, ch1, ch2);          // the updated critic w; publishes both qs
   const double q1 = qs[0], q2 = qs[1];
   const int sel = q2 < q1 ? 1 : 0;
-  // back through critic w: ∂(−Q_w/k)/∂Q_w = −1/k, δ2, δ1, then ∂/∂a[c] = Σ_i W1[i, D + c]·δ1[i], i ascending
-  const double dq = -1.0 / (double)k;
-  ds[w][lane] = ch2 > 0.0 ? (double)critic[oc.W3 + lane] * dq : 0.0;
-  __syncthreads();
-  const double t1 = w2t_row(critic + oc.W2, ds[w], lane);
-  __syncthreads();
-  ds[w][lane] = ch1 > 0.0 ? t1 : 0.0;
-  __syncthreads();
-  if (lane < A) {
-    double ga = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < GH; ++i) ga += (double)critic[oc.W1 + i + GH * (D + lane)] * ds[w][i];
-    gas[w][lane] = ga;
-  }
+  const double gw = critic_action_grad(critic, oc, D, A, -1.0 / (double)k, ch1, ch2, ds[w], lane);   // ∂(−Q_w/k)/∂a: ∂(−Q_w/k)/∂Q_w = −1/k
+  if (lane < A) gas[w][lane] = gw;
   __syncthreads();
   if (lane < A) {                                                                     // the selected critic's ∂/∂a, then through the squash to μ and s
     const double ga = gas[sel][lane], ak = alpha / (double)k;
@@ -149,12 +134,8 @@ __global__ void __launch_bounds__(128) sac_actor_kernel(DDPGDev a, SACDev sd) {
     if (w == 0) { a.aD3[(size_t)(2 * A) * b + lane] = du; a.aD3[(size_t)(2 * A) * b + A + lane] = dsr; }
   }
   __syncthreads();
-  double s2 = 0.0;
-  for (int r = 0; r < 2 * A; ++r) s2 += (double)a.actor[oa.W3 + r + 2 * A * lane] * d3s[w][r];
-  const double d2 = s2 * (1.0 - ah2 * ah2);
-  ds[w][lane] = d2;
-  __syncthreads();
-  const double d1 = w2t_row(a.actor + oa.W2, ds[w], lane) * (1.0 - ah1 * ah1);
+  double d1, d2;
+  actor_backprop(a.actor, oa, 2 * A, d3s[w], ah1, ah2, ds[w], lane, d1, d2);
   if (w == 0) {
     const size_t r = (size_t)GH * b + lane;
     a.aH1[r] = ah1; a.aH2[r] = ah2; a.aD1[r] = d1; a.aD2[r] = d2;
@@ -166,13 +147,9 @@ __global__ void __launch_bounds__(128) sac_actor_kernel(DDPGDev a, SACDev sd) {
 __global__ void __launch_bounds__(64) sac_actor_step(DDPGDev a, SACDev sd, int actor_blocks, int nc2) {
 #pragma clang fp contract(off)
   if (!a.ctl->train_pending) return;
-  if ((int)blockIdx.x >= actor_blocks) {
-    const int t = ((int)blockIdx.x - actor_blocks) * 64 + threadIdx.x;
-    if (t < nc2) a.critic_t[t] = (float)(a.cfg.tau * (double)a.critic[t] + (1.0 - a.cfg.tau) * (double)a.critic_t[t]);
-    return;
-  }
-  const int k = (int)a.cfg.batch_size, D = a.cfg.obs_dim, A = a.cfg.act_dim, p = blockIdx.x * 64 + threadIdx.x;
-  const NetOff o = net_off(D, 2 * A);
+  if ((int)blockIdx.x >= actor_blocks) { twin_polyak_tail(a, actor_blocks, nc2); return; }
+  const int k = (int)a.cfg.batch_size, A = a.cfg.act_dim, p = blockIdx.x * 64 + threadIdx.x;
+  const NetOff o = net_off(a.cfg.obs_dim, 2 * A);
   if (p == 0) {
     const double alpha = sac_alpha(sd), te = sd.opt.target_entropy;
     double sl = 0.0, se = 0.0, sp = 0.0;
@@ -183,19 +160,10 @@ __global__ void __launch_bounds__(64) sac_actor_step(DDPGDev a, SACDev sd, int a
     const double al = -(alpha * (se / (double)k));
     a.ctl->actor_loss = sl / (double)k;
     sd.sctl->alpha = alpha; sd.sctl->alpha_loss = al; sd.sctl->entropy = -(sp / (double)k);
-    if (sd.opt.autotune) {                                                             // ∂alpha_loss/∂log_alpha = alpha_loss
-      const double* bp = a.betap + 2 * SAC_ALPHA_PAIR;
-      float mi, vi, wi;
-      adam_entry((double)(float)al, sd.log_alpha[1], sd.log_alpha[2], sd.log_alpha[0], bp[0], bp[1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, wi);
-      sd.log_alpha[1] = mi; sd.log_alpha[2] = vi; sd.log_alpha[0] = wi;
-    }
+    // ∂alpha_loss/∂log_alpha = alpha_loss; log_alpha[0..3) = the weight, its m, its v
+    if (sd.opt.autotune) adam_step_entry(al, sd.log_alpha, sd.log_alpha + 1, sd.log_alpha + 2, a.betap + 2 * SAC_ALPHA_PAIR, a.cfg.lr, 0);
   }
-  if (p >= o.N) return;
-  const double g = actor_param_grad(a, o, D + A, 2 * A, k, p);
-  const double* bp = a.betap + 2 * net_array(o, p);
-  float mi, vi, wi;
-  adam_entry((double)(float)g, a.ma[p], a.va[p], a.actor[p], bp[0], bp[1], a.cfg.lr, /*clip=*/false, 1.0, mi, vi, wi);
-  a.ma[p] = mi; a.va[p] = vi; a.actor[p] = wi;
+  if (p < o.N) actor_adam_entry(a, o, 2 * A, p);
 }
 
 // the behaviour policy: DDPG's warm-up draw, then a sample from the actor with ε on stream 0x10, component word c
@@ -228,15 +196,13 @@ __global__ void __launch_bounds__(64) sac_act_kernel(DDPGDev a) { ddpg_act(a, sa
 
 // crl_ddpg_actor on a SAC handle: scale·tanh_fast(μ) + bias, one wave per column
 __global__ void __launch_bounds__(64) sac_actor_eval_kernel(DDPGDev a, const double* __restrict__ obs, int n, double* __restrict__ out) {
-#pragma clang fp contract(off)
   __shared__ double xs[DDPG_MAX_IN], h1s[GH], h2s[GH], zs[SAC_MAX_HEAD];
-  const int lane = threadIdx.x, b = blockIdx.x, D = a.cfg.obs_dim, A = a.cfg.act_dim;
-  if (b >= n) return;
-  for (int i = lane; i < D; i += GH) xs[i] = obs[(size_t)D * b + i];
-  __syncthreads();
-  double h1, h2;
-  sac_actor_head(a.actor, D, A, xs, h1s, h2s, zs, lane, h1, h2);
-  if (lane < A) out[(size_t)A * b + lane] = sac_scale(a.cfg) * tanh_fast64(zs[lane]) + sac_bias(a.cfg);
+  actor_eval_column(a, obs, n, out, xs, [&](int lane) {
+#pragma clang fp contract(off)
+    double h1, h2;
+    sac_actor_head(a.actor, a.cfg.obs_dim, a.cfg.act_dim, xs, h1s, h2s, zs, lane, h1, h2);
+    return lane < a.cfg.act_dim ? sac_scale(a.cfg) * tanh_fast64(zs[lane]) + sac_bias(a.cfg) : 0.0;
+  });
 }
 
 }  // namespace crl

@@ -21,7 +21,7 @@ for line in out.splitlines():
         cur = re.sub(r"\(.*", "", cur).replace("void crl::", "")
         rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+(\w[\w ]*\w|\w+)\s*(?:\[bytes/lane\])?: (\S+)", line)
+    m = re.search(r"remark:\s+(\w[\w ]*\w|\w+)\s*(?:\[[\w/]+\])?: (\S+)", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
