@@ -111,6 +111,8 @@ EXPORTS = [
     "crl_make_actor_critic", "crl_ppo_init_params", "crl_a2c_init_params", "crl_dqn_make_nn", "crl_dqn_init_params", "crl_comm_info", "crl_clock_probe", "crl_product_probe", "crl_ppo_iterate_async", "crl_ppo_drain",
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
+    "crl_ppo_create_gaussian", "crl_make_actor_critic_gaussian", "crl_policy_act_gaussian", "crl_logprob_actions_gaussian",
+    "crl_rollout_store_gaussian", "crl_env_step_gaussian",
 ]
 
 DQN_PARAM_COUNT = 10934
@@ -246,15 +248,24 @@ class CrlA2CEpisode(C.Structure):
     _fields_ = [("episode_return", C.c_double), ("episode_length", C.c_int64), ("global_step", C.c_int64)]
 
 
+class GaussianOptions(C.Structure):
+    """crl_ppo_gauss_options: the log-std squash of a Gaussian PPO handle, log_std = min + 0.5 (max - min)(tanh(s) + 1), and its value at initialisation."""
+    _fields_ = [("log_std_min", C.c_float), ("log_std_max", C.c_float), ("init_log_std", C.c_float)]
+
+    def __init__(self, log_std_min=-5.0, log_std_max=2.0, init_log_std=0.0):
+        super().__init__(log_std_min, log_std_max, init_log_std)
+
+
 # crl_field
 F_OBS, F_ACTION, F_LOGPROB, F_REWARD, F_TERMINAL, F_VALUE, F_ADVANTAGE, F_RETURN, F_PERM, F_PARAMS, F_GRADS, F_ADAM_M, \
     F_ADAM_V, F_ENV_STATE, F_CUR_OBS, F_NEXT_DONE, F_ENV_T, F_BETAP, F_ADV_SUMS = range(19)
+FIELD_ACTION_F = 19   # CRL_F_ACTION_F: float (act_dim, nt, k), Gaussian handles only — named apart from the F_* fields every handle can read
 GAE_COMPAT, GAE_FIXED = 0, 1
-ENV_CARTPOLE, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_MOUNTAINCAR, ENV_ACROBOT = 0, 1, 2, 3, 4
+ENV_CARTPOLE, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_MOUNTAINCAR, ENV_ACROBOT, ENV_PENDULUM = 0, 1, 2, 3, 4, 5
 EVAL_GREEDY, EVAL_SAMPLE = 0, 1
 SHUFFLE_FISHER_YATES, SHUFFLE_BIJECTION, SHUFFLE_BLOCKED_FY = 0, 1, 2
 K_ROLLOUT, K_GAE, K_SHUFFLE, K_ADV_STATS, K_UPDATE, K_REDUCE, K_OPTIM, K_ALLREDUCE, K_PACK, K_PERMUTE = range(10)
-KERNEL_NAMES = ["rollout", "gae", "shuffle", "adv_stats", "update", "reduce", "optim", "allreduce", "pack", "permute"]
+KERNEL_NAMES = ["rollout", "gae", "shuffle", "adv_stats", "update", "reduce", "optim", "allreduce", "pack", "permute", "loss"]
 
 _lib = None
 
@@ -273,6 +284,12 @@ def load():
     L.crl_last_error.restype = C.c_char_p
     L.crl_device_count.argtypes = [ip]
     L.crl_ppo_create.argtypes = [C.POINTER(CrlConfig), C.c_int32, C.POINTER(vp)]
+    L.crl_ppo_create_gaussian.argtypes = [C.POINTER(CrlConfig), C.POINTER(GaussianOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_make_actor_critic_gaussian.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(GaussianOptions), C.c_uint64, fp, C.c_size_t]
+    L.crl_policy_act_gaussian.argtypes = [vp, fp, fp, C.c_int32, fp, fp, fp]
+    L.crl_logprob_actions_gaussian.argtypes = [vp, fp, fp, C.c_int32, fp, fp]
+    L.crl_rollout_store_gaussian.argtypes = [vp, C.c_int32, fp, fp, fp, fp, u8p, fp]
+    L.crl_env_step_gaussian.argtypes = [vp, fp, C.c_uint64, fp, fp, u8p]
     L.crl_ppo_destroy.argtypes = [vp]
     L.crl_ppo_param_count.argtypes = [vp, C.POINTER(C.c_int64)]
     L.crl_sync.argtypes = [vp]
@@ -547,6 +564,14 @@ def make_actor_critic_host(obs_dim, n_act, hidden, seed=0):
     return out
 
 
+def make_actor_critic_gaussian_host(obs_dim, act_dim, hidden, opt=None, seed=0):
+    """crl_make_actor_critic_gaussian: make_actor_critic_host for a head of 2 act_dim rows, the s rows' biases at the init_log_std of `opt`."""
+    n = 2 * (hidden * obs_dim + hidden + hidden * hidden + hidden) + 2 * act_dim * (hidden + 1) + hidden + 1
+    out = np.zeros(n, np.float32)
+    check(load().crl_make_actor_critic_gaussian(obs_dim, act_dim, hidden, C.byref(opt) if opt is not None else None, seed, _ptr(out, C.c_float), n))
+    return out
+
+
 def dqn_make_nn_host(seed=0):
     """crl_dqn_make_nn: make_nn(env) of dqn.jl:22-26 (glorot-uniform weights, zero biases), flat in Flux.params order."""
     out = np.zeros(DQN_PARAM_COUNT, np.float32)
@@ -558,17 +583,23 @@ _FIELD_DTYPES = {
     F_OBS: np.float32, F_ACTION: np.int32, F_LOGPROB: np.float32, F_REWARD: np.float32, F_TERMINAL: np.uint8,
     F_VALUE: np.float32, F_ADVANTAGE: np.float32, F_RETURN: np.float32, F_PERM: np.int32, F_PARAMS: np.float32,
     F_GRADS: np.float32, F_ADAM_M: np.float32, F_ADAM_V: np.float32, F_ENV_STATE: np.float32, F_CUR_OBS: np.float32,
-    F_NEXT_DONE: np.uint8, F_ENV_T: np.int32, F_BETAP: np.float64, F_ADV_SUMS: np.float64,
+    F_NEXT_DONE: np.uint8, F_ENV_T: np.int32, F_BETAP: np.float64, F_ADV_SUMS: np.float64, FIELD_ACTION_F: np.float32,
 }
 
 
 class Handle:
     """Owns one crl_ppo (one GPU / one data-parallel shard)."""
 
-    def __init__(self, cfg: CrlConfig, device: int = 0):
+    def __init__(self, cfg: CrlConfig, device: int = 0, gaussian=None):
+        """gaussian: None = the softmax policy (crl_ppo_create); a GaussianOptions (or True for its defaults) = crl_ppo_create_gaussian, where
+        cfg.n_act is act_dim and actions are float (act_dim, ...) arrays."""
         self.cfg = cfg
         self._h = C.c_void_p()
-        check(load().crl_ppo_create(C.byref(cfg), device, C.byref(self._h)))
+        self.gaussian = GaussianOptions() if gaussian is True else gaussian
+        if self.gaussian is None:
+            check(load().crl_ppo_create(C.byref(cfg), device, C.byref(self._h)))
+        else:
+            check(load().crl_ppo_create_gaussian(C.byref(cfg), C.byref(self.gaussian), device, C.byref(self._h)))
         n = C.c_int64()
         check(load().crl_ppo_param_count(self._h, C.byref(n)))
         self.P = n.value
@@ -591,7 +622,7 @@ class Handle:
         nt, k, d, B, P = self.nt, self.k, self.d, self.B, self.P
         return {F_OBS: (d, nt, k), F_PERM: (B,), F_PARAMS: (P,), F_GRADS: (P,), F_ADAM_M: (P,), F_ADAM_V: (P,),
                 F_ENV_STATE: (d, nt), F_CUR_OBS: (d, nt), F_NEXT_DONE: (nt,), F_ENV_T: (nt,), F_BETAP: (24,),
-                F_ADV_SUMS: (2 * self.cfg.num_minibatches,)}.get(f, (nt, k))
+                F_ADV_SUMS: (2 * self.cfg.num_minibatches,), FIELD_ACTION_F: (self.A, nt, k)}.get(f, (nt, k))
 
     def read(self, f):
         out = np.zeros(self._shape(f), _FIELD_DTYPES[f], order="F")
@@ -629,6 +660,43 @@ class Handle:
         check(load().crl_logprob_actions(self._h, _ptr(obs, C.c_float), _ptr(actions, C.c_int32), n, _ptr(logprob, C.c_float),
                                          _ptr(ent, C.c_float)))
         return logprob, ent
+
+    # ---- the float-action twins of a Gaussian handle
+    def policy_act_gaussian(self, obs, xi, with_value=True):
+        """crl_policy_act_gaussian: a = mu + sigma xi on the caller's normals xi (act_dim, n). Returns (action (act_dim, n), logprob, value)."""
+        obs = np.asfortranarray(obs, np.float32)
+        n = obs.shape[1] if obs.ndim == 2 else 1
+        xi = np.asfortranarray(np.asarray(xi, np.float32).reshape((self.A, n), order="F"))
+        action = np.zeros((self.A, n), np.float32, order="F"); logprob = np.zeros(n, np.float32); value = np.zeros(n, np.float32)
+        check(load().crl_policy_act_gaussian(self._h, _ptr(obs, C.c_float), _ptr(xi, C.c_float), n, _ptr(action, C.c_float),
+                                             _ptr(logprob, C.c_float), _ptr(value, C.c_float) if with_value else None))
+        return action, logprob, value
+
+    def logprob_actions_gaussian(self, obs, actions):
+        """crl_logprob_actions_gaussian: (logprob[n], entropy[n]) of float actions (act_dim, n)."""
+        obs = np.asfortranarray(obs, np.float32)
+        n = obs.shape[1]
+        actions = np.asfortranarray(np.asarray(actions, np.float32).reshape((self.A, n), order="F"))
+        logprob = np.zeros(n, np.float32); ent = np.zeros(n, np.float32)
+        check(load().crl_logprob_actions_gaussian(self._h, _ptr(obs, C.c_float), _ptr(actions, C.c_float), n, _ptr(logprob, C.c_float), _ptr(ent, C.c_float)))
+        return logprob, ent
+
+    def rollout_store_gaussian(self, step, obs, action, logprob, reward, terminal, value):
+        obs = np.asfortranarray(obs, np.float32)
+        action = np.asfortranarray(np.asarray(action, np.float32).reshape((self.A, self.nt), order="F"))
+        logprob = np.ascontiguousarray(logprob, np.float32); reward = np.ascontiguousarray(reward, np.float32)
+        terminal = np.ascontiguousarray(terminal, np.uint8); value = np.ascontiguousarray(value, np.float32)
+        check(load().crl_rollout_store_gaussian(self._h, step, _ptr(obs, C.c_float), _ptr(action, C.c_float), _ptr(logprob, C.c_float),
+                                                _ptr(reward, C.c_float), _ptr(terminal, C.c_uint8), _ptr(value, C.c_float)))
+
+    def env_step_gaussian(self, action, gstep=0):
+        """crl_env_step_gaussian: the on-device Pendulum takes the caller's torques. Returns (next_obs (obs_dim, nt), reward, done)."""
+        action = np.ascontiguousarray(action, np.float32)
+        if action.shape != (self.nt,):
+            raise ValueError(f"env_step_gaussian: {self.nt} actions expected, got shape {action.shape}")
+        obs = np.zeros((self.d, self.nt), np.float32, order="F"); reward = np.zeros(self.nt, np.float32); done = np.zeros(self.nt, np.uint8)
+        check(load().crl_env_step_gaussian(self._h, _ptr(action, C.c_float), int(gstep), _ptr(obs, C.c_float), _ptr(reward, C.c_float), _ptr(done, C.c_uint8)))
+        return obs, reward, done
 
     def rollout_store(self, step, obs, action, logprob, reward, terminal, value):
         obs = np.asfortranarray(obs, np.float32); action = np.ascontiguousarray(action, np.int32)

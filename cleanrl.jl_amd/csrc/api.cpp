@@ -10,6 +10,7 @@
 
 #include "env.hpp"
 #include "ppo_ctx.hpp"
+#include "ppo_gauss.hpp"
 #include "stats.hpp"
 
 namespace crl {
@@ -159,8 +160,27 @@ static bool field_ref(crl_ppo* h, int f, FieldRef* out) {
     case CRL_F_ENV_T: *out = {h->env_t, nt * 4}; return true;
     case CRL_F_BETAP: *out = {h->betap, 24 * 8}; return true;
     case CRL_F_ADV_SUMS: *out = {h->adv_sums, (size_t)h->dc.nmb * 2 * 8}; return true;  // current slot
+    case CRL_F_ACTION_F: *out = {h->action_f, B * (size_t)h->act_dim * 4}; return true;
     default: return false;
   }
+}
+
+// the action plane is int32 (nt, k) on a discrete handle and float (act_dim, nt, k) on a Gaussian one: the other field is an error, never a silent read
+static int field_head_mismatch(const crl_ppo* h, int f, const char* who) {
+  if (f == CRL_F_ACTION && h->gauss) { set_error(std::string(who) + ": CRL_F_ACTION is the int32 action plane of a discrete handle — a Gaussian handle keeps float actions in CRL_F_ACTION_F"); return 1; }
+  if (f == CRL_F_ACTION_F && !h->gauss) { set_error(std::string(who) + ": CRL_F_ACTION_F is the float action plane of a Gaussian handle (crl_ppo_create_gaussian) — a discrete handle keeps int32 actions in CRL_F_ACTION"); return 1; }
+  return 0;
+}
+// entry points whose kernels exist for the softmax head only / for the Gaussian head only
+static int need_discrete(const crl_ppo* h, const char* who, const char* instead) {
+  if (!h->gauss) return 0;
+  set_error(std::string(who) + ": not built for Gaussian handles" + (instead ? std::string(" — use ") + instead : std::string(" (crl_ppo_create_gaussian: the softmax-head kernel behind this call has no Gaussian counterpart yet)")));
+  return 1;
+}
+static int need_gauss(const crl_ppo* h, const char* who) {
+  if (h->gauss) return 0;
+  set_error(std::string(who) + " needs a Gaussian handle (crl_ppo_create_gaussian)");
+  return 1;
 }
 
 static int prof_collect(crl_ppo* h) {
@@ -238,9 +258,8 @@ int32_t crl_device_count(int32_t* n) {
   return 0;
 }
 
-int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out) {
-  if (!cfg || !out) { set_error("crl_ppo_create: null argument"); return 1; }
-  *out = nullptr;
+// crl_ppo_create (g == nullptr; cfg as the caller gave it) and crl_ppo_create_gaussian (g = the checked options; cfg->n_act already the head width 2·act_dim)
+static int32_t ppo_create(const crl_ppo_config* cfg, const crl_ppo_gauss_options* g, int32_t device, crl_ppo** out) {
   if (cfg->num_envs <= 0 || cfg->num_steps <= 0 || cfg->num_minibatches <= 0 || cfg->update_epochs <= 0) {
     set_error("crl_ppo_create: num_envs, num_steps, num_minibatches, update_epochs must be positive"); return 1;
   }
@@ -256,6 +275,18 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
     std::string why;
     if (!wide_shape_ok(cfg, &why)) { set_error("unsupported network shape: " + why); return 1; }
   }
+  if (g && !wide) {
+    set_error("crl_ppo_create_gaussian: Gaussian handles are layer-wise only — obs_dim 4 / act_dim 1 / hidden 64 is the shape the route decision sends to the "
+              "4 / 2 / 64 kernels of update.hip, which have no Gaussian head (set CRL_FORCE_WIDE=1 or choose another hidden size)");
+    return 1;
+  }
+  if (g && cfg->env_kind != CRL_ENV_PENDULUM && cfg->env_kind != CRL_ENV_SYNTHETIC && cfg->env_kind != CRL_ENV_EXTERNAL) {
+    set_error("crl_ppo_create_gaussian: env_kind must be CRL_ENV_PENDULUM, CRL_ENV_SYNTHETIC or CRL_ENV_EXTERNAL (the other on-device envs take discrete actions)"); return 1;
+  }
+  if (g && cfg->env_kind == CRL_ENV_PENDULUM && (cfg->obs_dim != PENDULUM_OBS || cfg->n_act != 2)) {
+    set_error("env_kind = CRL_ENV_PENDULUM needs obs_dim=3, act_dim=1"); return 1;
+  }
+  if (!g && cfg->env_kind == CRL_ENV_PENDULUM) { set_error("env_kind = CRL_ENV_PENDULUM takes float actions: create the handle with crl_ppo_create_gaussian"); return 1; }
   static const struct { int kind; const char* name; int obs_dim, n_act; const char* hint; } kEnvShapes[] = {
       {CRL_ENV_CARTPOLE, "CRL_ENV_CARTPOLE", 4, 2, " (use CRL_ENV_SYNTHETIC or CRL_ENV_EXTERNAL)"},
       {CRL_ENV_ACROBOT, "CRL_ENV_ACROBOT", 6, 3, ""},
@@ -266,7 +297,7 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
       set_error(std::string("env_kind = ") + s.name + " needs obs_dim=" + std::to_string(s.obs_dim) + ", n_act=" + std::to_string(s.n_act) + s.hint); return 1;
     }
   if (cfg->env_kind != CRL_ENV_CARTPOLE && cfg->env_kind != CRL_ENV_SYNTHETIC && cfg->env_kind != CRL_ENV_EXTERNAL &&
-      cfg->env_kind != CRL_ENV_MOUNTAINCAR && cfg->env_kind != CRL_ENV_ACROBOT) {
+      cfg->env_kind != CRL_ENV_MOUNTAINCAR && cfg->env_kind != CRL_ENV_ACROBOT && cfg->env_kind != CRL_ENV_PENDULUM) {
     set_error("unknown env_kind"); return 1;
   }
   if (cfg->env_kind == CRL_ENV_SYNTHETIC && !wide) {
@@ -287,6 +318,7 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   crl_ppo* h = new (std::nothrow) crl_ppo();
   if (!h) { set_error("out of host memory"); return 1; }
   h->cfg = *cfg; h->device = device; h->wide = wide;
+  if (g) { h->gauss = true; h->act_dim = cfg->n_act / 2; h->ls_min = g->log_std_min; h->ls_max = g->log_std_max; h->ls_init = g->init_log_std; }
   for (int i = 0; i < OPT_COUNT; ++i) h->opt[i] = kOpts[i].dflt;
   h->window_len = (int)kOpts[OPT_GUARD_WINDOW].dflt;
   if (opt_apply_env(h)) { delete h; return 1; }
@@ -308,6 +340,7 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
     set_error("hipStreamCreate / hipEventCreate failed"); crl_ppo_destroy(h); return 1;
   }
   const size_t B = (size_t)c.B, nt = (size_t)c.nt;
+  if (g) rc |= dalloc(&h->action_f, B * (size_t)h->act_dim);
   rc |= dalloc(&h->obs, B * d); rc |= dalloc(&h->action, B); rc |= dalloc(&h->logprob, B); rc |= dalloc(&h->reward, B);
   rc |= dalloc(&h->terminal, B); rc |= dalloc(&h->value, B); rc |= dalloc(&h->adv, B); rc |= dalloc(&h->ret, B);
   rc |= dalloc(&h->env_state, nt * d); rc |= dalloc(&h->env_t, nt); rc |= dalloc(&h->cur_obs, nt * d);
@@ -363,6 +396,25 @@ int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out)
   return 0;
 }
 
+int32_t crl_ppo_create(const crl_ppo_config* cfg, int32_t device, crl_ppo** out) {
+  if (!cfg || !out) { set_error("crl_ppo_create: null argument"); return 1; }
+  *out = nullptr;
+  return ppo_create(cfg, nullptr, device, out);
+}
+
+static const crl_ppo_gauss_options kGaussDefaults = {-5.0f, 2.0f, 0.0f};
+int32_t crl_ppo_create_gaussian(const crl_ppo_config* cfg, const crl_ppo_gauss_options* opt, int32_t device, crl_ppo** out) {
+  if (!cfg || !out) { set_error("crl_ppo_create_gaussian: null argument"); return 1; }
+  *out = nullptr;
+  const crl_ppo_gauss_options g = opt ? *opt : kGaussDefaults;
+  if (cfg->n_act < 1 || cfg->n_act > GAUSS_AMAX) { set_error("crl_ppo_create_gaussian: n_act is read as act_dim and must be in 1..8, got " + std::to_string(cfg->n_act)); return 1; }
+  if (!(g.log_std_min < g.log_std_max)) { set_error("crl_ppo_create_gaussian: log_std_min must be below log_std_max"); return 1; }
+  if (!(g.init_log_std > g.log_std_min && g.init_log_std < g.log_std_max)) { set_error("crl_ppo_create_gaussian: init_log_std must lie strictly between log_std_min and log_std_max"); return 1; }
+  crl_ppo_config c = *cfg;
+  c.n_act = 2 * cfg->n_act;   // from here on n_act is the head width: parameter table, workspace and GEMMs see a head of 2·act_dim rows
+  return ppo_create(&c, &g, device, out);
+}
+
 int32_t crl_ppo_destroy(crl_ppo* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
@@ -373,7 +425,7 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
   void* ptrs[] = {h->obs, h->action, h->logprob, h->reward, h->terminal, h->value, h->adv, h->ret, h->env_state, h->env_t,
                   h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->next_value, h->ep_stats, h->ep_ring, h->ep_ring_count, h->params,
                   h->adam_m, h->adam_v, h->betap, h->optim_part, h->ticket, h->perm_base, h->recs, h->adv_part, h->perm_tmp, h->bfy_ws, h->bfy_adv_part, h->bfy_bucket_mb, h->bfy_mbid, h->bfy_dig1, h->gpart, h->lpart,
-                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws, h->ext_bad};
+                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws, h->ext_bad, h->action_f};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int s = 0; s < 2; ++s) {
     if (h->status_dev[s]) (void)hipFree(h->status_dev[s]);
@@ -421,6 +473,7 @@ int32_t crl_ppo_write(crl_ppo* h, int32_t field, const void* host, size_t nbytes
   CRL_GUARD(h);
   if (settle(h)) return 1;
   FieldRef fr;
+  if (field_head_mismatch(h, field, "crl_ppo_write")) return 1;
   if (!field_ref(h, field, &fr)) { set_error("crl_ppo_write: unknown field"); return 1; }
   if (nbytes != fr.bytes) { set_error("crl_ppo_write: size mismatch for field " + std::to_string(field) + ": got " +
                                       std::to_string(nbytes) + ", want " + std::to_string(fr.bytes)); return 1; }
@@ -440,7 +493,7 @@ int32_t crl_ppo_write(crl_ppo* h, int32_t field, const void* host, size_t nbytes
   if (field == CRL_F_PARAMS) { wide_mark_params_changed(h); h->params_set = true; }
   if (field == CRL_F_PERM) { h->perm_is_bijection = false; h->slot_fresh &= ~(1u << h->cur_slot); h->bfy_tbl_slots &= ~(1u << h->cur_slot); }
   if (field == CRL_F_PERM || field == CRL_F_ADVANTAGE) h->bfy_adv_parts = 0;  // a caller-supplied permutation has no closed-form inverse
-  if (field == CRL_F_OBS || field == CRL_F_ACTION || field == CRL_F_LOGPROB || field == CRL_F_VALUE || field == CRL_F_ADVANTAGE ||
+  if (field == CRL_F_OBS || field == CRL_F_ACTION || field == CRL_F_ACTION_F || field == CRL_F_LOGPROB || field == CRL_F_VALUE || field == CRL_F_ADVANTAGE ||
       field == CRL_F_RETURN) h->recs_dirty = true;
   if (field == CRL_F_ENV_STATE || field == CRL_F_CUR_OBS) h->env_ready = true;  // caller-supplied env state
   return 0;
@@ -449,7 +502,10 @@ int32_t crl_ppo_write(crl_ppo* h, int32_t field, const void* host, size_t nbytes
 int32_t crl_ppo_init_params(crl_ppo* h, uint64_t seed) {
   CRL_GUARD_SETTLED(h);
   std::vector<float> w((size_t)h->P);
-  if (crl_make_actor_critic(h->cfg.obs_dim, h->cfg.n_act, h->cfg.hidden, seed, w.data(), w.size())) return 1;
+  if (h->gauss) {
+    const crl_ppo_gauss_options g = {h->ls_min, h->ls_max, h->ls_init};
+    if (crl_make_actor_critic_gaussian(h->cfg.obs_dim, h->act_dim, h->cfg.hidden, &g, seed, w.data(), w.size())) return 1;
+  } else if (crl_make_actor_critic(h->cfg.obs_dim, h->cfg.n_act, h->cfg.hidden, seed, w.data(), w.size())) return 1;
   return crl_ppo_write(h, CRL_F_PARAMS, w.data(), w.size() * sizeof(float));
 }
 
@@ -457,6 +513,7 @@ int32_t crl_ppo_read(crl_ppo* h, int32_t field, void* host, size_t nbytes) {
   CRL_GUARD(h);
   if (settle(h)) return 1;
   FieldRef fr;
+  if (field_head_mismatch(h, field, "crl_ppo_read")) return 1;
   if (!field_ref(h, field, &fr)) { set_error("crl_ppo_read: unknown field"); return 1; }
   if (nbytes != fr.bytes) { set_error("crl_ppo_read: size mismatch for field " + std::to_string(field) + ": got " +
                                       std::to_string(nbytes) + ", want " + std::to_string(fr.bytes)); return 1; }
@@ -469,6 +526,7 @@ int32_t crl_policy_act(crl_ppo* h, const float* obs, const double* u, int32_t n,
                        float* value) {
   CRL_GUARD_SETTLED(h);
   CRL_NEED_PARAMS(h, "crl_policy_act");
+  if (need_discrete(h, "crl_policy_act", "crl_policy_act_gaussian")) return 1;
   if (n < 0 || (n > 0 && (!obs || !u || !action || !logprob))) { set_error("crl_policy_act: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t d = (size_t)h->dc.D, N = (size_t)n;
@@ -491,6 +549,7 @@ int32_t crl_logprob_actions(crl_ppo* h, const float* obs, const int32_t* actions
                             float* entropy) {
   CRL_GUARD_SETTLED(h);
   CRL_NEED_PARAMS(h, "crl_logprob_actions");
+  if (need_discrete(h, "crl_logprob_actions", "crl_logprob_actions_gaussian")) return 1;
   if (n < 0 || (n > 0 && (!obs || !actions || !logprob || !entropy))) { set_error("crl_logprob_actions: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t d = (size_t)h->dc.D, A = (size_t)h->dc.A, N = (size_t)n;
@@ -553,11 +612,71 @@ int32_t crl_gae_opt(int32_t device, const float* value, const float* reward, con
 int32_t crl_rollout_store(crl_ppo* h, int32_t step, const float* obs, const int32_t* action, const float* logprob,
                           const float* reward, const uint8_t* terminal, const float* value) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_rollout_store", "crl_rollout_store_gaussian")) return 1;
   if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_store: step out of range"); return 1; }
   if (!obs || !action || !logprob || !reward || !terminal || !value) { set_error("crl_rollout_store: null argument"); return 1; }
   const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D, off = nt * (size_t)step;
   CRL_HIP_CHECK(hipMemcpyAsync(h->obs + off * d, obs, nt * d * 4, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(h->action + off, action, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->logprob + off, logprob, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->reward + off, reward, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->terminal + off, terminal, nt, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->value + off, value, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));  // host buffers are only borrowed for the call
+  h->recs_dirty = true;
+  return 0;
+}
+
+// ---- the float-action twins of a Gaussian handle (ppo_gauss.hip): the same staging as the calls above them
+int32_t crl_policy_act_gaussian(crl_ppo* h, const float* obs, const float* xi, int32_t n, float* action, float* logprob, float* value) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_policy_act_gaussian")) return 1;
+  CRL_NEED_PARAMS(h, "crl_policy_act_gaussian");
+  if (n < 0 || (n > 0 && (!obs || !xi || !action || !logprob))) { set_error("crl_policy_act_gaussian: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  const size_t d = (size_t)h->dc.D, ad = (size_t)h->act_dim, N = (size_t)n;
+  const size_t o_obs = 0, o_xi = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_act = o_xi + N * ad * 4, o_lp = o_act + N * ad * 4, o_val = o_lp + N * 4,
+               total = o_val + N * 4;
+  if (ensure_stage(h, total)) return 1;
+  char* s = static_cast<char*>(h->stage);
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_xi, xi, N * ad * 4, hipMemcpyHostToDevice, h->stream));
+  if (wide_policy_act_gauss(h, (const float*)(s + o_obs), (const float*)(s + o_xi), n, (float*)(s + o_act), (float*)(s + o_lp), value ? (float*)(s + o_val) : nullptr)) return 1;
+  CRL_HIP_CHECK(hipMemcpyAsync(action, s + o_act, N * ad * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
+  if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, s + o_val, N * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_logprob_actions_gaussian(crl_ppo* h, const float* obs, const float* actions, int32_t n, float* logprob, float* entropy) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_logprob_actions_gaussian")) return 1;
+  CRL_NEED_PARAMS(h, "crl_logprob_actions_gaussian");
+  if (n < 0 || (n > 0 && (!obs || !actions || !logprob || !entropy))) { set_error("crl_logprob_actions_gaussian: bad arguments"); return 1; }
+  if (n == 0) return 0;
+  const size_t d = (size_t)h->dc.D, ad = (size_t)h->act_dim, N = (size_t)n;
+  const size_t o_obs = 0, o_act = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_lp = o_act + N * ad * 4, o_ent = o_lp + N * 4, total = o_ent + N * 4;
+  if (ensure_stage(h, total)) return 1;
+  char* s = static_cast<char*>(h->stage);
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, actions, N * ad * 4, hipMemcpyHostToDevice, h->stream));
+  if (wide_logprob_actions_gauss(h, (const float*)(s + o_obs), (const float*)(s + o_act), n, (float*)(s + o_lp), (float*)(s + o_ent))) return 1;
+  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(entropy, s + o_ent, N * 4, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t crl_rollout_store_gaussian(crl_ppo* h, int32_t step, const float* obs, const float* action, const float* logprob, const float* reward,
+                                   const uint8_t* terminal, const float* value) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_rollout_store_gaussian")) return 1;
+  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_store_gaussian: step out of range"); return 1; }
+  if (!obs || !action || !logprob || !reward || !terminal || !value) { set_error("crl_rollout_store_gaussian: null argument"); return 1; }
+  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D, ad = (size_t)h->act_dim, off = nt * (size_t)step;
+  CRL_HIP_CHECK(hipMemcpyAsync(h->obs + off * d, obs, nt * d * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->action_f + off * ad, action, nt * ad * 4, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(h->logprob + off, logprob, nt * 4, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(h->reward + off, reward, nt * 4, hipMemcpyHostToDevice, h->stream));
   CRL_HIP_CHECK(hipMemcpyAsync(h->terminal + off, terminal, nt, hipMemcpyHostToDevice, h->stream));
@@ -591,6 +710,7 @@ int32_t crl_rollout_run(crl_ppo* h) {
 
 int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_env_step", "crl_env_step_gaussian")) return 1;
   if (need_stateful_env(h, "crl_env_step")) return 1;
   if (!action) { set_error("crl_env_step: null action"); return 1; }
   if (ensure_env(h)) return 1;
@@ -611,9 +731,29 @@ int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* n
   return 0;
 }
 
+int32_t crl_env_step_gaussian(crl_ppo* h, const float* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_env_step_gaussian")) return 1;
+  if (!env_continuous(h->cfg.env_kind)) { set_error("crl_env_step_gaussian needs the on-device continuous env (CRL_ENV_PENDULUM)"); return 1; }
+  if (!action) { set_error("crl_env_step_gaussian: null action"); return 1; }
+  if (ensure_env(h)) return 1;
+  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D;
+  const size_t o_act = 0, o_rew = o_act + nt * 4, o_done = o_rew + nt * 4, total = o_done + nt;
+  if (ensure_stage(h, total)) return 1;
+  char* s = static_cast<char*>(h->stage);
+  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, action, nt * 4, hipMemcpyHostToDevice, h->stream));
+  if (gauss_env_step(h, (const float*)(s + o_act), gstep, (float*)(s + o_rew), (uint8_t*)(s + o_done))) return 1;
+  if (next_obs) CRL_HIP_CHECK(hipMemcpyAsync(next_obs, h->cur_obs, nt * d * 4, hipMemcpyDeviceToHost, h->stream));
+  if (reward) CRL_HIP_CHECK(hipMemcpyAsync(reward, s + o_rew, nt * 4, hipMemcpyDeviceToHost, h->stream));
+  if (done) CRL_HIP_CHECK(hipMemcpyAsync(done, s + o_done, nt, hipMemcpyDeviceToHost, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  return 0;
+}
+
 // Held-out evaluation (csrc/eval.hip): argument checks, scratch, ONE launch, the per-episode arrays back to the host, the report in Float64.
 int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report* report, float* returns, int32_t* lengths, int32_t* trace_action) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_ppo_evaluate", nullptr)) return 1;
   if (!cfg || !report) { set_error("crl_ppo_evaluate: null cfg or report"); return 1; }
   if (need_stateful_env(h, "crl_ppo_evaluate")) return 1;
   if (cfg->num_envs < 1) { set_error("crl_ppo_evaluate: num_envs must be >= 1, got " + std::to_string(cfg->num_envs)); return 1; }
@@ -664,6 +804,7 @@ int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report
 // Update diagnostics (csrc/diag.hip): ONE read-only launch over the resident buffer with the current parameters; the block records are added on the host.
 int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_ppo_diagnose", nullptr)) return 1;
   if (!out) { set_error("crl_ppo_diagnose: null out"); return 1; }
   CRL_NEED_PARAMS(h, "crl_ppo_diagnose");
   return launch_diag(h, out, new_logprob, new_value);
@@ -671,7 +812,7 @@ int32_t crl_ppo_diagnose(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, floa
 
 // CRL_ENV_MOUNTAINCAR / CRL_ENV_ACROBOT / CRL_ENV_EXTERNAL (extenv.hip: returns of any sign): the accumulator holds an order-preserving key of the true maximum (stats.hpp: stat_max_key), 0 = no episode
 static double return_max_of(const crl_ppo* h, double raw) {
-  if (!env_signed_returns(h->cfg.env_kind) && h->cfg.env_kind != CRL_ENV_EXTERNAL) return raw;
+  if (!env_signed_returns(h->cfg.env_kind) && h->cfg.env_kind != CRL_ENV_EXTERNAL && !(h->gauss && env_continuous(h->cfg.env_kind))) return raw;
   unsigned long long k; std::memcpy(&k, &raw, 8);
   return stat_max_unkey(k);
 }
@@ -1175,6 +1316,7 @@ int32_t crl_ppo_stream(crl_ppo* h, void** stream) {
 
 int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, int32_t* action_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_rollout_act_device", nullptr)) return 1;
   CRL_NEED_PARAMS(h, "crl_rollout_act_device");
   if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_act_device: step out of range"); return 1; }
   if (!obs_d || !done_d || !action_d) { set_error("crl_rollout_act_device: null argument"); return 1; }
@@ -1190,6 +1332,7 @@ int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, con
 
 int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_rollout_record_device", nullptr)) return 1;
   if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_record_device: step out of range"); return 1; }
   if (!reward_d || !next_obs_d || !next_done_d) { set_error("crl_rollout_record_device: null argument"); return 1; }
   if (peer_enter(h, peer_stream)) return 1;
@@ -1199,6 +1342,7 @@ int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_
 
 int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_env_step_device", nullptr)) return 1;
   if (need_stateful_env(h, "crl_env_step_device")) return 1;
   if (!action_d || !reward_d || !done_d) { set_error("crl_env_step_device: null action, reward or done"); return 1; }
   if (ensure_env(h)) return 1;

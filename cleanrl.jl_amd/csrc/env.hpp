@@ -208,6 +208,56 @@ __device__ __forceinline__ void env_transition(int kind, int stale_obs, float (&
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// PendulumEnv{Float32} — the continuous-action sibling (Gaussian PPO handles: crl_ppo_create_gaussian). Dynamics and reward are the ones ddpg.hip's
+// Float64 Pendulum documents (pendulum_step64), in Float32 with sincos_f32: g = 10, m = l = 1, dt = 0.05, torque clipped to ±2, θ̇ to ±8, θ held in
+// [−π, π), reward = −cost of the state BEFORE the step, done = t >= 200 (the time limit as terminal, like the other envs). State (θ, θ̇), observation
+// (cos θ, sin θ, θ̇). Contraction off. tests/ppo_gauss_ref.py is the Float64 restatement.
+// ------------------------------------------------------------------------------------------------------
+constexpr int PENDULUM_OBS = 3, PENDULUM_STATE = 2;
+__device__ __host__ __forceinline__ bool env_continuous(int kind) { return kind == CRL_ENV_PENDULUM; }
+__device__ __forceinline__ bool pendulum_step(float (&s)[4], int& t, float a0, float& reward) {
+#pragma clang fp contract(off)
+  const float pi = 3.14159265358979324f, two_pi = 6.28318530717958648f, dt = 0.05f;
+  const float th = s[0], thd = s[1];
+  const float u = fminf(fmaxf(a0, -2.0f), 2.0f);
+  const float cost = th * th + 0.1f * (thd * thd) + 0.001f * (u * u);
+  float nthd = thd + (15.0f * sin_f32(th) + 3.0f * u) * dt;
+  nthd = fminf(fmaxf(nthd, -8.0f), 8.0f);
+  float nth = th + nthd * dt;
+  if (nth >= pi) nth = nth - two_pi; else if (nth < -pi) nth = nth + two_pi;
+  s[0] = nth; s[1] = nthd;
+  t += 1;
+  reward = -cost;
+  return t >= ENV_MAX_STEPS_CC;
+}
+// θ ~ U(−π, π) from word x, θ̇ ~ U(−1, 1) from word y of ONE block of the env's reset stream
+__device__ __forceinline__ void pendulum_reset(float (&s)[4], uint64_t seed, uint32_t gid, uint64_t gstep, uint32_t stream) {
+#pragma clang fp contract(off)
+  const u32x4 o = philox_env(seed, gid, gstep, stream);
+  s[0] = 6.28318530717958648f * ((float)(o.x >> 8) * 0x1.0p-24f) - 3.14159265358979324f;
+  s[1] = 2.0f * ((float)(o.y >> 8) * 0x1.0p-24f) - 1.0f;
+  s[2] = 0.0f; s[3] = 0.0f;
+}
+__device__ __forceinline__ void pendulum_observe(const float (&s)[4], float (&o)[ENV_OBS_MAX]) {
+#pragma unroll
+  for (int i = 0; i < ENV_OBS_MAX; ++i) o[i] = 0.0f;
+  sincos_f32(s[0], o[1], o[0]);
+  o[2] = s[1];
+}
+// env_transition for float actions (act[0 … act_dim)): step with the action as it stands (the env clips what it applies), observe, and reset!(env) of a
+// terminated env from reset stream 1 keyed by gstep, exactly as env_transition does for the discrete kinds
+__device__ __forceinline__ void env_transition_c(int kind, int stale_obs, float (&s)[4], int& t, const float* act, uint64_t seed, uint32_t gid,
+                                                 uint64_t gstep, float (&obs)[ENV_OBS_MAX], float& reward, bool& done) {
+  done = pendulum_step(s, t, act[0], reward);       // CRL_ENV_PENDULUM is the one continuous kind
+  pendulum_observe(s, obs);
+  if (done) {
+    pendulum_reset(s, seed, gid, gstep, 1);
+    t = 0;
+    if (!stale_obs) pendulum_observe(s, obs);
+  }
+}
+
 // Synthetic env (oracle: synth_step): obs ~ U(-1,1)^d, reward ~ U(-1,1), done ~ Bernoulli(1/200), all from the env's
 // own Philox stream (streams 8+q for the observation quads, 3 for reward/done). Stateless: a "reset" is a no-op.
 __device__ __forceinline__ float synth_unit(uint32_t o) { return (float)(o >> 8) * 0x1.0p-23f - 1.0f; }

@@ -93,6 +93,20 @@ int32_t crl_make_actor_critic(int32_t obs_dim, int32_t n_act, int32_t hidden, ui
   return 0;
 }
 
+// the Gaussian actor-critic: crl_make_actor_critic's draws for a head of 2·act_dim rows, then the biases of the s rows set so that log_std = init_log_std
+int32_t crl_make_actor_critic_gaussian(int32_t obs_dim, int32_t act_dim, int32_t hidden, const crl_ppo_gauss_options* opt, uint64_t seed, float* out, size_t n) {
+  const crl_ppo_gauss_options g = opt ? *opt : crl_ppo_gauss_options{-5.0f, 2.0f, 0.0f};
+  if (act_dim < 1 || act_dim > 8) { set_error("crl_make_actor_critic_gaussian: act_dim must be in 1..8"); return 1; }
+  if (!(g.log_std_min < g.log_std_max)) { set_error("crl_make_actor_critic_gaussian: log_std_min must be below log_std_max"); return 1; }
+  if (!(g.init_log_std > g.log_std_min && g.init_log_std < g.log_std_max)) { set_error("crl_make_actor_critic_gaussian: init_log_std must lie strictly between log_std_min and log_std_max"); return 1; }
+  if (crl_make_actor_critic(obs_dim, 2 * act_dim, hidden, seed, out, n)) return 1;
+  const size_t h = (size_t)hidden, d = (size_t)obs_dim, A = 2 * (size_t)act_dim;
+  float* b3 = out + (h * d + h) + (h * h + h) + A * h;   // the actor head's bias
+  const double s0 = std::atanh(2.0 * ((double)g.init_log_std - (double)g.log_std_min) / ((double)g.log_std_max - (double)g.log_std_min) - 1.0);
+  for (int i = 0; i < act_dim; ++i) b3[act_dim + i] = (float)s0;
+  return 0;
+}
+
 int32_t crl_dqn_make_nn(uint64_t seed, float* out, size_t n) {
   if (!out || n != (size_t)CRL_DQN_PARAM_COUNT) { set_error("crl_dqn_make_nn: expected 10934 floats"); return 1; }
   crl::Rng rng{seed ^ 0xD09ull};

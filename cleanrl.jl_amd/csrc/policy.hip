@@ -825,6 +825,7 @@ int launch_next_value(crl_ppo* h) {
 
 int launch_env_reset(crl_ppo* h) {
   if (h->cfg.env_kind == CRL_ENV_SYNTHETIC) return wide_env_reset(h);
+  if (h->cfg.env_kind == CRL_ENV_PENDULUM) return gauss_env_reset(h);   // ppo_gauss.hip
   if (h->cfg.env_kind == CRL_ENV_MOUNTAINCAR || h->cfg.env_kind == CRL_ENV_ACROBOT) {
     hipLaunchKernelGGL(env_reset_kind_kernel, dim3((h->dc.nt + 255) / 256), dim3(256), 0, h->stream, h->dc, h->env_state, h->env_t,
                        h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->ep_stats);

@@ -201,6 +201,11 @@ struct crl_ppo {
   bool wide = false;
   void* wide_ws = nullptr;
 
+  // Gaussian policy (crl_ppo_create_gaussian; ppo_gauss.hpp): the actor head has 2·act_dim rows (cfg.n_act and dc.A hold that head width), actions are
+  // act_dim floats per sample in action_f (act_dim, nt, k) and the int32 action plane is unused
+  bool gauss = false; int act_dim = 0; float ls_min = 0.0f, ls_max = 0.0f, ls_init = 0.0f;
+  float* action_f = nullptr;
+
   int64_t opt[crl::OPT_COUNT] = {};   // crl_ppo_set_option
 
   int prof = 0;   // 0 off, 1 every kernel class (events recorded around the launches), 2 only the kernels whose events ride ON the dispatch
@@ -256,6 +261,7 @@ int launch_policy_act(crl_ppo* h, const float* obs_d, const double* u_d, int n, 
                       float* value_d);
 int launch_logprob_actions(crl_ppo* h, const float* obs_d, const int32_t* act_d, int n, float* logprob_d, float* ent_d);
 int launch_env_reset(crl_ppo* h);
+int gauss_env_reset(crl_ppo* h);   // ppo_gauss.hip: CRL_ENV_PENDULUM
 int launch_env_step(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* reward_d, uint8_t* done_d, uint32_t* bad_d);
 int launch_rollout(crl_ppo* h, bool fuse_gae = false);
 bool rollout_can_fuse_gae(const crl_ppo* h);
@@ -288,6 +294,8 @@ void wide_mark_params_changed(crl_ppo* h);
 bool wide_x2_active(const crl_ppo* h);
 int wide_policy_act(crl_ppo* h, const float* obs_d, const double* u_d, int n, int32_t* action_d, float* logprob_d, float* value_d);
 int wide_logprob_actions(crl_ppo* h, const float* obs_d, const int32_t* act_d, int n, float* logprob_d, float* ent_d);
+int wide_policy_act_gauss(crl_ppo* h, const float* obs_d, const float* xi_d, int n, float* action_d, float* logprob_d, float* value_d);
+int wide_logprob_actions_gauss(crl_ppo* h, const float* obs_d, const float* act_d, int n, float* logprob_d, float* ent_d);
 int wide_next_value(crl_ppo* h);
 int wide_env_reset(crl_ppo* h);
 int wide_rollout(crl_ppo* h);

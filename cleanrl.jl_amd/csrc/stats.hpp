@@ -7,11 +7,12 @@
 namespace crl {
 
 // "Training Statistics" (ppo.jl:247) from the (all-reduced) sums msg[P..P+3]; mode 0 also raises the value-loss
-// speculation flag (u > 0), mode 1 is the re-evaluation after the exact critic pass.
+// speculation flag (u > 0), mode 1 is the re-evaluation after the exact critic pass. ent_div: what the entropy sum is a mean over besides the samples —
+// n_act for the softmax head (s1 sums the (n_act, M) matrix −p·log p), 1 for the Gaussian head (s1 = Σ_b H_b, the entropy per sample).
 __device__ __forceinline__ void compute_stats4(float s0, float s1, float s2, float s3, const DevCfg& c, double Mglobal, const double* adv_ms,
-                                               int mb, double* vfix, crl_ppo_stats* out, int mode) {
+                                               int mb, double* vfix, crl_ppo_stats* out, int mode, double ent_div) {
   const double pg = (double)s0 / Mglobal;
-  const double ent = (double)(float)((double)s1 / ((double)c.A * Mglobal));
+  const double ent = (double)(float)((double)s1 / (ent_div * Mglobal));
   const double u = (double)(float)((double)s2 / Mglobal);
   const double vl = 0.5 * (double)(float)((double)s3 / Mglobal);
   if (mode == 0) {
@@ -29,7 +30,7 @@ __device__ __forceinline__ void compute_stats4(float s0, float s1, float s2, flo
 
 __device__ __forceinline__ void compute_stats(const float* msg, int P, const DevCfg& c, double Mglobal, const double* adv_ms,
                                               int mb, double* vfix, crl_ppo_stats* out, int mode) {
-  compute_stats4(msg[P], msg[P + 1], msg[P + 2], msg[P + 3], c, Mglobal, adv_ms, mb, vfix, out, mode);
+  compute_stats4(msg[P], msg[P + 1], msg[P + 2], msg[P + 3], c, Mglobal, adv_ms, mb, vfix, out, mode, (double)c.A);
 }
 
 // return_max of the env kinds whose episode returns can be negative (env_signed_returns, and CRL_ENV_EXTERNAL): ep_stats[3] holds an order-preserving map of

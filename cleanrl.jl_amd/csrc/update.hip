@@ -1009,7 +1009,7 @@ __global__ void __launch_bounds__(64 * RG) reduce_optim_kernel(const float* __re
   if (last) {
     dw_scale_rollover(st.dscale);
     __syncthreads();
-    if (threadIdx.x == 0) compute_stats4(gsum[0], gsum[1], gsum[2], gsum[3], st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, 0);
+    if (threadIdx.x == 0) compute_stats4(gsum[0], gsum[1], gsum[2], gsum[3], st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, 0, (double)st.c.A);
   }
   if (g != 0) return;                       // the optimiser half runs on the block's first wave
   // grid-wide meeting point. Everything that crosses blocks (the Σg² partials, the ticket) moves through agent-scope atomic

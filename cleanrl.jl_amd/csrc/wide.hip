@@ -24,11 +24,13 @@
 #include "optim.hpp"
 #include "policy_rt.hpp"
 #include "ppo_ctx.hpp"
+#include "ppo_gauss.hpp"
 #include "stats.hpp"
+#include "wide_step.hpp"
 
 namespace crl {
 
-constexpr int WXS = 36;    // LDS stride (floats) of one staged sample row: 32 k + 4 pad → conflict-free ds_read_b128
+constexpr int WXS = 36;   // LDS stride (floats) of one staged sample row: 32 k + 4 pad → conflict-free ds_read_b128
 constexpr int WLS = 24;    // doubles per loss-kernel block partial: pg, Σ-entropy, Σ(v−R²), Σ value term, db3a[16], db3c
 
 enum { EPI_TANH = 0, EPI_BIAS = 1, EPI_DTANH = 2, EPI_STORE = 3 };
@@ -172,7 +174,7 @@ int wide_create(crl_ppo* h) {
     rc |= walloc(&q.pW3, (size_t)w->Ss * H * q.NO);
   }
   rc |= walloc(reinterpret_cast<float**>(&w->lpart), (size_t)w->nlb * WLS * 2);
-  rc |= walloc(&w->wrec, (size_t)h->dc.B * 8);
+  rc |= walloc(&w->wrec, (size_t)h->dc.B * (h->gauss ? 16 : 8));   // Gaussian handles: 64-byte records (ppo_gauss.hip)
   rc |= walloc(reinterpret_cast<float**>(&w->vpart), 1024 * 2);
   if (rc) { wide_destroy(h); return 1; }
   wide_fill_net(h, w, 0); wide_fill_net(h, w, 1);
@@ -1212,17 +1214,7 @@ static int skinny_launch(hipStream_t st, int blocks, const SkinnyArgs& a) {
 // Per-sample pieces shared by the act / logprob / loss kernels (runtime n_act ≤ 16, same operation order as
 // softmax_logsoftmax<A> and sample_weights<A> in common.hpp)
 // ------------------------------------------------------------------------------------------------------
-// softmax_rt / sample_rt: policy_rt.hpp (shared with eval.hip)
-__device__ __forceinline__ float pick_rt(const float (&v)[AMAX], int A, int i) {
-  float r = v[0];
-#pragma unroll
-  for (int a = 1; a < AMAX; ++a) if (a < A) r = (i == a) ? v[a] : r;
-  return r;
-}
-__device__ __forceinline__ void load_logits(const float* Z, int A8, int A, size_t m, float (&z)[AMAX]) {
-#pragma unroll
-  for (int a = 0; a < AMAX; ++a) z[a] = a < A ? Z[(size_t)A8 * m + a] : 0.0f;
-}
+// softmax_rt / sample_rt: policy_rt.hpp (shared with eval.hip); pick_rt / load_logits: wide_step.hpp
 
 // get_action on precomputed logits (ppo.jl:23-31) with caller-supplied uniforms
 __global__ void __launch_bounds__(256) wide_sample_kernel(const float* __restrict__ Z, int A8, int A, const float* __restrict__ V,
@@ -1254,97 +1246,13 @@ __global__ void __launch_bounds__(256) wide_logprob_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------------
 // One rollout step after the two forward passes: sampling, env step, Buffer.add!, episode bookkeeping
-// (ppo.jl:125-165). One thread per env.
+// (ppo.jl:125-165). One thread per env. wide_step_env, with the head as a compile-time tag: wide_step.hpp; the Gaussian head's
+// per-step kernel: ppo_gauss.hip.
 // ------------------------------------------------------------------------------------------------------
-struct WStepArgs {
-  DevCfg c; const float* Z; int A8; const float* V;
-  float* obs; int32_t* action; float* logprob; float* reward; uint8_t* terminal; float* value;
-  float* env_state; int32_t* env_t; float* cur_obs; uint8_t* next_done; float* ep_return; int32_t* ep_length; double* ep_stats;
-  crl_episode_record* ring; uint32_t* ring_count; int ring_cap;
-  uint64_t iteration; int step;
-};
-
-// A lane's running return_max. CartPole / synthetic keep max(0, ·) (their accumulator is ordered as an unsigned bit pattern, which holds for values >= 0);
-// kinds whose returns can be negative (env_signed_returns) keep the true maximum of the lane's finished episodes: st_n says whether there was one yet.
-__device__ __forceinline__ double step_stat_max(int kind, double st_n, double st_max, double ep_ret) {
-  if (!env_signed_returns(kind)) return fmax(st_max, fmax(0.0, ep_ret));
-  return st_n > 1.0 ? fmax(st_max, ep_ret) : ep_ret;
-}
-// one env, one step; the episode statistics of a finished episode are added to the caller's running sums. zreg: the env's logits when the caller holds them
-// in registers (else they come from a.Z); xout: receives the env's next observation (16 floats, zero beyond obs_dim) besides cur_obs; a.V may be null (the
-// caller fills the value buffer later: wide_rs_rollout_kernel)
-__device__ __forceinline__ void wide_step_env(const WStepArgs& a, int e, int step, double& st_n, double& st_ret, double& st_len, double& st_max,
-                                              const float* zreg = nullptr, float* xout = nullptr) {
-  const DevCfg& c = a.c;
-  const int D = c.D, A = c.A;
-  const uint32_t gid = c.env_id_offset + (uint32_t)e;
-  const uint64_t gstep = a.iteration * (uint64_t)c.k + (uint64_t)step;
-  const size_t b = (size_t)e + (size_t)c.nt * step;
-  int ep_len = a.ep_length[e] + 1;                                   // ppo.jl:125
-  float z[AMAX], p[AMAX], lp[AMAX];
-  if (zreg) {
-#pragma unroll
-    for (int i = 0; i < AMAX; ++i) z[i] = (i < A && i < 8) ? zreg[i & 7] : 0.0f;
-  } else load_logits(a.Z, a.A8, A, (size_t)e, z);
-  softmax_rt(z, A, p, lp);                                          // ppo.jl:127 get_action
-  const double u = u53(philox_env(c.seed, gid, gstep, 0));
-  const int act = sample_rt(p, A, u);
-  const float lpa = pick_rt(lp, A, act);
-  float* co = a.cur_obs + (size_t)D * e;
-  float* es = a.env_state + (size_t)D * e;
-  float* ob = a.obs + b * (size_t)D;
-  for (int i = 0; i < D; ++i) ob[i] = co[i];                        // ppo.jl:133-140 Buffer.add!
-  a.action[b] = act; a.logprob[b] = lpa; a.terminal[b] = a.next_done[e]; if (a.V) a.value[b] = a.V[e];
-  bool done; float rew;
-  if (env_stateful(c.env_kind)) {
-    const int ns = env_state_dim(c.env_kind);
-    float s[4], so[ENV_OBS_MAX];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] = i < ns ? es[i] : 0.0f;
-    int t_env = a.env_t[e];
-    env_transition(c.env_kind, c.stale_obs, s, t_env, act, c.seed, gid, gstep, so, rew, done);   // ppo.jl:130-132,143,164
-#pragma unroll
-    for (int i = 0; i < ENV_OBS_MAX; ++i) if (i < D) { co[i] = so[i]; es[i] = i < ns ? s[i] : 0.0f; }
-    a.env_t[e] = t_env;
-    if (xout) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) xout[i] = (i < ENV_OBS_MAX && i < D) ? so[i] : 0.0f;
-    }
-  } else {
-    if (xout) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) xout[i] = 0.0f;
-    }
-    for (int q = 0; 4 * q < D; ++q) {
-      float o4[4];
-      synth_obs4(c.seed, gid, gstep, q, o4);
-      for (int i = 0; i < 4 && 4 * q + i < D; ++i) { es[4 * q + i] = o4[i]; co[4 * q + i] = o4[i]; }
-      if (xout) {                                                    // constant indices: the caller's array stays in registers
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq)
-          if (q == qq) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xout[4 * qq + i] = 4 * qq + i < D ? o4[i] : 0.0f;
-          }
-      }
-    }
-    synth_reward_done(c.seed, gid, gstep, rew, done);
-  }
-  a.reward[b] = rew;
-  a.next_done[e] = done ? 1 : 0;                                     // ppo.jl:144
-  float ep_ret = a.ep_return[e] + rew;                               // ppo.jl:145
-  if (done) {                                                        // ppo.jl:147-165
-    st_n += 1.0; st_ret += (double)ep_ret; st_len += (double)ep_len; st_max = step_stat_max(c.env_kind, st_n, st_max, (double)ep_ret);
-    episode_ring_push(a.ring, a.ring_count, a.ring_cap, ep_ret, ep_len, gid, step);
-    ep_ret = 0.0f; ep_len = 0;
-  }
-  a.ep_return[e] = ep_ret; a.ep_length[e] = ep_len;
-}
-
 __global__ void __launch_bounds__(256) wide_step_kernel(WStepArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   double st_n = 0.0, st_ret = 0.0, st_len = 0.0, st_max = 0.0;
-  if (e < a.c.nt) wide_step_env(a, e, a.step, st_n, st_ret, st_len, st_max);
+  if (e < a.c.nt) wide_step_env(a, HeadSoftmax{}, e, a.step, st_n, st_ret, st_len, st_max);
   episode_stats_flush(a.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(a.c.env_kind));
 }
 
@@ -1398,7 +1306,7 @@ __global__ void __launch_bounds__(512, 4) wide_rollout_persist_kernel(WRollArgs 
     __syncthreads();
     int e = m0 + tid;
     asm volatile("" : "+v"(e));          // as above: the dozen per-env addresses are formed per step, not kept across the loop
-    if (tid < 32 && e < nt) wide_step_env(r.s, e, step, st_n, st_ret, st_len, st_max);
+    if (tid < 32 && e < nt) wide_step_env(r.s, HeadSoftmax{}, e, step, st_n, st_ret, st_len, st_max);
     __syncthreads();
   }
   if (tid < 64) episode_stats_flush(r.s.ep_stats, st_n, st_ret, st_len, st_max, env_signed_returns(r.s.c.env_kind));
@@ -1653,7 +1561,7 @@ __global__ void __launch_bounds__(512) wide_rollout_pc_kernel(RollPCArgs r) {
       asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                                      // B_fold: logits and values of the 64 envs are out
       if (wave == 0) {
-        wide_step_env(r.s, m0 + lane, step, st_n, st_ret, st_len, st_max);
+        wide_step_env(r.s, HeadSoftmax{}, m0 + lane, step, st_n, st_ret, st_len, st_max);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
@@ -1872,6 +1780,7 @@ struct WRedArgs {
   int boff[13];                      // first block of every array (256 elements per block; arrays without partials get none)
   const double* lpart; int nlb; float* out; int P; int A;
   int with_stats; StatsArgs st;      // one GPU: the block that folds the loss sums also writes the "Training Statistics" record (no launch of its own)
+  double ent_div;                    // compute_stats4's entropy divisor: n_act (softmax head) | 1 (Gaussian head)
 };
 
 __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
@@ -1917,7 +1826,7 @@ __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
     }
     __syncthreads();
     if (a.with_stats && threadIdx.x == 0)
-      compute_stats4(lsum4[0], lsum4[1], lsum4[2], lsum4[3], a.st.c, a.st.Mglobal, a.st.adv_ms, a.st.mb, a.st.vfix, a.st.out, 1);
+      compute_stats4(lsum4[0], lsum4[1], lsum4[2], lsum4[3], a.st.c, a.st.Mglobal, a.st.adv_ms, a.st.mb, a.st.vfix, a.st.out, 1, a.ent_div);
     return;
   }
   // 256 elements of ONE array per block, 4 threads per element quad: thread (e4, pg) sums partials pg, pg + 4, … of four consecutive elements (16-byte
@@ -1961,9 +1870,9 @@ __global__ void __launch_bounds__(256) wide_reduce_kernel(WRedArgs a) {
   }
 }
 
-__global__ void wide_stats_kernel(const float* __restrict__ msg, int P, StatsArgs st) {
+__global__ void wide_stats_kernel(const float* __restrict__ msg, int P, StatsArgs st, double ent_div) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  compute_stats(msg, P, st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, 1);
+  compute_stats4(msg[P], msg[P + 1], msg[P + 2], msg[P + 3], st.c, st.Mglobal, st.adv_ms, st.mb, st.vfix, st.out, 1, ent_div);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1991,6 +1900,33 @@ int wide_logprob_actions(crl_ppo* h, const float* obs_d, const int32_t* act_d, i
     if (wide_forward(h, 0, obs_d + (size_t)w->D * o, w->D, nullptr, m, w->z, w->A8)) return 1;
     hipLaunchKernelGGL(wide_logprob_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, w->z, w->A8, w->A, act_d + o, m,
                        logprob_d + o, ent_d + (size_t)w->A * o);
+    CRL_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// the Gaussian twins of the two probes: the same forwards, then ppo_gauss.hip's kernels on the head output (xi: the caller's normals, (act_dim, n))
+int wide_policy_act_gauss(crl_ppo* h, const float* obs_d, const float* xi_d, int n, float* action_d, float* logprob_d, float* value_d) {
+  WideWs* w = static_cast<WideWs*>(h->wide_ws);
+  if (ensure_pack(h)) return 1;
+  const size_t ad = (size_t)h->act_dim;
+  for (int o = 0; o < n; o += w->Mw) {
+    const int m = (n - o) < w->Mw ? (n - o) : w->Mw;
+    if (wide_forward(h, 0, obs_d + (size_t)w->D * o, w->D, nullptr, m, w->z, w->A8)) return 1;
+    if (value_d && wide_forward(h, 1, obs_d + (size_t)w->D * o, w->D, nullptr, m, w->v, 1, true)) return 1;
+    gauss_launch_sample(h->stream, gauss_dist(h), w->z, w->A8, w->v, xi_d + ad * o, m, action_d + ad * o, logprob_d + o, value_d ? value_d + o : nullptr);
+    CRL_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+int wide_logprob_actions_gauss(crl_ppo* h, const float* obs_d, const float* act_d, int n, float* logprob_d, float* ent_d) {
+  WideWs* w = static_cast<WideWs*>(h->wide_ws);
+  if (ensure_pack(h)) return 1;
+  const size_t ad = (size_t)h->act_dim;
+  for (int o = 0; o < n; o += w->Mw) {
+    const int m = (n - o) < w->Mw ? (n - o) : w->Mw;
+    if (wide_forward(h, 0, obs_d + (size_t)w->D * o, w->D, nullptr, m, w->z, w->A8)) return 1;
+    gauss_launch_logprob(h->stream, gauss_dist(h), w->z, w->A8, act_d + ad * o, m, logprob_d + o, ent_d + o);
     CRL_HIP_CHECK(hipGetLastError());
   }
   return 0;
@@ -2031,6 +1967,8 @@ static WideRolloutRoute wide_rollout_route(const crl_ppo* h) {
   const bool x2_256 = w->H == 256 && wide_x2(h) && w->D <= 16;
   WideRolloutRoute r;
   r.critic_rs = false;
+  // a Gaussian handle takes the per-step route: the one-launch kernels are instantiated for the softmax head only
+  if (h->gauss) { r.kind = WideRolloutRoute::STEPWISE; return r; }
   if ((rs & 2) && x2_256 && w->A <= 8 && persist >= 2 && nt % RR_MB == 0 && w->lds_max >= RR_LDS && wide_fused_ok(h) && h->dc.B % FX_MB == 0) {
     r.kind = WideRolloutRoute::RS_ACTOR;
     r.critic_rs = (rs & 4) && w->D % 4 == 0 && w->lds_max >= R2_LDS;   // measured slower: 1.21 vs 0.87 ms at C3
@@ -2188,7 +2126,8 @@ int wide_rollout(crl_ppo* h) {
       for (int step = 0; step < h->dc.k; ++step) {
         if (wide_forward_pair(h, h->cur_obs, w->D, nt, w->z, w->A8, w->v, 1)) return 1;   // ppo.jl:127-128
         a.step = step;
-        hipLaunchKernelGGL(wide_step_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, a);
+        if (h->gauss) gauss_launch_step(h->stream, a, HeadGauss{gauss_dist(h), h->action_f});
+        else hipLaunchKernelGGL(wide_step_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, a);
         CRL_HIP_CHECK(hipGetLastError());
       }
       break;
@@ -2408,16 +2347,25 @@ static int wide_grad_passes(crl_ppo* h, int mb, const int32_t* perm, double Mglo
     }
   }
   {
-    WLossArgs a;
-    a.c = h->dc; a.perm = perm; a.Z = w->z; a.A8 = w->A8; a.V = w->v; a.dv8 = w->dv8;
     if (h->recs_dirty) {   // a buffer field changed since the records were packed (rollout, GAE, a host write)
       int nbr = (h->dc.B + 255) / 256; if (nbr > 4096) nbr = 4096;
-      hipLaunchKernelGGL(wide_pack_rec_kernel, dim3(nbr), dim3(256), 0, h->stream, h->dc.B, h->action, h->logprob, h->value, h->adv, h->ret, w->wrec);
+      if (h->gauss) gauss_launch_pack_rec(h->stream, h->dc.B, h->act_dim, h->action_f, h->logprob, h->value, h->adv, h->ret, w->wrec);
+      else hipLaunchKernelGGL(wide_pack_rec_kernel, dim3(nbr), dim3(256), 0, h->stream, h->dc.B, h->action, h->logprob, h->value, h->adv, h->ret, w->wrec);
       h->recs_dirty = false;
     }
-    a.rec = w->wrec;
-    a.adv_ms = h->adv_ms; a.mb = mb; a.vfix = h->vfix; a.Mglobal = Mglobal; a.lpart = w->lpart;
-    hipLaunchKernelGGL(wide_loss_kernel, dim3(w->nlb), dim3(256), 0, h->stream, a);
+    ProfScope pl(h, CRL_K_LOSS);
+    if (h->gauss) {   // the same contract on the Gaussian head: permutation gather, lpart slots, cotangents over Z, the value half (ppo_gauss.hip)
+      GaussLossArgs g;
+      g.M = M; g.A8 = w->A8; g.clip = h->dc.clip; g.ent_coeff = h->dc.ent_coeff; g.v_coef = h->dc.v_coef; g.clip_vloss = h->dc.clip_vloss;
+      g.perm = perm; g.Z = w->z; g.V = w->v; g.dv8 = w->dv8; g.rec = w->wrec;
+      g.adv_ms = h->adv_ms; g.mb = mb; g.vfix = h->vfix; g.Mglobal = Mglobal; g.lpart = w->lpart; g.g = gauss_dist(h);
+      gauss_launch_loss(h->stream, g, w->nlb);
+    } else {
+      WLossArgs a;
+      a.c = h->dc; a.perm = perm; a.Z = w->z; a.A8 = w->A8; a.V = w->v; a.dv8 = w->dv8; a.rec = w->wrec;
+      a.adv_ms = h->adv_ms; a.mb = mb; a.vfix = h->vfix; a.Mglobal = Mglobal; a.lpart = w->lpart;
+      hipLaunchKernelGGL(wide_loss_kernel, dim3(w->nlb), dim3(256), 0, h->stream, a);
+    }
     CRL_HIP_CHECK(hipGetLastError());
   }
   w->fb_blocks = 0; w->w3_blocks = 0;
@@ -2456,7 +2404,7 @@ int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot) {
       r.part[b + 5] = nullptr; r.nparts[b + 5] = 0;
     }
     r.lpart = w->lpart; r.nlb = w->nlb; r.out = h->comm_buf; r.P = P; r.A = w->A;
-    r.with_stats = dp ? 0 : 1;
+    r.with_stats = dp ? 0 : 1; r.ent_div = h->gauss ? 1.0 : (double)w->A;
     r.st.c = h->dc; r.st.Mglobal = Mglobal; r.st.adv_ms = h->adv_ms; r.st.mb = mb; r.st.vfix = h->vfix; r.st.out = stats_slot; r.st.fused = 0; r.st.dscale = nullptr;
     r.boff[0] = 0;
     for (int i = 0; i < 12; ++i) r.boff[i + 1] = r.boff[i] + (r.part[i] ? (r.tab.off[i + 1] - r.tab.off[i] + 255) / 256 : 0);
@@ -2472,7 +2420,7 @@ int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot) {
     StatsArgs st;
     st.c = h->dc; st.Mglobal = Mglobal; st.adv_ms = h->adv_ms; st.mb = mb; st.vfix = h->vfix; st.out = stats_slot; st.fused = 0;
     st.dscale = nullptr;
-    hipLaunchKernelGGL(wide_stats_kernel, dim3(1), dim3(64), 0, h->stream, h->comm_buf, P, st);
+    hipLaunchKernelGGL(wide_stats_kernel, dim3(1), dim3(64), 0, h->stream, h->comm_buf, P, st, h->gauss ? 1.0 : (double)w->A);
     CRL_HIP_CHECK(hipGetLastError());
   }
   return 0;

@@ -53,14 +53,25 @@ ENVS = {
 }
 
 
+# The continuous-action envs: env_kind, obs_dim, act_dim. An Agent for one of them carries the Gaussian policy (action="gaussian"), n_act = act_dim.
+ENVS_CONTINUOUS = {
+    "pendulum": (L.ENV_PENDULUM, 3, 1),        # PendulumEnv(T=Float32, max_steps=200)
+}
+
+
+def _env_key(env):
+    return str(env).lower().replace("env", "").replace("_", "").replace("-", "")
+
+
 def env_shape(env, **shape):
     """ppo.jl:82,85-86: the shape keywords of an Agent for the named env (`env=None`: the keywords as given — an explicit env_kind keeps working).
     obs_dim / n_act / env_kind given next to `env` must agree with it."""
     if env is None:
         return shape
-    key = str(env).lower().replace("env", "").replace("_", "").replace("-", "")
+    key = _env_key(env)
     if key not in ENVS:
-        raise ValueError(f"unknown env {env!r}: one of {sorted(ENVS)} (or pass env_kind / obs_dim / n_act yourself)")
+        hint = " — a continuous-action env: ppo_continuous" if key in ENVS_CONTINUOUS else ""
+        raise ValueError(f"unknown env {env!r}: one of {sorted(ENVS)} (or pass env_kind / obs_dim / n_act yourself){hint}")
     kind, obs_dim, n_act = ENVS[key]
     for name, want in (("env_kind", kind), ("obs_dim", obs_dim), ("n_act", n_act)):
         if shape.get(name, want) != want:
@@ -88,13 +99,22 @@ class Policy:
 class Agent:
     """Actor + critic + optimiser state + rollout buffer + vectorised env of one PPO run, all resident on one GPU."""
 
-    def __init__(self, config: PPOConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, options=None, **shape):
+    def __init__(self, config: PPOConfig, *, device=0, params=None, seed=0x5EED, init_seed=0, options=None, action="softmax", gaussian=None, **shape):
+        """action="softmax": the reference's categorical policy. action="gaussian": a diagonal Gaussian over n_act = act_dim float actions
+        (crl_ppo_create_gaussian, layer-wise path); `gaussian` is its GaussianOptions (log-std bounds and initial value)."""
+        if action not in ("softmax", "gaussian"):
+            raise ValueError(f"Agent: action must be 'softmax' or 'gaussian', got {action!r}")
+        if gaussian is not None and action != "gaussian":
+            raise ValueError("Agent: GaussianOptions need action='gaussian'")
         self.config = config
+        self.action = action
         self.crl_cfg = _crl_config(config, seed=seed, **shape)
-        self.handle = L.Handle(self.crl_cfg, device)
+        self.handle = L.Handle(self.crl_cfg, device, gaussian=(gaussian or L.GaussianOptions()) if action == "gaussian" else None)
         for key, value in (options or {}).items():      # crl_ppo_set_option: kernel-flavour switches of this handle
             self.handle.set_option(key, value)
-        if params is None:
+        if params is None and action == "gaussian":
+            params = L.make_actor_critic_gaussian_host(self.crl_cfg.obs_dim, self.crl_cfg.n_act, self.crl_cfg.hidden, self.handle.gaussian, seed=init_seed)
+        elif params is None:
             params = networks.make_actor_critic(self.crl_cfg.n_act, self.crl_cfg.obs_dim, [self.crl_cfg.hidden] * 2, seed=init_seed)
         self.set_params(params)
         self.actor, self.critic = Policy(self, "actor"), Policy(self, "critic")
@@ -420,6 +440,30 @@ def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_rec
     return agent
 
 
+def train_host_gaussian(agent: Agent, env, num_updates=None, rng=None):
+    """ppo.jl:117-253 for a Gaussian agent (env_kind=ENV_EXTERNAL) and a HOST env that declares act_dim: an object with num_envs, obs_dim, act_dim,
+    reset() -> (obs (obs_dim, num_envs), done) and step(action (act_dim, num_envs)) -> (reward, next_obs, next_done) on numpy arrays. Per step
+    crl_policy_act_gaussian on the caller's normals, env.step, crl_rollout_store_gaussian; per update crl_ppo_update. Logs "Training Statistics"."""
+    cfg, h = agent.config, agent.handle
+    rng = rng or np.random.default_rng(0)
+    batch_size = cfg.num_steps * cfg.num_envs
+    if num_updates is None:
+        num_updates = max(1, cfg.total_timesteps // batch_size)
+    obs, done = env.reset()
+    for _ in range(num_updates):
+        for step in range(cfg.num_steps):
+            obs = np.asfortranarray(obs, np.float32)
+            act, lp, val = h.policy_act_gaussian(obs, rng.standard_normal((h.A, cfg.num_envs)).astype(np.float32))
+            reward, nobs, ndone = env.step(act)
+            h.rollout_store_gaussian(step, obs, act, lp, reward, np.asarray(done, np.uint8), val)
+            obs, done = nobs, ndone
+        h.write(L.F_CUR_OBS, np.asfortranarray(obs, np.float32)); h.write(L.F_NEXT_DONE, np.asarray(done, np.uint8))
+        for s in h.update(want_stats=True) or []:
+            log.info("Training Statistics", extra={"crl": dict(loss=s["loss"], pg_loss=s["pg_loss"], v_loss=s["v_loss"], entropy_loss=s["entropy_loss"],
+                                                               log_step_increment=0)})
+    return agent
+
+
 def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096, run_name="ppo-2-test",
         logger_kw=None, env=None, eval_every=0, eval_envs=256, eval_episodes=1, diag_every=0, **shape):
     """ppo.jl:75 — `ppo(config::PPOConfig=PPOConfig())`: CartPole, 2x64 actor/critic, whole loop on one MI355X. `env="cartpole" | "mountaincar" |
@@ -434,6 +478,12 @@ def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=
     env_kind=ENV_EXTERNAL and the object's obs_dim / n_act, and the loop is train_external; an object that lacks a protocol attribute is a TypeError."""
     if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
         raise ValueError(f"ppo: diag_every must be an integer >= 0, got {diag_every!r}")
+    if env is not None and not isinstance(env, str) and hasattr(env, "act_dim") and not hasattr(env, "n_act"):
+        # a host env that declares act_dim instead of n_act takes float actions: the Gaussian handle (ppo_continuous)
+        if eval_every or diag_every:
+            raise ValueError("ppo: eval_every / diag_every are not built for Gaussian handles (crl_ppo_evaluate / crl_ppo_diagnose)")
+        return ppo_continuous(config, env=env, device=device, seed=seed, init_seed=init_seed, params=params, episode_records=episode_records,
+                              run_name=run_name, logger_kw=logger_kw, **shape)
     external = env is not None and not isinstance(env, str)
     if external:     # a device env (see the protocol above): its shape comes from the object, the loop is train_external
         check_device_env(env)
@@ -460,6 +510,44 @@ def ppo(config: PPOConfig = None, *, device=0, seed=0x5EED, init_seed=0, params=
     agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, **shape)
     try:
         train(agent, episode_records=episode_records, eval_every=eval_every, eval_envs=eval_envs, eval_episodes=eval_episodes, diag_every=diag_every)
+        return agent.get_params()
+    finally:
+        agent.close()
+
+
+def ppo_continuous(config: PPOConfig = None, *, env="pendulum", gaussian=None, device=0, seed=0x5EED, init_seed=0, params=None, episode_records=4096,
+                   run_name="ppo-continuous", logger_kw=None, **shape):
+    """Continuous-action PPO (CleanRL's ppo_continuous_action; ppo.jl samples a softmax only): `ppo` with the diagonal Gaussian policy of
+    crl_ppo_create_gaussian. `env="pendulum"`: the on-device Pendulum, whole loop on the GPU (`train`); `env=<object>` with num_envs, obs_dim, act_dim,
+    reset and step on numpy arrays: a host env stepped through crl_policy_act_gaussian / crl_rollout_store_gaussian (`train_host_gaussian`).
+    `gaussian`: GaussianOptions (log-std bounds and initial value). `shape`: hidden, gae_mode, stale_obs, shuffle_mode. Evaluation and diagnostics
+    records are not available: crl_ppo_evaluate / crl_ppo_diagnose are not built for Gaussian handles. An unknown env name is a ValueError before
+    anything is created."""
+    from . import logger as _logger
+    config = config or PPOConfig()
+    if isinstance(env, str):
+        key = _env_key(env)
+        if key not in ENVS_CONTINUOUS:
+            raise ValueError(f"unknown continuous env {env!r}: one of {sorted(ENVS_CONTINUOUS)}")
+        kind, obs_dim, act_dim = ENVS_CONTINUOUS[key]
+    else:
+        for name in ("num_envs", "obs_dim", "act_dim", "reset", "step"):
+            if not hasattr(env, name):
+                raise TypeError(f"env={type(env).__name__} is neither a continuous env name nor a host env: it has no `{name}`")
+        if env.num_envs != config.num_envs:
+            raise ValueError(f"ppo_continuous: the env has num_envs={env.num_envs}, the config {config.num_envs}")
+        kind, obs_dim, act_dim = L.ENV_EXTERNAL, int(env.obs_dim), int(env.act_dim)
+    for name in ("env_kind", "obs_dim", "n_act", "action"):
+        if name in shape:
+            raise ValueError(f"ppo_continuous: {name} follows from the env, do not pass it")
+    _logger.make_logger(run_name, **({"to_terminal": False} | (logger_kw or {})))
+    agent = Agent(config, device=device, seed=seed, init_seed=init_seed, params=params, action="gaussian", gaussian=gaussian,
+                  **(shape | dict(env_kind=kind, obs_dim=obs_dim, n_act=act_dim)))
+    try:
+        if isinstance(env, str):
+            train(agent, episode_records=episode_records)
+        else:
+            train_host_gaussian(agent, env)
         return agent.get_params()
     finally:
         agent.close()

@@ -38,6 +38,7 @@ extern "C" {
 #define CRL_ENV_EXTERNAL 2 /* envs stepped by the caller: crl_policy_act + crl_rollout_store */
 #define CRL_ENV_MOUNTAINCAR 3 /* MountainCarEnv(T=Float32, max_steps=200): obs_dim=2, n_act=3; on-device, layer-wise path (parity unpinned: csrc/env.hpp) */
 #define CRL_ENV_ACROBOT 4     /* AcrobotEnv(T=Float32, max_steps=200): obs_dim=6, n_act=3, RK4 "book" dynamics; on-device, layer-wise path (parity unpinned) */
+#define CRL_ENV_PENDULUM 5    /* PendulumEnv(T=Float32, max_steps=200): obs_dim=3 (cos θ, sin θ, θ̇), act_dim=1, float actions; Gaussian handles only (crl_ppo_create_gaussian) */
 /* shuffle mode */
 #define CRL_SHUFFLE_FISHER_YATES 0 /* exact serial Fisher–Yates on device (ppo.jl:194 semantics) */
 #define CRL_SHUFFLE_BIJECTION 1     /* perm[p] = keyed bijection of [0,B): O(1) per element, pseudo-random (throughput path) */
@@ -62,7 +63,9 @@ enum crl_field {
   CRL_F_NEXT_DONE = 15, /* uint8 (nt)          next_done of ppo.jl:115,144 */
   CRL_F_ENV_T = 16,     /* int32 (nt) steps since reset */
   CRL_F_BETAP = 17,     /* double (24) Adam running beta powers per array */
-  CRL_F_ADV_SUMS = 18   /* double (num_minibatches, 2) Σadv, Σadv² of the current permutation slices (what the ranks all-reduce) */
+  CRL_F_ADV_SUMS = 18,  /* double (num_minibatches, 2) Σadv, Σadv² of the current permutation slices (what the ranks all-reduce) */
+  CRL_F_ACTION_F = 19   /* float  (act_dim, nt, k)  the actions of a Gaussian handle (crl_ppo_create_gaussian), unclipped; an error on a discrete handle,
+                           as CRL_F_ACTION is on a Gaussian one */
 };
 
 /* Mirror of PPOConfig (ppo.jl:1-19) + the shapes the reference hard-codes (networks.jl:36, CartPole) */
@@ -308,6 +311,42 @@ int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep,
  * does not synchronise. stats (may be NULL; non-NULL synchronises) receives the update_epochs * num_minibatches records of this update. Single rank
  * only: with an RCCL, peer or external communicator attached the call returns an error (multi-rank external envs are not supported). */
 int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats);
+/* ---- Continuous-action PPO: a diagonal Gaussian policy on the layer-wise path (csrc/ppo_gauss.hpp, ppo_gauss.hip; CleanRL's ppo_continuous_action —
+ * no counterpart in ppo.jl, whose get_action samples a softmax). crl_ppo_create_gaussian reads cfg->n_act as act_dim, 1 … 8; the actor head has
+ * 2·act_dim rows, z = (μ, s), so the parameter vector is the one of crl_ppo_create with n_act = 2·act_dim (twelve arrays, same order) and everything
+ * that does not look at the head — forward, backward, weight gradients, reduce, ClipNorm + Adam, GAE, shuffle, all-reduce — is shared. The handle is
+ * LAYER-WISE ONLY: obs_dim <= 64, hidden 64 / 128 / 256; the one shape the route decision sends to the 4 / 2 / 64 kernels (obs_dim 4, act_dim 1, hidden
+ * 64, without CRL_FORCE_WIDE) is an error. env_kind: CRL_ENV_PENDULUM (obs_dim 3, act_dim 1), CRL_ENV_SYNTHETIC (ignores actions: any shape) or
+ * CRL_ENV_EXTERNAL. The distribution, in Float32 with contraction off, for i = 0 … act_dim − 1:
+ *   μ_i = z[i], s_i = z[act_dim + i]
+ *   log_std_i = log_std_min + (0.5f·(log_std_max − log_std_min))·(tanh(s_i) + 1), tanh = tanhf of the HIP device library (not NNlib's rational tanh_fast)
+ *   σ_i = expf(log_std_i);  a_i = μ_i + σ_i·ξ_i;  logπ = Σ_i ((−0.5f·ξ_i² − log_std_i) − 0.5·log 2π);  H = Σ_i (log_std_i + 0.5·(1 + log 2π))
+ * Sums run in index order in the rollout and the probes; the update's loss kernel adds the act_dim terms pairwise, (i, i^1), then ^2, ^4. Actions are
+ * stored and scored UNCLIPPED; an env clips what it applies. Rollout noise: ξ_i of env e at step t of iteration it is the Float64 Box–Muller of
+ * csrc/normal_bm.hpp, sqrt(−2·log(1 − u_xy))·cos(2π·u_zw), on ALL FOUR words of the Philox block (seed, env_id_offset + e, it·num_steps + t, stream
+ * 0x20 + i), rounded to Float32: one block per component, streams 0x20 … 0x27 — apart from 0 (the discrete sampler's uniform), 1 and 2 (resets), 3 and
+ * 8 … 23 (the synthetic env). The rollout takes the per-step route (two forward launches and one step launch per step); the one-launch rollouts are
+ * built for the softmax head only. The update: ξ_i = (a_i − μ_i)/σ_i, ratio = expf(logπ − old), the clipped surrogate and d loss / d logπ (dnlp) as for
+ * the discrete head, ∂/∂μ_i = dnlp·ξ_i/σ_i, ∂/∂s_i = (dnlp·(ξ_i² − 1) − ent_coeff/M)·0.5·(max − min)·(1 − tanh²(s_i)); crl_ppo_stats.entropy_loss is
+ * the mean of H over the minibatch (no division by the head width). CRL_ENV_PENDULUM: state (θ, θ̇), reset θ = 2π·u_x − π, θ̇ = 2·u_y − 1 with
+ * u = (word >> 8)·2^-24 of ONE block of the reset stream; g = 10, m = l = 1, dt = 0.05, torque clipped to ±2, θ̇ to ±8, θ held in [−π, π), reward = −(θ² +
+ * 0.1·θ̇² + 0.001·u²) of the state before the step, done after 200 steps; returns are signed (return_max as for MountainCar).
+ * NOT BUILT for Gaussian handles (each returns an error that says so): crl_ppo_evaluate, crl_ppo_diagnose, crl_rollout_act_device,
+ * crl_rollout_record_device, crl_env_step_device; nor a state-independent log-std vector, act_dim > 8, or the 4 / 2 / 64 headline kernels. The int32
+ * entry points (crl_policy_act, crl_logprob_actions, crl_rollout_store, crl_env_step) are errors on a Gaussian handle, their twins below on a discrete one. */
+typedef struct crl_ppo_gauss_options { float log_std_min, log_std_max, init_log_std; } crl_ppo_gauss_options;   /* defaults (opt = NULL): −5, 2, 0 */
+int32_t crl_ppo_create_gaussian(const crl_ppo_config* cfg, const crl_ppo_gauss_options* opt, int32_t device, crl_ppo** out);
+/* crl_make_actor_critic(obs_dim, 2·act_dim, hidden, seed, …) — the same draws, the same 0.01-gain head — with the biases of head rows act_dim … 2·act_dim − 1
+ * set to s0 = atanh(2·(init_log_std − min)/(max − min) − 1), the value at which log_std = init_log_std. Errors name the field: log_std_min >= log_std_max,
+ * init_log_std outside the open interval. crl_ppo_init_params on a Gaussian handle calls it with the handle's options. Host-only. */
+int32_t crl_make_actor_critic_gaussian(int32_t obs_dim, int32_t act_dim, int32_t hidden, const crl_ppo_gauss_options* opt, uint64_t seed, float* out, size_t n);
+/* The float-action twins. xi (act_dim, n): the caller's standard normals; action (act_dim, n); entropy[n] = H per sample. */
+int32_t crl_policy_act_gaussian(crl_ppo* h, const float* obs, const float* xi, int32_t n, float* action, float* logprob, float* value);
+int32_t crl_logprob_actions_gaussian(crl_ppo* h, const float* obs, const float* actions, int32_t n, float* logprob, float* entropy);
+int32_t crl_rollout_store_gaussian(crl_ppo* h, int32_t step, const float* obs, const float* action, const float* logprob, const float* reward,
+                                   const uint8_t* terminal, const float* value);   /* action (act_dim, num_envs) */
+int32_t crl_env_step_gaussian(crl_ppo* h, const float* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done);   /* CRL_ENV_PENDULUM; action[num_envs] */
+
 /* how many iterations had their update phase re-run with the exact value-loss pass under data parallelism: the fused
  * kernels speculate on u = mean(v - R^2) <= 0 (ppo.jl:232-237); with an RCCL communicator a failed speculation restores the
  * parameters / Adam state of the iteration's start and repeats its optimiser steps exactly (two more small all-reduces each) */
@@ -431,7 +470,8 @@ int32_t crl_ppo_option_count(int32_t* n);   /* number of options: enumerate with
  * all-reduces of a data-parallel run (recorded events: 32 packets per iteration); 0 = off. */
 enum crl_kernel_id { CRL_K_ROLLOUT = 0, CRL_K_GAE = 1, CRL_K_SHUFFLE = 2, CRL_K_ADV_STATS = 3, CRL_K_UPDATE = 4,
                      CRL_K_REDUCE = 5, CRL_K_OPTIM = 6, CRL_K_ALLREDUCE = 7, CRL_K_PACK = 8, CRL_K_PERMUTE = 9,
-                     CRL_K_COUNT = 10 };
+                     CRL_K_LOSS = 10, /* the layer-wise path's loss launch alone (wide_loss_kernel / wide_loss_gauss_kernel), inside CRL_K_UPDATE; on = 1 only */
+                     CRL_K_COUNT = 11 };
 /* Measurement entry (bench.py roofline_gae.beyond_cache, scripts/bench_gae.py): the standalone GAE scan (the kernel behind crl_gae /
  * crl_compute_gae, ppo.jl:48-73,173-181) on synthetic device-resident inputs of ANY size — value ~ U(-10,10), reward 0 with P 0.02,
  * terminal ~ B(0.02) — `reps` timed launches (HIP events on the dispatch), each followed by a timed launch of a hand-written float4

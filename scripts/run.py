@@ -4,6 +4,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
 
     python scripts/run.py ppo --num_envs 4096 --num_steps 128 --total_timesteps 10485760
     python scripts/run.py ppo --env acrobot --hidden 256 --num_envs 256 --num_steps 128      (--env cartpole | mountaincar | acrobot: ppo.jl:82)
+    python scripts/run.py ppo_continuous --env pendulum --hidden 64 --num_envs 256 --num_steps 128     (continuous actions: the Gaussian policy, crl_ppo_create_gaussian)
     python scripts/run.py ppo --env acrobot --eval_every 10 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": a greedy held-out score every 10 updates)
     python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
@@ -31,7 +32,7 @@ from cleanrl_jl_amd import config_parser  # noqa: E402
 
 
 def main():
-    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "a2c", "dqn", "ddpg", "td3", "sac"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("ppo", "ppo_continuous", "a2c", "dqn", "ddpg", "td3", "sac"):
         raise SystemExit(__doc__)
     algo, argv = sys.argv[1], sys.argv[2:]
 
@@ -52,6 +53,9 @@ def main():
         # not PPOConfig fields: the env of ppo.jl:82, the width of networks.jl:36 and the evaluation / diagnostics cadence (crl_ppo_evaluate, crl_ppo_diagnose)
         kw = take((("--env", str), ("--hidden", int), ("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int), ("--diag_every", int)))
         crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
+    elif algo == "ppo_continuous":
+        kw = take((("--env", str), ("--hidden", int)))      # the continuous env (default: the Pendulum) and the width of networks.jl:36
+        crl.ppo_continuous(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_a2c_evaluate)
         crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
