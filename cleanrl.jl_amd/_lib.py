@@ -112,8 +112,9 @@ EXPORTS = [
     "crl_env_step", "crl_ppo_evaluate", "crl_ppo_diagnose",
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
     "crl_ppo_create_gaussian", "crl_make_actor_critic_gaussian", "crl_policy_act_gaussian", "crl_logprob_actions_gaussian",
-    "crl_rollout_store_gaussian", "crl_env_step_gaussian",
+    "crl_rollout_store_gaussian", "crl_env_step_gaussian", "crl_ppo_rollout_route",
 ]
+ROLLOUT_ROUTES = ("headline", "stepwise", "persist", "pc", "rs_actor")   # enum crl_rollout_route, in order
 
 DQN_PARAM_COUNT = 10934
 
@@ -302,6 +303,7 @@ def load():
     L.crl_rollout_store.argtypes = [vp, C.c_int32, fp, ip, fp, fp, u8p, fp]
     L.crl_env_reset.argtypes = [vp]
     L.crl_rollout_run.argtypes = [vp]
+    L.crl_ppo_rollout_route.argtypes = [vp, ip]
     L.crl_env_step.argtypes = [vp, ip, C.c_uint64, fp, fp, u8p]
     L.crl_ppo_evaluate.argtypes = [vp, C.POINTER(CrlEvalConfig), C.POINTER(CrlEvalReport), fp, ip, ip]
     L.crl_ppo_diagnose.argtypes = [vp, C.POINTER(CrlDiag), fp, fp]
@@ -710,6 +712,12 @@ class Handle:
 
     def rollout_run(self):
         check(load().crl_rollout_run(self._h))
+
+    def rollout_route(self):
+        """crl_ppo_rollout_route: what the next rollout_run / iterate launches for the env loop — one of ROLLOUT_ROUTES."""
+        r = C.c_int32(-1)
+        check(load().crl_ppo_rollout_route(self._h, C.byref(r)))
+        return ROLLOUT_ROUTES[r.value]
 
     def env_step(self, action, gstep=0):
         """crl_env_step: the on-device envs take the caller's 0-based actions (ppo.jl:130-165 without the policy); gstep keys the reset stream like

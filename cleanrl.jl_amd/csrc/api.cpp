@@ -708,6 +708,12 @@ int32_t crl_rollout_run(crl_ppo* h) {
   return launch_rollout(h);
 }
 
+int32_t crl_ppo_rollout_route(const crl_ppo* h, int32_t* route) {
+  if (!h || !route) { set_error("crl_ppo_rollout_route: null argument"); return 1; }
+  *route = h->wide ? wide_rollout_route_id(h) : CRL_ROUTE_HEADLINE;
+  return 0;
+}
+
 int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done) {
   CRL_GUARD_SETTLED(h);
   if (need_discrete(h, "crl_env_step", "crl_env_step_gaussian")) return 1;

@@ -299,6 +299,7 @@ int wide_logprob_actions_gauss(crl_ppo* h, const float* obs_d, const float* act_
 int wide_next_value(crl_ppo* h);
 int wide_env_reset(crl_ppo* h);
 int wide_rollout(crl_ppo* h);
+int wide_rollout_route_id(const crl_ppo* h);   // what wide_rollout will launch, as a crl_rollout_route (reads wide_rollout_route)
 int wide_update(crl_ppo* h, int mb, crl_ppo_stats* stats_slot);
 void comm_destroy(crl_ppo* h);
 // peer.hip — one-shot all-reduce over hipIpc-shared mailboxes

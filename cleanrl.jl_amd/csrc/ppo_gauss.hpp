@@ -34,9 +34,12 @@ __device__ __forceinline__ float gauss_action(float mu, float sigma, float xi) {
   return mu + sigma * xi;
 }
 // the rollout's ξ_i: normal_bm.hpp's Float64 Box–Muller on all four words of the env's own block, rounded to Float32
-__device__ __forceinline__ float gauss_xi(uint64_t seed, uint32_t gid, uint64_t gstep, int i) {
-  return (float)box_muller(philox_env(seed, gid, gstep, GAUSS_STREAM0 + (uint32_t)i));
+// — in two halves, so a caller may put other work between the integer block and the Float64 chain (wide_rs_rollout_gauss_kernel)
+__device__ __forceinline__ u32x4 gauss_xi_block(uint64_t seed, uint32_t gid, uint64_t gstep, int i) {
+  return philox_env(seed, gid, gstep, GAUSS_STREAM0 + (uint32_t)i);
 }
+__device__ __forceinline__ float gauss_xi_of(const u32x4& block) { return (float)box_muller(block); }
+__device__ __forceinline__ float gauss_xi(uint64_t seed, uint32_t gid, uint64_t gstep, int i) { return gauss_xi_of(gauss_xi_block(seed, gid, gstep, i)); }
 
 // the Gaussian head tag of wide_step_env (wide_step.hpp): where the float actions go and the distribution's constants
 struct HeadGauss { GaussDist g; float* action_f; };

@@ -1571,6 +1571,7 @@ __global__ void __launch_bounds__(512) wide_rollout_pc_kernel(RollPCArgs r) {
 
 }  // namespace crl
 #include "wide_rs.hpp"
+#include "wide_rs_gauss.hpp"
 namespace crl {
 
 // env construction for the synthetic env (oracle: orc_env_init, gstep = ~0)
@@ -1967,15 +1968,28 @@ static WideRolloutRoute wide_rollout_route(const crl_ppo* h) {
   const bool x2_256 = w->H == 256 && wide_x2(h) && w->D <= 16;
   WideRolloutRoute r;
   r.critic_rs = false;
-  // a Gaussian handle takes the per-step route: the one-launch kernels are instantiated for the softmax head only
-  if (h->gauss) { r.kind = WideRolloutRoute::STEPWISE; return r; }
-  if ((rs & 2) && x2_256 && w->A <= 8 && persist >= 2 && nt % RR_MB == 0 && w->lds_max >= RR_LDS && wide_fused_ok(h) && h->dc.B % FX_MB == 0) {
+  // a Gaussian handle has ONE one-launch kernel, the register-stationary actor's (wide_rs_rollout_gauss_kernel: the on-device Pendulum or the synthetic
+  // env, head width 2·act_dim <= 8); PC and PERSIST are instantiated for the softmax head only
+  const bool gauss = h->gauss;
+  const bool rs_env = !gauss || h->cfg.env_kind == CRL_ENV_PENDULUM || h->cfg.env_kind == CRL_ENV_SYNTHETIC;
+  const int rs_lds = gauss ? RG_LDS : RR_LDS;
+  if ((rs & 2) && x2_256 && w->A <= 8 && persist >= 2 && nt % RR_MB == 0 && w->lds_max >= rs_lds && wide_fused_ok(h) && h->dc.B % FX_MB == 0 && rs_env) {
     r.kind = WideRolloutRoute::RS_ACTOR;
     r.critic_rs = (rs & 4) && w->D % 4 == 0 && w->lds_max >= R2_LDS;   // measured slower: 1.21 vs 0.87 ms at C3
-  } else if (x2_256 && w->A <= PC_AMAX && persist >= 2 && nt % RP_MB == 0 && w->lds_max >= RP_LDS) r.kind = WideRolloutRoute::PC;
+  } else if (gauss) r.kind = WideRolloutRoute::STEPWISE;
+  else if (x2_256 && w->A <= PC_AMAX && persist >= 2 && nt % RP_MB == 0 && w->lds_max >= RP_LDS) r.kind = WideRolloutRoute::PC;
   else if (x2_256 && persist) r.kind = WideRolloutRoute::PERSIST;
   else r.kind = WideRolloutRoute::STEPWISE;
   return r;
+}
+
+int wide_rollout_route_id(const crl_ppo* h) {
+  switch (wide_rollout_route(h).kind) {
+    case WideRolloutRoute::RS_ACTOR: return CRL_ROUTE_RS_ACTOR;
+    case WideRolloutRoute::PC: return CRL_ROUTE_PC;
+    case WideRolloutRoute::PERSIST: return CRL_ROUTE_PERSIST;
+    default: return CRL_ROUTE_STEPWISE;
+  }
 }
 
 // One minibatch of M samples. With bwd == BWD_LAYERS wide_backward runs per network, and split / wgrad / side_stream say nothing.
@@ -2083,7 +2097,13 @@ int wide_rollout(crl_ppo* h) {
       RsRollArgs r;
       r.n = roll_pc_net(w->net[0], 1); r.s = a; r.s.V = nullptr; r.D = w->D;
       wide_dp_na(w, [&](auto dp, auto na) {
-        hipLaunchKernelGGL((wide_rs_rollout_kernel<decltype(dp)::value, decltype(na)::value>), dim3(nt / RR_MB), dim3(512), RR_LDS, h->stream, r);
+        constexpr int DP = decltype(dp)::value, NA = decltype(na)::value;
+        if (!h->gauss) hipLaunchKernelGGL((wide_rs_rollout_kernel<DP, NA>), dim3(nt / RR_MB), dim3(512), RR_LDS, h->stream, r);
+        else {   // the components on waves of their own, or all on wave 0 (wide_rs_gauss.hpp)
+          const HeadGauss hd{gauss_dist(h), h->action_f};
+          if (h->act_dim >= CRL_RG_PAR_FROM) hipLaunchKernelGGL((wide_rs_rollout_gauss_kernel<DP, NA, true>), dim3(nt / RR_MB), dim3(512), RG_LDS, h->stream, r, hd);
+          else hipLaunchKernelGGL((wide_rs_rollout_gauss_kernel<DP, NA, false>), dim3(nt / RR_MB), dim3(512), RG_LDS, h->stream, r, hd);
+        }
       });
       CRL_HIP_CHECK(hipGetLastError());
       // values of all num_steps x num_envs stored observations (ppo.jl:128 evaluates the critic on the same observation the buffer keeps)

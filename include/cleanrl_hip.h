@@ -161,6 +161,12 @@ int32_t crl_rollout_store(crl_ppo* h, int32_t step, const float* obs, const int3
 int32_t crl_env_reset(crl_ppo* h);
 /* The whole `for step in 1:num_steps` loop — ppo.jl:123-166 — in one launch (on-device env + policy + sampling). */
 int32_t crl_rollout_run(crl_ppo* h);
+/* Which kernels the next crl_rollout_run / crl_ppo_iterate launches for the loop, from the handle's shape, options and batch size (the decision itself:
+ * wide_rollout_route in csrc/wide.hip; this call only reads it). HEADLINE: the 4 / 2 / 64 kernels; on the layer-wise path STEPWISE (two forward launches
+ * and a step launch per step), PERSIST / PC (one launch, both networks in the loop) or RS_ACTOR (one launch with the actor register-stationary, then one
+ * batched critic forward). Discrete and Gaussian handles; CRL_ENV_EXTERNAL handles run no rollout of their own and report what their shape would take. */
+enum crl_rollout_route { CRL_ROUTE_HEADLINE = 0, CRL_ROUTE_STEPWISE = 1, CRL_ROUTE_PERSIST = 2, CRL_ROUTE_PC = 3, CRL_ROUTE_RS_ACTOR = 4 };
+int32_t crl_ppo_rollout_route(const crl_ppo* h, int32_t* route);
 /* env(actions) + reward / is_terminated / state + reset!(env) of the terminated — ppo.jl:130-165 without the policy: steps the handle's on-device envs
  * with the caller's actions; gstep keys the reset stream like step `gstep` of the training loop. Outputs may be NULL. Leaves the rollout buffer alone.
  * action[num_envs] 0-based (out of range is an error); next_obs (obs_dim, num_envs) is what CRL_F_CUR_OBS holds afterwards (stale_obs decides whether a
@@ -325,8 +331,12 @@ int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats);
  * stored and scored UNCLIPPED; an env clips what it applies. Rollout noise: ξ_i of env e at step t of iteration it is the Float64 Box–Muller of
  * csrc/normal_bm.hpp, sqrt(−2·log(1 − u_xy))·cos(2π·u_zw), on ALL FOUR words of the Philox block (seed, env_id_offset + e, it·num_steps + t, stream
  * 0x20 + i), rounded to Float32: one block per component, streams 0x20 … 0x27 — apart from 0 (the discrete sampler's uniform), 1 and 2 (resets), 3 and
- * 8 … 23 (the synthetic env). The rollout takes the per-step route (two forward launches and one step launch per step); the one-launch rollouts are
- * built for the softmax head only. The update: ξ_i = (a_i − μ_i)/σ_i, ratio = expf(logπ − old), the clipped surrogate and d loss / d logπ (dnlp) as for
+ * 8 … 23 (the synthetic env). The rollout: at 2x256 (fp16x2, obs_dim <= 16) with act_dim <= 4, num_envs a multiple of 64, num_envs·num_steps a multiple
+ * of 128 and CRL_ENV_PENDULUM or CRL_ENV_SYNTHETIC it is ONE launch for all steps (wide_rs_rollout_gauss_kernel, csrc/wide_rs_gauss.hpp: the softmax
+ * handle's register-stationary actor with a Gaussian tail — ξ drawn one step ahead on idle waves, one wave per action component — then one batched critic
+ * forward), under the softmax handle's own switches (wide_rs bit 1, wide_rollout_persist >= 2); every other Gaussian handle takes the per-step route
+ * (two forward launches and one step launch per step). The two routes differ in the actor's forward flavour only: given the same head outputs, action,
+ * logπ and ξ are the same bits. crl_ppo_rollout_route says which one a handle takes. The update: ξ_i = (a_i − μ_i)/σ_i, ratio = expf(logπ − old), the clipped surrogate and d loss / d logπ (dnlp) as for
  * the discrete head, ∂/∂μ_i = dnlp·ξ_i/σ_i, ∂/∂s_i = (dnlp·(ξ_i² − 1) − ent_coeff/M)·0.5·(max − min)·(1 − tanh²(s_i)); crl_ppo_stats.entropy_loss is
  * the mean of H over the minibatch (no division by the head width). CRL_ENV_PENDULUM: state (θ, θ̇), reset θ = 2π·u_x − π, θ̇ = 2·u_y − 1 with
  * u = (word >> 8)·2^-24 of ONE block of the reset stream; g = 10, m = l = 1, dt = 0.05, torque clipped to ±2, θ̇ to ±8, θ held in [−π, π), reward = −(θ² +
