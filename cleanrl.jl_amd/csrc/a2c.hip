@@ -421,8 +421,8 @@ struct crl_a2c {
   double *h1[2] = {nullptr, nullptr}, *h2[2] = {nullptr, nullptr}, *d1 = nullptr, *d2 = nullptr;
   double *vout = nullptr, *z = nullptr, *G = nullptr, *adv = nullptr, *dvc = nullptr, *dza = nullptr, *lp_adv = nullptr;
   crl::ParamTable tab;   // the PPO layout at 4 / 2 / 64
-  void* stage = nullptr; size_t stage_bytes = 0;   // crl_a2c_forward
-  crl::ValueEvalScratch eval;                      // crl_a2c_evaluate
+  crl::Scratch stage;    // crl_a2c_forward
+  crl::Scratch eval;     // crl_a2c_evaluate
 };
 
 namespace crl {
@@ -432,15 +432,7 @@ static A2CDev dev_args(crl_a2c* h) {
   a.rb_state = h->rb_state; a.rb_action = h->rb_action; a.rb_reward = h->rb_reward; a.rb_terminal = h->rb_terminal;
   return a;
 }
-template <typename T>
-static int aalloc(T** p, size_t n) {
-  CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  CRL_HIP_CHECK(hipMemset(*p, 0, n * sizeof(T)));
-  return 0;
-}
-#define A2C_GUARD(h)                                           \
-  if (!(h)) { crl::set_error("null crl_a2c handle"); return 1; } \
-  CRL_HIP_CHECK(hipSetDevice((h)->device));
+#define A2C_GUARD(h) CRL_HANDLE_GUARD(h, "crl_a2c")
 
 static int a2c_update(crl_a2c* h, int n) {
   A2CDev a = dev_args(h);
@@ -498,13 +490,13 @@ int32_t crl_a2c_create(const crl_a2c_config* cfg, int32_t device, crl_a2c** out)
   if (se != hipSuccess) { set_error(std::string("hipStreamCreate: ") + hipGetErrorString(se)); delete h; return 1; }
   const size_t cap = (size_t)h->cap, P = (size_t)h->P;
   int rc = 0;
-  rc |= aalloc(&h->params, P); rc |= aalloc(&h->grads, P); rc |= aalloc(&h->m, P); rc |= aalloc(&h->v, P); rc |= aalloc(&h->betap, 24);
-  rc |= aalloc(&h->ctl, 1); rc |= aalloc(&h->eps, A2C_MAX_EPS);
-  rc |= aalloc(&h->rb_state, cap * AD); rc |= aalloc(&h->rb_action, cap); rc |= aalloc(&h->rb_reward, cap); rc |= aalloc(&h->rb_terminal, cap);
-  for (int n = 0; n < 2; ++n) { rc |= aalloc(&h->h1[n], cap * AH); rc |= aalloc(&h->h2[n], cap * AH); }
-  rc |= aalloc(&h->d1, cap * AH); rc |= aalloc(&h->d2, cap * AH);
-  rc |= aalloc(&h->vout, cap); rc |= aalloc(&h->z, cap * AA); rc |= aalloc(&h->G, cap); rc |= aalloc(&h->adv, cap);
-  rc |= aalloc(&h->dvc, cap); rc |= aalloc(&h->dza, cap * AA); rc |= aalloc(&h->lp_adv, cap);
+  rc |= dalloc(&h->params, P); rc |= dalloc(&h->grads, P); rc |= dalloc(&h->m, P); rc |= dalloc(&h->v, P); rc |= dalloc(&h->betap, 24);
+  rc |= dalloc(&h->ctl, 1); rc |= dalloc(&h->eps, A2C_MAX_EPS);
+  rc |= dalloc(&h->rb_state, cap * AD); rc |= dalloc(&h->rb_action, cap); rc |= dalloc(&h->rb_reward, cap); rc |= dalloc(&h->rb_terminal, cap);
+  for (int n = 0; n < 2; ++n) { rc |= dalloc(&h->h1[n], cap * AH); rc |= dalloc(&h->h2[n], cap * AH); }
+  rc |= dalloc(&h->d1, cap * AH); rc |= dalloc(&h->d2, cap * AH);
+  rc |= dalloc(&h->vout, cap); rc |= dalloc(&h->z, cap * AA); rc |= dalloc(&h->G, cap); rc |= dalloc(&h->adv, cap);
+  rc |= dalloc(&h->dvc, cap); rc |= dalloc(&h->dza, cap * AA); rc |= dalloc(&h->lp_adv, cap);
   if (rc) { crl_a2c_destroy(h); return 1; }
   double bp[24];
   for (int i = 0; i < 12; ++i) { bp[2 * i] = 0.9; bp[2 * i + 1] = 0.999; }
@@ -520,8 +512,9 @@ int32_t crl_a2c_destroy(crl_a2c* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->params, h->grads, h->m, h->v, h->betap, h->ctl, h->eps, h->rb_state, h->rb_action, h->rb_reward, h->rb_terminal,
-                  h->h1[0], h->h1[1], h->h2[0], h->h2[1], h->d1, h->d2, h->vout, h->z, h->G, h->adv, h->dvc, h->dza, h->lp_adv, h->stage, h->eval.p};
+                  h->h1[0], h->h1[1], h->h2[0], h->h2[1], h->d1, h->d2, h->vout, h->z, h->G, h->adv, h->dvc, h->dza, h->lp_adv};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  scratch_release(h->stage); scratch_release(h->eval);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -654,23 +647,17 @@ int32_t crl_a2c_forward(crl_a2c* h, int32_t net, const double* obs, int32_t n, d
   if (n < 0) { set_error("crl_a2c_forward: n must be >= 0, got " + std::to_string(n)); return 1; }
   if (n > 0 && (!obs || !out)) { set_error("crl_a2c_forward: null obs or out"); return 1; }
   if (n == 0) return 0;
-  const size_t N = (size_t)n, n_out = net ? 1 : AA, need = N * (AD + n_out) * 8;
-  if (h->stage_bytes < need) {
-    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
-    h->stage = nullptr; h->stage_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
-    h->stage_bytes = need;
-  }
-  double* so = static_cast<double*>(h->stage);
-  double* sz = so + N * AD;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * AD * 8, hipMemcpyHostToDevice, h->stream));
+  const size_t N = (size_t)n, n_out = net ? 1 : AA;
+  Staged s(h->stream);
+  const auto s_obs = s.add<double>(N * AD), s_out = s.add<double>(N * n_out);
+  if (s.reserve(h->stage)) return 1;
+  if (s.put(s_obs, obs)) return 1;
   // a wave per observation: the forward of the training batch without the stored activations
-  hipLaunchKernelGGL(a2c_forward_kernel, dim3(n), dim3(64), 0, h->stream, (const float*)h->params, (int)net, (const double*)so, (int)n,
-                     (double*)nullptr, (double*)nullptr, sz);
+  hipLaunchKernelGGL(a2c_forward_kernel, dim3(n), dim3(64), 0, h->stream, (const float*)h->params, (int)net, (const double*)s.at(s_obs), (int)n,
+                     (double*)nullptr, (double*)nullptr, s.at(s_out));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(out, sz, N * n_out * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_out, out)) return 1;
+  return s.finish();
 }
 
 // Held-out evaluation: argument checks, scratch, ONE launch (a2c_eval_kernel), the per-episode arrays back to the host, the report in Float64
@@ -680,7 +667,7 @@ int32_t crl_a2c_evaluate(crl_a2c* h, const crl_eval_config* cfg, crl_value_eval_
   if (value_eval_check("crl_a2c_evaluate", cfg, report, h->params_set, "crl_a2c_write_params or crl_a2c_init_params first (a2c.jl:37)",
                        h->cfg.max_steps, /*has_sampler=*/true, trace_action)) return 1;
   ValueEvalArgs ev;
-  if (value_eval_scratch(h->eval, cfg, ev)) return 1;
+  if (value_eval_scratch(h->eval, h->stream, cfg, ev)) return 1;
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
   hipLaunchKernelGGL(a2c_eval_kernel, dim3((unsigned)((ev.n + A2C_EVAL_WAVES - 1) / A2C_EVAL_WAVES)), dim3(64 * A2C_EVAL_WAVES), 0, h->stream,
                      (const float*)h->params, (int)h->cfg.max_steps, h->cfg.gamma, ev);

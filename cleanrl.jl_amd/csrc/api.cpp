@@ -112,29 +112,11 @@ int reset_dw_scale(crl_ppo* h) {
   return 0;
 }
 
-int ensure_scratch(crl_ppo* h, void** buf, size_t* have, size_t want) {
-  if (*have >= want) return 0;
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // work enqueued earlier may still read the old buffer
-  if (*buf) CRL_HIP_CHECK(hipFree(*buf));
-  *buf = nullptr; *have = 0;
-  CRL_HIP_CHECK(hipMalloc(buf, want));
-  *have = want;
-  return 0;
-}
-int ensure_stage(crl_ppo* h, size_t bytes) { return ensure_scratch(h, &h->stage, &h->stage_bytes, bytes < (1u << 20) ? (1u << 20) : bytes); }
-
 // the entry points that step an on-device env themselves
 static int need_stateful_env(const crl_ppo* h, const char* who) {
   if (env_stateful(h->cfg.env_kind)) return 0;
   set_error(std::string(who) + " needs a stateful on-device env (CRL_ENV_CARTPOLE, CRL_ENV_MOUNTAINCAR or CRL_ENV_ACROBOT)");
   return 1;
-}
-
-template <typename T>
-static int dalloc(T** p, size_t n, bool zero = true) {
-  CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  if (zero) CRL_HIP_CHECK(hipMemset(*p, 0, n * sizeof(T)));
-  return 0;
 }
 
 struct FieldRef { void* ptr; size_t bytes; };
@@ -224,9 +206,7 @@ bool rollout_can_fuse_gae(const crl_ppo* h) {
 
 using namespace crl;
 
-#define CRL_GUARD(h)                                         \
-  if (!(h)) { set_error("null crl_ppo handle"); return 1; } \
-  CRL_HIP_CHECK(hipSetDevice((h)->device));
+#define CRL_GUARD(h) CRL_HANDLE_GUARD(h, "crl_ppo")
 
 static int settle(crl_ppo* h);
 static int check_bfy(crl_ppo* h, bool host_syncs = true);
@@ -244,6 +224,75 @@ static int check_bfy(crl_ppo* h, bool host_syncs = true);
               "crl_ppo_init_params first (ppo.jl:87; a fresh handle holds zeros)");                                                    \
     return 1;                                                                                                                          \
   }
+
+// The staged bodies a softmax-head call and its Gaussian twin share; the checks that differ between the heads stay in the exported functions, and
+// `launch` is the head's kernel launcher on the device pointers. A row is one observation (policy calls) or one env (step, store).
+// act: obs and the draws in (draw_w per row: one uniform, or act_dim normals) — action (act_w per row), logprob and value out
+template <typename U, typename T, typename Launch>
+static int32_t policy_act_staged(crl_ppo* h, const float* obs, const U* draws, size_t draw_w, int32_t n, T* action, size_t act_w, float* logprob, float* value,
+                                 Launch launch) {
+  const size_t N = (size_t)n;
+  Staged s(h->stream);
+  const auto s_obs = s.add<float>(N * (size_t)h->dc.D);
+  const auto s_draw = s.add<U>(N * draw_w);
+  const auto s_act = s.add<T>(N * act_w);
+  const auto s_lp = s.add<float>(N), s_val = s.add<float>(N);
+  if (s.reserve(h->stage, STAGE_FLOOR)) return 1;
+  if (s.put(s_obs, obs) || s.put(s_draw, draws)) return 1;
+  if (launch(s.at(s_obs), s.at(s_draw), s.at(s_act), s.at(s_lp), s.at(s_val))) return 1;
+  if (s.get(s_act, action) || s.get(s_lp, logprob) || s.get(s_val, value)) return 1;
+  return s.finish();
+}
+// logprob: obs and the actions in (act_w per row) — logprob and the entropy (ent_w per row) out
+template <typename T, typename Launch>
+static int32_t logprob_actions_staged(crl_ppo* h, const float* obs, const T* actions, size_t act_w, int32_t n, float* logprob, float* entropy, size_t ent_w,
+                                      Launch launch) {
+  const size_t N = (size_t)n;
+  Staged s(h->stream);
+  const auto s_obs = s.add<float>(N * (size_t)h->dc.D);
+  const auto s_act = s.add<T>(N * act_w);
+  const auto s_lp = s.add<float>(N), s_ent = s.add<float>(N * ent_w);
+  if (s.reserve(h->stage, STAGE_FLOOR)) return 1;
+  if (s.put(s_obs, obs) || s.put(s_act, actions)) return 1;
+  if (launch(s.at(s_obs), s.at(s_act), s.at(s_lp), s.at(s_ent))) return 1;
+  if (s.get(s_lp, logprob) || s.get(s_ent, entropy)) return 1;
+  return s.finish();
+}
+// env step: one action per env in — reward and done out, the next observations from the handle; `bad` (softmax head only) receives the launch's
+// out-of-range-action word, cleared before it
+template <typename T, typename Launch>
+static int32_t env_step_staged(crl_ppo* h, const T* action, float* next_obs, float* reward, uint8_t* done, uint32_t* bad, Launch launch) {
+  const size_t nt = (size_t)h->dc.nt;
+  Staged s(h->stream);
+  const auto s_act = s.add<T>(nt);
+  const auto s_rew = s.add<float>(nt);
+  const auto s_bad = s.add<uint32_t>(bad ? 4 : 0);
+  const auto s_done = s.add<uint8_t>(nt);
+  if (s.reserve(h->stage, STAGE_FLOOR)) return 1;
+  if (s.put(s_act, action)) return 1;
+  if (bad) CRL_HIP_CHECK(hipMemsetAsync(s.at(s_bad), 0, 16, h->stream));
+  if (launch(s.at(s_act), s.at(s_rew), s.at(s_done), s.at(s_bad))) return 1;
+  if (bad) CRL_HIP_CHECK(hipMemcpyAsync(bad, s.at(s_bad), 4, hipMemcpyDeviceToHost, h->stream));
+  if (next_obs) CRL_HIP_CHECK(hipMemcpyAsync(next_obs, h->cur_obs, nt * (size_t)h->dc.D * 4, hipMemcpyDeviceToHost, h->stream));
+  if (s.get(s_rew, reward) || s.get(s_done, done)) return 1;
+  return s.finish();
+}
+// one step of a host-driven rollout into the resident buffer; the action plane is the int32 one or the float one, act_row bytes per env
+static int32_t rollout_store(crl_ppo* h, const char* who, int32_t step, const float* obs, void* action_plane, const void* action, size_t act_row,
+                             const float* logprob, const float* reward, const uint8_t* terminal, const float* value) {
+  if (step < 0 || step >= h->dc.k) { set_error(std::string(who) + ": step out of range"); return 1; }
+  if (!obs || !action || !logprob || !reward || !terminal || !value) { set_error(std::string(who) + ": null argument"); return 1; }
+  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D, off = nt * (size_t)step;
+  CRL_HIP_CHECK(hipMemcpyAsync(h->obs + off * d, obs, nt * d * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(static_cast<char*>(action_plane) + off * act_row, action, nt * act_row, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->logprob + off, logprob, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->reward + off, reward, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->terminal + off, terminal, nt, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipMemcpyAsync(h->value + off, value, nt * 4, hipMemcpyHostToDevice, h->stream));
+  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));  // host buffers are only borrowed for the call
+  h->recs_dirty = true;
+  return 0;
+}
 
 extern "C" {
 
@@ -425,8 +474,9 @@ int32_t crl_ppo_destroy(crl_ppo* h) {
   void* ptrs[] = {h->obs, h->action, h->logprob, h->reward, h->terminal, h->value, h->adv, h->ret, h->env_state, h->env_t,
                   h->cur_obs, h->next_done, h->ep_return, h->ep_length, h->next_value, h->ep_stats, h->ep_ring, h->ep_ring_count, h->params,
                   h->adam_m, h->adam_v, h->betap, h->optim_part, h->ticket, h->perm_base, h->recs, h->adv_part, h->perm_tmp, h->bfy_ws, h->bfy_adv_part, h->bfy_bucket_mb, h->bfy_mbid, h->bfy_dig1, h->gpart, h->lpart,
-                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->stage, h->eval_ws, h->diag_ws, h->ext_bad, h->action_f};
+                  h->adv_sums_base, h->adv_ms_base, h->newv, h->vfix, h->dscale, h->stats_dev, h->comm_buf, h->snap, h->snap_betap, h->snap_env, h->ext_bad, h->action_f};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  scratch_release(h->stage); scratch_release(h->eval_ws); scratch_release(h->diag_ws);
   for (int s = 0; s < 2; ++s) {
     if (h->status_dev[s]) (void)hipFree(h->status_dev[s]);
     if (h->status_host[s]) (void)hipHostFree(h->status_host[s]);
@@ -529,20 +579,9 @@ int32_t crl_policy_act(crl_ppo* h, const float* obs, const double* u, int32_t n,
   if (need_discrete(h, "crl_policy_act", "crl_policy_act_gaussian")) return 1;
   if (n < 0 || (n > 0 && (!obs || !u || !action || !logprob))) { set_error("crl_policy_act: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t d = (size_t)h->dc.D, N = (size_t)n;
-  const size_t o_obs = 0, o_u = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_act = o_u + N * 8, o_lp = o_act + N * 4,
-               o_val = o_lp + N * 4, total = o_val + N * 4;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_u, u, N * 8, hipMemcpyHostToDevice, h->stream));
-  if (launch_policy_act(h, (const float*)(s + o_obs), (const double*)(s + o_u), n, (int32_t*)(s + o_act), (float*)(s + o_lp),
-                        (float*)(s + o_val))) return 1;
-  CRL_HIP_CHECK(hipMemcpyAsync(action, s + o_act, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
-  if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, s + o_val, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return policy_act_staged(h, obs, u, 1, n, action, 1, logprob, value, [&](const float* o, const double* ud, int32_t* a, float* lp, float* v) {
+    return launch_policy_act(h, o, ud, n, a, lp, v);
+  });
 }
 
 int32_t crl_logprob_actions(crl_ppo* h, const float* obs, const int32_t* actions, int32_t n, float* logprob,
@@ -552,18 +591,9 @@ int32_t crl_logprob_actions(crl_ppo* h, const float* obs, const int32_t* actions
   if (need_discrete(h, "crl_logprob_actions", "crl_logprob_actions_gaussian")) return 1;
   if (n < 0 || (n > 0 && (!obs || !actions || !logprob || !entropy))) { set_error("crl_logprob_actions: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t d = (size_t)h->dc.D, A = (size_t)h->dc.A, N = (size_t)n;
-  const size_t o_obs = 0, o_act = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_lp = o_act + N * 4, o_ent = o_lp + N * 4,
-               total = o_ent + N * A * 4;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, actions, N * 4, hipMemcpyHostToDevice, h->stream));
-  if (launch_logprob_actions(h, (const float*)(s + o_obs), (const int32_t*)(s + o_act), n, (float*)(s + o_lp), (float*)(s + o_ent))) return 1;
-  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(entropy, s + o_ent, N * A * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return logprob_actions_staged(h, obs, actions, 1, n, logprob, entropy, (size_t)h->dc.A, [&](const float* o, const int32_t* a, float* lp, float* ent) {
+    return launch_logprob_actions(h, o, a, n, lp, ent);
+  });
 }
 
 int32_t crl_gae(int32_t device, const float* value, const float* reward, const uint8_t* terminal, const float* next_value,
@@ -613,40 +643,20 @@ int32_t crl_rollout_store(crl_ppo* h, int32_t step, const float* obs, const int3
                           const float* reward, const uint8_t* terminal, const float* value) {
   CRL_GUARD_SETTLED(h);
   if (need_discrete(h, "crl_rollout_store", "crl_rollout_store_gaussian")) return 1;
-  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_store: step out of range"); return 1; }
-  if (!obs || !action || !logprob || !reward || !terminal || !value) { set_error("crl_rollout_store: null argument"); return 1; }
-  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D, off = nt * (size_t)step;
-  CRL_HIP_CHECK(hipMemcpyAsync(h->obs + off * d, obs, nt * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->action + off, action, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->logprob + off, logprob, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->reward + off, reward, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->terminal + off, terminal, nt, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->value + off, value, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));  // host buffers are only borrowed for the call
-  h->recs_dirty = true;
-  return 0;
+  return rollout_store(h, "crl_rollout_store", step, obs, h->action, action, 4, logprob, reward, terminal, value);
 }
 
-// ---- the float-action twins of a Gaussian handle (ppo_gauss.hip): the same staging as the calls above them
+// ---- the float-action twins of a Gaussian handle (ppo_gauss.hip)
 int32_t crl_policy_act_gaussian(crl_ppo* h, const float* obs, const float* xi, int32_t n, float* action, float* logprob, float* value) {
   CRL_GUARD_SETTLED(h);
   if (need_gauss(h, "crl_policy_act_gaussian")) return 1;
   CRL_NEED_PARAMS(h, "crl_policy_act_gaussian");
   if (n < 0 || (n > 0 && (!obs || !xi || !action || !logprob))) { set_error("crl_policy_act_gaussian: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t d = (size_t)h->dc.D, ad = (size_t)h->act_dim, N = (size_t)n;
-  const size_t o_obs = 0, o_xi = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_act = o_xi + N * ad * 4, o_lp = o_act + N * ad * 4, o_val = o_lp + N * 4,
-               total = o_val + N * 4;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_xi, xi, N * ad * 4, hipMemcpyHostToDevice, h->stream));
-  if (wide_policy_act_gauss(h, (const float*)(s + o_obs), (const float*)(s + o_xi), n, (float*)(s + o_act), (float*)(s + o_lp), value ? (float*)(s + o_val) : nullptr)) return 1;
-  CRL_HIP_CHECK(hipMemcpyAsync(action, s + o_act, N * ad * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
-  if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, s + o_val, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  const size_t ad = (size_t)h->act_dim;
+  return policy_act_staged(h, obs, xi, ad, n, action, ad, logprob, value, [&](const float* o, const float* x, float* a, float* lp, float* v) {
+    return wide_policy_act_gauss(h, o, x, n, a, lp, value ? v : nullptr);
+  });
 }
 
 int32_t crl_logprob_actions_gaussian(crl_ppo* h, const float* obs, const float* actions, int32_t n, float* logprob, float* entropy) {
@@ -655,35 +665,16 @@ int32_t crl_logprob_actions_gaussian(crl_ppo* h, const float* obs, const float* 
   CRL_NEED_PARAMS(h, "crl_logprob_actions_gaussian");
   if (n < 0 || (n > 0 && (!obs || !actions || !logprob || !entropy))) { set_error("crl_logprob_actions_gaussian: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t d = (size_t)h->dc.D, ad = (size_t)h->act_dim, N = (size_t)n;
-  const size_t o_obs = 0, o_act = o_obs + ((N * d * 4 + 15) & ~(size_t)15), o_lp = o_act + N * ad * 4, o_ent = o_lp + N * 4, total = o_ent + N * 4;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_obs, obs, N * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, actions, N * ad * 4, hipMemcpyHostToDevice, h->stream));
-  if (wide_logprob_actions_gauss(h, (const float*)(s + o_obs), (const float*)(s + o_act), n, (float*)(s + o_lp), (float*)(s + o_ent))) return 1;
-  CRL_HIP_CHECK(hipMemcpyAsync(logprob, s + o_lp, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(entropy, s + o_ent, N * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return logprob_actions_staged(h, obs, actions, (size_t)h->act_dim, n, logprob, entropy, 1, [&](const float* o, const float* a, float* lp, float* ent) {
+    return wide_logprob_actions_gauss(h, o, a, n, lp, ent);
+  });
 }
 
 int32_t crl_rollout_store_gaussian(crl_ppo* h, int32_t step, const float* obs, const float* action, const float* logprob, const float* reward,
                                    const uint8_t* terminal, const float* value) {
   CRL_GUARD_SETTLED(h);
   if (need_gauss(h, "crl_rollout_store_gaussian")) return 1;
-  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_store_gaussian: step out of range"); return 1; }
-  if (!obs || !action || !logprob || !reward || !terminal || !value) { set_error("crl_rollout_store_gaussian: null argument"); return 1; }
-  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D, ad = (size_t)h->act_dim, off = nt * (size_t)step;
-  CRL_HIP_CHECK(hipMemcpyAsync(h->obs + off * d, obs, nt * d * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->action_f + off * ad, action, nt * ad * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->logprob + off, logprob, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->reward + off, reward, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->terminal + off, terminal, nt, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(h->value + off, value, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));  // host buffers are only borrowed for the call
-  h->recs_dirty = true;
-  return 0;
+  return rollout_store(h, "crl_rollout_store_gaussian", step, obs, h->action_f, action, (size_t)h->act_dim * 4, logprob, reward, terminal, value);
 }
 
 int32_t crl_env_reset(crl_ppo* h) {
@@ -720,19 +711,10 @@ int32_t crl_env_step(crl_ppo* h, const int32_t* action, uint64_t gstep, float* n
   if (need_stateful_env(h, "crl_env_step")) return 1;
   if (!action) { set_error("crl_env_step: null action"); return 1; }
   if (ensure_env(h)) return 1;
-  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D;
-  const size_t o_act = 0, o_rew = o_act + nt * 4, o_bad = o_rew + nt * 4, o_done = o_bad + 16, total = o_done + nt;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, action, nt * 4, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemsetAsync(s + o_bad, 0, 16, h->stream));
-  if (launch_env_step(h, (const int32_t*)(s + o_act), gstep, (float*)(s + o_rew), (uint8_t*)(s + o_done), (uint32_t*)(s + o_bad))) return 1;
   uint32_t bad = 0;
-  CRL_HIP_CHECK(hipMemcpyAsync(&bad, s + o_bad, 4, hipMemcpyDeviceToHost, h->stream));
-  if (next_obs) CRL_HIP_CHECK(hipMemcpyAsync(next_obs, h->cur_obs, nt * d * 4, hipMemcpyDeviceToHost, h->stream));
-  if (reward) CRL_HIP_CHECK(hipMemcpyAsync(reward, s + o_rew, nt * 4, hipMemcpyDeviceToHost, h->stream));
-  if (done) CRL_HIP_CHECK(hipMemcpyAsync(done, s + o_done, nt, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  if (env_step_staged(h, action, next_obs, reward, done, &bad, [&](const int32_t* a, float* r, uint8_t* dn, uint32_t* b) {
+        return launch_env_step(h, a, gstep, r, dn, b);
+      })) return 1;
   if (bad) { set_error("crl_env_step: an action is outside 0 … n_act - 1 (those envs were not stepped)"); return 1; }
   return 0;
 }
@@ -743,17 +725,9 @@ int32_t crl_env_step_gaussian(crl_ppo* h, const float* action, uint64_t gstep, f
   if (!env_continuous(h->cfg.env_kind)) { set_error("crl_env_step_gaussian needs the on-device continuous env (CRL_ENV_PENDULUM)"); return 1; }
   if (!action) { set_error("crl_env_step_gaussian: null action"); return 1; }
   if (ensure_env(h)) return 1;
-  const size_t nt = (size_t)h->dc.nt, d = (size_t)h->dc.D;
-  const size_t o_act = 0, o_rew = o_act + nt * 4, o_done = o_rew + nt * 4, total = o_done + nt;
-  if (ensure_stage(h, total)) return 1;
-  char* s = static_cast<char*>(h->stage);
-  CRL_HIP_CHECK(hipMemcpyAsync(s + o_act, action, nt * 4, hipMemcpyHostToDevice, h->stream));
-  if (gauss_env_step(h, (const float*)(s + o_act), gstep, (float*)(s + o_rew), (uint8_t*)(s + o_done))) return 1;
-  if (next_obs) CRL_HIP_CHECK(hipMemcpyAsync(next_obs, h->cur_obs, nt * d * 4, hipMemcpyDeviceToHost, h->stream));
-  if (reward) CRL_HIP_CHECK(hipMemcpyAsync(reward, s + o_rew, nt * 4, hipMemcpyDeviceToHost, h->stream));
-  if (done) CRL_HIP_CHECK(hipMemcpyAsync(done, s + o_done, nt, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
-  return 0;
+  return env_step_staged(h, action, next_obs, reward, done, nullptr, [&](const float* a, float* r, uint8_t* dn, uint32_t*) {
+    return gauss_env_step(h, a, gstep, r, dn);
+  });
 }
 
 // Held-out evaluation (csrc/eval.hip): argument checks, scratch, ONE launch, the per-episode arrays back to the host, the report in Float64.
@@ -774,19 +748,18 @@ int32_t crl_ppo_evaluate(crl_ppo* h, const crl_eval_config* cfg, crl_eval_report
     return 1;
   }
   CRL_NEED_PARAMS(h, "crl_ppo_evaluate");
-  const size_t ne = (size_t)(n * E), o_ret = 0, o_len = o_ret + ne * 4, o_tr = o_len + ne * 4, total = o_tr + (size_t)(T * n) * 4;
-  if (ensure_scratch(h, &h->eval_ws, &h->eval_ws_bytes, total)) return 1;
-  char* ws = static_cast<char*>(h->eval_ws);
+  const size_t ne = (size_t)(n * E);
+  Staged s(h->stream);
+  const auto s_ret = s.add<float>(ne);
+  const auto s_len = s.add<int32_t>(ne), s_tr = s.add<int32_t>((size_t)(T * n));
+  if (s.reserve(h->eval_ws)) return 1;
   // every (episode, env) slot is written by the launch (the loop bound covers the longest quota); a slot that was not shows as length 0 below.
   // Trace rows behind an env's last step — and behind the step a whole tile finished at — stay at -1.
-  CRL_HIP_CHECK(hipMemsetAsync(ws + o_ret, 0, 2 * ne * 4, h->stream));
-  if (T > 0) CRL_HIP_CHECK(hipMemsetAsync(ws + o_tr, 0xFF, (size_t)(T * n) * 4, h->stream));
-  if (launch_eval(h, cfg, (float*)(ws + o_ret), (int32_t*)(ws + o_len), T > 0 ? (int32_t*)(ws + o_tr) : nullptr)) return 1;
+  CRL_HIP_CHECK(hipMemsetAsync(s.at(s_ret), 0, (size_t)(reinterpret_cast<char*>(s.at(s_len) + ne) - reinterpret_cast<char*>(s.at(s_ret))), h->stream));   // returns and lengths
+  if (T > 0) CRL_HIP_CHECK(hipMemsetAsync(s.at(s_tr), 0xFF, (size_t)(T * n) * 4, h->stream));
+  if (launch_eval(h, cfg, s.at(s_ret), s.at(s_len), T > 0 ? s.at(s_tr) : nullptr)) return 1;
   std::vector<float> ret(ne); std::vector<int32_t> len(ne);
-  CRL_HIP_CHECK(hipMemcpyAsync(ret.data(), ws + o_ret, ne * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(len.data(), ws + o_len, ne * 4, hipMemcpyDeviceToHost, h->stream));
-  if (T > 0) CRL_HIP_CHECK(hipMemcpyAsync(trace_action, ws + o_tr, (size_t)(T * n) * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  if (s.get(s_ret, ret.data()) || s.get(s_len, len.data()) || s.get(s_tr, trace_action) || s.finish()) return 1;
   const int cap = eval_episode_cap(h->cfg.env_kind);
   double rsum = 0.0, lsum = 0.0, rmin = (double)ret[0], rmax = (double)ret[0];
   int64_t steps = 0;

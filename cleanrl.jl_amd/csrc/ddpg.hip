@@ -813,21 +813,12 @@ struct crl_ddpg {
   hipStream_t stream = nullptr;
   crl::DDPGDev d;
   double* pinned = nullptr;      // external env: the staging slot's host side
-  void* scratch = nullptr; size_t scratch_bytes = 0;   // crl_ddpg_actor / crl_ddpg_q_values
+  crl::Scratch scratch;          // crl_ddpg_actor / crl_ddpg_q_values / crl_ddpg_evaluate
 };
 
 using namespace crl;
 
-#define DDPG_GUARD(h)                                          \
-  if (!(h)) { set_error("null crl_ddpg handle"); return 1; }   \
-  CRL_HIP_CHECK(hipSetDevice((h)->device));
-
-template <typename T>
-static int galloc(T** p, size_t n) {
-  CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  CRL_HIP_CHECK(hipMemset(*p, 0, n * sizeof(T)));
-  return 0;
-}
+#define DDPG_GUARD(h) CRL_HANDLE_GUARD(h, "crl_ddpg")
 
 // the three kinds of handle: 0 DDPG, 1 TD3, 2 SAC
 static const char* const KIND[3] = {"ddpg", "td3", "sac"};
@@ -856,15 +847,6 @@ static void enqueue_cycle(const crl_ddpg* h) {
   if (kind == 2) launch(sac_collect_kernel, 1, 64, h->sd);                               // F
   else if (kind == 1) launch(td3_collect_kernel, 1, 64, h->topt);
   else launch(ddpg_collect_kernel, 1, 64);
-}
-
-static int ddpg_scratch(crl_ddpg* h, size_t need) {
-  if (h->scratch_bytes >= need) return 0;
-  if (h->scratch) CRL_HIP_CHECK(hipFree(h->scratch));
-  h->scratch = nullptr; h->scratch_bytes = 0;
-  CRL_HIP_CHECK(hipMalloc(&h->scratch, need));
-  h->scratch_bytes = need;
-  return 0;
 }
 
 // crl_ddpg_param_count (head_rows_per_act = 1) and crl_sac_param_count (2), fn the caller's name
@@ -918,20 +900,20 @@ static int32_t ddpg_create(const crl_ddpg_config* cfg, const crl_td3_options* to
   const size_t na = (size_t)h->na, nc = (size_t)h->nc;
   DDPGDev& d = h->d;
   int rc = 0;
-  rc |= galloc(&d.actor, na); rc |= galloc(&d.ma, na); rc |= galloc(&d.va, na);
-  rc |= galloc(&d.critic, Q * nc); rc |= galloc(&d.critic_t, Q * nc); rc |= galloc(&d.mc, Q * nc); rc |= galloc(&d.vc, Q * nc);
-  rc |= galloc(&d.betap, 12 * (Q + 1) + (sopt ? 2 : 0)); rc |= galloc(&d.ctl, 1); rc |= galloc(&d.eps, DDPG_MAX_EPS); rc |= galloc(&d.losses, DDPG_MAX_LOSSES);
-  rc |= galloc(&d.rb_state, cap * D); rc |= galloc(&d.rb_next, cap * D); rc |= galloc(&d.rb_action, cap * A); rc |= galloc(&d.rb_reward, cap);
-  rc |= galloc(&d.rb_terminal, cap); rc |= galloc(&d.idx, k);
-  rc |= galloc(&d.X, k * (D + A)); rc |= galloc(&d.cH1, Q * k * GH); rc |= galloc(&d.cH2, Q * k * GH);
-  rc |= galloc(&d.cD1, Q * k * GH); rc |= galloc(&d.cD2, Q * k * GH); rc |= galloc(&d.dz, Q * k); rc |= galloc(&d.sq, Q * k);
-  rc |= galloc(&d.aH1, k * GH); rc |= galloc(&d.aH2, k * GH); rc |= galloc(&d.aD1, k * GH); rc |= galloc(&d.aD2, k * GH);
-  rc |= galloc(&d.aD3, k * HR); rc |= galloc(&d.Qa, k);
-  if (!sopt) { rc |= galloc(&d.actor_t, na); rc |= galloc(&d.aY, k * A); }   // SAC has no target actor and keeps no tanh outputs: both stay null
+  rc |= dalloc(&d.actor, na); rc |= dalloc(&d.ma, na); rc |= dalloc(&d.va, na);
+  rc |= dalloc(&d.critic, Q * nc); rc |= dalloc(&d.critic_t, Q * nc); rc |= dalloc(&d.mc, Q * nc); rc |= dalloc(&d.vc, Q * nc);
+  rc |= dalloc(&d.betap, 12 * (Q + 1) + (sopt ? 2 : 0)); rc |= dalloc(&d.ctl, 1); rc |= dalloc(&d.eps, DDPG_MAX_EPS); rc |= dalloc(&d.losses, DDPG_MAX_LOSSES);
+  rc |= dalloc(&d.rb_state, cap * D); rc |= dalloc(&d.rb_next, cap * D); rc |= dalloc(&d.rb_action, cap * A); rc |= dalloc(&d.rb_reward, cap);
+  rc |= dalloc(&d.rb_terminal, cap); rc |= dalloc(&d.idx, k);
+  rc |= dalloc(&d.X, k * (D + A)); rc |= dalloc(&d.cH1, Q * k * GH); rc |= dalloc(&d.cH2, Q * k * GH);
+  rc |= dalloc(&d.cD1, Q * k * GH); rc |= dalloc(&d.cD2, Q * k * GH); rc |= dalloc(&d.dz, Q * k); rc |= dalloc(&d.sq, Q * k);
+  rc |= dalloc(&d.aH1, k * GH); rc |= dalloc(&d.aH2, k * GH); rc |= dalloc(&d.aD1, k * GH); rc |= dalloc(&d.aD2, k * GH);
+  rc |= dalloc(&d.aD3, k * HR); rc |= dalloc(&d.Qa, k);
+  if (!sopt) { rc |= dalloc(&d.actor_t, na); rc |= dalloc(&d.aY, k * A); }   // SAC has no target actor and keeps no tanh outputs: both stay null
   if (sopt) {
-    rc |= galloc(&h->sd.log_alpha, 3); rc |= galloc(&h->sd.lp, k); rc |= galloc(&h->sd.sctl, 1); rc |= galloc(&h->sd.arecs, DDPG_MAX_LOSSES);
+    rc |= dalloc(&h->sd.log_alpha, 3); rc |= dalloc(&h->sd.lp, k); rc |= dalloc(&h->sd.sctl, 1); rc |= dalloc(&h->sd.arecs, DDPG_MAX_LOSSES);
   }
-  rc |= galloc(&d.stage, 2 * D + 2 * A + 2);
+  rc |= dalloc(&d.stage, 2 * D + 2 * A + 2);
   if (!rc && hipHostMalloc(reinterpret_cast<void**>(&h->pinned), (2 * D + 2 * A + 2) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
     set_error("crl_ddpg_create: hipHostMalloc failed"); h->pinned = nullptr; rc = 1;
   }
@@ -1001,8 +983,9 @@ int32_t crl_ddpg_destroy(crl_ddpg* h) {
   DDPGDev& d = h->d;
   void* ptrs[] = {d.actor, d.actor_t, d.ma, d.va, d.critic, d.critic_t, d.mc, d.vc, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_action,
                   d.rb_reward, d.rb_terminal, d.idx, d.X, d.cH1, d.cH2, d.cD1, d.cD2, d.dz, d.sq, d.aH1, d.aH2, d.aD1, d.aD2, d.aY, d.aD3, d.Qa, d.stage,
-                  h->scratch, h->sd.log_alpha, h->sd.lp, h->sd.sctl, h->sd.arecs};
+                  h->sd.log_alpha, h->sd.lp, h->sd.sctl, h->sd.arecs};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  scratch_release(h->scratch);
   if (h->pinned) (void)hipHostFree(h->pinned);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -1182,16 +1165,15 @@ int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out) {
   if (n < 0 || (n > 0 && (!obs || !out))) { set_error("crl_ddpg_actor: bad arguments"); return 1; }
   if (n == 0) return 0;
   const size_t N = (size_t)n, D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
-  if (ddpg_scratch(h, N * (D + A) * 8)) return 1;
-  double* so = static_cast<double*>(h->scratch);
-  double* sa = so + N * D;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * D * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->sac) hipLaunchKernelGGL(sac_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, n, sa);
-  else hipLaunchKernelGGL(ddpg_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, so, n, sa);
+  Staged s(h->stream);
+  const auto s_obs = s.add<double>(N * D), s_act = s.add<double>(N * A);
+  if (s.reserve(h->scratch)) return 1;
+  if (s.put(s_obs, obs)) return 1;
+  if (h->sac) hipLaunchKernelGGL(sac_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, s.at(s_obs), n, s.at(s_act));
+  else hipLaunchKernelGGL(ddpg_actor_eval_kernel, dim3(n), dim3(64), 0, h->stream, h->d, s.at(s_obs), n, s.at(s_act));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(out, sa, N * A * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_act, out)) return 1;
+  return s.finish();
 }
 
 }  // extern "C"
@@ -1199,19 +1181,16 @@ int32_t crl_ddpg_actor(crl_ddpg* h, const double* obs, int32_t n, double* out) {
 // get_q of critic `which` (0; 1 on a TD3 handle) for n staged pairs
 static int32_t ddpg_q_eval(crl_ddpg* h, int which, const double* obs, const double* act, int32_t n, double* out) {
   const size_t N = (size_t)n, D = (size_t)h->cfg.obs_dim, A = (size_t)h->cfg.act_dim;
-  if (ddpg_scratch(h, N * (D + A + 1) * 8)) return 1;
-  double* so = static_cast<double*>(h->scratch);
-  double* sa = so + N * D;
-  double* sq = sa + N * A;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * D * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(sa, act, N * A * 8, hipMemcpyHostToDevice, h->stream));
+  Staged s(h->stream);
+  const auto s_obs = s.add<double>(N * D), s_act = s.add<double>(N * A), s_q = s.add<double>(N);
+  if (s.reserve(h->scratch)) return 1;
+  if (s.put(s_obs, obs) || s.put(s_act, act)) return 1;
   DDPGDev d = h->d;
   d.critic += (size_t)which * (size_t)h->nc;
-  hipLaunchKernelGGL(ddpg_q_eval_kernel, dim3(n), dim3(64), 0, h->stream, d, so, sa, n, sq);
+  hipLaunchKernelGGL(ddpg_q_eval_kernel, dim3(n), dim3(64), 0, h->stream, d, s.at(s_obs), s.at(s_act), n, s.at(s_q));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(out, sq, N * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_q, out)) return 1;
+  return s.finish();
 }
 
 // the parameter calls of a two-critic handle, behind crl_td3_* (want = 1) and crl_sac_* (want = 2); fn = the caller's name
@@ -1369,17 +1348,17 @@ int32_t crl_ddpg_evaluate(crl_ddpg* h, const crl_ddpg_eval_config* cfg, crl_ddpg
   if ((T > 0) != (trace_action != nullptr)) { set_error("crl_ddpg_evaluate: trace_action must be given exactly when trace_steps > 0"); return 1; }
   if (T * n > (1 << 24)) { set_error("crl_ddpg_evaluate: trace_steps * num_envs must be <= 16777216, got " + std::to_string(T * n)); return 1; }
   const size_t ne = (size_t)(n * E), nt = (size_t)(T * n);
-  if (ddpg_scratch(h, (3 * ne + nt) * 8)) return 1;
+  Staged s(h->stream);
+  const auto s_arrays = s.add<double>(3 * ne), s_trace = s.add<double>(nt);   // returns | discounted returns | q0 come back as one copy
+  if (s.reserve(h->scratch)) return 1;
   DDPGEvalArgs ev;
   ev.n = (int32_t)n; ev.episodes = (int32_t)E; ev.trace_steps = (int32_t)T; ev.head_rows = h->sac ? 2 : 1; ev.seed = cfg->seed;
-  ev.ret = static_cast<double*>(h->scratch); ev.disc_ret = ev.ret + ne; ev.q0 = ev.disc_ret + ne; ev.trace = ev.q0 + ne;
+  ev.ret = s.at(s_arrays); ev.disc_ret = ev.ret + ne; ev.q0 = ev.disc_ret + ne; ev.trace = s.at(s_trace);
   // every slot of the four arrays is written: each env runs episodes_per_env episodes of exactly max_steps steps
   hipLaunchKernelGGL(ddpg_eval_kernel, dim3((unsigned)((n + EVAL_WAVES - 1) / EVAL_WAVES)), dim3(64 * EVAL_WAVES), 0, h->stream, h->d, ev);
   CRL_HIP_CHECK(hipGetLastError());
   std::vector<double> host(3 * ne);
-  CRL_HIP_CHECK(hipMemcpyAsync(host.data(), ev.ret, 3 * ne * 8, hipMemcpyDeviceToHost, h->stream));
-  if (T > 0) CRL_HIP_CHECK(hipMemcpyAsync(trace_action, ev.trace, nt * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  if (s.get(s_arrays, host.data()) || s.get(s_trace, trace_action) || s.finish()) return 1;
   const double *ret = host.data(), *disc = ret + ne, *q = disc + ne;
   double rsum = 0.0, dsum = 0.0, qsum = 0.0, bsum = 0.0, rmin = ret[0], rmax = ret[0];
   for (size_t i = 0; i < ne; ++i) {

@@ -154,28 +154,25 @@ int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_va
   int per_cu = 0;
   if (rs_dispatch_h(H, [&](auto hc) { return rs_role_per_cu(diag_kernel<decltype(hc)::value>, H, lds, &per_cu); })) return 1;
   const int nblk = 2 * rs_role_pairs(h, per_cu, B);
-  const bool per_sample = new_logprob || new_value;
-  const size_t o_lp = ((size_t)nblk * DIAG_REC * 8 + 255) & ~(size_t)255, o_v = o_lp + (per_sample ? (size_t)B * 4 : 0), total = o_v + (per_sample ? (size_t)B * 4 : 0);
-  if (ensure_scratch(h, &h->diag_ws, &h->diag_ws_bytes, total)) return 1;
+  Staged s(h->stream);
+  const auto s_part = s.add<double>((size_t)nblk * DIAG_REC);
+  const auto s_lp = s.add<float>(new_logprob ? (size_t)B : 0), s_v = s.add<float>(new_value ? (size_t)B : 0);
+  if (s.reserve(h->diag_ws)) return 1;
   if (!h->diag_ev[0]) { CRL_HIP_CHECK(hipEventCreate(&h->diag_ev[0])); CRL_HIP_CHECK(hipEventCreate(&h->diag_ev[1])); }
-  char* ws = static_cast<char*>(h->diag_ws);
   DiagArgs a;
   a.params = h->params; a.Pa = h->Pa;
   a.obs = h->obs; a.action = h->action; a.logprob = h->logprob; a.value = h->value; a.ret = h->ret;
   a.D = D; a.w1_lds = w1_lds ? 1 : 0; a.A = A; a.B = B; a.clip = h->dc.clip;
-  a.part = reinterpret_cast<double*>(ws);
-  a.new_logprob = new_logprob ? reinterpret_cast<float*>(ws + o_lp) : nullptr;
-  a.new_value = new_value ? reinterpret_cast<float*>(ws + o_v) : nullptr;
+  a.part = s.at(s_part);
+  a.new_logprob = new_logprob ? s.at(s_lp) : nullptr;
+  a.new_value = new_value ? s.at(s_v) : nullptr;
   const dim3 grid(nblk), block(2 * H);
   CRL_HIP_CHECK(hipEventRecord(h->diag_ev[0], h->stream));
   rs_dispatch_h(H, [&](auto hc) { hipLaunchKernelGGL(diag_kernel<decltype(hc)::value>, grid, block, lds, h->stream, a); return 0; });
   CRL_HIP_CHECK(hipGetLastError());
   CRL_HIP_CHECK(hipEventRecord(h->diag_ev[1], h->stream));
   std::vector<double> part((size_t)nblk * DIAG_REC);
-  CRL_HIP_CHECK(hipMemcpyAsync(part.data(), ws, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  if (new_logprob) CRL_HIP_CHECK(hipMemcpyAsync(new_logprob, ws + o_lp, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (new_value) CRL_HIP_CHECK(hipMemcpyAsync(new_value, ws + o_v, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));   // host buffers are only borrowed for the call
+  if (s.get(s_part, part.data()) || s.get(s_lp, new_logprob) || s.get(s_v, new_value) || s.finish()) return 1;
   float ms = 0.0f;
   CRL_HIP_CHECK(hipEventElapsedTime(&ms, h->diag_ev[0], h->diag_ev[1]));
   h->diag_last_ns = (int64_t)((double)ms * 1e6);

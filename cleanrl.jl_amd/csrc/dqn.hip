@@ -11,6 +11,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 
@@ -986,17 +987,14 @@ struct crl_dqn {
   bool params_set = false;   // dqn.jl:39-40 has happened: q_net was uploaded or crl_dqn_init_params ran (a fresh handle holds zeros)
   hipStream_t stream = nullptr;
   crl::DQNDev d;
-  void* stage = nullptr; size_t stage_bytes = 0;
-  crl::ValueEvalScratch eval;   // crl_dqn_evaluate
+  crl::Scratch stage;           // the forward-only calls and the four probes
+  crl::Scratch eval;            // crl_dqn_evaluate
   hipGraphExec_t cycle_exec = nullptr; bool graph_failed = false;   // CRL_DQN_GRAPH=1 replays the cycle as a hipGraph
   bool per = false;                                                 // made by crl_dqn_per_create
-  double* probe_tree = nullptr; int32_t* probe_idx = nullptr; double* probe_w = nullptr;   // crl_dqn_per_probe's scratch
   bool tgt = false;                                                 // made by crl_dqn_create_with
-  void* walk_scratch = nullptr;                                     // crl_dqn_nstep_probe's scratch
   bool c51 = false;                                                 // the head has 2N rows: made with crl_dqn_c51_options, or with crl_dqn_qr_options (then qr holds too)
   bool qr = false;                                                  // made by crl_dqn_qr_create: the 2N rows are quantile locations (d.c51.kind == HEAD_QR)
   size_t P = (size_t)crl::QP;                                       // the handle's parameter count: 10934, 10764 + 85·2N on a C51 handle, 20928 + 255·R on a dueling one
-  void* proj_scratch = nullptr;                                     // crl_dqn_c51_project_probe's / crl_dqn_qr_loss_probe's scratch
   bool duel = false;                                                // made by crl_dqn_dueling_create: P = 20928 + 255·R, R = 1 or n_atoms
   bool noisy = false;                                               // made by crl_dqn_noisy_create: P is still the twin's count = the images' length
   size_t n_params = (size_t)crl::QP;                                // what crl_dqn_param_count reports and write / read take: P, or 2P (mu, sigma) on a noisy handle
@@ -1008,16 +1006,7 @@ struct crl_dqn {
 
 using namespace crl;
 
-#define DQN_GUARD(h)                                          \
-  if (!(h)) { set_error("null crl_dqn handle"); return 1; }   \
-  CRL_HIP_CHECK(hipSetDevice((h)->device));
-
-template <typename T>
-static int qalloc(T** p, size_t n) {
-  CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  CRL_HIP_CHECK(hipMemset(*p, 0, n * sizeof(T)));
-  return 0;
-}
+#define DQN_GUARD(h) CRL_HANDLE_GUARD(h, "crl_dqn")
 
 // dynamic LDS of the collect and the evaluation launch of a categorical / a dueling handle with P parameters
 static size_t c51_collect_lds(int P) { return C51_COLLECT_LDS + (size_t)P * 4; }
@@ -1094,20 +1083,20 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   const size_t U2 = duel ? DUEL_U2 : QH2, NARR = duel ? DUEL_ARRAYS : 6;   // hidden units of layer 2 per sample; arrays Adam keeps a β-power pair for
   const size_t NZ = noisy ? 2 : 1;   // a noisy handle keeps Adam state for mu and sigma: 2P entries, twice the arrays
   h->P = NP; h->n_params = NZ * NP;
-  rc |= qalloc(&d.q, NP); rc |= qalloc(&d.t, NP); rc |= qalloc(&d.grads, NP); rc |= qalloc(&d.m, NZ * NP); rc |= qalloc(&d.v, NZ * NP);
-  rc |= qalloc(&d.betap, 2 * NZ * NARR); rc |= qalloc(&d.ctl, 1); rc |= qalloc(&d.eps, DQN_MAX_EPS); rc |= qalloc(&d.losses, DQN_MAX_LOSSES);
-  rc |= qalloc(&d.rb_state, cap * QD); rc |= qalloc(&d.rb_next, cap * QD); rc |= qalloc(&d.rb_reward, cap);
-  rc |= qalloc(&d.rb_action, cap); rc |= qalloc(&d.rb_terminal, cap);
+  rc |= dalloc(&d.q, NP); rc |= dalloc(&d.t, NP); rc |= dalloc(&d.grads, NP); rc |= dalloc(&d.m, NZ * NP); rc |= dalloc(&d.v, NZ * NP);
+  rc |= dalloc(&d.betap, 2 * NZ * NARR); rc |= dalloc(&d.ctl, 1); rc |= dalloc(&d.eps, DQN_MAX_EPS); rc |= dalloc(&d.losses, DQN_MAX_LOSSES);
+  rc |= dalloc(&d.rb_state, cap * QD); rc |= dalloc(&d.rb_next, cap * QD); rc |= dalloc(&d.rb_reward, cap);
+  rc |= dalloc(&d.rb_action, cap); rc |= dalloc(&d.rb_terminal, cap);
   const size_t nets = tgt && tgt->double_q ? 3 : 2;
   d.nets = (int32_t)nets;
-  rc |= qalloc(&d.H1, nets * QH1 * k); rc |= qalloc(&d.H2, nets * U2 * k); rc |= qalloc(&d.Q, nets * QA * k);
-  rc |= qalloc(&d.dz, k); rc |= qalloc(&d.sq, k); rc |= qalloc(&d.d2, U2 * k); rc |= qalloc(&d.d1, QH1 * k); rc |= qalloc(&d.idx, k);
+  rc |= dalloc(&d.H1, nets * QH1 * k); rc |= dalloc(&d.H2, nets * U2 * k); rc |= dalloc(&d.Q, nets * QA * k);
+  rc |= dalloc(&d.dz, k); rc |= dalloc(&d.sq, k); rc |= dalloc(&d.d2, U2 * k); rc |= dalloc(&d.d1, QH1 * k); rc |= dalloc(&d.idx, k);
   d.boot = d.idx;
   if (tgt) {
     h->tgt = true;
     TgtDev& t = d.tgt;
     t.on = 1; t.n_step = tgt->n_step; t.double_q = tgt->double_q;
-    rc |= qalloc(&t.last, k); rc |= qalloc(&t.m, k); rc |= qalloc(&t.astar, k); rc |= qalloc(&t.nret, k); rc |= qalloc(&t.ndisc, k); rc |= qalloc(&t.td, k);
+    rc |= dalloc(&t.last, k); rc |= dalloc(&t.m, k); rc |= dalloc(&t.astar, k); rc |= dalloc(&t.nret, k); rc |= dalloc(&t.ndisc, k); rc |= dalloc(&t.td, k);
     d.boot = t.last;
   }
   if (per) {
@@ -1115,7 +1104,7 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     PerDev& p = d.per;
     p.on = 1; p.C = per_tree_leaves(cfg->buffer_size);
     p.alpha = per->alpha; p.beta_start = per->beta_start; p.beta_end = per->beta_end; p.beta_duration = per->beta_duration; p.eps = per->eps;
-    rc |= qalloc(&p.tree, 2 * (size_t)p.C); rc |= qalloc(&p.ctl, 1); rc |= qalloc(&p.w, k); rc |= qalloc(&p.abs_td, k);
+    rc |= dalloc(&p.tree, 2 * (size_t)p.C); rc |= dalloc(&p.ctl, 1); rc |= dalloc(&p.w, k); rc |= dalloc(&p.abs_td, k);
     if (!rc) {
       PerCtl pc;
       memset(&pc, 0, sizeof(pc));
@@ -1129,7 +1118,7 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
     const size_t N = (size_t)c51->n_atoms;
     c.on = 1; c.N = c51->n_atoms; c.P = (int32_t)NP; c.v_min = c51->v_min; c.v_max = c51->v_max;
     if (qr) { h->qr = true; c.kind = HEAD_QR; c.kappa = qr->kappa; }
-    rc |= qalloc(&c.L, nets * 2 * N * k); rc |= qalloc(&c.dl, N * k); rc |= qalloc(&c.proj, N * k); rc |= qalloc(&c.sloss, k);
+    rc |= dalloc(&c.L, nets * 2 * N * k); rc |= dalloc(&c.dl, N * k); rc |= dalloc(&c.proj, N * k); rc |= dalloc(&c.sloss, k);
     // the net in LDS passes the 64 KB a launch gets without asking at N >= 36; the CU has 160 KB. Set for the largest head (set_dyn_lds).
     constexpr int PMAX = QoW3 + 85 * 2 * C51_MAX_ATOMS;
     if (!rc && !(qr ? set_dyn_lds(dqn_c51_collect_kernel<true>, c51_collect_lds(PMAX)) && set_dyn_lds(dqn_c51_eval_kernel<true>, c51_eval_lds(PMAX))
@@ -1150,7 +1139,7 @@ static int32_t dqn_create(const crl_dqn_config* cfg, const crl_dqn_per_options* 
   if (noisy) {
     h->noisy = true; h->sigma0 = noisy->sigma0;
     d.noisy.on = 1; d.noisy.P = (int32_t)NP;
-    rc |= qalloc(&d.noisy.pq, 2 * NP); rc |= qalloc(&d.noisy.pt, 2 * NP); rc |= qalloc(&h->xi_scratch, (size_t)NOISY_MAX_XI);
+    rc |= dalloc(&d.noisy.pq, 2 * NP); rc |= dalloc(&d.noisy.pt, 2 * NP); rc |= dalloc(&h->xi_scratch, (size_t)NOISY_MAX_XI);
   }
   if (rc) { crl_dqn_destroy(h); return 1; }
   double bp[2 * 2 * DUEL_ARRAYS];
@@ -1311,17 +1300,6 @@ int32_t crl_dqn_noisy_noise(crl_dqn* h, uint64_t gen, int32_t net, float* xi, si
   return 0;
 }
 
-// the stage buffer of the forward-only calls, grown on demand
-static int dqn_stage(crl_dqn* h, size_t need) {
-  if (h->stage_bytes < need) {
-    if (h->stage) CRL_HIP_CHECK(hipFree(h->stage));
-    h->stage = nullptr; h->stage_bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&h->stage, need));
-    h->stage_bytes = need;
-  }
-  return 0;
-}
-
 // the one-observation-per-block launch of a handle with a 2N-row or a dueling head: Q(a), the head's rows (probabilities or quantile locations), the
 // streams — whichever pointers are given; the head kind picks the instantiation
 static void launch_obs_kernel(crl_dqn* h, const double* so, int32_t n, double* out_q, double* out_rows, double* out_v, double* out_a) {
@@ -1332,23 +1310,36 @@ static void launch_obs_kernel(crl_dqn* h, const double* so, int32_t n, double* o
                           out_rows);
 }
 
+// The forward-only calls: n observations in, one block per observation, the arrays the caller names out — each is one of the launch's outputs with
+// `width` doubles per observation. A section is staged for every named output, wanted by the host or not; a scalar single-head handle (reached by
+// crl_dqn_q_values only) has its own kernel.
+enum ObsSlot { OBS_Q, OBS_ROWS, OBS_V, OBS_A, OBS_SLOTS };
+struct ObsOut { ObsSlot slot; size_t width; double* host; };
+static int32_t dqn_obs_call(crl_dqn* h, const double* obs, int32_t n, std::initializer_list<ObsOut> outs) {
+  const size_t N = (size_t)n;
+  Staged s(h->stream);
+  const auto s_obs = s.add<double>(N * QD);
+  Section<double> sec[OBS_SLOTS];
+  for (const ObsOut& o : outs) sec[o.slot] = s.add<double>(N * o.width);
+  if (s.reserve(h->stage)) return 1;
+  double* dev[OBS_SLOTS] = {};
+  for (const ObsOut& o : outs) dev[o.slot] = s.at(sec[o.slot]);
+  if (s.put(s_obs, obs)) return 1;
+  if (h->duel || h->c51) launch_obs_kernel(h, s.at(s_obs), n, dev[OBS_Q], dev[OBS_ROWS], dev[OBS_V], dev[OBS_A]);
+  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), (const double*)s.at(s_obs), n, dev[OBS_Q]);
+  CRL_HIP_CHECK(hipGetLastError());
+  for (const ObsOut& o : outs) if (s.get(sec[o.slot], o.host)) return 1;
+  return s.finish();
+}
+
 int32_t crl_dqn_dueling_streams(crl_dqn* h, const double* obs, int32_t n, double* value, double* adv) {
   DQN_GUARD(h);
   if (!h->duel) { set_error("crl_dqn_dueling_streams: the handle has one head; crl_dqn_dueling_create makes a dueling handle"); return 1; }
   if (!h->params_set) { set_error("crl_dqn_dueling_streams: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
   if (n < 0 || (n > 0 && !obs)) { set_error("crl_dqn_dueling_streams: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t N = (size_t)n, R = (size_t)h->d.duel.R;
-  if (dqn_stage(h, N * (QD + 3 * R) * 8)) return 1;
-  double* so = static_cast<double*>(h->stage);
-  double *sv = so + N * QD, *sa = sv + N * R;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  launch_obs_kernel(h, so, n, nullptr, nullptr, sv, sa);
-  CRL_HIP_CHECK(hipGetLastError());
-  if (value) CRL_HIP_CHECK(hipMemcpyAsync(value, sv, N * R * 8, hipMemcpyDeviceToHost, h->stream));
-  if (adv) CRL_HIP_CHECK(hipMemcpyAsync(adv, sa, N * 2 * R * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  const size_t R = (size_t)h->d.duel.R;
+  return dqn_obs_call(h, obs, n, {{OBS_V, R, value}, {OBS_A, 2 * R, adv}});
 }
 
 int32_t crl_dqn_param_count(crl_dqn* h, size_t* n) {
@@ -1382,16 +1373,7 @@ int32_t crl_dqn_qr_quantiles(crl_dqn* h, const double* obs, int32_t n, double* t
   if (!h->params_set) { set_error("crl_dqn_qr_quantiles: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
   if (n < 0 || (n > 0 && (!obs || !theta))) { set_error("crl_dqn_qr_quantiles: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t N = (size_t)n, NA = 2 * (size_t)h->d.c51.N;
-  if (dqn_stage(h, N * (QD + NA) * 8)) return 1;
-  double* so = static_cast<double*>(h->stage);
-  double* sp = so + N * QD;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  launch_obs_kernel(h, so, n, nullptr, sp, nullptr, nullptr);
-  CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(theta, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return dqn_obs_call(h, obs, n, {{OBS_ROWS, 2 * (size_t)h->d.c51.N, theta}});
 }
 
 int32_t crl_dqn_qr_read(crl_dqn* h, double* target, double* sample_loss) {
@@ -1407,23 +1389,17 @@ int32_t crl_dqn_qr_loss_probe(crl_dqn* h, const double* theta, const double* tar
   DQN_QR_GUARD(h, "crl_dqn_qr_loss_probe");
   if (!theta || !target || !loss || !dtheta) { set_error("crl_dqn_qr_loss_probe: null argument"); return 1; }
   if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_qr_loss_probe: k must be in 1..1024"); return 1; }
-  // one allocation: theta | target | dtheta [1024·64] f64 each | loss [1024] f64
-  constexpr size_t rows = (size_t)DQN_MAX_BATCH * C51_MAX_ATOMS * 8, total = 3 * rows + (size_t)DQN_MAX_BATCH * 8;
-  if (!h->proj_scratch) CRL_HIP_CHECK(hipMalloc(&h->proj_scratch, total));
-  char* base = static_cast<char*>(h->proj_scratch);
-  double *dTh = reinterpret_cast<double*>(base), *dT = reinterpret_cast<double*>(base + rows), *dG = reinterpret_cast<double*>(base + 2 * rows),
-         *dL = reinterpret_cast<double*>(base + 3 * rows);
   const C51Dev& c = h->d.c51;
   const size_t K = (size_t)k, N = (size_t)c.N;
-  CRL_HIP_CHECK(hipMemcpyAsync(dTh, theta, K * N * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dT, target, K * N * 8, hipMemcpyHostToDevice, h->stream));
+  Staged s(h->stream);
+  const auto s_theta = s.add<double>(K * N), s_target = s.add<double>(K * N), s_dtheta = s.add<double>(K * N), s_loss = s.add<double>(K);
+  if (s.reserve(h->stage)) return 1;
+  if (s.put(s_theta, theta) || s.put(s_target, target)) return 1;
   hipLaunchKernelGGL(dqn_qr_loss_probe_kernel, dim3((unsigned)((k + C51_TD_WAVES - 1) / C51_TD_WAVES)), dim3(64 * C51_TD_WAVES), 0, h->stream,
-                     (const double*)dTh, (const double*)dT, (int)k, (int)c.N, c.kappa, dL, dG);
+                     (const double*)s.at(s_theta), (const double*)s.at(s_target), (int)k, (int)c.N, c.kappa, s.at(s_loss), s.at(s_dtheta));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(loss, dL, K * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dtheta, dG, K * N * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_loss, loss) || s.get(s_dtheta, dtheta)) return 1;
+  return s.finish();
 }
 
 int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* probs) {
@@ -1431,16 +1407,7 @@ int32_t crl_dqn_c51_probs(crl_dqn* h, const double* obs, int32_t n, double* prob
   if (!h->params_set) { set_error("crl_dqn_c51_probs: parameters not set — crl_dqn_write_params or crl_dqn_init_params first"); return 1; }
   if (n < 0 || (n > 0 && (!obs || !probs))) { set_error("crl_dqn_c51_probs: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t N = (size_t)n, NA = 2 * (size_t)h->d.c51.N, need = N * (QD + NA) * 8;
-  if (dqn_stage(h, need)) return 1;
-  double* so = static_cast<double*>(h->stage);
-  double* sp = so + N * QD;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  launch_obs_kernel(h, so, n, nullptr, sp, nullptr, nullptr);
-  CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(probs, sp, N * NA * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return dqn_obs_call(h, obs, n, {{OBS_ROWS, 2 * (size_t)h->d.c51.N, probs}});
 }
 
 int32_t crl_dqn_c51_read(crl_dqn* h, double* proj, double* sample_loss) {
@@ -1457,26 +1424,18 @@ int32_t crl_dqn_c51_project_probe(crl_dqn* h, const double* probs, const double*
   DQN_C51_GUARD(h, "crl_dqn_c51_project_probe");
   if (!probs || !nret || !ndisc || !terminal || !proj) { set_error("crl_dqn_c51_project_probe: null argument"); return 1; }
   if (k < 1 || k > DQN_MAX_BATCH) { set_error("crl_dqn_c51_project_probe: k must be in 1..1024"); return 1; }
-  // one allocation: probs [1024·64] f64 | proj [1024·64] f64 | nret [1024] f64 | ndisc [1024] f64 | terminal [1024] u8
-  constexpr size_t rows = (size_t)DQN_MAX_BATCH * C51_MAX_ATOMS * 8, oP = 0, oM = oP + rows, oR = oM + rows, oD = oR + (size_t)DQN_MAX_BATCH * 8,
-                   oT = oD + (size_t)DQN_MAX_BATCH * 8, total = oT + DQN_MAX_BATCH;
-  if (!h->proj_scratch) CRL_HIP_CHECK(hipMalloc(&h->proj_scratch, total));
-  char* base = static_cast<char*>(h->proj_scratch);
-  double *dP = reinterpret_cast<double*>(base + oP), *dM = reinterpret_cast<double*>(base + oM), *dR = reinterpret_cast<double*>(base + oR),
-         *dD = reinterpret_cast<double*>(base + oD);
-  uint8_t* dT = reinterpret_cast<uint8_t*>(base + oT);
   const C51Dev& c = h->d.c51;
   const size_t K = (size_t)k, N = (size_t)c.N;
-  CRL_HIP_CHECK(hipMemcpyAsync(dP, probs, K * N * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dR, nret, K * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dD, ndisc, K * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dT, terminal, K, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_c51_project_probe_kernel, dim3(1), dim3(64 * C51_TD_WAVES), 0, h->stream, (const double*)dP, (const double*)dR, (const double*)dD,
-                     (const uint8_t*)dT, (int)k, (int)c.N, c.v_min, c.v_max, dM);
+  Staged s(h->stream);
+  const auto s_probs = s.add<double>(K * N), s_proj = s.add<double>(K * N), s_nret = s.add<double>(K), s_ndisc = s.add<double>(K);
+  const auto s_term = s.add<uint8_t>(K);
+  if (s.reserve(h->stage)) return 1;
+  if (s.put(s_probs, probs) || s.put(s_nret, nret) || s.put(s_ndisc, ndisc) || s.put(s_term, terminal)) return 1;
+  hipLaunchKernelGGL(dqn_c51_project_probe_kernel, dim3(1), dim3(64 * C51_TD_WAVES), 0, h->stream, (const double*)s.at(s_probs), (const double*)s.at(s_nret),
+                     (const double*)s.at(s_ndisc), (const uint8_t*)s.at(s_term), (int)k, (int)c.N, c.v_min, c.v_max, s.at(s_proj));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(proj, dM, K * N * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_proj, proj)) return 1;
+  return s.finish();
 }
 
 int32_t crl_dqn_target_read(crl_dqn* h, int32_t* last, int32_t* m, double* nret, double* ndisc, int32_t* astar, double* td) {
@@ -1503,26 +1462,18 @@ int32_t crl_dqn_nstep_probe(crl_dqn* h, const double* reward, const uint8_t* ter
   if (n_step < 1 || n_step > TGT_MAX_N_STEP) { set_error("crl_dqn_nstep_probe: n_step must be in 1..16"); return 1; }
   for (int32_t j = 0; j < k; ++j)
     if (idx[j] < 0 || idx[j] >= cap) { set_error("crl_dqn_nstep_probe: every idx must be in 0..cap-1"); return 1; }
-  // one allocation: reward [65536] f64 | nret [1024] f64 | ndisc [1024] f64 | idx, last, m [1024] i32 each | terminal [65536] u8
-  constexpr size_t oR = 0, oN = oR + (size_t)DQN_MAX_CAP * 8, oD = oN + (size_t)DQN_MAX_BATCH * 8, oI = oD + (size_t)DQN_MAX_BATCH * 8,
-                   oL = oI + (size_t)DQN_MAX_BATCH * 4, oM = oL + (size_t)DQN_MAX_BATCH * 4, oT = oM + (size_t)DQN_MAX_BATCH * 4, total = oT + DQN_MAX_CAP;
-  if (!h->walk_scratch) CRL_HIP_CHECK(hipMalloc(&h->walk_scratch, total));
-  char* base = static_cast<char*>(h->walk_scratch);
-  double *dR = reinterpret_cast<double*>(base + oR), *dN = reinterpret_cast<double*>(base + oN), *dD = reinterpret_cast<double*>(base + oD);
-  int32_t *dI = reinterpret_cast<int32_t*>(base + oI), *dL = reinterpret_cast<int32_t*>(base + oL), *dM = reinterpret_cast<int32_t*>(base + oM);
-  uint8_t* dT = reinterpret_cast<uint8_t*>(base + oT);
-  CRL_HIP_CHECK(hipMemcpyAsync(dR, reward, (size_t)cap * 8, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dT, terminal, (size_t)cap, hipMemcpyHostToDevice, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(dI, idx, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_nstep_probe_kernel, dim3(1), dim3(1024), 0, h->stream, (const double*)dR, (const uint8_t*)dT, (int)cap, (int)ptr, (const int32_t*)dI,
-                     (int)k, (int)n_step, gamma, dL, dM, dN, dD);
+  const size_t C = (size_t)cap, K = (size_t)k;
+  Staged s(h->stream);
+  const auto s_reward = s.add<double>(C), s_nret = s.add<double>(K), s_ndisc = s.add<double>(K);
+  const auto s_idx = s.add<int32_t>(K), s_last = s.add<int32_t>(K), s_m = s.add<int32_t>(K);
+  const auto s_term = s.add<uint8_t>(C);
+  if (s.reserve(h->stage)) return 1;
+  if (s.put(s_reward, reward) || s.put(s_term, terminal) || s.put(s_idx, idx)) return 1;
+  hipLaunchKernelGGL(dqn_nstep_probe_kernel, dim3(1), dim3(1024), 0, h->stream, (const double*)s.at(s_reward), (const uint8_t*)s.at(s_term), (int)cap, (int)ptr,
+                     (const int32_t*)s.at(s_idx), (int)k, (int)n_step, gamma, s.at(s_last), s.at(s_m), s.at(s_nret), s.at(s_ndisc));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(last, dL, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(m, dM, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(nret, dN, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(ndisc, dD, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_last, last) || s.get(s_m, m) || s.get(s_nret, nret) || s.get(s_ndisc, ndisc)) return 1;
+  return s.finish();
 }
 
 int32_t crl_dqn_per_status_read(crl_dqn* h, crl_dqn_per_status* out) {
@@ -1563,23 +1514,19 @@ int32_t crl_dqn_per_probe(crl_dqn* h, const float* leaves, int32_t n, uint64_t g
   if (!(beta >= 0.0 && beta <= 1.0)) { set_error("crl_dqn_per_probe: beta must be in 0..1"); return 1; }
   for (int32_t i = 0; i < n; ++i)
     if (!((double)leaves[i] >= PER_LEAF_MIN && (double)leaves[i] <= PER_LEAF_MAX)) { set_error("crl_dqn_per_probe: every leaf must be in 2^-100..2^100"); return 1; }
-  if (!h->probe_tree) {
-    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_tree), 2 * (size_t)DQN_MAX_CAP * 8));
-    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_idx), (size_t)DQN_MAX_BATCH * 4));
-    CRL_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->probe_w), (size_t)DQN_MAX_BATCH * 8));
-  }
   const int C = per_tree_leaves(n);
   std::vector<double> t(2 * (size_t)C, 0.0);                 // leaves widened, slots >= n and the inner nodes 0.0 (the kernel rebuilds the inner nodes)
   for (int32_t i = 0; i < n; ++i) t[(size_t)C + (size_t)i] = (double)leaves[i];
-  CRL_HIP_CHECK(hipMemcpyAsync(h->probe_tree, t.data(), t.size() * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dqn_per_probe_kernel, dim3(1), dim3(1024), 0, h->stream, h->probe_tree, C, (int)n, (int)k, h->cfg.seed, gstep, beta, h->probe_idx,
-                     h->probe_w);
+  Staged s(h->stream);
+  const auto s_tree = s.add<double>(t.size());
+  const auto s_idx = s.add<int32_t>((size_t)k);
+  const auto s_w = s.add<double>((size_t)k);
+  if (s.reserve(h->stage)) return 1;
+  if (s.put(s_tree, t.data())) return 1;
+  hipLaunchKernelGGL(dqn_per_probe_kernel, dim3(1), dim3(1024), 0, h->stream, s.at(s_tree), C, (int)n, (int)k, h->cfg.seed, gstep, beta, s.at(s_idx), s.at(s_w));
   CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(idx, h->probe_idx, (size_t)k * 4, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipMemcpyAsync(weight, h->probe_w, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
-  if (tree) CRL_HIP_CHECK(hipMemcpyAsync(tree, h->probe_tree, t.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  if (s.get(s_idx, idx) || s.get(s_w, weight) || s.get(s_tree, tree)) return 1;
+  return s.finish();
 }
 
 int32_t crl_dqn_destroy(crl_dqn* h) {
@@ -1589,11 +1536,12 @@ int32_t crl_dqn_destroy(crl_dqn* h) {
   if (h->cycle_exec) (void)hipGraphExecDestroy(h->cycle_exec);
   DQNDev& d = h->d;
   void* ptrs[] = {d.q, d.t, d.grads, d.m, d.v, d.betap, d.ctl, d.eps, d.losses, d.rb_state, d.rb_next, d.rb_reward, d.rb_action,
-                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx, h->stage, h->eval.p,
-                  d.per.tree, d.per.ctl, d.per.w, d.per.abs_td, h->probe_tree, h->probe_idx, h->probe_w,
-                  d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td, h->walk_scratch,
-                  d.c51.L, d.c51.dl, d.c51.proj, d.c51.sloss, h->proj_scratch, d.noisy.pq, d.noisy.pt, h->xi_scratch};
+                  d.rb_terminal, d.H1, d.H2, d.Q, d.dz, d.sq, d.d2, d.d1, d.idx,
+                  d.per.tree, d.per.ctl, d.per.w, d.per.abs_td,
+                  d.tgt.last, d.tgt.m, d.tgt.astar, d.tgt.nret, d.tgt.ndisc, d.tgt.td,
+                  d.c51.L, d.c51.dl, d.c51.proj, d.c51.sloss, d.noisy.pq, d.noisy.pt, h->xi_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  scratch_release(h->stage); scratch_release(h->eval);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -1694,17 +1642,7 @@ int32_t crl_dqn_q_values(crl_dqn* h, const double* obs, int32_t n, double* q) {
   if (!h->params_set) { set_error("crl_dqn_q_values: parameters not set — crl_dqn_write_params or crl_dqn_init_params first (dqn.jl:39)"); return 1; }
   if (n < 0 || (n > 0 && (!obs || !q))) { set_error("crl_dqn_q_values: bad arguments"); return 1; }
   if (n == 0) return 0;
-  const size_t N = (size_t)n, need = N * (QD + QA) * 8;
-  if (dqn_stage(h, need)) return 1;
-  double* so = static_cast<double*>(h->stage);
-  double* sq = so + N * QD;
-  CRL_HIP_CHECK(hipMemcpyAsync(so, obs, N * QD * 8, hipMemcpyHostToDevice, h->stream));
-  if (h->duel || h->c51) launch_obs_kernel(h, so, n, sq, nullptr, nullptr, nullptr);
-  else hipLaunchKernelGGL(dqn_q_kernel, dim3(n), dim3(DQN_OBS_BLOCK), 0, h->stream, h->greedy_image(), (const double*)so, n, sq);
-  CRL_HIP_CHECK(hipGetLastError());
-  CRL_HIP_CHECK(hipMemcpyAsync(q, sq, N * QA * 8, hipMemcpyDeviceToHost, h->stream));
-  CRL_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return 0;
+  return dqn_obs_call(h, obs, n, {{OBS_Q, QA, q}});
 }
 
 // Held-out evaluation: argument checks, scratch, ONE launch (dqn_eval_kernel), the per-episode arrays back to the host, the report in Float64
@@ -1714,7 +1652,7 @@ int32_t crl_dqn_evaluate(crl_dqn* h, const crl_eval_config* cfg, crl_value_eval_
   if (value_eval_check("crl_dqn_evaluate", cfg, report, h->params_set, "crl_dqn_write_params or crl_dqn_init_params first (dqn.jl:39)",
                        h->cfg.max_steps, /*has_sampler=*/false, trace_action)) return 1;
   ValueEvalArgs ev;
-  if (value_eval_scratch(h->eval, cfg, ev)) return 1;
+  if (value_eval_scratch(h->eval, h->stream, cfg, ev)) return 1;
   // every slot of the arrays and of the trace is written: each env plays its quota and then fills the rest of its trace column
   const dim3 grid((unsigned)((ev.n + DQN_EVAL_WAVES - 1) / DQN_EVAL_WAVES)), block(64 * DQN_EVAL_WAVES);
   if (h->duel) hipLaunchKernelGGL(h->qr ? dqn_duel_eval_kernel<true> : dqn_duel_eval_kernel<false>, dim3((unsigned)((ev.n + DUEL_EVAL_WAVES - 1) / DUEL_EVAL_WAVES)), dim3(64 * DUEL_EVAL_WAVES),

@@ -8,20 +8,9 @@
 
 #include "../../include/cleanrl_hip.h"
 #include "optim.hpp"
+#include "stage.hpp"
 
 namespace crl {
-
-void set_error(const std::string& msg);
-
-#define CRL_HIP_CHECK(expr)                                                                                   \
-  do {                                                                                                        \
-    hipError_t _e = (expr);                                                                                   \
-    if (_e != hipSuccess) {                                                                                   \
-      crl::set_error(std::string(#expr) + " failed: " + hipGetErrorString(_e) + " (" + __FILE__ + ":" +      \
-                     std::to_string(__LINE__) + ")");                                                         \
-      return 1;                                                                                               \
-    }                                                                                                         \
-  } while (0)
 
 // Device-side mirror of the hyper-parameters kernels need
 struct DevCfg {
@@ -171,10 +160,10 @@ struct crl_ppo {
   int window_count = 0;        // iterations run speculatively since the snapshot
   int window_len = 8;          // option guard_window
   // staging for host-pointer calls
-  void* stage = nullptr; size_t stage_bytes = 0;
+  crl::Scratch stage;                                  // at least STAGE_FLOOR bytes once used
   void* pinned = nullptr; size_t pinned_bytes = 0;
-  void* eval_ws = nullptr; size_t eval_ws_bytes = 0;   // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
-  void* diag_ws = nullptr; size_t diag_ws_bytes = 0;   // crl_ppo_diagnose: per-block records | new_logprob | new_value (allocated on first use)
+  crl::Scratch eval_ws;                                // crl_ppo_evaluate: returns | lengths | action trace (allocated on first use)
+  crl::Scratch diag_ws;                                // crl_ppo_diagnose: per-block records | new_logprob | new_value (allocated on first use)
   hipEvent_t diag_ev[2] = {nullptr, nullptr}; int64_t diag_last_ns = 0;   // events around its launch (read-only option diag_last_ns)
   // device-resident external envs (extenv.hip): the peer_stream fences (recorded on the caller's stream before a launch, on the handle's after it), the
   // step kernel's blocks per CU (asked once), the sticky out-of-range-action word of crl_env_step_device (reported by crl_sync)
@@ -220,8 +209,7 @@ inline uint64_t shuffle_seed(const crl_ppo* h) {
 }
 void select_slot(crl_ppo* h, int slot);
 int ensure_records(crl_ppo* h);
-int ensure_scratch(crl_ppo* h, void** buf, size_t* have, size_t want);   // a device scratch buffer of the handle, grown on first use (the stream is drained before the old one is freed)
-int ensure_stage(crl_ppo* h, size_t bytes);
+constexpr size_t STAGE_FLOOR = (size_t)1 << 20;   // a crl_ppo handle's stage is never smaller: the usual calls (a few thousand envs) then never regrow it
 int reset_dw_scale(crl_ppo* h);
 // option "gemm": 2 (default) = fp16x2 products in the update kernel and the rollout's critic, bf16x3 for the rollout's actor
 // (mlp_x2.hpp); 1 = bf16x3 everywhere (mlp_x3.hpp) — the fallback flavour, also taken per block when a hidden-layer weight

@@ -25,8 +25,6 @@ __device__ __forceinline__ void value_eval_trace_tail(const ValueEvalArgs& ev, i
   for (int64_t r = row + lane; r < ev.trace_steps; r += 64) ev.trace[(size_t)r * ev.n + env] = -1;
 }
 
-struct ValueEvalScratch { void* p = nullptr; size_t bytes = 0; };
-
 // argument checks of crl_*_evaluate after the handle guard; `who` names the call in every message
 inline int value_eval_check(const char* who, const crl_eval_config* cfg, const crl_value_eval_report* report, bool params_set, const char* how_to_set,
                             int max_steps, bool has_sampler, const int32_t* trace_action) {
@@ -52,18 +50,15 @@ inline int value_eval_check(const char* who, const crl_eval_config* cfg, const c
 }
 
 // device scratch, grown on demand and kept on the handle: three double arrays, then the lengths, then the trace
-inline int value_eval_scratch(ValueEvalScratch& s, const crl_eval_config* cfg, ValueEvalArgs& ev) {
+inline int value_eval_scratch(Scratch& ws, hipStream_t st, const crl_eval_config* cfg, ValueEvalArgs& ev) {
   const size_t ne = (size_t)cfg->num_envs * (size_t)cfg->episodes_per_env, nt = (size_t)cfg->trace_steps * (size_t)cfg->num_envs;
-  const size_t need = 3 * ne * 8 + (ne + nt) * 4;
-  if (s.bytes < need) {
-    if (s.p) CRL_HIP_CHECK(hipFree(s.p));
-    s.p = nullptr; s.bytes = 0;
-    CRL_HIP_CHECK(hipMalloc(&s.p, need));
-    s.bytes = need;
-  }
+  Staged s(st);
+  const auto s_f64 = s.add<double>(3 * ne);   // one section: value_eval_finish fetches the three arrays with one copy
+  const auto s_len = s.add<int32_t>(ne), s_trace = s.add<int32_t>(nt);
+  if (s.reserve(ws)) return 1;
   ev.n = cfg->num_envs; ev.episodes = cfg->episodes_per_env; ev.trace_steps = cfg->trace_steps; ev.mode = cfg->mode; ev.seed = cfg->seed;
-  ev.ret = static_cast<double*>(s.p); ev.disc_ret = ev.ret + ne; ev.v0 = ev.disc_ret + ne;
-  ev.len = reinterpret_cast<int32_t*>(ev.v0 + ne); ev.trace = ev.len + ne;
+  ev.ret = s.at(s_f64); ev.disc_ret = ev.ret + ne; ev.v0 = ev.disc_ret + ne;
+  ev.len = s.at(s_len); ev.trace = s.at(s_trace);
   return 0;
 }
 
