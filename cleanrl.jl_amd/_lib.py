@@ -113,6 +113,7 @@ EXPORTS = [
     "crl_ppo_stream", "crl_rollout_act_device", "crl_rollout_record_device", "crl_env_step_device", "crl_ppo_update",
     "crl_ppo_create_gaussian", "crl_make_actor_critic_gaussian", "crl_policy_act_gaussian", "crl_logprob_actions_gaussian",
     "crl_rollout_store_gaussian", "crl_env_step_gaussian", "crl_ppo_rollout_route",
+    "crl_rollout_act_device_gaussian", "crl_rollout_record_device_gaussian", "crl_env_step_device_gaussian",
 ]
 ROLLOUT_ROUTES = ("headline", "stepwise", "persist", "pc", "rs_actor")   # enum crl_rollout_route, in order
 
@@ -428,6 +429,9 @@ def load():
     L.crl_rollout_act_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     L.crl_rollout_record_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     L.crl_env_step_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.crl_rollout_act_device_gaussian.argtypes = L.crl_rollout_act_device.argtypes
+    L.crl_rollout_record_device_gaussian.argtypes = L.crl_rollout_record_device.argtypes
+    L.crl_env_step_device_gaussian.argtypes = L.crl_env_step_device.argtypes
     L.crl_ppo_update.argtypes = [vp, C.POINTER(CrlStats)]
     L.crl_product_probe.argtypes = [C.c_int32, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp]
     for name in EXPORTS:
@@ -754,6 +758,27 @@ class Handle:
         a, r, d = devptr(action, "env_step_device: action"), devptr(reward, "env_step_device: reward"), devptr(done, "env_step_device: done")
         o, ps = devptr(next_obs, "env_step_device: next_obs", optional=True), devptr(peer_stream, "peer_stream", optional=True)
         check(load().crl_env_step_device(self._h, a, int(gstep), o, r, d, ps))
+
+    # the float-action twins on a Gaussian handle: `action` holds (act_dim, num_envs) floats — a contiguous (num_envs, act_dim) torch tensor
+    def act_device_gaussian(self, step, obs, done, action, peer_stream=None):
+        """crl_rollout_act_device_gaussian: act_device with a = mu + sigma xi on the on-device rollout's xi stream, one launch; the unclipped float
+        actions land in `action` and in slot `step` of CRL_F_ACTION_F."""
+        o, d, a = devptr(obs, "act_device_gaussian: obs"), devptr(done, "act_device_gaussian: done"), devptr(action, "act_device_gaussian: action")
+        ps = devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_rollout_act_device_gaussian(self._h, int(step), o, d, a, ps))
+
+    def record_device_gaussian(self, step, reward, next_obs, next_done, peer_stream=None):
+        """crl_rollout_record_device_gaussian: record_device on a Gaussian handle."""
+        r, o = devptr(reward, "record_device_gaussian: reward"), devptr(next_obs, "record_device_gaussian: next_obs")
+        d, ps = devptr(next_done, "record_device_gaussian: next_done"), devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_rollout_record_device_gaussian(self._h, int(step), r, o, d, ps))
+
+    def env_step_device_gaussian(self, action, gstep, next_obs, reward, done, peer_stream=None):
+        """crl_env_step_device_gaussian: crl_env_step_gaussian on device pointers, the on-device Pendulum (next_obs may be None: CRL_F_CUR_OBS holds it)."""
+        a, r = devptr(action, "env_step_device_gaussian: action"), devptr(reward, "env_step_device_gaussian: reward")
+        d = devptr(done, "env_step_device_gaussian: done")
+        o, ps = devptr(next_obs, "env_step_device_gaussian: next_obs", optional=True), devptr(peer_stream, "peer_stream", optional=True)
+        check(load().crl_env_step_device_gaussian(self._h, a, int(gstep), o, r, d, ps))
 
     def update(self, want_stats=True):
         """crl_ppo_update: ppo.jl:168-253 on the resident buffer (the update half of iterate)."""

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <utility>
 #include <vector>
@@ -1293,43 +1294,99 @@ int32_t crl_ppo_stream(crl_ppo* h, void** stream) {
   return 0;
 }
 
-int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, int32_t* action_d, void* peer_stream) {
-  CRL_GUARD_SETTLED(h);
-  if (need_discrete(h, "crl_rollout_act_device", nullptr)) return 1;
-  CRL_NEED_PARAMS(h, "crl_rollout_act_device");
-  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_act_device: step out of range"); return 1; }
-  if (!obs_d || !done_d || !action_d) { set_error("crl_rollout_act_device: null argument"); return 1; }
+}  // extern "C": the shared bodies below take their launch as a template argument
+// The bodies a softmax-head call and its Gaussian twin share (the head check stays in the exported functions, as for the staged calls above).
+static int null_arg(const char* who, std::initializer_list<std::pair<const char*, const void*>> args) {
+  for (const auto& a : args)
+    if (!a.second) { set_error(std::string(who) + ": null argument (" + a.first + ")"); return 1; }
+  return 0;
+}
+static int step_in_range(const crl_ppo* h, const char* who, int32_t step) {
+  if (step >= 0 && step < h->dc.k) return 0;
+  set_error(std::string(who) + ": step out of range (step = " + std::to_string(step) + ", num_steps = " + std::to_string(h->dc.k) + ")");
+  return 1;
+}
+template <class Launch>
+static int rollout_act_device(crl_ppo* h, const char* who, int32_t step, const void* obs_d, const void* done_d, const void* action_d, void* peer_stream,
+                              Launch&& launch) {
+  if (step_in_range(h, who, step)) return 1;
+  if (null_arg(who, {{"obs_d", obs_d}, {"done_d", done_d}, {"action_d", action_d}})) return 1;
   if (peer_enter(h, peer_stream)) return 1;
   if (step == 0) {   // a new rollout: its episode statistics and ring start empty, as in launch_rollout
     CRL_HIP_CHECK(hipMemsetAsync(h->ep_stats, 0, 4 * sizeof(double), h->stream));
     if (h->ep_ring_cap > 0) CRL_HIP_CHECK(hipMemsetAsync(h->ep_ring_count, 0, sizeof(uint32_t), h->stream));
   }
-  if (launch_ext_act(h, step, obs_d, done_d, action_d)) return 1;
+  if (launch()) return 1;
   h->recs_dirty = true;
   return peer_leave(h, peer_stream);
+}
+static int rollout_record_device(crl_ppo* h, const char* who, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d,
+                                 void* peer_stream) {
+  if (step_in_range(h, who, step)) return 1;
+  if (null_arg(who, {{"reward_d", reward_d}, {"next_obs_d", next_obs_d}, {"next_done_d", next_done_d}})) return 1;
+  if (peer_enter(h, peer_stream)) return 1;
+  if (launch_ext_record(h, step, reward_d, next_obs_d, next_done_d)) return 1;   // the kernel never looks at the head
+  return peer_leave(h, peer_stream);
+}
+// the env has been stepped into CRL_F_CUR_OBS by `launch`; the caller's copy of it, if asked for
+template <class Launch>
+static int env_step_device(crl_ppo* h, float* next_obs_d, void* peer_stream, Launch&& launch) {
+  if (ensure_env(h)) return 1;
+  if (peer_enter(h, peer_stream)) return 1;
+  if (launch()) return 1;
+  if (next_obs_d) CRL_HIP_CHECK(hipMemcpyAsync(next_obs_d, h->cur_obs, (size_t)h->dc.nt * h->dc.D * 4, hipMemcpyDeviceToDevice, h->stream));
+  return peer_leave(h, peer_stream);
+}
+
+extern "C" {
+
+int32_t crl_rollout_act_device(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, int32_t* action_d, void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  if (need_discrete(h, "crl_rollout_act_device", "crl_rollout_act_device_gaussian")) return 1;
+  CRL_NEED_PARAMS(h, "crl_rollout_act_device");
+  return rollout_act_device(h, "crl_rollout_act_device", step, obs_d, done_d, action_d, peer_stream, [&] { return launch_ext_act(h, step, obs_d, done_d, action_d); });
+}
+
+int32_t crl_rollout_act_device_gaussian(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, float* action_d, void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_rollout_act_device_gaussian")) return 1;
+  CRL_NEED_PARAMS(h, "crl_rollout_act_device_gaussian");
+  return rollout_act_device(h, "crl_rollout_act_device_gaussian", step, obs_d, done_d, action_d, peer_stream,
+                            [&] { return launch_ext_act_gauss(h, step, obs_d, done_d, action_d); });
 }
 
 int32_t crl_rollout_record_device(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
-  if (need_discrete(h, "crl_rollout_record_device", nullptr)) return 1;
-  if (step < 0 || step >= h->dc.k) { set_error("crl_rollout_record_device: step out of range"); return 1; }
-  if (!reward_d || !next_obs_d || !next_done_d) { set_error("crl_rollout_record_device: null argument"); return 1; }
-  if (peer_enter(h, peer_stream)) return 1;
-  if (launch_ext_record(h, step, reward_d, next_obs_d, next_done_d)) return 1;
-  return peer_leave(h, peer_stream);
+  if (need_discrete(h, "crl_rollout_record_device", "crl_rollout_record_device_gaussian")) return 1;
+  return rollout_record_device(h, "crl_rollout_record_device", step, reward_d, next_obs_d, next_done_d, peer_stream);
+}
+
+int32_t crl_rollout_record_device_gaussian(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d,
+                                           void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_rollout_record_device_gaussian")) return 1;
+  return rollout_record_device(h, "crl_rollout_record_device_gaussian", step, reward_d, next_obs_d, next_done_d, peer_stream);
 }
 
 int32_t crl_env_step_device(crl_ppo* h, const int32_t* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d, void* peer_stream) {
   CRL_GUARD_SETTLED(h);
-  if (need_discrete(h, "crl_env_step_device", nullptr)) return 1;
+  if (need_discrete(h, "crl_env_step_device", "crl_env_step_device_gaussian")) return 1;
   if (need_stateful_env(h, "crl_env_step_device")) return 1;
   if (!action_d || !reward_d || !done_d) { set_error("crl_env_step_device: null action, reward or done"); return 1; }
-  if (ensure_env(h)) return 1;
-  if (peer_enter(h, peer_stream)) return 1;
-  if (launch_env_step(h, action_d, gstep, reward_d, done_d, h->ext_bad)) return 1;
-  h->ext_bad_armed = true;
-  if (next_obs_d) CRL_HIP_CHECK(hipMemcpyAsync(next_obs_d, h->cur_obs, (size_t)h->dc.nt * h->dc.D * 4, hipMemcpyDeviceToDevice, h->stream));
-  return peer_leave(h, peer_stream);
+  return env_step_device(h, next_obs_d, peer_stream, [&] {
+    if (launch_env_step(h, action_d, gstep, reward_d, done_d, h->ext_bad)) return 1;
+    h->ext_bad_armed = true;
+    return 0;
+  });
+}
+
+int32_t crl_env_step_device_gaussian(crl_ppo* h, const float* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d,
+                                     void* peer_stream) {
+  CRL_GUARD_SETTLED(h);
+  if (need_gauss(h, "crl_env_step_device_gaussian")) return 1;
+  if (!env_continuous(h->cfg.env_kind)) { set_error("crl_env_step_device_gaussian needs the on-device continuous env (CRL_ENV_PENDULUM)"); return 1; }
+  if (null_arg("crl_env_step_device_gaussian", {{"action_d", action_d}, {"reward_d", reward_d}, {"done_d", done_d}})) return 1;
+  return env_step_device(h, next_obs_d, peer_stream, [&] { return gauss_env_step(h, action_d, gstep, reward_d, done_d); });
 }
 
 int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats) {

@@ -10,33 +10,88 @@
 //                    rollout kernel takes for that env and step —, sample_rt, the logprob of the drawn action; action to the buffer and to action_d, logprob
 //             critic the value; terminal <- done_d
 //   stores    plain vector stores to the (·, num_envs, num_steps) layout, env fastest; a partial last tile reads and writes nothing past num_envs.
+// ext_act_kernel<H, ExtHeadGauss> (crl_rollout_act_device_gaussian) is the same frame with the head rows read as (μ, s) of ppo_gauss.hpp: the actor block
+// draws the tile's ξ on all its threads in front of the first barrier (ext_gauss_draw) and, behind the last one, one thread per (env, component) forms
+// a = μ + σ·ξ and its logπ term, which wave 0 adds per env in index order (ext_gauss_tail). The critic block is the softmax handle's.
 //
 // ext_record_kernel: ppo.jl:132,137,143-165 for one step, one thread per env: reward to the slot, CRL_F_CUR_OBS / CRL_F_NEXT_DONE <- next_obs_d / next_done_d
 // (what the fixed-mode bootstrap reads), ep_length += 1, ep_return += reward (Float32, step order); where next_done: the four ep_stats doubles (wave sums, one
 // atomic set per wave like the rollout kernels), a record {return, length, env_id_offset + e, step} to the episode ring through the same atomic counter, and
 // zeroed accumulators. return_max keeps the order-preserving key of the signed env kinds (stat_max_key; api.cpp maps it back).
 #include "fwd_rs_x3.hpp"
+#include "ppo_gauss.hpp"
 #include "stats.hpp"
 
 namespace crl {
 
 struct ExtActArgs {
   const float* params; int64_t Pa;   // actor | critic, each W1(H,D) b1(H) W2(H,H) b2(H) W3(n_out,H) b3(n_out), (out,in) column-major
-  const float* obs_in; const uint8_t* done_in; int32_t* action_out;   // the caller's: (D, N), [N], [N]
-  float* obs; int32_t* action; float* logprob; float* value; uint8_t* terminal;   // slot `step` of the resident buffer: (D, N), [N] each
-  int D, A, N;
+  const float* obs_in; const uint8_t* done_in;   // the caller's: (D, N), [N]
+  float* obs; float* logprob; float* value; uint8_t* terminal;   // slot `step` of the resident buffer: (D, N), [N] each
+  int D, A, N;                       // A: the actor's head rows (n_act, or 2·act_dim on a Gaussian handle)
   int w1_lds;                        // 1 = W1 fits LDS next to everything else, 0 = layer 1 reads it from the parameters (hidden 256 with a wide observation)
   uint64_t seed, gstep; uint32_t gid0;
 };
+// What the actor's head rows mean is a compile-time tag, as for wide_step_env: where the actions go (slot `step` of the action plane and the caller's buffer)
+// and, for the Gaussian head, the distribution's constants. OWN: the LDS floats of the tail (the `own` region of rs_role_lds).
+struct ExtHeadSoftmax { int32_t* action; int32_t* action_out; static constexpr int OWN = 0; };                     // [N] each
+struct ExtHeadGauss { GaussDist g; float* action; float* action_out; static constexpr int OWN = 2 * GAUSS_AMAX * 32; };   // (act_dim, N) each; ξ [act_dim][32] | logπ terms [act_dim][32]
 
+// The Gaussian head of a tile, on the ACTOR block. Pair p = act_dim·m + i is component i of tile row m, so the tile's actions are the 32·act_dim
+// consecutive floats behind act_dim·e0 of either action array; pairs go to threads p, p + NT (two per thread only at hidden 64 with act_dim > 4), the same
+// thread in the draw and in the tail.
+// ext_gauss_draw: ξ of the thread's pairs into xil — the on-device rollout's draw, Philox block (seed, env id, gstep, 0x20 + i). The Float64 Box–Muller chain
+// needs nothing the forward produces: it is issued behind the tile's observation loads, in front of the first barrier, on every wave of the block.
 template <int H>
-__global__ void __launch_bounds__(2 * H) ext_act_kernel(ExtActArgs a) {
+__device__ __forceinline__ void ext_gauss_draw(const ExtActArgs& a, int ad, int e0, int ne, float* xil, int tid) {
+  const int rcp = (65536 + ad - 1) / ad;                         // uniform: a scalar division, once per tile
+  int p0 = tid;
+  asm volatile("" : "+v"(p0));                                  // formed per tile: hoisted pair indices would cost W2 its registers at 256
+  for (int p = p0; p < 32 * ad; p += RsGeom<H>::NT) {
+    const int m = (p * rcp) >> 16, i = p - m * ad;           // p / ad, exact for p < 256, ad <= 8
+    if (m < ne) xil[i * 32 + m] = gauss_xi_of(gauss_xi_block(a.seed, a.gid0 + (uint32_t)(e0 + m), a.gstep, i));
+  }
+}
+// ext_gauss_tail, behind the head-partials barrier: the pair's two head rows, a = μ + σ·ξ to both action arrays, its logπ term to lpl; then lanes 0-31 of
+// wave 0 add each env's terms in index order — the order the rollout kernels pin — and store the logprob. With at most 64 pairs everything happens in wave
+// 0, whose LDS accesses are in order; beyond that a barrier (uniform over the block: ad is) stands between the terms and their sum.
+template <int H>
+__device__ __forceinline__ void ext_gauss_tail(const ExtActArgs& a, const ExtHeadGauss& hd, const RsRoleLds& l, int e0, int ne, int tid) {
+  const int ad = hd.g.ad;
+  const float* xil = l.own;
+  float* lpl = l.own + GAUSS_AMAX * 32;
+  const int rcp = (65536 + ad - 1) / ad;                         // uniform: a scalar division, once per tile
+  int p0 = tid;
+  asm volatile("" : "+v"(p0));                                  // formed per tile: hoisted pair indices would cost W2 its registers at 256
+  for (int p = p0; p < 32 * ad; p += RsGeom<H>::NT) {
+    const int m = (p * rcp) >> 16, i = p - m * ad;           // p / ad, exact for p < 256, ad <= 8
+    if (m < ne) {
+      const float mu = rs_logit<H>(l.zp, l.b3l, i, m), s = rs_logit<H>(l.zp, l.b3l, ad + i, m), xi = xil[i * 32 + m];
+      float th;
+      const float ls = gauss_log_std(hd.g, s, th);
+      const float act = gauss_action(mu, expf(ls), xi);
+      const size_t o = (size_t)ad * e0 + p;
+      hd.action[o] = act; hd.action_out[o] = act;
+      lpl[i * 32 + m] = gauss_lp_term(xi, ls);
+    }
+  }
+  if (32 * ad > 64) __syncthreads();
+  if (tid < ne) {
+    float lpa = 0.0f;
+    for (int i = 0; i < ad; ++i) lpa += lpl[i * 32 + tid];
+    a.logprob[e0 + tid] = lpa;
+  }
+}
+
+template <int H, class Head>
+__global__ void __launch_bounds__(2 * H) ext_act_kernel(ExtActArgs a, Head hd) {
   constexpr int NT = RsGeom<H>::NT, KR = RsGeom<H>::KR;
+  constexpr bool GAUSS = std::is_same<Head, ExtHeadGauss>::value;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int D = a.D, XS = rs_xs(D), N = a.N;
   const int role = blockIdx.x & 1, rb = blockIdx.x >> 1, nrb = gridDim.x >> 1;   // 0 = actor, 1 = critic
   const int A = role ? 1 : a.A;
-  const RsRoleLds l = rs_role_lds<H>(sm, 0, D, a.A);
+  const RsRoleLds l = rs_role_lds<H>(sm, Head::OWN, D, a.A);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const RsNet net = rs_net<H>(a.params + (role ? a.Pa : 0), D, A);
 
@@ -58,6 +113,7 @@ __global__ void __launch_bounds__(2 * H) ext_act_kernel(ExtActArgs a) {
       }
       l.xt[m * XS + k] = x;
     }
+    if constexpr (GAUSS) if (role == 0) ext_gauss_draw<H>(a, hd.g.ad, e0, ne, l.own, tid);
     __syncthreads();
     rs_layer1_stream<H>(l, net.W1, a.w1_lds, D, tid);
     __syncthreads();
@@ -65,21 +121,25 @@ __global__ void __launch_bounds__(2 * H) ext_act_kernel(ExtActArgs a) {
     __syncthreads();                                             // every wave has read its h1 fragments: the region now takes the head partials
     rs_head_partials<H>(acc, l.w3c, A, l.zp, w, lane);
     __syncthreads();
-    if (mine) {                                                  // one lane per env; the next tile's first barrier stands between these reads of zp and layer 1's writes of h1
+    // the next tile's first barrier stands between these reads of zp and layer 1's writes of h1
+    if constexpr (GAUSS) if (role == 0) { ext_gauss_tail<H>(a, hd, l, e0, ne, tid); continue; }
+    if (mine) {                                                  // one lane per env
       const int e = e0 + lane;
       float z[AMAX];
       rs_logits<H>(l.zp, l.b3l, A, lane, z);
       if (role == 0) {                                           // ppo.jl:21-32 get_action
-        float p[AMAX], lp[AMAX];
+        if constexpr (!GAUSS) {
+          float p[AMAX], lp[AMAX];
 #pragma unroll
-        for (int aa = 0; aa < AMAX; ++aa) { p[aa] = 0.0f; lp[aa] = 0.0f; }
-        softmax_rt(z, A, p, lp);
-        const double u = u53(philox_env(a.seed, a.gid0 + (uint32_t)e, a.gstep, 0));
-        const int act = sample_rt(p, A, u);
-        float lpa = lp[0];
+          for (int aa = 0; aa < AMAX; ++aa) { p[aa] = 0.0f; lp[aa] = 0.0f; }
+          softmax_rt(z, A, p, lp);
+          const double u = u53(philox_env(a.seed, a.gid0 + (uint32_t)e, a.gstep, 0));
+          const int act = sample_rt(p, A, u);
+          float lpa = lp[0];
 #pragma unroll
-        for (int aa = 1; aa < AMAX; ++aa) lpa = (act == aa) ? lp[aa] : lpa;
-        a.action[e] = act; a.action_out[e] = act; a.logprob[e] = lpa;
+          for (int aa = 1; aa < AMAX; ++aa) lpa = (act == aa) ? lp[aa] : lpa;
+          hd.action[e] = act; hd.action_out[e] = act; a.logprob[e] = lpa;
+        }
       } else {
         a.value[e] = z[0];
         a.terminal[e] = a.done_in[e];
@@ -118,26 +178,38 @@ __global__ void __launch_bounds__(256) ext_record_kernel(ExtRecArgs a) {
   episode_stats_flush(a.ep_stats, st_n, st_ret, st_len, st_max, true);   // lanes past num_envs bring the neutral elements
 }
 
-// The launch of crl_rollout_act_device on the handle's stream.
-int launch_ext_act(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, int32_t* action_d) {
+// The launch of crl_rollout_act_device / crl_rollout_act_device_gaussian on the handle's stream; hd arrives with the caller's action_out.
+template <class Head>
+static int launch_ext_act_head(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, Head hd, size_t act_w, const char* err_shape,
+                               const char* err_lds) {
   const int H = h->cfg.hidden, D = h->dc.D, A = h->dc.A, N = h->dc.nt;
   bool w1_lds; size_t lds;
-  if (rs_role_shape(h, 0, "crl_rollout_act_device: no kernel for this shape (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256)",
-                    "crl_rollout_act_device: this shape needs more LDS than a CU has", &w1_lds, &lds)) return 1;
-  // the shape is fixed for the life of the handle: asked once, not per step
-  if (h->ext_per_cu == 0 && rs_dispatch_h(H, [&](auto hc) { return rs_role_per_cu(ext_act_kernel<decltype(hc)::value>, H, lds, &h->ext_per_cu); })) return 1;
+  if (rs_role_shape(h, Head::OWN, err_shape, err_lds, &w1_lds, &lds)) return 1;
+  // the shape and the head are fixed for the life of the handle: asked once, not per step
+  if (h->ext_per_cu == 0 && rs_dispatch_h(H, [&](auto hc) { return rs_role_per_cu(ext_act_kernel<decltype(hc)::value, Head>, H, lds, &h->ext_per_cu); })) return 1;
   const int nrb = rs_role_pairs(h, h->ext_per_cu, N);
   const size_t off = (size_t)N * (size_t)step;
   ExtActArgs a;
   a.params = h->params; a.Pa = h->Pa;
-  a.obs_in = obs_d; a.done_in = done_d; a.action_out = action_d;
-  a.obs = h->obs + off * (size_t)D; a.action = h->action + off; a.logprob = h->logprob + off; a.value = h->value + off; a.terminal = h->terminal + off;
+  a.obs_in = obs_d; a.done_in = done_d;
+  a.obs = h->obs + off * (size_t)D; a.logprob = h->logprob + off; a.value = h->value + off; a.terminal = h->terminal + off;
+  hd.action += off * act_w;
   a.D = D; a.A = A; a.N = N; a.w1_lds = w1_lds ? 1 : 0;
   a.seed = h->dc.seed; a.gstep = (uint64_t)h->iteration * (uint64_t)h->dc.k + (uint64_t)step; a.gid0 = h->dc.env_id_offset;
   const dim3 grid(2 * nrb), block(2 * H);
-  rs_dispatch_h(H, [&](auto hc) { hipLaunchKernelGGL(ext_act_kernel<decltype(hc)::value>, grid, block, lds, h->stream, a); return 0; });
+  rs_dispatch_h(H, [&](auto hc) { hipLaunchKernelGGL((ext_act_kernel<decltype(hc)::value, Head>), grid, block, lds, h->stream, a, hd); return 0; });
   CRL_HIP_CHECK(hipGetLastError());
   return 0;
+}
+int launch_ext_act(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, int32_t* action_d) {
+  return launch_ext_act_head(h, step, obs_d, done_d, ExtHeadSoftmax{h->action, action_d}, 1,
+                             "crl_rollout_act_device: no kernel for this shape (obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256)",
+                             "crl_rollout_act_device: this shape needs more LDS than a CU has");
+}
+int launch_ext_act_gauss(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, float* action_d) {
+  return launch_ext_act_head(h, step, obs_d, done_d, ExtHeadGauss{gauss_dist(h), h->action_f, action_d}, (size_t)h->act_dim,
+                             "crl_rollout_act_device_gaussian: no kernel for this shape (obs_dim <= 64, act_dim <= 8, hidden 64 / 128 / 256)",
+                             "crl_rollout_act_device_gaussian: this shape needs more LDS than a CU has");
 }
 
 int launch_ext_record(crl_ppo* h, int step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d) {

@@ -146,6 +146,14 @@ __device__ __forceinline__ void rs_logits(const float* zp, const float* b3l, int
   }
 }
 
+// head output `row` of tile row m alone, the same sum: for a tail that gives every (row, output) pair a thread of its own (ext_act_kernel's Gaussian head)
+template <int H>
+__device__ __forceinline__ float rs_logit(const float* zp, const float* b3l, int row, int m) {
+  float v = b3l[row];
+  for (int ww = 0; ww < RsGeom<H>::NW; ++ww) v += zp[(ww * AMAX + row) * 32 + m];
+  return v;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Role-pair kernels (diag_kernel, ext_act_kernel): obs_dim <= 64, n_act <= 16, hidden 64 / 128 / 256.
 // LDS (floats): the prefix | `own` floats of the kernel's own | b1 | b2 (C-fragment order) | b3 | W3 (C-fragment order) [n_out][H] | tile rows [32][D | 1] |

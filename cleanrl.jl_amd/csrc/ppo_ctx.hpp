@@ -271,8 +271,9 @@ int launch_eval(crl_ppo* h, const crl_eval_config* c, float* returns_d, int32_t*
 int eval_episode_cap(int kind);   // the longest episode of an env kind, in steps
 // diag.hip — crl_ppo_diagnose's one launch and the report
 int launch_diag(crl_ppo* h, crl_ppo_diag* out, float* new_logprob, float* new_value);
-// extenv.hip — the per-step launches of crl_rollout_act_device / crl_rollout_record_device
+// extenv.hip — the per-step launches of crl_rollout_act_device(_gaussian) / crl_rollout_record_device(_gaussian)
 int launch_ext_act(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, int32_t* action_d);
+int launch_ext_act_gauss(crl_ppo* h, int step, const float* obs_d, const uint8_t* done_d, float* action_d);   // action_d (act_dim, num_envs)
 int launch_ext_record(crl_ppo* h, int step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d);
 // wide.hip — layer-wise path for other network shapes
 bool wide_shape_ok(const crl_ppo_config* cfg, std::string* why);

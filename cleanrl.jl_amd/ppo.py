@@ -321,14 +321,17 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
 #   stream (optional)                 the hipStream_t (int) the env enqueues its work on; passed as peer_stream, so neither side waits on the host
 #   action (optional)                 pointer-like [num_envs] Int32 the env wants the actions written into (a torch env hands over its own tensor and
 #                                     gets it back in step); without it the loop allocates a DeviceBuffer
+# A continuous-action device env declares `act_dim` INSTEAD of `n_act` (and `on_device = True`, which tells ppo_continuous it is not a host env): it is
+# driven by a Gaussian agent through the `_gaussian` twins of the three calls, and `action` is (act_dim, num_envs) Float32 — a contiguous
+# (num_envs, act_dim) torch tensor — holding the unclipped actions.
 # where every pointer-like is an int device address or an object with data_ptr() (a torch tensor, a DeviceBuffer) into buffers the ENV owns, on the
 # agent's device. Nothing in the loop touches host memory; the one host wait per update is crl_ppo_update's (4 / 2 / 64 path only).
 _PROTOCOL = ("num_envs", "obs_dim", "n_act", "reset", "step")
 
 
-def check_device_env(env):
-    """TypeError naming the first protocol attribute `env` lacks (nothing on the device is touched)."""
-    for name in _PROTOCOL:
+def check_device_env(env, gaussian=False):
+    """TypeError naming the first protocol attribute `env` lacks (nothing on the device is touched); gaussian: `act_dim` takes the place of `n_act`."""
+    for name in (tuple("act_dim" if n == "n_act" else n for n in _PROTOCOL) if gaussian else _PROTOCOL):
         if not hasattr(env, name):
             raise TypeError(f"env={type(env).__name__} is neither an env name nor a device env: it has no `{name}` "
                             f"(the device-env protocol needs {', '.join(_PROTOCOL)} and optionally stream, action)")
@@ -339,17 +342,25 @@ def check_device_env(env):
 
 
 class LibraryEnv:
-    """One of the library's on-device envs ("cartpole", "mountaincar", "acrobot") behind the device-env protocol: a second handle's built-in env stepped
-    with crl_env_reset + crl_env_step_device into device buffers this object owns (hipMalloc through ctypes; torch is not needed). The reference
-    implementation of the protocol — and the env of its tests. stale_obs / env_id_offset as for an Agent: with the Agent's defaults the env is the one a
-    built-in-env Agent of the same seed trains on."""
+    """One of the library's on-device envs ("cartpole", "mountaincar", "acrobot", or the continuous "pendulum") behind the device-env protocol: a second
+    handle's built-in env stepped with crl_env_reset + crl_env_step_device (crl_env_step_device_gaussian for a continuous env: a Gaussian handle, float
+    actions) into device buffers this object owns (hipMalloc through ctypes; torch is not needed). The reference implementation of the protocol — and
+    the env of its tests. stale_obs / env_id_offset as for an Agent: with the Agent's defaults the env is the one a built-in-env Agent of the same seed
+    trains on. A continuous env declares act_dim and on_device instead of n_act."""
 
     def __init__(self, name, num_envs, seed=0x5EED, device=0, stale_obs=True, env_id_offset=0):
-        shape = env_shape(name)
-        self.name, self.num_envs, self.obs_dim, self.n_act = name, int(num_envs), shape["obs_dim"], shape["n_act"]
+        self.name, self.num_envs = name, int(num_envs)
+        self.continuous = _env_key(name) in ENVS_CONTINUOUS
+        if self.continuous:
+            kind, self.obs_dim, self.act_dim = ENVS_CONTINUOUS[_env_key(name)]
+            self.on_device = True
+            shape = dict(env_kind=kind, obs_dim=self.obs_dim, n_act=self.act_dim)
+        else:
+            shape = env_shape(name)
+            self.obs_dim, self.n_act = shape["obs_dim"], shape["n_act"]
         cfg = _crl_config(PPOConfig(num_envs=self.num_envs, num_steps=1, num_minibatches=1, total_timesteps=self.num_envs), seed=seed,
                           stale_obs=stale_obs, env_id_offset=env_id_offset, hidden=64, **shape)
-        self.handle = L.Handle(cfg, device)          # only its env is used: its parameters stay unset
+        self.handle = L.Handle(cfg, device, gaussian=True if self.continuous else None)   # only its env is used: its parameters stay unset
         self.stream = self.handle.stream
         n, d = self.num_envs, self.obs_dim
         self.obs, self.reward, self.done = L.DeviceBuffer(4 * n * d, device), L.DeviceBuffer(4 * n, device), L.DeviceBuffer(n, device)
@@ -364,7 +375,8 @@ class LibraryEnv:
         return self.obs, self.done
 
     def step(self, action):
-        self.handle.env_step_device(action, self.gstep, self.obs, self.reward, self.done)   # on the env handle's own stream
+        step = self.handle.env_step_device_gaussian if self.continuous else self.handle.env_step_device
+        step(action, self.gstep, self.obs, self.reward, self.done)                          # on the env handle's own stream
         self.gstep += 1
         return self.reward, self.obs, self.done
 
@@ -378,36 +390,43 @@ def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_rec
     """The `for update in 1:num_updates` loop of ppo.jl:117-253 with the env OUTSIDE the library but on the same GPU (the device-env protocol above):
     reset once; per step crl_rollout_act_device -> env.step -> crl_rollout_record_device; per update crl_ppo_update. Emits the records of `train`:
     "Episode Statistics" (one aggregate per rollout, or one per episode with episode_records=N), "Training Statistics", and "Policy Diagnostics" every
-    diag_every-th update. eval_every is refused: crl_ppo_evaluate has no external env to run."""
+    diag_every-th update. eval_every is refused: crl_ppo_evaluate has no external env to run. A Gaussian agent takes an env that declares act_dim: the
+    action buffer is (act_dim, num_envs) Float32, the calls are crl_rollout_act_device_gaussian / crl_rollout_record_device_gaussian, the records are
+    the same; diag_every is refused for it as well (crl_ppo_diagnose is not built for Gaussian handles)."""
     if eval_every:
         raise ValueError("train_external: eval_every is not available — crl_ppo_evaluate runs the library's own envs and has none for an external env")
+    gaussian = agent.action == "gaussian"
+    if gaussian and diag_every:
+        raise ValueError("train_external: diag_every is not available for a Gaussian agent — crl_ppo_diagnose is not built for Gaussian handles")
     if diag_every:
         if isinstance(diag_every, bool) or not isinstance(diag_every, (int, np.integer)) or diag_every < 0:
             raise ValueError(f"train_external: diag_every must be an integer >= 0, got {diag_every!r}")
-    check_device_env(env)
+    check_device_env(env, gaussian)
     cfg = agent.config
-    if (env.num_envs, env.obs_dim, env.n_act) != (cfg.num_envs, agent.crl_cfg.obs_dim, agent.crl_cfg.n_act):
-        raise ValueError(f"train_external: the env has (num_envs, obs_dim, n_act) = {(env.num_envs, env.obs_dim, env.n_act)}, the agent "
+    width = "act_dim" if gaussian else "n_act"            # an Agent's n_act is act_dim on a Gaussian one
+    if (env.num_envs, env.obs_dim, getattr(env, width)) != (cfg.num_envs, agent.crl_cfg.obs_dim, agent.crl_cfg.n_act):
+        raise ValueError(f"train_external: the env has (num_envs, obs_dim, {width}) = {(env.num_envs, env.obs_dim, getattr(env, width))}, the agent "
                          f"{(cfg.num_envs, agent.crl_cfg.obs_dim, agent.crl_cfg.n_act)}")
     batch_size = cfg.num_steps * cfg.num_envs
     if num_updates is None:
         num_updates = max(1, cfg.total_timesteps // batch_size)  # ppo.jl:91
     h = agent.handle
+    act_device, record_device = (h.act_device_gaussian, h.record_device_gaussian) if gaussian else (h.act_device, h.record_device)
     if episode_records:
         h.episode_ring_enable(int(episode_records))
     peer = getattr(env, "stream", None) or None
     action = getattr(env, "action", None)
     if action is None:
-        action = L.DeviceBuffer(4 * cfg.num_envs, agent.handle.device)
+        action = L.DeviceBuffer(4 * (env.act_dim if gaussian else 1) * cfg.num_envs, agent.handle.device)
     start_time = time.time()
     last_log_step = 0
     obs, done = env.reset()                                                        # ppo.jl:112-115
     for update in range(1, num_updates + 1):
         base = (update - 1) * batch_size
         for step in range(cfg.num_steps):                                          # ppo.jl:123-166
-            h.act_device(step, obs, done, action, peer_stream=peer)
+            act_device(step, obs, done, action, peer_stream=peer)
             reward, obs, done = env.step(action)
-            h.record_device(step, reward, obs, done, peer_stream=peer)
+            record_device(step, reward, obs, done, peer_stream=peer)
         # the episode records of this rollout are read before the next rollout's first step clears them; the reads are this loop's host waits
         ep = h.episode_stats()
         records = h.episode_records()[0] if episode_records else []
@@ -519,7 +538,9 @@ def ppo_continuous(config: PPOConfig = None, *, env="pendulum", gaussian=None, d
                    run_name="ppo-continuous", logger_kw=None, **shape):
     """Continuous-action PPO (CleanRL's ppo_continuous_action; ppo.jl samples a softmax only): `ppo` with the diagonal Gaussian policy of
     crl_ppo_create_gaussian. `env="pendulum"`: the on-device Pendulum, whole loop on the GPU (`train`); `env=<object>` with num_envs, obs_dim, act_dim,
-    reset and step on numpy arrays: a host env stepped through crl_policy_act_gaussian / crl_rollout_store_gaussian (`train_host_gaussian`).
+    reset and step on numpy arrays: a host env stepped through crl_policy_act_gaussian / crl_rollout_store_gaussian (`train_host_gaussian`); an object
+    that also declares `on_device = True` (LibraryEnv("pendulum", n), a torch-ROCm simulator) follows the device-env protocol with float actions and is
+    stepped by `train_external` through crl_rollout_act_device_gaussian / crl_rollout_record_device_gaussian, with nothing on the host inside the rollout.
     `gaussian`: GaussianOptions (log-std bounds and initial value). `shape`: hidden, gae_mode, stale_obs, shuffle_mode. Evaluation and diagnostics
     records are not available: crl_ppo_evaluate / crl_ppo_diagnose are not built for Gaussian handles. An unknown env name is a ValueError before
     anything is created."""
@@ -546,6 +567,8 @@ def ppo_continuous(config: PPOConfig = None, *, env="pendulum", gaussian=None, d
     try:
         if isinstance(env, str):
             train(agent, episode_records=episode_records)
+        elif getattr(env, "on_device", False):
+            train_external(agent, env, episode_records=episode_records)
         else:
             train_host_gaussian(agent, env)
         return agent.get_params()

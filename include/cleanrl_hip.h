@@ -341,9 +341,10 @@ int32_t crl_ppo_update(crl_ppo* h, crl_ppo_stats* stats);
  * the mean of H over the minibatch (no division by the head width). CRL_ENV_PENDULUM: state (θ, θ̇), reset θ = 2π·u_x − π, θ̇ = 2·u_y − 1 with
  * u = (word >> 8)·2^-24 of ONE block of the reset stream; g = 10, m = l = 1, dt = 0.05, torque clipped to ±2, θ̇ to ±8, θ held in [−π, π), reward = −(θ² +
  * 0.1·θ̇² + 0.001·u²) of the state before the step, done after 200 steps; returns are signed (return_max as for MountainCar).
- * NOT BUILT for Gaussian handles (each returns an error that says so): crl_ppo_evaluate, crl_ppo_diagnose, crl_rollout_act_device,
- * crl_rollout_record_device, crl_env_step_device; nor a state-independent log-std vector, act_dim > 8, or the 4 / 2 / 64 headline kernels. The int32
- * entry points (crl_policy_act, crl_logprob_actions, crl_rollout_store, crl_env_step) are errors on a Gaussian handle, their twins below on a discrete one. */
+ * NOT BUILT for Gaussian handles (each returns an error that says so): crl_ppo_evaluate, crl_ppo_diagnose; nor a state-independent log-std vector,
+ * act_dim > 8, or the 4 / 2 / 64 headline kernels. The int32 entry points (crl_policy_act, crl_logprob_actions, crl_rollout_store, crl_env_step,
+ * crl_rollout_act_device, crl_rollout_record_device, crl_env_step_device) are errors on a Gaussian handle — "not built for Gaussian handles", naming
+ * the twin to use —, their twins below on a discrete one. */
 typedef struct crl_ppo_gauss_options { float log_std_min, log_std_max, init_log_std; } crl_ppo_gauss_options;   /* defaults (opt = NULL): −5, 2, 0 */
 int32_t crl_ppo_create_gaussian(const crl_ppo_config* cfg, const crl_ppo_gauss_options* opt, int32_t device, crl_ppo** out);
 /* crl_make_actor_critic(obs_dim, 2·act_dim, hidden, seed, …) — the same draws, the same 0.01-gain head — with the biases of head rows act_dim … 2·act_dim − 1
@@ -356,6 +357,27 @@ int32_t crl_logprob_actions_gaussian(crl_ppo* h, const float* obs, const float* 
 int32_t crl_rollout_store_gaussian(crl_ppo* h, int32_t step, const float* obs, const float* action, const float* logprob, const float* reward,
                                    const uint8_t* terminal, const float* value);   /* action (act_dim, num_envs) */
 int32_t crl_env_step_gaussian(crl_ppo* h, const float* action, uint64_t gstep, float* next_obs, float* reward, uint8_t* done);   /* CRL_ENV_PENDULUM; action[num_envs] */
+/* The device-resident protocol on a Gaussian handle (csrc/extenv.hip): the float-action twins of crl_rollout_act_device, crl_rollout_record_device and
+ * crl_env_step_device — device pointers only, nothing staged, no host wait, the peer_stream rule and the errors (NULL pointers, step out of range,
+ * parameters never set; the argument is named) of the calls they mirror. crl_ppo_update closes the rollout as for a discrete handle.
+ * crl_rollout_act_device_gaussian, ONE launch (ext_act_kernel<H, ExtHeadGauss>: the frame and the bf16x3 / tanh_fast forward of crl_rollout_act_device,
+ * obs_dim <= 64, act_dim 1 … 8, hidden 64 / 128 / 256): for env e the actor's head z = (μ, s) and the critic's value of obs_d (obs_dim, num_envs); for
+ * i = 0 … act_dim − 1, in Float32 with contraction off and exactly the expressions above,
+ *   log_std_i = log_std_min + (0.5f·(log_std_max − log_std_min))·(tanhf(s_i) + 1);  σ_i = expf(log_std_i);  a_i = μ_i + σ_i·ξ_i
+ *   logπ = Σ_i ((−0.5f·ξ_i² − log_std_i) − 0.5·log 2π), the terms added in index order from 0.0f
+ * with ξ_i the ON-DEVICE ROLLOUT'S draw for that env and step: the Float64 Box–Muller of csrc/normal_bm.hpp on all four words of Philox block (seed,
+ * env_id_offset + e, iteration·num_steps + step, 0x20 + i), rounded to Float32. Given the same head outputs, action, logπ and ξ are the bits of the
+ * rollout routes. a goes UNCLIPPED to action_d (act_dim, num_envs) — column-major, i.e. a contiguous (num_envs, act_dim) torch tensor, the obs
+ * convention — and, with obs, logπ, value and terminal = done_d[e], into slot `step` of the resident buffer (CRL_F_ACTION_F). Nothing at or past
+ * num_envs is read or written. step = 0 starts a rollout: the episode statistics and the ring count are cleared on the stream first.
+ * crl_rollout_record_device_gaussian: crl_rollout_record_device (the kernel never looks at the head). Returns are signed, as for every external env.
+ * crl_env_step_device_gaussian: crl_env_step_gaussian without the staging, CRL_ENV_PENDULUM — action_d / reward_d / done_d [num_envs] and next_obs_d
+ * (obs_dim, num_envs; may be NULL: CRL_F_CUR_OBS holds it) are device memory; one handle's Pendulum as another handle's external env. */
+int32_t crl_rollout_act_device_gaussian(crl_ppo* h, int32_t step, const float* obs_d, const uint8_t* done_d, float* action_d, void* peer_stream);
+int32_t crl_rollout_record_device_gaussian(crl_ppo* h, int32_t step, const float* reward_d, const float* next_obs_d, const uint8_t* next_done_d,
+                                           void* peer_stream);
+int32_t crl_env_step_device_gaussian(crl_ppo* h, const float* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d,
+                                     void* peer_stream);
 
 /* how many iterations had their update phase re-run with the exact value-loss pass under data parallelism: the fused
  * kernels speculate on u = mean(v - R^2) <= 0 (ppo.jl:232-237); with an RCCL communicator a failed speculation restores the

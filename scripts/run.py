@@ -5,6 +5,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ppo --num_envs 4096 --num_steps 128 --total_timesteps 10485760
     python scripts/run.py ppo --env acrobot --hidden 256 --num_envs 256 --num_steps 128      (--env cartpole | mountaincar | acrobot: ppo.jl:82)
     python scripts/run.py ppo_continuous --env pendulum --hidden 64 --num_envs 256 --num_steps 128     (continuous actions: the Gaussian policy, crl_ppo_create_gaussian)
+    python scripts/run.py ppo_continuous --env pendulum --external --num_envs 256 --num_steps 128     (the same env as a device-resident external env: crl_rollout_act_device_gaussian / crl_rollout_record_device_gaussian)
     python scripts/run.py ppo --env acrobot --eval_every 10 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": a greedy held-out score every 10 updates)
     python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
@@ -55,7 +56,12 @@ def main():
         crl.ppo(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "ppo_continuous":
         kw = take((("--env", str), ("--hidden", int)))      # the continuous env (default: the Pendulum) and the width of networks.jl:36
-        crl.ppo_continuous(config_parser.argparse_struct(crl.PPOConfig(), argv), logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
+        external = "--external" in argv                     # the env as a device-resident EXTERNAL env (LibraryEnv): the crl_rollout_*_device_gaussian loop
+        argv = [a for a in argv if a != "--external"]
+        config = config_parser.argparse_struct(crl.PPOConfig(), argv)
+        if external:
+            kw["env"] = crl.LibraryEnv(kw.get("env", "pendulum"), config.num_envs)
+        crl.ppo_continuous(config, logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_a2c_evaluate)
         crl.a2c(config_parser.argparse_struct(crl.A2CConfig(), argv), to_terminal=True, to_tensorboard=False, **kw).close()
