@@ -12,10 +12,10 @@ from .dqn import C51Options, QROptions, DQNAgent, DQNConfig, DQNTargetOptions, P
 from .ddpg import DDPGAgent, DDPGConfig, ddpg, ddpg_evaluate, get_q, make_ddpg_nn, polyak_update
 from .td3 import TD3Agent, TD3Config, make_td3_nn, td3
 from .sac import SACAgent, SACConfig, make_sac_nn, sac
-from .ppo import Agent, LibraryEnv, Policy, PPOConfig, diagnose, evaluate, gae, get_action, logprob_actions, ppo, ppo_continuous, train, train_external
+from .ppo import Agent, LibraryEnv, NormalizedEnv, Policy, PPOConfig, diagnose, evaluate, gae, get_action, logprob_actions, ppo, ppo_continuous, train, train_external
 
 __all__ = ["_lib", "config_parser", "CrlError", "GaussianOptions", "Handle", "comm_unique_id", "device_count", "make_logger", "make_actor_critic", "Agent",
-           "Policy", "PPOConfig", "gae", "get_action", "logprob_actions", "ppo", "ppo_continuous", "train", "train_external", "LibraryEnv", "evaluate", "diagnose", "A2CAgent", "A2CConfig", "a2c",
+           "Policy", "PPOConfig", "gae", "get_action", "logprob_actions", "ppo", "ppo_continuous", "train", "train_external", "LibraryEnv", "NormalizedEnv", "evaluate", "diagnose", "A2CAgent", "A2CConfig", "a2c",
            "discounted_future_rewards", "DQNAgent", "DQNConfig", "PEROptions", "DQNTargetOptions", "C51Options", "QROptions", "make_nn_c51", "make_nn_dueling", "NoisyOptions", "make_nn_noisy", "noisy_sigma", "dqn", "linear_schedule", "make_nn",
            "DDPGAgent", "DDPGConfig", "ddpg", "ddpg_evaluate", "get_q", "make_ddpg_nn", "polyak_update", "dqn_evaluate", "a2c_evaluate",
            "TD3Agent", "TD3Config", "td3", "make_td3_nn",

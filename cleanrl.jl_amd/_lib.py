@@ -114,6 +114,8 @@ EXPORTS = [
     "crl_ppo_create_gaussian", "crl_make_actor_critic_gaussian", "crl_policy_act_gaussian", "crl_logprob_actions_gaussian",
     "crl_rollout_store_gaussian", "crl_env_step_gaussian", "crl_ppo_rollout_route",
     "crl_rollout_act_device_gaussian", "crl_rollout_record_device_gaussian", "crl_env_step_device_gaussian",
+    "crl_norm_create", "crl_norm_destroy", "crl_norm_reset_device", "crl_norm_step_device", "crl_norm_read", "crl_norm_write",
+    "crl_norm_episode_stats_read",
 ]
 ROLLOUT_ROUTES = ("headline", "stepwise", "persist", "pc", "rs_actor")   # enum crl_rollout_route, in order
 
@@ -256,6 +258,15 @@ class GaussianOptions(C.Structure):
 
     def __init__(self, log_std_min=-5.0, log_std_max=2.0, init_log_std=0.0):
         super().__init__(log_std_min, log_std_max, init_log_std)
+
+
+class NormOptions(C.Structure):
+    """crl_norm_options (48 bytes): what a running normaliser (crl_norm, csrc/norm.hip) is built with."""
+    _fields_ = [("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("norm_obs", C.c_int32), ("norm_reward", C.c_int32),
+                ("gamma", C.c_double), ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double)]
+
+    def __init__(self, num_envs, obs_dim, norm_obs=True, norm_reward=True, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0):
+        super().__init__(int(num_envs), int(obs_dim), int(bool(norm_obs)), int(bool(norm_reward)), gamma, epsilon, clip_obs, clip_reward)
 
 
 # crl_field
@@ -433,6 +444,13 @@ def load():
     L.crl_rollout_record_device_gaussian.argtypes = L.crl_rollout_record_device.argtypes
     L.crl_env_step_device_gaussian.argtypes = L.crl_env_step_device.argtypes
     L.crl_ppo_update.argtypes = [vp, C.POINTER(CrlStats)]
+    L.crl_norm_create.argtypes = [C.POINTER(NormOptions), C.c_int32, C.POINTER(vp)]
+    L.crl_norm_destroy.argtypes = [vp]
+    L.crl_norm_reset_device.argtypes = [vp, vp, vp, C.c_int32, vp]
+    L.crl_norm_step_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
+    L.crl_norm_read.argtypes = [vp, dp, C.c_size_t]
+    L.crl_norm_write.argtypes = [vp, dp, C.c_size_t]
+    L.crl_norm_episode_stats_read.argtypes = [vp, C.POINTER(CrlEpisodeStats), C.c_int32]
     L.crl_product_probe.argtypes = [C.c_int32, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp]
     for name in EXPORTS:
         if name not in ("crl_version", "crl_last_error"):
@@ -527,6 +545,55 @@ class DeviceBuffer:
         if self._p.value:
             self._R.hipFree(self._p)
             self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Normalizer:
+    """Owns one crl_norm: running observation / reward statistics (Float64) for `num_envs` device-resident envs. The two _device calls only enqueue
+    on `stream` (the hipStream_t, as an int, the env enqueues on; None = the null stream); state(), load_state() and episode_stats() synchronise it."""
+
+    def __init__(self, opt: NormOptions, device=0):
+        self.opt, self.device = opt, device
+        self._n = C.c_void_p()
+        check(load().crl_norm_create(C.byref(opt), device, C.byref(self._n)))
+
+    def reset_device(self, obs_in, obs_out, update=True, stream=None):
+        """crl_norm_reset_device: zero the per-env books, merge obs_in when `update`, write the normalised observations."""
+        i, o = devptr(obs_in, "reset_device: obs_in"), devptr(obs_out, "reset_device: obs_out")
+        check(load().crl_norm_reset_device(self._n, i, o, int(bool(update)), devptr(stream, "stream", optional=True)))
+
+    def step_device(self, obs_in, reward_in, done, obs_out, reward_out, update=True, stream=None):
+        """crl_norm_step_device: one env step — statistics (when `update`), normalised observations and rewards, raw episode books."""
+        i, r, d = devptr(obs_in, "step_device: obs_in"), devptr(reward_in, "step_device: reward_in"), devptr(done, "step_device: done")
+        o, ro = devptr(obs_out, "step_device: obs_out"), devptr(reward_out, "step_device: reward_out")
+        check(load().crl_norm_step_device(self._n, i, r, d, o, ro, int(bool(update)), devptr(stream, "stream", optional=True)))
+
+    def state(self):
+        """crl_norm_read: count_o, mean[D], var[D], count_r, mean_r, var_r as one Float64 vector."""
+        out = np.zeros(2 * self.opt.obs_dim + 4, np.float64)
+        check(load().crl_norm_read(self._n, _ptr(out, C.c_double), out.size))
+        return out
+
+    def load_state(self, state):
+        """crl_norm_write: restore (or share) the vector state() returns."""
+        a = np.ascontiguousarray(state, np.float64).ravel()
+        check(load().crl_norm_write(self._n, _ptr(a, C.c_double), a.size))
+
+    def episode_stats(self, clear=True):
+        """crl_norm_episode_stats_read: the RAW episodes that ended since the last clear."""
+        st = CrlEpisodeStats()
+        check(load().crl_norm_episode_stats_read(self._n, C.byref(st), int(bool(clear))))
+        return {"episodes": st.episodes, "return_sum": st.return_sum, "length_sum": st.length_sum, "return_max": st.return_max}
+
+    def close(self):
+        if getattr(self, "_n", None) is not None and self._n.value:
+            load().crl_norm_destroy(self._n)
+            self._n = C.c_void_p()
 
     def __del__(self):
         try:

@@ -321,6 +321,8 @@ def train(agent: Agent, num_updates=None, log_every=1, episode_records=0, eval_e
 #   stream (optional)                 the hipStream_t (int) the env enqueues its work on; passed as peer_stream, so neither side waits on the host
 #   action (optional)                 pointer-like [num_envs] Int32 the env wants the actions written into (a torch env hands over its own tensor and
 #                                     gets it back in step); without it the loop allocates a DeviceBuffer
+#   episode_stats() (optional)        the RAW episodes that ended since the last call, as Handle.episode_stats() returns them (read and clear): an env
+#                                     that transforms the rewards it hands over (NormalizedEnv) reports its true returns through it
 # A continuous-action device env declares `act_dim` INSTEAD of `n_act` (and `on_device = True`, which tells ppo_continuous it is not a host env): it is
 # driven by a Gaussian agent through the `_gaussian` twins of the three calls, and `action` is (act_dim, num_envs) Float32 — a contiguous
 # (num_envs, act_dim) torch tensor — holding the unclipped actions.
@@ -386,13 +388,76 @@ class LibraryEnv:
             b.close()
 
 
+class NormalizedEnv:
+    """CleanRL's NormalizeObservation -> clip -> NormalizeReward(gamma) -> clip around any device env, on the device (crl_norm, csrc/norm.hip): running
+    Float64 statistics over all envs, updated and applied on the env's stream with nothing on the host inside the rollout. Implements the device-env
+    protocol itself — num_envs, obs_dim, n_act OR act_dim, on_device and action are the inner env's — and owns the normalised obs / reward buffers;
+    done is the inner env's. `stream` defaults to the inner env's; an inner env without one needs the stream it enqueues on passed here (TypeError
+    otherwise). `training = False` freezes the statistics (evaluation). episode_stats() reports RAW returns (read and clear); state() / load_state()
+    carry the statistics; close() closes the inner env too. The crl_norm (and with it the check of the options) and the two buffers are made at
+    the first call that needs them, so building the wrapper touches no device."""
+
+    def __init__(self, env, norm_obs=True, norm_reward=True, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, stream=None, device=0):
+        for name in ("num_envs", "obs_dim", "reset", "step"):
+            if not hasattr(env, name):
+                raise TypeError(f"NormalizedEnv: env={type(env).__name__} has no `{name}` (the device-env protocol)")
+        if stream is None:
+            stream = getattr(env, "stream", None)
+        if stream is None:
+            raise TypeError(f"NormalizedEnv: env={type(env).__name__} has no `stream`: pass stream=<the hipStream_t it enqueues on>")
+        self.env, self.stream, self.training = env, stream, True
+        self.num_envs, self.obs_dim = int(env.num_envs), int(env.obs_dim)
+        for name in ("n_act", "act_dim", "on_device", "action"):
+            if hasattr(env, name):
+                setattr(self, name, getattr(env, name))
+        self.options, self.device = L.NormOptions(self.num_envs, self.obs_dim, norm_obs, norm_reward, gamma, epsilon, clip_obs, clip_reward), device
+        self._norm = self.obs = self.reward = None
+
+    @property
+    def norm(self):
+        if self._norm is None:
+            self._norm = L.Normalizer(self.options, self.device)
+            self.obs = L.DeviceBuffer(4 * self.num_envs * self.obs_dim, self.device)
+            self.reward = L.DeviceBuffer(4 * self.num_envs, self.device)
+        return self._norm
+
+    def reset(self):
+        obs, done = self.env.reset()
+        self.norm.reset_device(obs, self.obs, update=self.training, stream=self.stream)
+        return self.obs, done
+
+    def step(self, action):
+        reward, obs, done = self.env.step(action)
+        self.norm.step_device(obs, reward, done, self.obs, self.reward, update=self.training, stream=self.stream)
+        return self.reward, self.obs, done
+
+    def state(self):
+        return self.norm.state()
+
+    def load_state(self, state):
+        self.norm.load_state(state)
+
+    def episode_stats(self, clear=True):
+        return self.norm.episode_stats(clear)
+
+    def close(self):
+        if self._norm is not None:
+            self._norm.close()
+            self.obs.close(); self.reward.close()
+            self._norm = None
+        if callable(getattr(self.env, "close", None)):
+            self.env.close()
+
+
 def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_records=0, eval_every=0, diag_every=0):
     """The `for update in 1:num_updates` loop of ppo.jl:117-253 with the env OUTSIDE the library but on the same GPU (the device-env protocol above):
     reset once; per step crl_rollout_act_device -> env.step -> crl_rollout_record_device; per update crl_ppo_update. Emits the records of `train`:
     "Episode Statistics" (one aggregate per rollout, or one per episode with episode_records=N), "Training Statistics", and "Policy Diagnostics" every
     diag_every-th update. eval_every is refused: crl_ppo_evaluate has no external env to run. A Gaussian agent takes an env that declares act_dim: the
     action buffer is (act_dim, num_envs) Float32, the calls are crl_rollout_act_device_gaussian / crl_rollout_record_device_gaussian, the records are
-    the same; diag_every is refused for it as well (crl_ppo_diagnose is not built for Gaussian handles)."""
+    the same; diag_every is refused for it as well (crl_ppo_diagnose is not built for Gaussian handles). An env with a callable `episode_stats`
+    (NormalizedEnv) has transformed the rewards the handle records: its "Episode Statistics" record is built from env.episode_stats() — raw returns —
+    and is the one aggregate per rollout whatever episode_records says, because the handle's ring would hold normalised returns."""
     if eval_every:
         raise ValueError("train_external: eval_every is not available — crl_ppo_evaluate runs the library's own envs and has none for an external env")
     gaussian = agent.action == "gaussian"
@@ -412,6 +477,9 @@ def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_rec
         num_updates = max(1, cfg.total_timesteps // batch_size)  # ppo.jl:91
     h = agent.handle
     act_device, record_device = (h.act_device_gaussian, h.record_device_gaussian) if gaussian else (h.act_device, h.record_device)
+    env_stats = getattr(env, "episode_stats", None)
+    if callable(env_stats):
+        episode_records = 0
     if episode_records:
         h.episode_ring_enable(int(episode_records))
     peer = getattr(env, "stream", None) or None
@@ -428,7 +496,7 @@ def train_external(agent: Agent, env, num_updates=None, log_every=1, episode_rec
             reward, obs, done = env.step(action)
             record_device(step, reward, obs, done, peer_stream=peer)
         # the episode records of this rollout are read before the next rollout's first step clears them; the reads are this loop's host waits
-        ep = h.episode_stats()
+        ep = env_stats() if callable(env_stats) else h.episode_stats()
         records = h.episode_records()[0] if episode_records else []
         stats = h.update(want_stats=bool(log_every))                               # ppo.jl:168-253
         global_step = base + batch_size

@@ -379,6 +379,41 @@ int32_t crl_rollout_record_device_gaussian(crl_ppo* h, int32_t step, const float
 int32_t crl_env_step_device_gaussian(crl_ppo* h, const float* action_d, uint64_t gstep, float* next_obs_d, float* reward_d, uint8_t* done_d,
                                      void* peer_stream);
 
+/* ---- Running normalisation (csrc/norm.hip): CleanRL's NormalizeObservation -> clip -> NormalizeReward(gamma) -> clip for a DEVICE-RESIDENT env, as an
+ * object of its own: it sits between any device env and any agent behind the device-env protocol; no handle, rollout kernel or record layout knows it.
+ * All state is Float64. One crl_norm serves num_envs envs (N) of obs_dim (D) observations, (obs_dim, num_envs) column-major.
+ *   observation statistics  count = 1e-4, mean[D] = 0, var[D] = 1          return statistics  count = 1e-4, mean = 0, var = 1
+ *   per env                 acc[N] = 0 (discounted return), ep_ret[N] = 0, ep_len[N] = 0 (raw), and a raw aggregate of the crl_episode_stats shape
+ * merge(stat, batch) is gymnasium's update_from_moments with n_b = N, μ_b the batch mean and σ²_b the POPULATION variance:
+ *   δ = μ_b − mean;  tot = count + n_b;  mean += δ·n_b/tot;  M2 = var·count + σ²_b·n_b + δ²·count·n_b/tot;  var = M2/tot;  count = tot
+ * reset: acc, ep_ret, ep_len <- 0; if update, the N observations are merged into the observation statistics per dimension; then
+ *   obs_out[d,e] = float(clamp((double(obs_in[d,e]) − mean[d]) / sqrt(var[d] + epsilon), ±clip_obs))
+ * step, in this order: 1. if update, merge obs_in; obs_out as above with the statistics AFTER the merge. 2. acc[e] = acc[e]·gamma + double(reward_in[e]);
+ * if update, merge the N values of acc into the return statistics. 3. reward_out[e] = float(clamp(double(reward_in[e]) / sqrt(var_ret + epsilon),
+ * ±clip_reward)): the mean is not subtracted, as in gym. 4. ep_ret[e] += reward_in[e], ep_len[e] += 1; where done[e] the episode is added to the
+ * aggregate (envs in index order), then ep_ret[e] = ep_len[e] = 0 and acc[e] = 0.
+ * norm_obs = 0 copies observations through and leaves the observation statistics alone; norm_reward = 0 copies rewards through and leaves acc and the
+ * return statistics alone; step 4 runs either way. Defaults of the Python layer: gamma 0.99, epsilon 1e-8, both clips 10.
+ * Batch moments are formed per tile of 256 envs (Float64 sums, squares about the TILE mean) and the tiles are merged in index order with the formula
+ * above: a reordering of the whole-batch Float64 sums — not bit-equal to numpy, bit-identical from call to call. The divisions by tot and by sqrt(var + epsilon) are
+ * multiplications by their Float64 reciprocals. The aggregate is kept per tile and the tiles are added in index order when it is read; return_max is the
+ * true signed maximum, 0 when no episode ended.
+ * crl_norm_create checks, before the device is touched and naming the field: 1 <= num_envs <= 2^20, 1 <= obs_dim <= 64, gamma in [0, 1], epsilon > 0,
+ * clip_obs > 0, clip_reward > 0. `stream` is the hipStream_t the env enqueues on: the two _device calls only enqueue on it (one launch for
+ * num_envs <= 256 or update = 0, two otherwise) and never wait on the host; obs_out_d may be obs_in_d. crl_norm_read, crl_norm_write and
+ * crl_norm_episode_stats_read synchronise the stream of the last _device call. */
+typedef struct crl_norm_options { int32_t num_envs, obs_dim, norm_obs, norm_reward; double gamma, epsilon, clip_obs, clip_reward; } crl_norm_options;  /* crl_norm_options: 48 bytes */
+typedef struct crl_norm crl_norm;
+int32_t crl_norm_create(const crl_norm_options* opt, int32_t device, crl_norm** out);
+int32_t crl_norm_destroy(crl_norm* n);
+int32_t crl_norm_reset_device(crl_norm* n, const float* obs_in_d, float* obs_out_d, int32_t update, void* stream);
+int32_t crl_norm_step_device(crl_norm* n, const float* obs_in_d, const float* reward_in_d, const uint8_t* done_d, float* obs_out_d, float* reward_out_d,
+                             int32_t update, void* stream);
+/* count_o, mean[D], var[D], count_r, mean_r, var_r: 2·obs_dim + 4 doubles; write restores or shares statistics */
+int32_t crl_norm_read(crl_norm* n, double* out, size_t count);
+int32_t crl_norm_write(crl_norm* n, const double* in, size_t count);
+int32_t crl_norm_episode_stats_read(crl_norm* n, crl_episode_stats* out, int32_t clear);   /* raw returns since the last clear */
+
 /* how many iterations had their update phase re-run with the exact value-loss pass under data parallelism: the fused
  * kernels speculate on u = mean(v - R^2) <= 0 (ppo.jl:232-237); with an RCCL communicator a failed speculation restores the
  * parameters / Adam state of the iteration's start and repeats its optimiser steps exactly (two more small all-reduces each) */

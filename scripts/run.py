@@ -6,6 +6,7 @@ command line option (ConfigParser.argparse_struct), records go to the "CleanRL" 
     python scripts/run.py ppo --env acrobot --hidden 256 --num_envs 256 --num_steps 128      (--env cartpole | mountaincar | acrobot: ppo.jl:82)
     python scripts/run.py ppo_continuous --env pendulum --hidden 64 --num_envs 256 --num_steps 128     (continuous actions: the Gaussian policy, crl_ppo_create_gaussian)
     python scripts/run.py ppo_continuous --env pendulum --external --num_envs 256 --num_steps 128     (the same env as a device-resident external env: crl_rollout_act_device_gaussian / crl_rollout_record_device_gaussian)
+    python scripts/run.py ppo_continuous --env pendulum --external --normalize --num_envs 256 --num_steps 128     (… behind crl.NormalizedEnv: running observation / reward normalisation on the device)
     python scripts/run.py ppo --env acrobot --eval_every 10 --eval_envs 256 --eval_episodes 1   ("Evaluation Statistics": a greedy held-out score every 10 updates)
     python scripts/run.py ppo --env acrobot --diag_every 10   ("Policy Diagnostics": approx-KL, clip fraction, entropy, explained variance every 10 updates)
     python scripts/run.py a2c --total_timesteps 100000
@@ -57,10 +58,15 @@ def main():
     elif algo == "ppo_continuous":
         kw = take((("--env", str), ("--hidden", int)))      # the continuous env (default: the Pendulum) and the width of networks.jl:36
         external = "--external" in argv                     # the env as a device-resident EXTERNAL env (LibraryEnv): the crl_rollout_*_device_gaussian loop
-        argv = [a for a in argv if a != "--external"]
+        normalize = "--normalize" in argv                   # with --external: running obs / reward normalisation around it (crl.NormalizedEnv); default off
+        argv = [a for a in argv if a not in ("--external", "--normalize")]
+        if normalize and not external:
+            sys.exit("--normalize wraps a device-resident env: pass --external as well")
         config = config_parser.argparse_struct(crl.PPOConfig(), argv)
         if external:
             kw["env"] = crl.LibraryEnv(kw.get("env", "pendulum"), config.num_envs)
+            if normalize:
+                kw["env"] = crl.NormalizedEnv(kw["env"], gamma=config.gamma)
         crl.ppo_continuous(config, logger_kw=dict(to_terminal=True, to_tensorboard=False), **kw)
     elif algo == "a2c":
         kw = take((("--eval_every", int), ("--eval_envs", int), ("--eval_episodes", int)))      # the evaluation cadence (crl_a2c_evaluate)
